@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- robot-steps/sec of the img_env step() path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it sets the world up, spins the clocks up, warms up, times ONE pass of exactly
+K steps (no HIP event inside it) and prints the JSON line (`value`, `ms_per_step` = that pass's milliseconds per step).
+`--dump-outputs DIR` then writes what the last timed step handed its caller (every `imgenv_out` array of rank 0, as float32 /
+float64 .npy files; the large per-robot arrays as a fixed, seeded sample of robots, `sample_robots.npy`).  `--full` adds
+everything else the line used to carry: the median of 5 passes with the dominant kernel under HIP events, the per-kernel
+breakdown and roofline, the uninstrumented and with-reset passes, the CPU baseline, the secondary policies and
+configurations (`episode_policy`, `spec_policy`, `full_rewrite`, `multi_world`, `vec_env`, `shipped`) and, on cfg-4, the
+comparison of the crowd's first step with the oracle.
 
 N > 1 works both ways: launched by `python -m torch.distributed.run --nproc-per-node N ...` (RANK / WORLD_SIZE in the
 environment), or plainly as above -- the parent process then starts one child per GPU itself (it never touches a GPU) and
@@ -254,6 +263,34 @@ def first_step_ped_velocities(cfg_name, peds):
     return v
 
 
+DUMP_LIMIT = 60 << 20        # bytes of the whole dump at most
+DUMP_ROBOTS = 512            # robots of the fixed sample the large per-robot arrays are cut to (fewer where they would not fit)
+DUMP_WHOLE_BYTES = 4 << 20   # an array at most this large (after the dtype widening) is written whole
+
+
+def dump_outputs(world, out_dir):
+    """`--dump-outputs DIR`: every array imgenv_out hands the caller after the last timed step, as DIR/<name>.npy -- float64
+    stays float64, int32 widens to float64, everything else (u8 / i8 / f16 / f32) to float32, all exactly.  Per-robot arrays
+    larger than DUMP_WHOLE_BYTES keep the rows of a fixed, seeded sample of robots (sorted; DIR/sample_robots.npy), so that the
+    dump stays under DUMP_LIMIT (~30 MB at cfg-3) and two builds are compared on the same robots."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = world.n_local
+    arrays = {}
+    for name, a in sorted(world.snapshot().items()):
+        arrays[name] = a.astype(np.float64 if a.dtype in (np.float64, np.int32, np.int64, np.uint32) else np.float32)
+    big = [k for k, a in arrays.items() if a.nbytes > DUMP_WHOLE_BYTES and a.ndim >= 1 and a.shape[0] == n]
+    whole = sum(a.nbytes for k, a in arrays.items() if k not in big)
+    per_robot = sum(arrays[k].nbytes // n for k in big)
+    if big:
+        k_rob = max(1, min(n, DUMP_ROBOTS, (DUMP_LIMIT - whole) // max(per_robot, 1)))
+        sample = np.sort(np.random.default_rng(20240613).permutation(n)[:k_rob])
+        for k in big:
+            arrays[k] = arrays[k][sample]
+        arrays["sample_robots"] = sample.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -265,13 +302,18 @@ def main():
                     "views, 720 beams on 800x800, strong-scaled")
     ap.add_argument("--robots-per-gpu", type=int, default=None, help="diagnostic: robots per GPU instead of the configuration's")
     ap.add_argument("--peds", type=int, default=None, help="diagnostic: pedestrians instead of the configuration's")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-episode", action="store_true", help="skip the secondary policies (episode_policy, spec_policy) and full_rewrite")
-    ap.add_argument("--no-multi-world", action="store_true", help="skip the secondary env_num-style measurements")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline as well: per-kernel breakdown, "
+                    "roofline, CPU baseline, the secondary policies and configurations, 5 passes with the dominant kernel under HIP events")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0's "
+                    "imgenv_out arrays) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-episode", action="store_true", help="(--full) skip the secondary policies (episode_policy, spec_policy) and full_rewrite")
+    ap.add_argument("--no-multi-world", action="store_true", help="(--full) skip the secondary env_num-style measurements")
     ap.add_argument("--spinup", type=int, default=2000, help="untimed steps before the warm-up (clock ramp)")
-    ap.add_argument("--timing-mode", type=int, default=2, help="diagnostic: 0 = no HIP events in the timed pass")
-    ap.add_argument("--repeat", type=int, default=0, help="diagnostic: extra timed passes, printed to stderr")
-    ap.add_argument("--passes", type=int, default=5, help="timed passes of the SAME --steps; value = the median pass")
+    ap.add_argument("--timing-mode", type=int, default=2, help="(--full) diagnostic: 0 = no HIP events in the timed passes")
+    ap.add_argument("--repeat", type=int, default=0, help="(--full) diagnostic: extra timed passes, printed to stderr")
+    ap.add_argument("--passes", type=int, default=None, help="timed passes of the SAME --steps; value = the median pass "
+                    "(default: 1, with --full 5)")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) and use the "
                     "step_begin / all_gather / step_end path even with one rank (exercises the multi-GPU code on one GPU)")
     ap.add_argument("--cpu-worker", type=int, default=None, help=argparse.SUPPRESS)  # internal: one process of the all-core CPU baseline
@@ -282,6 +324,8 @@ def main():
     wl = WORKLOADS[args.config]
     if args.peds is None:
         args.peds = wl["peds"]
+    if args.passes is None:
+        args.passes = 5 if args.full else 1
     if args.cpu_worker is not None:
         return cpu_worker(args)
     if "RANK" not in os.environ and (args.gpus > 1 or os.environ.get("IMGENV_BENCH_FORCE_LAUNCHER")):
@@ -319,7 +363,7 @@ def main():
     # The CPU baseline runs FIRST, before this process makes its first GPU call: its all-core leg starts worker processes,
     # and nothing may be started from a process that holds a GPU context on this pool.
     cpu_base, oracle_first_v = None, None
-    if world_size == 1 and not args.no_cpu_baseline and not args.force_dist:
+    if args.full and world_size == 1 and not args.no_cpu_baseline and not args.force_dist:
         try:
             cpu_base = cpu_baseline(args.config, dict(params), grid, layouts[0], P)
         except Exception as e:
@@ -469,51 +513,55 @@ def main():
         world.timing(0)
         return {k: (float(np.median(v)) if v else 0.0) for k, v in samples.items()}
 
-    per_kernel_us = kernel_breakdown()
-    # every rank's kernel times (and the exchange's duration) travel with the line: a scaling curve then explains itself
-    per_rank_kernel_us = None
-    if use_dist:
-        gathered = [None] * world_size
-        dist.all_gather_object(gathered, {k: round(v, 2) for k, v in per_kernel_us.items() if v})
-        per_rank_kernel_us = gathered
-    # dominant = the per-robot kernel with the longest launch.  k_orca is left out: it is 200 single-wave workgroups of
-    # serial LP code that idle along on a side stream underneath k_view (latency, not work) and moves no per-robot bytes
-    # ... and so are the move and the rasters (k_integrate, k_raster, k_move_raster: a wavefront's chain of dependent round trips over 128
-    # bytes of state per robot; SURVEY 8(d) gives them no bytes to price) as long as a kernel that moves the observation's bytes ran:
-    # on cfg-2 k_move_raster and k_view<..., 8> are within a microsecond of each other, and which one is "longest" is a coin toss
-    latency_kernels = ("k_orca", "rccl_all_gather", "k_integrate", "k_raster", "k_move_raster", "k_remote")
-    longest_kernel = max((k for k in per_kernel_us if k not in ("k_orca", "rccl_all_gather")), key=per_kernel_us.get)
-    priced = [k for k in per_kernel_us if k not in latency_kernels and per_kernel_us[k] > 0]
-    dominant = max(priced, key=per_kernel_us.get) if priced else longest_kernel
-    dom_id = list(per_kernel_us).index(dominant)
+    # (--full only: a plain run times its pass without any HIP event and has no roofline to price)
+    per_kernel_us, per_rank_kernel_us, dominant, longest_kernel, dom_id = None, None, None, None, -1
+    if args.full:
+        per_kernel_us = kernel_breakdown()
+        # every rank's kernel times (and the exchange's duration) travel with the line: a scaling curve then explains itself
+        if use_dist:
+            gathered = [None] * world_size
+            dist.all_gather_object(gathered, {k: round(v, 2) for k, v in per_kernel_us.items() if v})
+            per_rank_kernel_us = gathered
+        # dominant = the per-robot kernel with the longest launch.  k_orca is left out: it is 200 single-wave workgroups of
+        # serial LP code that idle along on a side stream underneath k_view (latency, not work) and moves no per-robot bytes
+        # ... and so are the move and the rasters (k_integrate, k_raster, k_move_raster: a wavefront's chain of dependent round trips over 128
+        # bytes of state per robot; SURVEY 8(d) gives them no bytes to price) as long as a kernel that moves the observation's bytes ran:
+        # on cfg-2 k_move_raster and k_view<..., 8> are within a microsecond of each other, and which one is "longest" is a coin toss
+        latency_kernels = ("k_orca", "rccl_all_gather", "k_integrate", "k_raster", "k_move_raster", "k_remote")
+        longest_kernel = max((k for k in per_kernel_us if k not in ("k_orca", "rccl_all_gather")), key=per_kernel_us.get)
+        priced = [k for k in per_kernel_us if k not in latency_kernels and per_kernel_us[k] > 0]
+        dominant = max(priced, key=per_kernel_us.get) if priced else longest_kernel
+        dom_id = list(per_kernel_us).index(dominant)
+    timing_mode = args.timing_mode if args.full else 0
     # untimed spin-up: the first ~second of sustained work after start-up runs at lower clocks than steady state
     if args.spinup > 0:
         run("active", args.spinup, 0)
-    # pass 2: THE timed region; HIP events only around the dominant kernel
+    # pass 2: THE timed region; with --full HIP events only around the dominant kernel, none in a plain run
     # Several passes of exactly --steps steps each, every one bracketed by barrier + synchronize; the MEDIAN pass is the line's
     # value (boxes of the pool alternate between two step times from process to process and pass to pass, and the driver's 20-step
     # region is 2.5 ms long), min / max are reported beside it
     passes = []
     for q in range(max(1, args.passes)):
-        d_q, tm_q, fr_q = run("active", args.steps, args.warmup if q == 0 else min(args.warmup, 5), timing_mode=args.timing_mode, which=dom_id)
+        d_q, tm_q, fr_q = run("active", args.steps, args.warmup if q == 0 else min(args.warmup, 5), timing_mode=timing_mode, which=dom_id)
         passes.append((d_q, tm_q, fr_q, state["resets_timed"]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(world, args.dump_outputs)
     order = sorted(range(len(passes)), key=lambda q: passes[q][0])
     dt, tm, frozen_active, resets_timed = passes[order[len(order) // 2]]
-    dom_ms, dom_n = tm[dominant]
     value = R_job * args.steps / dt
     pass_values = [R_job * args.steps / p[0] for p in passes]
     # ... and the same passes once more WITHOUT the HIP events around the dominant kernel (every 8th launch carries a pair, and an
     # event operation is a dependency bubble on its stream: the timed region above pays just under 1 % for carrying the roofline's
     # measurement inside it).  Reported beside `value`, never instead of it.
     uninstrumented = None
-    if args.timing_mode != 0 and world_size == 1:
+    if args.full and args.timing_mode != 0 and world_size == 1:
         d0 = sorted(run("active", args.steps, min(args.warmup, 5), timing_mode=0)[0] for _ in range(3))[1]
         uninstrumented = dict(value=R_job * args.steps / d0, ms_per_step=1e3 * d0 / args.steps,
                               what="median of 3 more passes of the same %d steps with no HIP event in the timed region" % args.steps)
     # SURVEY 8(d) wants the auto-reset inside the timed region; a run shorter than an episode (the driver's 20 steps) never meets
     # one, so it is timed separately: the same N steps + ONE full imgenv_reset of the world
     with_reset = None
-    if args.steps <= TIME_MAX:
+    if args.full and args.steps <= TIME_MAX:
         acts_r = make_actions("active")
         state["episode"] = 0
         do_reset()
@@ -536,7 +584,7 @@ def main():
             dtr = float(t.item())
         with_reset = dict(value=R_job * args.steps / dtr, ms_per_step=1e3 * dtr / args.steps,
                           what="%d steps + one full imgenv_reset of the world inside the timed region" % args.steps)
-    for q in range(args.repeat):
+    for q in range(args.repeat if args.full else 0):
         for mode in (0, 2):
             d2, _, _ = run("active", args.steps, args.warmup, timing_mode=mode, which=dom_id)
             d3, _, _ = run("episode", args.steps, args.warmup, timing_mode=mode, which=dom_id)
@@ -544,7 +592,7 @@ def main():
                 print("repeat %d timing mode %d: active %.1f us/step, episode %.1f us/step"
                       % (q, mode, 1e6 * d2 / args.steps, 1e6 * d3 / args.steps), file=sys.stderr)
     episode = None
-    if not args.no_episode:
+    if args.full and not args.no_episode:
         dte, _, frozen_ep = run("episode", args.steps, args.warmup)
         episode = dict(value=R_job * args.steps / dte, frozen_fraction=frozen_ep,
                        what="v~U(0,0.6), w~U(-0.9,0.9) at the configuration's time_max %d: a shared world freezes most robots within a few steps" % TIME_MAX)
@@ -557,7 +605,7 @@ def main():
     # freeze (agent.cpp:358-360), so the episode's time limit is set to the longest T whose frozen robot-steps stay below 9 %
     # (measured on an untimed episode), and every episode ends in a full reset INSIDE the timed region.
     spec_policy = None
-    if not args.no_episode and world_size == 1 and not args.force_dist:
+    if args.full and not args.no_episode and world_size == 1 and not args.force_dist:
         try:
             acts_s = make_actions("spec")
             ctx["time_max"] = 10 ** 9
@@ -596,7 +644,7 @@ def main():
     # The safe boundary: IMGENV_FLAG_FULL_REWRITE hands out copies rewritten in full by every call (the reference's ownership,
     # img_env.cpp:745-749) -- the same passes under it
     full_rewrite = None
-    if not args.no_episode and world_size == 1 and not args.force_dist:
+    if args.full and not args.no_episode and world_size == 1 and not args.force_dist:
         try:
             w_fr = World(dict(params, output_guard="copy"), grid, device=local_rank)
             ctx["world"] = w_fr
@@ -611,7 +659,7 @@ def main():
         ctx["world"] = world
 
     multi_world = None
-    if world_size == 1 and args.config == "cfg3" and not args.no_multi_world and not args.force_dist:
+    if args.full and world_size == 1 and args.config == "cfg3" and not args.no_multi_world and not args.force_dist:
         # secondary: the reference's own env_num idiom -- E independent worlds of R/E robots at
         # 0.125 m in ONE handle, every world with its own obstacle map, crowd and time limit, reset on its own when its
         # time limit runs out (imgenv_reset_worlds); no collective, so N GPUs simply hold N times the worlds
@@ -625,7 +673,7 @@ def main():
             multi_world = {"error": repr(e)}
 
     vec_env = None
-    if world_size == 1 and args.config == "cfg3" and not args.no_multi_world and not args.force_dist:
+    if args.full and world_size == 1 and args.config == "cfg3" and not args.no_multi_world and not args.force_dist:
         # secondary: the trainer's end-to-end loop -- 1024 reference envs of 4 robots behind VecImageEnv (the wrapper stack's
         # outputs, NeverStopWrapper-style resets inside the library), Python call to Python return: with the device-side reset
         # (the value) and with the host in the loop
@@ -642,7 +690,7 @@ def main():
             vec_env = {"error": repr(e)}
 
     shipped = None
-    if world_size == 1 and args.config == "cfg3" and not args.no_multi_world and not args.force_dist:
+    if args.full and world_size == 1 and args.config == "cfg3" and not args.no_multi_world and not args.force_dist:
         # secondary: the geometry of the reference's shipped envs/cfg/test.yaml (BASELINE cfg-1): 400 x 400 cell views shrunk to
         # 48 x 48, 1000 beams, one robot + 4 leg pedestrians + 4 obstacles per env, VecImageEnv end to end with auto-resets
         try:
@@ -652,6 +700,36 @@ def main():
             shipped = {"error": repr(e)}
 
     if rank == 0:
+        build_id = world.lib.imgenv_build_id().decode()
+        out = {
+            "metric": "robot-steps/sec (whole node) at 8192 robots, 48x48 maps, 360 lasers",
+            "value": value, "unit": "robot-steps/s", "n_gpus": world_size, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
+            "scaling": "weak" if replicas else wl["scaling"], "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": (wl["name"] % dict(R=R, RL=RL, N=world_size, P=P, strong="" if world_size == 1 else
+                                                      ": strong scaling, the same world at every GPU count")) +
+                                   ", %dx%d grid @%.3f m, %dx%d sensor_map + 3ch ped_map, %d-beam laser, time_max %d, full reset whenever the "
+                                   "time limit runs out (%d inside the %d timed steps)" % (side, side, res, wl["view"], wl["view"], wl["beams"],
+                                                                                           TIME_MAX, resets_timed, args.steps),
+                       "baseline_config": args.config,
+                       "robots": R_job, "peds": P, "grid": side, "resolution": res, "view": wl["view"], "beams": wl["beams"],
+                       "policy": "active: v=0, w~U(-0.9,0.9): every robot-step runs the full view path (spec_policy: SURVEY 8(d)'s own actions)",
+                       "parallelism": (("%d independent replicas, no exchange" % world_size) if replicas else
+                                       "robot-sharded x%d, RCCL all-gather of robot records (%s)" % (
+                                           world_size, ("ncclAllGather inside imgenv_step, communicator of %d ranks as reported by RCCL" % comm_ranks)
+                                           if native else "torch.distributed between step_begin/step_end"))
+                       if use_dist else "single GPU"},
+            "resets_in_timed_region": resets_timed,
+            "passes": {"n": len(passes), "value_is": "median", "values": pass_values, "min": min(pass_values), "max": max(pass_values)},
+            "actions": "pre-generated in HBM; plain stream-ordered imgenv_step (IMGENV_STEP_ACTIONS_READY is without effect since round 6)",
+            "frozen_fraction": frozen_active,
+            "build_id": build_id,
+            "launches_per_step": launches_per_step,
+            "layer_mode": layer_mode,
+            "full": bool(args.full),
+        }
+    if rank == 0 and args.full:
+        dom_ms, dom_n = tm[dominant]
         ab = algorithmic_bytes(P, hv=wl["view"], wv=wl["view"], beams=wl["beams"])
         kernel_bytes = ab.get(dominant, ab["total"]) * RL
         dur_s = (dom_ms / dom_n) * 1e-3 if dom_n else float("nan")
@@ -660,7 +738,6 @@ def main():
         # counters: profiles/pmc_<config>.json (pmc_latest.json = the headline's, its name since round 1), collected by
         # tools/profile_cfg.sh on a named build
         pmc = os.path.join(ROOT, "profiles", "pmc_latest.json" if args.config == "cfg3" else "pmc_%s.json" % args.config)
-        build_id = world.lib.imgenv_build_id().decode()
         counters_ok = False  # the committed counters describe THIS library (same sources + flags), or they are not quoted
         default_shape = world_size == 1 and RL == wl["robots"] and P == wl["peds"] and not args.force_dist
         counters = {}
@@ -698,41 +775,17 @@ def main():
                          "ceiling_us_if_all_were_adds": lo, "frac": hi / (dur_s * 1e6), "source": "profiles/%s (SQ passes)" % os.path.basename(pmc)}
         except Exception:
             issue = None
-        out = {
-            "metric": "robot-steps/sec (whole node) at 8192 robots, 48x48 maps, 360 lasers",
-            "value": value, "unit": "robot-steps/s", "n_gpus": world_size, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
-            "scaling": "weak" if replicas else wl["scaling"], "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": (wl["name"] % dict(R=R, RL=RL, N=world_size, P=P, strong="" if world_size == 1 else
-                                                      ": strong scaling, the same world at every GPU count")) +
-                                   ", %dx%d grid @%.3f m, %dx%d sensor_map + 3ch ped_map, %d-beam laser, time_max %d, full reset whenever the "
-                                   "time limit runs out (%d inside the %d timed steps)" % (side, side, res, wl["view"], wl["view"], wl["beams"],
-                                                                                           TIME_MAX, resets_timed, args.steps),
-                       "baseline_config": args.config,
-                       "robots": R_job, "peds": P, "grid": side, "resolution": res, "view": wl["view"], "beams": wl["beams"],
-                       "policy": "active: v=0, w~U(-0.9,0.9): every robot-step runs the full view path (spec_policy: SURVEY 8(d)'s own actions)",
-                       "parallelism": (("%d independent replicas, no exchange" % world_size) if replicas else
-                                       "robot-sharded x%d, RCCL all-gather of robot records (%s)" % (
-                                           world_size, ("ncclAllGather inside imgenv_step, communicator of %d ranks as reported by RCCL" % comm_ranks)
-                                           if native else "torch.distributed between step_begin/step_end"))
-                       if use_dist else "single GPU"},
-            "resets_in_timed_region": resets_timed,
-            "passes": {"n": len(passes), "value_is": "median", "values": pass_values, "min": min(pass_values), "max": max(pass_values)},
+        out.update({
             "uninstrumented": uninstrumented,
-            "actions": "pre-generated in HBM; plain stream-ordered imgenv_step (IMGENV_STEP_ACTIONS_READY is without effect since round 6)",
             "with_reset": with_reset,
             "spec_policy": spec_policy,
             "full_rewrite": full_rewrite,
             "shipped": shipped,
-            "frozen_fraction": frozen_active,
             "multi_world": multi_world,
             "vec_env": vec_env,
             "episode_policy": episode,
             "kernel_us": per_kernel_us,
             "per_rank_kernel_us": per_rank_kernel_us,  # N > 1: every rank's kernels and `rccl_all_gather`, the in-library exchange
-            "build_id": build_id,
-            "launches_per_step": launches_per_step,
-            "layer_mode": layer_mode,
             "roofline": {"bound": "hbm", "kernel": dominant, "longest_kernel_by_events": longest_kernel, "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
                          "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": traffic_source,
                          # the same fraction from the COUNTERS' bytes of the dominant kernel: what it really moved (a kernel that
@@ -748,7 +801,7 @@ def main():
                          # path_traffic_frac above is the counter-based figure
                          "path_algorithmic_gbps": ab["total"] * value / world_size / 1e9,
                          "issue": issue},
-        }
+        })
         if sfm_flips is not None:
             out["sfm_first_step_sign_flips"] = sfm_flips
         if cpu_base is not None:

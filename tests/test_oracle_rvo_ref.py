@@ -1,5 +1,6 @@
 """Oracle RVO2/ERVO restatement vs (a) the reference's own RVO2 sources compiled unmodified into
-oracle/_ref/librvo_ref.so and (b) a committed trace generated from that library."""
+oracle/_ref/librvo_ref.so -- or, where that library cannot be built (no reference tree), the traces it gave for the same
+seeds (golden/rvo_ref_build_traces.npz) -- and (b) a committed trace generated from that library."""
 import os
 
 import numpy as np
@@ -8,6 +9,8 @@ import pytest
 from rvo_harness import OracleRvo, RefRvo, run_scenario
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "rvo_ref_traces.npz")
+GOLD_BUILD = os.path.join(os.path.dirname(__file__), "golden", "rvo_ref_build_traces.npz")
+BUILD_SEEDS = (2, 3, 4)
 CASES = {
     "plain": dict(),
     "ervo": dict(ervo=True),
@@ -26,11 +29,14 @@ def test_oracle_matches_committed_reference_trace(oracle_lib, case):
         assert np.array_equal(brute, got)
 
 
-@pytest.mark.skipif(not os.path.exists(RefRvo.path()), reason="oracle/_ref not built (no reference tree)")
 @pytest.mark.parametrize("case", list(CASES))
 def test_oracle_matches_reference_build(oracle_lib, case):
-    for seed in (2, 3, 4):
-        ref = run_scenario(RefRvo(0.25), seed, **CASES[case])
+    live = os.path.exists(RefRvo.path())  # oracle/_ref is built where the reference tree is; its stored traces stand in elsewhere
+    z = np.load(GOLD_BUILD)
+    for seed in BUILD_SEEDS:
+        ref = z["%s_%d" % (case, seed)]
+        if live:
+            assert np.array_equal(run_scenario(RefRvo(0.25), seed, **CASES[case]), ref)
         got = run_scenario(OracleRvo(0.25), seed, **CASES[case])
         assert np.array_equal(got, ref)
         assert np.abs(ref[-1, :, :2] - ref[0, :, :2]).max() > 0.5       # agents really moved

@@ -10,9 +10,10 @@ tag=${1:-set}
 cfg=${2:-cfg3}
 out=/root/repo/gpurun_out
 p=$out/${tag}_${cfg}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-B="python3 /root/repo/bench.py --config $cfg --steps 100 --warmup 10 --no-cpu-baseline --no-episode --no-multi-world"
-S="python3 /root/repo/bench.py --config $cfg --steps 6 --warmup 3 --spinup 0 --passes 1 --no-cpu-baseline --no-episode --no-multi-world"
+B="python3 $ROOT/bench.py --full --config $cfg --steps 100 --warmup 10 --no-cpu-baseline --no-episode --no-multi-world"
+S="python3 $ROOT/bench.py --full --config $cfg --steps 6 --warmup 3 --spinup 0 --passes 1 --no-cpu-baseline --no-episode --no-multi-world"
 rocprofv3 --kernel-trace --stats -d ${p}_trace -o t -- $B > ${p}_trace.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d ${p}_fetch -o p --output-format csv -- $S > ${p}_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d ${p}_write -o p --output-format csv -- $S > ${p}_write.log 2>&1

@@ -13,8 +13,10 @@ cd /root/repo
 for c in "cfg3 sq" "cfg2" "cfg4" "cfg5 sq"; do bash tools/profile_cfg.sh $tag $c; done
 cp gpurun_out/${tag}_cfg3_pmc.json profiles/pmc_latest.json
 for c in cfg2 cfg4 cfg5; do cp gpurun_out/${tag}_${c}_pmc.json profiles/pmc_$c.json; done
-python bench.py 2> gpurun_out/${tag}_bench.err | tail -1 > gpurun_out/${tag}_bench.json
-for c in cfg2 cfg4 cfg5; do python bench.py --config $c --no-multi-world 2> gpurun_out/${tag}_${c}_bench.err | tail -1 > gpurun_out/${tag}_${c}_bench.json; done
+# the bench lines go beside the profile set, into the directory tools/profile_cfg.sh wrote it to
+res=$(dirname "$(ls -d "$PWD"/*/"${tag}_cfg3_pmc.json" | head -1)")
+python bench.py --full 2> $res/${tag}_bench.err | tail -1 > $res/${tag}_bench.json
+for c in cfg2 cfg4 cfg5; do python bench.py --full --config $c --no-multi-world 2> $res/${tag}_${c}_bench.err | tail -1 > $res/${tag}_${c}_bench.json; done
 python tools/shard_probe.py cfg4 --time-max 1000 --out gpurun_out/${tag}_cfg4_shard_probe.json > /dev/null 2>&1
 python tools/shard_probe.py cfg3 --time-max 1000 --out gpurun_out/${tag}_cfg3_shard_probe.json > /dev/null 2>&1
 python -m pytest tests -m gpu -q --timeout 900 2>&1 | tail -12 > gpurun_out/${tag}_gpu_tests.log

@@ -2171,6 +2171,47 @@ __device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t x) {
     return x;
 }
 
+// the first-hit key of one 8-step chunk of a beam's path (ch: the chunk's number, cur: its 8 view cells): min over the steps of
+// value << 8 | step, with two 16-bit keys side by side (even steps in the low half, odd ones in the high half, one packed min for
+// both); < 0x0100 iff an occupied cell (value 0) lies on the chunk.  Padded entries point at the free dummy cell.
+__device__ __forceinline__ uint32_t beam_chunk_key(const uint8_t* src, const uint4 cur, int ch, uint32_t found2) {
+    const uint32_t wds[4] = {cur.x, cur.y, cur.z, cur.w};
+    const uint32_t steps0 = (uint32_t)(8 * ch) * 0x00010001u + 0x00010000u;  // (8 ch + 1) << 16 | 8 ch
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t lo = src[wds[j] & 0xFFFFu], hi = src[wds[j] >> 16];
+        const uint32_t two = __builtin_amdgcn_perm(hi, lo, 0x040C000Cu) | (steps0 + (uint32_t)j * 0x00020002u);
+        found2 = pk_min_u16(found2, two);
+    }
+    return found2;
+}
+
+// everything k_view stores for beam b once its first-hit key (value << 8 | step; no hit: >= 0x0100) is known
+__device__ __forceinline__ void beam_finish(const DevWorld& w, const RobotClassDev& k, uint32_t* hit, int l, int b, uint32_t first) {
+    const bool has = first < 0x0100u;  // value 0 in the key's top byte
+    const uint32_t hk = first & 0xFFu;
+    // how far behind the hit the beam stays in the hit cell's row or column: static per (step, beam)
+    // ... and its distance, as float32 and as the `lasers` value (hd / laser_max when laser_norm): one 16-byte record
+    const uint4 fin = k.ray_fin[(size_t)(has ? hk : 0u) * k.ray_stride + b];
+    const uint32_t run = has ? fin.x : 0u;
+    const float hd = has ? __uint_as_float(fin.y) : 6.0f;  // agent.cpp:513
+    hit[b] = has ? ((hk << 16) | (hk + run)) : 0xFFFFFFFFu;
+    w.lasers_raw[(size_t)l * w.B + b] = hd;
+    w.lasers[(size_t)l * w.B + b] = has ? __hiloint2double((int)fin.w, (int)fin.z) : w.laser_out_nohit;
+    if (w.hits_x) {  // hit_points_x_ / _y_ (agent.cpp:434-435), static per (step, beam); row ray_maxlen: no hit
+        const size_t at = (size_t)(has ? hk : (uint32_t)k.ray_maxlen) * k.ray_stride + b;
+        w.hits_x[(size_t)l * w.B + b] = k.ray_hx[at];
+        w.hits_y[(size_t)l * w.B + b] = k.ray_hy[at];
+    }
+}
+
+// one wavefront appends b of every lane with `live` to queue[n, ...) in lane order; returns how many
+__device__ __forceinline__ int beam_enqueue(uint16_t* queue, int n, bool live, int b) {
+    const unsigned long long m = __ballot(live);
+    if (live) queue[n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)b;
+    return __popcll(m);
+}
+
 // angular_map_ (agent.cpp:407-433): nearest hit of each 1/72 of the field of view, one bin per thread from the beams' hit words
 // (first-hit step << 16 | ..., 0xFFFFFFFF = no hit); a bin's beams are a contiguous range
 __device__ __forceinline__ void angular_bins(const DevWorld& w, const RobotClassDev& k, const uint32_t* hit, int l, int tid, int nt) {
@@ -2380,45 +2421,61 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(8, 8)
     if (laser) {
         const uint4* rows = (const uint4*)k.ray_rows;
         const int n_chunks = k.ray_kpad >> 3;
-        for (int b0 = 0; b0 < w.B; b0 += NT) {
-            const int b = b0 + tid;
-            const int bb = min(b, w.B - 1);
-            const int len = b < w.B ? (int)k.ray_len[bb] : 0;
-            // two 16-bit keys side by side, value << 8 | step (a path has at most 255 steps): even steps in the low half,
-            // odd ones in the high half, one packed min for both
-            uint32_t found2 = 0xFFFFFFFFu;
-            uint4 nxt = rows[bb];
-            for (int ch = 0; ch < n_chunks; ch++) {
+        if (NW == 1 && w.B <= 8 * Wv) {
+            // One wavefront: chunk by chunk over the beams still alive.  A round of 64 beams used to walk chunks until its LAST
+            // beam had hit or ended, every lane through every chunk; here chunk 0 of every beam is walked, and chunk ch + 1 only
+            // of the beams that neither hit nor ended in chunk ch, taken densely (64 per round) from a queue of beam numbers in
+            // the dead column table (B uint16 <= 16 Wv bytes), compacted in place: the survivors of a round are never more than
+            // the entries read so far.  A beam's first hit is its first chunk that holds an occupied cell, so the keys are those
+            // of the full walk.  hit[b] holds the key until the pass below turns it into the hit word.
+            uint16_t* queue = (uint16_t*)colt;
+            int n_live = 0;
+            uint4 nxt = rows[min(tid, w.B - 1)];
+            for (int b0 = 0; b0 < w.B; b0 += WAVE) {
+                const int b = b0 + tid, bb = min(b, w.B - 1);
                 const uint4 cur = nxt;
-                if (ch + 1 < n_chunks) nxt = rows[(size_t)(ch + 1) * k.ray_stride + bb];  // in flight while this chunk is walked
-                const uint32_t wds[4] = {cur.x, cur.y, cur.z, cur.w};
-                const uint32_t steps0 = (uint32_t)(8 * ch) * 0x00010001u + 0x00010000u;  // (8 ch + 1) << 16 | 8 ch
-#pragma unroll
-                for (int j = 0; j < 4; j++) {  // padded entries point at the free dummy cell
-                    const uint32_t lo = src[wds[j] & 0xFFFFu], hi = src[wds[j] >> 16];
-                    const uint32_t two = __builtin_amdgcn_perm(hi, lo, 0x040C000Cu) | (steps0 + (uint32_t)j * 0x00020002u);
-                    found2 = pk_min_u16(found2, two);
-                }
+                if (b0 + WAVE < w.B) nxt = rows[min(b + WAVE, w.B - 1)];  // in flight while this round is walked
+                const int len = (int)k.ray_len[bb];
+                const uint32_t found2 = beam_chunk_key(src, cur, 0, 0xFFFFFFFFu);
                 const uint32_t first = min(found2 & 0xFFFFu, found2 >> 16);
-                if (__all((first < 0x0100u) | (8 * ch + 8 >= len))) break;
+                const bool live = b < w.B && first >= 0x0100u && len > 8;
+                if (b < w.B && !live) hit[b] = first;
+                n_live += beam_enqueue(queue, n_live, live, b);
             }
-            if (b < w.B) {
-                const uint32_t first = min(found2 & 0xFFFFu, found2 >> 16);
-                const bool has = first < 0x0100u;  // value 0 in the key's top byte
-                const uint32_t hk = first & 0xFFu;
-                // how far behind the hit the beam stays in the hit cell's row or column: static per (step, beam)
-                // ... and its distance, as float32 and as the `lasers` value (hd / laser_max when laser_norm): one 16-byte record
-                const uint4 fin = k.ray_fin[(size_t)(has ? hk : 0u) * k.ray_stride + b];
-                const uint32_t run = has ? fin.x : 0u;
-                const float hd = has ? __uint_as_float(fin.y) : 6.0f;  // agent.cpp:513
-                hit[b] = has ? ((hk << 16) | (hk + run)) : 0xFFFFFFFFu;
-                w.lasers_raw[(size_t)l * w.B + b] = hd;
-                w.lasers[(size_t)l * w.B + b] = has ? __hiloint2double((int)fin.w, (int)fin.z) : w.laser_out_nohit;
-                if (w.hits_x) {  // hit_points_x_ / _y_ (agent.cpp:434-435), static per (step, beam); row ray_maxlen: no hit
-                    const size_t at = (size_t)(has ? hk : (uint32_t)k.ray_maxlen) * k.ray_stride + b;
-                    w.hits_x[(size_t)l * w.B + b] = k.ray_hx[at];
-                    w.hits_y[(size_t)l * w.B + b] = k.ray_hy[at];
+            for (int ch = 1; ch < n_chunks && n_live > 0; ch++) {  // (no beam is alive behind its last chunk: len <= ray_kpad)
+                __syncthreads();  // (one wavefront: orders the lanes' queue stores before the loads of other lanes)
+                int n_next = 0;
+                for (int q0 = 0; q0 < n_live; q0 += WAVE) {
+                    const int j = q0 + tid;
+                    const bool in = j < n_live;
+                    const int b = (int)queue[min(j, n_live - 1)];  // (read before this round's survivors are written)
+                    const uint4 cur = rows[(size_t)ch * k.ray_stride + b];
+                    const int len = (int)k.ray_len[b];
+                    const uint32_t found2 = beam_chunk_key(src, cur, ch, 0xFFFFFFFFu);
+                    const uint32_t first = min(found2 & 0xFFFFu, found2 >> 16);
+                    const bool live = in && first >= 0x0100u && len > 8 * ch + 8;
+                    if (in && !live) hit[b] = first;
+                    n_next += beam_enqueue(queue, n_next, live, b);
                 }
+                n_live = n_next;
+            }
+            __syncthreads();
+            for (int b = tid; b < w.B; b += WAVE) beam_finish(w, k, hit, l, b, hit[b]);
+        } else {
+            for (int b0 = 0; b0 < w.B; b0 += NT) {
+                const int b = b0 + tid;
+                const int bb = min(b, w.B - 1);
+                const int len = b < w.B ? (int)k.ray_len[bb] : 0;
+                uint32_t found2 = 0xFFFFFFFFu;
+                uint4 nxt = rows[bb];
+                for (int ch = 0; ch < n_chunks; ch++) {
+                    const uint4 cur = nxt;
+                    if (ch + 1 < n_chunks) nxt = rows[(size_t)(ch + 1) * k.ray_stride + bb];  // in flight while this chunk is walked
+                    found2 = beam_chunk_key(src, cur, ch, found2);
+                    const uint32_t first = min(found2 & 0xFFFFu, found2 >> 16);
+                    if (__all((first < 0x0100u) | (8 * ch + 8 >= len))) break;
+                }
+                if (b < w.B) beam_finish(w, k, hit, l, b, min(found2 & 0xFFFFu, found2 >> 16));
             }
         }
         if (tid == 0) hit[w.B] = 0u;  // the dummy beam of cells without any (see the final pass)

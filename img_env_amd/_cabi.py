@@ -27,6 +27,7 @@ FLAG_CHECK_OUTPUTS = 128  # debug: checksum every output array between calls, EI
 FLAG_FULL_REWRITE = 256   # the outputs are copies rewritten in full by every call (the reference's value-copy ownership)
 FLAG_CHECK_OUTPUTS_FIRST = 1024  # FLAG_CHECK_OUTPUTS for the handle's first 64 calls only (World's default)
 ANGULAR_BINS = 72
+STACK_MAX_DEPTH = 16  # IMGENV_STACK_MAX_DEPTH
 
 SHAPES = {"circle": SHAPE_CIRCLE, "rectangle": SHAPE_RECTANGLE, "leg": SHAPE_LEG}
 # Env.msg ped_scene_type strings (scenefactory.h:8-24): anything else is the EmptyScene
@@ -113,6 +114,25 @@ class Out(C.Structure):
         ("step_is_arrives", C.c_void_p), ("step_is_collisions", C.c_void_p), ("step_all_down", C.c_void_p),
         ("hits_x", C.c_void_p), ("hits_y", C.c_void_p), ("angular_map", C.c_void_p),
     ]
+
+
+class StackCfg(C.Structure):
+    _fields_ = [("struct_size", _i32), ("image_batch", _i32), ("state_batch", _i32), ("laser_batch", _i32),
+                ("arena", C.c_void_p), ("arena_bytes", _i64)]
+
+
+class StackOut(C.Structure):
+    _fields_ = [("struct_size", _i32), ("n_local", _i32), ("image_depth", _i32), ("state_depth", _i32), ("laser_depth", _i32),
+                ("reserved_", _i32), ("sensor_maps", C.c_void_p), ("vector_states", C.c_void_p), ("lasers", C.c_void_p)]
+
+
+def make_stack_cfg(image_batch, state_batch, laser_batch, arena=None, arena_bytes=0):
+    """the YAML keys of StateBatchWrapper (base.py:103-105) as an ``imgenv_stack_cfg``"""
+    s = StackCfg()
+    s.struct_size = C.sizeof(StackCfg)
+    s.image_batch, s.state_batch, s.laser_batch = int(image_batch), int(state_batch), int(laser_batch)
+    s.arena, s.arena_bytes = arena, int(arena_bytes)
+    return s
 
 
 #: name -> (numpy dtype, shape as a function of the Out header and the world sizes)
@@ -261,7 +281,8 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_records", "imgenv_outputs", "imgenv_step_launches", "imgenv_timing", "imgenv_timing_read",
            "imgenv_kernel_name", "imgenv_comm_unique_id", "imgenv_comm_init", "imgenv_comm_info", "imgenv_reset_world", "imgenv_reset_worlds", "imgenv_spawn",
            "imgenv_reset_worlds_spawn", "imgenv_step_autoreset", "imgenv_step_autoreset_device", "imgenv_autoreset_last",
-           "imgenv_world_placement", "imgenv_cv_resize_u8", "imgenv_build_id", "imgenv_step_flags", "imgenv_layer_mode")
+           "imgenv_world_placement", "imgenv_cv_resize_u8", "imgenv_build_id", "imgenv_step_flags", "imgenv_layer_mode",
+           "imgenv_stack_bytes", "imgenv_stack_enable", "imgenv_stack_outputs")
 K_COUNT = 14
 
 
@@ -308,6 +329,10 @@ def bind(lib):
     lib.imgenv_comm_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
     lib.imgenv_comm_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.imgenv_cv_resize_u8.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
+    lib.imgenv_stack_bytes.argtypes = [C.POINTER(Cfg), C.POINTER(StackCfg)]
+    lib.imgenv_stack_bytes.restype = C.c_int64
+    lib.imgenv_stack_enable.argtypes = [C.c_void_p, C.POINTER(StackCfg), C.POINTER(StackOut)]
+    lib.imgenv_stack_outputs.argtypes = [C.c_void_p, C.POINTER(StackOut)]
     lib.imgenv_kernel_name.argtypes = [C.c_int]
     lib.imgenv_kernel_name.restype = C.c_char_p
     return lib

@@ -22,6 +22,7 @@
 #include "spawn_host.h"
 #include "kernels.h"
 #include "world.h"
+#include "stack.h"
 
 static thread_local char g_err[512] = "";
 #define FAIL(code, ...)                              \
@@ -174,6 +175,10 @@ struct imgenv {
     int n_spans = 0, span_blocks = 0;
     unsigned long long* d_sums = nullptr;  // ... and their checksums: [2][n_spans], sealed | found at the next call
     const char* span_name[40];
+    // observation stacks (include/imgenv.h: imgenv_stack_enable; csrc/stack.h)
+    bool stack_on = false;       // imgenv_stack_enable has been called
+    StackDev stack;              // n_fields == 0: every depth is 0 or 1, nothing to launch
+    imgenv_stack_out stack_out;
     bool chain_open = false;  // a chain of launches that hands over through tail_sig / tail_cnt has started and not been completed
     std::vector<RvoObstacles> rvos;  // one obstacle set per world
     int sfm_cap_obs = 0;
@@ -1789,6 +1794,21 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
     h->early_step = false;
     if (h->P > 0 && !h->serial) HIPCHK(hipStreamWaitEvent(st, h->ev_join2, 0));
     h->launches += 3;
+    if (h->stack_on && h->stack.n_fields > 0) {
+        // the observation stacks (stack.h), behind the join of the side streams and in front of the seal: a step pushes every local
+        // robot's new frames, a reset chain restarts the stacks of the robots it covers -- all of them, or the worlds of the chain's
+        // list, whose length the host knows (act_nw) or a kernel has counted (act_n_dev: the grid is sized for every world and strides)
+        StackDev sd = h->stack;
+        sd.list = is_reset ? d.act_list : nullptr;
+        sd.n_dev = is_reset ? d.act_n_dev : nullptr;
+        sd.n_worlds = d.act_nw;
+        const size_t rows = sd.list ? (size_t)(sd.n_dev ? std::min(d.act_nw * h->Rw, std::max(h->act_hint, h->Rw)) : d.act_nw * h->Rw) : (size_t)h->RL;
+        const size_t items = rows * sd.chunks_per_robot;
+        const unsigned blocks = (unsigned)std::min<size_t>(STACK_MAX_BLOCKS, std::max<size_t>(1, (items + STACK_BLOCK - 1) / STACK_BLOCK));
+        if (is_reset) k_stack<true><<<dim3(blocks), dim3(STACK_BLOCK), 0, st>>>(sd);
+        else k_stack<false><<<dim3(blocks), dim3(STACK_BLOCK), 0, st>>>(sd);
+        h->launches += 1;
+    }
     HIPCHK(hipGetLastError());
     h->chain_open = false;
     return outputs_seal(h, st);
@@ -3228,6 +3248,102 @@ extern "C" int imgenv_outputs(imgenv_t* h, imgenv_out* out) {
         memcpy(out, &src, (size_t)want);
         out->struct_size = want;  // what the caller really holds, not this library's larger size
     }
+    return IMGENV_OK;
+}
+
+// ---- observation stacks (include/imgenv.h; the kernel is csrc/stack.h) ----
+struct StackPlan {
+    int depth[3];          // effective depths: sensor_maps, vector_states, lasers (0 = not stacked)
+    size_t frame_bytes[3];
+    size_t off[3], total;  // carve-outs of the fields of depth >= 2
+};
+static int plan_stack(const imgenv_cfg& c, const imgenv_stack_cfg& s, int RL, StackPlan& p) {
+    const int B = make_view_geom(c).B;
+    p.depth[0] = s.image_batch > 0 ? s.image_batch : 0;
+    p.depth[1] = s.state_batch > 0 ? s.state_batch : 0;
+    p.depth[2] = s.laser_batch >= 0 && B > 0 ? std::max(s.laser_batch, 1) : 0;
+    if (s.image_batch < 0 || s.state_batch < 0) FAIL(IMGENV_EINVAL, "image_batch / state_batch must be >= 0");
+    if (s.image_batch > IMGENV_STACK_MAX_DEPTH || s.state_batch > IMGENV_STACK_MAX_DEPTH || s.laser_batch > IMGENV_STACK_MAX_DEPTH)
+        FAIL(IMGENV_EINVAL, "a stack depth above IMGENV_STACK_MAX_DEPTH (%d)", IMGENV_STACK_MAX_DEPTH);
+    p.frame_bytes[0] = (size_t)c.image_size[0] * (size_t)c.image_size[1] * 2;
+    p.frame_bytes[1] = (size_t)c.state_dim * 4;
+    p.frame_bytes[2] = (size_t)B * 8;
+    p.total = 0;
+    for (int k = 0; k < 3; k++) {
+        p.off[k] = p.total;
+        if (p.depth[k] >= 2) p.total = align256(p.total + (size_t)RL * p.depth[k] * p.frame_bytes[k]);
+    }
+    return IMGENV_OK;
+}
+
+extern "C" int64_t imgenv_stack_bytes(const imgenv_cfg* cfg, const imgenv_stack_cfg* s) {
+    if (!cfg || !s) FAIL(IMGENV_EINVAL, "null argument");
+    if (cfg->struct_size != (int32_t)sizeof(imgenv_cfg) || s->struct_size != (int32_t)sizeof(imgenv_stack_cfg)) FAIL(IMGENV_EINVAL, "struct_size mismatch");
+    int r0, r1;
+    if (shard_of(*cfg, r0, r1)) FAIL(IMGENV_EINVAL, "bad robot shard");
+    StackPlan p;
+    if (int rc = plan_stack(*cfg, *s, r1 - r0, p)) return rc;
+    return (int64_t)p.total;
+}
+
+extern "C" int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgenv_stack_out* out) {
+    if (!h || !s) FAIL(IMGENV_EINVAL, "null argument");
+    if (s->struct_size != (int32_t)sizeof(imgenv_stack_cfg)) FAIL(IMGENV_EINVAL, "imgenv_stack_cfg.struct_size %d (this library's is %d)", s->struct_size, (int)sizeof(imgenv_stack_cfg));
+    if (out && out->struct_size != 0 && out->struct_size != (int32_t)sizeof(imgenv_stack_out)) FAIL(IMGENV_EINVAL, "imgenv_stack_out.struct_size");
+    if (h->stack_on) FAIL(IMGENV_ESTATE, "imgenv_stack_enable has already been called on this handle");
+    bool any_reset = h->has_reset;
+    for (char r : h->world_ready) any_reset = any_reset || r;
+    if (any_reset) FAIL(IMGENV_ESTATE, "imgenv_stack_enable after the first reset");
+    StackPlan p;
+    if (int rc = plan_stack(h->cfg, *s, h->RL, p)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    unsigned char* base = nullptr;
+    if (p.total > 0) {
+        if (s->arena) {
+            if (s->arena_bytes < (int64_t)p.total) FAIL(IMGENV_EINVAL, "stack arena too small: %lld < %zu", (long long)s->arena_bytes, p.total);
+            if ((uintptr_t)s->arena & 255) FAIL(IMGENV_EINVAL, "stack arena must be 256-byte aligned");
+            base = (unsigned char*)s->arena;
+            HIPCHK(hipMemset(base, 0, p.total));
+        } else {
+            RTRY(dev_alloc(h, &base, p.total));  // (zeroed)
+        }
+    }
+    const imgenv_out& pub = h->pub_arena ? h->pub_out : h->out;
+    unsigned char* const work[3] = {(unsigned char*)h->out.sensor_maps, (unsigned char*)h->out.vector_states, (unsigned char*)h->out.lasers};
+    unsigned char* const handed[3] = {(unsigned char*)pub.sensor_maps, (unsigned char*)pub.vector_states, (unsigned char*)pub.lasers};
+    unsigned char* ptr[3] = {nullptr, nullptr, nullptr};
+    StackDev sd;
+    memset(&sd, 0, sizeof(sd));
+    sd.RL = h->RL; sd.r0 = h->r0; sd.Rw = h->Rw;
+    for (int k = 0; k < 3; k++) {
+        if (p.depth[k] == 1) ptr[k] = handed[k];  // [R][1][...] is the imgenv_out array itself
+        if (p.depth[k] < 2) continue;
+        ptr[k] = base + p.off[k];
+        StackField& f = sd.f[sd.n_fields++];
+        f.stack = ptr[k];
+        f.frame = work[k];
+        f.frame_bytes = (uint32_t)p.frame_bytes[k];
+        f.unit = f.frame_bytes % 16 == 0 ? 16 : f.frame_bytes % 8 == 0 ? 8 : f.frame_bytes % 4 == 0 ? 4 : 2;
+        f.chunks = f.frame_bytes / f.unit;
+        f.depth = p.depth[k];
+        sd.chunks_per_robot += f.chunks;
+    }
+    h->stack = sd;
+    imgenv_stack_out& o = h->stack_out;
+    memset(&o, 0, sizeof(o));
+    o.struct_size = (int32_t)sizeof(imgenv_stack_out);
+    o.n_local = h->RL;
+    o.image_depth = p.depth[0]; o.state_depth = p.depth[1]; o.laser_depth = p.depth[2];
+    o.sensor_maps = (uint16_t*)ptr[0]; o.vector_states = (float*)ptr[1]; o.lasers = (double*)ptr[2];
+    h->stack_on = true;
+    if (out) *out = o;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_stack_outputs(imgenv_t* h, imgenv_stack_out* out) {
+    if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->stack_on) FAIL(IMGENV_ESTATE, "imgenv_stack_enable was not called");
+    *out = h->stack_out;
     return IMGENV_OK;
 }
 

@@ -35,7 +35,7 @@ class VecImageEnv:
     their rows of the returned state are already the new episode's first observation, as with NeverStopWrapper).
     """
 
-    def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False):
+    def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False):
         import torch
         from .world import World
         self.cfg = cfg
@@ -68,13 +68,33 @@ class VecImageEnv:
             self.params["flags"] = int(self.params.get("flags", 0)) | _cabi.FLAG_NO_VIEW_MAPS
         self.world = World(stack_params(self.params, self.env_num), self.grid, device=cfg.get("device", 0))
         self._all_down = self.world.out["step_all_down"].view(torch.bool) if native_spawn else None
+        # stack: StateBatchWrapper (base.py:97-150) inside the library, per env (imgenv_stack_enable): every state handed out
+        # carries each robot's last cfg["image_batch"] sensor maps, cfg["state_batch"] vector states and
+        # max(cfg["laser_batch"], 1) laser scans of its env's current episode, zero-padded after the env's reset -- whoever reset it,
+        # the host or the device.  If the YAML's wrapper list ends in ObsStateTmp / ObsLaserStateTmp (filter_states.py:6-20) the
+        # state is that wrapper's list of three tensors.  Opt-in: False hands out single frames, as before.
+        self.stack = bool(stack)
+        self._filter = None
+        if self.stack:
+            self.world.enable_stack(int(cfg.get("image_batch", 0)), int(cfg.get("state_batch", 0)), int(cfg.get("laser_batch", -1)))
+            names = [w for w in (cfg.get("wrapper") or []) if w in ("ObsStateTmp", "ObsLaserStateTmp")]
+            self._filter = names[-1] if names else None
 
     def __len__(self):
         return self.env_num * self.robot_total
 
     def _state(self):
         o = self.world.out
-        return ImageState(o["vector_states"], o["sensor_maps"], o["is_collisions"], o["is_arrives"], o["lasers"],
+        if not self.stack:
+            return ImageState(o["vector_states"], o["sensor_maps"], o["is_collisions"], o["is_arrives"], o["lasers"],
+                              o["ped_vector_states"], o["ped_maps"], o["step_ds"], o["ped_min_dists"])
+        k = self.world.stack
+        vector_states, sensor_maps, lasers = (k.get(f, o[f]) for f in ("vector_states", "sensor_maps", "lasers"))
+        if self._filter == "ObsStateTmp":
+            return [sensor_maps, vector_states, o["ped_maps"]]
+        if self._filter == "ObsLaserStateTmp":
+            return [lasers, vector_states, o["ped_maps"]]
+        return ImageState(vector_states, sensor_maps, o["is_collisions"], o["is_arrives"], lasers,
                           o["ped_vector_states"], o["ped_maps"], o["step_ds"], o["ped_min_dists"])
 
     def reset(self, layouts=None):

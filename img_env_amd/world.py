@@ -92,6 +92,8 @@ class World:
                         if 0 <= off and off + n <= int(nbytes) else None)
         self.robot_begin = cfg.robot_begin
         self.robot_end = cfg.robot_end if cfg.robot_end else cfg.n_robots
+        self.stack = None  # enable_stack()
+        self.stack_arena = None
 
     def _check(self, rc, what):
         if rc != 0:
@@ -100,6 +102,49 @@ class World:
     def _stream(self):
         import torch
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def enable_stack(self, image_batch, state_batch, laser_batch):
+        """Device-side StateBatchWrapper (``imgenv_stack_enable``; once, before the first reset): from now on every reset / step
+        also keeps ``self.stack`` -- zero-copy tensors ``sensor_maps`` float16 ``[R, Ki, H, W]``, ``vector_states`` float32
+        ``[R, Ks * state_dim]``, ``lasers`` float64 ``[R, Kl, B]`` holding each robot's last K frames of the current episode,
+        oldest first, zero-padded after a reset.  Depths are the YAML keys (``image_batch`` / ``state_batch`` 0 = not stacked,
+        ``laser_batch`` < 0 = not stacked, 0 = depth 1); a field that is not stacked has no key.  torch owns the memory, as it
+        owns the output arena; a field of depth 1 is a view of ``self.out``'s tensor.  Read-only, like ``out``."""
+        import torch
+        s = _cabi.make_stack_cfg(image_batch, state_batch, laser_batch)
+        nbytes = self.lib.imgenv_stack_bytes(C.byref(self.cfg), C.byref(s))
+        if nbytes < 0:
+            raise ValueError("imgenv_stack_bytes: %s" % self.lib.imgenv_last_error().decode())
+        if nbytes > 0:
+            with torch.cuda.device(self.device):
+                self.stack_arena = torch.zeros(int(nbytes), dtype=torch.uint8, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()  # (the library's kernels may run on any stream)
+            s.arena, s.arena_bytes = self.stack_arena.data_ptr(), int(nbytes)
+        so = _cabi.StackOut()
+        rc = self.lib.imgenv_stack_enable(self.h, C.byref(s), C.byref(so))
+        if rc == -4:
+            raise RuntimeError("imgenv_stack_enable: %s" % self.lib.imgenv_last_error().decode())
+        if rc != 0:
+            raise ValueError("imgenv_stack_enable: %s" % self.lib.imgenv_last_error().decode())
+        R, o = self.n_local, self.out
+        H, Wd = o["sensor_maps"].shape[1:]
+        shapes = {"sensor_maps": (so.image_depth, torch.float16, (R, so.image_depth, H, Wd)),
+                  "vector_states": (so.state_depth, torch.float32, (R, so.state_depth * o["vector_states"].shape[1])),
+                  "lasers": (so.laser_depth, torch.float64, (R, so.laser_depth, o["lasers"].shape[1]))}
+        self.stack = {}
+        for name, (depth, dt, shape) in shapes.items():
+            ptr = getattr(so, name)
+            if depth == 0 or not ptr:
+                continue
+            if depth == 1:  # the library handed out the imgenv_out array itself
+                assert ptr == o[name].data_ptr()
+                self.stack[name] = o[name].view(*shape)
+                continue
+            off = ptr - self.stack_arena.data_ptr()
+            n = int(np.prod(shape)) * torch.empty(0, dtype=dt).element_size()
+            self.stack[name] = self.stack_arena[off:off + n].view(dt).view(*shape)
+        self.stack_depths = (so.image_depth, so.state_depth, so.laser_depth)
+        return self.stack
 
     def reset(self, layout):
         """Reset everything.  A handle of several worlds (``n_worlds`` > 1) takes either one batch of all robots and

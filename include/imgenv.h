@@ -438,6 +438,54 @@ int imgenv_autoreset_last(imgenv_t* h, int32_t* worlds_out, int32_t cap, int32_t
 int imgenv_world_placement(imgenv_t* h, int32_t world, uint64_t* placement, double* robot_pose, double* robot_goal, double* ped_pose,
                            double* ped_goal, double* ped_traj, int32_t* ped_traj_len, int32_t* obs_shape, float* obs_size, double* obs_pose);
 
+/* ---- observation stacks: StateBatchWrapper (envs/wrapper/base.py:97-150) for every robot of the handle, on the device ----
+ * The reference's policy never sees one frame: it sees the last image_batch sensor maps, the last state_batch vector states and
+ * the last max(laser_batch, 1) laser scans of the current episode, zero-padded at the episode's start.  With stacks enabled the
+ * library keeps, for every local robot and every stacked field of depth K, after any call has completed on the stream:
+ *   the call reset the robot's world (imgenv_reset, imgenv_reset_world(s), imgenv_reset_worlds_spawn, the worlds an
+ *   imgenv_step_autoreset / imgenv_step_autoreset_device call restarted):   stack = [0, ..., 0, F]
+ *   otherwise (a step):                                                     stack = [old[1], ..., old[K-1], F]
+ * F = the field's row of imgenv_out after that call, 0 = all-zero bytes; oldest first, newest last, contiguous per robot (the
+ * reference's [n, k, ...] layout, vector states flattened to [n, k * state_dim], base.py:116-136).  A frozen robot's row keeps
+ * repeating its last frame, as the reference pushes it.  One extra kernel launch per chain (csrc/stack.h), none when every depth is
+ * 0 or 1, no host synchronisation, allocation or copy per step.
+ * Depths are the YAML keys: image_batch > 0 stacks the sensor maps, 0 leaves them alone; state_batch likewise; laser_batch >= 0
+ * stacks max(laser_batch, 1) scans, < 0 leaves them alone (base.py:103-105).  No depth may exceed IMGENV_STACK_MAX_DEPTH. */
+#define IMGENV_STACK_MAX_DEPTH 16
+typedef struct imgenv_stack_cfg {
+    int32_t struct_size;          /* sizeof(imgenv_stack_cfg) */
+    int32_t image_batch, state_batch, laser_batch;
+    /* Optional caller-owned DEVICE memory for the stacks (a host framework can alias it zero-copy); size it with
+     * imgenv_stack_bytes(), 256-byte aligned.  NULL = the library allocates (and frees) its own. */
+    void* arena;
+    int64_t arena_bytes;
+} imgenv_stack_cfg;
+/* Device pointers of the stacks, R = robot_end - robot_begin local robots (a robot shard stacks its local rows; nothing crosses
+ * ranks).  Ownership as for imgenv_out: valid until imgenv_destroy(), contents valid once the stream work of the last reset / step
+ * has completed; they are the library's working copies, READ-ONLY for the caller -- the next step's shift reads them back, so
+ * whatever a caller wrote would travel through the stack.  The IMGENV_FLAG_CHECK_OUTPUTS* guards do NOT cover them.  A field of
+ * depth 1 costs nothing: its pointer IS the array imgenv_outputs() hands out ([R][1][...] is the same bytes; with
+ * IMGENV_FLAG_FULL_REWRITE that is the public copy) and it takes no arena space.  Deeper stacks are always fed from the kernels'
+ * private working arrays, also under IMGENV_FLAG_FULL_REWRITE. */
+typedef struct imgenv_stack_out {
+    int32_t struct_size;          /* on entry 0 or sizeof(imgenv_stack_out) */
+    int32_t n_local;              /* R */
+    int32_t image_depth, state_depth, laser_depth; /* effective depths; 0 = the field is not stacked and its pointer is NULL */
+    int32_t reserved_;
+    uint16_t* sensor_maps;        /* [R][image_depth][image_h][image_w]  float16 bits */
+    float* vector_states;         /* [R][state_depth * state_dim] */
+    double* lasers;               /* [R][laser_depth][B]; NULL on a handle without lasers whatever laser_batch says */
+} imgenv_stack_out;
+/* bytes of stack memory a handle created from `cfg` needs for `s`: the sum over the fields of depth >= 2 of
+ * R * depth * frame bytes, each rounded up to 256 (0 when nothing is deeper than 1).  Negative IMGENV_E* code for a bad
+ * configuration or a depth above the cap.  Needs no device, like imgenv_arena_bytes(). */
+int64_t imgenv_stack_bytes(const imgenv_cfg* cfg, const imgenv_stack_cfg* s);
+/* Legal once per handle, after imgenv_create() and before its first reset (IMGENV_ESTATE otherwise); IMGENV_EINVAL for a depth
+ * above the cap or an arena that is too short or misaligned.  `out` (may be NULL) receives the pointers; imgenv_stack_outputs()
+ * hands them out again later.  A handle that never calls it behaves, launch for launch, as if this section did not exist. */
+int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgenv_stack_out* out);
+int imgenv_stack_outputs(imgenv_t* h, imgenv_stack_out* out);
+
 /* The two OpenCV resizes of the path for one-channel 8-bit images, as the library performs them (OpenCV 4.2.0's generic
  * fixed-point CPU path restated, csrc/cv_resize.h): host buffers, no device needed.  kind 0: INTER_LINEAR, 1: INTER_CUBIC. */
 int imgenv_cv_resize_u8(int kind, const uint8_t* src, int32_t sh, int32_t sw, uint8_t* dst, int32_t dh, int32_t dw);

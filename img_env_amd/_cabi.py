@@ -28,6 +28,9 @@ FLAG_FULL_REWRITE = 256   # the outputs are copies rewritten in full by every ca
 FLAG_CHECK_OUTPUTS_FIRST = 1024  # FLAG_CHECK_OUTPUTS for the handle's first 64 calls only (World's default)
 ANGULAR_BINS = 72
 STACK_MAX_DEPTH = 16  # IMGENV_STACK_MAX_DEPTH
+MAPS_KEEP, MAPS_BY_PLACEMENT = 0, 1  # imgenv_maps_policy
+MAP_POLICIES = {"keep": MAPS_KEEP, "placement": MAPS_BY_PLACEMENT}
+EINVAL, ENOMEM, EDEVICE, ESTATE = -1, -2, -3, -4
 
 SHAPES = {"circle": SHAPE_CIRCLE, "rectangle": SHAPE_RECTANGLE, "leg": SHAPE_LEG}
 # Env.msg ped_scene_type strings (scenefactory.h:8-24): anything else is the EmptyScene
@@ -282,7 +285,8 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_kernel_name", "imgenv_comm_unique_id", "imgenv_comm_init", "imgenv_comm_info", "imgenv_reset_world", "imgenv_reset_worlds", "imgenv_spawn",
            "imgenv_reset_worlds_spawn", "imgenv_step_autoreset", "imgenv_step_autoreset_device", "imgenv_autoreset_last",
            "imgenv_world_placement", "imgenv_cv_resize_u8", "imgenv_build_id", "imgenv_step_flags", "imgenv_layer_mode",
-           "imgenv_stack_bytes", "imgenv_stack_enable", "imgenv_stack_outputs")
+           "imgenv_stack_bytes", "imgenv_stack_enable", "imgenv_stack_outputs",
+           "imgenv_maps_add", "imgenv_world_maps_set", "imgenv_maps_policy", "imgenv_map_for_placement", "imgenv_world_maps")
 K_COUNT = 14
 
 
@@ -333,9 +337,20 @@ def bind(lib):
     lib.imgenv_stack_bytes.restype = C.c_int64
     lib.imgenv_stack_enable.argtypes = [C.c_void_p, C.POINTER(StackCfg), C.POINTER(StackOut)]
     lib.imgenv_stack_outputs.argtypes = [C.c_void_p, C.POINTER(StackOut)]
+    lib.imgenv_maps_add.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
+    lib.imgenv_world_maps_set.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
+    lib.imgenv_maps_policy.argtypes = [C.c_void_p, C.c_int32]
+    lib.imgenv_map_for_placement.argtypes = [C.c_uint64, C.c_int32]
+    lib.imgenv_map_for_placement.restype = C.c_int32
+    lib.imgenv_world_maps.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
     lib.imgenv_kernel_name.argtypes = [C.c_int]
     lib.imgenv_kernel_name.restype = C.c_char_p
     return lib
+
+
+def map_for_placement(seed, n_maps):
+    """``imgenv_map_for_placement``: the map an episode placed from ``seed`` runs on under the "placement" policy (needs no GPU)"""
+    return int(load_library().imgenv_map_for_placement(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(n_maps)))
 
 
 def load_library():

@@ -21,12 +21,30 @@ def read_yaml(file):
 def load_map(cfg):
     """The map image in its own pixels: ``imread(map_file, IMREAD_GRAYSCALE)`` of GridMap::read_image (grid_map.cpp:28-38),
     or an in-memory grid given as ``cfg['global_map']['map_array']`` (extension used by the synthetic worlds).  The resize to
-    the view resolution (cv::resize INTER_LINEAR) happens inside ``imgenv_create``."""
+    the view resolution (cv::resize INTER_LINEAR) happens inside ``imgenv_create``.
+
+    ``map_file`` may be a LIST of files and ``map_array`` a 3-D array (or a list of 2-D arrays): the maps of a bank
+    (``imgenv_maps_add``), returned as one ``[n_maps, H, W]`` stack; they must share one size.  A string / 2-D array gives the
+    2-D map, as ever."""
     gm = cfg["global_map"]
-    if gm.get("map_array") is not None:
-        return np.ascontiguousarray(gm["map_array"], np.uint8)
+    arr = gm.get("map_array")
+    if arr is not None:
+        if isinstance(arr, (list, tuple)) and len(arr) and np.ndim(arr[0]) == 2:
+            return _stack_maps([np.ascontiguousarray(m, np.uint8) for m in arr])
+        return np.ascontiguousarray(arr, np.uint8)
+    if isinstance(gm["map_file"], (list, tuple)):
+        return _stack_maps([_read_map(cfg, f) for f in gm["map_file"]])
+    return _read_map(cfg, gm["map_file"])
+
+
+def _stack_maps(maps):
+    if not maps or any(m.shape != maps[0].shape for m in maps):
+        raise ValueError("global_map: the maps of one env must share one size (%s)" % [m.shape for m in maps])
+    return np.ascontiguousarray(np.stack(maps), np.uint8)
+
+
+def _read_map(cfg, path):
     from PIL import Image
-    path = gm["map_file"]
     if not os.path.isabs(path):
         for base in (cfg.get("map_dir"), os.path.join(os.path.dirname(__file__), "maps"), os.getcwd()):
             if base and os.path.exists(os.path.join(base, path)):

@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "world.h"
 #include "stack.h"
+#include "map_bank.h"
 
 static thread_local char g_err[512] = "";
 #define FAIL(code, ...)                              \
@@ -80,7 +81,15 @@ struct imgenv {
     struct StageSegHost { void* dst; const void* src; size_t bytes; };
     std::vector<StageSegHost> segs;  // copies queued for the next stage_flush
     size_t seg_max = 0;
-    uint8_t* d_static_map = nullptr;  // the map every reset starts from
+    uint8_t* d_static_map = nullptr;  // the map every reset starts from; with a bank (imgenv_maps_add) [n_maps][map_stride], map 0 first
+    // map bank (include/imgenv.h: imgenv_maps_add; csrc/map_bank.h)
+    int Hg_in = 0, Wg_in = 0;       // the size of the map as imgenv_create received it (before the load-time resize)
+    int n_maps = 1;
+    size_t map_stride = 0;          // bytes between two maps of the bank
+    int* d_map_cur = nullptr;       // [W] map of each world's current episode (nullptr: no bank)
+    int* d_map_next = nullptr;      // [W] map each world's next reset starts from
+    int maps_policy = 0;            // IMGENV_MAPS_*
+    const int* reset_map_ids = nullptr;  // host-placed resets under BY_PLACEMENT: the maps of the worlds being reset, in list order (for the call in progress)
     struct ObstInstHost { double x, y, sh, ch, cx, cy, r; int m0, m1, n0, n1, shape, world; };
     std::vector<ObstInstHost> oinst;  // obstacles of the reset being staged
     void* d_oinst = nullptr;
@@ -501,6 +510,14 @@ extern "C" void imgenv_destroy(imgenv_t* h) {
     delete h;
 }
 
+// view_big.h's one-byte-per-cell summary of a static map (world.h: crop_map), in 8 x 8 tiles
+static void tile_crop(const uint8_t* map, int Hg, int Wg, uint32_t wt, size_t crop_ws, std::vector<uint8_t>& tiled) {
+    tiled.assign(crop_ws, 0);
+    for (int m = 0; m < Hg; m++)
+        for (int n = 0; n < Wg; n++)
+            tiled[(((size_t)(m >> 3) * wt + (n >> 3)) << 6) | ((m & 7) << 3) | (n & 7)] = map[(size_t)m * Wg + n] >= 250 ? 128 : 0;
+}
+
 // ---------------------------------------------------------------------------------------- create
 extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, int32_t Hg, int32_t Wg,
                              imgenv_t** out) {
@@ -543,6 +560,7 @@ extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, i
     const bool view_resize = cfg->image_size[0] != g.Wv || cfg->image_size[1] != g.Hv;
     // GridMap::read_image (grid_map.cpp:28-38): the image is resized (INTER_LINEAR) to the view resolution
     std::vector<uint8_t> resized_map;
+    int Hg_in = Hg, Wg_in = Wg;
     if (cfg->global_resolution != cfg->view_resolution) {
         const double resolution_ = (double)cfg->global_resolution, view_res = (double)cfg->view_resolution;
         const double w2d = floor(Wg * resolution_ / view_res), h2d = floor(Hg * resolution_ / view_res);  // (range-checked before the cast)
@@ -551,6 +569,8 @@ extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, i
         resized_map.resize((size_t)w2 * h2);
         cv_resize_u8(false, static_map, Hg, Wg, resized_map.data(), h2, w2);
         static_map = resized_map.data();
+        Hg_in = Hg;
+        Wg_in = Wg;
         Hg = h2;
         Wg = w2;
         // the kernels index the worlds' copies of a layer with 32 bits: checked again on the grid the handle really works on
@@ -573,6 +593,9 @@ extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, i
     h->RL = r1 - r0;
     h->Hg = Hg;
     h->Wg = Wg;
+    h->Hg_in = Hg_in;
+    h->Wg_in = Wg_in;
+    h->map_stride = ((size_t)Hg * Wg + 15) & ~(size_t)15;
     h->W = W;
     h->Rw = h->R / W;
     h->Pw = h->P / W;
@@ -892,10 +915,8 @@ extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, i
                         FAIL(IMGENV_EINVAL, "internal: row of cell %llu by multiply-shift", cl);
                     }
                 }
-            std::vector<uint8_t> tiled((size_t)d.crop_ws, 0);
-            for (int m = 0; m < Hg; m++)
-                for (int n = 0; n < Wg; n++)
-                    tiled[(((size_t)(m >> 3) * wt + (n >> 3)) << 6) | ((m & 7) << 3) | (n & 7)] = static_map[(size_t)m * Wg + n] >= 250 ? 128 : 0;
+            std::vector<uint8_t> tiled;
+            tile_crop(static_map, Hg, Wg, wt, (size_t)d.crop_ws, tiled);
             uint8_t* sc = nullptr;
             TRY(dev_alloc(h, &sc, (size_t)d.crop_ws));
             HIPCHK_H(hipMemcpy(sc, tiled.data(), tiled.size(), hipMemcpyHostToDevice));
@@ -1855,6 +1876,7 @@ struct ResetArgs {
     const double* ped3;
     int n_robots, n_peds, whole;
     int stamp;  // STAMP mode: the class layer gets its base classes here too (k_reset_obstacles keeps it in step)
+    MapSel maps;  // map bank: which map of static_map[n_maps][stride] each world starts from (csrc/map_bank.h)
 };
 static int stage_begin(imgenv* h) {
     h->gen = (h->gen + 1) % imgenv::STAGE_GENS;
@@ -1951,10 +1973,19 @@ __global__ __launch_bounds__(256) void k_reset_apply(DevWorld w, ResetArgs a) {
     if (b < a.n_worlds * MAP_BLOCKS) {
         const int q = b / MAP_BLOCKS, world = a.list ? a.list[q] : q;
         const size_t n16 = ((size_t)w.Hg * w.Wg + 15) / 16;  // (both buffers are padded to 16 bytes)
+        int map_id = 0;
+        if (a.maps.cur) {  // the world's map of the bank: what imgenv_world_maps_set chose, or the host's draw for this placement
+            map_id = a.maps.ids ? a.maps.ids[q] : a.maps.next[world];
+            if (b == q * MAP_BLOCKS && threadIdx.x == 0) {  // (no block of this launch reads what this writes)
+                a.maps.cur[world] = map_id;
+                if (a.maps.ids) a.maps.next[world] = map_id;
+            }
+        }
+        const uint4* bank = (const uint4*)(a.static_map + (size_t)map_id * a.maps.stride);
         uint4* dst = (uint4*)(const_cast<uint8_t*>(w.obs_map) + (size_t)world * w.Gs);
         uint4* cls = (uint4*)(w.cell + (size_t)world * w.Gs);
         for (size_t e = (size_t)(b - q * MAP_BLOCKS) * blockDim.x + threadIdx.x; e < n16; e += (size_t)MAP_BLOCKS * blockDim.x) {
-            const uint4 v = ((const uint4*)a.static_map)[e];
+            const uint4 v = bank[e];
             dst[e] = v;
             if (a.stamp) {  // base class of 16 cells, no stamp (2, SUM mode: the counts on the cells stay -- their owners take them off)
                 const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
@@ -1973,7 +2004,7 @@ __global__ __launch_bounds__(256) void k_reset_apply(DevWorld w, ResetArgs a) {
             }
         }
         if (w.crop_map) {  // view_big.h's one-byte-per-cell summary of the map starts over with it
-            const uint4* src = (const uint4*)w.static_crop;
+            const uint4* src = (const uint4*)(w.static_crop + (size_t)map_id * w.crop_ws);
             uint4* cm = (uint4*)(w.crop_map + (size_t)world * w.crop_ws);
             for (size_t e = (size_t)(b - q * MAP_BLOCKS) * blockDim.x + threadIdx.x; e < w.crop_ws / 16; e += (size_t)MAP_BLOCKS * blockDim.x) cm[e] = src[e];
         }
@@ -2313,6 +2344,14 @@ static int reset_blocks(imgenv* h, int n, const int* list) {
     return 0;
 }
 
+static MapSel map_sel(const imgenv* h) {
+    MapSel m;
+    m.cur = h->d_map_cur; m.next = h->d_map_next; m.ids = nullptr;
+    m.stride = h->map_stride; m.n_maps = h->n_maps;
+    m.by_placement = h->maps_policy == IMGENV_MAPS_BY_PLACEMENT && h->n_maps > 1 ? 1 : 0;
+    return m;
+}
+
 static int sfm_ahead_drop(imgenv* h, hipStream_t st);
 static int reset_launch(imgenv* h, const int* list, int n, hipStream_t st, int whole) {
     DevWorld& d = h->d;
@@ -2361,6 +2400,13 @@ static int reset_launch(imgenv* h, const int* list, int n, hipStream_t st, int w
         a.list = h->pin_list;
         a.n_worlds = d.act_nw;
         a.static_map = h->d_static_map;
+        a.maps = map_sel(h);
+        if (h->d_map_cur && h->reset_map_ids) {
+            unsigned char* ids = nullptr;
+            RTRY(stage_room(h, sizeof(int) * (size_t)d.act_nw, &ids));
+            memcpy(ids, h->reset_map_ids, sizeof(int) * (size_t)d.act_nw);
+            a.maps.ids = (const int*)ids;
+        }
         a.rob3 = h->pin_rob3;
         a.rr = (const ResetRobot*)h->pin_rr;
         a.ped3 = h->pin_ped3;
@@ -2518,11 +2564,153 @@ extern "C" int imgenv_reset_worlds_spawn(imgenv_t* h, int32_t n, const int32_t* 
         if (const char* why = spawn_world(*cfg, seeds[q], outs[q])) FAIL(IMGENV_EINVAL, "spawn of world %d: %s", worlds[q], why);
         batches[q] = outs[q].batch;
     }
-    return imgenv_reset_worlds(h, n, worlds, batches.data(), stream);
+    std::vector<int> ids;
+    if (h->d_map_cur && h->maps_policy == IMGENV_MAPS_BY_PLACEMENT) {  // the placement's seed also draws the map
+        for (int q = 0; q < n; q++) ids.push_back(map_for_placement(seeds[q], h->n_maps));
+        h->reset_map_ids = ids.data();
+    }
+    const int rc = imgenv_reset_worlds(h, n, worlds, batches.data(), stream);
+    h->reset_map_ids = nullptr;
+    return rc;
 }
 
 extern "C" int imgenv_reset_world(imgenv_t* h, int32_t world, const imgenv_reset_batch* b, void* stream) {
     return imgenv_reset_worlds(h, 1, &world, b, stream);
+}
+
+// ---------------------------------------------------------------------------------------- map bank
+extern "C" int32_t imgenv_map_for_placement(uint64_t seed, int32_t n_maps) { return map_for_placement(seed, n_maps); }
+
+extern "C" int imgenv_maps_add(imgenv_t* h, int32_t n, const uint8_t* maps, int32_t Hg, int32_t Wg) {
+    if (!h || !maps || n < 1) FAIL(IMGENV_EINVAL, "null argument or no maps");
+    if (h->n_maps > 1) FAIL(IMGENV_ESTATE, "imgenv_maps_add has already been called on this handle");
+    bool any_reset = h->has_reset;
+    for (char r : h->world_ready) any_reset = any_reset || r;
+    if (any_reset) FAIL(IMGENV_ESTATE, "imgenv_maps_add after the first reset");
+    if (h->RL != h->R) FAIL(IMGENV_EINVAL, "imgenv_maps_add on a robot shard is not supported");
+    if (Hg != h->Hg_in || Wg != h->Wg_in)
+        FAIL(IMGENV_EINVAL, "maps of %d x %d pixels, the handle was created with %d x %d: one size per handle", Hg, Wg, h->Hg_in, h->Wg_in);
+    if (n > (1 << 20)) FAIL(IMGENV_EINVAL, "too many maps");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const int n_maps = n + 1, W = h->W;
+    const size_t G = (size_t)h->Hg * h->Wg, G_in = (size_t)Hg * Wg, stride = h->map_stride;
+    const bool resize = h->Hg != Hg || h->Wg != Wg || h->cfg.global_resolution != h->cfg.view_resolution;
+    DevWorld& d = h->d;
+    // everything is allocated and filled before the handle changes: a failure leaves it on its one map
+    uint8_t* bank = nullptr;
+    uint8_t* crops = nullptr;
+    int *cur = nullptr, *next = nullptr;
+    auto undo = [&]() { dev_free(h, bank); dev_free(h, crops); dev_free(h, cur); dev_free(h, next); };
+#define MTRY(expr, code)                                                          \
+    do {                                                                          \
+        if (int rc_ = (expr)) { undo(); return (code) ? (code) : rc_; }           \
+    } while (0)
+#define MHIP(expr)                                                                                          \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess) {                                                                             \
+            snprintf(g_err, sizeof(g_err), "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+            undo();                                                                                         \
+            return e_ == hipErrorOutOfMemory ? IMGENV_ENOMEM : IMGENV_EDEVICE;                              \
+        }                                                                                                   \
+    } while (0)
+    {
+        void* p = nullptr;
+        if (hipMalloc(&p, stride * (size_t)n_maps) != hipSuccess) FAIL(IMGENV_ENOMEM, "no device memory for a bank of %d maps", n_maps);
+        h->allocs.push_back(p);
+        bank = (uint8_t*)p;
+    }
+    MHIP(hipMemset(bank, 0, stride * (size_t)n_maps));
+    MHIP(hipMemcpy(bank, h->d_static_map, stride, hipMemcpyDeviceToDevice));  // map 0: the map of imgenv_create
+    if (d.crop_map) {
+        void* p = nullptr;
+        if (hipMalloc(&p, (size_t)d.crop_ws * n_maps) != hipSuccess) {
+            undo();
+            FAIL(IMGENV_ENOMEM, "no device memory for the crop images of %d maps", n_maps);
+        }
+        h->allocs.push_back(p);
+        crops = (uint8_t*)p;
+        MHIP(hipMemcpy(crops, d.static_crop, (size_t)d.crop_ws, hipMemcpyDeviceToDevice));
+    }
+    std::vector<uint8_t> resized, tiled;
+    for (int k = 0; k < n; k++) {
+        const uint8_t* src = maps + (size_t)k * G_in;
+        if (resize) {  // GridMap::read_image (grid_map.cpp:28-38), as imgenv_create does for the first map
+            resized.resize(G);
+            cv_resize_u8(false, src, Hg, Wg, resized.data(), h->Hg, h->Wg);
+            src = resized.data();
+        }
+        MHIP(hipMemcpy(bank + (size_t)(k + 1) * stride, src, G, hipMemcpyHostToDevice));
+        if (crops) {
+            tile_crop(src, h->Hg, h->Wg, d.crop_wt, (size_t)d.crop_ws, tiled);
+            MHIP(hipMemcpy(crops + (size_t)(k + 1) * d.crop_ws, tiled.data(), tiled.size(), hipMemcpyHostToDevice));
+        }
+    }
+    MTRY(dev_alloc(h, &cur, (size_t)W), IMGENV_ENOMEM);   // (zeroed: every world starts on map 0)
+    MTRY(dev_alloc(h, &next, (size_t)W), IMGENV_ENOMEM);
+#undef MTRY
+#undef MHIP
+    // (nothing has been launched on this handle yet -- no reset has happened -- so the single-map buffers can go)
+    dev_free(h, h->d_static_map);
+    h->d_static_map = bank;
+    if (crops) {
+        uint8_t* old = const_cast<uint8_t*>(d.static_crop);
+        dev_free(h, old);
+        d.static_crop = crops;
+    }
+    h->d_map_cur = cur;
+    h->d_map_next = next;
+    h->n_maps = n_maps;
+    return IMGENV_OK;
+}
+
+// next[worlds[q]] = ids[q], from page-locked host memory
+__global__ void k_maps_select(int* __restrict__ next, const int* __restrict__ worlds, const int* __restrict__ ids, int n) {
+    const int q = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (q < n) next[worlds[q]] = ids[q];
+}
+
+extern "C" int imgenv_world_maps_set(imgenv_t* h, int32_t n, const int32_t* worlds, const int32_t* map_ids, void* stream) {
+    if (!h || n < 0 || (n > 0 && (!worlds || !map_ids))) FAIL(IMGENV_EINVAL, "null argument");
+    std::vector<char> seen(h->W, 0);
+    for (int q = 0; q < n; q++) {  // everything is checked before anything is applied
+        if (worlds[q] < 0 || worlds[q] >= h->W) FAIL(IMGENV_EINVAL, "world %d out of range (n_worlds %d)", worlds[q], h->W);
+        if (seen[worlds[q]]) FAIL(IMGENV_EINVAL, "world %d listed twice", worlds[q]);
+        seen[worlds[q]] = 1;
+        if (map_ids[q] < 0 || map_ids[q] >= h->n_maps) FAIL(IMGENV_EINVAL, "map %d out of range (the handle holds %d)", map_ids[q], h->n_maps);
+    }
+    if (n == 0 || !h->d_map_next) return IMGENV_OK;  // (one map: every id is 0)
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    RTRY(stage_begin(h));
+    unsigned char* p = nullptr;
+    RTRY(stage_room(h, sizeof(int) * 2 * (size_t)n, &p));
+    int* pin = (int*)p;
+    memcpy(pin, worlds, sizeof(int) * (size_t)n);
+    memcpy(pin + n, map_ids, sizeof(int) * (size_t)n);
+    k_maps_select<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(h->d_map_next, pin, pin + n, n);
+    HIPCHK(hipGetLastError());
+    return stage_end(h, st);
+}
+
+extern "C" int imgenv_maps_policy(imgenv_t* h, int32_t policy) {
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (policy != IMGENV_MAPS_KEEP && policy != IMGENV_MAPS_BY_PLACEMENT) FAIL(IMGENV_EINVAL, "unknown map policy %d", policy);
+    h->maps_policy = policy;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_world_maps(imgenv_t* h, int32_t* map_ids, void* stream) {
+    if (!h || !map_ids) FAIL(IMGENV_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    if (int rc = check_device_flags(h)) return rc;
+    if (!h->d_map_cur) {
+        for (int k = 0; k < h->W; k++) map_ids[k] = 0;
+        return IMGENV_OK;
+    }
+    HIPCHK(hipMemcpy(map_ids, h->d_map_cur, sizeof(int) * (size_t)h->W, hipMemcpyDeviceToHost));
+    return IMGENV_OK;
 }
 
 // ---------------------------------------------------------------------------------------- step
@@ -2834,7 +3022,13 @@ extern "C" int imgenv_step_autoreset(imgenv_t* h, const float* actions, const im
         for (int q = 0; q < n; q++) batches[q] = use[q]->batch;
         h->spawn_ahead_n = std::min(256, std::max(8, 2 * n));  // twice what this step needed
         if (trace) tp[3] = std::chrono::steady_clock::now();
+        std::vector<int> ids;
+        if (h->d_map_cur && h->maps_policy == IMGENV_MAPS_BY_PLACEMENT) {  // the placement's seed also draws the map
+            for (int q = 0; q < n; q++) ids.push_back(map_for_placement(seed0 + (uint64_t)q, h->n_maps));
+            h->reset_map_ids = ids.data();
+        }
         rc = imgenv_reset_worlds(h, n, worlds.data(), batches.data(), stream);
+        h->reset_map_ids = nullptr;
         if (rc == IMGENV_OK) {
             *n_out = n;
             for (int q = 0; q < n && worlds_out && q < cap; q++) worlds_out[q] = worlds[q];
@@ -3065,13 +3259,14 @@ static int autoreset_device_chain(imgenv* h, const float* actions, hipStream_t s
     // (also the set-up's fill, which runs on the side stream whatever this call's fill_due was: k_respawn must not meet half-drawn slots)
     if (h->fill_pending) HIPCHK(hipStreamWaitEvent(st, h->ev_fill, 0));
     h->fill_pending = false;
-    k_respawn<<<dim3(W), dim3(WAVE), 0, st>>>(d, c, h->elapsed);
+    const MapSel maps = map_sel(h);
+    k_respawn<<<dim3(W), dim3(WAVE), 0, st>>>(d, c, h->elapsed, maps);
     // grids for a guess of the finished worlds (four times the last count; the kernels stride over the rest if there are more)
     const int last_n = h->finished_host[0];  // (page-locked, written by k_finished_dev: stale by a step or two)
     const int guess = std::min(W, std::max(16, 4 * std::max(last_n, 0)));
     const int restore_blocks = 4 * MAP_BLOCKS;  // per world
-    if (h->pow2) k_restore_maps_dev<true><<<dim3((unsigned)(guess * restore_blocks)), dim3(256), 0, st>>>(d, c, h->d_static_map, h->stamp ? 1 : h->sum ? 2 : 0, restore_blocks);
-    else k_restore_maps_dev<false><<<dim3((unsigned)(guess * restore_blocks)), dim3(256), 0, st>>>(d, c, h->d_static_map, h->stamp ? 1 : h->sum ? 2 : 0, restore_blocks);
+    if (h->pow2) k_restore_maps_dev<true><<<dim3((unsigned)(guess * restore_blocks)), dim3(256), 0, st>>>(d, c, h->d_static_map, maps, h->stamp ? 1 : h->sum ? 2 : 0, restore_blocks);
+    else k_restore_maps_dev<false><<<dim3((unsigned)(guess * restore_blocks)), dim3(256), 0, st>>>(d, c, h->d_static_map, maps, h->stamp ? 1 : h->sum ? 2 : 0, restore_blocks);
     if (nob > 0) {
         const int parts = 4;
         if (h->pow2) k_reset_obstacles<true><<<dim3((unsigned)(guess * nob * parts)), dim3(256), 0, st>>>(d, c.inst_out, h->stamp ? 1 : h->sum ? 2 : 0, c.fin_n, nob, parts, c.w_inst, c.w_inst_valid);

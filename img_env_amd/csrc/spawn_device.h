@@ -614,7 +614,7 @@ __global__ __launch_bounds__(1024) void k_finished_dev(DevWorld w, SpawnDev c) {
 }
 
 // The q-th finished world receives its placement: what stage_world + k_reset_apply do for a host-made batch.
-__global__ __launch_bounds__(WAVE) void k_respawn(DevWorld w, SpawnDev c, int elapsed) {
+__global__ __launch_bounds__(WAVE) void k_respawn(DevWorld w, SpawnDev c, int elapsed, MapSel maps) {
     const int q = blockIdx.x;
     if (q >= *c.fin_n) return;
     const int world = c.fin_list[q], tid = threadIdx.x;
@@ -632,6 +632,18 @@ __global__ __launch_bounds__(WAVE) void k_respawn(DevWorld w, SpawnDev c, int el
     const int nr = c.n_robots, np = c.n_peds, na = nr + np;
     const SlotAgent* ag = c.s_agents + (size_t)s * na;
     if (tid == 0) c.place_serial[world] = n;
+    if (maps.cur && tid == 0) {
+        // The world's map of the bank (csrc/map_bank.h): drawn from the placement's seed (IMGENV_MAPS_BY_PLACEMENT) or what
+        // imgenv_world_maps_set chose.  The map restore behind this launch reads cur[]; its shortcut -- only the old obstacles'
+        // cells go back -- holds for a world that stays on its map, so a world that changes map loses it here and takes the
+        // full-map path (k_reset_obstacles then records the new obstacles and gives the shortcut back for the next reset).
+        const int id = maps.by_placement ? map_for_placement(c.seed0 + n, maps.n_maps) : maps.next[world];
+        if (id != maps.cur[world]) {
+            maps.cur[world] = id;
+            c.w_inst_valid[world] = 0;
+        }
+        maps.next[world] = id;
+    }
     for (int e = tid; e < c.n_obstacles; e += WAVE) c.place_obst[(size_t)world * c.n_obstacles + e] = c.s_obst[(size_t)s * c.n_obstacles + e];
     for (int a = tid; a < na; a += WAVE) {
         const SlotAgent o = ag[a];
@@ -730,7 +742,7 @@ __global__ __launch_bounds__(WAVE) void k_respawn(DevWorld w, SpawnDev c, int el
 // stamps of the old episode stay on the class layer and expire with their step tags as always.  map_blocks blocks per world,
 // sized for every world of the handle.
 template <bool POW2>
-__global__ __launch_bounds__(256) void k_restore_maps_dev(DevWorld w, SpawnDev c, const uint8_t* __restrict__ static_map, int stamp, int map_blocks) {
+__global__ __launch_bounds__(256) void k_restore_maps_dev(DevWorld w, SpawnDev c, const uint8_t* __restrict__ bank, MapSel maps, int stamp, int map_blocks) {
     // (the grid covers a guess of the number of finished worlds, not every world of the handle: a block whose world does not
     // exist still costs the dispatcher its nanosecond -- 65 536 of them were most of this kernel's 30 us at 2048 envs)
     const int q0 = blockIdx.x / map_blocks, part = blockIdx.x - q0 * map_blocks, q_stride = (int)gridDim.x / map_blocks;
@@ -739,6 +751,8 @@ __global__ __launch_bounds__(256) void k_restore_maps_dev(DevWorld w, SpawnDev c
         if (c.place_serial[world] != c.consumed[1] + (unsigned long long)q) continue;  // k_respawn could not place it: the old episode's map stays
         uint8_t* map = const_cast<uint8_t*>(w.obs_map) + (size_t)world * w.Gs;
         uint32_t* cell = w.cell + (size_t)world * w.Gs;
+        const int map_id = maps.cur ? maps.cur[world] : 0;  // (k_respawn, in front of this launch, has set it)
+        const uint8_t* __restrict__ static_map = bank + (size_t)map_id * maps.stride;
         if (c.w_inst_valid[world]) {
             const double resolution = 0.01;
             for (int e = 0; e < c.n_obstacles; e++) {
@@ -770,7 +784,7 @@ __global__ __launch_bounds__(256) void k_restore_maps_dev(DevWorld w, SpawnDev c
             continue;
         }
         if (w.crop_map) {
-            const uint4* src = (const uint4*)w.static_crop;
+            const uint4* src = (const uint4*)(w.static_crop + (size_t)map_id * w.crop_ws);
             uint4* cm = (uint4*)(w.crop_map + (size_t)world * w.crop_ws);
             for (size_t e = (size_t)part * blockDim.x + threadIdx.x; e < w.crop_ws / 16; e += (size_t)map_blocks * blockDim.x) cm[e] = src[e];
         }

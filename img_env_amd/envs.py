@@ -146,7 +146,7 @@ class ImageEnv(Env):
         self.ped_image_size = tuple(cfg["ped_image_size"])
         self.world = World(self.params, self.grid, device=cfg.get("device", 0))
         self.env_pose = spawn.EnvPos(cfg, seed=cfg.get("seed"))
-        self._extent = max(self.grid.shape) * float(cfg["global_map"]["resolution"])
+        self._extent = max(self.grid.shape[-2:]) * float(cfg["global_map"]["resolution"])
         self.dones = None
         self._zeros_info = None
 
@@ -184,6 +184,11 @@ class ImageEnv(Env):
         # copies, like the reference's `deepcopy(self.dones)`: the library's buffers are rewritten in place by the next
         # step -- or by the reset NeverStopWrapper issues inside this very step() call
         return self._state(), o["base_rewards"].clone(), o["base_dones"].clone(), {"dones_info": self._zeros_info}
+
+    def set_map(self, i):
+        """With several maps (``global_map.map_file`` a list): the env runs on map ``i`` from its next ``reset()`` on; it starts
+        on map 0."""
+        self.world.set_world_maps([0], [int(i)])
 
     def end_ep(self, robot_res=None):
         """yaml_env.py:379-390: episode recording is out of scope; kept for API compatibility"""

@@ -35,7 +35,8 @@ class VecImageEnv:
     their rows of the returned state are already the new episode's first observation, as with NeverStopWrapper).
     """
 
-    def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False):
+    def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False,
+                 map_policy="keep", world_maps=None):
         import torch
         from .world import World
         self.cfg = cfg
@@ -61,13 +62,31 @@ class VecImageEnv:
         # device-side resets number their placements seed0 + k on their own: a stream 2^63 away from the host-side resets'
         # (_spawn_seed + episodes so far), so that an env reset by the host never replays an episode the device handed out
         self._device_seed0 = (self._spawn_seed + (1 << 63)) & 0xFFFFFFFFFFFFFFFF
-        self._extent = max(self.grid.shape) * float(cfg["global_map"]["resolution"])
+        self._extent = max(self.grid.shape[-2:]) * float(cfg["global_map"]["resolution"])
         if not cfg.get("keep_view_maps", False):
             # ImageState has no full-size view: where the view is shrunk into the sensor_map (the shipped 400 x 400 -> 48 x 48)
             # the library then only evaluates the view cells the shrink reads (IMGENV_FLAG_NO_VIEW_MAPS)
             self.params["flags"] = int(self.params.get("flags", 0)) | _cabi.FLAG_NO_VIEW_MAPS
         self.world = World(stack_params(self.params, self.env_num), self.grid, device=cfg.get("device", 0))
         self._all_down = self.world.out["step_all_down"].view(torch.bool) if native_spawn else None
+        # Several maps (global_map.map_file a list, map_array 3-D): the maps of the handle's bank.  world_maps[k] is the map env k
+        # starts on; None spreads them k % n_maps -- the reference's layout of several YAMLs with env_num envs each
+        # (create_launch.py:57-65).  map_policy "keep": an env stays on its map until set_world_maps moves it; "placement": every
+        # new episode draws its map with its placement (imgenv_maps_policy), which needs the placements to be drawn inside the
+        # library (native_spawn or device_reset).
+        if map_policy not in _cabi.MAP_POLICIES:
+            raise ValueError("map_policy: keep | placement")
+        if map_policy == "placement" and not self.native_spawn:
+            raise ValueError('map_policy="placement" needs native_spawn=True or device_reset=True')
+        self.n_maps = self.world.n_maps
+        self.map_policy = map_policy
+        if world_maps is None:
+            world_maps = [k % self.n_maps for k in range(self.env_num)]
+        if len(world_maps) != self.env_num:
+            raise ValueError("world_maps: one map id per env")
+        if self.n_maps > 1 or any(int(m) != 0 for m in world_maps):
+            self.world.set_world_maps(range(self.env_num), world_maps)
+        self.world.set_maps_policy(map_policy)
         # stack: StateBatchWrapper (base.py:97-150) inside the library, per env (imgenv_stack_enable): every state handed out
         # carries each robot's last cfg["image_batch"] sensor maps, cfg["state_batch"] vector states and
         # max(cfg["laser_batch"], 1) laser scans of its env's current episode, zero-padded after the env's reset -- whoever reset it,
@@ -161,6 +180,14 @@ class VecImageEnv:
                 self.reset_envs(finished)
                 info["reset_envs"] = finished
         return self._state(), rewards, dones, info
+
+    def world_maps(self):
+        """the map each env's current episode runs on (numpy int32 ``[env_num]``); synchronises the stream"""
+        return self.world.world_maps()
+
+    def set_world_maps(self, envs, ids):
+        """env ``envs[q]`` moves to map ``ids[q]`` at its next reset"""
+        self.world.set_world_maps(envs, ids)
 
     def end_ep(self, robot_res=None):
         return True

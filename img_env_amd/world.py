@@ -52,7 +52,17 @@ class World:
         elif guard == "first" and not int(self.params.get("flags", 0)) & (_cabi.FLAG_CHECK_OUTPUTS | _cabi.FLAG_FULL_REWRITE):
             self.params["flags"] = int(self.params.get("flags", 0)) | _cabi.FLAG_CHECK_OUTPUTS_FIRST
         self.output_guard = guard
-        self.grid = np.ascontiguousarray(grid, np.uint8)
+        # grid: one 2-D map, or a 3-D array / list of equal-shaped 2-D maps -- the first is the map of imgenv_create, the rest
+        # join it in the handle's bank (imgenv_maps_add); every world starts on map 0
+        if isinstance(grid, (list, tuple)) or np.ndim(grid) == 3:
+            maps = [np.ascontiguousarray(m, np.uint8) for m in grid]
+            if not maps or any(m.ndim != 2 or m.shape != maps[0].shape for m in maps):
+                raise ValueError("grid: a 2-D map or a stack of equal-shaped 2-D maps")
+            self.grids = np.ascontiguousarray(np.stack(maps))
+        else:
+            self.grids = np.ascontiguousarray(grid, np.uint8)[None]
+        self.grid = self.grids[0]
+        self.n_maps = len(self.grids)
         cfg, self._keep = _cabi.make_cfg(self.params)
         nbytes = self.lib.imgenv_arena_bytes(C.byref(cfg))
         if nbytes <= 0:
@@ -94,6 +104,41 @@ class World:
         self.robot_end = cfg.robot_end if cfg.robot_end else cfg.n_robots
         self.stack = None  # enable_stack()
         self.stack_arena = None
+        if self.n_maps > 1:
+            rest = self.grids[1:]
+            rc = self.lib.imgenv_maps_add(self.h, len(rest), rest.ctypes.data, rest.shape[1], rest.shape[2])
+            if rc != 0:
+                msg = self.lib.imgenv_last_error().decode()
+                self.close()
+                raise ValueError("imgenv_maps_add: %s" % msg)
+        self._maps_buf = None
+
+    def set_world_maps(self, worlds, ids):
+        """``imgenv_world_maps_set``: world ``worlds[q]`` starts from map ``ids[q]`` of the bank at its next reset of any kind
+        queued after this call; its current episode is untouched.  ValueError (nothing applied) for an id, a world out of range
+        or a world listed twice."""
+        worlds, ids = [int(k) for k in worlds], [int(k) for k in ids]
+        if len(worlds) != len(ids):
+            raise ValueError("one map id per world")
+        n = len(worlds)
+        rc = self.lib.imgenv_world_maps_set(self.h, n, (C.c_int32 * max(n, 1))(*worlds), (C.c_int32 * max(n, 1))(*ids), self._stream())
+        if rc == _cabi.EINVAL:
+            raise ValueError("imgenv_world_maps_set: %s" % self.lib.imgenv_last_error().decode())
+        self._check(rc, "imgenv_world_maps_set")
+
+    def world_maps(self):
+        """``imgenv_world_maps``: the map each world's current episode runs on (numpy int32 ``[n_worlds]``); synchronises the stream"""
+        if self._maps_buf is None:
+            self._maps_buf = (C.c_int32 * self.n_worlds)()
+        self._check(self.lib.imgenv_world_maps(self.h, self._maps_buf, self._stream()), "imgenv_world_maps")
+        return np.array(self._maps_buf[:], np.int32)
+
+    def set_maps_policy(self, name):
+        """``imgenv_maps_policy``: "keep" (``set_world_maps`` alone chooses) or "placement" (every reset that draws its placement
+        from a seed draws the map with it, ``_cabi.map_for_placement(seed, n_maps)`` -- inside the device-side reset chain too)"""
+        if name not in _cabi.MAP_POLICIES:
+            raise ValueError("map policy: keep | placement")
+        self._check(self.lib.imgenv_maps_policy(self.h, _cabi.MAP_POLICIES[name]), "imgenv_maps_policy")
 
     def _check(self, rc, what):
         if rc != 0:

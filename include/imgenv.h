@@ -149,7 +149,8 @@ typedef struct imgenv_cfg {
     int64_t out_arena_bytes;
 
     /* ---- independent worlds in one handle: the reference's env_num processes, batched ---- */
-    /* n_worlds copies of the same map and parameters; n_robots and n_peds are TOTALS (multiples of n_worlds), numbered
+    /* n_worlds copies of the same parameters, every one on the map of imgenv_create (or, with imgenv_maps_add, on the map of a
+     * bank chosen per world and episode); n_robots and n_peds are TOTALS (multiples of n_worlds), numbered
      * world-major: world k owns robots [k n_robots / n_worlds, (k + 1) n_robots / n_worlds) and the same share of the
      * pedestrians.  Robots and pedestrians only ever see their own world.  0 or 1 = a single world.  Each world is reset
      * on its own with imgenv_reset_world(); its time limit counts from its own reset. */
@@ -485,6 +486,48 @@ int64_t imgenv_stack_bytes(const imgenv_cfg* cfg, const imgenv_stack_cfg* s);
  * hands them out again later.  A handle that never calls it behaves, launch for launch, as if this section did not exist. */
 int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgenv_stack_out* out);
 int imgenv_stack_outputs(imgenv_t* h, imgenv_stack_out* out);
+
+/* ---- map bank: several static maps in one handle, one of them per world and episode ----
+ * The reference trains one policy over a set of maps: its trainer is started from several YAML files side by side
+ * (create_launch.py:57-65, one node per (env_name, env_num) pair), each env process loads its own global_map.map_file
+ * (yaml_env.py:163, 203).  Here the maps form a bank inside ONE handle and every world of it runs its current episode on one of
+ * them, so a set of maps still costs one chain of launches per step.  Every world owns its copy of every grid layer and the hot
+ * kernels read only that copy; the bank is read by resets alone.
+ *
+ * imgenv_maps_add: legal once per handle, after imgenv_create() and before its first reset (IMGENV_ESTATE otherwise, also on a
+ * second call).  `maps` is HOST memory [n][Hg][Wg] in the same pixels as the map handed to imgenv_create(); Hg x Wg must equal
+ * that map's size (IMGENV_EINVAL: one grid size per handle -- the world stride, the index divisions and the crop tiling are per
+ * handle).  The bank becomes [create's map, maps[0], ..., maps[n-1]]: map 0 is always the map of imgenv_create(), every world
+ * starts on map 0, and a handle that never selects another map behaves exactly as one without a bank, launch for launch.  Each
+ * added map goes through the same load-time resize as the first (global_resolution != view_resolution) and gets its own image
+ * for the tiled big-view kernels where the handle keeps one.  IMGENV_EINVAL on a robot shard (robot_begin / robot_end not the
+ * whole world): banks in sharded, multi-GPU handles are out of scope.  IMGENV_ENOMEM when the bank cannot be allocated; the
+ * handle is then unchanged. */
+int imgenv_maps_add(imgenv_t* h, int32_t n, const uint8_t* maps, int32_t Hg, int32_t Wg);
+/* World worlds[q] starts from map map_ids[q] at its NEXT reset of any kind queued on `stream` after this call (imgenv_reset,
+ * imgenv_reset_world(s), imgenv_reset_worlds_spawn, the resets inside imgenv_step_autoreset / imgenv_step_autoreset_device);
+ * until then its current episode is untouched.  The choice stays until it is replaced (by this call, or by a draw under
+ * IMGENV_MAPS_BY_PLACEMENT).  Host arrays, copied during the call.  An out-of-range map id, an out-of-range world or a world listed
+ * twice: IMGENV_EINVAL, and nothing is applied.  One small launch; no synchronisation. */
+int imgenv_world_maps_set(imgenv_t* h, int32_t n, const int32_t* worlds, const int32_t* map_ids, void* stream);
+/* Who chooses the map of a new episode.  IMGENV_MAPS_KEEP (the default): imgenv_world_maps_set alone.  IMGENV_MAPS_BY_PLACEMENT:
+ * every reset that draws its placement from a 64-bit seed draws the map with it, map = imgenv_map_for_placement(seed, n_maps) --
+ * on the host for imgenv_reset_worlds_spawn (seeds[q]) and imgenv_step_autoreset (seed0 + k), and INSIDE the device-side reset
+ * chain for imgenv_step_autoreset_device (seed0 + placement number: k_respawn computes it where the placement number is known and
+ * the map restore of the same chain reads it from device memory): no host read-back, no synchronisation, no additional launch --
+ * the map curriculum without the host in the loop.  Such a draw also becomes the world's choice for later resets; resets from
+ * explicit batches (imgenv_reset, imgenv_reset_world(s)) never draw and keep the world's choice.  May be called at any time; takes
+ * effect with the next call that resets.  On a handle with one map it is accepted and changes nothing. */
+#define IMGENV_MAPS_KEEP 0
+#define IMGENV_MAPS_BY_PLACEMENT 1
+int imgenv_maps_policy(imgenv_t* h, int32_t policy);
+/* The draw itself: a pure function, needs no device, exported so that checkers and trainers can reproduce it.  An integer mix of
+ * the seed (splitmix64's finaliser) reduced to [0, n_maps) by multiply-shift of its upper 32 bits: no modulo bias beyond 2^-32, no
+ * floating point -- one definition (csrc/map_bank.h) compiled for host and device, which agree bit for bit.  n_maps <= 1 gives 0. */
+int32_t imgenv_map_for_placement(uint64_t seed, int32_t n_maps);
+/* map_ids[n_worlds]: the map each world's CURRENT episode runs on (all 0 without a bank).  Synchronises `stream`, like
+ * imgenv_autoreset_last(). */
+int imgenv_world_maps(imgenv_t* h, int32_t* map_ids, void* stream);
 
 /* The two OpenCV resizes of the path for one-channel 8-bit images, as the library performs them (OpenCV 4.2.0's generic
  * fixed-point CPU path restated, csrc/cv_resize.h): host buffers, no device needed.  kind 0: INTER_LINEAR, 1: INTER_CUBIC. */

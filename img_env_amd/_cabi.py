@@ -138,6 +138,37 @@ def make_stack_cfg(image_batch, state_batch, laser_batch, arena=None, arena_byte
     return s
 
 
+class EpisodesCfg(C.Structure):
+    _fields_ = [("struct_size", _i32), ("min_steps", _i32), ("dt", _f64)]
+
+
+#: imgenv_episodes_out's arrays: name -> (numpy dtype, rows: 0 = [R], k = [k][R])
+EP_END_BINS, EP_FIGURES, EP_OPEN_F64 = 6, 8, 15
+EP_ENDS = ("arrive", "timeout", "static_collision", "ped_collision", "other_collision", "aborted")  # rows of ``ends``
+EP_FIGURE_NAMES = ("w_variance", "w_zero", "v_acc", "w_acc", "v_jerk", "w_jerk", "v_avg", "w_avg")  # rows of ``figure_sums``
+EP_OPEN_NAMES = ("n", "sum_v", "sum_w", "sum_ww", "sum_absw", "acc_v", "acc_w", "jerk_v", "jerk_w", "prev_v", "prev_w", "prev2_v",
+                 "prev2_w", "w_zero", "ep_return")  # rows of ``open_f64``
+EPISODE_ARRAYS = {
+    "ends": (np.int32, EP_END_BINS), "episodes": (np.int32, 0), "short_episodes": (np.int32, 0), "speed_steps": (np.int32, 0),
+    "arrive_steps": (np.int32, 0), "len_sum": (np.int32, 0), "v_sum": (np.float64, 0), "w_sum": (np.float64, 0),
+    "figure_sums": (np.float64, EP_FIGURES), "return_sum": (np.float64, 0), "last_code": (np.int32, 0), "last_steps": (np.int32, 0),
+    "last_len": (np.int32, 0), "last_episode": (np.int32, 0), "last_return": (np.float64, 0), "open_f64": (np.float64, EP_OPEN_F64),
+    "open_steps": (np.int32, 0), "open_len": (np.int32, 0), "open": (np.int32, 0),
+}
+
+
+class EpisodesOut(C.Structure):
+    _fields_ = [("struct_size", _i32), ("n_local", _i32)] + [(name, C.c_void_p) for name in EPISODE_ARRAYS]
+
+
+def make_episodes_cfg(min_steps, dt):
+    """``imgenv_episodes_cfg``: TestEpisodeWrapper's ``tmp_steps > 3`` (TestEpisodeWrapper.py:48) and ``control_hz`` (:17)"""
+    c = EpisodesCfg()
+    c.struct_size = C.sizeof(EpisodesCfg)
+    c.min_steps, c.dt = int(min_steps), float(dt)
+    return c
+
+
 #: name -> (numpy dtype, shape as a function of the Out header and the world sizes)
 def out_layout(o, n_peds, hp, wp):
     R, B = o.n_local, max(o.n_beams, 1)
@@ -286,6 +317,7 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_reset_worlds_spawn", "imgenv_step_autoreset", "imgenv_step_autoreset_device", "imgenv_autoreset_last",
            "imgenv_world_placement", "imgenv_cv_resize_u8", "imgenv_build_id", "imgenv_step_flags", "imgenv_layer_mode",
            "imgenv_stack_bytes", "imgenv_stack_enable", "imgenv_stack_outputs",
+           "imgenv_episodes_enable", "imgenv_episodes_outputs", "imgenv_episodes_clear",
            "imgenv_maps_add", "imgenv_world_maps_set", "imgenv_maps_policy", "imgenv_map_for_placement", "imgenv_world_maps")
 K_COUNT = 14
 
@@ -337,6 +369,9 @@ def bind(lib):
     lib.imgenv_stack_bytes.restype = C.c_int64
     lib.imgenv_stack_enable.argtypes = [C.c_void_p, C.POINTER(StackCfg), C.POINTER(StackOut)]
     lib.imgenv_stack_outputs.argtypes = [C.c_void_p, C.POINTER(StackOut)]
+    lib.imgenv_episodes_enable.argtypes = [C.c_void_p, C.POINTER(EpisodesCfg), C.POINTER(EpisodesOut)]
+    lib.imgenv_episodes_outputs.argtypes = [C.c_void_p, C.POINTER(EpisodesOut)]
+    lib.imgenv_episodes_clear.argtypes = [C.c_void_p, C.c_void_p]
     lib.imgenv_maps_add.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
     lib.imgenv_world_maps_set.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
     lib.imgenv_maps_policy.argtypes = [C.c_void_p, C.c_int32]

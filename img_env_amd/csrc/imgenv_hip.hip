@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "world.h"
 #include "stack.h"
+#include "episodes.h"
 #include "map_bank.h"
 
 static thread_local char g_err[512] = "";
@@ -188,6 +189,13 @@ struct imgenv {
     bool stack_on = false;       // imgenv_stack_enable has been called
     StackDev stack;              // n_fields == 0: every depth is 0 or 1, nothing to launch
     imgenv_stack_out stack_out;
+    // episode statistics (include/imgenv.h: imgenv_episodes_enable; csrc/episodes.h)
+    bool ep_on = false;          // imgenv_episodes_enable has been called
+    EpisodesDev ep;
+    imgenv_episodes_cfg ep_cfg;
+    imgenv_episodes_out ep_out;
+    size_t ep_clear_bytes = 0;   // what imgenv_episodes_clear zeroes, from ep.f on
+    const float* ep_actions = nullptr;  // the actions of the step in progress (the caller keeps them until the chain's end)
     bool chain_open = false;  // a chain of launches that hands over through tail_sig / tail_cnt has started and not been completed
     std::vector<RvoObstacles> rvos;  // one obstacle set per world
     int sfm_cap_obs = 0;
@@ -1830,6 +1838,20 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
         else k_stack<false><<<dim3(blocks), dim3(STACK_BLOCK), 0, st>>>(sd);
         h->launches += 1;
     }
+    if (h->ep_on) {
+        // the episode statistics (episodes.h), in the same place: a step's command, reward and is_clean go into every local robot's
+        // open episode, a reset chain folds the episodes of the robots it covers by the last step's dones_info (grid as for k_stack)
+        EpisodesDev ed = h->ep;
+        ed.actions = h->ep_actions;
+        ed.list = is_reset ? d.act_list : nullptr;
+        ed.n_dev = is_reset ? d.act_n_dev : nullptr;
+        ed.n_worlds = d.act_nw;
+        const size_t rows = ed.list ? (size_t)(ed.n_dev ? std::min(d.act_nw * h->Rw, std::max(h->act_hint, h->Rw)) : d.act_nw * h->Rw) : (size_t)h->RL;
+        const unsigned blocks = (unsigned)std::min<size_t>(EP_MAX_BLOCKS, std::max<size_t>(1, (rows + EP_BLOCK - 1) / EP_BLOCK));
+        if (is_reset) k_episodes<true><<<dim3(blocks), dim3(EP_BLOCK), 0, st>>>(ed);
+        else k_episodes<false><<<dim3(blocks), dim3(EP_BLOCK), 0, st>>>(ed);
+        h->launches += 1;
+    }
     HIPCHK(hipGetLastError());
     h->chain_open = false;
     return outputs_seal(h, st);
@@ -2768,6 +2790,7 @@ extern "C" int imgenv_step_begin(imgenv_t* h, const float* actions, void* stream
     // (from here on the step's own kernels write output arrays; the chain's end seals them again.  A step that is begun and never
     // ended -- the caller's exchange failed -- must not read as "the caller wrote into imgenv_out" at the reset that recovers it)
     h->guard_sealed = false;
+    h->ep_actions = actions;
     DevWorld& d = h->d;
     h->launches = 0;
     // _step_ped_normal (img_env.cpp:304-359): the ORCA solve for this step ran on the side stream during the previous
@@ -3539,6 +3562,71 @@ extern "C" int imgenv_stack_outputs(imgenv_t* h, imgenv_stack_out* out) {
     if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
     if (!h->stack_on) FAIL(IMGENV_ESTATE, "imgenv_stack_enable was not called");
     *out = h->stack_out;
+    return IMGENV_OK;
+}
+
+// ---- episode statistics (include/imgenv.h; the kernel is csrc/episodes.h) ----
+static_assert(EPF_OPEN_ROWS == IMGENV_EP_OPEN_F64 && EPI_EPISODES - EPI_ENDS0 == IMGENV_EP_END_BINS && EPF_RETURN_SUM - EPF_FIG0 == IMGENV_EP_FIGURES,
+              "episodes.h rows against include/imgenv.h");
+extern "C" int imgenv_episodes_enable(imgenv_t* h, const imgenv_episodes_cfg* c, imgenv_episodes_out* out) {
+    // (the cfg first: its refusals need no handle, and so no device)
+    if (!c) FAIL(IMGENV_EINVAL, "null argument");
+    if (c->struct_size != (int32_t)sizeof(imgenv_episodes_cfg))
+        FAIL(IMGENV_EINVAL, "imgenv_episodes_cfg.struct_size %d (this library's is %d)", c->struct_size, (int)sizeof(imgenv_episodes_cfg));
+    if (out && out->struct_size != 0 && out->struct_size != (int32_t)sizeof(imgenv_episodes_out)) FAIL(IMGENV_EINVAL, "imgenv_episodes_out.struct_size");
+    if (!(c->dt > 0.0) || !std::isfinite(c->dt)) FAIL(IMGENV_EINVAL, "imgenv_episodes_cfg.dt must be > 0 (the YAML's control_hz)");
+    if (c->min_steps < 0) FAIL(IMGENV_EINVAL, "imgenv_episodes_cfg.min_steps must be >= 0");
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (h->ep_on) {
+        if (c->min_steps != h->ep_cfg.min_steps || c->dt != h->ep_cfg.dt)
+            FAIL(IMGENV_EINVAL, "imgenv_episodes_enable: the handle already keeps statistics with min_steps %d, dt %g", h->ep_cfg.min_steps, h->ep_cfg.dt);
+        if (out) *out = h->ep_out;
+        return IMGENV_OK;
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t RL = (size_t)h->RL, f_bytes = sizeof(double) * EPF_ROWS * RL, i_bytes = sizeof(int32_t) * EPI_ROWS * RL;
+    unsigned char* base = nullptr;
+    RTRY(dev_alloc(h, &base, f_bytes + i_bytes));  // (zeroed: no episode open)
+    EpisodesDev e;
+    memset(&e, 0, sizeof(e));
+    e.f = (double*)base;
+    e.i = (int32_t*)(base + f_bytes);
+    e.step_rewards = h->out.step_rewards;  // (the working arena, also under IMGENV_FLAG_FULL_REWRITE)
+    e.step_is_clean = h->out.step_is_clean;
+    e.step_dones_info = h->out.step_dones_info;
+    e.dt = c->dt;
+    e.min_steps = c->min_steps;
+    e.RL = h->RL; e.r0 = h->r0; e.Rw = h->Rw;
+    h->ep = e;
+    h->ep_cfg = *c;
+    h->ep_clear_bytes = f_bytes + sizeof(int32_t) * EPI_CLEARED_ROWS * RL;
+    imgenv_episodes_out& o = h->ep_out;
+    memset(&o, 0, sizeof(o));
+    o.struct_size = (int32_t)sizeof(imgenv_episodes_out);
+    o.n_local = h->RL;
+    o.ends = e.i + EPI_ENDS0 * RL; o.episodes = e.i + EPI_EPISODES * RL; o.short_episodes = e.i + EPI_SHORT * RL;
+    o.speed_steps = e.i + EPI_SPEED_STEPS * RL; o.arrive_steps = e.i + EPI_ARRIVE_STEPS * RL; o.len_sum = e.i + EPI_LEN_SUM * RL;
+    o.v_sum = e.f + EPF_V_SUM * RL; o.w_sum = e.f + EPF_W_SUM * RL; o.figure_sums = e.f + EPF_FIG0 * RL; o.return_sum = e.f + EPF_RETURN_SUM * RL;
+    o.last_code = e.i + EPI_LAST_CODE * RL; o.last_steps = e.i + EPI_LAST_STEPS * RL; o.last_len = e.i + EPI_LAST_LEN * RL;
+    o.last_episode = e.i + EPI_LAST_EPISODE * RL; o.last_return = e.f + EPF_LAST_RETURN * RL;
+    o.open_f64 = e.f; o.open_steps = e.i + EPI_TMP_STEPS * RL; o.open_len = e.i + EPI_LEN * RL; o.open = e.i + EPI_OPEN * RL;
+    h->ep_on = true;
+    if (out) *out = o;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_episodes_outputs(imgenv_t* h, imgenv_episodes_out* out) {
+    if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->ep_on) FAIL(IMGENV_ESTATE, "imgenv_episodes_enable was not called");
+    *out = h->ep_out;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_episodes_clear(imgenv_t* h, void* stream) {
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->ep_on) FAIL(IMGENV_ESTATE, "imgenv_episodes_enable was not called");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipMemsetAsync(h->ep.f, 0, h->ep_clear_bytes, (hipStream_t)stream));
     return IMGENV_OK;
 }
 

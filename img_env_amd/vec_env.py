@@ -36,7 +36,7 @@ class VecImageEnv:
     """
 
     def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False,
-                 map_policy="keep", world_maps=None):
+                 map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3):
         import torch
         from .world import World
         self.cfg = cfg
@@ -98,6 +98,47 @@ class VecImageEnv:
             self.world.enable_stack(int(cfg.get("image_batch", 0)), int(cfg.get("state_batch", 0)), int(cfg.get("laser_batch", -1)))
             names = [w for w in (cfg.get("wrapper") or []) if w in ("ObsStateTmp", "ObsLaserStateTmp")]
             self._filter = names[-1] if names else None
+        # episode_stats: TestEpisodeWrapper (evaluation_wrapper/TestEpisodeWrapper.py:8-119) inside the library, per robot of every
+        # env (imgenv_episodes_enable): how episodes end, steps to arrive, returns, lengths and the path figures of the commands,
+        # kept by one small launch per chain -- also where the device resets the envs and the host never sees an episode end.
+        # Opt-in: False launches nothing.
+        self.episode_stats = bool(episode_stats)
+        if self.episode_stats:
+            self.world.enable_episodes(int(episode_min_steps), float(cfg["control_hz"]))
+
+    def episode_tensors(self):
+        """the per-robot device tensors of the statistics (``World.episodes``: ``ends`` [6, n], ``episodes``, ``last_episode``,
+        ``last_return`` ...), as they are -- no synchronisation; ordered on the current stream behind the last reset / step"""
+        if not self.episode_stats:
+            raise RuntimeError("VecImageEnv was made without episode_stats=True")
+        return self.world.episodes
+
+    def episode_statistics(self):
+        """The keys of the reference's ``TestEpisodeWrapper`` print-out (TestEpisodeWrapper.py:87-117) over all robots of all envs
+        and their counted episodes so far -- the reference divides by ``max_episodes``, which is the number of counted episodes when
+        it prints -- plus ``aborted_rate``, ``episodes``, ``short_episodes``, ``avg_return`` and ``avg_len``.  SYNCHRONISES: it waits
+        for the stream and copies a few small tensors to the host."""
+        import torch
+        e = {k: v.sum(dim=-1) for k, v in self.episode_tensors().items()
+             if k in ("ends", "episodes", "short_episodes", "speed_steps", "arrive_steps", "len_sum", "v_sum", "w_sum", "figure_sums",
+                      "return_sum")}
+        torch.cuda.current_stream(self.world.device).synchronize()
+        e = {k: v.cpu().numpy() for k, v in e.items()}
+        ends = dict(zip(_cabi.EP_ENDS, (int(c) for c in e["ends"])))
+        fig = dict(zip(_cabi.EP_FIGURE_NAMES, (float(x) for x in e["figure_sums"])))
+        n, steps = max(1, int(e["episodes"])), max(1, int(e["speed_steps"]))
+        return dict(arrive_rate=ends["arrive"] / n, static_coll_rate=ends["static_collision"] / n, ped_coll_rate=ends["ped_collision"] / n,
+                    other_coll_rate=ends["other_collision"] / n, avg_arrive_steps=int(e["arrive_steps"]) / max(1, ends["arrive"]),
+                    stuck_rate=ends["timeout"] / n, avg_v=float(e["v_sum"]) / steps, avg_w=float(e["w_sum"]) / steps,
+                    avg_w_variance=fig["w_variance"] / n, avg_v_jerk=fig["v_jerk"] / n, avg_w_jerk=fig["w_jerk"] / n,
+                    avg_w_zero=fig["w_zero"] / n, aborted_rate=ends["aborted"] / n, episodes=int(e["episodes"]),
+                    short_episodes=int(e["short_episodes"]), avg_return=float(e["return_sum"]) / n, avg_len=int(e["len_sum"]) / n)
+
+    def clear_episode_statistics(self):
+        """every total and the open episodes' sums back to zero (``imgenv_episodes_clear``), ordered on the current stream"""
+        if not self.episode_stats:
+            raise RuntimeError("VecImageEnv was made without episode_stats=True")
+        self.world.clear_episodes()
 
     def __len__(self):
         return self.env_num * self.robot_total

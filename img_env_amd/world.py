@@ -24,6 +24,14 @@ def _torch_dtype(np_dtype):
     return _TORCH_DTYPES[np.dtype(np_dtype)]
 
 
+class _DeviceArray:
+    """library-owned device memory as the CUDA array interface describes it: ``torch.as_tensor`` makes a zero-copy view of it"""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2,
+                                         "strides": None}
+
+
 class World:
     """create -> reset(layout) -> step(actions) ... ; ``out`` maps output names to device tensors."""
 
@@ -104,6 +112,7 @@ class World:
         self.robot_end = cfg.robot_end if cfg.robot_end else cfg.n_robots
         self.stack = None  # enable_stack()
         self.stack_arena = None
+        self.episodes = None  # enable_episodes()
         if self.n_maps > 1:
             rest = self.grids[1:]
             rc = self.lib.imgenv_maps_add(self.h, len(rest), rest.ctypes.data, rest.shape[1], rest.shape[2])
@@ -190,6 +199,36 @@ class World:
             self.stack[name] = self.stack_arena[off:off + n].view(dt).view(*shape)
         self.stack_depths = (so.image_depth, so.state_depth, so.laser_depth)
         return self.stack
+
+    def enable_episodes(self, min_steps=3, dt=None):
+        """Device-side TestEpisodeWrapper (``imgenv_episodes_enable``): from now on every step takes each local robot's command,
+        reward and ``is_clean`` into its open episode and every reset folds the episodes of the robots it covers into per-robot
+        totals (include/imgenv.h).  ``self.episodes`` maps the names of ``imgenv_episodes_out`` to zero-copy tensors over the
+        library's own memory: int32 / float64 ``[R]``, or ``[rows, R]`` for ``ends`` (``_cabi.EP_ENDS``), ``figure_sums``
+        (``_cabi.EP_FIGURE_NAMES``) and ``open_f64`` (``_cabi.EP_OPEN_NAMES``).  Read-only; valid until ``close()``.  ``dt`` is the
+        YAML's ``control_hz`` (default: the handle's step time); ValueError for a bad cfg or a second call with another one."""
+        import torch
+        c = _cabi.make_episodes_cfg(min_steps, self.cfg.step_hz if dt is None else dt)
+        eo = _cabi.EpisodesOut()
+        rc = self.lib.imgenv_episodes_enable(self.h, C.byref(c), C.byref(eo))
+        if rc == _cabi.EINVAL:
+            raise ValueError("imgenv_episodes_enable: %s" % self.lib.imgenv_last_error().decode())
+        self._check(rc, "imgenv_episodes_enable")
+        if self.episodes is None:
+            R = eo.n_local
+            self.episodes = {}
+            for name, (dt_, rows) in _cabi.EPISODE_ARRAYS.items():
+                arr = _DeviceArray(getattr(eo, name), (rows, R) if rows else (R,), np.dtype(dt_).str)
+                with torch.cuda.device(self.device):
+                    t = torch.as_tensor(arr, device=self.device)
+                if t.data_ptr() != getattr(eo, name) or t.dtype != _torch_dtype(dt_):
+                    raise RuntimeError("imgenv_episodes_out.%s: torch made a copy instead of a view" % name)
+                self.episodes[name] = t
+        return self.episodes
+
+    def clear_episodes(self):
+        """``imgenv_episodes_clear``: totals, ``last_*`` and the open episodes' sums back to zero, ordered on the current stream"""
+        self._check(self.lib.imgenv_episodes_clear(self.h, self._stream()), "imgenv_episodes_clear")
 
     def reset(self, layout):
         """Reset everything.  A handle of several worlds (``n_worlds`` > 1) takes either one batch of all robots and
@@ -316,10 +355,14 @@ class World:
 
     def step_begin(self, actions):
         a = self._actions(actions)
+        # (kept until step_end: the step's kernels read the actions up to the chain's end, include/imgenv.h -- a tensor made here
+        # from host data would otherwise go back to torch's allocator, and to whoever allocates next, between the two calls)
+        self._step_actions = a
         self._check(self.lib.imgenv_step_begin(self.h, C.c_void_p(a.data_ptr()), self._stream()), "imgenv_step_begin")
 
     def step_end(self):
         self._check(self.lib.imgenv_step_end(self.h, self._stream()), "imgenv_step_end")
+        self._step_actions = None
         return self.out
 
     def init_comm(self, rank=None, n_ranks=None):
@@ -375,6 +418,7 @@ class World:
 
     def close(self):
         if getattr(self, "h", None):
+            self.episodes = None  # (views of memory the handle owns)
             self.lib.imgenv_destroy(self.h)
             self.h = None
 

@@ -487,6 +487,89 @@ int64_t imgenv_stack_bytes(const imgenv_cfg* cfg, const imgenv_stack_cfg* s);
 int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgenv_stack_out* out);
 int imgenv_stack_outputs(imgenv_t* h, imgenv_stack_out* out);
 
+/* ---- episode statistics: TestEpisodeWrapper (envs/wrapper/evaluation_wrapper/TestEpisodeWrapper.py:8-119) and its
+ * TrajectoryPathHelper (evaluation_wrapper/utils.py:5-133) for every robot of the handle, on the device ----
+ * The reference evaluates a policy by wrapping ONE env in TestEpisodeWrapper: how its episodes end (arrive / collision classes /
+ * time-out, by dones_info), steps to arrive, mean v and |w|, and per episode the variance and sign changes of w and the mean
+ * |acceleration| and |jerk| of the commands.  With episode statistics enabled the library keeps the same for every local robot,
+ * plus the episode's return and length, with no host in the loop -- also behind imgenv_step_autoreset_device, where the host never
+ * learns that an episode ended.  One extra kernel launch per chain (csrc/episodes.h), no host synchronisation, allocation or copy
+ * per step; everything in float64 / int32, one fixed operation order per robot (results are deterministic).
+ *
+ * After a step (any imgenv_step* call), per local robot with an open episode (TestEpisodeWrapper.py:37-45, utils.py:26-28, 60-100):
+ *   the command is (v, w) of the robot's `actions` row, promoted to double, (0, 0) where imgenv_out.step_is_clean is 0
+ *   (MultiRobotCleanWrapper masks info["speeds"], base.py:58, 83); steps += 1; v_sum += v; w_sum += |w|; the open episode's path
+ *   sums take the command (n, sum v, sum w, sum w^2, sum |w|, sum |acc| and |jerk| of v and w from the last two commands with
+ *   acc = (x - prev) / dt, sign changes of w counted against the previous command, 0 before the first);
+ *   ep_return += imgenv_out.step_rewards; ep_len += imgenv_out.step_is_clean (the reference keeps neither).
+ * At a reset of the robot's world (imgenv_reset, imgenv_reset_world(s), imgenv_reset_worlds_spawn, the worlds an
+ * imgenv_step_autoreset / imgenv_step_autoreset_device call restarted), reading the LAST step's imgenv_out.step_dones_info
+ * (TestEpisodeWrapper.py:47-85):
+ *   steps > min_steps: the episode is COUNTED -- ends[bin] += 1 (bins below; a reset of an unfinished robot, code 0, is
+ *   `aborted`: the reference's wrapper exits there), episodes += 1, speed_steps += steps, arrive_steps += steps where the code is
+ *   5, the episode's figures w_variance = sum w^2 / n - (sum w / n)^2, w_zero, v_acc = sum |acc v| / max(n - 1, 1), w_acc, v_jerk =
+ *   sum |jerk v| / max(n - 2, 1), w_jerk, v_avg = sum v / n, w_avg = sum |w| / n -- each but w_zero rounded to 4 places,
+ *   rint(x * 1e4) / 1e4 -- are added to the robot's totals, return_sum += ep_return, len_sum += ep_len, last_* record the
+ *   episode, and the path sums restart.
+ *   otherwise the episode is too short to count (the reference's `tmp_steps > 3`): short_episodes += 1 and its path sums are NOT
+ *   restarted -- its commands ride into the next counted episode, as in the reference, whose helper is only emptied by a
+ *   counted reset.
+ *   Either way steps, ep_return and ep_len restart, and an episode is open from now on.
+ * Enabling marks every robot "no episode open": steps are ignored until the first reset after enabling, which folds nothing. */
+typedef struct imgenv_episodes_cfg {
+    int32_t struct_size;          /* sizeof(imgenv_episodes_cfg) */
+    int32_t min_steps;            /* an episode counts when it took MORE steps than this; the reference's is 3 (TestEpisodeWrapper.py:48) */
+    double dt;                    /* the YAML's control_hz: the divisor of the acceleration / jerk terms (utils.py:86-100) */
+} imgenv_episodes_cfg;
+#define IMGENV_EP_ARRIVE 0        /* rows of imgenv_episodes_out.ends: dones_info 5 */
+#define IMGENV_EP_TIMEOUT 1       /* 10 */
+#define IMGENV_EP_COLLISION 2     /* 1 static, then 2 pedestrian, 3 other robot */
+#define IMGENV_EP_ABORTED 5       /* any other code: the caller reset an unfinished robot */
+#define IMGENV_EP_END_BINS 6
+#define IMGENV_EP_FIGURES 8       /* rows of figure_sums: w_variance, w_zero, v_acc, w_acc, v_jerk, w_jerk, v_avg, w_avg */
+#define IMGENV_EP_OPEN_F64 15     /* rows of open_f64: n, sum v, sum w, sum w^2, sum |w|, sum |acc v|, sum |acc w|, sum |jerk v|,
+                                   * sum |jerk w|, prev v, prev w, last-but-one v, last-but-one w, w_zero, ep_return */
+/* Device pointers of the per-robot statistics, R = robot_end - robot_begin local robots (a robot shard keeps its local rows).
+ * Two-dimensional arrays are [row][R]: one row per quantity, robots contiguous.  Ownership as for imgenv_out: owned by the handle,
+ * valid until imgenv_destroy(), contents valid once the stream work of the last reset / step has completed, READ-ONLY for the
+ * caller (they are the running sums themselves). */
+typedef struct imgenv_episodes_out {
+    int32_t struct_size;          /* on entry 0 or sizeof(imgenv_episodes_out) */
+    int32_t n_local;              /* R */
+    /* totals over the robot's counted episodes (TestEpisodeWrapper.py:15-35) */
+    int32_t* ends;                /* [IMGENV_EP_END_BINS][R]  arrive_num, stuck_num, static / ped / other_coll_num, aborted */
+    int32_t* episodes;            /* [R] counted episodes (cur_episode) */
+    int32_t* short_episodes;      /* [R] episodes too short to count */
+    int32_t* speed_steps;         /* [R] speed_step: steps of the counted episodes */
+    int32_t* arrive_steps;        /* [R] steps: steps of the episodes that arrived */
+    int32_t* len_sum;             /* [R] clean steps of the counted episodes */
+    double* v_sum;                /* [R] sum of v over every step (not only those of counted episodes, as in the reference) */
+    double* w_sum;                /* [R] sum of |w| */
+    double* figure_sums;          /* [IMGENV_EP_FIGURES][R]  the rounded figures summed over the counted episodes */
+    double* return_sum;           /* [R] returns of the counted episodes */
+    /* the robot's last counted episode: a trainer polls last_episode for completions */
+    int32_t* last_code;           /* [R] dones_info it ended with */
+    int32_t* last_steps;          /* [R] */
+    int32_t* last_len;            /* [R] */
+    int32_t* last_episode;        /* [R] its number, 1-based (= episodes when it was counted); 0: none yet */
+    double* last_return;          /* [R] */
+    /* the open episode */
+    double* open_f64;             /* [IMGENV_EP_OPEN_F64][R] */
+    int32_t* open_steps;          /* [R] steps since the robot's last reset (tmp_steps) */
+    int32_t* open_len;            /* [R] of which clean */
+    int32_t* open;                /* [R] 1 once a reset after enabling has opened an episode */
+} imgenv_episodes_out;
+/* Legal at any time; the memory is the library's.  IMGENV_EINVAL for a wrong struct_size, dt <= 0 (or not finite), min_steps < 0,
+ * or a second call whose cfg differs from the first's; a second call with the same cfg changes nothing and hands out the same
+ * pointers.  `out` may be NULL.  A handle that never calls it behaves, launch for launch, as if this section did not exist. */
+int imgenv_episodes_enable(imgenv_t* h, const imgenv_episodes_cfg* cfg, imgenv_episodes_out* out);
+/* IMGENV_ESTATE before imgenv_episodes_enable() */
+int imgenv_episodes_outputs(imgenv_t* h, imgenv_episodes_out* out);
+/* TestEpisodeWrapper.__init__'s zeros (TestEpisodeWrapper.py:15-35) again, ordered on `stream`: every total, last_* and the open
+ * episode's sums and counters become 0 (one memset); `open` keeps its value, so what follows of an episode in flight still counts
+ * if it is long enough. */
+int imgenv_episodes_clear(imgenv_t* h, void* stream);
+
 /* ---- map bank: several static maps in one handle, one of them per world and episode ----
  * The reference trains one policy over a set of maps: its trainer is started from several YAML files side by side
  * (create_launch.py:57-65, one node per (env_name, env_num) pair), each env process loads its own global_map.map_file

@@ -6,7 +6,11 @@ placements drawn by the Python EnvPos or inside the library (native_spawn).
 
 --stack IMAGE,STATE,LASER adds the frame stacks of StateBatchWrapper at those depths (the YAML keys), kept by the library
 (imgenv_stack_enable); --torch-stack keeps them with torch ops on top of an unstacked VecImageEnv instead -- what a user had to
-write before; --stack-compare alternates no stack / library stack / torch stack over several rounds and writes the raw figures."""
+write before; --stack-compare alternates no stack / library stack / torch stack over several rounds and writes the raw figures.
+
+--episodes adds the per-robot episode statistics of TestEpisodeWrapper kept by the library (imgenv_episodes_enable);
+--torch-episodes keeps the same figures with EpisodeStats and torch ops on top of a plain VecImageEnv; --episodes-compare
+alternates no statistics / library / torch over several rounds and writes the raw figures."""
 import argparse
 import json
 import os
@@ -43,15 +47,94 @@ class TorchStack:
         return self.stack
 
 
+class TorchEpisodes:
+    """TestEpisodeWrapper per robot with torch ops on a plain VecImageEnv: ``EpisodeStats.add`` every step, then the fold of the
+    envs that restarted as ``torch.where`` on the per-robot all_down mask (no host synchronisation: the best a user could write)"""
+    FIGURES = ("w_variance", "w_zero", "v_acc", "w_acc", "v_jerk", "w_jerk", "v_avg", "w_avg")
+    CODES = (5, 10, 1, 2, 3)
+
+    def __init__(self, env, min_steps=3):
+        import torch
+        from img_env_amd.envs import EpisodeStats
+        n, dev = len(env), env.world.device
+        self.env, self.min_steps = env, int(min_steps)
+        self.stats = EpisodeStats(n, float(env.cfg["control_hz"]), dev)
+        f64 = lambda *shape: torch.zeros(*shape, n, dtype=torch.float64, device=dev)  # noqa: E731
+        i64 = lambda *shape: torch.zeros(*shape, n, dtype=torch.int64, device=dev)  # noqa: E731
+        self.steps, self.ep_len, self.ep_return = i64(), i64(), f64()
+        self.ends, self.figure_sums = i64(6), f64(8)
+        self.episodes, self.short_episodes, self.speed_steps, self.arrive_steps, self.len_sum = i64(), i64(), i64(), i64(), i64()
+        self.v_sum, self.w_sum, self.return_sum = f64(), f64(), f64()
+
+    def reset(self):
+        """every env has just been reset for the first time: nothing to fold"""
+        self.steps.zero_()
+        self.ep_len.zero_()
+        self.ep_return.zero_()
+
+    def push(self, actions, rewards, info):
+        import torch
+        st = self.stats
+        clean = info["is_clean"] != 0
+        zero = torch.zeros((), dtype=torch.float64, device=actions.device)
+        v, w = torch.where(clean, actions[:, 0].double(), zero), torch.where(clean, actions[:, 1].double(), zero)
+        self.steps += 1
+        self.v_sum += v
+        self.w_sum += w.abs()
+        st.add(v, w)
+        self.ep_return += rewards
+        self.ep_len += clean
+        down, codes = info["all_down"], info["dones_info"]
+        counted = down & (self.steps > self.min_steps)
+        c = counted.to(torch.int64)
+        bins = torch.full_like(codes, 5)
+        for b, code in enumerate(self.CODES):
+            bins = torch.where(codes == code, b, bins)
+        self.ends.scatter_add_(0, bins.view(1, -1).long(), c.view(1, -1))
+        self.episodes += c
+        self.short_episodes += (down & ~counted).to(torch.int64)
+        self.speed_steps += c * self.steps
+        self.arrive_steps += c * (codes == 5) * self.steps
+        n = st.n.clamp(min=1)
+        n1, n2 = (st.n - 1).clamp(min=1), (st.n - 2).clamp(min=1)
+        mean_w = st.sum_w / n
+        fig = torch.stack([st.sum_ww / n - mean_w * mean_w, st.w_zero, st.sum_abs_acc[0] / n1, st.sum_abs_acc[1] / n1,
+                           st.sum_abs_jerk[0] / n2, st.sum_abs_jerk[1] / n2, st.sum_v / n, st.sum_absw / n])
+        fig = torch.where(torch.arange(8, device=fig.device).view(-1, 1) == 1, fig, torch.round(fig * 1e4) / 1e4)
+        self.figure_sums += torch.where(counted, fig, zero)
+        self.return_sum += torch.where(counted, self.ep_return, zero)
+        self.len_sum += c * self.ep_len
+        for name in ("n", "sum_v", "sum_w", "sum_ww", "sum_absw", "w_zero"):
+            setattr(st, name, torch.where(counted, zero, getattr(st, name)))
+        for name in ("sum_abs_acc", "sum_abs_jerk", "prev", "prev2"):
+            setattr(st, name, [torch.where(counted, zero, t) for t in getattr(st, name)])
+        self.steps = torch.where(down, 0, self.steps)
+        self.ep_len = torch.where(down, 0, self.ep_len)
+        self.ep_return = torch.where(down, zero, self.ep_return)
+
+    def statistics(self):
+        """the keys of ``VecImageEnv.episode_statistics()``; synchronises"""
+        ends = [int(x) for x in self.ends.sum(dim=1).cpu()]
+        fig = dict(zip(self.FIGURES, (float(x) for x in self.figure_sums.sum(dim=1).cpu())))
+        n, steps = max(1, int(self.episodes.sum())), max(1, int(self.speed_steps.sum()))
+        return dict(arrive_rate=ends[0] / n, static_coll_rate=ends[2] / n, ped_coll_rate=ends[3] / n, other_coll_rate=ends[4] / n,
+                    avg_arrive_steps=int(self.arrive_steps.sum()) / max(1, ends[0]), stuck_rate=ends[1] / n,
+                    avg_v=float(self.v_sum.sum()) / steps, avg_w=float(self.w_sum.sum()) / steps, avg_w_variance=fig["w_variance"] / n,
+                    avg_v_jerk=fig["v_jerk"] / n, avg_w_jerk=fig["w_jerk"] / n, avg_w_zero=fig["w_zero"] / n, aborted_rate=ends[5] / n,
+                    episodes=int(self.episodes.sum()), short_episodes=int(self.short_episodes.sum()),
+                    avg_return=float(self.return_sum.sum()) / n, avg_len=int(self.len_sum.sum()) / n)
+
+
 def stack_depths(stack):
     """(image, state, laser) YAML keys -> effective depths (base.py:103-105)"""
     return (max(stack[0], 0), max(stack[1], 0), max(stack[2], 1) if stack[2] >= 0 else 0)
 
 
 def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, natives=(False, True, "device"), stack=None,
-            torch_stack=False):
+            torch_stack=False, episodes=None):
     """robot-steps/s of VecImageEnv over `steps` steps, after the envs have drifted out of phase.  ``stack`` = (image_batch,
-    state_batch, laser_batch): with the library's frame stacks, or (``torch_stack``) the same kept by torch ops on top"""
+    state_batch, laser_batch): with the library's frame stacks, or (``torch_stack``) the same kept by torch ops on top;
+    ``episodes`` = "library" | "torch": with the per-robot episode statistics, kept by the library or by ``TorchEpisodes``"""
     import torch
     from img_env_amd import worldgen
     from img_env_amd.vec_env import VecImageEnv
@@ -62,7 +145,8 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
         if stack is not None:
             cfg.update(image_batch=stack[0], state_batch=stack[1], laser_batch=stack[2])
         env = VecImageEnv(cfg, env_num=envs, seed=5, native_spawn=bool(native), device_reset=native == "device",
-                          stack=stack is not None and not torch_stack)
+                          stack=stack is not None and not torch_stack, episode_stats=episodes == "library")
+        te = TorchEpisodes(env) if episodes == "torch" else None
         ts = TorchStack(env, stack_depths(stack)) if stack is not None and torch_stack else None
         n = len(env)
         g = torch.Generator(device="cuda").manual_seed(1)
@@ -73,19 +157,25 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
         env.reset()
         if ts:
             ts.reset()
+        if te:
+            te.reset()
         torch.cuda.synchronize()
         t_reset = time.perf_counter() - t0
         for s in range(time_max + 20):  # past the first wave of time limits: the envs drift out of phase as robots collide
-            _, _, _, info = env.step(acts[s % 16])
+            _, rew, _, info = env.step(acts[s % 16])
             if ts:
                 ts.push(info["all_down"])
+            if te:
+                te.push(acts[s % 16], rew, info)
         torch.cuda.synchronize()
         placed0 = sum(env.world.autoreset_last()[::-1][0:1]) + len(env.world.autoreset_last()[0]) if native == "device" else 0
         resets, t0 = 0, time.perf_counter()
         for s in range(steps):
-            _, _, _, info = env.step(acts[s % 16])
+            _, rew, _, info = env.step(acts[s % 16])
             if ts:
                 ts.push(info["all_down"])
+            if te:
+                te.push(acts[s % 16], rew, info)
             if info["reset_envs"] is not None:  # (device-side reset: nothing comes back to the host)
                 resets += len(info["reset_envs"])
         torch.cuda.synchronize()
@@ -95,7 +185,9 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
             resets = first + len(worlds) - placed0
         res = dict(robot_steps_per_s=n * steps / dt, us_per_step=1e6 * dt / steps, env_resets_per_step=resets / steps,
                    first_reset_ms=1e3 * t_reset)
-        if native is True and stack is None:  # the same steps without the reset half: what NeverStopWrapper costs on top of the step
+        if episodes is not None:  # (after the clock has stopped: this synchronises)
+            res["episodes_counted"] = (te.statistics() if te else env.episode_statistics())["episodes"]
+        if native is True and stack is None and episodes is None:  # the same steps without the reset half: what NeverStopWrapper costs on top of the step
             env.auto_reset = False
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -106,6 +198,8 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
         out["device_reset" if native == "device" else ("native_spawn" if native else "python_spawn")] = res
         env.close()
     extra = {} if stack is None else dict(stack=list(stack), stack_by="torch" if torch_stack else "library")
+    if episodes is not None:
+        extra["episodes_by"] = episodes
     return dict(envs=envs, robots_per_env=robots, peds_per_env=peds, **extra, **out)
 
 
@@ -136,6 +230,32 @@ def compare_stacks(args, depths_list, rounds=3):
                 rounds=rounds, runs=runs, summary=summary)
 
 
+def compare_episodes(args, rounds=3):
+    """no statistics / library / torch_episodes, alternating, `rounds` times, per reset variant"""
+    natives = (True, "device")
+    runs = []
+    for rnd in range(rounds):
+        for mode in ("none", "library", "torch_episodes"):
+            r = measure(args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max, natives,
+                        episodes=None if mode == "none" else mode.split("_")[0])
+            for variant in ("native_spawn", "device_reset"):
+                runs.append(dict(round=rnd, mode=mode, variant=variant, us_per_step=r[variant]["us_per_step"],
+                                 env_resets_per_step=r[variant]["env_resets_per_step"],
+                                 episodes_counted=r[variant].get("episodes_counted")))
+                print(json.dumps(runs[-1]), flush=True)
+    summary = []
+    for variant in ("native_spawn", "device_reset"):
+        row = dict(variant=variant)
+        for mode in ("none", "library", "torch_episodes"):
+            v = [r["us_per_step"] for r in runs if r["variant"] == variant and r["mode"] == mode]
+            row[mode] = dict(us_per_step_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
+        row["added_us_library"] = row["library"]["median"] - row["none"]["median"]
+        row["added_us_torch"] = row["torch_episodes"]["median"] - row["none"]["median"]
+        summary.append(row)
+    return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, steps=args.steps, time_max=args.time_max,
+                rounds=rounds, runs=runs, summary=summary)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
@@ -149,9 +269,20 @@ def main():
     ap.add_argument("--torch-stack", action="store_true", help="keep the stacks with torch ops instead of the library's kernel")
     ap.add_argument("--stack-compare", default=None, metavar="I,S,L[;I,S,L...]",
                     help="no stack / library / torch, alternating over --rounds rounds per depth setting")
+    ap.add_argument("--episodes", action="store_true", help="per-robot episode statistics kept by the library")
+    ap.add_argument("--torch-episodes", action="store_true", help="the same statistics kept with EpisodeStats and torch ops")
+    ap.add_argument("--episodes-compare", action="store_true",
+                    help="no statistics / library / torch_episodes, alternating over --rounds rounds")
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=None, help="--stack-compare: also write the JSON here")
+    ap.add_argument("--out", default=None, help="--stack-compare / --episodes-compare: also write the JSON here")
     args = ap.parse_args()
+    if args.episodes_compare:
+        res = compare_episodes(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
+        return
     if args.stack_compare:
         res = compare_stacks(args, [tuple(int(v) for v in d.split(",")) for d in args.stack_compare.split(";")], args.rounds)
         if args.out:
@@ -162,7 +293,7 @@ def main():
     natives = ("device",) if args.device_only else (False, True, "device")
     stack = tuple(int(v) for v in args.stack.split(",")) if args.stack else None
     print(json.dumps(measure(args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max, natives, stack=stack,
-                             torch_stack=args.torch_stack)))
+                             torch_stack=args.torch_stack, episodes="torch" if args.torch_episodes else "library" if args.episodes else None)))
 
 
 if __name__ == "__main__":

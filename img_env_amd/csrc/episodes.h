@@ -19,8 +19,7 @@
 #pragma once
 #include <stdint.h>
 
-#define EP_BLOCK 256
-#define EP_MAX_BLOCKS 1024
+#include "launch_plan.h"  // EP_BLOCK, EP_MAX_BLOCKS
 
 // float64 rows: the open episode first (EpisodeStats' members, envs.py:388-396, then the running return) ...
 enum {

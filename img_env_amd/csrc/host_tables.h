@@ -19,6 +19,7 @@
 
 #include "../../include/imgenv.h"
 #include "fp_rows.h"
+#include "launch_plan.h"  // VBT_T
 #include "tfm.h"
 
 struct Pts {
@@ -453,7 +454,7 @@ static void build_robot_class(RobotClassHost& k, const ViewGeom& g, bool force_b
 // by), and two cold ones -- the cell's ray list {first entry, count} and its bit address in the tiled crop bitmap -- for the
 // taps a top beam leaves alone or the own footprint covers.  xofs / yofs: source index of tap 1 per destination column / row
 // (csrc/cv_resize.h), borders replicated as OpenCV does.
-#define TAP_CHUNK_PIXELS 256  // (= VBT_T, k_taps_big's workgroup)
+constexpr int TAP_CHUNK_PIXELS = VBT_T;  // k_taps_big's workgroup
 static void build_big_taps(RobotClassHost& k, const ViewGeom& g, const std::vector<int>& xofs, const std::vector<int>& yofs) {
     const int IW = (int)xofs.size(), IH = (int)yofs.size(), NP = IW * IH;
     std::vector<char> chunk_dyn((size_t)(NP + TAP_CHUNK_PIXELS - 1) / TAP_CHUNK_PIXELS, g.B > 0 ? 0 : 1);  // (no laser: the crop decides everywhere)

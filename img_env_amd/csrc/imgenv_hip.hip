@@ -20,6 +20,7 @@
 #include "host_tables.h"
 #include "cv_resize.h"
 #include "spawn_host.h"
+#include "launch_plan.h"
 #include "kernels.h"
 #include "world.h"
 #include "stack.h"
@@ -56,6 +57,7 @@ struct imgenv {
     std::vector<double> rsl;
     std::vector<float> pmax;
     DevWorld d;
+    PlanHandle plan;  // what the launch rules (launch_plan.h) read of this handle: plan_facts
     std::vector<void*> allocs;
     unsigned char* arena = nullptr;
     bool own_arena = false;
@@ -354,9 +356,6 @@ struct OutField {
     size_t offset, bytes;
 };
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-// LDS of k_taps_big: hit words (+ the dummy beam) | 16 tap values per pixel | list of the taps that need a second look | counter
-static size_t taps_lds_bytes(int B) { return 16 * (size_t)((B + 4) / 4) + 16 * (size_t)VBT_T + 2 * 16 * (size_t)VBT_T + 16; }
-
 
 struct ArenaPlan {
     size_t total = 0;
@@ -516,6 +515,86 @@ extern "C" void imgenv_destroy(imgenv_t* h) {
     if (h->own_arena && h->arena) (void)hipFree(h->arena);
     if (h->own_pub && h->pub_arena) (void)hipFree(h->pub_arena);
     delete h;
+}
+
+// ---------------------------------------------------------------------------------------- launch plans and kernel variants
+// The kernel families that have template variants.  Each function names its family's instantiations ONCE (launch_plan.h: pick)
+// and returns the chosen one: the launches go through here and so do imgenv_create's LDS attributes (lds_attributes), so a
+// variant that can be launched has been given its LDS.
+static auto k_raster_for(const PlanHandle& p, int nw) {
+    decltype(&k_raster<true, 0, 1>) k = nullptr;
+    pick([&](auto P2, auto LM, auto NW) { k = k_raster<P2(), LM(), NW()>; }, p.pow2, OneOf<0, 1, 2>{p.layer}, OneOf<1, 4>{nw});
+    return k;
+}
+static auto k_move_raster_for(const PlanHandle& p, int nw) {
+    decltype(&k_move_raster<true, 0, 1>) k = nullptr;
+    pick([&](auto P2, auto LM, auto NW) { k = k_move_raster<P2(), LM(), NW()>; }, p.pow2, OneOf<0, 1, 2>{p.layer}, OneOf<1, 4>{nw});
+    return k;
+}
+static auto k_remote_for(const PlanHandle& p) { return p.pow2 ? k_remote<true> : k_remote<false>; }
+static auto k_view_for(const PlanHandle& p, int nw) {
+    decltype(&k_view<true, true, true, 1>) k = nullptr;
+    pick([&](auto P2, auto A4, auto ST, auto NW) { k = k_view<P2(), A4(), ST(), NW()>; }, p.pow2, p.view_a4, p.layer == LAYER_STAMP, OneOf<1, 2, 4, 8>{nw});
+    return k;
+}
+static auto k_crop_big_for(int sel) {  // (ViewPlan::crop_sel: <STAMP, TILED>, never tiled without the stamps)
+    return sel == 2 ? k_crop_big<true, true> : sel == 1 ? k_crop_big<true, false> : k_crop_big<false, false>;
+}
+static auto k_beams_big_for(const PlanHandle& p) {
+    decltype(&k_beams_big<true, true, true>) k = nullptr;
+    pick([&](auto P2, auto ST, auto LB) { k = k_beams_big<P2(), ST(), LB()>; }, p.pow2, p.layer == LAYER_STAMP, p.big_bits_in_lds);
+    return k;
+}
+static auto k_obs_for(const PlanHandle& p) {
+    decltype(&k_obs<0>) k = nullptr;
+    pick([&](auto E) { k = k_obs<E()>; }, OneOf<1, 2, 4, 8, 16, 0>{p.obs_E});
+    return k;
+}
+
+// what the launch rules read of the handle, once imgenv_create has decided it
+static void plan_facts(imgenv* h) {
+    const DevWorld& d = h->d;
+    PlanHandle& p = h->plan;
+    p.R = h->R; p.RL = h->RL; p.P = h->P; p.W = h->W; p.Rw = h->Rw; p.Pw = h->Pw; p.NA = h->NA;
+    p.sharded = d.sharded != 0; p.sum_shard = d.sum_shard != 0; p.pow2 = h->pow2;
+    p.layer = h->stamp ? LAYER_STAMP : h->sum ? LAYER_SUM : LAYER_COMPOSED;
+    p.serial = h->serial; p.big_view = h->big_view; p.view_a4 = h->geom.Wv % 4 == 0;
+    p.B = d.B; p.lds_view = h->lds_view; p.lds_obs = h->lds_obs; p.lds_view_big = h->lds_view_big;
+    p.obs_E = h->obs_E; p.n_sub = h->n_sub; p.relation = d.relation; p.scene = h->cfg.ped_scene_type;
+    p.early = h->early; p.gates_work = h->gates_work;
+    p.Gs = h->Gs; p.box_cells = d.box_cells;
+    p.big_max_crop = h->big_max_crop; p.big_full_chunks = h->big_full_chunks; p.big_tap_chunks_dyn = h->big_tap_chunks_dyn;
+    p.big_bits_in_lds = h->big_bits_in_lds; p.crop_map = d.crop_map != nullptr;
+    p.img_w = d.img_w; p.img_h = d.img_h; p.resize = d.resize != 0; p.keep_view_maps = d.keep_view_maps != 0;
+}
+// ... and of the chain of launches in hand (set_active has said what it covers)
+static PlanChain chain_facts(const imgenv* h, int is_reset, bool moved = false, bool local_only = false) {
+    static const bool early_off = getenv("IMGENV_EARLY_OBS") && atoi(getenv("IMGENV_EARLY_OBS")) == 0;  // (measurement switch)
+    const DevWorld& d = h->d;
+    PlanChain c;
+    c.act_ng = d.act_ng; c.act_np = d.act_np; c.act_nl = d.act_nl; c.act_nw = d.act_nw; c.act_cells = d.act_cells;
+    c.listed = d.act_list != nullptr; c.n_dev = d.act_n_dev != nullptr; c.act_hint = h->act_hint;
+    c.is_reset = is_reset != 0; c.moved = moved; c.local_only = local_only;
+    c.stamp_seq = h->stamp_seq;
+    c.orca_cap = std::max(h->cap_obst, d.n_obst);
+    c.chain_open = h->chain_open; c.orca_ran = h->orca_seq > 0; c.view_ran = h->view_seq > 0; c.in_step = h->in_step;
+    c.comm = h->comm != nullptr; c.crowd_ahead = h->sfm_ahead; c.early_off = early_off;
+    return c;
+}
+// every variant of this handle that wants more than the default 64 KiB of LDS is allowed it
+static int lds_attributes(imgenv* h) {
+    const PlanHandle& p = h->plan;
+    auto allow = [](const void* k, size_t bytes) -> int {
+        if (bytes > LDS_DEFAULT_MAX) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        return 0;
+    };
+    if (p.big_view) {
+        if (int rc = allow((const void*)k_taps_big, taps_lds_bytes(p.B))) return rc;
+        if (int rc = allow((const void*)k_beams_big_for(p), p.lds_view_big)) return rc;
+    }
+    for (int nw : {1, 2, 4, 8})
+        if (int rc = allow((const void*)k_view_for(p, nw), p.lds_view)) return rc;
+    return allow((const void*)k_obs_for(p), p.lds_obs);
 }
 
 // view_big.h's one-byte-per-cell summary of a static map (world.h: crop_map), in 8 x 8 tiles
@@ -738,14 +817,7 @@ extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, i
         // where the agents cover a good part of the map (the headline world: 0.133 against 0.138 ms per step), stamped
         // where the maps are much larger than what the agents touch (8192 one-robot worlds: 52 against 43 M robot-steps/s).
         const size_t cells = (size_t)Hg * Wg * W;
-        h->stamp = RL == R && cells > (size_t)512 * (R + P);  // measured: composed wins at 277 cells per agent, stamped at 1000
-        // ... and handles whose rasters and views are single small launches (at most 1024 blocks: bound by launch latency, not by
-        // their work) are better off without the k_compose launch however dense they are (cfg-2, 1024 robots at 156 cells per
-        // agent: 38.8 -> 36.3 us per step)
-        if (RL == R && R + P <= 1024) h->stamp = true;
-        if (cfg->flags & IMGENV_FLAG_COMPOSE_DENSE) h->stamp = false;
-        if ((cfg->flags & IMGENV_FLAG_COMPOSE_SPARSE) && RL == R) h->stamp = true;
-        if (h->stamp && R >= STAMP_MAX_ROBOTS) h->stamp = false;
+        h->stamp = plan_layer_stamp(RL == R, cells, R, P, cfg->flags);  // (where each wins, measured: launch_plan.h)
         // ... and where the owner layers + k_compose used to be the answer, the counting layer is (round 5: no pass over every cell
         // of every world per step, a robot that covers the same cells as a step ago issues no atomic at all) -- wherever it can
         // run: every footprint fits the rasters' LDS box, views through k_view, and the word has room for the counts: 3 bits of
@@ -1287,9 +1359,8 @@ extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, i
         TRY(dev_alloc(h, &h->d_sums, 2 * (size_t)h->n_spans));
         h->guard_check = true;
     }
-    h->PP = WAVE;  // sort slots of k_obs: a power of two, 64 * E of them in registers up to 1024 pedestrians
-    while (h->PP < h->Pw) h->PP <<= 1;
-    h->obs_E = h->PP <= 1024 ? h->PP / WAVE : 0;
+    h->PP = plan_obs_slots(h->Pw);  // sort slots of k_obs: a power of two, 64 * E of them in registers up to 1024 pedestrians
+    h->obs_E = plan_obs_E(h->PP);
     if (h->obs_E >= 2) {
         // last step's pedestrian order per robot (k_obs): any permutation of the slots will do to start from
         std::vector<uint16_t> ident((size_t)h->PP);
@@ -1304,47 +1375,25 @@ extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, i
     const size_t NC = (size_t)g.Hv * g.Wv;
     max_stride += 4;  // + the dummy beam of view cells that no beam crosses (kept a multiple of 16 bytes)
     d.hit_stride = (int)max_stride;
-    // src u8 (+ dummy cells) | hit u32 | column terms | cursors of the final pass | largest hit step of blocks of beams (3 levels)
-    h->lds_view = ((NC + 16) & ~(size_t)15) + 4 * max_stride + 16 * (size_t)g.Wv + 16 + 4 * (2 * (max_stride / 8 + 1) + 4);
+    h->lds_view = plan_lds_view(NC, max_stride, g.Wv);
     static_assert(PM_CAP * 2 <= WAVE * 7 * 4, "the touched-cell list reuses the staging buffer");
-    h->lds_obs = (h->obs_E == 0 ? (size_t)h->PP * 8 : 0) + (size_t)(h->Pw > 0 ? h->Pw : 1) * 8 + (size_t)h->PP * 4 + WAVE * 7 * 4 + 16;
+    h->lds_obs = plan_lds_obs(h->obs_E, h->PP, h->Pw);
     if (h->big_view) {  // k_beams_big: the occupied plane of the crop bitmap; k_taps_big: the hit words
-        const size_t lds_bits = 4 * (size_t)d.big_words;
-        h->big_bits_in_lds = lds_bits <= 150 * 1024;  // beyond that (views above ~1000 x 1000 cells) the beams read the bitmap from HBM
-        h->lds_view_big = (h->big_bits_in_lds ? lds_bits : 0) + 16;
+        h->big_bits_in_lds = plan_big_bits_in_lds((size_t)d.big_words);
+        h->lds_view_big = plan_lds_view_big((size_t)d.big_words);
         h->lds_view = 16;
         d.big_bits_in_lds = h->big_bits_in_lds ? 1 : 0;
-        if (taps_lds_bytes(g.B) > 160 * 1024) {
+        if (taps_lds_bytes(g.B) > LDS_MAX) {
             imgenv_destroy(h);
             FAIL(IMGENV_EINVAL, "the hit words of %d beams do not fit the 160 KiB LDS", g.B);
         }
-        if (taps_lds_bytes(g.B) > 64 * 1024)
-            HIPCHK_H(hipFuncSetAttribute((const void*)k_taps_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)taps_lds_bytes(g.B)));
     }
-    if (h->lds_view_big > 64 * 1024) {
-        for (const void* f : {(const void*)k_beams_big<true, true, true>, (const void*)k_beams_big<true, false, true>,
-                              (const void*)k_beams_big<false, true, true>, (const void*)k_beams_big<false, false, true>})
-            HIPCHK_H(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_view_big));
-    }
-    if (h->lds_view > 160 * 1024 || h->lds_obs > 160 * 1024) {
+    if (h->lds_view > LDS_MAX || h->lds_obs > LDS_MAX) {
         imgenv_destroy(h);
         FAIL(IMGENV_EINVAL, "view (%zu B) or pedestrian list (%zu B) does not fit the 160 KiB LDS", h->lds_view, h->lds_obs);
     }
-    if (h->lds_view > 64 * 1024) {
-        for (const void* f : {(const void*)k_view<true, true, false, 1>, (const void*)k_view<true, false, false, 1>,
-                              (const void*)k_view<false, true, false, 1>, (const void*)k_view<false, false, false, 1>,
-                              (const void*)k_view<true, true, true, 1>, (const void*)k_view<true, false, true, 1>,
-                              (const void*)k_view<false, true, true, 1>, (const void*)k_view<false, false, true, 1>,
-                              (const void*)k_view<true, true, false, 4>, (const void*)k_view<true, false, false, 4>,
-                              (const void*)k_view<false, true, false, 4>, (const void*)k_view<false, false, false, 4>,
-                              (const void*)k_view<true, true, true, 4>, (const void*)k_view<true, false, true, 4>,
-                              (const void*)k_view<false, true, true, 4>, (const void*)k_view<false, false, true, 4>})
-            HIPCHK_H(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_view));
-    }
     if (cfg->ped_scene_type == IMGENV_SCENE_PEDSIM)
         HIPCHK_H(hipFuncSetAttribute((const void*)k_sfm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(SfmNode) * SFM_LDS_NODES)));
-    if (h->lds_obs > 64 * 1024)
-        HIPCHK_H(hipFuncSetAttribute((const void*)k_obs<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_obs));
     {   // early-observation steps: worlds owned whole, an ORCA crowd that nothing but the solve moves (no beep lottery), no
         // limiter history to carry, views through k_view -- the headline shape and cfg-5; everything else keeps k_obs behind the move
         const bool limiters = cfg->limiter_v.has_velocity_limits || cfg->limiter_v.has_acceleration_limits || cfg->limiter_v.has_jerk_limits ||
@@ -1359,7 +1408,7 @@ extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, i
         // publishing is done
         // (robot shards too, since round 6: k_obs reads the rank's own robots' snapshots and the replicated pedestrians')
         h->early = !h->serial && P > 0 && (h->NA > 0 || h->sfm_ahead) && !d.beep_on && !limiters && !h->big_view &&
-                   h->n_sub >= 1 && h->n_sub + 2 <= INT_ITEMS;
+                   plan_integrate_fits(h->n_sub);
         if (h->early) {
             TRY(dev_alloc(h, &d.sync, 8));
             TRY(dev_alloc(h, &h->rec_snap[0], (size_t)RL * IMGENV_RECORD_DOUBLES));
@@ -1392,6 +1441,8 @@ extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, i
     HIPCHK_H(hipEventCreateWithFlags(&h->ev_join2, hipEventDisableTiming | hipEventDisableSystemFence));
     HIPCHK_H(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming | hipEventDisableSystemFence));
     HIPCHK_H(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming | hipEventDisableSystemFence));
+    plan_facts(h);
+    TRY(lds_attributes(h));
     HIPCHK_H(hipDeviceSynchronize());
     *out = h;
     return IMGENV_OK;
@@ -1483,8 +1534,6 @@ static int check_device_flags(imgenv* h) {
     return 0;
 }
 
-// fork: the pedestrian half of the observation needs the local robots' new poses only, so it starts right behind
-// k_integrate (in a sharded world: underneath the record exchange) on its own stream
 // what the tails need, whichever kernel ends up running them (tail_group)
 static void set_tail_fields(imgenv* h, int is_reset, int tail_elapsed) {
     DevWorld& d = h->d;
@@ -1544,26 +1593,14 @@ static int outputs_verify(imgenv* h, hipStream_t st) {
 
 static int launch_obs_kernel(imgenv* h, hipStream_t s_obs) {
     DevWorld& d = h->d;
-    const dim3 go(d.act_nl), bo(WAVE);
-    const size_t lds_obs = h->lds_obs;
-    switch (h->obs_E) {
-        case 1: TIMED(h, IMGENV_K_OBS, s_obs, (k_obs<1><<<go, bo, lds_obs, s_obs>>>(d, h->PP))); break;
-        case 2: TIMED(h, IMGENV_K_OBS, s_obs, (k_obs<2><<<go, bo, lds_obs, s_obs>>>(d, h->PP))); break;
-        case 4: TIMED(h, IMGENV_K_OBS, s_obs, (k_obs<4><<<go, bo, lds_obs, s_obs>>>(d, h->PP))); break;
-        case 8: TIMED(h, IMGENV_K_OBS, s_obs, (k_obs<8><<<go, bo, lds_obs, s_obs>>>(d, h->PP))); break;
-        // (four wavefronts per robot for 513 .. 1024 pedestrians -- three times the occupancy, a third of the LDS per wavefront --
-        // were measured in round 6 and LOSE: cfg-5 277 -> 325 us per step, 321 with two, 406 with eight: the step is bound by the
-        // instructions it issues, k_obs beside k_view, not by this kernel's occupancy.  docs/HISTORY.md)
-        case 16: TIMED(h, IMGENV_K_OBS, s_obs, (k_obs<16><<<go, bo, lds_obs, s_obs>>>(d, h->PP))); break;
-        default: TIMED(h, IMGENV_K_OBS, s_obs, (k_obs<0><<<go, bo, lds_obs, s_obs>>>(d, h->PP))); break;
-    }
+    const LaunchShape o = plan_obs(h->plan, chain_facts(h, 0));
+    TIMED(h, IMGENV_K_OBS, s_obs, (k_obs_for(h->plan)<<<dim3(o.grid), dim3(o.block), o.lds, s_obs>>>(d, h->PP)));
     h->launches += 1;
     return 0;
 }
 
 static int launch_obs(imgenv* h, hipStream_t st) {
     if (int rc = chain_begin(h, st)) return rc;
-    DevWorld& d = h->d;
     const bool overlap = !h->serial;
     hipStream_t s_obs = overlap ? h->side2 : st;
     if (overlap) {
@@ -1576,247 +1613,122 @@ static int launch_obs(imgenv* h, hipStream_t st) {
     return 0;
 }
 
-// The rasters of a chain of launches (in front of them, in STAMP mode, every STAMP_TAGS steps the sweep): every robot of the launch
-// and every pedestrian -- or, local_only (a step of a robot shard in SUM mode, world.h: sum_shard), this rank's robots and the
-// pedestrians: the other ranks' robots follow behind the exchange (k_remote)
+// The rasters of a chain of launches, as plan_rasters shapes them (in front of them, in STAMP mode, every STAMP_TAGS steps the sweep)
 static int launch_rasters(imgenv* h, hipStream_t st, int is_reset, bool moved, bool local_only, bool from_begin = false) {
     DevWorld& d = h->d;
+    const PlanHandle& p = h->plan;
+    const RasterPlan r = plan_rasters(p, chain_facts(h, is_reset, moved, local_only));
     const int keep_ng = d.act_ng;
     if (local_only) {
         d.act_ng = h->RL;
         d.act_g0 = h->r0;
     }
-    const int n_g = d.act_ng, n_p = d.act_np;
-    // k_compose / k_cell_base: 4 cells per thread over everything, or a fixed number of 256-thread blocks per listed world
-    const unsigned compose_blocks = d.act_list ? (unsigned)(((h->Gs / 4 + 255) / 256) * d.act_nw) : (unsigned)((d.act_cells / 4 + 255) / 256 + 1);
-    // STAMP mode: no compose.  A reset has given the worlds it covers their base classes together with their obstacle maps
-    // (k_reset_apply, k_reset_obstacles); every STAMP_TAGS steps one sweep drops all stamps before their tags come round again.
-    if (h->stamp && !is_reset && h->stamp_seq % STAMP_TAGS == 0)
-        TIMED(h, IMGENV_K_COMPOSE, st, (k_cell_base<<<dim3(compose_blocks), dim3(256), 0, st>>>(d)));
-    const int n_blocks = n_p > n_g ? n_p : n_g;
-    // four wavefronts per robot / pedestrian when the launch cannot fill the machine (device-side auto-reset: by the expected
-    // number of robots, the grid itself is sized for every world)
-    const bool small = (d.act_n_dev ? std::min(n_blocks, h->act_hint) : n_blocks) <= 1024;
-    // robots and pedestrians in blocks of their own while all of them fit the chip at once (8192 wavefronts): a robot and a
-    // pedestrian one behind the other in one block is twice a block's chain of memory round trips
-    // (1024 envs x (4 + 3): k_raster 34 -> 22 us; the headline's 8192 + 200 stay as they are: a second, nearly empty round)
-    const bool roomy = !small && n_g + n_p <= 8192;
-    const int split = (small || roomy) && n_g > 0 && n_p > 0 ? n_g : 0;
-    const dim3 gr(split || moved ? n_g + n_p : n_blocks), br(small ? 4 * WAVE : WAVE);
-    const size_t lds = 4 * (size_t)d.box_cells + 16;
-    const int variant = (h->pow2 ? 3 : 0) + (h->stamp ? 1 : h->sum ? 2 : 0);
-    // (k_move_raster: the step's move in the same launch -- the RVO / recorded pedestrians' too; a social-force crowd has moved in k_sfm)
+    if (r.sweep) TIMED(h, IMGENV_K_COMPOSE, st, (k_cell_base<<<dim3(r.sweep_blocks), dim3(256), 0, st>>>(d)));
+    const dim3 gr(r.launch.grid), br(r.launch.block);
     // (imgenv_step_end has counted the step when it launches this; imgenv_step_begin has not yet)
-    const int move_peds = h->P > 0 && (h->NA > 0 || h->cfg.ped_scene_type == IMGENV_SCENE_DATASET) ? 1 : 0, step_now = from_begin ? h->elapsed : h->elapsed - 1;
-#define RASTER_CASE(N, P2, LM)                                                                                        \
-    case N:                                                                                                           \
-        if (moved && small) TIMED(h, IMGENV_K_MOVE_RASTER, st, (k_move_raster<P2, LM, 4><<<gr, br, lds, st>>>(d, h->move_actions, h->n_sub, step_now, move_peds))); \
-        else if (moved) TIMED(h, IMGENV_K_MOVE_RASTER, st, (k_move_raster<P2, LM, 1><<<gr, br, lds, st>>>(d, h->move_actions, h->n_sub, step_now, move_peds))); \
-        else if (small) TIMED(h, IMGENV_K_RASTER, st, (k_raster<P2, LM, 4><<<gr, br, lds, st>>>(d, is_reset, split)));     \
-        else TIMED(h, IMGENV_K_RASTER, st, (k_raster<P2, LM, 1><<<gr, br, lds, st>>>(d, is_reset, split)));               \
-        break;
-    switch (variant) {
-        RASTER_CASE(5, true, 2)
-        RASTER_CASE(4, true, 1)
-        RASTER_CASE(3, true, 0)
-        RASTER_CASE(2, false, 2)
-        RASTER_CASE(1, false, 1)
-        RASTER_CASE(0, false, 0)
-    }
-#undef RASTER_CASE
+    const int step_now = from_begin ? h->elapsed : h->elapsed - 1;
+    if (r.move)
+        TIMED(h, IMGENV_K_MOVE_RASTER, st, (k_move_raster_for(p, r.nw)<<<gr, br, r.launch.lds, st>>>(d, h->move_actions, h->n_sub, step_now, r.move_peds)));
+    else
+        TIMED(h, IMGENV_K_RASTER, st, (k_raster_for(p, r.nw)<<<gr, br, r.launch.lds, st>>>(d, is_reset, r.split)));
     d.act_ng = keep_ng;
     d.act_g0 = 0;
     return 0;
 }
 
+// The chain behind the move: side launches, rasters, compose, views, the tails' stacks and statistics -- plan, then launch in stream order
 static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
     DevWorld& d = h->d;
-    const int n_g = d.act_ng, n_p = d.act_np, n_l = d.act_nl;
-    // k_compose: 4 cells per thread over everything, or a fixed number of 256-thread blocks per listed world
+    const PlanHandle& p = h->plan;
     set_tail_fields(h, is_reset, h->elapsed);
     if (h->P == 0)
         if (int rc = chain_begin(h, st)) return rc;
-    const unsigned compose_blocks = d.act_list ? (unsigned)(((h->Gs / 4 + 255) / 256) * d.act_nw) : (unsigned)((d.act_cells / 4 + 255) / 256 + 1);
     // the rasters: in a step whose move was left to them (imgenv_step_begin: k_move_raster) they come first and the side stream forks
     // behind them, otherwise behind the side launches; a robot shard in SUM mode has drawn its own robots in imgenv_step_begin, in
     // front of the exchange, and takes the other ranks' from their records now (k_remote)
     const bool moved = h->move_pending;
     h->move_pending = false;
-    const bool remote_only = h->d.sum_shard && !is_reset;
-    // what the side streams read of the OTHER ranks' robots: their RVO agents (k_side_robots, k_orca) -- nothing when the crowd
-    // ignores the robots or is no RVO crowd
-    const bool side_reads_all = h->P > 0 && h->NA > 0 && d.relation == 1;
+    const PlanChain c = chain_facts(h, is_reset, moved);
+    const SidePlan s = plan_side(p, c);
+    const ViewPlan v = plan_views(p, c);
     auto rasters = [&]() -> int {
-        if (!remote_only) return launch_rasters(h, st, is_reset, moved, false);
+        if (!s.remote_only) return launch_rasters(h, st, is_reset, moved, false);
         return 0;  // (k_remote went out in front of the side launches: below)
     };
-    if (remote_only) {
+    if (s.remote_only) {
         // the other ranks' robots, right behind the exchange; "the records are complete" for the side streams rides on this kernel's
         // dispatch packet (a hipEventRecord behind the exchange is a packet of its own on the caller's stream: ~6 us)
-        const unsigned nb = (unsigned)((h->R - h->RL + 255) / 256);
-        const hipEvent_t ev = side_reads_all && !h->serial ? h->ev_fork2 : nullptr;
-        if (h->pow2) TIMED(h, IMGENV_K_REMOTE, st, (hipExtLaunchKernelGGL(k_remote<true>, dim3(nb), dim3(256), 0, st, nullptr, ev, 0, d)));
-        else TIMED(h, IMGENV_K_REMOTE, st, (hipExtLaunchKernelGGL(k_remote<false>, dim3(nb), dim3(256), 0, st, nullptr, ev, 0, d)));
+        const hipEvent_t ev = s.side_reads_all && !h->serial ? h->ev_fork2 : nullptr;
+        TIMED(h, IMGENV_K_REMOTE, st, (hipExtLaunchKernelGGL(k_remote_for(p), dim3(s.remote.grid), dim3(s.remote.block), 0, st, nullptr, ev, 0, d)));
         h->launches += 1;
     }
     if (moved)
         if (int rc = rasters()) return rc;
     if (h->P > 0) {
         // One fork and one join per step on the caller's stream (every event operation costs it a ~6 us dependency
-        // bubble).  Beside the rasters, compose and view run, on two side streams, the pedestrian half of the
-        // observation and the next step's _step_ped_normal solve (img_env.cpp:304-343); both need poses only.  The
-        // observation stream finally waits for the solve, so its join event covers both.
-        // (IMGENV_SERIAL=1 in the environment keeps everything on the caller's stream: clean per-kernel timings.)
-        const bool overlap = !h->serial;
-        // Handles of at most 4096 robots keep ONE side stream: observation, robot records and the solve one behind the other (they
-        // fit underneath the rasters + views with room to spare: 31 us against 72 at 1024 envs x (4 + 3)), which saves three of the
-        // seven event operations of a phase -- such shapes are bound by the host's call rate (tools/host_issue_probe.py:
-        // ~6 us per launch or event call, ~30 calls per step with a device-side reset)
-        const bool one_side = overlap && !d.sharded && h->RL <= 4096;
-        hipStream_t s_orca = overlap ? (one_side ? h->side2 : h->side) : st;
+        // bubble).  Beside the rasters, compose and view run, on two side streams (one for handles of at most 4096 robots:
+        // plan_side), the pedestrian half of the observation and the next step's _step_ped_normal solve (img_env.cpp:304-343);
+        // both need poses only.  The observation stream finally waits for the solve, so its join event covers both.
+        hipStream_t s_orca = s.overlap ? (s.one_side ? h->side2 : h->side) : st;
         if (!h->obs_forked)
             if (int rc = launch_obs(h, st)) return rc;
         h->obs_forked = false;
-        hipStream_t s_obs = overlap ? h->side2 : st;
-        if (h->early_step && one_side) HIPCHK(hipStreamWaitEvent(s_orca, h->ev_fork, 0));  // (k_obs went out with the step, in front of the move: the solve waits for it)
-        if (overlap && !one_side) {
-            if (d.sharded && side_reads_all) {  // the solve needs every rank's robots: a second fork behind the exchange
-                if (!remote_only) HIPCHK(hipEventRecord(h->ev_fork2, st));  // (k_remote carries it otherwise)
+        hipStream_t s_obs = s.overlap ? h->side2 : st;
+        if (h->early_step && s.one_side) HIPCHK(hipStreamWaitEvent(s_orca, h->ev_fork, 0));  // (k_obs went out with the step, in front of the move: the solve waits for it)
+        if (s.overlap && !s.one_side) {
+            if (d.sharded && s.side_reads_all) {  // the solve needs every rank's robots: a second fork behind the exchange
+                if (!s.remote_only) HIPCHK(hipEventRecord(h->ev_fork2, st));  // (k_remote carries it otherwise)
                 HIPCHK(hipStreamWaitEvent(s_orca, h->ev_fork2, 0));
             } else {
                 HIPCHK(hipStreamWaitEvent(s_orca, h->ev_fork, 0));
             }
         }
-        // handles of several worlds with RVO crowds: k_orca does k_side_robots' part for its world itself (one launch less per phase)
-        const bool fold_side = h->W > 1 && h->NA > 0;
-        if (!fold_side) {
-            // (slices of >= 48 pedestrians, four at most: 8192 robots x 200 pedestrians = 128 x 4 wavefronts.  More of them -- cfg-5's
-            // 1000 pedestrians in 16 slices -- only take issue slots from the rasters and the views: 281-286 us per step against 276-278)
-            const int rvo_agents = h->NA > 0 && d.relation == 1, slices = rvo_agents && h->W == 1 ? std::min(4, std::max(1, (h->P + 47) / 48)) : 1;
-            k_side_robots<<<dim3((unsigned)((n_g + WAVE - 1) / WAVE) * (unsigned)slices), dim3(WAVE), 0, s_orca>>>(d, is_reset, rvo_agents, slices);
+        if (!s.fold_side) {
+            k_side_robots<<<dim3(s.robots.grid), dim3(s.robots.block), 0, s_orca>>>(d, is_reset, s.rvo_agents, s.slices);
             h->launches += 1;
         }
-        if (h->NA > 0) {
-            // groups of up to 4 pedestrians of one world per wavefront; an agent's LDS scratch sized by the largest obstacle table
-            // any world of the handle can hold, the table itself staged into LDS when it fits 256 segments
-            OrcaLaunch L;
-            const int per_world = h->W > 1 ? h->Pw : h->P, cap = std::max(std::max(h->cap_obst, d.n_obst), 1);
-            L.G = per_world > 2 ? 4 : per_world;  // a row of 16 lanes per agent
-            L.groups = (per_world + L.G - 1) / L.G;
-            L.cap_on = std::max(std::min(ORCA_MAX_ON, cap), ORCA_ROW - ORCA_MAX_AN);  // (a round's 16 candidate lines borrow the projection area)
-            L.cap_stack = std::min(ORCA_STACK, cap + 1);
-            L.fold_side = fold_side ? 1 : 0;
-            L.zero_vel = is_reset;
-            L.stage_obst = std::min(cap, 256);  // (a world with more segments than that is solved out of HBM: the kernel checks its count)
-            const unsigned blocks = (unsigned)((n_p / per_world) * L.groups);
+        if (s.orca) {
             // (world.h: what the next step's early k_obs reads.  A launch over every world writes one buffer and the next one the
             // other; a launch over some worlds -- a reset chain, nothing else is in flight -- writes both and does not take a turn)
             const bool partial = d.act_list != nullptr;
             d.ped_snap_out = h->early ? h->ped_snap[h->orca_seq & 1] : nullptr;
             d.ped_snap_out2 = h->early && partial ? h->ped_snap[(h->orca_seq + 1) & 1] : nullptr;
-            TIMED(h, IMGENV_K_ORCA, s_orca, (k_orca<<<dim3(blocks), dim3(WAVE), orca_lds_bytes(L), s_orca>>>(d, L)));
+            TIMED(h, IMGENV_K_ORCA, s_orca, (k_orca<<<dim3(s.orca_blocks), dim3(WAVE), orca_lds_bytes(s.L), s_orca>>>(d, s.L)));
             if (!partial) h->orca_seq += 1;
             h->launches += 1;
         }
-        if (overlap) {
-            if (!one_side) {
+        if (s.overlap) {
+            if (!s.one_side) {
                 HIPCHK(hipEventRecord(h->ev_join, s_orca));
                 HIPCHK(hipStreamWaitEvent(s_obs, h->ev_join, 0));
             }
             HIPCHK(hipEventRecord(h->ev_join2, s_obs));
         }
     }
-    if (h->P == 0 && is_reset) {  // no side streams: after a reset Agent::get_state gets its own small launch (in a step k_integrate does it, with pedestrians k_side_robots)
-        k_state<<<dim3((n_l + 127) / 128), dim3(128), 0, st>>>(d);
+    if (s.state) {
+        k_state<<<dim3(s.state_shape.grid), dim3(s.state_shape.block), 0, st>>>(d);
         h->launches += 1;
     }
     if (!moved)
         if (int rc = rasters()) return rc;
-    if (!h->stamp && !h->sum) TIMED(h, IMGENV_K_COMPOSE, st, (k_compose<<<dim3(compose_blocks), dim3(256), 0, st>>>(d)));
-    if (h->big_view) {  // view_big.h: crop (tiles of every robot spread over the chip) -> beams (a workgroup per robot and 256
-                        // beams) -> the shrunk sensor_map (a thread per pixel) -> the full view, only where it is an output
-        const int quarters = std::max(1, (d.B + VBB_T - 1) / VBB_T), tap_chunks = (d.img_w * d.img_h + VBT_T - 1) / VBT_T;
-        const bool full = d.keep_view_maps || !d.resize;
-        // tiles per wavefront: 8 while the launch is a handful of robots (a reset of a few worlds: every robot on ~40 workgroups), 32-64
-        // once there are enough robots to fill the chip anyway
-        // (measured again after the kernel's gathers stopped binding it: a wavefront's prologue -- pose, fixed-point terms, its tiles'
-        // corner records -- is worth ~8 tiles, so even 256 robots want 32 tiles per wavefront: 36 -> 29 us; 2048 robots 64: 152 -> 133.
-        // Handing the fixed-point terms over from the robot's raster instead of recomputing them per wavefront was measured too:
-        // 155 us at 2048 robots, i.e. worse -- the prologue's cost is its loads, not its arithmetic.)
-        const int n_eff = d.act_n_dev ? std::min(n_l, h->act_hint) : n_l;
-        const int tpw = n_eff >= 1024 ? 64 : n_eff >= 48 ? 32 : 8, crop_chunks = (h->big_max_crop + (VBC_T / WAVE) * tpw - 1) / ((VBC_T / WAVE) * tpw);
-        // (2048 robots x 1000 beams: one block of 256 beams per workgroup 98 us, two 87, four 87 -- but end to end two win: 3.85 M robot-steps/s
-        // against 3.79 / 3.78: the first workgroup of a robot also hands the collision code to the step's tail)
-        const int qpw = n_eff >= 1024 ? std::min(2, quarters) : 1;
-        const dim3 gc((unsigned)((n_l + 7) / 8 * 8) * (unsigned)crop_chunks), gb((unsigned)n_l * (unsigned)((quarters + qpw - 1) / qpw));
-        const dim3 gf((unsigned)n_l * (unsigned)h->big_full_chunks);
-        static_assert(VBT_T == TAP_CHUNK_PIXELS, "host_tables.h lists k_taps_big's chunks");
-        if (h->stamp && d.crop_map) TIMED(h, IMGENV_K_CROP, st, (k_crop_big<true, true><<<gc, dim3(VBC_T), 0, st>>>(d, crop_chunks, n_l, tpw)));
-        else if (h->stamp) TIMED(h, IMGENV_K_CROP, st, (k_crop_big<true, false><<<gc, dim3(VBC_T), 0, st>>>(d, crop_chunks, n_l, tpw)));
-        else TIMED(h, IMGENV_K_CROP, st, (k_crop_big<false, false><<<gc, dim3(VBC_T), 0, st>>>(d, crop_chunks, n_l, tpw)));
-        const int variant = (h->pow2 ? 4 : 0) | (h->stamp ? 2 : 0) | (h->big_bits_in_lds ? 1 : 0);
-#define BEAMS_CASE(N, P2, ST, LB) \
-    case N: TIMED(h, IMGENV_K_VIEW, st, (k_beams_big<P2, ST, LB><<<gb, dim3(VBB_T), h->lds_view_big, st>>>(d, quarters, qpw))); break;
-        switch (variant) {
-            BEAMS_CASE(7, true, true, true)
-            BEAMS_CASE(6, true, true, false)
-            BEAMS_CASE(5, true, false, true)
-            BEAMS_CASE(4, true, false, false)
-            BEAMS_CASE(3, false, true, true)
-            BEAMS_CASE(2, false, true, false)
-            BEAMS_CASE(1, false, false, true)
-            BEAMS_CASE(0, false, false, false)
-        }
-#undef BEAMS_CASE
+    if (p.layer == LAYER_COMPOSED) TIMED(h, IMGENV_K_COMPOSE, st, (k_compose<<<dim3(plan_compose_blocks(p, c)), dim3(256), 0, st>>>(d)));
+    if (p.big_view) {  // view_big.h: crop -> beams -> the shrunk sensor_map -> the full view, only where it is an output
+        TIMED(h, IMGENV_K_CROP, st, (k_crop_big_for(v.crop_sel)<<<dim3(v.crop.grid), dim3(v.crop.block), 0, st>>>(d, v.crop_chunks, c.act_nl, v.tpw)));
+        TIMED(h, IMGENV_K_VIEW, st, (k_beams_big_for(p)<<<dim3(v.beams.grid), dim3(v.beams.block), v.beams.lds, st>>>(d, v.quarters, v.qpw)));
         // the last kernel of the chain commits the robots' new is_collision_
-        // (a step only runs the chunks of pixels a beam can reach: static list per class; the chunks behind the sensor hold their
-        // 200 / 100 since the reset)
-        const bool listed = !is_reset && h->big_tap_chunks_dyn > 0 && h->big_tap_chunks_dyn < tap_chunks;
-        const int tap_wgs = listed ? h->big_tap_chunks_dyn : tap_chunks;
-        if (d.resize) TIMED(h, IMGENV_K_TAPS, st, (k_taps_big<<<dim3((unsigned)n_l * (unsigned)tap_wgs), dim3(VBT_T), taps_lds_bytes(d.B), st>>>(d, tap_wgs, full ? 0 : 1, listed ? 1 : 0)));
-        if (full) TIMED(h, IMGENV_K_FULLVIEW, st, (k_fullview_big<<<gf, dim3(VBF_T), 16 * (size_t)((d.B + 4) / 4), st>>>(d, h->big_full_chunks, 1)));
-        h->launches += (d.resize ? 1 : 0) + (full ? 1 : 0);
+        if (v.taps)
+            TIMED(h, IMGENV_K_TAPS, st, (k_taps_big<<<dim3(v.taps_shape.grid), dim3(v.taps_shape.block), v.taps_shape.lds, st>>>(d, v.tap_wgs, v.full ? 0 : 1, v.listed ? 1 : 0)));
+        if (v.full)
+            TIMED(h, IMGENV_K_FULLVIEW, st, (k_fullview_big<<<dim3(v.fullview.grid), dim3(v.fullview.block), v.fullview.lds, st>>>(d, h->big_full_chunks, 1)));
+        h->launches += (v.taps ? 1 : 0) + (v.full ? 1 : 0);
     } else {
-        // one wavefront per robot when the launch fills the machine, four when it is small (a reset of a few worlds): then
-        // the single wavefront's latency is all there is
-        // ... and whenever a view's LDS (crop + hit words + column table: 15 KB at 96 x 96 cells and 720 beams) would leave a
-        // compute unit with 16 or fewer one-wavefront workgroups -- four or fewer wavefronts per SIMD where the registers allow
-        // eight: four wavefronts then share one view's LDS (cfg-5, 8192 robots: k_view 252 -> 179 us alone, the step 472 -> 377 us;
-        // at 48 x 48 cells, 5 KB and 32 workgroups per unit, it loses: 63 -> 87 us)
-        const bool lds_bound = (160 * 1024) / ((h->lds_view + 1279) / 1280 * 1280) <= 16;
-        const bool small = lds_bound || (d.act_n_dev ? std::min(n_l, h->act_hint) : n_l) <= 1024;
-        // two wavefronts per robot in between (1025-4096 robots: every wavefront still resident at once; 1024 envs x 4: 39 -> 28 us)
-        const int n_view = d.act_n_dev ? std::min(n_l, h->act_hint) : n_l;
-        const bool two = !small && n_view <= 4096;
-        // ... and eight where a launch is at most 1024 robots and the view small (48 x 48 cells and 360 beams are then ONE round of groups
-        // and ONE round of beams per wavefront: cfg-2 k_view 21.6 -> 20.4 us)
-        const bool eight = small && !lds_bound;
-        const dim3 gv(n_l), bv(eight ? 8 * WAVE : small ? 4 * WAVE : two ? 2 * WAVE : WAVE);
         {   // (world.h: what the next step's early k_obs reads; turns as for ped_snap)
             const bool partial = d.act_list != nullptr;
             d.rec_snap_out = h->early ? h->rec_snap[h->view_seq & 1] : nullptr;
             d.rec_snap_out2 = h->early && partial ? h->rec_snap[(h->view_seq + 1) & 1] : nullptr;
             if (!partial) h->view_seq += 1;
         }
-        const int variant = (h->pow2 ? 4 : 0) | (h->geom.Wv % 4 == 0 ? 2 : 0) | (h->stamp ? 1 : 0);
-#define VIEW_CASE(N, P2, A4_, ST)                                                                                               \
-    case N:                                                                                                                     \
-        if (eight) TIMED(h, IMGENV_K_VIEW, st, (hipExtLaunchKernelGGL((k_view<P2, A4_, ST, 8>), gv, bv, (uint32_t)h->lds_view, st, nullptr, nullptr, 0, d)));      \
-        else if (small) TIMED(h, IMGENV_K_VIEW, st, (hipExtLaunchKernelGGL((k_view<P2, A4_, ST, 4>), gv, bv, (uint32_t)h->lds_view, st, nullptr, nullptr, 0, d))); \
-        else if (two) TIMED(h, IMGENV_K_VIEW, st, (hipExtLaunchKernelGGL((k_view<P2, A4_, ST, 2>), gv, bv, (uint32_t)h->lds_view, st, nullptr, nullptr, 0, d)));   \
-        else TIMED(h, IMGENV_K_VIEW, st, (hipExtLaunchKernelGGL((k_view<P2, A4_, ST, 1>), gv, bv, (uint32_t)h->lds_view, st, nullptr, nullptr, 0, d)));            \
-        break;
-        switch (variant) {
-            VIEW_CASE(7, true, true, true)
-            VIEW_CASE(6, true, true, false)
-            VIEW_CASE(5, true, false, true)
-            VIEW_CASE(4, true, false, false)
-            VIEW_CASE(3, false, true, true)
-            VIEW_CASE(2, false, true, false)
-            VIEW_CASE(1, false, false, true)
-            VIEW_CASE(0, false, false, false)
-        }
-#undef VIEW_CASE
+        TIMED(h, IMGENV_K_VIEW, st, (hipExtLaunchKernelGGL(k_view_for(p, v.nw), dim3(v.view.grid), dim3(v.view.block), (uint32_t)v.view.lds, st, nullptr, nullptr, 0, d)));
     }
     // no launch for the per-robot scalars: the k_view / k_obs wavefront that completes a group of 64 robots runs them
     // (tail_group).  The caller's stream ends the step behind both side streams
@@ -1825,17 +1737,13 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
     h->launches += 3;
     if (h->stack_on && h->stack.n_fields > 0) {
         // the observation stacks (stack.h), behind the join of the side streams and in front of the seal: a step pushes every local
-        // robot's new frames, a reset chain restarts the stacks of the robots it covers -- all of them, or the worlds of the chain's
-        // list, whose length the host knows (act_nw) or a kernel has counted (act_n_dev: the grid is sized for every world and strides)
+        // robot's new frames, a reset chain restarts the stacks of the robots it covers (plan_tail_rows)
         StackDev sd = h->stack;
         sd.list = is_reset ? d.act_list : nullptr;
         sd.n_dev = is_reset ? d.act_n_dev : nullptr;
         sd.n_worlds = d.act_nw;
-        const size_t rows = sd.list ? (size_t)(sd.n_dev ? std::min(d.act_nw * h->Rw, std::max(h->act_hint, h->Rw)) : d.act_nw * h->Rw) : (size_t)h->RL;
-        const size_t items = rows * sd.chunks_per_robot;
-        const unsigned blocks = (unsigned)std::min<size_t>(STACK_MAX_BLOCKS, std::max<size_t>(1, (items + STACK_BLOCK - 1) / STACK_BLOCK));
-        if (is_reset) k_stack<true><<<dim3(blocks), dim3(STACK_BLOCK), 0, st>>>(sd);
-        else k_stack<false><<<dim3(blocks), dim3(STACK_BLOCK), 0, st>>>(sd);
+        const LaunchShape g = plan_stack_launch(p, c, sd.chunks_per_robot);
+        (is_reset ? k_stack<true> : k_stack<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(sd);
         h->launches += 1;
     }
     if (h->ep_on) {
@@ -1846,10 +1754,8 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
         ed.list = is_reset ? d.act_list : nullptr;
         ed.n_dev = is_reset ? d.act_n_dev : nullptr;
         ed.n_worlds = d.act_nw;
-        const size_t rows = ed.list ? (size_t)(ed.n_dev ? std::min(d.act_nw * h->Rw, std::max(h->act_hint, h->Rw)) : d.act_nw * h->Rw) : (size_t)h->RL;
-        const unsigned blocks = (unsigned)std::min<size_t>(EP_MAX_BLOCKS, std::max<size_t>(1, (rows + EP_BLOCK - 1) / EP_BLOCK));
-        if (is_reset) k_episodes<true><<<dim3(blocks), dim3(EP_BLOCK), 0, st>>>(ed);
-        else k_episodes<false><<<dim3(blocks), dim3(EP_BLOCK), 0, st>>>(ed);
+        const LaunchShape g = plan_episodes_launch(p, c);
+        (is_reset ? k_episodes<true> : k_episodes<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(ed);
         h->launches += 1;
     }
     HIPCHK(hipGetLastError());
@@ -1886,7 +1792,6 @@ __global__ __launch_bounds__(256) void k_stage_copy(const StageSeg* __restrict__
 //   n_seg * per_seg : the segment copies (trajectories, RVO polygons, per-world tables, the world list)
 //   n_worlds * MAP_BLOCKS : obs_map_ of each world being reset starts from the static map again (img_env.cpp:166-168)
 //   robots, pedestrians : init_pose / set_goal / setPedPos ..., straight from the page-locked host blocks
-#define MAP_BLOCKS 8
 struct ResetArgs {
     const StageSeg* table;
     int n_seg, per_seg;
@@ -2097,6 +2002,9 @@ __global__ __launch_bounds__(256) void k_reset_obstacles(DevWorld w, const ObstI
 }
 
 #include "spawn_device.h"  // device-side auto-reset: k_spawn_fill, k_finished_dev, k_respawn, k_restore_maps_dev
+
+static auto k_reset_obstacles_for(const PlanHandle& p) { return p.pow2 ? k_reset_obstacles<true> : k_reset_obstacles<false>; }
+static auto k_restore_maps_dev_for(const PlanHandle& p) { return p.pow2 ? k_restore_maps_dev<true> : k_restore_maps_dev<false>; }
 
 // the obstacle list of one world's reset batch: instances for k_reset_obstacles, the RVO polygons with their BSP
 // (RVOScene::addObs + processObs, rvoscene.h:19-26, img_env.cpp:283) and the social-force segments (pedscene.h:22-26)
@@ -2345,8 +2253,6 @@ static int reset_checks(imgenv* h, int n, const imgenv_reset_batch* b, int peds_
     return 0;
 }
 
-// Device half of a reset, for every world (list == nullptr) or the n worlds listed: one upload launch, the obstacle
-// maps, the robot / pedestrian state, then view_agent + get_states (img_env.cpp:285-286) for those worlds' robots.
 // page-locked blocks for the robots / pedestrians of the n worlds of this reset, in list order (read by k_reset_apply)
 static int reset_blocks(imgenv* h, int n, const int* list) {
     unsigned char* p = nullptr;
@@ -2411,6 +2317,7 @@ static int reset_launch(imgenv* h, const int* list, int n, hipStream_t st, int w
     if (n_inst) RTRY(stage_put(h, h->d_oinst, h->oinst.data(), n_inst * sizeof(ObstInst)));
     h->oinst.clear();
     set_active(h, list ? h->d_act_list : nullptr, n);
+    const ResetPlan rp = plan_reset(h->plan, chain_facts(h, 1), h->segs.size(), h->seg_max, n_inst);
     {   // one launch: segment copies | map restore | robot state | pedestrian state
         ResetArgs a;
         unsigned char* table = nullptr;
@@ -2418,7 +2325,7 @@ static int reset_launch(imgenv* h, const int* list, int n, hipStream_t st, int w
         memcpy(table, h->segs.data(), h->segs.size() * sizeof(StageSeg));
         a.table = (const StageSeg*)table;
         a.n_seg = (int)h->segs.size();
-        a.per_seg = (int)std::min<size_t>((h->seg_max / 16 + 255) / 256 + 1, 16);
+        a.per_seg = rp.per_seg;
         a.list = h->pin_list;
         a.n_worlds = d.act_nw;
         a.static_map = h->d_static_map;
@@ -2435,17 +2342,14 @@ static int reset_launch(imgenv* h, const int* list, int n, hipStream_t st, int w
         a.n_robots = d.act_ng;
         a.n_peds = d.act_np;
         a.whole = whole;
-        a.stamp = h->stamp ? 1 : h->sum ? 2 : 0;
-        const size_t blocks = (size_t)a.n_seg * a.per_seg + (size_t)a.n_worlds * MAP_BLOCKS + (a.n_robots + 255) / 256 + (a.n_peds + 255) / 256;
-        k_reset_apply<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(d, a);
+        a.stamp = h->plan.layer;
+        k_reset_apply<<<dim3(rp.apply.grid), dim3(rp.apply.block), 0, st>>>(d, a);
         h->segs.clear();
         h->seg_max = 0;
     }
-    if (n_inst) {
-        if (h->pow2) k_reset_obstacles<true><<<dim3((unsigned)n_inst), dim3(256), 0, st>>>(d, (const ObstInst*)h->d_oinst, h->stamp ? 1 : h->sum ? 2 : 0, nullptr, 0, 1, nullptr, nullptr);
-        else k_reset_obstacles<false><<<dim3((unsigned)n_inst), dim3(256), 0, st>>>(d, (const ObstInst*)h->d_oinst, h->stamp ? 1 : h->sum ? 2 : 0, nullptr, 0, 1, nullptr, nullptr);
-    }
-    if (d.sharded) k_reset_bbox<<<dim3((h->RL + 255) / 256), dim3(256), 0, st>>>(d, h->pin_rob3);
+    if (n_inst)
+        k_reset_obstacles_for(h->plan)<<<dim3(rp.obstacles.grid), dim3(rp.obstacles.block), 0, st>>>(d, (const ObstInst*)h->d_oinst, h->plan.layer, nullptr, 0, 1, nullptr, nullptr);
+    if (d.sharded) k_reset_bbox<<<dim3(rp.bbox.grid), dim3(rp.bbox.block), 0, st>>>(d, h->pin_rob3);
     HIPCHK(hipGetLastError());
     h->launches = 2;
     const int rc = launch_views(h, st, 1);
@@ -2842,21 +2746,10 @@ extern "C" int imgenv_step_begin(imgenv_t* h, const float* actions, void* stream
         k_evac<<<dim3(h->P), dim3(WAVE), 0, st>>>(d);
         h->launches += 2;
     }
-    // _step_robot (img_env.cpp:388-410)
-    // (a robot shard in SUM mode draws its own robots in this call anyway: the move goes into that launch, whoever runs the exchange)
-    const bool fuse_ok = h->n_sub >= 1 && h->n_sub + 2 <= INT_ITEMS;
-    const bool whole_call = h->in_step && !d.sharded && !h->comm && h->RL == h->R;  // imgenv_step on a handle that owns its world
-    const bool fuse_small = (whole_call || d.sum_shard) && fuse_ok && (h->P == 0 ? h->RL <= 4096 : h->RL <= 1024);
-    // (the move inside the raster launch of BIG handles, with the early observation gated on that launch, was measured again in round 6:
-    // 95.0 -> 103.1 us per headline step, cfg-4 117-123 -> 126, cfg-5 280 -> 282: the move's serial chain in front of every robot's
-    // raster costs more than the launch it saves)
-    const bool fuse_move = fuse_small;
-    // early-observation step (world.h): k_obs goes out with the move, on its side stream, instead of behind it -- behind a gate that
-    // opens when the caller's stream reaches this step's move (world.h: sync; only where gates work: k_gate_probe)
-    static const int force_early = getenv("IMGENV_EARLY_OBS") ? atoi(getenv("IMGENV_EARLY_OBS")) : -1;  // (measurement switch)
-    const bool live_peds = h->NA == 0;  // (a social-force crowd a step ahead: see imgenv_create)
-    const bool early_step = h->early && h->gates_work && !fuse_move && !h->chain_open && (live_peds ? h->sfm_ahead : h->orca_seq > 0) &&
-                            h->view_seq > 0 && force_early != 0;
+    // _step_robot (img_env.cpp:388-410): the move in a launch of its own, or left to the raster launch; k_obs behind it or, in an
+    // early-observation step (world.h), with it on its side stream, behind a gate that opens when the caller's stream reaches the move
+    const StepPlan sp = plan_step(h->plan, chain_facts(h, 0));
+    const bool early_step = sp.early_step, live_peds = h->NA == 0;  // (a social-force crowd a step ahead: see imgenv_create)
     if (early_step) h->gate_seq += 1;
     // k_obs beside the move instead of behind it (world.h): it needs nothing of this step but the actions.  It waits behind a gate
     // that opens when the caller's stream reaches the move (k_gate): everything queued there in front of the step is then complete
@@ -2880,7 +2773,7 @@ extern "C" int imgenv_step_begin(imgenv_t* h, const float* actions, void* stream
         h->early_step = true;
         return 0;
     };
-    if (fuse_move && d.sum_shard) {  // k_move_raster over the shard's own robots and the pedestrians, now (in front of the exchange); the observation behind it
+    if (sp.sum_shard_now) {  // k_move_raster over the shard's own robots and the pedestrians, now (in front of the exchange); the observation behind it
         h->move_actions = actions;
         if (int rc = launch_rasters(h, st, 0, true, true, true)) return rc;
         h->launches += 1;
@@ -2890,25 +2783,19 @@ extern "C" int imgenv_step_begin(imgenv_t* h, const float* actions, void* stream
         HIPCHK(hipGetLastError());
         return sfm_launch_ahead(h);
     }
-    if (fuse_move) {  // k_move_raster, launched by launch_views (the fork of the side stream with it)
+    if (sp.fuse_move) {  // k_move_raster, launched by launch_views (the fork of the side stream with it)
         h->move_pending = true;
         h->move_actions = actions;
         return sfm_launch_ahead(h);
     }
-    {   // ... and the pedestrians' move (img_env.cpp:343-358) in the same launch
-        const bool peds = h->P > 0 && (h->NA > 0 || h->cfg.ped_scene_type == IMGENV_SCENE_DATASET);
-        if (h->n_sub >= 1 && h->n_sub + 2 <= INT_ITEMS) {
-            const int nb_robot = (h->RL + INT_ROBOTS - 1) / INT_ROBOTS, nb_ped = peds ? (h->P + INT_G * INT_ROBOTS - 1) / (INT_G * INT_ROBOTS) : 0;
-            // (the fork of the side streams follows right behind the move, on its dispatch packet)
-            h->fork_on_move = h->P > 0 && !h->serial && !h->chain_open;
-            TIMED(h, IMGENV_K_INTEGRATE, st, (hipExtLaunchKernelGGL(k_integrate, dim3(nb_robot + nb_ped), dim3(INT_G * INT_ROBOTS), 0, st, nullptr,
-                                                                   h->fork_on_move ? h->ev_fork : nullptr, 0, d, actions, nb_robot, h->n_sub, h->elapsed,
-                                                                   early_step ? h->gate_seq : 0u)));
-        } else {
-            const int nb_robot = (h->RL + 127) / 128, nb_ped = peds ? (h->P + 127) / 128 : 0;
-            TIMED(h, IMGENV_K_INTEGRATE, st, (k_integrate_serial<<<dim3(nb_robot + nb_ped), dim3(128), 0, st>>>(d, actions, nb_robot, h->elapsed)));
-        }
-    }
+    // (the fork of the side streams follows right behind the move, on its dispatch packet)
+    h->fork_on_move = sp.fork_on_move;
+    if (!sp.serial_move)
+        TIMED(h, IMGENV_K_INTEGRATE, st, (hipExtLaunchKernelGGL(k_integrate, dim3(sp.move.grid), dim3(sp.move.block), 0, st, nullptr,
+                                                               sp.fork_on_move ? h->ev_fork : nullptr, 0, d, actions, sp.nb_robot, h->n_sub, h->elapsed,
+                                                               early_step ? h->gate_seq : 0u)));
+    else
+        TIMED(h, IMGENV_K_INTEGRATE, st, (k_integrate_serial<<<dim3(sp.move.grid), dim3(sp.move.block), 0, st>>>(d, actions, sp.nb_robot, h->elapsed)));
     h->launches += 1;
     set_tail_fields(h, 0, h->elapsed + 1);  // imgenv_step_end counts the step; k_obs goes out before that
     if (early_step) {
@@ -2983,14 +2870,21 @@ static uint64_t spawn_cfg_fingerprint(const imgenv_spawn_cfg& c) {
     return hsh;
 }
 
-extern "C" int imgenv_step_autoreset(imgenv_t* h, const float* actions, const imgenv_spawn_cfg* cfg, uint64_t seed0, int32_t* worlds_out,
-                                     int32_t cap, int32_t* n_out, void* stream) {
-    if (!h || !actions || !n_out) FAIL(IMGENV_EINVAL, "null argument");
+// what both auto-reset calls ask of their arguments
+static int autoreset_checks(imgenv* h, const float* actions, const imgenv_spawn_cfg* cfg, const char* who) {
+    if (!h || !actions) FAIL(IMGENV_EINVAL, "null argument");
     if (int rc = spawn_cfg_check(cfg)) return rc;
     if (cfg->n_robots != h->Rw || cfg->n_peds != h->Pw)
         FAIL(IMGENV_EINVAL, "spawn cfg is for %d robots / %d pedestrians, a world of this handle has %d / %d", cfg->n_robots,
              cfg->n_peds, h->Rw, h->Pw);
-    if (h->RL != h->R) FAIL(IMGENV_EINVAL, "imgenv_step_autoreset needs all robots of every world on this handle");
+    if (h->RL != h->R) FAIL(IMGENV_EINVAL, "%s needs all robots of every world on this handle", who);
+    return 0;
+}
+
+extern "C" int imgenv_step_autoreset(imgenv_t* h, const float* actions, const imgenv_spawn_cfg* cfg, uint64_t seed0, int32_t* worlds_out,
+                                     int32_t cap, int32_t* n_out, void* stream) {
+    if (!n_out) FAIL(IMGENV_EINVAL, "null argument");
+    if (int rc = autoreset_checks(h, actions, cfg, "imgenv_step_autoreset")) return rc;
     *n_out = 0;
     static const bool trace = getenv("IMGENV_TRACE_RESET") != nullptr;  // where the host's time goes, every 200 calls
     double* acc = h->trace_acc;
@@ -3075,10 +2969,6 @@ extern "C" int imgenv_step_autoreset(imgenv_t* h, const float* actions, const im
 
 
 // ---------------------------------------------------------------------------------------- device-side auto-reset
-template <typename T>
-static int sd_alloc(imgenv* h, T** out, size_t n) {
-    return dev_alloc(h, out, n);
-}
 static int spawn_device_setup(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t seed0, hipStream_t st) {
     const int na = cfg->n_robots + cfg->n_peds, nob = cfg->n_obstacles;
     if (na > SPAWN_MAX_AGENTS || nob > SPAWN_MAX_OBST)
@@ -3284,17 +3174,12 @@ static int autoreset_device_chain(imgenv* h, const float* actions, hipStream_t s
     h->fill_pending = false;
     const MapSel maps = map_sel(h);
     k_respawn<<<dim3(W), dim3(WAVE), 0, st>>>(d, c, h->elapsed, maps);
-    // grids for a guess of the finished worlds (four times the last count; the kernels stride over the rest if there are more)
-    const int last_n = h->finished_host[0];  // (page-locked, written by k_finished_dev: stale by a step or two)
-    const int guess = std::min(W, std::max(16, 4 * std::max(last_n, 0)));
-    const int restore_blocks = 4 * MAP_BLOCKS;  // per world
-    if (h->pow2) k_restore_maps_dev<true><<<dim3((unsigned)(guess * restore_blocks)), dim3(256), 0, st>>>(d, c, h->d_static_map, maps, h->stamp ? 1 : h->sum ? 2 : 0, restore_blocks);
-    else k_restore_maps_dev<false><<<dim3((unsigned)(guess * restore_blocks)), dim3(256), 0, st>>>(d, c, h->d_static_map, maps, h->stamp ? 1 : h->sum ? 2 : 0, restore_blocks);
-    if (nob > 0) {
-        const int parts = 4;
-        if (h->pow2) k_reset_obstacles<true><<<dim3((unsigned)(guess * nob * parts)), dim3(256), 0, st>>>(d, c.inst_out, h->stamp ? 1 : h->sum ? 2 : 0, c.fin_n, nob, parts, c.w_inst, c.w_inst_valid);
-        else k_reset_obstacles<false><<<dim3((unsigned)(guess * nob * parts)), dim3(256), 0, st>>>(d, c.inst_out, h->stamp ? 1 : h->sum ? 2 : 0, c.fin_n, nob, parts, c.w_inst, c.w_inst_valid);
-    }
+    // grids for a guess of the finished worlds (plan_dev_reset; the count is page-locked, written by k_finished_dev: stale by a step or two)
+    const PlanHandle& p = h->plan;
+    const DevResetPlan rp = plan_dev_reset(p, h->finished_host[0], nob);
+    k_restore_maps_dev_for(p)<<<dim3(rp.restore.grid), dim3(rp.restore.block), 0, st>>>(d, c, h->d_static_map, maps, p.layer, rp.restore_blocks);
+    if (nob > 0)
+        k_reset_obstacles_for(p)<<<dim3(rp.obstacles.grid), dim3(rp.obstacles.block), 0, st>>>(d, c.inst_out, p.layer, c.fin_n, nob, rp.parts, c.w_inst, c.w_inst_valid);
     HIPCHK(hipGetLastError());
     if (h->stamp) {
         // The step's rasters have stamped the finished worlds' agents where they stood BEFORE the reset, with this step's tag,
@@ -3302,10 +3187,7 @@ static int autoreset_device_chain(imgenv* h, const float* actions, hipStream_t s
         // own, under which those stamps have expired like any older ones (two tags per step; the sweep comes round accordingly)
         h->stamp_seq += 1;
         d.stamp_tag = h->stamp_seq % STAMP_TAGS + 1;
-        if (h->stamp_seq % STAMP_TAGS == 0) {
-            const unsigned blocks = (unsigned)((d.act_cells / 4 + 255) / 256 + 1);
-            k_cell_base<<<dim3(blocks), dim3(256), 0, st>>>(d);
-        }
+        if (h->stamp_seq % STAMP_TAGS == 0) k_cell_base<<<dim3(plan_compose_blocks(p, chain_facts(h, 1))), dim3(256), 0, st>>>(d);
     }
     // the launches behind: sized for every world, the list and its length read from device memory
     set_active(h, c.fin_list, W);
@@ -3320,12 +3202,7 @@ static int autoreset_device_chain(imgenv* h, const float* actions, hipStream_t s
 }
 
 extern "C" int imgenv_step_autoreset_device(imgenv_t* h, const float* actions, const imgenv_spawn_cfg* cfg, uint64_t seed0, void* stream) {
-    if (!h || !actions) FAIL(IMGENV_EINVAL, "null argument");
-    if (int rc = spawn_cfg_check(cfg)) return rc;
-    if (cfg->n_robots != h->Rw || cfg->n_peds != h->Pw)
-        FAIL(IMGENV_EINVAL, "spawn cfg is for %d robots / %d pedestrians, a world of this handle has %d / %d", cfg->n_robots,
-             cfg->n_peds, h->Rw, h->Pw);
-    if (h->RL != h->R) FAIL(IMGENV_EINVAL, "imgenv_step_autoreset_device needs all robots of every world on this handle");
+    if (int rc = autoreset_checks(h, actions, cfg, "imgenv_step_autoreset_device")) return rc;
     if (!h->has_reset) FAIL(IMGENV_ESTATE, "step before reset");
     if (h->obs_forked) FAIL(IMGENV_ESTATE, "imgenv_step_autoreset_device between imgenv_step_begin and imgenv_step_end");
     hipStream_t st = (hipStream_t)stream;
@@ -3340,10 +3217,7 @@ extern "C" int imgenv_step_autoreset_device(imgenv_t* h, const float* actions, c
     }
     if (int rc = spawn_dev_refresh(h, st)) return rc;
     if (!h->d_act_list) RTRY(dev_alloc(h, &h->d_act_list, (size_t)h->W));
-    {   // how many worlds the last steps reset (page-locked, written by k_finished_dev; stale by a step or two: a hint only)
-        const int last = h->finished_host[0];
-        h->act_hint = std::max(8, 2 * std::max(last, 0)) * std::max(std::max(h->Rw, h->Pw), 1);  // (twice the last count: with four times, 64 worlds of 4 pedestrians sat ON the 1024 threshold and flipped between the kernel variants)
-    }
+    h->act_hint = plan_act_hint(h->plan, h->finished_host[0]);  // (page-locked, written by k_finished_dev; stale by a step or two: a hint only)
     const int rc = autoreset_device_chain(h, actions, st);
     if (rc == IMGENV_OK) h->dev_reset_used = true;
     return rc;
@@ -3639,7 +3513,7 @@ extern "C" int imgenv_cv_resize_u8(int kind, const uint8_t* src, int32_t sh, int
 extern "C" int imgenv_step_launches(imgenv_t* h) { return h ? h->launches : 0; }
 extern "C" int imgenv_layer_mode(imgenv_t* h) {
     if (!h) return -1;
-    return (h->stamp ? 1 : h->sum ? 2 : 0) | (h->d.sum_shard ? 4 : 0) | (h->early && h->gates_work ? 8 : 0) | (h->sfm_ahead ? 16 : 0);
+    return h->plan.layer | (h->d.sum_shard ? 4 : 0) | (h->early && h->gates_work ? 8 : 0) | (h->sfm_ahead ? 16 : 0);
 }
 
 // debug: read (and clear) the per-phase cycle counters of IMGENV_PHASE_PROFILE builds

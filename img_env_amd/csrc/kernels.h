@@ -418,19 +418,7 @@ __device__ __forceinline__ void tail_arrive_obs(const DevWorld& w, int t, int l,
 // (History: one pedestrian per wavefront with everything on lane 0 out of HBM took 129 us at 2048 shipped envs x 4 pedestrians,
 // one lane per agent out of LDS 62 us alone -- a single agent's chain of ~9000 dependent instructions.)
 __device__ __forceinline__ void state_robot(const DevWorld& w, int l);  // Agent::get_state, below
-struct OrcaLaunch {
-    int G;          // agents per wavefront (1, 2 or 4: one row of 16 lanes each)
-    int groups;     // wavefronts per world
-    int cap_on;     // obstacle neighbours an agent's scratch holds (the handle's largest obstacle table, at most ORCA_MAX_ON)
-    int cap_stack;  // tree levels its walk may stack up
-    int stage_obst; // obstacle segments / nodes the LDS staging area holds (0: read them from HBM, everything on the home lane)
-    int fold_side;  // handles of several worlds: this kernel also does k_side_robots' part for its world (a launch less per phase):
-                    // the world's robot agents out of the robot records (setRobotPos, img_env.cpp:411-417), Agent::get_state of
-                    // its robots (group 0), and the robots taken as neighbour candidates directly instead of through near lists
-    int zero_vel;   // (with fold_side) a reset: robot agents start at rest
-};
-#define ORCA_GROUP_MAX 4
-#define ORCA_ROW 16
+// (OrcaLaunch: launch_plan.h)
 __host__ __device__ inline size_t orca_row_bytes(const OrcaLaunch& L) {  // an agent's scratch + per-node records + the row's exchange words
     static_assert(ORCA_ROW * 4 % 16 == 0 && sizeof(RvoObstDev) % 4 == 0, "k_orca's LDS carving keeps its uint4 records 16-byte aligned");
     return orca_scratch_bytes(L.cap_on, L.cap_stack) + (size_t)L.stage_obst * 16 + ORCA_ROW * 4;
@@ -1232,9 +1220,7 @@ __device__ __forceinline__ void integrate_finish(const DevWorld& w, int l, doubl
     w.is_arr[l] = is_arrive ? 1 : 0;
 }
 
-#define INT_G 8        // lanes per robot in k_integrate
-#define INT_ITEMS 32   // sin / cos pairs per robot: the sub-step headings, the new heading and its half
-#define INT_ROBOTS 32  // robots per 256-thread block
+// (INT_G lanes per robot, INT_ITEMS sin / cos pairs per robot, INT_ROBOTS robots per block: launch_plan.h)
 
 // One launch for the two independent per-agent updates of a step: blocks [0, nb_robot) integrate the robots,
 // the blocks behind them move the ORCA pedestrians by the velocities k_orca solved for.

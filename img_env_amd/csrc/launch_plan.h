@@ -1,0 +1,419 @@
+// launch_plan.h -- the launch-shape rules as pure functions: which kernel variant runs at which grid, block
+// and LDS size, decided from plain facts about the handle (fixed at imgenv_create) and about the chain of launches in hand.
+// Nothing of HIP in here: plain C++17, compiled by g++ for tests/host/launch_plan_check.cpp, which pins every threshold
+// below with its two neighbours.  The launch functions of imgenv_hip.hip build the facts, ask for a plan and issue the
+// launches in stream order; what is launched at what shape is decided here, the ordering (forks, joins, gates) there.
+//
+// Also the one home of the constants that both the kernels and these rules read, and of `pick`, the step from a plan's
+// runtime selector to a template instantiation.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <type_traits>
+
+#include "../../include/imgenv.h"
+
+// ---------------------------------------------------------------------------------------- shared constants
+#define WAVE 64
+#define INT_G 8        // lanes per robot in k_integrate
+#define INT_ITEMS 32   // sin / cos pairs per robot: the sub-step headings, the new heading and its half
+#define INT_ROBOTS 32  // robots per 256-thread block
+#define VBC_T 256    // k_crop_big: up to 4 wavefronts
+#define VBB_T 256    // k_beams_big: one beam per thread
+#define VBT_T 256    // k_taps_big: one sensor_map pixel per thread (host_tables.h lists its chunks of this many pixels)
+#define VBF_T 256    // k_fullview_big
+#define STAMP_MAX_ROBOTS (1 << 19)
+#define STAMP_TAGS 255
+#define MAP_BLOCKS 8  // k_reset_apply: workgroups that restore one world's map
+#define STACK_BLOCK 256
+#define STACK_MAX_BLOCKS 2048
+#define EP_BLOCK 256
+#define EP_MAX_BLOCKS 1024
+#define ORCA_NEAR_CAP 64  // robot agents a pedestrian can have within its 0.5 m neighbour range before k_orca falls back to the full scan
+#define ORCA_MAX_ON 118   // obstacle neighbours kept per agent
+#define ORCA_MAX_AN 10    // rvoscene.h:57,63 maxNeighbors
+#define ORCA_MAX_LINES (ORCA_MAX_ON + ORCA_MAX_AN)
+#define ORCA_STACK 128
+#define ORCA_GROUP_MAX 4
+#define ORCA_ROW 16
+#define SFM_MAX_AGENTS 256
+
+enum { LAYER_COMPOSED = 0, LAYER_STAMP = 1, LAYER_SUM = 2 };  // the class layer's mode (world.h), as the kernels take it
+
+// ---------------------------------------------------------------------------------------- from selector to instantiation
+// pick(f, a, b, ...) calls f(A, B, ...) with every runtime selector turned into a compile-time constant: a bool into
+// std::true_type / std::false_type, a OneOf<V0, V1, ...>{v} into std::integral_constant<int, Vk> for the Vk that equals v
+// (the LAST of the list when none does).  Each kernel family with more than two variants has one function that names its
+// instantiations through this (imgenv_hip.hip: k_view_for, ...); launches and imgenv_create's LDS attributes both go through
+// that function, so what gets the attribute is what can be launched.
+template <int... Vs>
+struct OneOf {
+    int v;
+};
+template <class F>
+inline void pick(F&& f) {
+    f();
+}
+template <class F, class... Rest>
+inline void pick(F&& f, bool b, Rest... rest);
+template <class F, int V0, int... Vs, class... Rest>
+inline void pick(F&& f, OneOf<V0, Vs...> o, Rest... rest) {
+    if constexpr (sizeof...(Vs) > 0) {
+        if (o.v != V0) return pick(f, OneOf<Vs...>{o.v}, rest...);
+    }
+    pick([&](auto... cs) { f(std::integral_constant<int, V0>{}, cs...); }, rest...);
+}
+template <class F, class... Rest>
+inline void pick(F&& f, bool b, Rest... rest) {
+    if (b) return pick([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    pick([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+
+// ---------------------------------------------------------------------------------------- facts
+// what imgenv_create fixes (imgenv_stack_enable / imgenv_episodes_enable add nothing here: their chunking is an argument)
+struct PlanHandle {
+    int R = 0, RL = 0, P = 0, W = 1, Rw = 0, Pw = 0, NA = 0;  // robots, local robots, pedestrians, worlds, per world, RVO agents
+    bool sharded = false, sum_shard = false;                    // a robot shard; ... in SUM mode (world.h)
+    bool pow2 = false;                                          // the resolution is an exact power of two
+    int layer = LAYER_COMPOSED;
+    bool serial = false;                                        // IMGENV_SERIAL=1: no side streams
+    bool big_view = false, view_a4 = false;                     // view_big.h's kernels; Wv % 4 == 0
+    int B = 0;                                                  // beams
+    size_t lds_view = 0, lds_obs = 0, lds_view_big = 0;
+    int obs_E = 0, n_sub = 0, relation = 0, scene = 0;
+    bool early = false, gates_work = false;
+    size_t Gs = 0;                                              // cells of one world's grid layer
+    int box_cells = 0;                                          // the rasters' LDS box
+    int big_max_crop = 1, big_full_chunks = 1, big_tap_chunks_dyn = 0;
+    bool big_bits_in_lds = true, crop_map = false;
+    int img_w = 0, img_h = 0;
+    bool resize = false, keep_view_maps = false;
+};
+// what the chain of launches in hand adds
+struct PlanChain {
+    int act_ng = 0, act_np = 0, act_nl = 0, act_nw = 0;  // robots, pedestrians, local robots, worlds the chain covers
+    size_t act_cells = 0;
+    bool listed = false;      // a world list is in use ...
+    bool n_dev = false;       // ... whose length only the device knows (act_n_dev): grids by every world, variants by act_hint
+    int act_hint = 0;
+    bool is_reset = false, moved = false, local_only = false;
+    unsigned stamp_seq = 0;
+    int orca_cap = 1;         // the largest obstacle table any world of the handle can hold
+    // what imgenv_step_begin reads
+    bool chain_open = false, orca_ran = false, view_ran = false, in_step = false, comm = false, crowd_ahead = false;
+    bool early_off = false;   // IMGENV_EARLY_OBS=0 (measurement switch)
+};
+struct LaunchShape {
+    unsigned grid = 0, block = 0;
+    size_t lds = 0;
+};
+
+// the count a variant is chosen by: what the launch covers, or what a device-side reset chain is expected to cover
+inline int plan_by_hint(const PlanChain& c, int n) { return c.n_dev ? std::min(n, c.act_hint) : n; }
+// k_integrate's LDS table of headings holds the step's sub-steps; otherwise k_integrate_serial, no fused move, no early step
+inline bool plan_integrate_fits(int n_sub) { return n_sub >= 1 && n_sub + 2 <= INT_ITEMS; }
+// the pedestrians move in the step's move launch (k_integrate, k_move_raster): RVO and recorded crowds; a social-force crowd has moved in k_sfm
+inline bool plan_peds_move(const PlanHandle& h) { return h.P > 0 && (h.NA > 0 || h.scene == IMGENV_SCENE_DATASET); }
+// k_compose / k_cell_base: 4 cells per thread over everything, or a fixed number of 256-thread blocks per listed world
+inline unsigned plan_compose_blocks(const PlanHandle& h, const PlanChain& c) {
+    return c.listed ? (unsigned)(((h.Gs / 4 + 255) / 256) * c.act_nw) : (unsigned)((c.act_cells / 4 + 255) / 256 + 1);
+}
+
+// ---------------------------------------------------------------------------------------- imgenv_create
+// STAMP mode of the class layer instead of two owner layers + k_compose.  Composed wins where the agents cover a good part of
+// the map (the headline world: 0.133 against 0.138 ms per step), stamped where the maps are much larger than what the agents
+// touch (8192 one-robot worlds: 52 against 43 M robot-steps/s) -- measured: composed wins at 277 cells per agent, stamped at 1000
+// ... and handles whose rasters and views are single small launches (at most 1024 blocks: bound by launch latency, not by
+// their work) are better off without the k_compose launch however dense they are (cfg-2, 1024 robots at 156 cells per
+// agent: 38.8 -> 36.3 us per step)
+inline bool plan_layer_stamp(bool owns_all, size_t cells, int R, int P, uint32_t flags) {
+    bool stamp = owns_all && cells > (size_t)512 * (R + P);
+    if (owns_all && R + P <= 1024) stamp = true;
+    if (flags & IMGENV_FLAG_COMPOSE_DENSE) stamp = false;
+    if ((flags & IMGENV_FLAG_COMPOSE_SPARSE) && owns_all) stamp = true;
+    if (stamp && R >= STAMP_MAX_ROBOTS) stamp = false;
+    return stamp;
+}
+// sort slots of k_obs: a power of two, 64 * E of them in registers up to 1024 pedestrians (E = 0: LDS sort)
+inline int plan_obs_slots(int Pw) {
+    int PP = WAVE;
+    while (PP < Pw) PP <<= 1;
+    return PP;
+}
+inline int plan_obs_E(int PP) { return PP <= 1024 ? PP / WAVE : 0; }
+// k_view: src u8 (+ dummy cells) | hit u32 | column terms | cursors of the final pass | largest hit step of blocks of beams (3 levels)
+inline size_t plan_lds_view(size_t view_cells, size_t hit_stride, int Wv) {
+    return ((view_cells + 16) & ~(size_t)15) + 4 * hit_stride + 16 * (size_t)Wv + 16 + 4 * (2 * (hit_stride / 8 + 1) + 4);
+}
+inline size_t plan_lds_obs(int obs_E, int PP, int Pw) {
+    return (obs_E == 0 ? (size_t)PP * 8 : 0) + (size_t)(Pw > 0 ? Pw : 1) * 8 + (size_t)PP * 4 + WAVE * 7 * 4 + 16;
+}
+// k_beams_big: the occupied plane of the crop bitmap next to the hit words; beyond 150 KiB (views above ~1000 x 1000 cells) the
+// beams read the bitmap from HBM
+inline bool plan_big_bits_in_lds(size_t big_words) { return 4 * big_words <= 150 * 1024; }
+inline size_t plan_lds_view_big(size_t big_words) { return (plan_big_bits_in_lds(big_words) ? 4 * big_words : 0) + 16; }
+inline size_t plan_lds_fullview(int B) { return 16 * (size_t)((B + 4) / 4); }  // k_fullview_big: hit words (+ the dummy beam)
+// k_taps_big: hit words (+ the dummy beam) | 16 tap values per pixel | list of the taps that need a second look | counter
+inline size_t taps_lds_bytes(int B) { return plan_lds_fullview(B) + 16 * (size_t)VBT_T + 2 * 16 * (size_t)VBT_T + 16; }
+inline constexpr size_t LDS_DEFAULT_MAX = 64 * 1024, LDS_MAX = 160 * 1024;  // above the first a kernel needs hipFuncAttributeMaxDynamicSharedMemorySize
+
+// ---------------------------------------------------------------------------------------- step entry (imgenv_step_begin)
+struct StepPlan {
+    // the move is left to the raster launch (k_move_raster): launch_views', or -- sum_shard_now -- this call's own, over the shard's
+    // robots and the pedestrians, in front of the exchange
+    bool fuse_move = false, sum_shard_now = false;
+    bool early_step = false;   // k_obs goes out with the move, behind a gate, instead of behind it (world.h)
+    bool serial_move = false;  // k_integrate_serial
+    int nb_robot = 0;          // the robots' blocks of the move; the pedestrians' follow
+    LaunchShape move;
+    bool fork_on_move = false;  // ev_fork rides on k_integrate's dispatch packet
+};
+inline StepPlan plan_step(const PlanHandle& h, const PlanChain& c) {
+    StepPlan s;
+    const bool fits = plan_integrate_fits(h.n_sub);
+    // (a robot shard in SUM mode draws its own robots in this call anyway: the move goes into that launch, whoever runs the exchange)
+    const bool whole_call = c.in_step && !h.sharded && !c.comm && h.RL == h.R;  // imgenv_step on a handle that owns its world
+    // (the move inside the raster launch of BIG handles, with the early observation gated on that launch, was measured again in round 6:
+    // 95.0 -> 103.1 us per headline step, cfg-4 117-123 -> 126, cfg-5 280 -> 282: the move's serial chain in front of every robot's
+    // raster costs more than the launch it saves)
+    s.fuse_move = (whole_call || h.sum_shard) && fits && (h.P == 0 ? h.RL <= 4096 : h.RL <= 1024);
+    s.sum_shard_now = s.fuse_move && h.sum_shard;
+    // early-observation step: only where gates work (k_gate_probe), no chain is half-way, and the snapshots it reads exist -- an RVO
+    // crowd's from the last solve, a social-force crowd a step ahead stands still during the step
+    const bool crowd_ready = h.NA == 0 ? c.crowd_ahead : c.orca_ran;
+    s.early_step = h.early && h.gates_work && !s.fuse_move && !c.chain_open && crowd_ready && c.view_ran && !c.early_off;
+    if (s.fuse_move) return s;
+    s.serial_move = !fits;
+    const int per_block = fits ? INT_G * INT_ROBOTS : 128, robots = fits ? INT_ROBOTS : 128;
+    s.nb_robot = (h.RL + robots - 1) / robots;
+    // ... and the pedestrians' move (img_env.cpp:343-358) in the same launch
+    const int nb_ped = plan_peds_move(h) ? (h.P + per_block - 1) / per_block : 0;
+    s.move = {(unsigned)(s.nb_robot + nb_ped), (unsigned)per_block, 0};
+    // (the fork of the side streams follows right behind the move, on its dispatch packet)
+    s.fork_on_move = fits && h.P > 0 && !h.serial && !c.chain_open;
+    return s;
+}
+
+// ---------------------------------------------------------------------------------------- rasters (launch_rasters)
+// The rasters of a chain of launches (in front of them, in STAMP mode, every STAMP_TAGS steps the sweep): every robot of the launch
+// and every pedestrian -- or, local_only (a step of a robot shard in SUM mode, world.h: sum_shard), this rank's robots and the
+// pedestrians: the other ranks' robots follow behind the exchange (k_remote)
+struct RasterPlan {
+    int n_g = 0, n_p = 0;
+    bool small = false, roomy = false;
+    int split = 0;         // robots and pedestrians in blocks of their own: the robots' blocks (0: block b draws robot b AND pedestrian b)
+    int nw = 1;            // wavefronts per block: 1 or 4
+    bool move = false;     // k_move_raster instead of k_raster
+    int move_peds = 0;
+    LaunchShape launch;    // k_raster / k_move_raster <pow2, layer, nw>
+    bool sweep = false;    // STAMP mode: k_cell_base drops all stamps before their tags come round again
+    unsigned sweep_blocks = 0;
+};
+inline RasterPlan plan_rasters(const PlanHandle& h, const PlanChain& c) {
+    RasterPlan r;
+    r.n_g = c.local_only ? h.RL : c.act_ng;
+    r.n_p = c.act_np;
+    // STAMP mode: no compose.  A reset has given the worlds it covers their base classes together with their obstacle maps
+    // (k_reset_apply, k_reset_obstacles); every STAMP_TAGS steps one sweep drops all stamps before their tags come round again.
+    r.sweep = h.layer == LAYER_STAMP && !c.is_reset && c.stamp_seq % STAMP_TAGS == 0;
+    r.sweep_blocks = plan_compose_blocks(h, c);
+    const int n_blocks = std::max(r.n_p, r.n_g);
+    // four wavefronts per robot / pedestrian when the launch cannot fill the machine (device-side auto-reset: by the expected
+    // number of robots, the grid itself is sized for every world)
+    r.small = plan_by_hint(c, n_blocks) <= 1024;
+    // robots and pedestrians in blocks of their own while all of them fit the chip at once (8192 wavefronts): a robot and a
+    // pedestrian one behind the other in one block is twice a block's chain of memory round trips
+    // (1024 envs x (4 + 3): k_raster 34 -> 22 us; the headline's 8192 + 200 stay as they are: a second, nearly empty round)
+    r.roomy = !r.small && r.n_g + r.n_p <= 8192;
+    r.split = (r.small || r.roomy) && r.n_g > 0 && r.n_p > 0 ? r.n_g : 0;
+    r.nw = r.small ? 4 : 1;
+    // (k_move_raster: the step's move in the same launch -- the RVO / recorded pedestrians' too)
+    r.move = c.moved;
+    r.move_peds = plan_peds_move(h) ? 1 : 0;
+    r.launch = {(unsigned)(r.split || r.move ? r.n_g + r.n_p : n_blocks), (unsigned)(r.nw * WAVE), 4 * (size_t)h.box_cells + 16};
+    return r;
+}
+
+// ---------------------------------------------------------------------------------------- side launches (launch_views, launch_obs)
+struct OrcaLaunch {
+    int G;          // agents per wavefront (1, 2 or 4: one row of 16 lanes each)
+    int groups;     // wavefronts per world
+    int cap_on;     // obstacle neighbours an agent's scratch holds (the handle's largest obstacle table, at most ORCA_MAX_ON)
+    int cap_stack;  // tree levels its walk may stack up
+    int stage_obst; // obstacle segments / nodes the LDS staging area holds (0: read them from HBM, everything on the home lane)
+    int fold_side;  // handles of several worlds: this kernel also does k_side_robots' part for its world (a launch less per phase):
+                    // the world's robot agents out of the robot records (setRobotPos, img_env.cpp:411-417), Agent::get_state of
+                    // its robots (group 0), and the robots taken as neighbour candidates directly instead of through near lists
+    int zero_vel;   // (with fold_side) a reset: robot agents start at rest
+};
+// The pedestrian half of the observation needs the local robots' new poses only, so it starts right behind k_integrate (in a
+// sharded world: underneath the record exchange) on its own stream; beside the rasters, compose and view run, on two side
+// streams, that and the next step's _step_ped_normal solve (img_env.cpp:304-343).
+struct SidePlan {
+    bool remote_only = false;     // a robot shard in SUM mode has drawn its own robots in imgenv_step_begin: k_remote draws the other ranks'
+    LaunchShape remote;
+    bool side_reads_all = false;  // the side streams read the OTHER ranks' robots: their RVO agents (k_side_robots, k_orca)
+    bool overlap = false, one_side = false;
+    bool fold_side = false;       // k_orca does k_side_robots' part for its world itself (one launch less per phase)
+    int rvo_agents = 0, slices = 1;
+    LaunchShape robots;           // k_side_robots (unless fold_side)
+    bool orca = false;
+    OrcaLaunch L = {};
+    unsigned orca_blocks = 0;     // (its LDS: orca_lds_bytes(L), kernels.h -- sized by the device's record types)
+    bool state = false;           // no side streams: after a reset Agent::get_state gets its own small launch (in a step k_integrate
+    LaunchShape state_shape;      // does it, with pedestrians k_side_robots)
+};
+inline SidePlan plan_side(const PlanHandle& h, const PlanChain& c) {
+    SidePlan s;
+    s.remote_only = h.sum_shard && !c.is_reset;
+    s.remote = {(unsigned)((h.R - h.RL + 255) / 256), 256, 0};
+    s.side_reads_all = h.P > 0 && h.NA > 0 && h.relation == 1;
+    s.state = h.P == 0 && c.is_reset;
+    s.state_shape = {(unsigned)((c.act_nl + 127) / 128), 128, 0};
+    if (h.P == 0) return s;
+    // (IMGENV_SERIAL=1 in the environment keeps everything on the caller's stream: clean per-kernel timings.)
+    s.overlap = !h.serial;
+    // Handles of at most 4096 robots keep ONE side stream: observation, robot records and the solve one behind the other (they
+    // fit underneath the rasters + views with room to spare: 31 us against 72 at 1024 envs x (4 + 3)), which saves three of the
+    // seven event operations of a phase -- such shapes are bound by the host's call rate (tools/host_issue_probe.py:
+    // ~6 us per launch or event call, ~30 calls per step with a device-side reset)
+    s.one_side = s.overlap && !h.sharded && h.RL <= 4096;
+    // handles of several worlds with RVO crowds: k_orca does k_side_robots' part for its world itself (one launch less per phase)
+    s.fold_side = h.W > 1 && h.NA > 0;
+    // (slices of >= 48 pedestrians, four at most: 8192 robots x 200 pedestrians = 128 x 4 wavefronts.  More of them -- cfg-5's
+    // 1000 pedestrians in 16 slices -- only take issue slots from the rasters and the views: 281-286 us per step against 276-278)
+    s.rvo_agents = h.NA > 0 && h.relation == 1 ? 1 : 0;
+    s.slices = s.rvo_agents && h.W == 1 ? std::min(4, std::max(1, (h.P + 47) / 48)) : 1;
+    s.robots = {(unsigned)((c.act_ng + WAVE - 1) / WAVE) * (unsigned)s.slices, WAVE, 0};
+    s.orca = h.NA > 0;
+    if (s.orca) {
+        // groups of up to 4 pedestrians of one world per wavefront; an agent's LDS scratch sized by the largest obstacle table
+        // any world of the handle can hold, the table itself staged into LDS when it fits 256 segments
+        const int per_world = h.W > 1 ? h.Pw : h.P, cap = std::max(c.orca_cap, 1);
+        s.L.G = per_world > 2 ? ORCA_GROUP_MAX : per_world;  // a row of 16 lanes per agent
+        s.L.groups = (per_world + s.L.G - 1) / s.L.G;
+        s.L.cap_on = std::max(std::min(ORCA_MAX_ON, cap), ORCA_ROW - ORCA_MAX_AN);  // (a round's 16 candidate lines borrow the projection area)
+        s.L.cap_stack = std::min(ORCA_STACK, cap + 1);
+        s.L.fold_side = s.fold_side ? 1 : 0;
+        s.L.zero_vel = c.is_reset ? 1 : 0;
+        s.L.stage_obst = std::min(cap, 256);  // (a world with more segments than that is solved out of HBM: the kernel checks its count)
+        s.orca_blocks = (unsigned)((c.act_np / per_world) * s.L.groups);
+    }
+    return s;
+}
+// k_obs<E>: a wavefront per local robot
+// (four wavefronts per robot for 513 .. 1024 pedestrians -- three times the occupancy, a third of the LDS per wavefront --
+// were measured in round 6 and LOSE: cfg-5 277 -> 325 us per step, 321 with two, 406 with eight: the step is bound by the
+// instructions it issues, k_obs beside k_view, not by this kernel's occupancy.  docs/HISTORY.md)
+inline LaunchShape plan_obs(const PlanHandle& h, const PlanChain& c) { return {(unsigned)c.act_nl, WAVE, h.lds_obs}; }
+
+// ---------------------------------------------------------------------------------------- views (launch_views)
+struct ViewPlan {
+    // k_view <pow2, a4, stamp, nw>
+    bool lds_bound = false;
+    int nw = 1;  // wavefronts per view: 1, 2, 4 or 8
+    LaunchShape view;
+    // view_big.h: crop (tiles of every robot spread over the chip) -> beams (a workgroup per robot and 256 beams) -> the shrunk
+    // sensor_map (a thread per pixel) -> the full view, only where it is an output
+    int quarters = 0, tap_chunks = 0;
+    int tpw = 0, crop_chunks = 0;  // tiles per k_crop_big wavefront; its chunks per robot
+    int qpw = 0;                   // blocks of 256 beams per k_beams_big workgroup
+    int crop_sel = 0;              // k_crop_big: 0 <false, false>, 1 <STAMP, false>, 2 <STAMP, crop_map>
+    bool taps = false, full = false, listed = false;
+    int tap_wgs = 0;
+    LaunchShape crop, beams, taps_shape, fullview;
+};
+// one wavefront per robot when the launch fills the machine, four when it is small (a reset of a few worlds): then
+// the single wavefront's latency is all there is
+// ... and whenever a view's LDS (crop + hit words + column table: 15 KB at 96 x 96 cells and 720 beams) would leave a
+// compute unit with 16 or fewer one-wavefront workgroups -- four or fewer wavefronts per SIMD where the registers allow
+// eight: four wavefronts then share one view's LDS (cfg-5, 8192 robots: k_view 252 -> 179 us alone, the step 472 -> 377 us;
+// at 48 x 48 cells, 5 KB and 32 workgroups per unit, it loses: 63 -> 87 us)
+inline bool plan_lds_bound(size_t lds_view) { return LDS_MAX / ((lds_view + 1279) / 1280 * 1280) <= 16; }
+inline ViewPlan plan_views(const PlanHandle& h, const PlanChain& c) {
+    ViewPlan v;
+    const int n_l = c.act_nl, n_eff = plan_by_hint(c, n_l);
+    if (!h.big_view) {
+        v.lds_bound = plan_lds_bound(h.lds_view);
+        // two wavefronts per robot in between (1025-4096 robots: every wavefront still resident at once; 1024 envs x 4: 39 -> 28 us)
+        // ... and eight where a launch is at most 1024 robots and the view small (48 x 48 cells and 360 beams are then ONE round of groups
+        // and ONE round of beams per wavefront: cfg-2 k_view 21.6 -> 20.4 us)
+        v.nw = v.lds_bound ? 4 : n_eff <= 1024 ? 8 : n_eff <= 4096 ? 2 : 1;
+        v.view = {(unsigned)n_l, (unsigned)(v.nw * WAVE), h.lds_view};
+        return v;
+    }
+    v.quarters = std::max(1, (h.B + VBB_T - 1) / VBB_T);
+    v.tap_chunks = (h.img_w * h.img_h + VBT_T - 1) / VBT_T;
+    v.full = h.keep_view_maps || !h.resize;
+    v.taps = h.resize;
+    // tiles per wavefront: 8 while the launch is a handful of robots (a reset of a few worlds: every robot on ~40 workgroups), 32-64
+    // once there are enough robots to fill the chip anyway
+    // (measured again after the kernel's gathers stopped binding it: a wavefront's prologue -- pose, fixed-point terms, its tiles'
+    // corner records -- is worth ~8 tiles, so even 256 robots want 32 tiles per wavefront: 36 -> 29 us; 2048 robots 64: 152 -> 133.
+    // Handing the fixed-point terms over from the robot's raster instead of recomputing them per wavefront was measured too:
+    // 155 us at 2048 robots, i.e. worse -- the prologue's cost is its loads, not its arithmetic.)
+    v.tpw = n_eff >= 1024 ? 64 : n_eff >= 48 ? 32 : 8;
+    v.crop_chunks = (h.big_max_crop + (VBC_T / WAVE) * v.tpw - 1) / ((VBC_T / WAVE) * v.tpw);
+    // (2048 robots x 1000 beams: one block of 256 beams per workgroup 98 us, two 87, four 87 -- but end to end two win: 3.85 M robot-steps/s
+    // against 3.79 / 3.78: the first workgroup of a robot also hands the collision code to the step's tail)
+    v.qpw = n_eff >= 1024 ? std::min(2, v.quarters) : 1;
+    v.crop_sel = h.layer == LAYER_STAMP ? (h.crop_map ? 2 : 1) : 0;
+    v.crop = {(unsigned)((n_l + 7) / 8 * 8) * (unsigned)v.crop_chunks, VBC_T, 0};
+    v.beams = {(unsigned)n_l * (unsigned)((v.quarters + v.qpw - 1) / v.qpw), VBB_T, h.lds_view_big};
+    // (a step only runs the chunks of pixels a beam can reach: static list per class; the chunks behind the sensor hold their
+    // 200 / 100 since the reset)
+    v.listed = !c.is_reset && h.big_tap_chunks_dyn > 0 && h.big_tap_chunks_dyn < v.tap_chunks;
+    v.tap_wgs = v.listed ? h.big_tap_chunks_dyn : v.tap_chunks;
+    v.taps_shape = {(unsigned)n_l * (unsigned)v.tap_wgs, VBT_T, taps_lds_bytes(h.B)};
+    v.fullview = {(unsigned)n_l * (unsigned)h.big_full_chunks, VBF_T, plan_lds_fullview(h.B)};
+    return v;
+}
+
+// ---------------------------------------------------------------------------------------- chain tail: k_stack, k_episodes
+// A step covers every local robot; a reset chain the robots of its list's worlds, whose length the host knows (act_nw) or a
+// kernel has counted (n_dev: the grid is sized for a guess and strides).
+inline size_t plan_tail_rows(const PlanHandle& h, const PlanChain& c) {
+    if (!c.is_reset || !c.listed) return (size_t)h.RL;
+    return (size_t)(c.n_dev ? std::min(c.act_nw * h.Rw, std::max(c.act_hint, h.Rw)) : c.act_nw * h.Rw);
+}
+inline LaunchShape plan_tail(size_t items, int block, int max_blocks) {
+    return {(unsigned)std::min<size_t>((size_t)max_blocks, std::max<size_t>(1, (items + block - 1) / block)), (unsigned)block, 0};
+}
+inline LaunchShape plan_stack_launch(const PlanHandle& h, const PlanChain& c, size_t chunks_per_robot) {
+    return plan_tail(plan_tail_rows(h, c) * chunks_per_robot, STACK_BLOCK, STACK_MAX_BLOCKS);
+}
+inline LaunchShape plan_episodes_launch(const PlanHandle& h, const PlanChain& c) { return plan_tail(plan_tail_rows(h, c), EP_BLOCK, EP_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------------------------------- resets
+// Device half of a host-side reset, for every world or the n worlds listed: one upload launch (segment copies | map restore |
+// robot state | pedestrian state), the obstacle maps, then view_agent + get_states (img_env.cpp:285-286) for those worlds' robots.
+struct ResetPlan {
+    int per_seg = 1;  // workgroups per staged segment
+    LaunchShape apply, obstacles, bbox;
+};
+inline ResetPlan plan_reset(const PlanHandle& h, const PlanChain& c, size_t n_seg, size_t seg_max, size_t n_inst) {
+    ResetPlan r;
+    r.per_seg = (int)std::min<size_t>((seg_max / 16 + 255) / 256 + 1, 16);
+    r.apply = {(unsigned)(n_seg * r.per_seg + (size_t)c.act_nw * MAP_BLOCKS + (c.act_ng + 255) / 256 + (c.act_np + 255) / 256), 256, 0};
+    r.obstacles = {(unsigned)n_inst, 256, 0};  // one workgroup per obstacle
+    r.bbox = {(unsigned)((h.RL + 255) / 256), 256, 0};
+    return r;
+}
+// Device-side reset chain: nobody on the host knows how many worlds the step finished, so the grids are sized for a guess (four
+// times the last count the host has seen; the kernels stride over the rest if there are more) ...
+struct DevResetPlan {
+    int guess = 0, restore_blocks = 4 * MAP_BLOCKS /* per world */, parts = 4 /* workgroups per obstacle */;
+    LaunchShape restore, obstacles;
+};
+inline DevResetPlan plan_dev_reset(const PlanHandle& h, int last_n, int n_obstacles) {
+    DevResetPlan r;
+    r.guess = std::min(h.W, std::max(16, 4 * std::max(last_n, 0)));
+    r.restore = {(unsigned)(r.guess * r.restore_blocks), 256, 0};
+    r.obstacles = {(unsigned)(r.guess * n_obstacles * r.parts), 256, 0};
+    return r;
+}
+// ... and the variants of the chain behind chosen by the robots it is expected to cover (twice the last count: with four times,
+// 64 worlds of 4 pedestrians sat ON the 1024 threshold and flipped between the kernel variants)
+inline int plan_act_hint(const PlanHandle& h, int last_n) { return std::max(8, 2 * std::max(last_n, 0)) * std::max(std::max(h.Rw, h.Pw), 1); }

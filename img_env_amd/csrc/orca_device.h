@@ -35,10 +35,7 @@
 #include "world.h"
 
 #define RVO_EPS 0.00001f
-#define ORCA_MAX_ON 118  // obstacle neighbours kept per agent
-#define ORCA_MAX_AN 10   // rvoscene.h:57,63 maxNeighbors
-#define ORCA_MAX_LINES (ORCA_MAX_ON + ORCA_MAX_AN)
-#define ORCA_STACK 128
+// (ORCA_MAX_ON / ORCA_MAX_AN / ORCA_MAX_LINES / ORCA_STACK: launch_plan.h)
 
 struct f2 {
     float x, y;

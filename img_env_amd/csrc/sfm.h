@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "cr_atan2.h"
+#include "launch_plan.h"  // SFM_MAX_AGENTS
 
 #if defined(__HIPCC__)
 #define SFM_HD __host__ __device__
@@ -35,7 +36,6 @@
 #define SFM_HD
 #endif
 
-#define SFM_MAX_AGENTS 256
 #define SFM_MAX_WP 8
 #define SFM_LEAF_CAP 12
 #define SFM_MAX_DEPTH 64

@@ -17,10 +17,10 @@
 #pragma once
 #include <stdint.h>
 
+#include "launch_plan.h"  // STACK_BLOCK, STACK_MAX_BLOCKS
+
 #define STACK_MAX_DEPTH 16   // documented cap (include/imgenv.h: IMGENV_STACK_MAX_DEPTH)
 #define STACK_BATCH 8        // slots a lane keeps in registers at once
-#define STACK_BLOCK 256
-#define STACK_MAX_BLOCKS 2048
 
 struct StackField {
     unsigned char* stack;        // [RL][depth][frame_bytes]

@@ -25,11 +25,8 @@
 // occupied: such cells skip the beams altogether, which also keeps the walks away from the long ray lists around the sensor.
 #pragma once
 
-#define VBC_T 256    // k_crop_big: up to 4 wavefronts
+// (workgroup sizes VBC_T / VBB_T / VBT_T / VBF_T: launch_plan.h)
 #define VBC_U 4      // tiles a wavefront keeps in flight (8: measured slower, 321 against 304 us for 2048 shipped views)
-#define VBB_T 256    // k_beams_big: one beam per thread
-#define VBT_T 256    // k_taps_big: one sensor_map pixel per thread
-#define VBF_T 256    // k_fullview_big
 
 __device__ __forceinline__ long long uniform_i64(long long v) {  // a value known to be the same in every lane, into scalar registers
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(unsigned long long)v);

@@ -4,15 +4,14 @@
 #include <stdint.h>
 
 #include "fp_rows.h"
+#include "launch_plan.h"  // WAVE, STAMP_TAGS, STAMP_MAX_ROBOTS, ORCA_NEAR_CAP: the constants the launch rules share
 #include "sfm.h"
 #include "tfm.h"
 
-#define WAVE 64
 #define OWNER_MULTI 0xFFFFFEu  // 24-bit owner field of the composed layer: several robots cover the cell
 #define RC_INLINE 6           // distinct robot classes (shape, size, sensor) per world, carried in the kernel arguments
 #define PC_INLINE 4           // distinct pedestrian classes per world
 #define BEEP_T 256            // rand() values one round of k_beep produces
-#define ORCA_NEAR_CAP 64       // robot agents a pedestrian can have within its 0.5 m neighbour range before k_orca falls back to the full scan
 
 // composed class layer byte (k_compose): low 3 bits = base class, bit 3 = "some robot covers it"
 #define CLS_STATIC 0   // occupancy value 0: static map / obstacle      (collision code 1)
@@ -35,8 +34,6 @@
 #define STAMP_KIND_SHIFT 3
 #define STAMP_TAG_SHIFT 5
 #define STAMP_OWNER_SHIFT 13
-#define STAMP_MAX_ROBOTS (1 << 19)
-#define STAMP_TAGS 255
 
 // The same layer in SUM mode (round 5; dense worlds whose handle owns every robot): `cell` = the base class of the obstacle map
 // plus COUNTS of what stands on the cell, kept up to date by the agents themselves with fire-and-forget atomic adds -- every robot

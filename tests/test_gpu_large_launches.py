@@ -1,6 +1,6 @@
 """The kernel variants only LARGE launches select, against the oracle.
 
-The library picks kernel variants by launch size (csrc/imgenv_hip.hip, launch_views): one wavefront per robot / pedestrian
+The library picks kernel variants by launch size (csrc/launch_plan.h; tests/test_launch_plan.py pins the rules on the CPU): one wavefront per robot / pedestrian
 instead of four in `k_raster` above 1024 blocks (robots and pedestrians in blocks of their own up to 8192 blocks, one block for a
 robot AND a pedestrian beyond), eight / two / one wavefronts per `k_view` up to 1024 / up to 4096 / more robots (four where the
 view's LDS bounds the occupancy: cfg-5), the step's move

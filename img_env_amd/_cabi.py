@@ -169,6 +169,70 @@ def make_episodes_cfg(min_steps, dt):
     return c
 
 
+ACTIONS_TABLE, ACTIONS_CLIP, ACTIONS_MAX_TABLE = 0, 1, 4096
+RAW_I32, RAW_I64, RAW_F32, RAW_F64 = 0, 1, 2, 3  # ``dtype`` of imgenv_actions_decode
+RAW_DTYPES = {np.dtype(np.int32): RAW_I32, np.dtype(np.int64): RAW_I64, np.dtype(np.float32): RAW_F32, np.dtype(np.float64): RAW_F64}
+OBS_PED_NORM, OBS_CLOSE = 1, 2
+#: StatePedVectorWrapper.avg / .std (base.py:20-21) and InfoLogWrapper's ``ped_min_dist < 1`` (base.py:250)
+PED_NORM_AVG = (0.0, 0.0, 0.0, 0.0, 0.25, 0.25, 0.0)
+PED_NORM_STD = (6.0, 6.0, 0.6, 0.9, 0.50, 0.5, 6.0)
+CLOSE_DIST = 1.0
+
+
+class ActionsCfg(C.Structure):
+    _fields_ = [("struct_size", _i32), ("mode", _i32), ("n_cols", _i32), ("n_table", _i32), ("table", C.c_void_p), ("clip", (_f32 * 2) * 3)]
+
+
+#: imgenv_actions_out's arrays: name -> (numpy dtype, columns: the array is [R][columns]; 0 = one element for the handle)
+ACTION_ARRAYS = {"actions": (np.float32, 3), "speeds": (np.float32, 2), "n_bad": (np.int32, 0)}
+
+
+class ActionsOut(C.Structure):
+    _fields_ = [("struct_size", _i32), ("n_local", _i32)] + [(name, C.c_void_p) for name in ACTION_ARRAYS]
+
+
+def make_actions_cfg(table=None, clip=None, n_cols=2):
+    """``imgenv_actions_cfg``: TABLE mode from the YAML's ``discrete_actions`` (rows of 2 or 3 values; a two-column row gets beep
+    0, action.py:29-30), or CLIP mode from its ``continuous_actions`` (at least ``n_cols`` rows of (lo, hi)).  Returns the struct
+    and what it points to."""
+    c = ActionsCfg()
+    c.struct_size = C.sizeof(ActionsCfg)
+    c.n_cols = int(n_cols)
+    keep = None
+    if table is not None:
+        rows = [list(r) for r in table]
+        if any(len(r) not in (2, 3) for r in rows):
+            raise ValueError("discrete_actions: rows of (v, w) or (v, w, beep)")
+        keep = np.ascontiguousarray([[r[0], r[1], r[2] if len(r) == 3 else 0] for r in rows], np.float32).reshape(-1, 3)
+        c.mode, c.n_table, c.table = ACTIONS_TABLE, len(keep), keep.ctypes.data if len(keep) else None
+    else:
+        rng = np.asarray(clip, np.float64).reshape(-1, 2)
+        if c.n_cols in (2, 3) and len(rng) < c.n_cols:
+            raise ValueError("continuous_actions: %d ranges for %d columns (IndexError in base.py:50)" % (len(rng), c.n_cols))
+        c.mode = ACTIONS_CLIP
+        for i, (lo, hi) in enumerate(rng[:3]):
+            c.clip[i][0], c.clip[i][1] = float(lo), float(hi)
+    return c, keep
+
+
+class ObsPostCfg(C.Structure):
+    _fields_ = [("struct_size", _i32), ("flags", _i32), ("avg", _f64 * 7), ("std", _f64 * 7), ("close_dist", _f64)]
+
+
+class ObsPostOut(C.Structure):
+    _fields_ = [("struct_size", _i32), ("n_local", _i32), ("ped_vector_norm", C.c_void_p), ("close_to_human", C.c_void_p)]
+
+
+def make_obs_post_cfg(ped_norm=True, close=True, avg=PED_NORM_AVG, std=PED_NORM_STD, close_dist=CLOSE_DIST):
+    """``imgenv_obs_post_cfg`` with the reference's constants as defaults"""
+    c = ObsPostCfg()
+    c.struct_size = C.sizeof(ObsPostCfg)
+    c.flags = (OBS_PED_NORM if ped_norm else 0) | (OBS_CLOSE if close else 0)
+    c.avg[:], c.std[:] = [float(x) for x in avg], [float(x) for x in std]
+    c.close_dist = float(close_dist)
+    return c
+
+
 #: name -> (numpy dtype, shape as a function of the Out header and the world sizes)
 def out_layout(o, n_peds, hp, wp):
     R, B = o.n_local, max(o.n_beams, 1)
@@ -318,6 +382,7 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_world_placement", "imgenv_cv_resize_u8", "imgenv_build_id", "imgenv_step_flags", "imgenv_layer_mode",
            "imgenv_stack_bytes", "imgenv_stack_enable", "imgenv_stack_outputs",
            "imgenv_episodes_enable", "imgenv_episodes_outputs", "imgenv_episodes_clear",
+           "imgenv_actions_enable", "imgenv_actions_outputs", "imgenv_actions_decode", "imgenv_obs_post_enable", "imgenv_obs_post_outputs",
            "imgenv_maps_add", "imgenv_world_maps_set", "imgenv_maps_policy", "imgenv_map_for_placement", "imgenv_world_maps")
 K_COUNT = 14
 
@@ -372,6 +437,11 @@ def bind(lib):
     lib.imgenv_episodes_enable.argtypes = [C.c_void_p, C.POINTER(EpisodesCfg), C.POINTER(EpisodesOut)]
     lib.imgenv_episodes_outputs.argtypes = [C.c_void_p, C.POINTER(EpisodesOut)]
     lib.imgenv_episodes_clear.argtypes = [C.c_void_p, C.c_void_p]
+    lib.imgenv_actions_enable.argtypes = [C.c_void_p, C.POINTER(ActionsCfg), C.POINTER(ActionsOut)]
+    lib.imgenv_actions_outputs.argtypes = [C.c_void_p, C.POINTER(ActionsOut)]
+    lib.imgenv_actions_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.imgenv_obs_post_enable.argtypes = [C.c_void_p, C.POINTER(ObsPostCfg), C.POINTER(ObsPostOut)]
+    lib.imgenv_obs_post_outputs.argtypes = [C.c_void_p, C.POINTER(ObsPostOut)]
     lib.imgenv_maps_add.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
     lib.imgenv_world_maps_set.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
     lib.imgenv_maps_policy.argtypes = [C.c_void_p, C.c_int32]

@@ -25,6 +25,8 @@
 #include "world.h"
 #include "stack.h"
 #include "episodes.h"
+#include "actions.h"
+#include "obs_post.h"
 #include "map_bank.h"
 
 static thread_local char g_err[512] = "";
@@ -198,6 +200,18 @@ struct imgenv {
     imgenv_episodes_out ep_out;
     size_t ep_clear_bytes = 0;   // what imgenv_episodes_clear zeroes, from ep.f on
     const float* ep_actions = nullptr;  // the actions of the step in progress (the caller keeps them until the chain's end)
+    // action decoding (include/imgenv.h: imgenv_actions_enable; csrc/actions.h)
+    bool act_on = false;         // imgenv_actions_enable has been called
+    ActionsDev act;
+    imgenv_actions_cfg act_cfg;  // (its table pointer is not kept: act_table is the copy)
+    std::vector<float> act_table;
+    imgenv_actions_out act_out;
+    int decode_launches = 0;     // k_actions launches since the last step: they count with the step that consumes them
+    // observation post-processing (imgenv_obs_post_enable; csrc/obs_post.h)
+    bool post_on = false;
+    ObsPostDev post;
+    imgenv_obs_post_cfg post_cfg;
+    imgenv_obs_post_out post_out;
     bool chain_open = false;  // a chain of launches that hands over through tail_sig / tail_cnt has started and not been completed
     std::vector<RvoObstacles> rvos;  // one obstacle set per world
     int sfm_cap_obs = 0;
@@ -1758,6 +1772,17 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
         (is_reset ? k_episodes<true> : k_episodes<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(ed);
         h->launches += 1;
     }
+    if (h->post_on) {
+        // the normalised pedestrian vectors and close_to_human (obs_post.h), last: of every local robot after a step, of the robots
+        // a reset chain covers (k_stack<true>'s cases)
+        ObsPostDev pd = h->post;
+        pd.list = is_reset ? d.act_list : nullptr;
+        pd.n_dev = is_reset ? d.act_n_dev : nullptr;
+        pd.n_worlds = d.act_nw;
+        const LaunchShape g = plan_obs_post_launch(p, c, (size_t)pd.per_row);
+        (is_reset ? k_obs_post<true> : k_obs_post<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(pd);
+        h->launches += 1;
+    }
     HIPCHK(hipGetLastError());
     h->chain_open = false;
     return outputs_seal(h, st);
@@ -2696,7 +2721,8 @@ extern "C" int imgenv_step_begin(imgenv_t* h, const float* actions, void* stream
     h->guard_sealed = false;
     h->ep_actions = actions;
     DevWorld& d = h->d;
-    h->launches = 0;
+    h->launches = h->decode_launches;  // (imgenv_actions_decode in front of this step)
+    h->decode_launches = 0;
     // _step_ped_normal (img_env.cpp:304-359): the ORCA solve for this step ran on the side stream during the previous
     // step's views and was joined at the end of that step; its velocities are applied by k_integrate's pedestrian blocks
     if (h->cfg.ped_scene_type == IMGENV_SCENE_PEDSIM && h->d.sfm.n > 0) {  // PedScene::step + write-back (img_env.cpp:343-358)
@@ -3501,6 +3527,171 @@ extern "C" int imgenv_episodes_clear(imgenv_t* h, void* stream) {
     if (!h->ep_on) FAIL(IMGENV_ESTATE, "imgenv_episodes_enable was not called");
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(hipMemsetAsync(h->ep.f, 0, h->ep_clear_bytes, (hipStream_t)stream));
+    return IMGENV_OK;
+}
+
+// ---- action decoding (include/imgenv.h; the kernel is csrc/actions.h) ----
+static bool actions_cfg_same(const imgenv* h, const imgenv_actions_cfg* c) {
+    const imgenv_actions_cfg& o = h->act_cfg;
+    if (c->mode != o.mode || c->n_cols != o.n_cols) return false;
+    if (c->mode == IMGENV_ACTIONS_TABLE)
+        return c->n_table == o.n_table && memcmp(c->table, h->act_table.data(), sizeof(float) * 3 * (size_t)c->n_table) == 0;
+    return memcmp(c->clip, o.clip, sizeof(float) * 2 * (size_t)c->n_cols) == 0;
+}
+extern "C" int imgenv_actions_enable(imgenv_t* h, const imgenv_actions_cfg* c, imgenv_actions_out* out) {
+    // (the cfg first: its refusals need no handle, and so no device)
+    if (!c) FAIL(IMGENV_EINVAL, "null argument");
+    if (c->struct_size != (int32_t)sizeof(imgenv_actions_cfg))
+        FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.struct_size %d (this library's is %d)", c->struct_size, (int)sizeof(imgenv_actions_cfg));
+    if (out && out->struct_size != 0 && out->struct_size != (int32_t)sizeof(imgenv_actions_out)) FAIL(IMGENV_EINVAL, "imgenv_actions_out.struct_size");
+    if (c->mode != IMGENV_ACTIONS_TABLE && c->mode != IMGENV_ACTIONS_CLIP) FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.mode %d", c->mode);
+    if (c->n_cols != 2 && c->n_cols != 3) FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.n_cols %d: 2 (v, w) or 3 (v, w, beep)", c->n_cols);
+    if (c->mode == IMGENV_ACTIONS_TABLE) {
+        if (!c->table || c->n_table < 1 || c->n_table > IMGENV_ACTIONS_MAX_TABLE)
+            FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.table: 1 .. %d rows (n_table %d)", IMGENV_ACTIONS_MAX_TABLE, c->n_table);
+        for (int q = 0; q < 3 * c->n_table; q++)
+            if (!std::isfinite(c->table[q])) FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.table row %d holds a value that is not finite", q / 3);
+    } else {
+        for (int i = 0; i < c->n_cols; i++)
+            if (!std::isfinite(c->clip[i][0]) || !std::isfinite(c->clip[i][1]) || c->clip[i][0] > c->clip[i][1])
+                FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.clip[%d] = (%g, %g): finite bounds with lo <= hi", i, c->clip[i][0], c->clip[i][1]);
+    }
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (h->act_on) {
+        if (!actions_cfg_same(h, c)) FAIL(IMGENV_EINVAL, "imgenv_actions_enable: the handle already decodes actions with another cfg");
+        if (out) *out = h->act_out;
+        return IMGENV_OK;
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t RL = (size_t)h->RL;
+    ActionsDev a;
+    memset(&a, 0, sizeof(a));
+    RTRY(dev_alloc(h, &a.actions, RL * 3));  // (zeroed)
+    RTRY(dev_alloc(h, &a.speeds, RL * 2));
+    RTRY(dev_alloc(h, &a.n_bad, 1));
+    std::vector<float> table;
+    if (c->mode == IMGENV_ACTIONS_TABLE) {
+        table.assign(c->table, c->table + 3 * (size_t)c->n_table);
+        RTRY(dev_upload(h, &a.table, table));
+        a.n_table = c->n_table;
+    } else {
+        for (int i = 0; i < c->n_cols; i++) { a.lo[i] = c->clip[i][0]; a.hi[i] = c->clip[i][1]; }
+    }
+    a.clean_state = h->d.clean_state;
+    a.n_cols = c->n_cols;
+    a.RL = h->RL;
+    h->act = a;
+    h->act_cfg = *c;
+    h->act_cfg.table = nullptr;
+    h->act_table.swap(table);
+    imgenv_actions_out& o = h->act_out;
+    memset(&o, 0, sizeof(o));
+    o.struct_size = (int32_t)sizeof(imgenv_actions_out);
+    o.n_local = h->RL;
+    o.actions = a.actions; o.speeds = a.speeds; o.n_bad = a.n_bad;
+    h->act_on = true;
+    if (out) *out = o;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_actions_outputs(imgenv_t* h, imgenv_actions_out* out) {
+    if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->act_on) FAIL(IMGENV_ESTATE, "imgenv_actions_enable was not called");
+    *out = h->act_out;
+    return IMGENV_OK;
+}
+
+// k_actions<DTYPE, MODE>: the six instantiations (indices are not clipped)
+typedef void (*ActionsKernel)(const ActionsDev);
+static ActionsKernel k_actions_for(int dtype, int mode) {
+    if (mode == IMGENV_ACTIONS_CLIP) return dtype == IMGENV_RAW_F32 ? k_actions<IMGENV_RAW_F32, IMGENV_ACTIONS_CLIP> : k_actions<IMGENV_RAW_F64, IMGENV_ACTIONS_CLIP>;
+    switch (dtype) {
+        case IMGENV_RAW_I32: return k_actions<IMGENV_RAW_I32, IMGENV_ACTIONS_TABLE>;
+        case IMGENV_RAW_I64: return k_actions<IMGENV_RAW_I64, IMGENV_ACTIONS_TABLE>;
+        case IMGENV_RAW_F32: return k_actions<IMGENV_RAW_F32, IMGENV_ACTIONS_TABLE>;
+        default: return k_actions<IMGENV_RAW_F64, IMGENV_ACTIONS_TABLE>;
+    }
+}
+extern "C" int imgenv_actions_decode(imgenv_t* h, const void* raw, int32_t dtype, void* stream) {
+    if (!h || !raw) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->act_on) FAIL(IMGENV_ESTATE, "imgenv_actions_enable was not called");
+    if (!h->has_reset) FAIL(IMGENV_ESTATE, "imgenv_actions_decode before the first reset");
+    if (dtype < IMGENV_RAW_I32 || dtype > IMGENV_RAW_F64) FAIL(IMGENV_EINVAL, "imgenv_actions_decode: dtype %d", dtype);
+    const bool integer = dtype == IMGENV_RAW_I32 || dtype == IMGENV_RAW_I64;
+    if (integer && h->act_cfg.mode == IMGENV_ACTIONS_CLIP) FAIL(IMGENV_EINVAL, "imgenv_actions_decode: indices in CLIP mode (the handle has no table)");
+    const size_t elem = dtype == IMGENV_RAW_I32 || dtype == IMGENV_RAW_F32 ? 4 : 8;
+    if ((uintptr_t)raw % elem != 0) FAIL(IMGENV_EINVAL, "imgenv_actions_decode: raw is not aligned to its %d-byte elements", (int)elem);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    ActionsDev a = h->act;
+    a.raw = raw;
+    const LaunchShape g = plan_actions_launch(h->plan);
+    k_actions_for(dtype, h->act_cfg.mode)<<<dim3(g.grid), dim3(g.block), 0, (hipStream_t)stream>>>(a);
+    HIPCHK(hipGetLastError());
+    h->decode_launches += 1;
+    return IMGENV_OK;
+}
+
+// ---- observation post-processing (include/imgenv.h; the kernel is csrc/obs_post.h) ----
+extern "C" int imgenv_obs_post_enable(imgenv_t* h, const imgenv_obs_post_cfg* c, imgenv_obs_post_out* out) {
+    if (!c) FAIL(IMGENV_EINVAL, "null argument");
+    if (c->struct_size != (int32_t)sizeof(imgenv_obs_post_cfg))
+        FAIL(IMGENV_EINVAL, "imgenv_obs_post_cfg.struct_size %d (this library's is %d)", c->struct_size, (int)sizeof(imgenv_obs_post_cfg));
+    if (out && out->struct_size != 0 && out->struct_size != (int32_t)sizeof(imgenv_obs_post_out)) FAIL(IMGENV_EINVAL, "imgenv_obs_post_out.struct_size");
+    if (c->flags == 0 || (c->flags & ~(IMGENV_OBS_PED_NORM | IMGENV_OBS_CLOSE))) FAIL(IMGENV_EINVAL, "imgenv_obs_post_cfg.flags %d", c->flags);
+    if (c->flags & IMGENV_OBS_PED_NORM)
+        for (int k = 0; k < OBS_POST_DIM; k++) {
+            if (!std::isfinite(c->avg[k]) || !std::isfinite(c->std[k])) FAIL(IMGENV_EINVAL, "imgenv_obs_post_cfg: avg[%d] / std[%d] is not finite", k, k);
+            if (c->std[k] == 0.0) FAIL(IMGENV_EINVAL, "imgenv_obs_post_cfg.std[%d] is 0", k);
+        }
+    if ((c->flags & IMGENV_OBS_CLOSE) && std::isnan(c->close_dist)) FAIL(IMGENV_EINVAL, "imgenv_obs_post_cfg.close_dist is not a number");
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (h->post_on) {
+        const imgenv_obs_post_cfg& o = h->post_cfg;
+        bool same = c->flags == o.flags;
+        if (same && (c->flags & IMGENV_OBS_PED_NORM)) same = memcmp(c->avg, o.avg, sizeof(o.avg)) == 0 && memcmp(c->std, o.std, sizeof(o.std)) == 0;
+        if (same && (c->flags & IMGENV_OBS_CLOSE)) same = c->close_dist == o.close_dist;
+        if (!same) FAIL(IMGENV_EINVAL, "imgenv_obs_post_enable: the handle already post-processes its observations with another cfg");
+        if (out) *out = h->post_out;
+        return IMGENV_OK;
+    }
+    if ((c->flags & IMGENV_OBS_PED_NORM) && h->cfg.ped_vec_dim != OBS_POST_DIM)
+        FAIL(IMGENV_EINVAL, "IMGENV_OBS_PED_NORM: ped_vec_dim %d (the wrapper's constants are for %d)", h->cfg.ped_vec_dim, OBS_POST_DIM);
+    if ((c->flags & IMGENV_OBS_CLOSE) && h->P == 0) FAIL(IMGENV_EINVAL, "IMGENV_OBS_CLOSE on a handle without pedestrians");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    ObsPostDev p;
+    memset(&p, 0, sizeof(p));
+    p.flags = c->flags;
+    p.PV = h->d.PV;
+    p.max_ped = h->cfg.max_ped;
+    p.per_row = (c->flags & IMGENV_OBS_PED_NORM) ? p.PV : 1;
+    p.ped_vector_states = h->out.ped_vector_states;  // (the working arena, also under IMGENV_FLAG_FULL_REWRITE)
+    p.ped_min_dists = h->out.ped_min_dists;
+    if (c->flags & IMGENV_OBS_PED_NORM) {
+        RTRY(dev_alloc(h, &p.norm, (size_t)h->RL * p.PV));
+        for (int k = 0; k < OBS_POST_DIM; k++) { p.avg[k] = c->avg[k]; p.std[k] = c->std[k]; }
+    }
+    if (c->flags & IMGENV_OBS_CLOSE) {
+        RTRY(dev_alloc(h, &p.close, (size_t)h->RL));
+        p.close_dist = c->close_dist;
+    }
+    p.RL = h->RL; p.r0 = h->r0; p.Rw = h->Rw;
+    h->post = p;
+    h->post_cfg = *c;
+    imgenv_obs_post_out& o = h->post_out;
+    memset(&o, 0, sizeof(o));
+    o.struct_size = (int32_t)sizeof(imgenv_obs_post_out);
+    o.n_local = h->RL;
+    o.ped_vector_norm = p.norm;
+    o.close_to_human = p.close;
+    h->post_on = true;
+    if (out) *out = o;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_obs_post_outputs(imgenv_t* h, imgenv_obs_post_out* out) {
+    if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->post_on) FAIL(IMGENV_ESTATE, "imgenv_obs_post_enable was not called");
+    *out = h->post_out;
     return IMGENV_OK;
 }
 

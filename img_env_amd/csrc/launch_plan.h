@@ -31,6 +31,9 @@
 #define STACK_MAX_BLOCKS 2048
 #define EP_BLOCK 256
 #define EP_MAX_BLOCKS 1024
+#define ACT_BLOCK 256       // k_actions: one lane per local robot
+#define OBS_POST_BLOCK 256  // k_obs_post: one lane per element of a robot's ped_vector row
+#define OBS_POST_MAX_BLOCKS 2048
 #define ORCA_NEAR_CAP 64  // robot agents a pedestrian can have within its 0.5 m neighbour range before k_orca falls back to the full scan
 #define ORCA_MAX_ON 118   // obstacle neighbours kept per agent
 #define ORCA_MAX_AN 10    // rvoscene.h:57,63 maxNeighbors
@@ -385,6 +388,16 @@ inline LaunchShape plan_stack_launch(const PlanHandle& h, const PlanChain& c, si
     return plan_tail(plan_tail_rows(h, c) * chunks_per_robot, STACK_BLOCK, STACK_MAX_BLOCKS);
 }
 inline LaunchShape plan_episodes_launch(const PlanHandle& h, const PlanChain& c) { return plan_tail(plan_tail_rows(h, c), EP_BLOCK, EP_MAX_BLOCKS); }
+// k_obs_post (obs_post.h), behind them: `per_row` lanes per robot of the chain -- the 1 + 7 max_ped elements of its ped_vector row,
+// or one where only close_to_human is kept
+inline LaunchShape plan_obs_post_launch(const PlanHandle& h, const PlanChain& c, size_t per_row) {
+    return plan_tail(plan_tail_rows(h, c) * per_row, OBS_POST_BLOCK, OBS_POST_MAX_BLOCKS);
+}
+
+// ---------------------------------------------------------------------------------------- in front of the chain: k_actions
+// imgenv_actions_decode (actions.h): one lane per local robot, every wavefront whole (the ballot that counts bad rows runs on all
+// 64 lanes), no cap and no stride: 2^19 robots are 2048 blocks
+inline LaunchShape plan_actions_launch(const PlanHandle& h) { return {(unsigned)((h.RL + ACT_BLOCK - 1) / ACT_BLOCK), ACT_BLOCK, 0}; }
 
 // ---------------------------------------------------------------------------------------- resets
 // Device half of a host-side reset, for every world or the n worlds listed: one upload launch (segment copies | map restore |

@@ -33,10 +33,12 @@ class VecImageEnv:
     ``info``: ``dones_info`` (InfoLogWrapper codes, 10 = time limit), ``is_clean`` (MultiRobotCleanWrapper), ``arrive``,
     ``collision``, ``all_down`` (per robot: its env is finished) and ``reset_envs`` (the envs that were reset after this step:
     their rows of the returned state are already the new episode's first observation, as with NeverStopWrapper).
+    ``wrappers=True``: ``step`` takes the policy's own output (indices or raw float rows) and ``info`` gains ``speeds`` and, with
+    pedestrians, ``bool_get_close_to_human`` (of the state handed out: an env that restarted shows its new episode's).
     """
 
     def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False,
-                 map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3):
+                 map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3, wrappers=False):
         import torch
         from .world import World
         self.cfg = cfg
@@ -106,6 +108,27 @@ class VecImageEnv:
         if self.episode_stats:
             self.world.enable_episodes(int(episode_min_steps), float(cfg["control_hz"]))
 
+        # wrappers: the input side of the YAML's wrapper list and its two small output wrappers inside the library.
+        #   VelActionWrapper (base.py:37-66): ``step`` takes what the policy emits -- a 1-D integer array of indices into
+        #   cfg["discrete_actions"] (discrete_action: True) or a 2-D float array [n, act_dim], clipped by cfg["continuous_actions"]
+        #   where discrete_action is False -- and decodes it with one launch in front of the step (imgenv_actions_decode);
+        #   info["speeds"] is the decoded (v, w) masked by the is_clean of before the step (base.py:58, 81-83).
+        #   StatePedVectorWrapper (base.py:19-34), iff the YAML lists it: the state's ped_vector_states is the normalised array.
+        #   info["bool_get_close_to_human"] (base.py:250-252), iff the envs have pedestrians.
+        # Opt-in: False takes float32 [n, 3] = (v, w, beep) and launches nothing more, as before.
+        self.wrappers = bool(wrappers)
+        self._ped_norm = self._close = False
+        if self.wrappers:
+            act_dim = int(cfg.get("act_dim", 2))
+            if cfg.get("discrete_action"):
+                self.world.enable_actions(discrete_actions=cfg["discrete_actions"], act_dim=act_dim)
+            else:
+                self.world.enable_actions(continuous_actions=cfg["continuous_actions"], act_dim=act_dim)
+            self._ped_norm = "StatePedVectorWrapper" in (cfg.get("wrapper") or [])
+            self._close = self.ped_total > 0
+            if self._ped_norm or self._close:
+                self.world.enable_obs_post(ped_norm=self._ped_norm, close=self._close)
+
     def episode_tensors(self):
         """the per-robot device tensors of the statistics (``World.episodes``: ``ends`` [6, n], ``episodes``, ``last_episode``,
         ``last_return`` ...), as they are -- no synchronisation; ordered on the current stream behind the last reset / step"""
@@ -145,9 +168,10 @@ class VecImageEnv:
 
     def _state(self):
         o = self.world.out
+        ped_vector = self.world.obs_post["ped_vector_norm"] if self._ped_norm else o["ped_vector_states"]
         if not self.stack:
             return ImageState(o["vector_states"], o["sensor_maps"], o["is_collisions"], o["is_arrives"], o["lasers"],
-                              o["ped_vector_states"], o["ped_maps"], o["step_ds"], o["ped_min_dists"])
+                              ped_vector, o["ped_maps"], o["step_ds"], o["ped_min_dists"])
         k = self.world.stack
         vector_states, sensor_maps, lasers = (k.get(f, o[f]) for f in ("vector_states", "sensor_maps", "lasers"))
         if self._filter == "ObsStateTmp":
@@ -155,7 +179,7 @@ class VecImageEnv:
         if self._filter == "ObsLaserStateTmp":
             return [lasers, vector_states, o["ped_maps"]]
         return ImageState(vector_states, sensor_maps, o["is_collisions"], o["is_arrives"], lasers,
-                          o["ped_vector_states"], o["ped_maps"], o["step_ds"], o["ped_min_dists"])
+                          ped_vector, o["ped_maps"], o["step_ds"], o["ped_min_dists"])
 
     def reset(self, layouts=None):
         """every env starts a new episode (ImageEnv.reset per env, yaml_env.py:296-317)"""
@@ -178,7 +202,17 @@ class VecImageEnv:
         self.world.reset_worlds(envs, layouts)
         return self._state()
 
+    def _info(self, info):
+        """what ``wrappers=True`` adds: library-owned tensors, rewritten by the next decode / chain"""
+        if self.wrappers:
+            info["speeds"] = self.world.action_outputs["speeds"]
+            if self._close:
+                info["bool_get_close_to_human"] = self.world.obs_post["close_to_human"]
+        return info
+
     def _actions(self, actions):
+        if self.wrappers:  # the policy's output: indices [n] or float rows [n, act_dim], decoded on the device
+            return self.world.decode_actions(actions)
         if isinstance(actions, (list, tuple)) and len(actions) and isinstance(actions[0], ContinuousAction):
             actions = np.array([[a.v, a.w, a.beep] for a in actions], np.float32)  # float32 wire (Agent.msg:8-10)
         return actions
@@ -191,13 +225,13 @@ class VecImageEnv:
         self._episodes += len(finished)
         info = {"dones_info": o["step_dones_info"], "is_clean": o["step_is_clean"], "arrive": o["step_is_arrives"],
                 "collision": o["step_is_collisions"], "all_down": self._all_down, "reset_envs": finished}
-        return self._state(), o["step_rewards"], o["step_dones"], info
+        return self._state(), o["step_rewards"], o["step_dones"], self._info(info)
 
     def _step_device(self, actions):
         o = self.world.step_autoreset_device(self._actions(actions), self._spawn_cfg, self._device_seed0)
         info = {"dones_info": o["step_dones_info"], "is_clean": o["step_is_clean"], "arrive": o["step_is_arrives"],
                 "collision": o["step_is_collisions"], "all_down": self._all_down, "reset_envs": None}
-        return self._state(), o["step_rewards"], o["step_dones"], info
+        return self._state(), o["step_rewards"], o["step_dones"], self._info(info)
 
     def step(self, actions):
         import torch
@@ -220,7 +254,7 @@ class VecImageEnv:
                 info["arrive"], info["collision"] = o["is_arrives"].clone(), o["is_collisions"].clone()
                 self.reset_envs(finished)
                 info["reset_envs"] = finished
-        return self._state(), rewards, dones, info
+        return self._state(), rewards, dones, self._info(info)
 
     def world_maps(self):
         """the map each env's current episode runs on (numpy int32 ``[env_num]``); synchronises the stream"""

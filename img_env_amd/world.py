@@ -20,7 +20,7 @@ def _torch_dtype(np_dtype):
     if _TORCH_DTYPES is None:
         _TORCH_DTYPES = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
                          np.dtype(np.float16): torch.float16, np.dtype(np.uint8): torch.uint8,
-                         np.dtype(np.int8): torch.int8, np.dtype(np.int32): torch.int32}
+                         np.dtype(np.int8): torch.int8, np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64}
     return _TORCH_DTYPES[np.dtype(np_dtype)]
 
 
@@ -113,6 +113,8 @@ class World:
         self.stack = None  # enable_stack()
         self.stack_arena = None
         self.episodes = None  # enable_episodes()
+        self.action_outputs = None  # enable_actions()
+        self.obs_post = None  # enable_obs_post()
         if self.n_maps > 1:
             rest = self.grids[1:]
             rc = self.lib.imgenv_maps_add(self.h, len(rest), rest.ctypes.data, rest.shape[1], rest.shape[2])
@@ -229,6 +231,91 @@ class World:
     def clear_episodes(self):
         """``imgenv_episodes_clear``: totals, ``last_*`` and the open episodes' sums back to zero, ordered on the current stream"""
         self._check(self.lib.imgenv_episodes_clear(self.h, self._stream()), "imgenv_episodes_clear")
+
+    def _views(self, out, arrays, what):
+        """zero-copy tensors over library-owned arrays: ``arrays`` maps a name of ``out`` to (numpy dtype, shape)"""
+        import torch
+        views = {}
+        for name, (dt_, shape) in arrays.items():
+            ptr = getattr(out, name)
+            if not ptr:
+                continue
+            with torch.cuda.device(self.device):
+                t = torch.as_tensor(_DeviceArray(ptr, shape, np.dtype(dt_).str), device=self.device)
+            if t.data_ptr() != ptr or t.dtype != _torch_dtype(dt_):
+                raise RuntimeError("%s.%s: torch made a copy instead of a view" % (what, name))
+            views[name] = t
+        return views
+
+    def enable_actions(self, discrete_actions=None, continuous_actions=None, act_dim=2):
+        """Device-side VelActionWrapper (``imgenv_actions_enable``): ``discrete_actions`` -- the YAML's table, rows of (v, w) or
+        (v, w, beep) -- selects TABLE mode, ``continuous_actions`` -- its (lo, hi) per column -- CLIP mode; ``act_dim`` (2 or 3) is
+        the width of a float input row.  ``self.action_outputs`` maps ``actions`` float32 ``[R, 3]``, ``speeds`` float32 ``[R, 2]``
+        and ``n_bad`` int32 ``[1]`` to zero-copy tensors over the library's memory, filled by ``decode_actions``.  Read-only; valid
+        until ``close()``.  ValueError for a bad cfg or a second call with another one."""
+        if (discrete_actions is None) == (continuous_actions is None):
+            raise ValueError("enable_actions: discrete_actions (a table) or continuous_actions (clip ranges)")
+        c, keep = _cabi.make_actions_cfg(table=discrete_actions, clip=continuous_actions, n_cols=act_dim)
+        ao = _cabi.ActionsOut()
+        rc = self.lib.imgenv_actions_enable(self.h, C.byref(c), C.byref(ao))
+        if rc == _cabi.EINVAL:
+            raise ValueError("imgenv_actions_enable: %s" % self.lib.imgenv_last_error().decode())
+        self._check(rc, "imgenv_actions_enable")
+        if self.action_outputs is None:
+            R = ao.n_local
+            self.action_outputs = self._views(ao, {k: (dt, (R, n) if n else (1,)) for k, (dt, n) in _cabi.ACTION_ARRAYS.items()},
+                                              "imgenv_actions_out")
+            self._act_cols, self._act_table = int(act_dim), discrete_actions is not None
+        return self.action_outputs
+
+    def decode_actions(self, raw):
+        """``imgenv_actions_decode``: what the policy emitted -- a torch tensor or numpy array of int32 / int64 indices ``[R]``
+        (TABLE mode) or float32 / float64 rows ``[R, act_dim]``, kept in its dtype; host data is copied to the device first --
+        becomes ``action_outputs["actions"]``, which is returned and goes to any step call on the same stream.  One launch,
+        ordered on the current stream; also rewrites ``speeds`` and adds the rows it zeroed to ``n_bad``."""
+        import torch
+        if self.action_outputs is None:
+            raise RuntimeError("decode_actions failed (%d): enable_actions was not called" % _cabi.ESTATE)
+        if not isinstance(raw, torch.Tensor):
+            raw = np.ascontiguousarray(raw)
+            if raw.dtype not in _cabi.RAW_DTYPES:
+                raw = raw.astype(np.int64 if raw.dtype.kind in "iub" else np.float64 if raw.dtype.itemsize > 4 else np.float32)
+            raw = torch.as_tensor(raw, device=self.device)
+        if raw.device != self.device or not raw.is_contiguous():
+            raw = raw.to(device=self.device).contiguous()
+        code = {torch.int32: _cabi.RAW_I32, torch.int64: _cabi.RAW_I64, torch.float32: _cabi.RAW_F32, torch.float64: _cabi.RAW_F64}.get(raw.dtype)
+        if code is None:
+            raise ValueError("decode_actions: int32 / int64 indices or float32 / float64 rows, not %s" % raw.dtype)
+        integer = code in (_cabi.RAW_I32, _cabi.RAW_I64)
+        if raw.numel() != self.n_local * (1 if integer else self._act_cols):
+            raise ValueError("decode_actions: %s" % ("one index per robot, [%d]" % self.n_local if integer else
+                                                     "[%d, %d] floats" % (self.n_local, self._act_cols)))
+        # (kept until the next decode: the launch reads it in stream order, a tensor made here from host data must outlive it)
+        self._raw_actions = raw
+        rc = self.lib.imgenv_actions_decode(self.h, C.c_void_p(raw.data_ptr()), code, self._stream())
+        if rc == _cabi.EINVAL:
+            raise ValueError("imgenv_actions_decode: %s" % self.lib.imgenv_last_error().decode())
+        self._check(rc, "imgenv_actions_decode")
+        return self.action_outputs["actions"]
+
+    def enable_obs_post(self, ped_norm=True, close=None, avg=_cabi.PED_NORM_AVG, std=_cabi.PED_NORM_STD, close_dist=_cabi.CLOSE_DIST):
+        """Device-side StatePedVectorWrapper and ``bool_get_close_to_human`` (``imgenv_obs_post_enable``): from now on every reset /
+        step also keeps ``self.obs_post`` -- ``ped_vector_norm`` float32 ``[R, 1 + 7 max_ped]`` (``ped_norm``) and
+        ``close_to_human`` uint8 ``[R]`` (``close``; None = where the handle has pedestrians) -- as zero-copy tensors over the
+        library's memory.  ``out["ped_vector_states"]`` stays the raw vector.  Defaults are the reference's constants."""
+        if close is None:
+            close = self.n_peds > 0
+        c = _cabi.make_obs_post_cfg(ped_norm, close, avg, std, close_dist)
+        po = _cabi.ObsPostOut()
+        rc = self.lib.imgenv_obs_post_enable(self.h, C.byref(c), C.byref(po))
+        if rc == _cabi.EINVAL:
+            raise ValueError("imgenv_obs_post_enable: %s" % self.lib.imgenv_last_error().decode())
+        self._check(rc, "imgenv_obs_post_enable")
+        if self.obs_post is None:
+            R = po.n_local
+            self.obs_post = self._views(po, {"ped_vector_norm": (np.float32, (R, self.out["ped_vector_states"].shape[1])),
+                                             "close_to_human": (np.uint8, (R,))}, "imgenv_obs_post_out")
+        return self.obs_post
 
     def reset(self, layout):
         """Reset everything.  A handle of several worlds (``n_worlds`` > 1) takes either one batch of all robots and
@@ -418,7 +505,7 @@ class World:
 
     def close(self):
         if getattr(self, "h", None):
-            self.episodes = None  # (views of memory the handle owns)
+            self.episodes = self.action_outputs = self.obs_post = None  # (views of memory the handle owns)
             self.lib.imgenv_destroy(self.h)
             self.h = None
 

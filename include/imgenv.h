@@ -570,6 +570,100 @@ int imgenv_episodes_outputs(imgenv_t* h, imgenv_episodes_out* out);
  * if it is long enough. */
 int imgenv_episodes_clear(imgenv_t* h, void* stream);
 
+/* ---- action decoding: VelActionWrapper.action (envs/wrapper/base.py:37-66, envs/action/action.py:8-38) and the `speeds` of
+ * info (base.py:58) as MultiRobotCleanWrapper masks them (base.py:81-83), for every local robot, on the device ----
+ * The step functions take float32 [R][3] = (v, w, beep).  A policy trained on a YAML with discrete_action: True emits one index
+ * into discrete_actions per robot; one trained on continuous_actions emits raw floats that the wrapper clips.  With action
+ * decoding enabled the library turns either into the (v, w, beep) rows itself: imgenv_actions_decode queues ONE launch
+ * (k_actions, csrc/actions.h) on the caller's stream that fills the handle-owned `actions` and `speeds`; the caller then passes
+ * imgenv_actions_out.actions to any imgenv_step*, imgenv_step_begin or imgenv_step_autoreset* call ON THE SAME STREAM.  No step
+ * entry point changes, and a handle that never enables this behaves, launch for launch, as if this section did not exist.
+ *
+ * Per local robot r (a robot shard decodes its local rows; `raw` is [R] or [R][n_cols], contiguous, naturally aligned):
+ *   TABLE mode, integer raw [R]        actions[r] = table[raw[r]] (a two-column row of the YAML has beep 0, action.py:29-30).  An
+ *                                      index outside [0, n_table) gives (0, 0, 0) and is counted in n_bad; it is never read.
+ *                                      (Python would wrap a negative index: a stated deviation.)
+ *   TABLE mode, float raw [R][n_cols]  ContinuousAction(*x) (base.py:43): rounded to float32, not clipped, beep 0 when n_cols is 2
+ *   CLIP mode, float raw [R][n_cols]   column i: x = float32(raw), x = x >= float32(lo_i) ? x : float32(lo_i), then
+ *                                      x = x <= float32(hi_i) ? x : float32(hi_i) (np.clip per component, base.py:45-51; float64
+ *                                      input is rounded first -- rounding is monotone, so this is the reference's clip in double
+ *                                      put on the float32 wire); beep 0 when n_cols is 2.  Integer raw is IMGENV_EINVAL.
+ *   a component that is not finite -- as it came, or once it is float32 (a double beyond float32 that nothing clipped) -- makes
+ *   the whole row (0, 0, 0) and is counted in n_bad.  The reference would carry a NaN into the node; the library must not: cell
+ *   indices are rounded poses.  n_bad is a counter (it only grows), not an error state.
+ *   speeds[r] = (v, w) of the decoded row where the robot is clean, (0, 0) where it is not: `clean` is MultiRobotCleanWrapper's
+ *   state as the last step left it (1 after a reset) -- the is_clean of BEFORE the step, which the step then hands out as
+ *   imgenv_out.step_is_clean and which the reference masks info["speeds"] with.
+ * Ordering: the decode sits on the caller's stream in front of the step's first launch, and every reader of the actions is
+ * ordered behind that launch; `actions` and `speeds` are overwritten only by the next decode, which the caller queues behind the
+ * end of the step's chain.  The decode counts as one launch in the imgenv_step_launches of the step that follows it. */
+#define IMGENV_ACTIONS_TABLE 0
+#define IMGENV_ACTIONS_CLIP 1
+#define IMGENV_ACTIONS_MAX_TABLE 4096
+#define IMGENV_RAW_I32 0   /* `dtype` of imgenv_actions_decode */
+#define IMGENV_RAW_I64 1
+#define IMGENV_RAW_F32 2
+#define IMGENV_RAW_F64 3
+typedef struct imgenv_actions_cfg {
+    int32_t struct_size;          /* sizeof(imgenv_actions_cfg) */
+    int32_t mode;                 /* IMGENV_ACTIONS_TABLE (the YAML's discrete_action: True) | IMGENV_ACTIONS_CLIP */
+    int32_t n_cols;               /* columns of a float `raw` row: 2 (v, w) or 3 (v, w, beep) -- the YAML's act_dim */
+    int32_t n_table;              /* TABLE mode: rows of `table`, 1 .. IMGENV_ACTIONS_MAX_TABLE */
+    const float* table;           /* TABLE mode: HOST [n_table][3] = v, w, beep, every value finite; copied by the call */
+    float clip[3][2];             /* CLIP mode: (lo, hi) of column i < n_cols (the YAML's continuous_actions), finite, lo <= hi */
+} imgenv_actions_cfg;
+/* Device pointers, R = robot_end - robot_begin local robots; owned by the handle, valid until imgenv_destroy(), contents valid
+ * once the stream work of the last imgenv_actions_decode has completed, READ-ONLY for the caller. */
+typedef struct imgenv_actions_out {
+    int32_t struct_size;          /* on entry 0 or sizeof(imgenv_actions_out) */
+    int32_t n_local;              /* R */
+    float* actions;               /* [R][3]  what the step functions take */
+    float* speeds;                /* [R][2]  info["speeds"] */
+    int32_t* n_bad;               /* [1]     rows zeroed so far (out-of-range index, non-finite component) */
+} imgenv_actions_out;
+/* Legal at any time; the memory is the library's.  IMGENV_EINVAL for a wrong struct_size, an unknown mode, n_cols outside {2, 3},
+ * TABLE mode with a null, empty, over-long or non-finite table, CLIP mode with lo > hi or a bound that is not finite in a column
+ * < n_cols, or a second call whose cfg differs from the first's (same cfg: nothing changes, same pointers).  `out` may be NULL. */
+int imgenv_actions_enable(imgenv_t* h, const imgenv_actions_cfg* cfg, imgenv_actions_out* out);
+/* IMGENV_ESTATE before imgenv_actions_enable() */
+int imgenv_actions_outputs(imgenv_t* h, imgenv_actions_out* out);
+/* `raw`: DEVICE pointer, [R] of dtype I32 / I64 (TABLE mode only) or [R][n_cols] of F32 / F64, aligned to its element size, valid
+ * until the launch has run.  IMGENV_ESTATE before imgenv_actions_enable() or before the first reset; IMGENV_EINVAL for a null or
+ * misaligned `raw`, an unknown dtype, or integer `raw` in CLIP mode. */
+int imgenv_actions_decode(imgenv_t* h, const void* raw, int32_t dtype, void* stream);
+
+/* ---- observation post-processing: StatePedVectorWrapper (envs/wrapper/base.py:19-34) and InfoLogWrapper's
+ * bool_get_close_to_human (base.py:250-252) for every local robot, on the device ----
+ * One extra launch at the end of every chain (k_obs_post, csrc/obs_post.h; behind the stacks and the episode statistics): a step
+ * covers every local robot, a reset the robots of the worlds it resets.  Per robot row of imgenv_out.ped_vector_states:
+ *   n = min(int(row[0]), max_ped); ped_vector_norm[0] = row[0];
+ *   for j < n, c < 7: ped_vector_norm[1 + 7 j + c] = float32((double(row[1 + 7 j + c]) - avg[c]) / std[c]) -- the reference's
+ *   float32 slice minus and divided by float64 constants, stored back into the float32 row; the padding behind n is copied.
+ *   close_to_human[r] = imgenv_out.ped_min_dists[r] < close_dist (the reference's close_dist is 1).
+ * The results go to arrays of their own: imgenv_out.ped_vector_states stays the raw vector (normalising it in place is not
+ * offered: the observation kernel and the output guards own that array). */
+#define IMGENV_OBS_PED_NORM 1     /* needs imgenv_cfg.ped_vec_dim == 7 */
+#define IMGENV_OBS_CLOSE 2        /* needs a handle with pedestrians */
+typedef struct imgenv_obs_post_cfg {
+    int32_t struct_size;          /* sizeof(imgenv_obs_post_cfg) */
+    int32_t flags;                /* IMGENV_OBS_PED_NORM | IMGENV_OBS_CLOSE, at least one */
+    double avg[7], std[7];        /* PED_NORM: the reference's are (0, 0, 0, 0, 0.25, 0.25, 0) and (6, 6, 0.6, 0.9, 0.5, 0.5, 6) */
+    double close_dist;            /* CLOSE */
+} imgenv_obs_post_cfg;
+typedef struct imgenv_obs_post_out {
+    int32_t struct_size;          /* on entry 0 or sizeof(imgenv_obs_post_out) */
+    int32_t n_local;              /* R */
+    float* ped_vector_norm;       /* [R][1 + 7 max_ped]; NULL without IMGENV_OBS_PED_NORM */
+    uint8_t* close_to_human;      /* [R]; NULL without IMGENV_OBS_CLOSE */
+} imgenv_obs_post_out;
+/* Legal at any time (the arrays are zero until the next chain has run); the memory is the library's, ownership as for
+ * imgenv_actions_out.  IMGENV_EINVAL for a wrong struct_size, no or unknown flags, PED_NORM with std[c] == 0, a constant that is
+ * not finite or ped_vec_dim != 7, CLOSE on a handle without pedestrians or with a close_dist that is not a number, or a second
+ * call whose cfg differs from the first's (same cfg: nothing changes, same pointers).  `out` may be NULL. */
+int imgenv_obs_post_enable(imgenv_t* h, const imgenv_obs_post_cfg* cfg, imgenv_obs_post_out* out);
+/* IMGENV_ESTATE before imgenv_obs_post_enable() */
+int imgenv_obs_post_outputs(imgenv_t* h, imgenv_obs_post_out* out);
+
 /* ---- map bank: several static maps in one handle, one of them per world and episode ----
  * The reference trains one policy over a set of maps: its trainer is started from several YAML files side by side
  * (create_launch.py:57-65, one node per (env_name, env_num) pair), each env process loads its own global_map.map_file

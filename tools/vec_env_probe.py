@@ -10,7 +10,12 @@ write before; --stack-compare alternates no stack / library stack / torch stack 
 
 --episodes adds the per-robot episode statistics of TestEpisodeWrapper kept by the library (imgenv_episodes_enable);
 --torch-episodes keeps the same figures with EpisodeStats and torch ops on top of a plain VecImageEnv; --episodes-compare
-alternates no statistics / library / torch over several rounds and writes the raw figures."""
+alternates no statistics / library / torch over several rounds and writes the raw figures.
+
+--wrappers table|clip feeds the policy's raw output (indices into a 28-row table, or float rows to be clipped) to
+VecImageEnv(wrappers=True): decode, speeds, normalised pedestrian vectors and close_to_human kept by the library;
+--torch-wrappers keeps the same with torch ops on top of a plain VecImageEnv; --wrappers-compare alternates pre-decoded actions
+with nothing enabled / library / torch over several rounds, for the table and for the clip, and writes the raw figures."""
 import argparse
 import json
 import os
@@ -125,16 +130,55 @@ class TorchEpisodes:
                     avg_return=float(self.return_sum.sum()) / n, avg_len=int(self.len_sum.sum()) / n)
 
 
+TABLE28 = [[v, w] for v in (0.0, 0.2, 0.4, 0.6) for w in (-0.9, -0.6, -0.3, 0.0, 0.3, 0.6, 0.9)]  # the shape of the shipped YAMLs' table
+WRAPPER_LIST = ["VelActionWrapper", "TimeLimitWrapper", "SensorsPaperRewardWrapper", "InfoLogWrapper", "MultiRobotCleanWrapper",
+                "StatePedVectorWrapper"]
+
+
+class TorchWrappers:
+    """what ``VecImageEnv(wrappers=True)`` hands out, kept with torch ops around a plain VecImageEnv: ``VelActionWrapper.action``'s
+    torch path (img_env_amd/envs.py) in front of the step; behind it the speeds masked by the step's ``is_clean``, the pedestrian
+    vectors normalised under a mask of the per-row counts (no ``.item()``: no host synchronisation) and ``ped_min_dists < 1``"""
+
+    def __init__(self, env):
+        import torch
+        from img_env_amd import _cabi
+        from img_env_amd.envs import VelActionWrapper
+        self.env, dev = env, env.world.device
+        self.vel = VelActionWrapper(None, env.cfg)
+        self.max_ped = int(env.cfg["max_ped"])
+        self.avg = torch.tensor(_cabi.PED_NORM_AVG, dtype=torch.float64, device=dev)
+        self.std = torch.tensor(_cabi.PED_NORM_STD, dtype=torch.float64, device=dev)
+        self.slots = torch.arange(self.max_ped, device=dev).view(1, -1, 1)
+
+    def action(self, raw):
+        return self.vel.action(raw)
+
+    def after(self, a, info):
+        import torch
+        o = self.env.world.out
+        speeds = a[:, :2] * info["is_clean"].unsqueeze(1).to(a.dtype)
+        p = o["ped_vector_states"]
+        body = p[:, 1:].view(p.shape[0], self.max_ped, 7)
+        normed = ((body.double() - self.avg) / self.std).float()
+        n = p[:, 0].clamp(max=self.max_ped).long().view(-1, 1, 1)
+        norm = torch.cat([p[:, :1], torch.where(self.slots < n, normed, body).view(p.shape[0], -1)], dim=1)
+        close = o["ped_min_dists"] < 1
+        return speeds, norm, close
+
+
 def stack_depths(stack):
     """(image, state, laser) YAML keys -> effective depths (base.py:103-105)"""
     return (max(stack[0], 0), max(stack[1], 0), max(stack[2], 1) if stack[2] >= 0 else 0)
 
 
 def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, natives=(False, True, "device"), stack=None,
-            torch_stack=False, episodes=None):
+            torch_stack=False, episodes=None, wrappers=None):
     """robot-steps/s of VecImageEnv over `steps` steps, after the envs have drifted out of phase.  ``stack`` = (image_batch,
     state_batch, laser_batch): with the library's frame stacks, or (``torch_stack``) the same kept by torch ops on top;
-    ``episodes`` = "library" | "torch": with the per-robot episode statistics, kept by the library or by ``TorchEpisodes``"""
+    ``episodes`` = "library" | "torch": with the per-robot episode statistics, kept by the library or by ``TorchEpisodes``;
+    ``wrappers`` = (kind, by): kind "table" | "clip", by "none" (pre-decoded actions, nothing enabled) | "library"
+    (``wrappers=True`` fed the raw output) | "torch" (``TorchWrappers`` fed the raw output)"""
     import torch
     from img_env_amd import worldgen
     from img_env_amd.vec_env import VecImageEnv
@@ -144,8 +188,11 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
         cfg = worldgen.make_yaml_cfg(robots, peds, grid, time_max=time_max, n_obstacles=obstacles, seed=5)
         if stack is not None:
             cfg.update(image_batch=stack[0], state_batch=stack[1], laser_batch=stack[2])
+        if wrappers is not None:
+            cfg.update(max_ped=10, wrapper=list(WRAPPER_LIST), discrete_action=wrappers[0] == "table", discrete_actions=TABLE28)
         env = VecImageEnv(cfg, env_num=envs, seed=5, native_spawn=bool(native), device_reset=native == "device",
-                          stack=stack is not None and not torch_stack, episode_stats=episodes == "library")
+                          stack=stack is not None and not torch_stack, episode_stats=episodes == "library",
+                          wrappers=wrappers is not None and wrappers[1] == "library")
         te = TorchEpisodes(env) if episodes == "torch" else None
         ts = TorchStack(env, stack_depths(stack)) if stack is not None and torch_stack else None
         n = len(env)
@@ -153,6 +200,31 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
         acts = torch.zeros(16, n, 3, device="cuda")
         acts[:, :, 0] = torch.rand(16, n, generator=g, device="cuda") * 0.6
         acts[:, :, 1] = torch.rand(16, n, generator=g, device="cuda") * 1.8 - 0.9
+        tw = None
+        if wrappers is not None:
+            # the policy's raw output: indices, or (v, w) a third of which lie outside the clip range; "none" steps what they decode to
+            from img_env_amd.envs import VelActionWrapper
+            if wrappers[0] == "table":
+                raw = torch.randint(0, len(TABLE28), (16, n), generator=g, device="cuda")
+            else:
+                raw = torch.stack([torch.rand(16, n, generator=g, device="cuda") * 0.9 - 0.15,
+                                   torch.rand(16, n, generator=g, device="cuda") * 2.7 - 1.35], dim=2)
+            if wrappers[1] == "none":
+                vel = VelActionWrapper(None, cfg)
+                acts = torch.stack([vel.action(raw[k]) for k in range(16)]).float().contiguous()
+            else:
+                acts = raw
+                tw = TorchWrappers(env) if wrappers[1] == "torch" else None
+        kept = None
+
+        def step(a):
+            nonlocal kept
+            if tw is None:
+                return env.step(a)
+            a = tw.action(a)
+            res = env.step(a)
+            kept = tw.after(a, res[3])
+            return res
         t0 = time.perf_counter()
         env.reset()
         if ts:
@@ -162,7 +234,7 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
         torch.cuda.synchronize()
         t_reset = time.perf_counter() - t0
         for s in range(time_max + 20):  # past the first wave of time limits: the envs drift out of phase as robots collide
-            _, rew, _, info = env.step(acts[s % 16])
+            _, rew, _, info = step(acts[s % 16])
             if ts:
                 ts.push(info["all_down"])
             if te:
@@ -171,7 +243,7 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
         placed0 = sum(env.world.autoreset_last()[::-1][0:1]) + len(env.world.autoreset_last()[0]) if native == "device" else 0
         resets, t0 = 0, time.perf_counter()
         for s in range(steps):
-            _, rew, _, info = env.step(acts[s % 16])
+            _, rew, _, info = step(acts[s % 16])
             if ts:
                 ts.push(info["all_down"])
             if te:
@@ -200,6 +272,8 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
     extra = {} if stack is None else dict(stack=list(stack), stack_by="torch" if torch_stack else "library")
     if episodes is not None:
         extra["episodes_by"] = episodes
+    if wrappers is not None:
+        extra["wrappers"], extra["wrappers_by"] = wrappers
     return dict(envs=envs, robots_per_env=robots, peds_per_env=peds, **extra, **out)
 
 
@@ -256,6 +330,33 @@ def compare_episodes(args, rounds=3):
                 rounds=rounds, runs=runs, summary=summary)
 
 
+def compare_wrappers(args, rounds=3):
+    """pre-decoded actions with nothing enabled / wrappers=True / torch ops, alternating, `rounds` times, for the table and the
+    clip, per reset variant"""
+    natives = (True, "device")
+    runs = []
+    for kind in ("table", "clip"):
+        for rnd in range(rounds):
+            for mode in ("none", "library", "torch"):
+                r = measure(args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max, natives, wrappers=(kind, mode))
+                for variant in ("native_spawn", "device_reset"):
+                    runs.append(dict(kind=kind, round=rnd, mode=mode, variant=variant, us_per_step=r[variant]["us_per_step"],
+                                     env_resets_per_step=r[variant]["env_resets_per_step"]))
+                    print(json.dumps(runs[-1]), flush=True)
+    summary = []
+    for kind in ("table", "clip"):
+        for variant in ("native_spawn", "device_reset"):
+            row = dict(kind=kind, variant=variant)
+            for mode in ("none", "library", "torch"):
+                v = [r["us_per_step"] for r in runs if r["kind"] == kind and r["variant"] == variant and r["mode"] == mode]
+                row[mode] = dict(us_per_step_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
+            row["added_us_library"] = row["library"]["median"] - row["none"]["median"]
+            row["added_us_torch"] = row["torch"]["median"] - row["none"]["median"]
+            summary.append(row)
+    return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, steps=args.steps, time_max=args.time_max,
+                rounds=rounds, runs=runs, summary=summary)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
@@ -273,9 +374,20 @@ def main():
     ap.add_argument("--torch-episodes", action="store_true", help="the same statistics kept with EpisodeStats and torch ops")
     ap.add_argument("--episodes-compare", action="store_true",
                     help="no statistics / library / torch_episodes, alternating over --rounds rounds")
+    ap.add_argument("--wrappers", default=None, choices=("table", "clip"), help="the policy's raw output decoded by the library (wrappers=True)")
+    ap.add_argument("--torch-wrappers", action="store_true", help="with --wrappers: the same kept with torch ops on a plain VecImageEnv")
+    ap.add_argument("--wrappers-compare", action="store_true",
+                    help="pre-decoded actions / library / torch, alternating over --rounds rounds, table and clip")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None, help="--stack-compare / --episodes-compare: also write the JSON here")
     args = ap.parse_args()
+    if args.wrappers_compare:
+        res = compare_wrappers(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
+        return
     if args.episodes_compare:
         res = compare_episodes(args, args.rounds)
         if args.out:
@@ -293,7 +405,8 @@ def main():
     natives = ("device",) if args.device_only else (False, True, "device")
     stack = tuple(int(v) for v in args.stack.split(",")) if args.stack else None
     print(json.dumps(measure(args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max, natives, stack=stack,
-                             torch_stack=args.torch_stack, episodes="torch" if args.torch_episodes else "library" if args.episodes else None)))
+                             torch_stack=args.torch_stack, episodes="torch" if args.torch_episodes else "library" if args.episodes else None,
+                             wrappers=(args.wrappers, "torch" if args.torch_wrappers else "library") if args.wrappers else None)))
 
 
 if __name__ == "__main__":

@@ -5,7 +5,9 @@
 //                               before an early return are untouched, so counter differences between builds are phase costs
 //                               (tools/run_exp_pmc.sh)
 //   -DIMGENV_EXP_TINY_RESOLVE   hardly any room for the chunk descriptors / result slots of the resolve: every robot runs its
-//                               "no room" fallbacks; the parity suites run on such a build (tools/check_k_view.sh)
+//                               "no room" fallbacks (a developer switch: the product build's fallbacks are held by
+//                               tests/test_k_view_resolve_room.py, which replays the resolve on the CPU with these caps, and by
+//                               tests/test_gpu_k_view_resolve_room.py, whose views run out of the product caps)
 //   -DIMGENV_EXP_RESOLVE_STATS  device-side counts of the cells a top beam leaves alone and of the ray lists behind them
 //                               (tools/resolve_stats.py)
 //   -DIMGENV_EXP_EVERY_CELL     k_view's crop and final pass over every cell in the steps too (what they did until round 4)

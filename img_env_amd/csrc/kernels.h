@@ -2594,7 +2594,7 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu(8, 8)
         const int n_even = (n_skip + 1) & ~1;
         uint2* desc = (uint2*)(skip_list + n_even);
         uint32_t* slots = (uint32_t*)colt;
-        const int cap_d = EXP_RESOLVE_CAP((NCp / 4 - n_even) / 2, 5), cap_r = EXP_RESOLVE_CAP(4 * Wv, 2);  // (test builds: hardly any room)
+        const int cap_d = plan_resolve_cap_d(NC, n_skip, EXP_RESOLVE_CAP(false, true)), cap_r = plan_resolve_cap_r(Wv, EXP_RESOLVE_CAP(false, true));  // (launch_plan.h; test builds: hardly any room)
         const uint2 NOP = make_uint2(0xFFFFFFFFu, 0u);
         const uint32_t h01 = h0 | (h1 << 16);
         EXP_RESOLVE_STATS_CELLS(w, k, hit, skip_list, n_skip, tid, NT);

@@ -150,6 +150,19 @@ inline int plan_obs_E(int PP) { return PP <= 1024 ? PP / WAVE : 0; }
 inline size_t plan_lds_view(size_t view_cells, size_t hit_stride, int Wv) {
     return ((view_cells + 16) & ~(size_t)15) + 4 * hit_stride + 16 * (size_t)Wv + 16 + 4 * (2 * (hit_stride / 8 + 1) + 4);
 }
+// k_view step (5): the room its resolve has in LDS that is dead by then, for a view of NC cells in rows of Wv whose final pass left
+// n_skip entries in the skip list -- cap_d chunk descriptors (8 bytes each) behind the list, in what remains of the crop's
+// ((NC + 16) & ~15) bytes, and cap_r result slots (4 bytes each) in the column table's 16 Wv bytes.  A cell that finds no room
+// walks its list alone.  tiny: the -DIMGENV_EXP_TINY_RESOLVE build (exp_hooks.h), where nearly every cell does.
+// (constexpr: the kernel calls it too; tests/host/k_view_resolve_room_check.cpp replays step (5) with these and smaller caps)
+struct ResolveRoom {
+    int cap_d, cap_r;
+};
+inline constexpr int plan_resolve_cap_d(int NC, int n_skip, bool tiny) { return tiny ? 5 : (((NC + 16) & ~15) / 4 - ((n_skip + 1) & ~1)) / 2; }
+inline constexpr int plan_resolve_cap_r(int Wv, bool tiny) { return tiny ? 2 : 4 * Wv; }
+inline constexpr ResolveRoom plan_resolve_room(int NC, int Wv, int n_skip, bool tiny = false) {
+    return ResolveRoom{plan_resolve_cap_d(NC, n_skip, tiny), plan_resolve_cap_r(Wv, tiny)};
+}
 inline size_t plan_lds_obs(int obs_E, int PP, int Pw) {
     return (obs_E == 0 ? (size_t)PP * 8 : 0) + (size_t)(Pw > 0 ? Pw : 1) * 8 + (size_t)PP * 4 + WAVE * 7 * 4 + 16;
 }

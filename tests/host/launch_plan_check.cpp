@@ -533,6 +533,18 @@ static void thresholds() {
     CHECK_EQ(plan_lds_obs(1, 64, 0), 8 + 64 * 4 + 64 * 7 * 4 + 16);
     // k_view's LDS: src u8 (+ dummy cells, to 16 bytes) | hit u32 | column terms | cursors | three levels of largest hit steps
     CHECK_EQ(plan_lds_view(48 * 48, 364, 48), 2320 + 4 * 364 + 16 * 48 + 16 + 4 * (2 * 46 + 4));
+    // the room of k_view's step (5): descriptors (8 bytes) in what the skip list (rounded to an even count) leaves of the crop's
+    // 2320 bytes, slots (4 bytes) in the column table's 16 bytes per column; the tiny build's caps
+    CHECK_EQ(plan_resolve_room(48 * 48, 48, 0).cap_d, 290);
+    CHECK_EQ(plan_resolve_room(48 * 48, 48, 35).cap_d, (580 - 36) / 2);
+    CHECK_EQ(plan_resolve_room(48 * 48, 48, 36).cap_d, (580 - 36) / 2);
+    CHECK_EQ(plan_resolve_room(48 * 48, 48, 35).cap_r, 192);
+    CHECK_EQ(plan_resolve_room(16 * 16, 16, 21).cap_d, 23);
+    CHECK_EQ(plan_resolve_room(48 * 8, 8, 82).cap_d, 9);
+    CHECK_EQ(plan_resolve_room(48 * 8, 8, 82).cap_r, 32);
+    CHECK_EQ(plan_resolve_room(12, 4, 3).cap_d, 0);  // (never negative: a view of NC cells lists at most (NC + 3) / 4 entries)
+    CHECK_EQ(plan_resolve_room(48 * 48, 48, 35, true).cap_d, 5);
+    CHECK_EQ(plan_resolve_room(48 * 48, 48, 35, true).cap_r, 2);
     CHECK_EQ(LDS_DEFAULT_MAX, 64 * 1024);
     CHECK_EQ(LDS_MAX, 160 * 1024);
 }

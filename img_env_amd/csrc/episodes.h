@@ -5,7 +5,7 @@
 //
 // One kernel, two instantiations, launched at the end of every chain (launch_views) on the caller's stream:
 //   accumulate (a step)         every local robot takes the step's command, reward and is_clean into its open episode
-//   fold       (a reset chain)  the robots of the worlds the chain covers close their episode by the LAST STEP's dones_info
+//   fold       (a reset chain)  the robots of the worlds the chain covers (tail_rows.h) close their episode by the LAST STEP's dones_info
 //                               (imgenv_out.step_dones_info: a reset never touches it) and open the next one
 // An auto-reset call runs a step chain and a reset chain, so a finished world's last step is accumulated and then folded.
 //
@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "launch_plan.h"  // EP_BLOCK, EP_MAX_BLOCKS
+#include "tail_rows.h"
 
 // float64 rows: the open episode first (EpisodeStats' members, envs.py:388-396, then the running return) ...
 enum {
@@ -57,18 +58,14 @@ struct EpisodesDev {
     const int32_t* step_dones_info;
     double dt;                   // control_hz: the divisor of the acceleration / jerk terms
     int32_t min_steps;
-    int32_t RL, r0, Rw;          // local robots, first local robot's world-wide index, robots per world
-    // fold: the worlds of the reset chain (nullptr = every local robot), their count on the host or in device memory
-    const int* list;
-    const int* n_dev;
-    int32_t n_worlds;
+    TailRows rows;               // the robots of this launch (fold: those of the reset chain's worlds)
 };
 
 __device__ __forceinline__ double ep_round4(double x) { return rint(x * 1e4) / 1e4; }  // torch.round(x * 1e4) / 1e4
 
 // EpisodeStats.add (envs.py:398-415) and TestEpisodeWrapper.step (envs.py:466-475) for robot row `r`
 __device__ __forceinline__ void ep_accumulate(const EpisodesDev& e, size_t r) {
-    const size_t RL = (size_t)e.RL;
+    const size_t RL = (size_t)e.rows.RL;
     double* f = e.f + r;
     int32_t* q = e.i + r;
     if (q[EPI_OPEN * RL] == 0) return;  // enabled in mid-episode: nothing is kept until a reset has opened one
@@ -107,7 +104,7 @@ __device__ __forceinline__ void ep_accumulate(const EpisodesDev& e, size_t r) {
 
 // TestEpisodeWrapper.reset / _count (envs.py:477-500) and EpisodeStats.finish (envs.py:417-431) for robot row `r`
 __device__ __forceinline__ void ep_fold(const EpisodesDev& e, size_t r) {
-    const size_t RL = (size_t)e.RL;
+    const size_t RL = (size_t)e.rows.RL;
     double* f = e.f + r;
     int32_t* q = e.i + r;
     const int steps = q[EPI_TMP_STEPS * RL];
@@ -156,18 +153,11 @@ __device__ __forceinline__ void ep_fold(const EpisodesDev& e, size_t r) {
 
 template <bool FOLD>
 __global__ __launch_bounds__(EP_BLOCK) void k_episodes(const EpisodesDev e) {
-    // robots of this launch: every local one, or those of the listed worlds (blocks stride over whatever the count turns out to be)
-    const bool listed = FOLD && e.list != nullptr;
-    const size_t total = listed ? (size_t)(e.n_dev ? *e.n_dev : e.n_worlds) * (size_t)e.Rw : (size_t)e.RL;
-    const size_t stride = (size_t)gridDim.x * EP_BLOCK;
+    // robots of this launch (tail_rows.h; blocks stride over whatever the count turns out to be)
+    const bool listed = FOLD && e.rows.list != nullptr;
+    const size_t total = tail_rows_count(e.rows, listed), stride = (size_t)gridDim.x * EP_BLOCK;
     for (size_t t = (size_t)blockIdx.x * EP_BLOCK + threadIdx.x; t < total; t += stride) {
-        size_t row = t;
-        if (listed) {
-            const size_t w = t / (size_t)e.Rw;
-            const long long g = (long long)e.list[w] * e.Rw + (long long)(t - w * (size_t)e.Rw) - e.r0;
-            if (g < 0 || g >= e.RL) continue;  // (a world of another shard: nothing of it lives here)
-            row = (size_t)g;
-        }
+        const size_t row = tail_rows_row(e.rows, listed, t);
         if (FOLD) ep_fold(e, row);
         else ep_accumulate(e, row);
     }

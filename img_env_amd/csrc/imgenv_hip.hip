@@ -1650,6 +1650,12 @@ static int launch_rasters(imgenv* h, hipStream_t st, int is_reset, bool moved, b
     return 0;
 }
 
+// The robot rows the chain in hand covers, for its tail kernels (tail_rows.h): every local one, or those of a reset chain's list
+static TailRows tail_rows(const imgenv* h, int is_reset) {
+    const DevWorld& d = h->d;
+    return {h->RL, h->Rw, is_reset ? d.act_list : nullptr, is_reset ? d.act_n_dev : nullptr, d.act_nw};
+}
+
 // The chain behind the move: side launches, rasters, compose, views, the tails' stacks and statistics -- plan, then launch in stream order
 static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
     DevWorld& d = h->d;
@@ -1753,10 +1759,8 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
         // the observation stacks (stack.h), behind the join of the side streams and in front of the seal: a step pushes every local
         // robot's new frames, a reset chain restarts the stacks of the robots it covers (plan_tail_rows)
         StackDev sd = h->stack;
-        sd.list = is_reset ? d.act_list : nullptr;
-        sd.n_dev = is_reset ? d.act_n_dev : nullptr;
-        sd.n_worlds = d.act_nw;
-        const LaunchShape g = plan_stack_launch(p, c, sd.chunks_per_robot);
+        sd.rows = tail_rows(h, is_reset);
+        const LaunchShape g = plan_tail_launch(p, c, sd.chunks_per_robot, STACK_BLOCK, STACK_MAX_BLOCKS);
         (is_reset ? k_stack<true> : k_stack<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(sd);
         h->launches += 1;
     }
@@ -1765,10 +1769,8 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
         // open episode, a reset chain folds the episodes of the robots it covers by the last step's dones_info (grid as for k_stack)
         EpisodesDev ed = h->ep;
         ed.actions = h->ep_actions;
-        ed.list = is_reset ? d.act_list : nullptr;
-        ed.n_dev = is_reset ? d.act_n_dev : nullptr;
-        ed.n_worlds = d.act_nw;
-        const LaunchShape g = plan_episodes_launch(p, c);
+        ed.rows = tail_rows(h, is_reset);
+        const LaunchShape g = plan_tail_launch(p, c, 1, EP_BLOCK, EP_MAX_BLOCKS);
         (is_reset ? k_episodes<true> : k_episodes<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(ed);
         h->launches += 1;
     }
@@ -1776,10 +1778,8 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
         // the normalised pedestrian vectors and close_to_human (obs_post.h), last: of every local robot after a step, of the robots
         // a reset chain covers (k_stack<true>'s cases)
         ObsPostDev pd = h->post;
-        pd.list = is_reset ? d.act_list : nullptr;
-        pd.n_dev = is_reset ? d.act_n_dev : nullptr;
-        pd.n_worlds = d.act_nw;
-        const LaunchShape g = plan_obs_post_launch(p, c, (size_t)pd.per_row);
+        pd.rows = tail_rows(h, is_reset);
+        const LaunchShape g = plan_tail_launch(p, c, (size_t)pd.per_row, OBS_POST_BLOCK, OBS_POST_MAX_BLOCKS);
         (is_reset ? k_obs_post<true> : k_obs_post<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(pd);
         h->launches += 1;
     }
@@ -3369,6 +3369,35 @@ extern "C" int imgenv_outputs(imgenv_t* h, imgenv_out* out) {
     return IMGENV_OK;
 }
 
+// ---- what the enable / outputs entry points of the optional features (stacks, episode statistics, action decoding, observation
+// post-processing) share ----
+// the cfg and the caller's out struct of an enable call, before the handle is looked at: these refusals need no device.  An out
+// struct says 0 or this library's size.
+template <typename Cfg, typename Out>
+static int enable_args(const Cfg* c, const char* cfg_name, const Out* out, const char* out_name) {
+    if (!c) FAIL(IMGENV_EINVAL, "null argument");
+    if (c->struct_size != (int32_t)sizeof(Cfg)) FAIL(IMGENV_EINVAL, "%s.struct_size %d (this library's is %d)", cfg_name, c->struct_size, (int)sizeof(Cfg));
+    if (out && out->struct_size != 0 && out->struct_size != (int32_t)sizeof(Out)) FAIL(IMGENV_EINVAL, "%s.struct_size", out_name);
+    return IMGENV_OK;
+}
+// the end of an enable call: `o`, zeroed but for the feature's own fields, becomes the handle's struct and the feature is on
+template <typename Out>
+static int enable_done(imgenv* h, Out o, Out imgenv::*stored, bool imgenv::*on, Out* out) {
+    o.struct_size = (int32_t)sizeof(Out);
+    o.n_local = h->RL;
+    h->*stored = o;
+    h->*on = true;
+    if (out) *out = o;
+    return IMGENV_OK;
+}
+template <typename Out>
+static int feature_outputs(imgenv* h, bool imgenv::*on, Out imgenv::*stored, Out* out, const char* enable_name) {
+    if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
+    if (!(h->*on)) FAIL(IMGENV_ESTATE, "%s was not called", enable_name);
+    *out = h->*stored;
+    return IMGENV_OK;
+}
+
 // ---- observation stacks (include/imgenv.h; the kernel is csrc/stack.h) ----
 struct StackPlan {
     int depth[3];          // effective depths: sensor_maps, vector_states, lasers (0 = not stacked)
@@ -3405,9 +3434,9 @@ extern "C" int64_t imgenv_stack_bytes(const imgenv_cfg* cfg, const imgenv_stack_
 }
 
 extern "C" int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgenv_stack_out* out) {
-    if (!h || !s) FAIL(IMGENV_EINVAL, "null argument");
-    if (s->struct_size != (int32_t)sizeof(imgenv_stack_cfg)) FAIL(IMGENV_EINVAL, "imgenv_stack_cfg.struct_size %d (this library's is %d)", s->struct_size, (int)sizeof(imgenv_stack_cfg));
-    if (out && out->struct_size != 0 && out->struct_size != (int32_t)sizeof(imgenv_stack_out)) FAIL(IMGENV_EINVAL, "imgenv_stack_out.struct_size");
+    // (unlike the other three: the handle with the cfg, a second call is refused, and so is one after the first reset)
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    RTRY(enable_args(s, "imgenv_stack_cfg", out, "imgenv_stack_out"));
     if (h->stack_on) FAIL(IMGENV_ESTATE, "imgenv_stack_enable has already been called on this handle");
     bool any_reset = h->has_reset;
     for (char r : h->world_ready) any_reset = any_reset || r;
@@ -3432,7 +3461,6 @@ extern "C" int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgen
     unsigned char* ptr[3] = {nullptr, nullptr, nullptr};
     StackDev sd;
     memset(&sd, 0, sizeof(sd));
-    sd.RL = h->RL; sd.r0 = h->r0; sd.Rw = h->Rw;
     for (int k = 0; k < 3; k++) {
         if (p.depth[k] == 1) ptr[k] = handed[k];  // [R][1][...] is the imgenv_out array itself
         if (p.depth[k] < 2) continue;
@@ -3447,22 +3475,14 @@ extern "C" int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgen
         sd.chunks_per_robot += f.chunks;
     }
     h->stack = sd;
-    imgenv_stack_out& o = h->stack_out;
-    memset(&o, 0, sizeof(o));
-    o.struct_size = (int32_t)sizeof(imgenv_stack_out);
-    o.n_local = h->RL;
+    imgenv_stack_out o = {};
     o.image_depth = p.depth[0]; o.state_depth = p.depth[1]; o.laser_depth = p.depth[2];
     o.sensor_maps = (uint16_t*)ptr[0]; o.vector_states = (float*)ptr[1]; o.lasers = (double*)ptr[2];
-    h->stack_on = true;
-    if (out) *out = o;
-    return IMGENV_OK;
+    return enable_done(h, o, &imgenv::stack_out, &imgenv::stack_on, out);
 }
 
 extern "C" int imgenv_stack_outputs(imgenv_t* h, imgenv_stack_out* out) {
-    if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->stack_on) FAIL(IMGENV_ESTATE, "imgenv_stack_enable was not called");
-    *out = h->stack_out;
-    return IMGENV_OK;
+    return feature_outputs(h, &imgenv::stack_on, &imgenv::stack_out, out, "imgenv_stack_enable");
 }
 
 // ---- episode statistics (include/imgenv.h; the kernel is csrc/episodes.h) ----
@@ -3470,10 +3490,7 @@ static_assert(EPF_OPEN_ROWS == IMGENV_EP_OPEN_F64 && EPI_EPISODES - EPI_ENDS0 ==
               "episodes.h rows against include/imgenv.h");
 extern "C" int imgenv_episodes_enable(imgenv_t* h, const imgenv_episodes_cfg* c, imgenv_episodes_out* out) {
     // (the cfg first: its refusals need no handle, and so no device)
-    if (!c) FAIL(IMGENV_EINVAL, "null argument");
-    if (c->struct_size != (int32_t)sizeof(imgenv_episodes_cfg))
-        FAIL(IMGENV_EINVAL, "imgenv_episodes_cfg.struct_size %d (this library's is %d)", c->struct_size, (int)sizeof(imgenv_episodes_cfg));
-    if (out && out->struct_size != 0 && out->struct_size != (int32_t)sizeof(imgenv_episodes_out)) FAIL(IMGENV_EINVAL, "imgenv_episodes_out.struct_size");
+    RTRY(enable_args(c, "imgenv_episodes_cfg", out, "imgenv_episodes_out"));
     if (!(c->dt > 0.0) || !std::isfinite(c->dt)) FAIL(IMGENV_EINVAL, "imgenv_episodes_cfg.dt must be > 0 (the YAML's control_hz)");
     if (c->min_steps < 0) FAIL(IMGENV_EINVAL, "imgenv_episodes_cfg.min_steps must be >= 0");
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
@@ -3496,30 +3513,21 @@ extern "C" int imgenv_episodes_enable(imgenv_t* h, const imgenv_episodes_cfg* c,
     e.step_dones_info = h->out.step_dones_info;
     e.dt = c->dt;
     e.min_steps = c->min_steps;
-    e.RL = h->RL; e.r0 = h->r0; e.Rw = h->Rw;
     h->ep = e;
     h->ep_cfg = *c;
     h->ep_clear_bytes = f_bytes + sizeof(int32_t) * EPI_CLEARED_ROWS * RL;
-    imgenv_episodes_out& o = h->ep_out;
-    memset(&o, 0, sizeof(o));
-    o.struct_size = (int32_t)sizeof(imgenv_episodes_out);
-    o.n_local = h->RL;
+    imgenv_episodes_out o = {};
     o.ends = e.i + EPI_ENDS0 * RL; o.episodes = e.i + EPI_EPISODES * RL; o.short_episodes = e.i + EPI_SHORT * RL;
     o.speed_steps = e.i + EPI_SPEED_STEPS * RL; o.arrive_steps = e.i + EPI_ARRIVE_STEPS * RL; o.len_sum = e.i + EPI_LEN_SUM * RL;
     o.v_sum = e.f + EPF_V_SUM * RL; o.w_sum = e.f + EPF_W_SUM * RL; o.figure_sums = e.f + EPF_FIG0 * RL; o.return_sum = e.f + EPF_RETURN_SUM * RL;
     o.last_code = e.i + EPI_LAST_CODE * RL; o.last_steps = e.i + EPI_LAST_STEPS * RL; o.last_len = e.i + EPI_LAST_LEN * RL;
     o.last_episode = e.i + EPI_LAST_EPISODE * RL; o.last_return = e.f + EPF_LAST_RETURN * RL;
     o.open_f64 = e.f; o.open_steps = e.i + EPI_TMP_STEPS * RL; o.open_len = e.i + EPI_LEN * RL; o.open = e.i + EPI_OPEN * RL;
-    h->ep_on = true;
-    if (out) *out = o;
-    return IMGENV_OK;
+    return enable_done(h, o, &imgenv::ep_out, &imgenv::ep_on, out);
 }
 
 extern "C" int imgenv_episodes_outputs(imgenv_t* h, imgenv_episodes_out* out) {
-    if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->ep_on) FAIL(IMGENV_ESTATE, "imgenv_episodes_enable was not called");
-    *out = h->ep_out;
-    return IMGENV_OK;
+    return feature_outputs(h, &imgenv::ep_on, &imgenv::ep_out, out, "imgenv_episodes_enable");
 }
 
 extern "C" int imgenv_episodes_clear(imgenv_t* h, void* stream) {
@@ -3540,10 +3548,7 @@ static bool actions_cfg_same(const imgenv* h, const imgenv_actions_cfg* c) {
 }
 extern "C" int imgenv_actions_enable(imgenv_t* h, const imgenv_actions_cfg* c, imgenv_actions_out* out) {
     // (the cfg first: its refusals need no handle, and so no device)
-    if (!c) FAIL(IMGENV_EINVAL, "null argument");
-    if (c->struct_size != (int32_t)sizeof(imgenv_actions_cfg))
-        FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.struct_size %d (this library's is %d)", c->struct_size, (int)sizeof(imgenv_actions_cfg));
-    if (out && out->struct_size != 0 && out->struct_size != (int32_t)sizeof(imgenv_actions_out)) FAIL(IMGENV_EINVAL, "imgenv_actions_out.struct_size");
+    RTRY(enable_args(c, "imgenv_actions_cfg", out, "imgenv_actions_out"));
     if (c->mode != IMGENV_ACTIONS_TABLE && c->mode != IMGENV_ACTIONS_CLIP) FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.mode %d", c->mode);
     if (c->n_cols != 2 && c->n_cols != 3) FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.n_cols %d: 2 (v, w) or 3 (v, w, beep)", c->n_cols);
     if (c->mode == IMGENV_ACTIONS_TABLE) {
@@ -3584,21 +3589,13 @@ extern "C" int imgenv_actions_enable(imgenv_t* h, const imgenv_actions_cfg* c, i
     h->act_cfg = *c;
     h->act_cfg.table = nullptr;
     h->act_table.swap(table);
-    imgenv_actions_out& o = h->act_out;
-    memset(&o, 0, sizeof(o));
-    o.struct_size = (int32_t)sizeof(imgenv_actions_out);
-    o.n_local = h->RL;
+    imgenv_actions_out o = {};
     o.actions = a.actions; o.speeds = a.speeds; o.n_bad = a.n_bad;
-    h->act_on = true;
-    if (out) *out = o;
-    return IMGENV_OK;
+    return enable_done(h, o, &imgenv::act_out, &imgenv::act_on, out);
 }
 
 extern "C" int imgenv_actions_outputs(imgenv_t* h, imgenv_actions_out* out) {
-    if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->act_on) FAIL(IMGENV_ESTATE, "imgenv_actions_enable was not called");
-    *out = h->act_out;
-    return IMGENV_OK;
+    return feature_outputs(h, &imgenv::act_on, &imgenv::act_out, out, "imgenv_actions_enable");
 }
 
 // k_actions<DTYPE, MODE>: the six instantiations (indices are not clipped)
@@ -3633,10 +3630,8 @@ extern "C" int imgenv_actions_decode(imgenv_t* h, const void* raw, int32_t dtype
 
 // ---- observation post-processing (include/imgenv.h; the kernel is csrc/obs_post.h) ----
 extern "C" int imgenv_obs_post_enable(imgenv_t* h, const imgenv_obs_post_cfg* c, imgenv_obs_post_out* out) {
-    if (!c) FAIL(IMGENV_EINVAL, "null argument");
-    if (c->struct_size != (int32_t)sizeof(imgenv_obs_post_cfg))
-        FAIL(IMGENV_EINVAL, "imgenv_obs_post_cfg.struct_size %d (this library's is %d)", c->struct_size, (int)sizeof(imgenv_obs_post_cfg));
-    if (out && out->struct_size != 0 && out->struct_size != (int32_t)sizeof(imgenv_obs_post_out)) FAIL(IMGENV_EINVAL, "imgenv_obs_post_out.struct_size");
+    // (the cfg first, as above)
+    RTRY(enable_args(c, "imgenv_obs_post_cfg", out, "imgenv_obs_post_out"));
     if (c->flags == 0 || (c->flags & ~(IMGENV_OBS_PED_NORM | IMGENV_OBS_CLOSE))) FAIL(IMGENV_EINVAL, "imgenv_obs_post_cfg.flags %d", c->flags);
     if (c->flags & IMGENV_OBS_PED_NORM)
         for (int k = 0; k < OBS_POST_DIM; k++) {
@@ -3674,25 +3669,16 @@ extern "C" int imgenv_obs_post_enable(imgenv_t* h, const imgenv_obs_post_cfg* c,
         RTRY(dev_alloc(h, &p.close, (size_t)h->RL));
         p.close_dist = c->close_dist;
     }
-    p.RL = h->RL; p.r0 = h->r0; p.Rw = h->Rw;
     h->post = p;
     h->post_cfg = *c;
-    imgenv_obs_post_out& o = h->post_out;
-    memset(&o, 0, sizeof(o));
-    o.struct_size = (int32_t)sizeof(imgenv_obs_post_out);
-    o.n_local = h->RL;
+    imgenv_obs_post_out o = {};
     o.ped_vector_norm = p.norm;
     o.close_to_human = p.close;
-    h->post_on = true;
-    if (out) *out = o;
-    return IMGENV_OK;
+    return enable_done(h, o, &imgenv::post_out, &imgenv::post_on, out);
 }
 
 extern "C" int imgenv_obs_post_outputs(imgenv_t* h, imgenv_obs_post_out* out) {
-    if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->post_on) FAIL(IMGENV_ESTATE, "imgenv_obs_post_enable was not called");
-    *out = h->post_out;
-    return IMGENV_OK;
+    return feature_outputs(h, &imgenv::post_on, &imgenv::post_out, out, "imgenv_obs_post_enable");
 }
 
 extern "C" int imgenv_cv_resize_u8(int kind, const uint8_t* src, int32_t sh, int32_t sw, uint8_t* dst, int32_t dh, int32_t dw) {

@@ -387,7 +387,7 @@ inline ViewPlan plan_views(const PlanHandle& h, const PlanChain& c) {
     return v;
 }
 
-// ---------------------------------------------------------------------------------------- chain tail: k_stack, k_episodes
+// ---------------------------------------------------------------------------------------- chain tail: k_stack, k_episodes, k_obs_post
 // A step covers every local robot; a reset chain the robots of its list's worlds, whose length the host knows (act_nw) or a
 // kernel has counted (n_dev: the grid is sized for a guess and strides).
 inline size_t plan_tail_rows(const PlanHandle& h, const PlanChain& c) {
@@ -397,14 +397,11 @@ inline size_t plan_tail_rows(const PlanHandle& h, const PlanChain& c) {
 inline LaunchShape plan_tail(size_t items, int block, int max_blocks) {
     return {(unsigned)std::min<size_t>((size_t)max_blocks, std::max<size_t>(1, (items + block - 1) / block)), (unsigned)block, 0};
 }
-inline LaunchShape plan_stack_launch(const PlanHandle& h, const PlanChain& c, size_t chunks_per_robot) {
-    return plan_tail(plan_tail_rows(h, c) * chunks_per_robot, STACK_BLOCK, STACK_MAX_BLOCKS);
-}
-inline LaunchShape plan_episodes_launch(const PlanHandle& h, const PlanChain& c) { return plan_tail(plan_tail_rows(h, c), EP_BLOCK, EP_MAX_BLOCKS); }
-// k_obs_post (obs_post.h), behind them: `per_row` lanes per robot of the chain -- the 1 + 7 max_ped elements of its ped_vector row,
-// or one where only close_to_human is kept
-inline LaunchShape plan_obs_post_launch(const PlanHandle& h, const PlanChain& c, size_t per_row) {
-    return plan_tail(plan_tail_rows(h, c) * per_row, OBS_POST_BLOCK, OBS_POST_MAX_BLOCKS);
+// `per_row` lanes per robot of the chain, striding over at most `max_blocks` blocks: k_stack its chunks_per_robot (STACK_BLOCK,
+// STACK_MAX_BLOCKS), k_episodes one (EP_*), k_obs_post the 1 + 7 max_ped elements of a ped_vector row, or one where only
+// close_to_human is kept (OBS_POST_*)
+inline LaunchShape plan_tail_launch(const PlanHandle& h, const PlanChain& c, size_t per_row, int block, int max_blocks) {
+    return plan_tail(plan_tail_rows(h, c) * per_row, block, max_blocks);
 }
 
 // ---------------------------------------------------------------------------------------- in front of the chain: k_actions

@@ -10,7 +10,7 @@
 // One kernel, two instantiations, launched at the end of every chain (launch_views) behind k_stack / k_episodes and in front of
 // the seal, on the caller's stream:
 //   <false> (a step)          every local robot
-//   <true>  (a reset chain)   the robots of the worlds the chain covers (k_stack<true>'s cases)
+//   <true>  (a reset chain)   the robots of the worlds the chain covers (tail_rows.h: k_stack<true>'s cases)
 // One lane per element of a row (1 + 7 max_ped of them; one per robot where only close_to_human is kept): neighbouring lanes read
 // and write neighbouring floats, row[0] is one broadcast read per row.  The lane of element 0 also writes close_to_human.
 // Only - /, conversions and compares, without contraction: IEEE-exact, tests/action_model.py gives the same bits.
@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "launch_plan.h"  // OBS_POST_BLOCK, OBS_POST_MAX_BLOCKS
+#include "tail_rows.h"
 
 #define OBS_POST_DIM 7  // values per pedestrian (imgenv_cfg.ped_vec_dim of every shipped YAML; the wrapper's avg / std have 7)
 
@@ -29,11 +30,7 @@ struct ObsPostDev {
     uint8_t* close;                  // [RL]      (CLOSE)
     double avg[OBS_POST_DIM], std[OBS_POST_DIM], close_dist;
     int32_t flags, PV, max_ped, per_row;  // per_row: PV with PED_NORM, else 1
-    int32_t RL, r0, Rw;              // local robots, first local robot's world-wide index, robots per world
-    // <true>: the worlds of the reset chain (nullptr = every local robot), their count on the host or in device memory
-    const int* list;
-    const int* n_dev;
-    int32_t n_worlds;
+    TailRows rows;                   // the robots of this launch (<true>: those of the reset chain's worlds)
 };
 
 // a[c] for a kernel argument: selects on scalar registers, no indexed copy of the struct
@@ -46,19 +43,12 @@ __device__ __forceinline__ double obs_post_at(const double (&a)[OBS_POST_DIM], i
 
 template <bool RESTART>
 __global__ __launch_bounds__(OBS_POST_BLOCK) void k_obs_post(const ObsPostDev p) {
-    const bool listed = RESTART && p.list != nullptr;
-    const size_t n_rows = listed ? (size_t)(p.n_dev ? *p.n_dev : p.n_worlds) * (size_t)p.Rw : (size_t)p.RL;
-    const size_t per_row = (size_t)p.per_row, total = n_rows * per_row, stride = (size_t)gridDim.x * OBS_POST_BLOCK;
+    const bool listed = RESTART && p.rows.list != nullptr;
+    const size_t per_row = (size_t)p.per_row, total = tail_rows_count(p.rows, listed) * per_row, stride = (size_t)gridDim.x * OBS_POST_BLOCK;
     for (size_t t = (size_t)blockIdx.x * OBS_POST_BLOCK + threadIdx.x; t < total; t += stride) {
         const size_t m = t / per_row;
         const int e = (int)(t - m * per_row);
-        size_t row = m;
-        if (listed) {
-            const size_t q = m / (size_t)p.Rw;
-            const long long g = (long long)p.list[q] * p.Rw + (long long)(m - q * (size_t)p.Rw) - p.r0;
-            if (g < 0 || g >= p.RL) continue;  // (a world of another shard: nothing of it lives here)
-            row = (size_t)g;
-        }
+        const size_t row = tail_rows_row(p.rows, listed, m);
         if (e == 0 && (p.flags & IMGENV_OBS_CLOSE)) p.close[row] = p.ped_min_dists[row] < p.close_dist ? 1 : 0;
         if (!(p.flags & IMGENV_OBS_PED_NORM)) continue;
         const float* src = p.ped_vector_states + row * (size_t)p.PV;

@@ -3,7 +3,7 @@
 //
 // One kernel, two instantiations, launched at the end of every chain (launch_views) on the caller's stream:
 //   push    (a step)          stack = [old[1], ..., old[K-1], F]   for every local robot
-//   restart (a reset chain)   stack = [0, ..., 0, F]               for the robots of the worlds the chain covers
+//   restart (a reset chain)   stack = [0, ..., 0, F]               for the robots of the worlds the chain covers (tail_rows.h)
 // where F is the field's row of imgenv_out (always the kernels' working arena) after that chain.  An auto-reset call runs a step
 // chain and a reset chain, so its finished worlds are pushed and then restarted: the reference's result by composition.
 //
@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "launch_plan.h"  // STACK_BLOCK, STACK_MAX_BLOCKS
+#include "tail_rows.h"
 
 #define STACK_MAX_DEPTH 16   // documented cap (include/imgenv.h: IMGENV_STACK_MAX_DEPTH)
 #define STACK_BATCH 8        // slots a lane keeps in registers at once
@@ -35,11 +36,7 @@ struct StackDev {
     StackField f[3];
     int32_t n_fields;            // fields of depth >= 2
     uint32_t chunks_per_robot;   // sum of f[].chunks
-    int32_t RL, r0, Rw;          // local robots, first local robot's world-wide index, robots per world
-    // restart: the worlds of the reset chain (nullptr = every local robot), their count on the host or in device memory
-    const int* list;
-    const int* n_dev;
-    int32_t n_worlds;
+    TailRows rows;               // the robots of this launch (restart: those of the reset chain's worlds)
 };
 
 // chunk `c` of robot row `row` of one field (the field's members by value: they stay in scalar registers)
@@ -70,20 +67,13 @@ __device__ __forceinline__ void stack_chunk(unsigned char* stack, const unsigned
 
 template <bool RESTART>
 __global__ __launch_bounds__(STACK_BLOCK) void k_stack(const StackDev sd) {
-    // robots of this launch: every local one, or those of the listed worlds (blocks stride over whatever the count turns out to be)
-    const bool listed = RESTART && sd.list != nullptr;
-    const size_t n_rows = listed ? (size_t)(sd.n_dev ? *sd.n_dev : sd.n_worlds) * (size_t)sd.Rw : (size_t)sd.RL;
-    const size_t total = n_rows * sd.chunks_per_robot, stride = (size_t)gridDim.x * STACK_BLOCK;
+    // robots of this launch (tail_rows.h; blocks stride over whatever the count turns out to be)
+    const bool listed = RESTART && sd.rows.list != nullptr;
+    const size_t total = tail_rows_count(sd.rows, listed) * sd.chunks_per_robot, stride = (size_t)gridDim.x * STACK_BLOCK;
     for (size_t t = (size_t)blockIdx.x * STACK_BLOCK + threadIdx.x; t < total; t += stride) {
         const size_t m = t / sd.chunks_per_robot;
         uint32_t c = (uint32_t)(t - m * sd.chunks_per_robot);
-        size_t row = m;
-        if (listed) {
-            const size_t q = m / (size_t)sd.Rw;
-            const long long g = (long long)sd.list[q] * sd.Rw + (long long)(m - q * (size_t)sd.Rw) - sd.r0;
-            if (g < 0 || g >= sd.RL) continue;  // (a world of another shard: nothing of it lives here)
-            row = (size_t)g;
-        }
+        const size_t row = tail_rows_row(sd.rows, listed, m);
         // (member by member: selects on scalar kernel arguments, no indexed copy of the struct)
         unsigned char* stack = sd.f[0].stack;
         const unsigned char* frame = sd.f[0].frame;

@@ -155,6 +155,12 @@ class World:
         if rc != 0:
             raise RuntimeError("%s failed (%d): %s" % (what, rc, self.lib.imgenv_last_error().decode()))
 
+    def _call(self, rc, what, value_codes=(_cabi.EINVAL,)):
+        """the return code of an enable or decode entry point: ValueError for a refused argument, RuntimeError otherwise"""
+        if rc in value_codes:
+            raise ValueError("%s: %s" % (what, self.lib.imgenv_last_error().decode()))
+        self._check(rc, what)
+
     def _stream(self):
         import torch
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -177,11 +183,9 @@ class World:
             torch.cuda.current_stream(self.device).synchronize()  # (the library's kernels may run on any stream)
             s.arena, s.arena_bytes = self.stack_arena.data_ptr(), int(nbytes)
         so = _cabi.StackOut()
-        rc = self.lib.imgenv_stack_enable(self.h, C.byref(s), C.byref(so))
-        if rc == -4:
-            raise RuntimeError("imgenv_stack_enable: %s" % self.lib.imgenv_last_error().decode())
-        if rc != 0:
-            raise ValueError("imgenv_stack_enable: %s" % self.lib.imgenv_last_error().decode())
+        # (only a call out of order is a RuntimeError here)
+        self._call(self.lib.imgenv_stack_enable(self.h, C.byref(s), C.byref(so)), "imgenv_stack_enable",
+                   value_codes=(_cabi.EINVAL, _cabi.ENOMEM, _cabi.EDEVICE))
         R, o = self.n_local, self.out
         H, Wd = o["sensor_maps"].shape[1:]
         shapes = {"sensor_maps": (so.image_depth, torch.float16, (R, so.image_depth, H, Wd)),
@@ -209,23 +213,13 @@ class World:
         library's own memory: int32 / float64 ``[R]``, or ``[rows, R]`` for ``ends`` (``_cabi.EP_ENDS``), ``figure_sums``
         (``_cabi.EP_FIGURE_NAMES``) and ``open_f64`` (``_cabi.EP_OPEN_NAMES``).  Read-only; valid until ``close()``.  ``dt`` is the
         YAML's ``control_hz`` (default: the handle's step time); ValueError for a bad cfg or a second call with another one."""
-        import torch
         c = _cabi.make_episodes_cfg(min_steps, self.cfg.step_hz if dt is None else dt)
         eo = _cabi.EpisodesOut()
-        rc = self.lib.imgenv_episodes_enable(self.h, C.byref(c), C.byref(eo))
-        if rc == _cabi.EINVAL:
-            raise ValueError("imgenv_episodes_enable: %s" % self.lib.imgenv_last_error().decode())
-        self._check(rc, "imgenv_episodes_enable")
+        self._call(self.lib.imgenv_episodes_enable(self.h, C.byref(c), C.byref(eo)), "imgenv_episodes_enable")
         if self.episodes is None:
             R = eo.n_local
-            self.episodes = {}
-            for name, (dt_, rows) in _cabi.EPISODE_ARRAYS.items():
-                arr = _DeviceArray(getattr(eo, name), (rows, R) if rows else (R,), np.dtype(dt_).str)
-                with torch.cuda.device(self.device):
-                    t = torch.as_tensor(arr, device=self.device)
-                if t.data_ptr() != getattr(eo, name) or t.dtype != _torch_dtype(dt_):
-                    raise RuntimeError("imgenv_episodes_out.%s: torch made a copy instead of a view" % name)
-                self.episodes[name] = t
+            self.episodes = self._views(eo, {k: (dt_, (rows, R) if rows else (R,)) for k, (dt_, rows) in _cabi.EPISODE_ARRAYS.items()},
+                                        "imgenv_episodes_out")
         return self.episodes
 
     def clear_episodes(self):
@@ -257,10 +251,7 @@ class World:
             raise ValueError("enable_actions: discrete_actions (a table) or continuous_actions (clip ranges)")
         c, keep = _cabi.make_actions_cfg(table=discrete_actions, clip=continuous_actions, n_cols=act_dim)
         ao = _cabi.ActionsOut()
-        rc = self.lib.imgenv_actions_enable(self.h, C.byref(c), C.byref(ao))
-        if rc == _cabi.EINVAL:
-            raise ValueError("imgenv_actions_enable: %s" % self.lib.imgenv_last_error().decode())
-        self._check(rc, "imgenv_actions_enable")
+        self._call(self.lib.imgenv_actions_enable(self.h, C.byref(c), C.byref(ao)), "imgenv_actions_enable")
         if self.action_outputs is None:
             R = ao.n_local
             self.action_outputs = self._views(ao, {k: (dt, (R, n) if n else (1,)) for k, (dt, n) in _cabi.ACTION_ARRAYS.items()},
@@ -292,10 +283,7 @@ class World:
                                                      "[%d, %d] floats" % (self.n_local, self._act_cols)))
         # (kept until the next decode: the launch reads it in stream order, a tensor made here from host data must outlive it)
         self._raw_actions = raw
-        rc = self.lib.imgenv_actions_decode(self.h, C.c_void_p(raw.data_ptr()), code, self._stream())
-        if rc == _cabi.EINVAL:
-            raise ValueError("imgenv_actions_decode: %s" % self.lib.imgenv_last_error().decode())
-        self._check(rc, "imgenv_actions_decode")
+        self._call(self.lib.imgenv_actions_decode(self.h, C.c_void_p(raw.data_ptr()), code, self._stream()), "imgenv_actions_decode")
         return self.action_outputs["actions"]
 
     def enable_obs_post(self, ped_norm=True, close=None, avg=_cabi.PED_NORM_AVG, std=_cabi.PED_NORM_STD, close_dist=_cabi.CLOSE_DIST):
@@ -307,10 +295,7 @@ class World:
             close = self.n_peds > 0
         c = _cabi.make_obs_post_cfg(ped_norm, close, avg, std, close_dist)
         po = _cabi.ObsPostOut()
-        rc = self.lib.imgenv_obs_post_enable(self.h, C.byref(c), C.byref(po))
-        if rc == _cabi.EINVAL:
-            raise ValueError("imgenv_obs_post_enable: %s" % self.lib.imgenv_last_error().decode())
-        self._check(rc, "imgenv_obs_post_enable")
+        self._call(self.lib.imgenv_obs_post_enable(self.h, C.byref(c), C.byref(po)), "imgenv_obs_post_enable")
         if self.obs_post is None:
             R = po.n_local
             self.obs_post = self._views(po, {"ped_vector_norm": (np.float32, (R, self.out["ped_vector_states"].shape[1])),

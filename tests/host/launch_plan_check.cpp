@@ -218,11 +218,11 @@ static void worlds_300() {  // tests/test_gpu_large_launches.py: 300 worlds x (4
     CHECK_EQ(plan_tail_rows(h, c), 1200);
     CHECK_EQ(plan_tail_rows(h, big), 1000);
     CHECK_EQ(plan_tail_rows(h, all_worlds(h, true)), 1200);
-    CHECK_EQ(plan_episodes_launch(h, big).grid, 4);
-    CHECK_EQ(plan_episodes_launch(h, c).grid, 5);
-    CHECK_EQ(plan_stack_launch(h, c, 100).grid, (1200 * 100 + 255) / 256);
-    CHECK_EQ(plan_stack_launch(h, c, 100).block, STACK_BLOCK);
-    CHECK_EQ(plan_stack_launch(h, c, 10000).grid, STACK_MAX_BLOCKS);
+    CHECK_EQ(plan_tail_launch(h, big, 1, EP_BLOCK, EP_MAX_BLOCKS).grid, 4);
+    CHECK_EQ(plan_tail_launch(h, c, 1, EP_BLOCK, EP_MAX_BLOCKS).grid, 5);
+    CHECK_EQ(plan_tail_launch(h, c, 100, STACK_BLOCK, STACK_MAX_BLOCKS).grid, (1200 * 100 + 255) / 256);
+    CHECK_EQ(plan_tail_launch(h, c, 100, STACK_BLOCK, STACK_MAX_BLOCKS).block, STACK_BLOCK);
+    CHECK_EQ(plan_tail_launch(h, c, 10000, STACK_BLOCK, STACK_MAX_BLOCKS).grid, STACK_MAX_BLOCKS);
     CHECK_EQ(plan_tail(0, EP_BLOCK, EP_MAX_BLOCKS).grid, 1);
     CHECK_EQ(plan_tail((size_t)EP_BLOCK * EP_MAX_BLOCKS + 1, EP_BLOCK, EP_MAX_BLOCKS).grid, EP_MAX_BLOCKS);
     // the upload launch: segment copies | MAP_BLOCKS per world | 256 robots | 256 pedestrians per block

@@ -1,4 +1,4 @@
-"""The launch shapes of k_actions and k_obs_post (img_env_amd/csrc/launch_plan.h: plan_actions_launch, plan_obs_post_launch) on
+"""The launch shapes of k_actions and k_obs_post (img_env_amd/csrc/launch_plan.h: plan_actions_launch, plan_tail_launch) on
 the CPU, beside tests/test_launch_plan.py: tests/host/launch_plan_actions_check.cpp compiles the header the library's launch
 functions call and asserts the shapes at 1, 256 and 257 local robots, at a listed reset chain of 2 worlds x 3 robots, at a
 device-side chain and at the block cap."""

@@ -30,6 +30,9 @@ ANGULAR_BINS = 72
 STACK_MAX_DEPTH = 16  # IMGENV_STACK_MAX_DEPTH
 MAPS_KEEP, MAPS_BY_PLACEMENT = 0, 1  # imgenv_maps_policy
 MAP_POLICIES = {"keep": MAPS_KEEP, "placement": MAPS_BY_PLACEMENT}
+TRACKS_KEEP, TRACKS_BY_PLACEMENT, TRACKS_CYCLE = 0, 1, 2  # imgenv_tracks_policy
+TRACK_POLICIES = {"keep": TRACKS_KEEP, "placement": TRACKS_BY_PLACEMENT, "cycle": TRACKS_CYCLE}
+TRACKS_PLACEMENT_SALT = 0xBB67AE8584CAA73B  # imgenv_tracks_for_placement (csrc/track_bank.h)
 EINVAL, ENOMEM, EDEVICE, ESTATE = -1, -2, -3, -4
 
 SHAPES = {"circle": SHAPE_CIRCLE, "rectangle": SHAPE_RECTANGLE, "leg": SHAPE_LEG}
@@ -383,7 +386,8 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_stack_bytes", "imgenv_stack_enable", "imgenv_stack_outputs",
            "imgenv_episodes_enable", "imgenv_episodes_outputs", "imgenv_episodes_clear",
            "imgenv_actions_enable", "imgenv_actions_outputs", "imgenv_actions_decode", "imgenv_obs_post_enable", "imgenv_obs_post_outputs",
-           "imgenv_maps_add", "imgenv_world_maps_set", "imgenv_maps_policy", "imgenv_map_for_placement", "imgenv_world_maps")
+           "imgenv_maps_add", "imgenv_world_maps_set", "imgenv_maps_policy", "imgenv_map_for_placement", "imgenv_world_maps",
+           "imgenv_tracks_add", "imgenv_world_tracks_set", "imgenv_tracks_policy", "imgenv_tracks_for_placement", "imgenv_world_tracks")
 K_COUNT = 14
 
 
@@ -448,6 +452,12 @@ def bind(lib):
     lib.imgenv_map_for_placement.argtypes = [C.c_uint64, C.c_int32]
     lib.imgenv_map_for_placement.restype = C.c_int32
     lib.imgenv_world_maps.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
+    lib.imgenv_tracks_add.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.imgenv_world_tracks_set.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
+    lib.imgenv_tracks_policy.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.imgenv_tracks_for_placement.argtypes = [C.c_uint64, C.c_int32]
+    lib.imgenv_tracks_for_placement.restype = C.c_int32
+    lib.imgenv_world_tracks.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
     lib.imgenv_kernel_name.argtypes = [C.c_int]
     lib.imgenv_kernel_name.restype = C.c_char_p
     return lib
@@ -456,6 +466,45 @@ def bind(lib):
 def map_for_placement(seed, n_maps):
     """``imgenv_map_for_placement``: the map an episode placed from ``seed`` runs on under the "placement" policy (needs no GPU)"""
     return int(load_library().imgenv_map_for_placement(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(n_maps)))
+
+
+def tracks_for_placement(seed, n_sets):
+    """``imgenv_tracks_for_placement``: the track set an episode placed from ``seed`` replays under the "placement" policy (needs no GPU)"""
+    return int(load_library().imgenv_tracks_for_placement(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(n_sets)))
+
+
+def pack_track_sets(sets, n_peds):
+    """The arrays of ``imgenv_tracks_add`` from a list of sets.  A set is ``[P, T, 5]`` rows (x, y, yaw, vx, vy) per pedestrian and
+    step -- what ``PedTrajectoryDatasetWrapper.change_world()`` hands out, every series its full length -- or a dict / pair
+    ``(series, lengths)`` with ``lengths[P]`` the true length of each right-padded series.  Sets are right-padded to the longest
+    ``T``.  Returns ``(n_sets, cap, ped_pose [n, P, 4], ped_traj [n, P, cap, 3], ped_traj_v [n, P, cap, 2], ped_traj_len [n, P])``;
+    the start pose is the first row, its quaternion ``(sin(yaw / 2), cos(yaw / 2))`` as in ``spawn.init_ped_dataset``."""
+    items = []
+    for one in sets:
+        if isinstance(one, dict):
+            d, ln = one["series"], one.get("lengths")
+        elif isinstance(one, tuple) and len(one) == 2:
+            d, ln = one
+        else:
+            d, ln = one, None
+        d = np.asarray(d, np.float64)
+        if d.ndim != 3 or d.shape[0] != n_peds or d.shape[2] != 5 or d.shape[1] < 1:
+            raise ValueError("a track set is [%d pedestrians, steps, 5]; got %s" % (n_peds, d.shape))
+        ln = np.full(n_peds, d.shape[1], np.int32) if ln is None else np.asarray(ln, np.int32).reshape(n_peds)
+        if (ln < 1).any() or (ln > d.shape[1]).any():
+            raise ValueError("track lengths must lie in [1, %d]" % d.shape[1])
+        items.append((d, ln))
+    if not items:
+        raise ValueError("no track sets")
+    n, cap = len(items), max(d.shape[1] for d, _ in items)
+    pose, traj = np.zeros((n, n_peds, 4)), np.zeros((n, n_peds, cap, 3))
+    traj_v, length = np.zeros((n, n_peds, cap, 2)), np.zeros((n, n_peds), np.int32)
+    for s, (d, ln) in enumerate(items):
+        T = d.shape[1]
+        traj[s, :, :T], traj_v[s, :, :T], length[s] = d[:, :, :3], d[:, :, 3:5], ln
+        pose[s, :, 0], pose[s, :, 1] = d[:, 0, 0], d[:, 0, 1]
+        pose[s, :, 2], pose[s, :, 3] = np.sin(d[:, 0, 2] / 2.0), np.cos(d[:, 0, 2] / 2.0)
+    return n, cap, pose, traj, traj_v, length
 
 
 def load_library():

@@ -95,6 +95,15 @@ struct imgenv {
     int* d_map_next = nullptr;      // [W] map each world's next reset starts from
     int maps_policy = 0;            // IMGENV_MAPS_*
     const int* reset_map_ids = nullptr;  // host-placed resets under BY_PLACEMENT: the maps of the worlds being reset, in list order (for the call in progress)
+    // track bank (include/imgenv.h: imgenv_tracks_add; csrc/track_bank.h)
+    int n_track_sets = 0, trk_cap = 0;   // sets of the bank (0: none); records per pedestrian in it
+    double *d_trk_traj = nullptr, *d_trk_traj_v = nullptr, *d_trk_pose3 = nullptr;
+    int* d_trk_len = nullptr;
+    int *d_trk_cur = nullptr, *d_trk_next = nullptr;  // [W] (nullptr: no bank)
+    uint32_t* d_trk_count = nullptr;                  // [W]
+    int tracks_policy = 0, tracks_repeat = 1;         // IMGENV_TRACKS_*
+    const int* reset_track_ids = nullptr;  // host-placed resets under BY_PLACEMENT: the sets of the worlds being reset, in list order (for the call in progress)
+    std::vector<int> trk_fed, trk_fed_ids;  // the worlds of the reset being staged whose batch brought no tracks, and the host's draw for each (-1: the device resolves)
     struct ObstInstHost { double x, y, sh, ch, cx, cy, r; int m0, m1, n0, n1, shape, world; };
     std::vector<ObstInstHost> oinst;  // obstacles of the reset being staged
     void* d_oinst = nullptr;
@@ -2027,6 +2036,7 @@ __global__ __launch_bounds__(256) void k_reset_obstacles(DevWorld w, const ObstI
 }
 
 #include "spawn_device.h"  // device-side auto-reset: k_spawn_fill, k_finished_dev, k_respawn, k_restore_maps_dev
+#include "track_bank.h"    // recorded crowds: k_tracks_install
 
 static auto k_reset_obstacles_for(const PlanHandle& p) { return p.pow2 ? k_reset_obstacles<true> : k_reset_obstacles<false>; }
 static auto k_restore_maps_dev_for(const PlanHandle& p) { return p.pow2 ? k_restore_maps_dev<true> : k_restore_maps_dev<false>; }
@@ -2139,8 +2149,17 @@ static int stage_world(imgenv* h, int k, int q_list, const imgenv_reset_batch* b
     // pedestrians (img_env.cpp:220-250)
     if (Pw > 0) {
         const bool dataset = h->cfg.ped_scene_type == IMGENV_SCENE_DATASET;
-        if (dataset && !b->ped_traj_v) FAIL(IMGENV_EINVAL, "dataset scene: ped_traj_v is missing from the reset batch");
-        if (b->ped_traj_cap > h->traj_cap) {  // longer trajectories than any before: re-lay the table out (other worlds keep theirs)
+        const bool fed = dataset && h->d_trk_cur && !b->ped_traj_v;  // bank-fed: k_tracks_install brings this world's pedestrians
+        if (dataset && !b->ped_traj_v && !fed) FAIL(IMGENV_EINVAL, "dataset scene: ped_traj_v is missing from the reset batch");
+        if (fed) {  // (the batch's own pedestrian arrays are ignored; reset_ped's pass over the world writes zeros that the install replaces)
+            h->trk_fed.push_back(k);
+            h->trk_fed_ids.push_back(h->reset_track_ids ? h->reset_track_ids[q_list] : -1);
+            memset(h->pin_ped3 + (size_t)q_list * Pw * 3, 0, sizeof(double) * 3 * (size_t)Pw);
+        } else if (dataset && h->d_trk_cur) {  // its own tracks: imgenv_world_tracks says -1, the CYCLE count stays
+            static const int minus_one = -1;
+            RTRY(stage_put(h, h->d_trk_cur + k, &minus_one, sizeof(int)));
+        }
+        if (!fed && b->ped_traj_cap > h->traj_cap) {  // longer trajectories than any before: re-lay the table out (other worlds keep theirs)
             RTRY(stage_flush(h, st));  // (queued copies aim at the old table)
             const int old_cap = h->traj_cap;
             double *old_t = h->d_traj, *old_v = h->d_traj_v;
@@ -2158,8 +2177,8 @@ static int stage_world(imgenv* h, int k, int q_list, const imgenv_reset_batch* b
         std::vector<int>& tlen = h->tmp_i0;
         std::vector<double>& traj = h->tmp_d1;
         tlen.resize(Pw);
-        traj.assign((size_t)Pw * h->traj_cap * 3, 0.0);
-        for (int j = 0; j < Pw; j++) {
+        traj.assign(fed ? 0 : (size_t)Pw * h->traj_cap * 3, 0.0);
+        for (int j = 0; j < Pw && !fed; j++) {
             const double* p = b->ped_pose + 4 * j;
             ped3[3 * j] = p[0];
             ped3[3 * j + 1] = p[1];
@@ -2169,9 +2188,13 @@ static int stage_world(imgenv* h, int k, int q_list, const imgenv_reset_batch* b
             for (int q = 0; q < tlen[j]; q++)
                 memcpy(&traj[((size_t)j * h->traj_cap + q) * 3], b->ped_traj + ((size_t)j * b->ped_traj_cap + q) * 3, 24);
         }
-        RTRY(stage_put(h, h->d_traj + (size_t)p_lo * h->traj_cap * 3, traj.data(), traj.size() * 8));
-        RTRY(stage_put(h, h->d_traj_len + p_lo, tlen.data(), sizeof(int) * Pw));
-        if (dataset) {  // trajectory_v (img_env.cpp:246-247) + the yaw _step_ped_dataset derives from it, with the host's libm
+        if (!fed) {
+            RTRY(stage_put(h, h->d_traj + (size_t)p_lo * h->traj_cap * 3, traj.data(), traj.size() * 8));
+            RTRY(stage_put(h, h->d_traj_len + p_lo, tlen.data(), sizeof(int) * Pw));
+        }
+        if (fed) {
+            d.ptraj_v = h->d_traj_v;
+        } else if (dataset) {  // trajectory_v (img_env.cpp:246-247) + the yaw _step_ped_dataset derives from it, with the host's libm
             std::vector<double>& tv = h->tmp_d1;
             tv.assign((size_t)Pw * h->traj_cap * 3, 0.0);
             for (int j = 0; j < Pw; j++)
@@ -2247,13 +2270,16 @@ static int reset_checks(imgenv* h, int n, const imgenv_reset_batch* b, int peds_
     if (!h || !b) FAIL(IMGENV_EINVAL, "null argument");
     for (int q = 0; q < n; q++) {
         if (b[q].struct_size != (int32_t)sizeof(imgenv_reset_batch)) FAIL(IMGENV_EINVAL, "reset batch ABI mismatch");
-        if (b[q].n_obstacles < 0 || (h->P > 0 && b[q].ped_traj_cap < 1)) FAIL(IMGENV_EINVAL, "bad reset batch");
+        // (bank-fed: a dataset handle with a track bank takes the pedestrians of a batch without ped_traj_v from the bank, and the
+        // batch's own pedestrian arrays are ignored)
+        const bool fed = h->d_trk_cur && h->cfg.ped_scene_type == IMGENV_SCENE_DATASET && !b[q].ped_traj_v;
+        if (b[q].n_obstacles < 0 || (h->P > 0 && !fed && b[q].ped_traj_cap < 1)) FAIL(IMGENV_EINVAL, "bad reset batch");
         if (b[q].n_obstacles > 0 && (!b[q].obs_shape || !b[q].obs_size || !b[q].obs_pose)) FAIL(IMGENV_EINVAL, "reset batch %d: null obstacle arrays", q);
         if (!b[q].robot_pose || !b[q].robot_goal) FAIL(IMGENV_EINVAL, "reset batch %d: null robot arrays", q);
         for (int o = 0; o < b[q].n_obstacles; o++)
             if (b[q].obs_shape[o] != IMGENV_SHAPE_CIRCLE && b[q].obs_shape[o] != IMGENV_SHAPE_RECTANGLE)
                 FAIL(IMGENV_EINVAL, "reset batch %d, obstacle %d: unsupported shape %d", q, o, b[q].obs_shape[o]);
-        if (peds_per_batch > 0) {
+        if (peds_per_batch > 0 && !fed) {
             if (!b[q].ped_pose || !b[q].ped_traj_len || !b[q].ped_traj) FAIL(IMGENV_EINVAL, "reset batch %d: null pedestrian arrays", q);
             if (h->cfg.ped_scene_type == IMGENV_SCENE_DATASET && !b[q].ped_traj_v)
                 FAIL(IMGENV_EINVAL, "dataset scene: ped_traj_v is missing from the reset batch");
@@ -2289,6 +2315,8 @@ static int reset_blocks(imgenv* h, int n, const int* list) {
     RTRY(stage_room(h, sizeof(double) * 3 * std::max<size_t>((size_t)n * h->Pw, 1), &p));
     h->pin_ped3 = (double*)p;
     h->pin_list = nullptr;
+    h->trk_fed.clear();
+    h->trk_fed_ids.clear();
     if (list) {
         RTRY(stage_room(h, sizeof(int) * n, &p));
         h->pin_list = (int*)p;
@@ -2303,6 +2331,15 @@ static MapSel map_sel(const imgenv* h) {
     m.stride = h->map_stride; m.n_maps = h->n_maps;
     m.by_placement = h->maps_policy == IMGENV_MAPS_BY_PLACEMENT && h->n_maps > 1 ? 1 : 0;
     return m;
+}
+
+static TrackSel track_sel(const imgenv* h) {
+    TrackSel t;
+    t.traj = h->d_trk_traj; t.traj_v = h->d_trk_traj_v; t.pose3 = h->d_trk_pose3; t.len = h->d_trk_len;
+    t.cur = h->d_trk_cur; t.next = h->d_trk_next; t.count = h->d_trk_count;
+    t.n_sets = h->n_track_sets; t.cap = h->trk_cap;
+    t.policy = h->tracks_policy; t.repeat = h->tracks_repeat;
+    return t;
 }
 
 static int sfm_ahead_drop(imgenv* h, hipStream_t st);
@@ -2375,8 +2412,21 @@ static int reset_launch(imgenv* h, const int* list, int n, hipStream_t st, int w
     if (n_inst)
         k_reset_obstacles_for(h->plan)<<<dim3(rp.obstacles.grid), dim3(rp.obstacles.block), 0, st>>>(d, (const ObstInst*)h->d_oinst, h->plan.layer, nullptr, 0, 1, nullptr, nullptr);
     if (d.sharded) k_reset_bbox<<<dim3(rp.bbox.grid), dim3(rp.bbox.block), 0, st>>>(d, h->pin_rob3);
+    const int n_fed = (int)h->trk_fed.size();
+    if (n_fed > 0) {  // the worlds whose batch brought no tracks take their set of the bank: behind the staged copies, in front of the rasters
+        unsigned char* pl = nullptr;
+        RTRY(stage_room(h, sizeof(int) * 2 * (size_t)n_fed, &pl));
+        int* fed_list = (int*)pl;
+        memcpy(fed_list, h->trk_fed.data(), sizeof(int) * (size_t)n_fed);
+        memcpy(fed_list + n_fed, h->trk_fed_ids.data(), sizeof(int) * (size_t)n_fed);
+        const TracksPlan tp = plan_tracks_install(h->plan, n_fed, false, 0, h->trk_cap);
+        k_tracks_install<<<dim3(tp.install.grid), dim3(tp.install.block), 0, st>>>(d, track_sel(h), fed_list, nullptr, n_fed, fed_list + n_fed, nullptr, nullptr,
+                                                                                 0ull, h->d_traj, h->d_traj_v, h->d_traj_len, h->traj_cap);
+        h->trk_fed.clear();
+        h->trk_fed_ids.clear();
+    }
     HIPCHK(hipGetLastError());
-    h->launches = 2;
+    h->launches = 2 + (n_fed > 0 ? 1 : 0);
     const int rc = launch_views(h, st, 1);
     set_active(h, nullptr, 0);
     // k_reset_apply is in flight and reads this generation's page-locked chunks: mark them pending whatever came after
@@ -2396,10 +2446,10 @@ extern "C" int imgenv_reset(imgenv_t* h, const imgenv_reset_batch* b, void* stre
         sub.robot_pose = b->robot_pose + (size_t)4 * k * h->Rw;
         sub.robot_goal = b->robot_goal + (size_t)2 * k * h->Rw;
         if (h->P > 0) {
-            sub.ped_pose = b->ped_pose + (size_t)4 * k * h->Pw;
+            sub.ped_pose = b->ped_pose ? b->ped_pose + (size_t)4 * k * h->Pw : nullptr;  // (null: a bank-fed batch, reset_checks)
             sub.ped_goal = b->ped_goal ? b->ped_goal + (size_t)2 * k * h->Pw : nullptr;
-            sub.ped_traj_len = b->ped_traj_len + (size_t)k * h->Pw;
-            sub.ped_traj = b->ped_traj + (size_t)k * h->Pw * b->ped_traj_cap * 3;
+            sub.ped_traj_len = b->ped_traj_len ? b->ped_traj_len + (size_t)k * h->Pw : nullptr;
+            sub.ped_traj = b->ped_traj ? b->ped_traj + (size_t)k * h->Pw * b->ped_traj_cap * 3 : nullptr;
             sub.ped_traj_v = b->ped_traj_v ? b->ped_traj_v + (size_t)k * h->Pw * b->ped_traj_cap * 2 : nullptr;
         }
         RTRY(stage_world(h, k, k, &sub, st));
@@ -2520,8 +2570,14 @@ extern "C" int imgenv_reset_worlds_spawn(imgenv_t* h, int32_t n, const int32_t* 
         for (int q = 0; q < n; q++) ids.push_back(map_for_placement(seeds[q], h->n_maps));
         h->reset_map_ids = ids.data();
     }
+    std::vector<int> sets;
+    if (h->d_trk_cur && h->tracks_policy == IMGENV_TRACKS_BY_PLACEMENT) {  // ... and the recorded crowd
+        for (int q = 0; q < n; q++) sets.push_back(tracks_for_placement(seeds[q], h->n_track_sets));
+        h->reset_track_ids = sets.data();
+    }
     const int rc = imgenv_reset_worlds(h, n, worlds, batches.data(), stream);
     h->reset_map_ids = nullptr;
+    h->reset_track_ids = nullptr;
     return rc;
 }
 
@@ -2661,6 +2717,134 @@ extern "C" int imgenv_world_maps(imgenv_t* h, int32_t* map_ids, void* stream) {
         return IMGENV_OK;
     }
     HIPCHK(hipMemcpy(map_ids, h->d_map_cur, sizeof(int) * (size_t)h->W, hipMemcpyDeviceToHost));
+    return IMGENV_OK;
+}
+
+// ---------------------------------------------------------------------------------------- track bank
+extern "C" int32_t imgenv_tracks_for_placement(uint64_t seed, int32_t n_sets) { return tracks_for_placement(seed, n_sets); }
+
+// room on the device that fails softly (imgenv_tracks_add undoes what it has got)
+template <typename T>
+static bool tracks_room(imgenv* h, T** out, size_t n, int fill) {
+    void* p = nullptr;
+    const size_t bytes = sizeof(T) * (n ? n : 1);
+    if (hipMalloc(&p, bytes) != hipSuccess) return false;
+    h->allocs.push_back(p);
+    *out = (T*)p;
+    return hipMemset(p, fill, bytes) == hipSuccess;
+}
+
+extern "C" int imgenv_tracks_add(imgenv_t* h, int32_t n_sets, int32_t cap, const double* ped_pose, const double* ped_traj,
+                                 const double* ped_traj_v, const int32_t* ped_traj_len) {
+    if (!h || !ped_pose || !ped_traj || !ped_traj_v || !ped_traj_len) FAIL(IMGENV_EINVAL, "null argument");
+    if (h->n_track_sets > 0) FAIL(IMGENV_ESTATE, "imgenv_tracks_add has already been called on this handle");
+    bool any_reset = h->has_reset;
+    for (char r : h->world_ready) any_reset = any_reset || r;
+    if (any_reset) FAIL(IMGENV_ESTATE, "imgenv_tracks_add after the first reset");
+    if (h->cfg.ped_scene_type != IMGENV_SCENE_DATASET) FAIL(IMGENV_EINVAL, "imgenv_tracks_add: the pedestrian scene is not IMGENV_SCENE_DATASET");
+    if (h->Pw < 1) FAIL(IMGENV_EINVAL, "imgenv_tracks_add: the handle has no pedestrians");
+    if (h->RL != h->R) FAIL(IMGENV_EINVAL, "imgenv_tracks_add on a robot shard is not supported");
+    if (n_sets < 1 || n_sets > (1 << 20) || cap < 1 || cap > (1 << 24)) FAIL(IMGENV_EINVAL, "imgenv_tracks_add: %d sets of %d records", n_sets, cap);
+    const int Pw = h->Pw, stride = std::max(cap, 2);
+    const size_t words = (size_t)Pw * stride * 3;
+    // every set as a reset would stage it (track_bank.h), on the host first: a bad set fails the call before anything is allocated
+    std::vector<double> pose3((size_t)n_sets * Pw * 3), traj((size_t)n_sets * words), traj_v((size_t)n_sets * words);
+    std::vector<int32_t> len((size_t)n_sets * Pw);
+    for (int s = 0; s < n_sets; s++) {
+        const int bad = tracks_convert_set(Pw, cap, stride, ped_pose + (size_t)s * Pw * 4, ped_traj + (size_t)s * Pw * cap * 3,
+                                           ped_traj_v + (size_t)s * Pw * cap * 2, ped_traj_len + (size_t)s * Pw, pose3.data() + (size_t)s * Pw * 3,
+                                           traj.data() + (size_t)s * words, traj_v.data() + (size_t)s * words, len.data() + (size_t)s * Pw);
+        if (bad > 0) FAIL(IMGENV_EINVAL, "imgenv_tracks_add: set %d, pedestrian %d: bad trajectory length %d (cap %d)", s, bad - 1, ped_traj_len[(size_t)s * Pw + bad - 1], cap);
+        if (bad < 0) FAIL(IMGENV_EINVAL, "imgenv_tracks_add: set %d, pedestrian %d: a value that is not finite", s, -bad - 1);
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    // everything is allocated and filled before the handle changes: a failure leaves it without a bank
+    double *b_traj = nullptr, *b_traj_v = nullptr, *b_pose3 = nullptr, *t_traj = nullptr, *t_traj_v = nullptr;
+    int *b_len = nullptr, *cur = nullptr, *next = nullptr;
+    uint32_t* count = nullptr;
+    auto undo = [&]() {
+        dev_free(h, b_traj); dev_free(h, b_traj_v); dev_free(h, b_pose3); dev_free(h, t_traj); dev_free(h, t_traj_v);
+        dev_free(h, b_len); dev_free(h, cur); dev_free(h, next); dev_free(h, count);
+    };
+    auto room = [&](auto** out, size_t n, int fill) -> bool { return tracks_room(h, out, n, fill); };
+    const size_t P = (size_t)h->P, W = (size_t)h->W;
+    const bool ok = room(&b_traj, traj.size(), 0) && room(&b_traj_v, traj_v.size(), 0) && room(&b_pose3, pose3.size(), 0) && room(&b_len, len.size(), 0) &&
+                    room(&cur, W, 0xFF) && room(&next, W, 0) && room(&count, W, 0) &&
+                    (h->traj_cap >= stride || (room(&t_traj, P * stride * 3, 0) && room(&t_traj_v, P * stride * 3, 0))) &&
+                    hipMemcpy(b_traj, traj.data(), 8 * traj.size(), hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(b_traj_v, traj_v.data(), 8 * traj_v.size(), hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(b_pose3, pose3.data(), 8 * pose3.size(), hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(b_len, len.data(), 4 * len.size(), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        undo();
+        FAIL(IMGENV_ENOMEM, "no device memory for a bank of %d track sets", n_sets);
+    }
+    if (t_traj) {  // the per-world tables with room for a set, so that the first reset finds them (no reset has happened: nothing reads the old ones)
+        dev_free(h, h->d_traj);
+        dev_free(h, h->d_traj_v);
+        h->d_traj = t_traj;
+        h->d_traj_v = t_traj_v;
+        h->traj_cap = stride;
+    }
+    h->d.ptraj = h->d_traj;
+    h->d.ptraj_v = h->d_traj_v;
+    h->d.traj_cap = h->traj_cap;
+    h->d_trk_traj = b_traj; h->d_trk_traj_v = b_traj_v; h->d_trk_pose3 = b_pose3; h->d_trk_len = b_len;
+    h->d_trk_cur = cur; h->d_trk_next = next; h->d_trk_count = count;
+    h->n_track_sets = n_sets;
+    h->trk_cap = stride;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_world_tracks_set(imgenv_t* h, int32_t n, const int32_t* worlds, const int32_t* set_ids, void* stream) {
+    if (!h || n < 0 || (n > 0 && (!worlds || !set_ids))) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->d_trk_next) FAIL(IMGENV_ESTATE, "imgenv_world_tracks_set: the handle has no track bank (imgenv_tracks_add)");
+    std::vector<char> seen(h->W, 0);
+    for (int q = 0; q < n; q++) {  // everything is checked before anything is applied
+        if (worlds[q] < 0 || worlds[q] >= h->W) FAIL(IMGENV_EINVAL, "world %d out of range (n_worlds %d)", worlds[q], h->W);
+        if (seen[worlds[q]]) FAIL(IMGENV_EINVAL, "world %d listed twice", worlds[q]);
+        seen[worlds[q]] = 1;
+        if (set_ids[q] < 0 || set_ids[q] >= h->n_track_sets) FAIL(IMGENV_EINVAL, "track set %d out of range (the handle holds %d)", set_ids[q], h->n_track_sets);
+    }
+    if (n == 0) return IMGENV_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    RTRY(stage_begin(h));
+    unsigned char* p = nullptr;
+    RTRY(stage_room(h, sizeof(int) * 2 * (size_t)n, &p));
+    int* pin = (int*)p;
+    memcpy(pin, worlds, sizeof(int) * (size_t)n);
+    memcpy(pin + n, set_ids, sizeof(int) * (size_t)n);
+    k_tracks_select<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(h->d_trk_next, pin, pin + n, n);
+    HIPCHK(hipGetLastError());
+    return stage_end(h, st);
+}
+
+extern "C" int imgenv_tracks_policy(imgenv_t* h, int32_t policy, int32_t repeat) {
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (policy != IMGENV_TRACKS_KEEP && policy != IMGENV_TRACKS_BY_PLACEMENT && policy != IMGENV_TRACKS_CYCLE) FAIL(IMGENV_EINVAL, "unknown track policy %d", policy);
+    if (repeat < 1) FAIL(IMGENV_EINVAL, "imgenv_tracks_policy: repeat %d (at least 1)", repeat);
+    if (!h->d_trk_count) FAIL(IMGENV_ESTATE, "imgenv_tracks_policy: the handle has no track bank (imgenv_tracks_add)");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipDeviceSynchronize());  // (resets in flight still count with the old policy)
+    HIPCHK(hipMemset(h->d_trk_count, 0, sizeof(uint32_t) * (size_t)h->W));
+    HIPCHK(hipDeviceSynchronize());
+    h->tracks_policy = policy;
+    h->tracks_repeat = repeat;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_world_tracks(imgenv_t* h, int32_t* set_ids, void* stream) {
+    if (!h || !set_ids) FAIL(IMGENV_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    if (int rc = check_device_flags(h)) return rc;
+    if (!h->d_trk_cur) {
+        for (int k = 0; k < h->W; k++) set_ids[k] = -1;
+        return IMGENV_OK;
+    }
+    HIPCHK(hipMemcpy(set_ids, h->d_trk_cur, sizeof(int) * (size_t)h->W, hipMemcpyDeviceToHost));
     return IMGENV_OK;
 }
 
@@ -2970,8 +3154,14 @@ extern "C" int imgenv_step_autoreset(imgenv_t* h, const float* actions, const im
             for (int q = 0; q < n; q++) ids.push_back(map_for_placement(seed0 + (uint64_t)q, h->n_maps));
             h->reset_map_ids = ids.data();
         }
+        std::vector<int> sets;
+        if (h->d_trk_cur && h->tracks_policy == IMGENV_TRACKS_BY_PLACEMENT) {  // ... and the recorded crowd
+            for (int q = 0; q < n; q++) sets.push_back(tracks_for_placement(seed0 + (uint64_t)q, h->n_track_sets));
+            h->reset_track_ids = sets.data();
+        }
         rc = imgenv_reset_worlds(h, n, worlds.data(), batches.data(), stream);
         h->reset_map_ids = nullptr;
+        h->reset_track_ids = nullptr;
         if (rc == IMGENV_OK) {
             *n_out = n;
             for (int q = 0; q < n && worlds_out && q < cap; q++) worlds_out[q] = worlds[q];
@@ -2999,7 +3189,7 @@ static int spawn_device_setup(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t s
     const int na = cfg->n_robots + cfg->n_peds, nob = cfg->n_obstacles;
     if (na > SPAWN_MAX_AGENTS || nob > SPAWN_MAX_OBST)
         FAIL(IMGENV_EINVAL, "device-side auto-reset places at most %d agents and %d obstacles per world", SPAWN_MAX_AGENTS, SPAWN_MAX_OBST);
-    if (h->cfg.ped_scene_type == IMGENV_SCENE_DATASET)
+    if (h->cfg.ped_scene_type == IMGENV_SCENE_DATASET && !h->d_trk_cur)  // (with a track bank the chain's k_tracks_install brings them)
         FAIL(IMGENV_EINVAL, "device-side auto-reset: dataset scenes (recorded crowds come with the reset call) are reset by the host (imgenv_step_autoreset)");
     const bool sfm = h->cfg.ped_scene_type == IMGENV_SCENE_PEDSIM && h->d.sfm.n > 0;
     if (sfm && (h->W < 2 || !h->d.sfm.n_obs_w))
@@ -3200,6 +3390,12 @@ static int autoreset_device_chain(imgenv* h, const float* actions, hipStream_t s
     h->fill_pending = false;
     const MapSel maps = map_sel(h);
     k_respawn<<<dim3(W), dim3(WAVE), 0, st>>>(d, c, h->elapsed, maps);
+    if (h->d_trk_cur) {  // recorded crowds: every placed world takes its set of the bank (over the sampler's pedestrians, as init_ped_dataset does)
+        const TracksPlan tp = plan_tracks_install(h->plan, 0, true, h->finished_host[0], h->trk_cap);
+        k_tracks_install<<<dim3(tp.install.grid), dim3(tp.install.block), 0, st>>>(d, track_sel(h), c.fin_list, c.fin_n, 0, nullptr, c.place_serial, c.consumed,
+                                                                                 (unsigned long long)c.seed0, h->d_traj, h->d_traj_v, h->d_traj_len, h->traj_cap);
+        h->launches += 1;
+    }
     // grids for a guess of the finished worlds (plan_dev_reset; the count is page-locked, written by k_finished_dev: stale by a step or two)
     const PlanHandle& p = h->plan;
     const DevResetPlan rp = plan_dev_reset(p, h->finished_host[0], nob);

@@ -34,6 +34,7 @@
 #define ACT_BLOCK 256       // k_actions: one lane per local robot
 #define OBS_POST_BLOCK 256  // k_obs_post: one lane per element of a robot's ped_vector row
 #define OBS_POST_MAX_BLOCKS 2048
+#define TRACKS_BLOCK 256    // k_tracks_install: one workgroup per world of the chain
 #define ORCA_NEAR_CAP 64  // robot agents a pedestrian can have within its 0.5 m neighbour range before k_orca falls back to the full scan
 #define ORCA_MAX_ON 118   // obstacle neighbours kept per agent
 #define ORCA_MAX_AN 10    // rvoscene.h:57,63 maxNeighbors
@@ -436,6 +437,24 @@ inline DevResetPlan plan_dev_reset(const PlanHandle& h, int last_n, int n_obstac
     r.restore = {(unsigned)(r.guess * r.restore_blocks), 256, 0};
     r.obstacles = {(unsigned)(r.guess * n_obstacles * r.parts), 256, 0};
     return r;
+}
+// k_tracks_install (track_bank.h): a workgroup per world that takes its recorded crowd from the bank.  A host chain knows its
+// worlds (n_worlds of them; none: nothing to launch, grid 0); the device chain sizes the grid for plan_dev_reset's guess and the
+// workgroups stride over the count the device holds.  A world's copy is `words` 8-byte words for each of the two tables
+// (Pw * cap * 3: an odd product leaves every other world's rows 8-byte aligned only, so the unit of the copy is never wider)
+// in `rounds` rounds of the workgroup's lanes.
+struct TracksPlan {
+    LaunchShape install;
+    size_t words = 0;
+    int rounds = 0;
+};
+inline TracksPlan plan_tracks_install(const PlanHandle& h, int n_worlds, bool n_dev, int last_n, int cap) {
+    TracksPlan t;
+    const int grid = n_dev ? plan_dev_reset(h, last_n, 0).guess : std::max(n_worlds, 0);
+    t.install = {(unsigned)grid, TRACKS_BLOCK, 0};
+    t.words = (size_t)h.Pw * (size_t)std::max(cap, 0) * 3;
+    t.rounds = (int)((t.words + TRACKS_BLOCK - 1) / TRACKS_BLOCK);
+    return t;
 }
 // ... and the variants of the chain behind chosen by the robots it is expected to cover (twice the last count: with four times,
 // 64 worlds of 4 pedestrians sat ON the 1024 threshold and flipped between the kernel variants)

@@ -735,6 +735,38 @@ class PedTrajectoryDatasetWrapper(Wrapper):
             self.cur_repeated_time_per_env = 0
 
 
+def dataset_track_sets(cfg):
+    """The recorded crowds of a dataset YAML as the sets of a track bank (``World.tracks_add``, ``VecImageEnv(ped_tracks="yaml")``):
+    for every entry of ``cfg["ped_dataset_worlds"]`` the series ``PedTrajectoryDatasetWrapper.change_world()`` would hand out for
+    that world, in order.  Every set has the pedestrian count of the FIRST world, as the reference fixes ``ped_sim.total`` from
+    world 0 (PedTrajectoryDatasetWrapper.py:15-60); a world that yields fewer (the ``max_time`` cut dropped somebody) is a
+    ValueError where the reference raises IndexError.  Returns a list of ``(series, lengths)``: ``series`` float64
+    ``[P, cap, 5]`` (x, y, theta, vx, vy) right-padded with zeros to the longest world, ``lengths`` int32 ``[P]`` the world's true
+    number of steps.  ``cfg`` is not modified and no file is written."""
+    w = PedTrajectoryDatasetWrapper.__new__(PedTrajectoryDatasetWrapper)  # the reader alone: no env, no output file
+    w.cfg = cfg
+    w.dt = cfg.get("control_hz", 0.4)
+    if cfg.get("ped_traj_dataset") is None:
+        raise ValueError("dataset_track_sets needs cfg['ped_traj_dataset']")
+    w._read_dataset(cfg["ped_traj_dataset"])
+    worlds = cfg.get("ped_dataset_worlds", [[0, 10]])
+    total = worlds[0][1] - worlds[0][0] + 1
+    series = []
+    for k, (lo, _) in enumerate(worlds):
+        try:
+            one = w._generate_humans(lo, total)
+        except IndexError:
+            raise ValueError("ped_dataset_worlds[%d] yields fewer than the %d pedestrians of the first world" % (k, total)) from None
+        series.append(np.array(one, dtype=np.float64))
+    cap = max(s.shape[1] for s in series)
+    out = []
+    for s in series:
+        padded = np.zeros((total, cap, 5))
+        padded[:, :s.shape[1]] = s
+        out.append((padded, np.full(total, s.shape[1], np.int32)))
+    return out
+
+
 wrapper_dict = {
     "StatePedVectorWrapper": StatePedVectorWrapper,
     "VelActionWrapper": VelActionWrapper,

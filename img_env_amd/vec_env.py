@@ -38,11 +38,28 @@ class VecImageEnv:
     """
 
     def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False,
-                 map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3, wrappers=False):
+                 map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3, wrappers=False,
+                 ped_tracks=None, tracks_policy="keep", tracks_repeat=1, info_track_sets=False):
         import torch
         from .world import World
         self.cfg = cfg
         self.env_num = int(env_num if env_num is not None else cfg.get("env_num", 1))
+        # ped_tracks: the recorded crowds of ``ped_sim.type: dataset`` as a bank inside the handle (imgenv_tracks_add) -- a list of
+        # sets ([P, T, 5] rows x, y, yaw, vx, vy, or (series, lengths) pairs) or "yaml" for envs.dataset_track_sets(cfg), which also
+        # fixes ped_sim.total from the first world as the reference's wrapper does.  Every reset mode then works for a dataset YAML
+        # (Python spawn, native_spawn, device_reset): a reset takes the env's pedestrians from the bank.  tracks_policy: "keep"
+        # (set_world_tracks chooses), "placement" (drawn with the placement's seed; native_spawn / device_reset) or "cycle" (the
+        # reference wrapper's order, tracks_repeat = repeated_time_per_env).  None: a dataset VecImageEnv behaves as before.
+        if ped_tracks is not None and cfg["ped_sim"].get("type") != "dataset":
+            raise ValueError("ped_tracks needs ped_sim.type: dataset")
+        if tracks_policy not in _cabi.TRACK_POLICIES:
+            raise ValueError("tracks_policy: keep | placement | cycle")
+        if isinstance(ped_tracks, str):
+            if ped_tracks != "yaml":
+                raise ValueError('ped_tracks: a list of sets or "yaml"')
+            from .envs import dataset_track_sets
+            ped_tracks = dataset_track_sets(cfg)
+            cfg["ped_sim"]["total"] = int(ped_tracks[0][0].shape[0])
         self.params = config.params_from_cfg(cfg)
         self.grid = config.load_map(cfg)
         self.robot_total = self.params["n_robots"]  # per env, as in the reference
@@ -89,6 +106,16 @@ class VecImageEnv:
         if self.n_maps > 1 or any(int(m) != 0 for m in world_maps):
             self.world.set_world_maps(range(self.env_num), world_maps)
         self.world.set_maps_policy(map_policy)
+        self.tracks_policy = tracks_policy
+        self.info_track_sets = bool(info_track_sets)  # info["track_sets"]: world_tracks() with every step -- it synchronises
+        if ped_tracks is not None:
+            if tracks_policy == "placement" and not self.native_spawn:
+                raise ValueError('tracks_policy="placement" needs native_spawn=True or device_reset=True')
+            self.world.tracks_add(ped_tracks)
+            self.world.tracks_policy(tracks_policy, tracks_repeat)
+        elif tracks_policy != "keep" or self.info_track_sets:
+            raise ValueError("tracks_policy / info_track_sets need ped_tracks")
+        self.n_track_sets = self.world.n_track_sets
         # stack: StateBatchWrapper (base.py:97-150) inside the library, per env (imgenv_stack_enable): every state handed out
         # carries each robot's last cfg["image_batch"] sensor maps, cfg["state_batch"] vector states and
         # max(cfg["laser_batch"], 1) laser scans of its env's current episode, zero-padded after the env's reset -- whoever reset it,
@@ -208,6 +235,8 @@ class VecImageEnv:
             info["speeds"] = self.world.action_outputs["speeds"]
             if self._close:
                 info["bool_get_close_to_human"] = self.world.obs_post["close_to_human"]
+        if self.info_track_sets:
+            info["track_sets"] = self.world.world_tracks()
         return info
 
     def _actions(self, actions):
@@ -263,6 +292,15 @@ class VecImageEnv:
     def set_world_maps(self, envs, ids):
         """env ``envs[q]`` moves to map ``ids[q]`` at its next reset"""
         self.world.set_world_maps(envs, ids)
+
+    def world_tracks(self):
+        """the track set each env's current episode replays, -1 where its reset brought its own (numpy int32 ``[env_num]``);
+        synchronises the stream"""
+        return self.world.world_tracks()
+
+    def set_world_tracks(self, envs, ids):
+        """env ``envs[q]`` replays set ``ids[q]`` from its next bank-fed reset on (tracks_policy "keep")"""
+        self.world.set_world_tracks(envs, ids)
 
     def end_ep(self, robot_res=None):
         return True

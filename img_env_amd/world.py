@@ -123,6 +123,45 @@ class World:
                 self.close()
                 raise ValueError("imgenv_maps_add: %s" % msg)
         self._maps_buf = None
+        self.n_track_sets = 0  # tracks_add()
+        self._tracks_buf = None
+
+    def tracks_add(self, sets):
+        """``imgenv_tracks_add``: the handle's bank of recorded crowds (dataset scene), once, before the first reset.  ``sets``: a list
+        of ``[P, T, 5]`` arrays (x, y, yaw, vx, vy per pedestrian and step; ``P`` = pedestrians per world) or ``(series, lengths)``
+        pairs -- ``_cabi.pack_track_sets``.  From then on a reset whose layout carries no ``ped_traj_v`` takes the world's
+        pedestrians from the bank.  ValueError for refused arguments, RuntimeError for a call out of order."""
+        n, cap, pose, traj, traj_v, length = _cabi.pack_track_sets(sets, self.n_peds // self.n_worlds)
+        rc = self.lib.imgenv_tracks_add(self.h, n, cap, pose.ctypes.data, traj.ctypes.data, traj_v.ctypes.data, length.ctypes.data)
+        self._call(rc, "imgenv_tracks_add")
+        self.n_track_sets = n
+
+    def set_world_tracks(self, worlds, ids):
+        """``imgenv_world_tracks_set``: world ``worlds[q]`` takes set ``ids[q]`` at its next bank-fed reset queued after this call
+        (policy "keep"); its running episode is untouched.  ValueError (nothing applied) for an id or a world out of range or a
+        world listed twice."""
+        worlds, ids = [int(k) for k in worlds], [int(k) for k in ids]
+        if len(worlds) != len(ids):
+            raise ValueError("one set id per world")
+        n = len(worlds)
+        self._call(self.lib.imgenv_world_tracks_set(self.h, n, (C.c_int32 * max(n, 1))(*worlds), (C.c_int32 * max(n, 1))(*ids), self._stream()),
+                   "imgenv_world_tracks_set")
+
+    def tracks_policy(self, name, repeat=1):
+        """``imgenv_tracks_policy``: "keep" (``set_world_tracks`` alone chooses), "placement" (``_cabi.tracks_for_placement(seed,
+        n_sets)`` of the placement's seed, inside the device-side reset chain too) or "cycle" (a world's e-th bank-fed reset since
+        this call takes set ``(e // repeat) % n_sets``: the reference wrapper's order, wrapping where it exits).  Waits for the device."""
+        if name not in _cabi.TRACK_POLICIES:
+            raise ValueError("track policy: keep | placement | cycle")
+        self._call(self.lib.imgenv_tracks_policy(self.h, _cabi.TRACK_POLICIES[name], int(repeat)), "imgenv_tracks_policy")
+
+    def world_tracks(self):
+        """``imgenv_world_tracks``: the set each world's current episode replays, -1 where its last reset brought its own tracks
+        (numpy int32 ``[n_worlds]``); synchronises the stream"""
+        if self._tracks_buf is None:
+            self._tracks_buf = (C.c_int32 * self.n_worlds)()
+        self._check(self.lib.imgenv_world_tracks(self.h, self._tracks_buf, self._stream()), "imgenv_world_tracks")
+        return np.array(self._tracks_buf[:], np.int32)
 
     def set_world_maps(self, worlds, ids):
         """``imgenv_world_maps_set``: world ``worlds[q]`` starts from map ``ids[q]`` of the bank at its next reset of any kind

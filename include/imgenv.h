@@ -706,6 +706,63 @@ int32_t imgenv_map_for_placement(uint64_t seed, int32_t n_maps);
  * imgenv_autoreset_last(). */
 int imgenv_world_maps(imgenv_t* h, int32_t* map_ids, void* stream);
 
+/* ---- track bank: recorded crowds in one handle, one set of tracks per world and episode ----
+ * The dataset pedestrian scene (IMGENV_SCENE_DATASET; img_env.cpp:294-296, 361-386) replays recorded ETH / UCY tracks that the
+ * reference's PedTrajectoryDatasetWrapper (PedTrajectoryDatasetWrapper.py:15-291) hands to every reset.  A recorded crowd is the
+ * same kind of object as a static map: a small set of immutable arrays an episode starts from.  Here the sets form a bank inside
+ * the handle; a reset that brings no tracks of its own takes the world's set from it, on the device, so dataset worlds can be
+ * reset by imgenv_reset_worlds_spawn, imgenv_step_autoreset and imgenv_step_autoreset_device like every other scene.  The step
+ * kernels read the per-world tables they always read: a reset COPIES the chosen set into the world's rows (k_tracks_install,
+ * Pw * cap * 48 bytes per world reset: 24 KB for 10 pedestrians of 50 records); nothing is added to a step.
+ *
+ * imgenv_tracks_add: legal once per handle, after imgenv_create() and before its first reset (IMGENV_ESTATE otherwise, also on a
+ * second call).  All arrays are HOST memory with the fields and meaning of imgenv_reset_batch for ONE world, repeated per set:
+ * ped_pose [n_sets][Pw][4] (x, y, qz, qw), ped_traj [n_sets][Pw][cap][3], ped_traj_v [n_sets][Pw][cap][2], ped_traj_len
+ * [n_sets][Pw], each in [1, cap]; Pw = n_peds / n_worlds.  Each set is converted once into what a reset stages for such a batch
+ * (img_env.cpp:220-250: the yaw of the quaternion, atan2(vy, vx) of the host's libm beside the velocities, records behind a
+ * pedestrian's length zero), so a bank-fed reset leaves the state an explicit batch of the same tracks leaves, bit for bit.
+ * The handle's trajectory tables are allocated here with max(cap, 2) records per pedestrian; a later explicit batch with a longer
+ * ped_traj_cap still re-lays them out, the bank keeps its own stride.  IMGENV_EINVAL: the scene is not IMGENV_SCENE_DATASET, the
+ * handle has no pedestrians or is a robot shard, n_sets < 1 or cap < 1, a length outside [1, cap], a value that is not finite.
+ * IMGENV_ENOMEM when the bank cannot be allocated; the handle is then unchanged. */
+int imgenv_tracks_add(imgenv_t* h, int32_t n_sets, int32_t cap, const double* ped_pose, const double* ped_traj,
+                      const double* ped_traj_v, const int32_t* ped_traj_len);
+/* World worlds[q] takes set set_ids[q] at its NEXT bank-fed reset queued on `stream` after this call (under
+ * IMGENV_TRACKS_KEEP; the other policies replace the choice); its running episode is untouched.  Host arrays, copied during the
+ * call.  An out-of-range set id, an out-of-range world, a world listed twice: IMGENV_EINVAL, and nothing is applied;
+ * IMGENV_ESTATE on a handle without a bank.  One small launch; no synchronisation. */
+int imgenv_world_tracks_set(imgenv_t* h, int32_t n, const int32_t* worlds, const int32_t* set_ids, void* stream);
+/* Which resets are bank-fed, and who chooses their set.
+ * A reset batch that carries ped_traj_v behaves as on a handle without a bank: it never consults the bank, does not advance the
+ * CYCLE count, and imgenv_world_tracks reports -1 for its world.  On a handle WITH a bank a batch without ped_traj_v is
+ * bank-fed -- what imgenv_reset_worlds_spawn / imgenv_step_autoreset build, an explicit batch with ped_traj_v == NULL -- and
+ * the batch's own ped_pose / ped_traj / ped_traj_len are ignored (they may be NULL); without a bank it stays IMGENV_EINVAL.
+ * imgenv_step_autoreset_device accepts a dataset handle once it has a bank.  The sampler still places the YAML's n_peds
+ * pedestrians and the result is discarded, as EnvPos.reset does before init_ped_dataset overwrites them
+ * (reset_helper.py:417-432): the robots' placements and the placement numbering do not depend on the bank, and
+ * imgenv_world_placement keeps reporting the SAMPLER's pedestrian poses -- the recorded ones are identified by imgenv_world_tracks.
+ *   IMGENV_TRACKS_KEEP (the default): the set of imgenv_world_tracks_set (set 0 until then).
+ *   IMGENV_TRACKS_BY_PLACEMENT: set = imgenv_tracks_for_placement(seed, n_sets) with the placement's seed -- seeds[q] for
+ *     imgenv_reset_worlds_spawn, seed0 + k for imgenv_step_autoreset, seed0 + placement number inside the device-side chain.
+ *     A bank-fed reset without a seed (an explicit batch) keeps the world's choice.
+ *   IMGENV_TRACKS_CYCLE: the reference wrapper's own order: a world's e-th bank-fed reset since this call (e = 0, 1, ...) takes
+ *     set (e / repeat) % n_sets -- PedTrajectoryDatasetWrapper.reset with repeated_time_per_env = repeat and cur_world.
+ *     DEVIATION: after the last set the reference calls sys.exit(); this wraps to set 0.
+ * Every resolved set also becomes the world's choice for KEEP.  repeat < 1 or an unknown policy: IMGENV_EINVAL; IMGENV_ESTATE
+ * without a bank.  Takes effect with the next call that resets; it zeroes the per-world counts, for which it waits for the
+ * device (not a call for the hot loop). */
+#define IMGENV_TRACKS_KEEP 0
+#define IMGENV_TRACKS_BY_PLACEMENT 1
+#define IMGENV_TRACKS_CYCLE 2
+int imgenv_tracks_policy(imgenv_t* h, int32_t policy, int32_t repeat);
+/* The draw under IMGENV_TRACKS_BY_PLACEMENT: imgenv_map_for_placement(seed + 0xBB67AE8584CAA73B, n_sets), the sum modulo 2^64 --
+ * the salt (the fractional bits of sqrt 3) keeps a handle with both banks from tying map m to set m.  A pure function, one
+ * definition (csrc/track_bank.h) compiled for host and device.  n_sets <= 1 gives 0. */
+int32_t imgenv_tracks_for_placement(uint64_t seed, int32_t n_sets);
+/* set_ids[n_worlds]: the set each world's CURRENT episode replays, -1 where its last reset brought its own tracks (every world
+ * before its first reset, and all of them without a bank).  Synchronises `stream`, like imgenv_world_maps(). */
+int imgenv_world_tracks(imgenv_t* h, int32_t* set_ids, void* stream);
+
 /* The two OpenCV resizes of the path for one-channel 8-bit images, as the library performs them (OpenCV 4.2.0's generic
  * fixed-point CPU path restated, csrc/cv_resize.h): host buffers, no device needed.  kind 0: INTER_LINEAR, 1: INTER_CUBIC. */
 int imgenv_cv_resize_u8(int kind, const uint8_t* src, int32_t sh, int32_t sw, uint8_t* dst, int32_t dh, int32_t dw);

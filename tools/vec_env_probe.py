@@ -15,7 +15,11 @@ alternates no statistics / library / torch over several rounds and writes the ra
 --wrappers table|clip feeds the policy's raw output (indices into a 28-row table, or float rows to be clipped) to
 VecImageEnv(wrappers=True): decode, speeds, normalised pedestrian vectors and close_to_human kept by the library;
 --torch-wrappers keeps the same with torch ops on top of a plain VecImageEnv; --wrappers-compare alternates pre-decoded actions
-with nothing enabled / library / torch over several rounds, for the table and for the clip, and writes the raw figures."""
+with nothing enabled / library / torch over several rounds, for the table and for the clip, and writes the raw figures.
+
+--tracks-compare (with --peds 10) runs the dataset pedestrian scene -- recorded crowds of --records records per pedestrian --
+three ways, alternating over several rounds: a Python loop that reads all_down and uploads the finished envs' tracks in explicit
+batches (what a handle without a track bank can do), native_spawn with the bank (imgenv_tracks_add) and device_reset with it."""
 import argparse
 import json
 import os
@@ -357,6 +361,102 @@ def compare_wrappers(args, rounds=3):
                 rounds=rounds, runs=runs, summary=summary)
 
 
+def track_sets(n_sets, peds, records, dt, seed=3, box=(3.0, 22.0)):
+    """n_sets recorded crowds of `peds` straight walks of `records` records each: [peds, records, 5] rows (x, y, yaw, vx, vy)"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    sets = []
+    for _ in range(n_sets):
+        d = np.zeros((peds, records, 5))
+        for j in range(peds):
+            x0, y0 = rng.uniform(box[0], box[1], 2)
+            vx, vy = rng.uniform(-0.3, 0.3, 2)
+            q = np.arange(records)
+            d[j, :, 0], d[j, :, 1], d[j, :, 2] = x0 + vx * dt * q, y0 + vy * dt * q, np.arctan2(vy, vx)
+            d[j, 1:, 3], d[j, 1:, 4] = vx, vy
+        sets.append(d)
+    return sets
+
+
+def measure_tracks(variant, envs=1024, robots=4, peds=10, records=50, obstacles=2, steps=300, time_max=100, n_sets=8):
+    """us per step of a dataset-scene VecImageEnv that never stops.  variant "python_loop": what exists without a track bank --
+    imgenv_step, a host read of all_down, the finished envs' placements drawn by the library's host sampler and their recorded
+    tracks uploaded in explicit batches (imgenv_reset_worlds); "native_spawn" / "device_reset": the bank (imgenv_tracks_add),
+    sets drawn with the placements"""
+    import torch
+    from img_env_amd import _cabi, spawn, worldgen
+    from img_env_amd.vec_env import VecImageEnv
+    grid = worldgen.make_grid(200, 2)
+    cfg = worldgen.make_yaml_cfg(robots, peds, grid, scene="dataset", time_max=time_max, n_obstacles=obstacles, seed=5)
+    sets = track_sets(n_sets, peds, records, float(cfg["control_hz"]))
+    loop = variant == "python_loop"
+    env = VecImageEnv(cfg, env_num=envs, seed=5, native_spawn=variant != "python_loop", device_reset=variant == "device_reset",
+                      auto_reset=not loop, ped_tracks=None if loop else sets, tracks_policy="keep" if loop else "placement")
+    n = len(env)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    acts = torch.zeros(16, n, 3, device="cuda")
+    acts[:, :, 0] = torch.rand(16, n, generator=g, device="cuda") * 0.6
+    acts[:, :, 1] = torch.rand(16, n, generator=g, device="cuda") * 1.8 - 0.9
+    state = dict(episodes=0, resets=0)
+    spawn_cfg = spawn.make_spawn_cfg(cfg)
+
+    def fresh(k_list):
+        lays = []
+        for _ in k_list:
+            seed = env._spawn_seed + state["episodes"]
+            state["episodes"] += 1
+            lays.append(spawn.init_ped_dataset(spawn.native_spawn(cfg, seed, spawn_cfg), sets[_cabi.tracks_for_placement(seed, n_sets)]))
+        return lays
+
+    def step(a):
+        if not loop:
+            info = env.step(a)[3]
+            if info["reset_envs"] is not None:
+                state["resets"] += len(info["reset_envs"])
+            return
+        o = env.world.step(a)
+        down = (o["dones"].view(envs, robots) > 0).all(dim=1)
+        finished = torch.nonzero(down).flatten().tolist()  # the host read in front of every reset
+        if finished:
+            env.reset_envs(finished, fresh(finished))
+            state["resets"] += len(finished)
+    if loop:
+        env.reset(fresh(range(envs)))
+    else:
+        env.reset()
+    for s in range(time_max + 20):  # past the first wave of time limits
+        step(acts[s % 16])
+    torch.cuda.synchronize()
+    placed0 = sum(env.world.autoreset_last()[::-1][0:1]) + len(env.world.autoreset_last()[0]) if variant == "device_reset" else 0
+    state["resets"], t0 = 0, time.perf_counter()
+    for s in range(steps):
+        step(acts[s % 16])
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if variant == "device_reset":
+        worlds, first = env.world.autoreset_last()
+        state["resets"] = first + len(worlds) - placed0
+    env.close()
+    return dict(us_per_step=1e6 * dt / steps, env_resets_per_step=state["resets"] / steps, bytes_per_world_reset=peds * records * 48)
+
+
+def compare_tracks(args, rounds=3):
+    """python_loop / native_spawn / device_reset over recorded crowds, alternating, `rounds` times"""
+    variants = ("python_loop", "native_spawn", "device_reset")
+    runs = []
+    for rnd in range(rounds):
+        for variant in variants:
+            r = measure_tracks(variant, args.envs, args.robots, args.peds, args.records, args.obstacles, args.steps, args.time_max)
+            runs.append(dict(round=rnd, variant=variant, **r))
+            print(json.dumps(runs[-1]), flush=True)
+    summary = {}
+    for variant in variants:
+        v = [r["us_per_step"] for r in runs if r["variant"] == variant]
+        summary[variant] = dict(us_per_step_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
+    return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, records=args.records, steps=args.steps,
+                time_max=args.time_max, rounds=rounds, runs=runs, summary=summary)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
@@ -378,9 +478,20 @@ def main():
     ap.add_argument("--torch-wrappers", action="store_true", help="with --wrappers: the same kept with torch ops on a plain VecImageEnv")
     ap.add_argument("--wrappers-compare", action="store_true",
                     help="pre-decoded actions / library / torch, alternating over --rounds rounds, table and clip")
+    ap.add_argument("--tracks-compare", action="store_true",
+                    help="dataset scene: explicit track batches from a Python loop / native_spawn with a track bank / device_reset with "
+                         "it, alternating over --rounds rounds (use --peds 10)")
+    ap.add_argument("--records", type=int, default=50, help="--tracks-compare: records per recorded pedestrian")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None, help="--stack-compare / --episodes-compare: also write the JSON here")
     args = ap.parse_args()
+    if args.tracks_compare:
+        res = compare_tracks(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
+        return
     if args.wrappers_compare:
         res = compare_wrappers(args, args.rounds)
         if args.out:

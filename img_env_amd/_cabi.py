@@ -33,6 +33,10 @@ MAP_POLICIES = {"keep": MAPS_KEEP, "placement": MAPS_BY_PLACEMENT}
 TRACKS_KEEP, TRACKS_BY_PLACEMENT, TRACKS_CYCLE = 0, 1, 2  # imgenv_tracks_policy
 TRACK_POLICIES = {"keep": TRACKS_KEEP, "placement": TRACKS_BY_PLACEMENT, "cycle": TRACKS_CYCLE}
 TRACKS_PLACEMENT_SALT = 0xBB67AE8584CAA73B  # imgenv_tracks_for_placement (csrc/track_bank.h)
+SCENARIOS_OFF, SCENARIOS_QUEUE, SCENARIOS_BY_PLACEMENT = 0, 1, 2  # imgenv_scenarios_policy
+SCENARIO_POLICIES = {"off": SCENARIOS_OFF, "queue": SCENARIOS_QUEUE, "placement": SCENARIOS_BY_PLACEMENT}
+SCENARIO_PLACEMENT_SALT = 0x3C6EF372FE94F82B  # imgenv_scenario_for_placement (csrc/scenario_bank.h)
+SPAWN_MAX_AGENTS, SPAWN_MAX_OBST = 256, 24  # one world's cast in the device-side reset (csrc/spawn_slot.h)
 EINVAL, ENOMEM, EDEVICE, ESTATE = -1, -2, -3, -4
 
 SHAPES = {"circle": SHAPE_CIRCLE, "rectangle": SHAPE_RECTANGLE, "leg": SHAPE_LEG}
@@ -387,7 +391,9 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_episodes_enable", "imgenv_episodes_outputs", "imgenv_episodes_clear",
            "imgenv_actions_enable", "imgenv_actions_outputs", "imgenv_actions_decode", "imgenv_obs_post_enable", "imgenv_obs_post_outputs",
            "imgenv_maps_add", "imgenv_world_maps_set", "imgenv_maps_policy", "imgenv_map_for_placement", "imgenv_world_maps",
-           "imgenv_tracks_add", "imgenv_world_tracks_set", "imgenv_tracks_policy", "imgenv_tracks_for_placement", "imgenv_world_tracks")
+           "imgenv_tracks_add", "imgenv_world_tracks_set", "imgenv_tracks_policy", "imgenv_tracks_for_placement", "imgenv_world_tracks",
+           "imgenv_scenarios_add", "imgenv_scenarios_policy", "imgenv_scenario_for_placement", "imgenv_reset_worlds_scenarios",
+           "imgenv_world_scenarios")
 K_COUNT = 14
 
 
@@ -458,6 +464,12 @@ def bind(lib):
     lib.imgenv_tracks_for_placement.argtypes = [C.c_uint64, C.c_int32]
     lib.imgenv_tracks_for_placement.restype = C.c_int32
     lib.imgenv_world_tracks.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
+    lib.imgenv_scenarios_add.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 9
+    lib.imgenv_scenarios_policy.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p]
+    lib.imgenv_scenario_for_placement.argtypes = [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32]
+    lib.imgenv_scenario_for_placement.restype = C.c_int32
+    lib.imgenv_reset_worlds_scenarios.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
+    lib.imgenv_world_scenarios.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
     lib.imgenv_kernel_name.argtypes = [C.c_int]
     lib.imgenv_kernel_name.restype = C.c_char_p
     return lib
@@ -471,6 +483,48 @@ def map_for_placement(seed, n_maps):
 def tracks_for_placement(seed, n_sets):
     """``imgenv_tracks_for_placement``: the track set an episode placed from ``seed`` replays under the "placement" policy (needs no GPU)"""
     return int(load_library().imgenv_tracks_for_placement(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(n_sets)))
+
+
+def scenario_for_placement(policy, seed0, first, n, n_scenarios):
+    """``imgenv_scenario_for_placement``: the scenario placement number ``n`` replays under ``policy`` ("queue": ``(first + n) %
+    n_scenarios``; "placement": a draw from ``seed0 + n``; "off": -1).  Needs no GPU."""
+    m = 0xFFFFFFFFFFFFFFFF
+    code = SCENARIO_POLICIES[policy] if isinstance(policy, str) else int(policy)
+    return int(load_library().imgenv_scenario_for_placement(code, C.c_uint64(int(seed0) & m), C.c_uint64(int(first) & m), C.c_uint64(int(n) & m),
+                                                            int(n_scenarios)))
+
+
+#: the arrays of one recorded episode, in the order of ``imgenv_spawn`` / ``imgenv_scenarios_add``: name -> (dtype, shape per episode)
+def scenario_arrays(R, P, O):
+    return {"robot_pose": (np.float64, (R, 4)), "robot_goal": (np.float64, (R, 2)), "ped_pose": (np.float64, (P, 4)),
+            "ped_goal": (np.float64, (P, 2)), "ped_traj": (np.float64, (P, 2, 3)), "ped_traj_len": (np.int32, (P,)),
+            "obs_shape": (np.int32, (O,)), "obs_size": (np.float32, (O, 4)), "obs_pose": (np.float64, (O, 4))}
+
+
+def pack_scenarios(layouts, R, P, O):
+    """The arrays of ``imgenv_scenarios_add`` from a list of recorded episodes -- the layout objects ``spawn.native_spawn`` /
+    ``EnvPos.reset`` return (or dicts with the same fields): a dict name -> array with a leading ``[n]`` axis, in the order of the C
+    prototype.  Every episode must hold ``R`` robots, ``P`` pedestrians with trajectories of at most two points and ``O``
+    obstacles: one cast per bank."""
+    layouts = list(layouts)
+    if not layouts:
+        raise ValueError("no scenarios")
+    spec = scenario_arrays(R, P, O)
+    out = {k: np.zeros((len(layouts),) + shape, dt) for k, (dt, shape) in spec.items()}
+    for s, lay in enumerate(layouts):
+        get = (lambda k: lay.get(k)) if isinstance(lay, dict) else (lambda k: getattr(lay, k, None))
+        for k, (dt, shape) in spec.items():
+            v = get(k)
+            if v is None:
+                v = np.zeros(shape, dt)
+            v = np.asarray(v)
+            if k == "ped_traj" and v.ndim == 3 and v.shape[0] == P and v.shape[1] == 1:  # a one-point trajectory: the second is zero
+                v = np.concatenate([v, np.zeros_like(v)], axis=1)
+            if v.size != int(np.prod(shape)) or (v.ndim > 1 and v.shape != shape):
+                raise ValueError("scenario %d: %s is %s, the bank's cast needs %s (%d robots, %d pedestrians, %d obstacles)"
+                                 % (s, k, v.shape, shape, R, P, O))
+            out[k][s] = v.reshape(shape)
+    return out
 
 
 def pack_track_sets(sets, n_peds):

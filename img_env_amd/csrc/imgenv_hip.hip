@@ -28,6 +28,7 @@
 #include "actions.h"
 #include "obs_post.h"
 #include "map_bank.h"
+#include "spawn_slot.h"
 
 static thread_local char g_err[512] = "";
 #define FAIL(code, ...)                              \
@@ -104,6 +105,23 @@ struct imgenv {
     int tracks_policy = 0, tracks_repeat = 1;         // IMGENV_TRACKS_*
     const int* reset_track_ids = nullptr;  // host-placed resets under BY_PLACEMENT: the sets of the worlds being reset, in list order (for the call in progress)
     std::vector<int> trk_fed, trk_fed_ids;  // the worlds of the reset being staged whose batch brought no tracks, and the host's draw for each (-1: the device resolves)
+    // scenario bank (include/imgenv.h: imgenv_scenarios_add; csrc/scenario_bank.h)
+    int n_scn = 0, scn_obst = 0;               // episodes of the bank (0: none); obstacles of each
+    std::vector<SlotAgent> scn_agents;         // [n_scn][Rw + Pw] the host copy (imgenv_reset_worlds_scenarios, checkers)
+    std::vector<SlotObstacle> scn_obstacles;   // [n_scn][scn_obst]
+    SlotAgent* d_scn_agents = nullptr;
+    SlotObstacle* d_scn_obst = nullptr;
+    int scn_policy = 0;                        // IMGENV_SCENARIOS_*
+    uint64_t scn_first = 0;
+    int* d_scn_world = nullptr;                // [W] the scenario of each world's last HOST reset, -1: not from the bank
+    unsigned long long* d_scn_mark = nullptr;  // [W] the placement number the world held at that reset (k_scenario_mark)
+    const int* reset_scn_ids = nullptr;        // imgenv_reset_worlds_scenarios: the scenarios of the worlds being reset, in list order (for the call in progress)
+    // which policy the device's placements were filled under: epoch e covers the placement numbers from its start on, the start
+    // being the device's count when imgenv_scenarios_policy was queued -- copied on the device, read at imgenv_world_scenarios
+    struct ScnEpoch { int policy; uint64_t first; };
+    std::vector<ScnEpoch> scn_epochs;
+    unsigned long long* d_scn_starts = nullptr;  // [scn_starts_cap]
+    size_t scn_starts_cap = 0;
     struct ObstInstHost { double x, y, sh, ch, cx, cy, r; int m0, m1, n0, n1, shape, world; };
     std::vector<ObstInstHost> oinst;  // obstacles of the reset being staged
     void* d_oinst = nullptr;
@@ -2037,6 +2055,7 @@ __global__ __launch_bounds__(256) void k_reset_obstacles(DevWorld w, const ObstI
 
 #include "spawn_device.h"  // device-side auto-reset: k_spawn_fill, k_finished_dev, k_respawn, k_restore_maps_dev
 #include "track_bank.h"    // recorded crowds: k_tracks_install
+#include "scenario_bank.h"  // recorded episodes: k_scenario_fill
 
 static auto k_reset_obstacles_for(const PlanHandle& p) { return p.pow2 ? k_reset_obstacles<true> : k_reset_obstacles<false>; }
 static auto k_restore_maps_dev_for(const PlanHandle& p) { return p.pow2 ? k_restore_maps_dev<true> : k_restore_maps_dev<false>; }
@@ -2425,8 +2444,21 @@ static int reset_launch(imgenv* h, const int* list, int n, hipStream_t st, int w
         h->trk_fed.clear();
         h->trk_fed_ids.clear();
     }
+    if (h->d_scn_world) {  // a handle with a scenario bank: what imgenv_world_scenarios answers for the worlds of this reset
+        const int n_mark = list ? n : h->W;
+        const int* ids = nullptr;
+        if (h->reset_scn_ids) {
+            unsigned char* pi = nullptr;
+            RTRY(stage_room(h, sizeof(int) * (size_t)n_mark, &pi));
+            memcpy(pi, h->reset_scn_ids, sizeof(int) * (size_t)n_mark);
+            ids = (const int*)pi;
+        }
+        k_scenario_mark<<<dim3((unsigned)((n_mark + 255) / 256)), dim3(256), 0, st>>>(h->d_scn_world, h->d_scn_mark,
+                                                                                      h->sd_ready ? ((SpawnDev*)h->sd_storage)->place_serial : nullptr,
+                                                                                      list ? h->pin_list : nullptr, ids, n_mark);
+    }
     HIPCHK(hipGetLastError());
-    h->launches = 2 + (n_fed > 0 ? 1 : 0);
+    h->launches = 2 + (n_fed > 0 ? 1 : 0) + (h->d_scn_world ? 1 : 0);
     const int rc = launch_views(h, st, 1);
     set_active(h, nullptr, 0);
     // k_reset_apply is in flight and reads this generation's page-locked chunks: mark them pending whatever came after
@@ -2848,6 +2880,187 @@ extern "C" int imgenv_world_tracks(imgenv_t* h, int32_t* set_ids, void* stream) 
     return IMGENV_OK;
 }
 
+// ---------------------------------------------------------------------------------------- scenario bank
+extern "C" int32_t imgenv_scenario_for_placement(int32_t policy, uint64_t seed0, uint64_t first, uint64_t n, int32_t n_scenarios) {
+    return scenario_for_placement(policy, seed0, first, n, n_scenarios);
+}
+
+// RVO obstacle vertices / BSP nodes a pool slot of the device-side reset has room for, whatever the handle's own tables hold
+// (spawn_device_setup only ever raises it to the handle's capacity)
+static int spawn_slot_cap(int nob) { return std::max(16, std::min(SPAWN_BSP_CAP, 16 * std::max(nob, 1))); }
+
+extern "C" int imgenv_scenarios_add(imgenv_t* h, int32_t n, int32_t n_obstacles, const double* robot_pose, const double* robot_goal,
+                                    const double* ped_pose, const double* ped_goal, const double* ped_traj, const int32_t* ped_traj_len,
+                                    const int32_t* obs_shape, const float* obs_size, const double* obs_pose) {
+    if (!h || !robot_pose || !robot_goal) FAIL(IMGENV_EINVAL, "null argument");
+    if (h->n_scn > 0) FAIL(IMGENV_ESTATE, "imgenv_scenarios_add has already been called on this handle");
+    if (h->sd_ready) FAIL(IMGENV_ESTATE, "imgenv_scenarios_add after the first imgenv_step_autoreset_device");
+    if (h->RL != h->R) FAIL(IMGENV_EINVAL, "imgenv_scenarios_add on a robot shard is not supported");
+    const int Rw = h->Rw, Pw = h->Pw, na = Rw + Pw, O = n_obstacles;
+    if (n < 1 || n > (1 << 24)) FAIL(IMGENV_EINVAL, "imgenv_scenarios_add: %d scenarios", n);
+    if (O < 0 || O > SPAWN_MAX_OBST || na > SPAWN_MAX_AGENTS)
+        FAIL(IMGENV_EINVAL, "imgenv_scenarios_add: %d agents and %d obstacles per world, the device-side reset places at most %d and %d", na, O,
+             SPAWN_MAX_AGENTS, SPAWN_MAX_OBST);
+    if (Pw > 0 && (!ped_pose || !ped_goal || !ped_traj || !ped_traj_len)) FAIL(IMGENV_EINVAL, "imgenv_scenarios_add: null pedestrian arrays");
+    if (O > 0 && (!obs_shape || !obs_size || !obs_pose)) FAIL(IMGENV_EINVAL, "imgenv_scenarios_add: null obstacle arrays");
+    // the whole bank on the host first: bad input fails the call before anything is allocated
+    std::vector<SlotAgent> agents((size_t)n * std::max(na, 1));
+    std::vector<SlotObstacle> obst((size_t)n * std::max(O, 1));
+    int where = 0, which = 0;
+    if (const int bad = scenarios_convert(n, Rw, Pw, O, robot_pose, robot_goal, ped_pose, ped_goal, ped_traj, ped_traj_len, obs_shape, obs_size,
+                                          obs_pose, agents.data(), obst.data(), &where, &which))
+        FAIL(IMGENV_EINVAL, "imgenv_scenarios_add: scenario %d, %s %d: %s", where,
+             bad >= SCENARIO_BAD_SHAPE ? "obstacle" : (which < Rw ? "robot" : "pedestrian"), bad >= SCENARIO_BAD_SHAPE || which < Rw ? which : which - Rw,
+             scenario_error_text(bad));
+    if (na > 0) agents.resize((size_t)n * na);
+    if (O > 0) obst.resize((size_t)n * O);
+    if (h->NA > 0 && O > 0) {  // RVO agents: every scenario's polygons and their BSP, built by the device BSP's host twin, must fit a slot
+        const int cap = spawn_slot_cap(O);
+        RvoObstacles rvo;
+        for (int s = 0; s < n; s++) {
+            rvo.clear();
+            for (int q = 0; q < O; q++) {
+                const SlotObstacle& o = obst[(size_t)s * O + q];
+                const double sizes[4] = {(double)o.size[0], (double)o.size[1], (double)o.size[2], (double)o.size[3]};
+                const double yaw = tf_yaw_from_quaternion_zw(o.qz, o.qw);
+                const Tf2 bw = tf_from_pose_sc(o.x, o.y, sin(yaw * 0.5), cos(yaw * 0.5));
+                double pax, pay, pbx, pby;
+                get_corners(o.shape, sizes, bw, pax, pay, pbx, pby);
+                const float v[8] = {(float)pax, (float)pay, (float)pax, (float)pby, (float)pbx, (float)pby, (float)pbx, (float)pay};
+                rvo.add(v, 4);
+            }
+            rvo.process();
+            if ((int)rvo.ob.size() > cap || (int)rvo.nodes.size() > cap)
+                FAIL(IMGENV_EINVAL, "imgenv_scenarios_add: scenario %d: %d RVO obstacle vertices and %d BSP nodes, a pool slot has room for %d", s,
+                     (int)rvo.ob.size(), (int)rvo.nodes.size(), cap);
+        }
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    SlotAgent* da = nullptr;
+    SlotObstacle* dob = nullptr;
+    int* scn = nullptr;
+    unsigned long long *mark = nullptr, *starts = nullptr;
+    const size_t starts_cap = 256;
+    auto room = [&](auto** out, size_t cnt, int fill) -> bool { return tracks_room(h, out, cnt, fill); };
+    const bool ok = room(&da, agents.size(), 0) && room(&dob, obst.size(), 0) && room(&scn, (size_t)h->W, 0xFF) && room(&mark, (size_t)h->W, 0xFF) &&
+                    room(&starts, starts_cap, 0) &&
+                    (agents.empty() || hipMemcpy(da, agents.data(), sizeof(SlotAgent) * agents.size(), hipMemcpyHostToDevice) == hipSuccess) &&
+                    (obst.empty() || hipMemcpy(dob, obst.data(), sizeof(SlotObstacle) * obst.size(), hipMemcpyHostToDevice) == hipSuccess);
+    if (!ok) {  // everything is allocated and filled before the handle changes: a failure leaves it without a bank
+        (void)hipGetLastError();
+        dev_free(h, da); dev_free(h, dob); dev_free(h, scn); dev_free(h, mark); dev_free(h, starts);
+        FAIL(IMGENV_ENOMEM, "no device memory for a bank of %d scenarios", n);
+    }
+    h->scn_agents.swap(agents);
+    h->scn_obstacles.swap(obst);
+    h->d_scn_agents = da; h->d_scn_obst = dob; h->d_scn_world = scn; h->d_scn_mark = mark;
+    h->d_scn_starts = starts; h->scn_starts_cap = starts_cap;
+    h->n_scn = n;
+    h->scn_obst = O;
+    h->scn_policy = IMGENV_SCENARIOS_OFF;
+    h->scn_first = 0;
+    h->scn_epochs.assign(1, imgenv::ScnEpoch{IMGENV_SCENARIOS_OFF, 0});  // (epoch 0 starts at placement 0: the array is zeroed)
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_scenarios_policy(imgenv_t* h, int32_t policy, uint64_t first, void* stream) {
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (policy != IMGENV_SCENARIOS_OFF && policy != IMGENV_SCENARIOS_QUEUE && policy != IMGENV_SCENARIOS_BY_PLACEMENT)
+        FAIL(IMGENV_EINVAL, "unknown scenario policy %d", policy);
+    if (h->n_scn < 1) FAIL(IMGENV_ESTATE, "imgenv_scenarios_policy: the handle has no scenario bank (imgenv_scenarios_add)");
+    hipStream_t st = (hipStream_t)stream;
+    if (h->sd_ready) {
+        // The pool's slots were drawn under the old policy and must not be handed out: every slot loses its serial on the caller's
+        // stream and the next chain's fill -- forced, behind this on the chain's event -- draws them again (spawn_dev_refresh's
+        // stride path does the same).  The placements from the device's present count on belong to the new policy: the count is
+        // copied on the device, for imgenv_world_scenarios.  Nothing here waits for the device.
+        HIPCHK(hipSetDevice(h->cfg.device));
+        SpawnDev& c = *(SpawnDev*)h->sd_storage;
+        if (h->scn_epochs.size() >= h->scn_starts_cap) {  // (every 256th switch and rarer: the log doubles; the old block lives until imgenv_destroy)
+            unsigned long long* grown = nullptr;
+            RTRY(dev_alloc(h, &grown, h->scn_starts_cap * 2));
+            HIPCHK(hipMemcpyAsync(grown, h->d_scn_starts, sizeof(unsigned long long) * h->scn_starts_cap, hipMemcpyDeviceToDevice, st));
+            h->d_scn_starts = grown;
+            h->scn_starts_cap *= 2;
+        }
+        HIPCHK(hipMemcpyAsync(h->d_scn_starts + h->scn_epochs.size(), c.consumed, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+        h->scn_epochs.push_back(imgenv::ScnEpoch{policy, first});
+        HIPCHK(hipMemsetAsync(c.slot_serial, 0xFF, sizeof(unsigned long long) * (size_t)c.S, st));
+        h->fill_due = 0;
+    } else {  // no pool yet: its first fill takes the policy, from placement 0
+        h->scn_epochs.assign(1, imgenv::ScnEpoch{policy, first});
+    }
+    h->scn_policy = policy;
+    h->scn_first = first;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_reset_worlds_scenarios(imgenv_t* h, int32_t n, const int32_t* worlds, const int32_t* ids, void* stream) {
+    if (!h || n < 0 || (n > 0 && (!worlds || !ids))) FAIL(IMGENV_EINVAL, "null argument");
+    if (h->n_scn < 1) FAIL(IMGENV_ESTATE, "imgenv_reset_worlds_scenarios: the handle has no scenario bank (imgenv_scenarios_add)");
+    for (int q = 0; q < n; q++)
+        if (ids[q] < 0 || ids[q] >= h->n_scn) FAIL(IMGENV_EINVAL, "scenario %d out of range (the handle holds %d)", ids[q], h->n_scn);
+    if (n == 0) return IMGENV_OK;
+    const int Rw = h->Rw, Pw = h->Pw, O = h->scn_obst, na = Rw + Pw;
+    // the batches of imgenv_reset_worlds, out of the bank's host copy (trajectories of two points, as imgenv_spawn lays them out)
+    const size_t N = (size_t)n;
+    std::vector<double> rp(N * Rw * 4 + 1), rg(N * Rw * 2 + 1), pp(N * Pw * 4 + 1), pg(N * Pw * 2 + 1), pt(N * Pw * 6 + 1), op(N * O * 4 + 1);
+    std::vector<int32_t> pl(N * Pw + 1), os(N * O + 1);
+    std::vector<float> oz(N * O * 4 + 1);
+    std::vector<imgenv_reset_batch> batches(N);
+    for (size_t q = 0; q < N; q++) {
+        const size_t id = (size_t)ids[q];
+        scenario_to_arrays(Rw, Pw, O, h->scn_agents.data() + id * na, h->scn_obstacles.data() + id * O, rp.data() + q * Rw * 4, rg.data() + q * Rw * 2,
+                           pp.data() + q * Pw * 4, pg.data() + q * Pw * 2, pt.data() + q * Pw * 6, pl.data() + q * Pw, os.data() + q * O,
+                           oz.data() + q * O * 4, op.data() + q * O * 4);
+        imgenv_reset_batch& b = batches[q];
+        memset(&b, 0, sizeof(b));
+        b.struct_size = (int32_t)sizeof(b);
+        b.n_obstacles = O;
+        b.obs_shape = os.data() + q * O; b.obs_size = oz.data() + q * O * 4; b.obs_pose = op.data() + q * O * 4;
+        b.robot_pose = rp.data() + q * Rw * 4; b.robot_goal = rg.data() + q * Rw * 2;
+        b.ped_pose = pp.data() + q * Pw * 4; b.ped_goal = pg.data() + q * Pw * 2;
+        b.ped_traj_len = pl.data() + q * Pw; b.ped_traj = pt.data() + q * Pw * 6;
+        b.ped_traj_cap = 2;
+    }
+    h->reset_scn_ids = ids;
+    const int rc = imgenv_reset_worlds(h, n, worlds, batches.data(), stream);
+    h->reset_scn_ids = nullptr;
+    return rc;
+}
+
+extern "C" int imgenv_world_scenarios(imgenv_t* h, int32_t* ids, void* stream) {
+    if (!h || !ids) FAIL(IMGENV_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    if (int rc = check_device_flags(h)) return rc;
+    const size_t W = (size_t)h->W;
+    for (size_t k = 0; k < W; k++) ids[k] = -1;
+    if (h->n_scn < 1) return IMGENV_OK;
+    std::vector<int> scn(W);
+    std::vector<unsigned long long> mark(W), serial(W, ~0ull), starts(h->scn_epochs.size());
+    HIPCHK(hipMemcpy(scn.data(), h->d_scn_world, sizeof(int) * W, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(mark.data(), h->d_scn_mark, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(starts.data(), h->d_scn_starts, sizeof(unsigned long long) * starts.size(), hipMemcpyDeviceToHost));
+    uint64_t seed0 = 0;
+    if (h->sd_ready) {
+        const SpawnDev& c = *(SpawnDev*)h->sd_storage;
+        HIPCHK(hipMemcpy(serial.data(), c.place_serial, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost));
+        seed0 = c.seed0;
+    }
+    starts[0] = 0;
+    for (size_t k = 0; k < W; k++) {
+        if (serial[k] == mark[k]) {  // the host reset it last (or nobody has)
+            ids[k] = scn[k];
+            continue;
+        }
+        size_t e = starts.size() - 1;  // the device handed placement serial[k] out: under the policy of the epoch it falls into
+        while (e > 0 && starts[e] > serial[k]) e--;
+        ids[k] = scenario_for_placement(h->scn_epochs[e].policy, seed0, h->scn_epochs[e].first, serial[k], h->n_scn);
+    }
+    return IMGENV_OK;
+}
+
 // ---------------------------------------------------------------------------------------- step
 // k_sfm for one step of every crowd, on stream s: from the live set into `out` (null: in place), with or without the write-back to
 // the pedestrians' arrays
@@ -3185,6 +3398,23 @@ extern "C" int imgenv_step_autoreset(imgenv_t* h, const float* actions, const im
 
 
 // ---------------------------------------------------------------------------------------- device-side auto-reset
+// The pool's fill on the side stream, by the handle's scenario policy: the sampler (k_spawn_fill) or the bank (k_scenario_fill,
+// the same launch shape: one wave64 workgroup per slot).  ev_fill says when it is done; the next chain waits for it in front of
+// its k_respawn.
+static int launch_pool_fill(imgenv* h, const SpawnDev& c) {
+    if (h->scn_policy != IMGENV_SCENARIOS_OFF) {
+        ScenarioSel b;
+        b.agents = h->d_scn_agents; b.obst = h->d_scn_obst;
+        b.n = h->n_scn; b.policy = h->scn_policy; b.first = (unsigned long long)h->scn_first;
+        k_scenario_fill<<<dim3(c.S), dim3(WAVE), 0, h->side3>>>(c, b);
+    } else {
+        k_spawn_fill<<<dim3(c.S), dim3(WAVE), 0, h->side3>>>(c);
+    }
+    HIPCHK(hipEventRecord(h->ev_fill, h->side3));
+    h->fill_pending = true;
+    return 0;
+}
+
 static int spawn_device_setup(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t seed0, hipStream_t st) {
     const int na = cfg->n_robots + cfg->n_peds, nob = cfg->n_obstacles;
     if (na > SPAWN_MAX_AGENTS || nob > SPAWN_MAX_OBST)
@@ -3202,6 +3432,7 @@ static int spawn_device_setup(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t s
         h->sd_delete = [](void* p) { delete (SpawnDev*)p; };
     }
     SpawnDev& c = *(SpawnDev*)h->sd_storage;
+    const bool rebuilt = h->sd_ready;
     if (h->sd_ready) {  // another spawn cfg: the old pool goes (a curriculum that alternates cfgs would otherwise grow until imgenv_destroy)
         HIPCHK(hipStreamSynchronize(h->side3));
         HIPCHK(hipStreamSynchronize(st));
@@ -3325,9 +3556,12 @@ static int spawn_device_setup(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t s
         HIPCHK(hipEventCreateWithFlags(&h->ev_consumed, hipEventDisableTiming | hipEventDisableSystemFence));
     }
     HIPCHK(hipStreamSynchronize(st));  // (set-up only: the uploads above were synchronous copies)
-    k_spawn_fill<<<dim3(S), dim3(WAVE), 0, h->side3>>>(c);
-    HIPCHK(hipEventRecord(h->ev_fill, h->side3));
-    h->fill_pending = true;  // the next chain waits for this fill in front of its k_respawn, whatever fill_due says
+    if (h->n_scn > 0 && rebuilt) {  // a new pool numbers its placements from 0 again: one epoch of the present policy, and no world's
+        h->scn_epochs.assign(1, imgenv::ScnEpoch{h->scn_policy, h->scn_first});  // placement number means anything any more
+        HIPCHK(hipMemset(h->d_scn_world, 0xFF, sizeof(int) * (size_t)W));
+        HIPCHK(hipMemset(h->d_scn_mark, 0xFF, sizeof(unsigned long long) * (size_t)W));
+    }
+    RTRY(launch_pool_fill(h, c));  // (the next chain waits for this fill in front of its k_respawn, whatever fill_due says)
     h->fill_due = 0;
     h->sd_ready = true;
     return 0;
@@ -3377,9 +3611,7 @@ static int autoreset_device_chain(imgenv* h, const float* actions, hipStream_t s
     if (fill) {
         HIPCHK(hipEventRecord(h->ev_consumed, st));
         HIPCHK(hipStreamWaitEvent(h->side3, h->ev_consumed, 0));
-        k_spawn_fill<<<dim3(c.S), dim3(WAVE), 0, h->side3>>>(c);
-        HIPCHK(hipEventRecord(h->ev_fill, h->side3));
-        h->fill_pending = true;
+        RTRY(launch_pool_fill(h, c));
         h->fill_due = SPAWN_FILL_PERIOD;
     }
     h->fill_due -= 1;
@@ -3432,6 +3664,9 @@ extern "C" int imgenv_step_autoreset_device(imgenv_t* h, const float* actions, c
         if (int rc = sfm_ahead_drop(h, st)) return rc;
         h->sfm_ahead = false;
     }
+    if (h->scn_policy != IMGENV_SCENARIOS_OFF && (cfg->n_robots != h->Rw || cfg->n_peds != h->Pw || cfg->n_obstacles != h->scn_obst))
+        FAIL(IMGENV_EINVAL, "imgenv_step_autoreset_device: the spawn cfg has %d robots / %d pedestrians / %d obstacles, the scenario bank %d / %d / %d",
+             cfg->n_robots, cfg->n_peds, cfg->n_obstacles, h->Rw, h->Pw, h->scn_obst);
     const uint64_t fp = spawn_cfg_fingerprint(*cfg);
     if (!h->sd_ready || fp != h->sd_fp) {  // the first call fixes seed0: the k-th world reset from now on takes placement seed0 + k
         if (int rc = spawn_device_setup(h, cfg, seed0, st)) return rc;

@@ -18,9 +18,8 @@
 // imgenv_spawn_slot() reads a placement back for checkers.
 #pragma once
 
-#define SPAWN_MAX_AGENTS 256  // robots + pedestrians of one world (the distance tests take them 64 at a time)
-#define SPAWN_MAX_OBST 24     // obstacles of one world
-#define SPAWN_BSP_CAP 256     // RVO obstacle vertices of one world, splits included
+#include "spawn_slot.h"  // SPAWN_MAX_AGENTS, SPAWN_MAX_OBST, SPAWN_BSP_CAP, SlotAgent, SlotObstacle (plain C++: the scenario bank's host half shares them)
+
 #define SPAWN_LIST_CAP 6144   // arena of the BSP's per-node vertex lists
 #define SPAWN_GUARD 200000    // draws before a placement is given up (the host gives up after 2e7: a kernel must not spin that long)
 #define SPAWN_FILL_PERIOD 2    // the pool is refilled on every second call; it holds 4 W placements: a refill sees the count of
@@ -36,16 +35,6 @@ struct DevSpawnObstacle {
     int shape, pose_type;
     double size_range[4];
     double pose[6];
-};
-struct SlotAgent {  // a robot or a pedestrian as ResetEnv.srv carries it
-    double x, y, qz, qw, gx, gy;
-    double traj[2][3];
-    int traj_len, pad;
-};
-struct SlotObstacle {
-    double x, y, qz, qw;
-    float size[4];
-    int shape, pad;
 };
 struct SpawnDev {
     int n_robots, n_peds, n_obstacles, go_back, ignore_obstacle, rvo;  // rvo: the world has RVO agents (obstacle polygons + BSP wanted)
@@ -492,25 +481,11 @@ __device__ int sp_rvo_build(SpawnScratch& L) {
     return ret;
 }
 
-// One pool slot: placement number n = the smallest n >= consumed with n % S == slot, unless the slot holds it already.
-// "consumed" is the count BEFORE the worlds of the last completed step took theirs (consumed[1]): this kernel runs beside a
-// step on its own stream, and with the up-to-date count it could recycle a slot whose placement that very step's k_respawn has
-// been handed (k_finished_dev advances consumed[0] before k_respawn reads the slots) -- one step's worth of placements is
-// redrawn into slots that are not read any more, which the pool's size allows for (SPAWN_FILL_PERIOD).
-__global__ __launch_bounds__(WAVE) void k_spawn_fill(SpawnDev c) {
-    __shared__ SpawnScratch L;
-    const int s = blockIdx.x;
-    const unsigned long long done = c.consumed[1];
-    const unsigned long long S = (unsigned long long)c.S;
-    unsigned long long n = done - done % S + (unsigned long long)s;
-    if (n < done) n += S;
-    if (c.slot_serial[s] == n) return;
-    // one wavefront in lockstep: rejection sampling and the BSP's partition are sequential, their distance tests and pair
-    // evaluations use the lanes (every lane computes and writes the same values otherwise)
-    const int na = c.n_robots + c.n_peds;
-    SlotAgent* ag = c.s_agents + (size_t)s * na;
-    SlotObstacle* ob = c.s_obst + (size_t)s * (c.n_obstacles > 0 ? c.n_obstacles : 1);
-    L.status = dev_spawn_world(c, c.seed0 + n, L, ag, ob);
+// What a filled slot holds beyond the placement itself, derived from its obstacles `ob` (L.status says whether there is a placement):
+// the obstacle instances for k_reset_obstacles, the pedscene segments, RVO2's obstacle list + BSP, the capacity checks; then the
+// slot is published under its serial.  One function for every fill -- the sampler's (k_spawn_fill) and the scenario bank's
+// (csrc/scenario_bank.h: k_scenario_fill) -- so that the two cannot drift apart.  The whole wavefront, uniform control flow.
+__device__ __forceinline__ void sp_slot_finish(const SpawnDev& c, SpawnScratch& L, int s, unsigned long long n, const SlotObstacle* ob) {
     L.n_ob = 0;
     L.n_nodes = 0;
     int root = -1;
@@ -570,6 +545,28 @@ __global__ __launch_bounds__(WAVE) void k_spawn_fill(SpawnDev c) {
     c.slot_status[s] = L.status;
     __threadfence();
     c.slot_serial[s] = n;
+}
+
+// One pool slot: placement number n = the smallest n >= consumed with n % S == slot, unless the slot holds it already.
+// "consumed" is the count BEFORE the worlds of the last completed step took theirs (consumed[1]): this kernel runs beside a
+// step on its own stream, and with the up-to-date count it could recycle a slot whose placement that very step's k_respawn has
+// been handed (k_finished_dev advances consumed[0] before k_respawn reads the slots) -- one step's worth of placements is
+// redrawn into slots that are not read any more, which the pool's size allows for (SPAWN_FILL_PERIOD).
+__global__ __launch_bounds__(WAVE) void k_spawn_fill(SpawnDev c) {
+    __shared__ SpawnScratch L;
+    const int s = blockIdx.x;
+    const unsigned long long done = c.consumed[1];
+    const unsigned long long S = (unsigned long long)c.S;
+    unsigned long long n = done - done % S + (unsigned long long)s;
+    if (n < done) n += S;
+    if (c.slot_serial[s] == n) return;
+    // one wavefront in lockstep: rejection sampling and the BSP's partition are sequential, their distance tests and pair
+    // evaluations use the lanes (every lane computes and writes the same values otherwise)
+    const int na = c.n_robots + c.n_peds;
+    SlotAgent* ag = c.s_agents + (size_t)s * na;
+    SlotObstacle* ob = c.s_obst + (size_t)s * (c.n_obstacles > 0 ? c.n_obstacles : 1);
+    L.status = dev_spawn_world(c, c.seed0 + n, L, ag, ob);
+    sp_slot_finish(c, L, s, n, ob);
 }
 
 // The worlds whose robots are all done, ascending, and their count, in device memory (and, for a host that wants to know, in the

@@ -168,3 +168,10 @@ def native_spawn(cfg, seed, spawn_cfg=None):
     if rc != 0:
         raise RuntimeError("imgenv_spawn failed (%d): %s" % (rc, lib.imgenv_last_error().decode()))
     return ResetLayout(ignore_obstacle=bool(c.ignore_obstacle), **out)
+
+
+def record_scenarios(cfg, n, seed):
+    """The analogue of the reference's ``save_envs_bag``: ``n`` recorded episodes, placement ``k`` from ``native_spawn(cfg, seed + k)``,
+    as a list of ``ResetLayout`` -- what ``World.scenarios_add`` / ``VecImageEnv(scenarios=...)`` take (no device needed)."""
+    spawn_cfg = make_spawn_cfg(cfg)
+    return [native_spawn(cfg, int(seed) + k, spawn_cfg) for k in range(int(n))]

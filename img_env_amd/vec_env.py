@@ -39,7 +39,7 @@ class VecImageEnv:
 
     def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False,
                  map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3, wrappers=False,
-                 ped_tracks=None, tracks_policy="keep", tracks_repeat=1, info_track_sets=False):
+                 ped_tracks=None, tracks_policy="keep", tracks_repeat=1, info_track_sets=False, scenarios=None, scenario_policy="queue"):
         import torch
         from .world import World
         self.cfg = cfg
@@ -54,6 +54,10 @@ class VecImageEnv:
             raise ValueError("ped_tracks needs ped_sim.type: dataset")
         if tracks_policy not in _cabi.TRACK_POLICIES:
             raise ValueError("tracks_policy: keep | placement | cycle")
+        if scenarios is not None and scenario_policy not in ("queue", "placement"):
+            raise ValueError("scenario_policy: queue | placement")
+        if scenarios is not None and auto_reset and not device_reset:
+            raise ValueError("scenarios need device_reset=True or auto_reset=False (the host-side auto-reset keeps sampling)")
         if isinstance(ped_tracks, str):
             if ped_tracks != "yaml":
                 raise ValueError('ped_tracks: a list of sets or "yaml"')
@@ -116,6 +120,16 @@ class VecImageEnv:
         elif tracks_policy != "keep" or self.info_track_sets:
             raise ValueError("tracks_policy / info_track_sets need ped_tracks")
         self.n_track_sets = self.world.n_track_sets
+        # scenarios: a fixed list of recorded episodes (the reference's cfg_type: bag, yaml_env.py:223-244) as a bank inside the
+        # handle (imgenv_scenarios_add) -- a list of layouts, e.g. spawn.record_scenarios(cfg, n, seed).  reset() gives env k episode
+        # k % N; with device_reset=True the device-side reset then continues the queue (scenario_policy "queue": the k-th env reset
+        # from then on replays episode (env_num + k) % N) or draws an episode with every placement ("placement").  With
+        # auto_reset=False the caller chooses: reset_envs(envs, scenario_ids=...).  None: nothing changes.
+        self.n_scenarios = 0
+        self.scenario_policy = scenario_policy
+        if scenarios is not None:
+            self.world.scenarios_add(scenarios)
+            self.n_scenarios = self.world.n_scenarios
         # stack: StateBatchWrapper (base.py:97-150) inside the library, per env (imgenv_stack_enable): every state handed out
         # carries each robot's last cfg["image_batch"] sensor maps, cfg["state_batch"] vector states and
         # max(cfg["laser_batch"], 1) laser scans of its env's current episode, zero-padded after the env's reset -- whoever reset it,
@@ -210,6 +224,11 @@ class VecImageEnv:
 
     def reset(self, layouts=None):
         """every env starts a new episode (ImageEnv.reset per env, yaml_env.py:296-317)"""
+        if layouts is None and self.n_scenarios:  # env k replays episode k % N; the device continues the queue from env_num on
+            self.world.reset_worlds_scenarios(range(self.env_num), [k % self.n_scenarios for k in range(self.env_num)])
+            if self.device_reset:
+                self.world.scenarios_policy(self.scenario_policy, first=self.env_num)
+            return self._state()
         if layouts is None and self.native_spawn:
             return self.reset_envs(range(self.env_num))
         if layouts is None:
@@ -217,8 +236,13 @@ class VecImageEnv:
         self.world.reset(list(layouts))
         return self._state()
 
-    def reset_envs(self, envs, layouts=None):
+    def reset_envs(self, envs, layouts=None, scenario_ids=None):
         envs = [int(k) for k in envs]
+        if scenario_ids is not None:  # env envs[q] starts the bank's episode scenario_ids[q]
+            if layouts is not None or not self.n_scenarios:
+                raise ValueError("scenario_ids need a VecImageEnv made with scenarios, and no layouts beside them")
+            self.world.reset_worlds_scenarios(envs, scenario_ids)
+            return self._state()
         if layouts is None and self.native_spawn:
             seeds = [self._spawn_seed + self._episodes + q for q in range(len(envs))]
             self._episodes += len(envs)
@@ -297,6 +321,11 @@ class VecImageEnv:
         """the track set each env's current episode replays, -1 where its reset brought its own (numpy int32 ``[env_num]``);
         synchronises the stream"""
         return self.world.world_tracks()
+
+    def world_scenarios(self):
+        """the recorded episode each env's current episode replays, -1 where its reset did not come from the bank (numpy int32
+        ``[env_num]``); synchronises the stream"""
+        return self.world.world_scenarios()
 
     def set_world_tracks(self, envs, ids):
         """env ``envs[q]`` replays set ``ids[q]`` from its next bank-fed reset on (tracks_policy "keep")"""

@@ -125,6 +125,53 @@ class World:
         self._maps_buf = None
         self.n_track_sets = 0  # tracks_add()
         self._tracks_buf = None
+        self.n_scenarios = 0  # scenarios_add()
+        self.scenario_obstacles = 0
+        self._scenarios_buf = None
+
+    def scenarios_add(self, layouts):
+        """``imgenv_scenarios_add``: the handle's bank of recorded episodes (the reference's ``cfg_type: bag``), once, before the
+        first ``step_autoreset_device``.  ``layouts``: a list of the layout objects ``spawn.native_spawn`` / ``EnvPos.reset`` /
+        ``spawn.record_scenarios`` return, all of one cast (this handle's robots and pedestrians per world, the first episode's
+        number of obstacles).  ValueError for refused input, RuntimeError for a call out of order."""
+        layouts = list(layouts)
+        if not layouts:
+            raise ValueError("no scenarios")
+        first = layouts[0]
+        shape = first["obs_shape"] if isinstance(first, dict) else first.obs_shape
+        R, P, O = self.n_robots // self.n_worlds, self.n_peds // self.n_worlds, int(len(shape))
+        arrays = _cabi.pack_scenarios(layouts, R, P, O)
+        rc = self.lib.imgenv_scenarios_add(self.h, len(layouts), O, *[a.ctypes.data for a in arrays.values()])
+        self._call(rc, "imgenv_scenarios_add")
+        self.n_scenarios, self.scenario_obstacles = len(layouts), O
+
+    def scenarios_policy(self, name, first=0):
+        """``imgenv_scenarios_policy``: what fills the device-side reset's pool from now on -- "off" (the sampler), "queue" (placement
+        number k replays scenario ``(first + k) % n_scenarios``) or "placement" (``_cabi.scenario_for_placement`` of the placement's
+        seed).  Ordered on the current stream, no synchronisation; the first reset behind the call already obeys it."""
+        if name not in _cabi.SCENARIO_POLICIES:
+            raise ValueError("scenario policy: off | queue | placement")
+        self._call(self.lib.imgenv_scenarios_policy(self.h, _cabi.SCENARIO_POLICIES[name], C.c_uint64(int(first) & 0xFFFFFFFFFFFFFFFF),
+                                                    self._stream()), "imgenv_scenarios_policy")
+
+    def reset_worlds_scenarios(self, worlds, ids):
+        """``imgenv_reset_worlds_scenarios``: world ``worlds[q]`` starts the bank's episode ``ids[q]`` (a host-side reset; the device's
+        placement count does not move).  ValueError for an id or a world out of range."""
+        worlds, ids = [int(k) for k in worlds], [int(k) for k in ids]
+        if len(worlds) != len(ids):
+            raise ValueError("one scenario id per world")
+        n = len(worlds)
+        self._call(self.lib.imgenv_reset_worlds_scenarios(self.h, n, (C.c_int32 * max(n, 1))(*worlds), (C.c_int32 * max(n, 1))(*ids),
+                                                          self._stream()), "imgenv_reset_worlds_scenarios")
+        return self.out
+
+    def world_scenarios(self):
+        """``imgenv_world_scenarios``: the scenario each world's current episode came from, -1 where its reset did not come from the
+        bank (numpy int32 ``[n_worlds]``); synchronises the stream"""
+        if self._scenarios_buf is None:
+            self._scenarios_buf = (C.c_int32 * self.n_worlds)()
+        self._check(self.lib.imgenv_world_scenarios(self.h, self._scenarios_buf, self._stream()), "imgenv_world_scenarios")
+        return np.array(self._scenarios_buf[:], np.int32)
 
     def tracks_add(self, sets):
         """``imgenv_tracks_add``: the handle's bank of recorded crowds (dataset scene), once, before the first reset.  ``sets``: a list

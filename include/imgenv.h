@@ -763,6 +763,63 @@ int32_t imgenv_tracks_for_placement(uint64_t seed, int32_t n_sets);
  * before its first reset, and all of them without a bank).  Synchronises `stream`, like imgenv_world_maps(). */
 int imgenv_world_tracks(imgenv_t* h, int32_t* set_ids, void* stream);
 
+/* ---- scenario bank: recorded episodes in one handle, replayed by the device-side reset ----
+ * The reference has two sources for an episode's placement (envs/env/yaml_env.py:223-244): `cfg_type: yaml` draws a fresh one
+ * (EnvPos.reset; here imgenv_spawn and the device-side sampler), `cfg_type: bag` replays the recorded ResetEnv requests of a file
+ * written by save_envs_bag, the k-th reset taking request reset_index % len(reset_reqs) -- how a fixed test set is run: the same
+ * N episodes for every policy and checkpoint.  Here the recorded episodes form a bank inside the handle.  The device-side reset
+ * never samples where it hands a placement out: it copies placement number n out of a pool slot filled ahead from that number
+ * alone, and with a policy other than OFF the fill copies a scenario of the bank instead of sampling (k_scenario_fill,
+ * csrc/scenario_bank.h) and derives the same data from it (obstacle instances, RVO polygons + BSP, pedscene segments).  Every
+ * kernel behind the pool is what it was.
+ *
+ * imgenv_scenarios_add: legal once per handle, before the first imgenv_step_autoreset_device (IMGENV_ESTATE on a second call).
+ * n episodes in imgenv_spawn()'s array layout with a leading [n] axis, HOST memory, copied during the call; Rw = n_robots /
+ * n_worlds, Pw = n_peds / n_worlds, O = n_obstacles:
+ *   robot_pose [n][Rw][4], robot_goal [n][Rw][2], ped_pose [n][Pw][4], ped_goal [n][Pw][2], ped_traj [n][Pw][2][3],
+ *   ped_traj_len [n][Pw], obs_shape [n][O], obs_size [n][O][4], obs_pose [n][O][4]
+ * (pedestrian arrays may be NULL with Pw == 0, obstacle arrays with O == 0).  IMGENV_EINVAL with a message that names the scenario:
+ * a value that is not finite, a zero quaternion, a ped_traj_len outside 0..2, a shape that is neither circle nor rectangle, an
+ * empty or oversized obstacle footprint, Rw + Pw > 256 or O > 24 (the device-side reset's limits), n < 1, a robot shard, and -- on
+ * handles with RVO agents -- a scenario whose obstacle polygons and their BSP do not fit a pool slot.
+ * Limits: a trajectory of at most 2 points per pedestrian (what a slot holds and what EnvPos produces); one cast per bank;
+ * a scenario carries no map id -- with a map bank the caller keeps the worlds on the map the episodes were recorded on
+ * (IMGENV_MAPS_KEEP); a dataset handle's recorded crowds still come from the track bank, over the scenario's pedestrians. */
+int imgenv_scenarios_add(imgenv_t* h, int32_t n, int32_t n_obstacles, const double* robot_pose, const double* robot_goal,
+                         const double* ped_pose, const double* ped_goal, const double* ped_traj, const int32_t* ped_traj_len,
+                         const int32_t* obs_shape, const float* obs_size, const double* obs_pose);
+/* What fills the pool of imgenv_step_autoreset_device from now on.
+ *   IMGENV_SCENARIOS_OFF (the default): the sampler, exactly as on a handle without a bank.
+ *   IMGENV_SCENARIOS_QUEUE: placement number k (the k-th world the device resets, counted over the whole handle) replays
+ *     scenario (first + k) % n -- the reference's reset_index % len(reset_reqs), shared by the handle's worlds: one pass of n
+ *     resets runs every scenario once.
+ *   IMGENV_SCENARIOS_BY_PLACEMENT: a draw from the placement's seed, imgenv_scenario_for_placement.
+ * May be called between any two calls: the pool's slots, drawn under the old policy, are invalidated on `stream` and the next
+ * imgenv_step_autoreset_device refills them before it hands any out -- the first reset behind the call obeys the new policy.
+ * No host synchronisation.  imgenv_step_autoreset_device then refuses (IMGENV_EINVAL) a spawn cfg whose n_robots / n_peds /
+ * n_obstacles differ from the bank's; the cfg is still needed for the counts and the fingerprint, nothing else about the call
+ * changes.  imgenv_step_autoreset, the HOST-side auto-reset, keeps sampling and ignores the bank.
+ * IMGENV_ESTATE without a bank (also for OFF), IMGENV_EINVAL for an unknown policy. */
+#define IMGENV_SCENARIOS_OFF 0
+#define IMGENV_SCENARIOS_QUEUE 1
+#define IMGENV_SCENARIOS_BY_PLACEMENT 2
+int imgenv_scenarios_policy(imgenv_t* h, int32_t policy, uint64_t first, void* stream);
+/* The scenario placement number n takes: QUEUE (first + n) % n_scenarios, the sum modulo 2^64; BY_PLACEMENT
+ * imgenv_map_for_placement(seed0 + n + 0x3C6EF372FE94F82B, n_scenarios) -- the salt (the fractional bits of sqrt 5) is distinct
+ * from the track bank's, so the three banks' draws of one seed are not tied.  -1 under OFF or with n_scenarios < 1.  A pure
+ * function, needs no device; one definition (csrc/scenario_bank.h) compiled for host and device. */
+int32_t imgenv_scenario_for_placement(int32_t policy, uint64_t seed0, uint64_t first, uint64_t n, int32_t n_scenarios);
+/* imgenv_reset_worlds() with the bank's episode ids[q] for world worlds[q]: the first reset, and callers that choose by hand.
+ * Host code only -- the batches are built from the bank's host copy and go through imgenv_reset_worlds (ped_traj_v is NULL, so a
+ * dataset handle with a track bank takes its crowd from that bank); the device's placement count does not advance.  A
+ * pedestrian recorded with ped_traj_len 0 is refused here as any reset batch refuses it.  IMGENV_EINVAL for an id out of range,
+ * IMGENV_ESTATE without a bank. */
+int imgenv_reset_worlds_scenarios(imgenv_t* h, int32_t n, const int32_t* worlds, const int32_t* ids, void* stream);
+/* ids[n_worlds]: the scenario each world's CURRENT episode came from, -1 where its reset did not come from the bank (the sampler,
+ * an explicit batch, a host spawn; every world before its first reset, all of them without a bank).  Synchronises `stream`.  After
+ * the pool has been rebuilt for another spawn cfg the worlds report -1 until their next reset. */
+int imgenv_world_scenarios(imgenv_t* h, int32_t* ids, void* stream);
+
 /* The two OpenCV resizes of the path for one-channel 8-bit images, as the library performs them (OpenCV 4.2.0's generic
  * fixed-point CPU path restated, csrc/cv_resize.h): host buffers, no device needed.  kind 0: INTER_LINEAR, 1: INTER_CUBIC. */
 int imgenv_cv_resize_u8(int kind, const uint8_t* src, int32_t sh, int32_t sw, uint8_t* dst, int32_t dh, int32_t dw);

@@ -19,7 +19,13 @@ with nothing enabled / library / torch over several rounds, for the table and fo
 
 --tracks-compare (with --peds 10) runs the dataset pedestrian scene -- recorded crowds of --records records per pedestrian --
 three ways, alternating over several rounds: a Python loop that reads all_down and uploads the finished envs' tracks in explicit
-batches (what a handle without a track bank can do), native_spawn with the bank (imgenv_tracks_add) and device_reset with it."""
+batches (what a handle without a track bank can do), native_spawn with the bank (imgenv_tracks_add) and device_reset with it.
+
+--scenarios-compare runs a fixed list of --scenarios recorded episodes (the reference's cfg_type: bag): "python_loop" (imgenv_step, a
+host read of all_down, reset_worlds with layouts from the list -- the only way without a scenario bank), "scenarios"
+(device_reset=True, scenarios=...), "sampler" (device_reset=True drawing fresh placements) and, with --parent-tree DIR, "parent"
+(the sampler variant with img_env_amd imported from another, built checkout: the commit before the bank).  Every variant of every
+round is a process of its own (--scenarios-variant), alternating."""
 import argparse
 import json
 import os
@@ -27,6 +33,8 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--tree" in sys.argv[1:-1]:  # (its value follows it) import img_env_amd from another checkout (A/B against another commit, same tool)
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--tree") + 1])
 sys.path.insert(0, ROOT)
 
 
@@ -457,6 +465,95 @@ def compare_tracks(args, rounds=3):
                 time_max=args.time_max, rounds=rounds, runs=runs, summary=summary)
 
 
+def measure_scenarios(variant, envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n_scenarios=500):
+    """us per VecImageEnv.step of an RVO VecImageEnv that never stops, over a fixed list of recorded episodes ("python_loop",
+    "scenarios") or over fresh placements ("sampler"; also what another checkout is asked for)"""
+    import torch
+    from img_env_amd import spawn, worldgen
+    from img_env_amd.vec_env import VecImageEnv
+    grid = worldgen.make_grid(200, 2)
+    cfg = worldgen.make_yaml_cfg(robots, peds, grid, time_max=time_max, n_obstacles=obstacles, seed=5)
+    loop, banked = variant == "python_loop", variant == "scenarios"
+    bank = None
+    if loop or banked:
+        spawn_cfg = spawn.make_spawn_cfg(cfg)
+        bank = [spawn.native_spawn(cfg, 1000 + k, spawn_cfg) for k in range(n_scenarios)]
+    if banked:
+        env = VecImageEnv(cfg, env_num=envs, seed=5, device_reset=True, scenarios=bank)
+    elif loop:
+        env = VecImageEnv(cfg, env_num=envs, seed=5, auto_reset=False)
+    else:
+        env = VecImageEnv(cfg, env_num=envs, seed=5, device_reset=True)
+    n = len(env)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    acts = torch.zeros(16, n, 3, device="cuda")
+    acts[:, :, 0] = torch.rand(16, n, generator=g, device="cuda") * 0.6
+    acts[:, :, 1] = torch.rand(16, n, generator=g, device="cuda") * 1.8 - 0.9
+    state = dict(next=0, resets=0)
+
+    def from_list(count):  # the queue: reset_index % len(reset_reqs)
+        lays = [bank[(state["next"] + q) % n_scenarios] for q in range(count)]
+        state["next"] += count
+        return lays
+
+    def step(a):
+        if not loop:
+            env.step(a)
+            return
+        o = env.world.step(a)
+        down = (o["dones"].view(envs, robots) > 0).all(dim=1)
+        finished = torch.nonzero(down).flatten().tolist()  # the host read in front of every reset
+        if finished:
+            env.reset_envs(finished, from_list(len(finished)))
+            state["resets"] += len(finished)
+    if loop:
+        env.reset(from_list(envs))
+    else:
+        env.reset()
+    for s in range(time_max + 20):  # the drift phase: past the first wave of time limits
+        step(acts[s % 16])
+    torch.cuda.synchronize()
+    placed0 = 0
+    if not loop:
+        worlds, first = env.world.autoreset_last()
+        placed0 = first + len(worlds)
+    state["resets"], t0 = 0, time.perf_counter()
+    for s in range(steps):
+        step(acts[s % 16])
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if not loop:
+        worlds, first = env.world.autoreset_last()
+        state["resets"] = first + len(worlds) - placed0
+    env.close()
+    return dict(us_per_step=1e6 * dt / steps, env_resets_per_step=state["resets"] / steps)
+
+
+def compare_scenarios(args, rounds=3):
+    """python_loop / scenarios / sampler (/ parent), alternating, `rounds` times; one process per measurement"""
+    import subprocess
+    variants = ["python_loop", "scenarios", "sampler"] + (["parent"] if args.parent_tree else [])
+    base = [sys.executable, os.path.abspath(__file__), "--envs", str(args.envs), "--robots", str(args.robots), "--peds", str(args.peds),
+            "--obstacles", str(args.obstacles), "--steps", str(args.steps), "--time-max", str(args.time_max), "--scenarios", str(args.scenarios)]
+    runs = []
+    for rnd in range(rounds):
+        for variant in variants:
+            cmd = base + ["--scenarios-variant", "sampler" if variant == "parent" else variant]
+            if variant == "parent":
+                cmd += ["--tree", args.parent_tree]
+            out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            if out.returncode != 0:
+                raise RuntimeError("%s: exit %d\n%s" % (" ".join(cmd), out.returncode, out.stderr[-2000:]))
+            runs.append(dict(round=rnd, variant=variant, **json.loads(out.stdout.strip().splitlines()[-1])))
+            print(json.dumps(runs[-1]), flush=True)
+    summary = {}
+    for variant in variants:
+        v = [r["us_per_step"] for r in runs if r["variant"] == variant]
+        summary[variant] = dict(us_per_step_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
+    return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, scenarios=args.scenarios, steps=args.steps,
+                time_max=args.time_max, rounds=rounds, runs=runs, summary=summary)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
@@ -482,9 +579,27 @@ def main():
                     help="dataset scene: explicit track batches from a Python loop / native_spawn with a track bank / device_reset with "
                          "it, alternating over --rounds rounds (use --peds 10)")
     ap.add_argument("--records", type=int, default=50, help="--tracks-compare: records per recorded pedestrian")
+    ap.add_argument("--scenarios-compare", action="store_true",
+                    help="a fixed list of recorded episodes: a Python loop with reset_worlds / device_reset with the scenario bank / "
+                         "device_reset with the sampler (/ the sampler of --parent-tree), alternating over --rounds rounds")
+    ap.add_argument("--scenarios", type=int, default=500, help="--scenarios-compare: recorded episodes in the list")
+    ap.add_argument("--scenarios-variant", default=None, choices=("python_loop", "scenarios", "sampler"), help="one measurement of --scenarios-compare")
+    ap.add_argument("--parent-tree", default=None, help="--scenarios-compare: a built checkout of another commit, measured as variant \"parent\"")
+    ap.add_argument("--tree", default=None, help="import img_env_amd from this checkout instead of the tool's own")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None, help="--stack-compare / --episodes-compare: also write the JSON here")
     args = ap.parse_args()
+    if args.scenarios_variant:
+        print(json.dumps(measure_scenarios(args.scenarios_variant, args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max,
+                                           args.scenarios)))
+        return
+    if args.scenarios_compare:
+        res = compare_scenarios(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
+        return
     if args.tracks_compare:
         res = compare_tracks(args, args.rounds)
         if args.out:

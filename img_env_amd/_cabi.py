@@ -176,6 +176,43 @@ def make_episodes_cfg(min_steps, dt):
     return c
 
 
+EPLOG_MAX_CAPACITY, EPLOG_I32, EPLOG_F64, EPLOG_SCN_DEVICE = 1 << 22, 10, 9, -2
+#: rows of imgenv_episode_log_out.i32 and .f64
+EPLOG_I32_NAMES = ("robot", "world", "code", "steps", "len", "counted", "episode", "map", "tracks", "scenario_raw")
+EPLOG_F64_NAMES = ("ep_return",) + EP_FIGURE_NAMES
+#: imgenv_episode_log_out's arrays: name -> (numpy dtype, rows: 0 = [capacity], k = [k][capacity], -1 = [1]).  The two uint64 arrays
+#: are viewed as int64 (torch has no arithmetic on uint64): a placement of ~0, "none", reads -1.
+EPISODE_LOG_ARRAYS = {"n_written": (np.int64, -1), "i32": (np.int32, EPLOG_I32), "f64": (np.float64, EPLOG_F64), "placement": (np.int64, 0)}
+
+
+class EpisodeLogCfg(C.Structure):
+    _fields_ = [("struct_size", _i32), ("capacity", _i32)]
+
+
+class EpisodeLogOut(C.Structure):
+    _fields_ = [("struct_size", _i32), ("capacity", _i32)] + [(name, C.c_void_p) for name in EPISODE_LOG_ARRAYS]
+
+
+class EpisodeRecord(C.Structure):
+    """``imgenv_episode_record``: 128 bytes"""
+    _fields_ = ([("seq", C.c_uint64), ("placement", C.c_uint64)] +
+                [(k, _i32) for k in ("robot", "world", "code", "steps", "len", "counted", "episode", "map", "tracks", "scenario")] +
+                [("ep_return", _f64), ("figures", _f64 * EP_FIGURES)])
+
+
+#: ``EpisodeRecord`` as a numpy record dtype (the same 128 bytes)
+EPISODE_RECORD_DTYPE = np.dtype([("seq", np.uint64), ("placement", np.uint64)] +
+                                [(k, np.int32) for k in ("robot", "world", "code", "steps", "len", "counted", "episode", "map", "tracks", "scenario")] +
+                                [("ep_return", np.float64), ("figures", np.float64, (EP_FIGURES,))])
+
+
+def make_episode_log_cfg(capacity):
+    c = EpisodeLogCfg()
+    c.struct_size = C.sizeof(EpisodeLogCfg)
+    c.capacity = int(capacity)
+    return c
+
+
 ACTIONS_TABLE, ACTIONS_CLIP, ACTIONS_MAX_TABLE = 0, 1, 4096
 RAW_I32, RAW_I64, RAW_F32, RAW_F64 = 0, 1, 2, 3  # ``dtype`` of imgenv_actions_decode
 RAW_DTYPES = {np.dtype(np.int32): RAW_I32, np.dtype(np.int64): RAW_I64, np.dtype(np.float32): RAW_F32, np.dtype(np.float64): RAW_F64}
@@ -389,6 +426,7 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_world_placement", "imgenv_cv_resize_u8", "imgenv_build_id", "imgenv_step_flags", "imgenv_layer_mode",
            "imgenv_stack_bytes", "imgenv_stack_enable", "imgenv_stack_outputs",
            "imgenv_episodes_enable", "imgenv_episodes_outputs", "imgenv_episodes_clear",
+           "imgenv_episode_log_enable", "imgenv_episode_log_outputs", "imgenv_episode_log_read",
            "imgenv_actions_enable", "imgenv_actions_outputs", "imgenv_actions_decode", "imgenv_obs_post_enable", "imgenv_obs_post_outputs",
            "imgenv_maps_add", "imgenv_world_maps_set", "imgenv_maps_policy", "imgenv_map_for_placement", "imgenv_world_maps",
            "imgenv_tracks_add", "imgenv_world_tracks_set", "imgenv_tracks_policy", "imgenv_tracks_for_placement", "imgenv_world_tracks",
@@ -447,6 +485,10 @@ def bind(lib):
     lib.imgenv_episodes_enable.argtypes = [C.c_void_p, C.POINTER(EpisodesCfg), C.POINTER(EpisodesOut)]
     lib.imgenv_episodes_outputs.argtypes = [C.c_void_p, C.POINTER(EpisodesOut)]
     lib.imgenv_episodes_clear.argtypes = [C.c_void_p, C.c_void_p]
+    lib.imgenv_episode_log_enable.argtypes = [C.c_void_p, C.POINTER(EpisodeLogCfg), C.POINTER(EpisodeLogOut)]
+    lib.imgenv_episode_log_outputs.argtypes = [C.c_void_p, C.POINTER(EpisodeLogOut)]
+    lib.imgenv_episode_log_read.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    lib.imgenv_episode_log_read.restype = C.c_int64
     lib.imgenv_actions_enable.argtypes = [C.c_void_p, C.POINTER(ActionsCfg), C.POINTER(ActionsOut)]
     lib.imgenv_actions_outputs.argtypes = [C.c_void_p, C.POINTER(ActionsOut)]
     lib.imgenv_actions_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]

@@ -16,11 +16,20 @@
 //
 // State per robot: 27 float64 + 18 int32 = 288 bytes.  A step reads and writes the 15 + 2 rows of the open episode and the two
 // running totals (152 bytes each way, + 17 bytes of inputs), a fold of a counted episode nearly all of it.
+//
+// The per-robot rules below compile as plain C++ as well (EP_HD), for tests/host/episode_log_check.cpp; the kernel is HIP only.
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 #include "launch_plan.h"  // EP_BLOCK, EP_MAX_BLOCKS
 #include "tail_rows.h"
+
+#if defined(__HIPCC__)
+#define EP_HD __host__ __device__ __forceinline__
+#else
+#define EP_HD inline
+#endif
 
 // float64 rows: the open episode first (EpisodeStats' members, envs.py:388-396, then the running return) ...
 enum {
@@ -61,10 +70,10 @@ struct EpisodesDev {
     TailRows rows;               // the robots of this launch (fold: those of the reset chain's worlds)
 };
 
-__device__ __forceinline__ double ep_round4(double x) { return rint(x * 1e4) / 1e4; }  // torch.round(x * 1e4) / 1e4
+EP_HD double ep_round4(double x) { return rint(x * 1e4) / 1e4; }  // torch.round(x * 1e4) / 1e4
 
 // EpisodeStats.add (envs.py:398-415) and TestEpisodeWrapper.step (envs.py:466-475) for robot row `r`
-__device__ __forceinline__ void ep_accumulate(const EpisodesDev& e, size_t r) {
+EP_HD void ep_accumulate(const EpisodesDev& e, size_t r) {
     const size_t RL = (size_t)e.rows.RL;
     double* f = e.f + r;
     int32_t* q = e.i + r;
@@ -102,8 +111,24 @@ __device__ __forceinline__ void ep_accumulate(const EpisodesDev& e, size_t r) {
     q[EPI_LEN * RL] += clean ? 1 : 0;
 }
 
-// TestEpisodeWrapper.reset / _count (envs.py:477-500) and EpisodeStats.finish (envs.py:417-431) for robot row `r`
-__device__ __forceinline__ void ep_fold(const EpisodesDev& e, size_t r) {
+// EpisodeStats.finish (envs.py:417-431): the eight figures of the open episode of the robot whose float64 rows start at `f` (stride
+// RL) -- what a fold adds to the robot's figure_sums and what the episode log (episode_log.h) records, from this one function
+EP_HD void ep_figures(const double* f, size_t RL, double fig[8]) {
+    const double n = f[EPF_N * RL];
+    const double n0 = n < 1.0 ? 1.0 : n, n1 = n - 1.0 < 1.0 ? 1.0 : n - 1.0, n2 = n - 2.0 < 1.0 ? 1.0 : n - 2.0;  // clamp(min=1)
+    const double mean_w = f[EPF_SUM_W * RL] / n0;
+    fig[0] = ep_round4(f[EPF_SUM_WW * RL] / n0 - mean_w * mean_w);
+    fig[1] = f[EPF_W_ZERO * RL];
+    fig[2] = ep_round4(f[EPF_ACC_V * RL] / n1);
+    fig[3] = ep_round4(f[EPF_ACC_W * RL] / n1);
+    fig[4] = ep_round4(f[EPF_JERK_V * RL] / n2);
+    fig[5] = ep_round4(f[EPF_JERK_W * RL] / n2);
+    fig[6] = ep_round4(f[EPF_SUM_V * RL] / n0);
+    fig[7] = ep_round4(f[EPF_SUM_ABSW * RL] / n0);
+}
+
+// TestEpisodeWrapper.reset / _count (envs.py:477-500) for robot row `r`
+EP_HD void ep_fold(const EpisodesDev& e, size_t r) {
     const size_t RL = (size_t)e.rows.RL;
     double* f = e.f + r;
     int32_t* q = e.i + r;
@@ -116,19 +141,11 @@ __device__ __forceinline__ void ep_fold(const EpisodesDev& e, size_t r) {
         q[EPI_EPISODES * RL] = episode;
         q[EPI_SPEED_STEPS * RL] += steps;
         q[EPI_ARRIVE_STEPS * RL] += code == 5 ? steps : 0;
-        const double n = f[EPF_N * RL];
-        const double n0 = n < 1.0 ? 1.0 : n, n1 = n - 1.0 < 1.0 ? 1.0 : n - 1.0, n2 = n - 2.0 < 1.0 ? 1.0 : n - 2.0;  // clamp(min=1)
-        const double mean_w = f[EPF_SUM_W * RL] / n0;
         double fig[8];
-        fig[0] = ep_round4(f[EPF_SUM_WW * RL] / n0 - mean_w * mean_w);
-        fig[1] = f[EPF_W_ZERO * RL];
-        fig[2] = ep_round4(f[EPF_ACC_V * RL] / n1);
-        fig[3] = ep_round4(f[EPF_ACC_W * RL] / n1);
-        fig[4] = ep_round4(f[EPF_JERK_V * RL] / n2);
-        fig[5] = ep_round4(f[EPF_JERK_W * RL] / n2);
-        fig[6] = ep_round4(f[EPF_SUM_V * RL] / n0);
-        fig[7] = ep_round4(f[EPF_SUM_ABSW * RL] / n0);
+        ep_figures(f, RL, fig);
+#if defined(__HIPCC__)
 #pragma unroll
+#endif
         for (int k = 0; k < 8; k++) f[(EPF_FIG0 + k) * RL] += fig[k];
         const double ret = f[EPF_RETURN * RL];
         const int len = q[EPI_LEN * RL];
@@ -139,7 +156,9 @@ __device__ __forceinline__ void ep_fold(const EpisodesDev& e, size_t r) {
         q[EPI_LAST_STEPS * RL] = steps;
         q[EPI_LAST_LEN * RL] = len;
         q[EPI_LAST_EPISODE * RL] = episode;
+#if defined(__HIPCC__)
 #pragma unroll
+#endif
         for (int k = 0; k < EPF_PATH_ROWS; k++) f[k * RL] = 0.0;
     } else if (q[EPI_OPEN * RL] != 0) {
         // too short to count (TestEpisodeWrapper.py: `if self.tmp_steps > 3`): its commands ride into the next counted episode
@@ -151,6 +170,7 @@ __device__ __forceinline__ void ep_fold(const EpisodesDev& e, size_t r) {
     q[EPI_OPEN * RL] = 1;
 }
 
+#if defined(__HIPCC__)
 template <bool FOLD>
 __global__ __launch_bounds__(EP_BLOCK) void k_episodes(const EpisodesDev e) {
     // robots of this launch (tail_rows.h; blocks stride over whatever the count turns out to be)
@@ -162,3 +182,4 @@ __global__ __launch_bounds__(EP_BLOCK) void k_episodes(const EpisodesDev e) {
         else ep_accumulate(e, row);
     }
 }
+#endif  // __HIPCC__

@@ -25,6 +25,7 @@
 #include "world.h"
 #include "stack.h"
 #include "episodes.h"
+#include "episode_log.h"
 #include "actions.h"
 #include "obs_post.h"
 #include "map_bank.h"
@@ -227,6 +228,11 @@ struct imgenv {
     imgenv_episodes_out ep_out;
     size_t ep_clear_bytes = 0;   // what imgenv_episodes_clear zeroes, from ep.f on
     const float* ep_actions = nullptr;  // the actions of the step in progress (the caller keeps them until the chain's end)
+    // episode log (include/imgenv.h: imgenv_episode_log_enable; csrc/episode_log.h)
+    bool eplog_on = false;
+    unsigned long long* d_place_serial = nullptr;  // SpawnDev::place_serial of the present pool (valid while sd_ready)
+    EpisodeLogDev eplog;
+    imgenv_episode_log_out eplog_out;
     // action decoding (include/imgenv.h: imgenv_actions_enable; csrc/actions.h)
     bool act_on = false;         // imgenv_actions_enable has been called
     ActionsDev act;
@@ -1797,6 +1803,20 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
         EpisodesDev ed = h->ep;
         ed.actions = h->ep_actions;
         ed.rows = tail_rows(h, is_reset);
+        if (is_reset && h->eplog_on) {
+            // the episode log (episode_log.h), in front of the fold whose state it reads: one record per episode this chain closes,
+            // and the tags of the episodes it opens -- from the words the chain's earlier launches have written (the banks' pointers
+            // are taken here: a bank or the device-side reset's pool may have come, or been rebuilt, after the log was enabled)
+            EpisodeLogDev lg = h->eplog;
+            lg.map_cur = h->d_map_cur;
+            lg.trk_cur = h->d_trk_cur;
+            lg.scn_world = h->d_scn_world;
+            lg.scn_mark = h->d_scn_mark;
+            lg.place_serial = h->sd_ready ? h->d_place_serial : nullptr;
+            const LaunchShape gl = plan_episode_log_launch();
+            k_episode_log<<<dim3(gl.grid), dim3(gl.block), 0, st>>>(ed, lg);
+            h->launches += 1;
+        }
         const LaunchShape g = plan_tail_launch(p, c, 1, EP_BLOCK, EP_MAX_BLOCKS);
         (is_reset ? k_episodes<true> : k_episodes<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(ed);
         h->launches += 1;
@@ -3563,6 +3583,7 @@ static int spawn_device_setup(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t s
     }
     RTRY(launch_pool_fill(h, c));  // (the next chain waits for this fill in front of its k_respawn, whatever fill_due says)
     h->fill_due = 0;
+    h->d_place_serial = c.place_serial;
     h->sd_ready = true;
     return 0;
 }
@@ -3967,6 +3988,126 @@ extern "C" int imgenv_episodes_clear(imgenv_t* h, void* stream) {
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(hipMemsetAsync(h->ep.f, 0, h->ep_clear_bytes, (hipStream_t)stream));
     return IMGENV_OK;
+}
+
+// ---- episode log (include/imgenv.h; the kernel is csrc/episode_log.h) ----
+static_assert(EPL_I32_ROWS == IMGENV_EPLOG_I32 && EPL_F64_ROWS == IMGENV_EPLOG_F64 && EPLOG_SCN_DEVICE == IMGENV_EPLOG_SCN_DEVICE &&
+                  sizeof(imgenv_episode_record) == 128,
+              "episode_log.h rows against include/imgenv.h");
+extern "C" int imgenv_episode_log_enable(imgenv_t* h, const imgenv_episode_log_cfg* c, imgenv_episode_log_out* out) {
+    RTRY(enable_args(c, "imgenv_episode_log_cfg", out, "imgenv_episode_log_out"));
+    if (c->capacity < 1 || c->capacity > IMGENV_EPLOG_MAX_CAPACITY)
+        FAIL(IMGENV_EINVAL, "imgenv_episode_log_cfg.capacity %d: 1 .. %d", c->capacity, IMGENV_EPLOG_MAX_CAPACITY);
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->ep_on) FAIL(IMGENV_ESTATE, "imgenv_episode_log_enable before imgenv_episodes_enable");
+    if (h->eplog_on) {
+        if (c->capacity != h->eplog.capacity)
+            FAIL(IMGENV_EINVAL, "imgenv_episode_log_enable: the handle already keeps a log of capacity %d", h->eplog.capacity);
+        if (out) *out = h->eplog_out;
+        return IMGENV_OK;
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    // one block: the counter, the ring's placement | f64 | i32 columns, then the per-robot tags (placement | i32); the tags start as
+    // "open before the log was" (all bits set: -1 and ~0), the rest zeroed.  Nothing of the handle changes before both fills are done.
+    const size_t C = (size_t)c->capacity, RL = (size_t)h->RL;
+    const size_t ring_bytes = 8 + C * (8 + 8 * EPL_F64_ROWS + 4 * EPL_I32_ROWS), ring_pad = (ring_bytes + 7) & ~(size_t)7;
+    const size_t tag_bytes = RL * (8 + 4 * EPT_ROWS);
+    void* block = nullptr;
+    if (hipMalloc(&block, ring_pad + tag_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        FAIL(IMGENV_ENOMEM, "no device memory for an episode log of %d records", c->capacity);
+    }
+    hipError_t filled = hipMemset(block, 0, ring_pad);
+    if (filled == hipSuccess) filled = hipMemset((unsigned char*)block + ring_pad, 0xFF, tag_bytes);
+    if (filled != hipSuccess) {  // (a device error, not a lack of memory: reported as HIPCHK does, with the block given back)
+        (void)hipFree(block);
+        FAIL(IMGENV_EDEVICE, "imgenv_episode_log_enable: hipMemset: %s (%s:%d)", hipGetErrorString(filled), __FILE__, __LINE__);
+    }
+    h->allocs.push_back(block);
+    unsigned char* b = (unsigned char*)block;
+    EpisodeLogDev g;
+    memset(&g, 0, sizeof(g));
+    g.n_written = (unsigned long long*)b;
+    g.placement = (unsigned long long*)(b + 8);
+    g.f64 = (double*)(b + 8 + 8 * C);
+    g.i32 = (int32_t*)(b + 8 + 8 * C + 8 * EPL_F64_ROWS * C);
+    g.tag_place = (unsigned long long*)(b + ring_pad);
+    g.tags = (int32_t*)(b + ring_pad + 8 * RL);
+    g.capacity = c->capacity;
+    g.W = h->W;
+    h->eplog = g;
+    imgenv_episode_log_out o = {};
+    o.struct_size = (int32_t)sizeof(o);
+    o.capacity = c->capacity;
+    o.n_written = (uint64_t*)g.n_written; o.i32 = g.i32; o.f64 = g.f64; o.placement = (uint64_t*)g.placement;
+    h->eplog_out = o;
+    h->eplog_on = true;
+    if (out) *out = o;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_episode_log_outputs(imgenv_t* h, imgenv_episode_log_out* out) {
+    return feature_outputs(h, &imgenv::eplog_on, &imgenv::eplog_out, out, "imgenv_episode_log_enable");
+}
+
+extern "C" int64_t imgenv_episode_log_read(imgenv_t* h, uint64_t first, int32_t max, imgenv_episode_record* rec, uint64_t* oldest, uint64_t* n_written,
+                                           void* stream) {
+    if (!h || max < 0 || (max > 0 && !rec)) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->eplog_on) FAIL(IMGENV_ESTATE, "imgenv_episode_log_enable was not called");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    if (int rc = check_device_flags(h)) return rc;
+    const EpisodeLogDev& g = h->eplog;
+    const uint64_t C = (uint64_t)g.capacity;
+    unsigned long long n = 0;
+    HIPCHK(hipMemcpy(&n, g.n_written, sizeof(n), hipMemcpyDeviceToHost));
+    const uint64_t old = n > C ? n - C : 0;
+    if (oldest) *oldest = old;
+    if (n_written) *n_written = n;
+    const uint64_t lo = std::max(first, old), want_end = first + (uint64_t)max, hi = want_end < first ? n : std::min<uint64_t>(want_end, n);
+    if (lo >= hi) return 0;
+    const size_t cnt = (size_t)(hi - lo);
+    // the slots of [lo, hi): one or two runs of the ring, column by column
+    std::vector<int32_t> ci(cnt * EPL_I32_ROWS);
+    std::vector<double> cf(cnt * EPL_F64_ROWS);
+    std::vector<unsigned long long> cp(cnt);
+    const size_t s0 = (size_t)(lo % C), run0 = std::min(cnt, (size_t)C - s0), run1 = cnt - run0;
+    auto pull = [&](void* dst, const void* col, size_t elem) -> hipError_t {
+        hipError_t e = hipMemcpy(dst, (const unsigned char*)col + s0 * elem, run0 * elem, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && run1) e = hipMemcpy((unsigned char*)dst + run0 * elem, col, run1 * elem, hipMemcpyDeviceToHost);
+        return e;
+    };
+    for (int k = 0; k < EPL_I32_ROWS; k++) HIPCHK(pull(ci.data() + (size_t)k * cnt, g.i32 + (size_t)k * C, 4));
+    for (int k = 0; k < EPL_F64_ROWS; k++) HIPCHK(pull(cf.data() + (size_t)k * cnt, g.f64 + (size_t)k * C, 8));
+    HIPCHK(pull(cp.data(), g.placement, 8));
+    // the scenario of a device-placed episode: its placement number under the policy of the epoch it falls into (imgenv_world_scenarios)
+    std::vector<unsigned long long> starts(h->scn_epochs.size());
+    uint64_t seed0 = 0;
+    if (h->n_scn > 0) {
+        HIPCHK(hipMemcpy(starts.data(), h->d_scn_starts, sizeof(unsigned long long) * starts.size(), hipMemcpyDeviceToHost));
+        starts[0] = 0;
+        if (h->sd_ready) seed0 = ((SpawnDev*)h->sd_storage)->seed0;
+    }
+    for (size_t q = 0; q < cnt; q++) {
+        imgenv_episode_record& r = rec[q];
+        const int32_t* i = ci.data() + q;
+        r.seq = lo + q;
+        r.placement = cp[q];
+        r.robot = i[EPL_ROBOT * cnt]; r.world = i[EPL_WORLD * cnt]; r.code = i[EPL_CODE * cnt]; r.steps = i[EPL_STEPS * cnt];
+        r.len = i[EPL_LEN * cnt]; r.counted = i[EPL_COUNTED * cnt]; r.episode = i[EPL_EPISODE * cnt]; r.map = i[EPL_MAP * cnt];
+        r.tracks = i[EPL_TRACKS * cnt];
+        int32_t scn = i[EPL_SCENARIO * cnt];
+        if (h->n_scn < 1) scn = -1;
+        else if (scn == IMGENV_EPLOG_SCN_DEVICE) {
+            size_t e = starts.size() - 1;
+            while (e > 0 && starts[e] > cp[q]) e--;
+            scn = scenario_for_placement(h->scn_epochs[e].policy, seed0, h->scn_epochs[e].first, cp[q], h->n_scn);
+        }
+        r.scenario = scn;
+        r.ep_return = cf[EPL_RETURN * cnt + q];
+        for (int k = 0; k < 8; k++) r.figures[k] = cf[(EPL_FIG0 + k) * cnt + q];
+    }
+    return (int64_t)cnt;
 }
 
 // ---- action decoding (include/imgenv.h; the kernel is csrc/actions.h) ----

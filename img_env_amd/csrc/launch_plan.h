@@ -31,6 +31,7 @@
 #define STACK_MAX_BLOCKS 2048
 #define EP_BLOCK 256
 #define EP_MAX_BLOCKS 1024
+#define EPLOG_BLOCK 1024    // k_episode_log: ONE workgroup (its records are numbered by a running count), 16 wavefronts
 #define ACT_BLOCK 256       // k_actions: one lane per local robot
 #define OBS_POST_BLOCK 256  // k_obs_post: one lane per element of a robot's ped_vector row
 #define OBS_POST_MAX_BLOCKS 2048
@@ -404,6 +405,10 @@ inline LaunchShape plan_tail(size_t items, int block, int max_blocks) {
 inline LaunchShape plan_tail_launch(const PlanHandle& h, const PlanChain& c, size_t per_row, int block, int max_blocks) {
     return plan_tail(plan_tail_rows(h, c) * per_row, block, max_blocks);
 }
+
+// k_episode_log (episode_log.h), in front of a reset chain's k_episodes<true>: one workgroup whatever the chain covers -- the
+// records take their numbers from a count that runs through the block, chunk by chunk of EPLOG_BLOCK rows
+inline LaunchShape plan_episode_log_launch() { return {1, EPLOG_BLOCK, 0}; }
 
 // ---------------------------------------------------------------------------------------- in front of the chain: k_actions
 // imgenv_actions_decode (actions.h): one lane per local robot, every wavefront whole (the ballot that counts bad rows runs on all

@@ -735,6 +735,28 @@ class PedTrajectoryDatasetWrapper(Wrapper):
             self.cur_repeated_time_per_env = 0
 
 
+def episode_log_lines(records, dt, kind):
+    """The lines the reference's dataset wrappers append to ``output_file`` per episode (``PedTrajectoryDatasetWrapper.out2logfile``,
+    ``BarnDataSetWrapper.out2logfile``) from the device-side episode log: ``records`` is the dict of columns
+    ``VecImageEnv.episode_log()`` returns (``counted``, ``code``, ``steps``, ``tracks`` / ``map`` and the figures), ``dt`` the YAML's
+    ``control_hz``.  ``kind="ped_dataset"``: ``cur_world`` is the record's track set and the collision column the pedestrian one
+    (code 2); ``kind="barn"``: ``cur_world`` is its map and the column the static one (code 1).  Columns: ``cur_world, arrive,
+    collision, stuck, v_avg, w_avg, v_acc, w_acc, v_jerk, w_jerk, w_zero, path_time, steps`` with ``path_time = round(steps * dt,
+    4)``.  Counted records only, in log order; a list of strings without the newline."""
+    if kind not in ("ped_dataset", "barn"):
+        raise ValueError("kind: ped_dataset | barn")
+    world, coll = ("tracks", 2) if kind == "ped_dataset" else ("map", 1)
+    lines = []
+    for q in np.flatnonzero(np.asarray(records["counted"]) != 0):
+        code, steps = int(records["code"][q]), int(records["steps"][q])
+        m = {k: float(records[k][q]) for k in ("v_avg", "w_avg", "v_acc", "w_acc", "v_jerk", "w_jerk")}
+        m.update(cur_world=int(records[world][q]), arrive=1 if code == 5 else 0, collision=1 if code == coll else 0,
+                 stuck=1 if code == 10 else 0, w_zero=int(records["w_zero"][q]), path_time=round(steps * float(dt), 4), steps=steps)
+        lines.append("{cur_world}, {arrive}, {collision}, {stuck}, {v_avg}, {w_avg}, {v_acc}, {w_acc}, {v_jerk}, {w_jerk}, {w_zero}, "
+                     "{path_time}, {steps}".format_map(m))
+    return lines
+
+
 def dataset_track_sets(cfg):
     """The recorded crowds of a dataset YAML as the sets of a track bank (``World.tracks_add``, ``VecImageEnv(ped_tracks="yaml")``):
     for every entry of ``cfg["ped_dataset_worlds"]`` the series ``PedTrajectoryDatasetWrapper.change_world()`` would hand out for

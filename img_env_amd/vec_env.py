@@ -39,7 +39,8 @@ class VecImageEnv:
 
     def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False,
                  map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3, wrappers=False,
-                 ped_tracks=None, tracks_policy="keep", tracks_repeat=1, info_track_sets=False, scenarios=None, scenario_policy="queue"):
+                 ped_tracks=None, tracks_policy="keep", tracks_repeat=1, info_track_sets=False, scenarios=None, scenario_policy="queue",
+                 episode_log=0):
         import torch
         from .world import World
         self.cfg = cfg
@@ -145,9 +146,16 @@ class VecImageEnv:
         # env (imgenv_episodes_enable): how episodes end, steps to arrive, returns, lengths and the path figures of the commands,
         # kept by one small launch per chain -- also where the device resets the envs and the host never sees an episode end.
         # Opt-in: False launches nothing.
-        self.episode_stats = bool(episode_stats)
+        # episode_log=N: besides the totals, one record per finished episode in a ring of N records on the device
+        # (imgenv_episode_log_enable): how it ended, its steps, return and figures, and the map / track set / scenario / placement it
+        # ran on -- one more small launch per RESET chain, none per step.  Implies episode_stats.  episode_log() reads it.
+        self._log_capacity = int(episode_log or 0)
+        self._log_cursor = 0
+        self.episode_stats = bool(episode_stats) or self._log_capacity > 0
         if self.episode_stats:
             self.world.enable_episodes(int(episode_min_steps), float(cfg["control_hz"]))
+        if self._log_capacity > 0:
+            self.world.enable_episode_log(self._log_capacity)
 
         # wrappers: the input side of the YAML's wrapper list and its two small output wrappers inside the library.
         #   VelActionWrapper (base.py:37-66): ``step`` takes what the policy emits -- a 1-D integer array of indices into
@@ -197,6 +205,24 @@ class VecImageEnv:
                     avg_w_variance=fig["w_variance"] / n, avg_v_jerk=fig["v_jerk"] / n, avg_w_jerk=fig["w_jerk"] / n,
                     avg_w_zero=fig["w_zero"] / n, aborted_rate=ends["aborted"] / n, episodes=int(e["episodes"]),
                     short_episodes=int(e["short_episodes"]), avg_return=float(e["return_sum"]) / n, avg_len=int(e["len_sum"]) / n)
+
+    def episode_log(self, since=None):
+        """The finished episodes' records as a dict of numpy columns: ``seq``, ``placement`` (uint64; ~0: none), ``robot``,
+        ``world``, ``code``, ``steps``, ``len``, ``counted``, ``episode``, ``map``, ``tracks``, ``scenario`` (int32), ``ep_return``
+        and the eight figures ``w_variance ... w_avg`` (float64), in log order; plus the scalars ``oldest`` and ``n_written``.
+        ``since=None`` continues behind the last call's records (a cursor kept here); an integer starts at that ``seq``.  Records
+        the ring has overwritten are gone: the first ``seq`` returned is then ``oldest``.  SYNCHRONISES: it waits for the stream
+        and copies the records to the host (``imgenv_episode_log_read``)."""
+        if self._log_capacity <= 0:
+            raise RuntimeError("VecImageEnv was made without episode_log=N")
+        first = self._log_cursor if since is None else int(since)
+        rec, oldest, written = self.world.read_episode_log(first)
+        self._log_cursor = written
+        out = {k: np.ascontiguousarray(rec[k]) for k in rec.dtype.names if k != "figures"}
+        for q, name in enumerate(_cabi.EP_FIGURE_NAMES):
+            out[name] = np.ascontiguousarray(rec["figures"][:, q])
+        out["oldest"], out["n_written"] = oldest, written
+        return out
 
     def clear_episode_statistics(self):
         """every total and the open episodes' sums back to zero (``imgenv_episodes_clear``), ordered on the current stream"""

@@ -113,6 +113,8 @@ class World:
         self.stack = None  # enable_stack()
         self.stack_arena = None
         self.episodes = None  # enable_episodes()
+        self.episode_log = None  # enable_episode_log()
+        self.episode_log_capacity = 0
         self.action_outputs = None  # enable_actions()
         self.obs_post = None  # enable_obs_post()
         if self.n_maps > 1:
@@ -311,6 +313,40 @@ class World:
     def clear_episodes(self):
         """``imgenv_episodes_clear``: totals, ``last_*`` and the open episodes' sums back to zero, ordered on the current stream"""
         self._check(self.lib.imgenv_episodes_clear(self.h, self._stream()), "imgenv_episodes_clear")
+
+    def enable_episode_log(self, capacity):
+        """Device-side episode log (``imgenv_episode_log_enable``; after ``enable_episodes``): from now on every reset chain appends
+        one record per episode it closes to a ring of ``capacity`` records, tagged with the map, track set, scenario and placement
+        the episode ran on (include/imgenv.h).  ``self.episode_log`` maps ``n_written`` (int64 ``[1]``), ``i32`` (int32
+        ``[10, capacity]``, rows ``_cabi.EPLOG_I32_NAMES``), ``f64`` (float64 ``[9, capacity]``, rows ``_cabi.EPLOG_F64_NAMES``) and
+        ``placement`` (int64 ``[capacity]``, -1: none) to zero-copy tensors over the library's memory; record ``q`` lives in slot
+        ``q % capacity``.  Read-only; valid until ``close()``.  ValueError for a bad capacity or a second call with another one,
+        RuntimeError before ``enable_episodes``."""
+        c = _cabi.make_episode_log_cfg(capacity)
+        lo = _cabi.EpisodeLogOut()
+        self._call(self.lib.imgenv_episode_log_enable(self.h, C.byref(c), C.byref(lo)), "imgenv_episode_log_enable")
+        if self.episode_log is None:
+            n = lo.capacity
+            self.episode_log = self._views(lo, {k: (dt_, (1,) if rows < 0 else ((rows, n) if rows else (n,)))
+                                                for k, (dt_, rows) in _cabi.EPISODE_LOG_ARRAYS.items()}, "imgenv_episode_log_out")
+            self.episode_log_capacity = n
+        return self.episode_log
+
+    def read_episode_log(self, first=0, max_records=None):
+        """``imgenv_episode_log_read``: ``(records, oldest, n_written)`` -- the records with ``seq`` in ``[max(first, oldest),
+        min(first + max_records, n_written))`` (``max_records=None``: up to ``n_written``, so a ``first`` the ring has overwritten starts at
+        ``oldest``) as a numpy record array (``_cabi.EPISODE_RECORD_DTYPE``; ``scenario`` resolved as
+        ``world_scenarios()`` would have answered while the episode ran).  SYNCHRONISES the current stream."""
+        if self.episode_log is None:
+            raise RuntimeError("enable_episode_log() was not called")
+        # (whatever the window, the library copies records of [oldest, n_written) only: never more than the ring holds)
+        n = 0x7FFFFFFF if max_records is None else max(0, min(int(max_records), 0x7FFFFFFF))
+        rec = np.zeros(max(min(n, self.episode_log_capacity), 1), _cabi.EPISODE_RECORD_DTYPE)
+        oldest, written = C.c_uint64(), C.c_uint64()
+        got = self.lib.imgenv_episode_log_read(self.h, C.c_uint64(int(first)), n, rec.ctypes.data, C.byref(oldest), C.byref(written), self._stream())
+        if got < 0:
+            self._check(int(got), "imgenv_episode_log_read")
+        return rec[:int(got)], int(oldest.value), int(written.value)
 
     def _views(self, out, arrays, what):
         """zero-copy tensors over library-owned arrays: ``arrays`` maps a name of ``out`` to (numpy dtype, shape)"""
@@ -576,7 +612,7 @@ class World:
 
     def close(self):
         if getattr(self, "h", None):
-            self.episodes = self.action_outputs = self.obs_post = None  # (views of memory the handle owns)
+            self.episodes = self.episode_log = self.action_outputs = self.obs_post = None  # (views of memory the handle owns)
             self.lib.imgenv_destroy(self.h)
             self.h = None
 

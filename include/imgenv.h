@@ -7,7 +7,7 @@
  *   ~init_image_env   (src/comn_pkg/srv/InitEnv.srv:1-21)   -> imgenv_create()
  *   ~reset_image_env  (src/comn_pkg/srv/ResetEnv.srv:1-8)   -> imgenv_reset()
  *   ~step_image_env   (src/comn_pkg/srv/StepEnv.srv:1-5)    -> imgenv_step()
- *   ~ep_end_image_env (src/comn_pkg/srv/EndEp.srv)          -> (episode recording: out of scope)
+ *   ~ep_end_image_env (src/comn_pkg/srv/EndEp.srv)          -> per-episode results: imgenv_episode_log_*; trajectories: out of scope
  *
  * and the Python post-processing of the response (reference envs/env/yaml_env.py:392-481,
  * envs/wrapper/base.py:153-254) which this library also performs on the device, so the
@@ -569,6 +569,67 @@ int imgenv_episodes_outputs(imgenv_t* h, imgenv_episodes_out* out);
  * episode's sums and counters become 0 (one memset); `open` keeps its value, so what follows of an episode in flight still counts
  * if it is long enough. */
 int imgenv_episodes_clear(imgenv_t* h, void* stream);
+
+/* ---- episode log: one record per finished episode, with what it ran on ----
+ * The reference writes one line per episode of a fixed test set (PedTrajectoryDatasetWrapper.out2logfile, BarnDataSetWrapper.
+ * out2logfile: which world, how it ended, v_avg ... w_zero, path_time, steps), and TestEpisodeWrapper keeps per-episode lists
+ * (w_variance_array, ...).  The statistics above are running totals per robot; the log is their per-episode half: a ring of records
+ * in device memory.  Every reset chain (imgenv_reset, imgenv_reset_world(s), imgenv_reset_worlds_spawn / _scenarios, the resets inside
+ * imgenv_step_autoreset / imgenv_step_autoreset_device) appends one record per episode it closes, on the caller's stream, with no
+ * host synchronisation, allocation or copy: one extra launch per RESET chain (csrc/episode_log.h, in front of the fold); a step
+ * chain launches nothing new.
+ *
+ * A reset chain covers robot rows in a fixed order (every local robot ascending, or robot by robot of the worlds it lists, in list
+ * order); each covered robot with an open episode (imgenv_episodes_out.open != 0) appends one record, in that order -- the log is
+ * deterministic: chains in stream order, rows in chain order.  Record q (counted from enabling) lives in slot q % capacity.
+ *   robot     the local row; world = row / robots-per-world (0 on a robot shard)
+ *   code      the last step's imgenv_out.step_dones_info;  steps, len, ep_return: open_steps, open_len and the open return
+ *   counted   steps > min_steps;  episode: the robot's `episodes` after this fold (0 when not counted)
+ *   figures   the IMGENV_EP_FIGURES figures this fold adds to figure_sums (zeros when not counted: a short episode's commands ride
+ *             into the next counted one, as above)
+ *   map, tracks, scenario_raw, placement   what the episode ran on, noted when it OPENED -- every covered robot, open or not, takes
+ *             them for the episode that starts: its world's map of the bank (0 without one), its track set (-1 without a bank or
+ *             where the reset brought its own tracks), the scenario of a host reset or IMGENV_EPLOG_SCN_DEVICE where the device
+ *             placed the world (-1 without a scenario bank), and the world's placement number (imgenv_world_placement; ~0: none).
+ *   Episodes already open when the log is enabled carry map -1, tracks -1, scenario_raw -1 and placement ~0.
+ * imgenv_episodes_clear does not touch the log; `episode` follows the cleared counter. */
+#define IMGENV_EPLOG_MAX_CAPACITY (1 << 22)
+#define IMGENV_EPLOG_I32 10   /* rows of i32: robot, world, code, steps, len, counted, episode, map, tracks, scenario_raw */
+#define IMGENV_EPLOG_F64 9    /* rows of f64: ep_return, then the IMGENV_EP_FIGURES figures in their order */
+#define IMGENV_EPLOG_SCN_DEVICE (-2) /* scenario_raw: placed by the device; the id follows from `placement` */
+typedef struct imgenv_episode_log_cfg {
+    int32_t struct_size;          /* sizeof(imgenv_episode_log_cfg) */
+    int32_t capacity;             /* records the ring holds: 1 .. IMGENV_EPLOG_MAX_CAPACITY */
+} imgenv_episode_log_cfg;
+typedef struct imgenv_episode_log_out {
+    int32_t struct_size;          /* on entry 0 or sizeof(imgenv_episode_log_out) */
+    int32_t capacity;
+    uint64_t* n_written;          /* [1]  records appended since enabling; record q lives in slot q % capacity */
+    int32_t* i32;                 /* [IMGENV_EPLOG_I32][capacity] */
+    double* f64;                  /* [IMGENV_EPLOG_F64][capacity] */
+    uint64_t* placement;          /* [capacity] place_serial of the episode's world when it opened, ~0: none */
+} imgenv_episode_log_out;
+typedef struct imgenv_episode_record {  /* 128 bytes, what imgenv_episode_log_read hands to the host */
+    uint64_t seq, placement;
+    int32_t robot, world, code, steps, len, counted, episode, map, tracks, scenario;
+    double ep_return, figures[8];
+} imgenv_episode_record;
+/* IMGENV_ESTATE before imgenv_episodes_enable(); IMGENV_EINVAL for a wrong struct_size, a capacity outside 1 ..
+ * IMGENV_EPLOG_MAX_CAPACITY, or a second call with another capacity; the same capacity again changes nothing and hands out the same
+ * pointers.  IMGENV_ENOMEM, like IMGENV_EDEVICE, leaves the handle unchanged.  The memory is the library's (zeroed); `out` may be
+ * NULL.  A handle that never calls it behaves, launch for launch, as if this section did not exist. */
+int imgenv_episode_log_enable(imgenv_t* h, const imgenv_episode_log_cfg* cfg, imgenv_episode_log_out* out);
+/* IMGENV_ESTATE before imgenv_episode_log_enable() */
+int imgenv_episode_log_outputs(imgenv_t* h, imgenv_episode_log_out* out);
+/* The records on the host.  Synchronises `stream`, like imgenv_world_scenarios.  *oldest = max(0, n_written - capacity) and
+ * *n_written as they stand then (either may be NULL); the records with seq in [max(first, oldest), min(first + max, n_written)) are
+ * copied to rec[] in order and their number is returned (a negative IMGENV_E* on failure).  rec may be NULL when max is 0.
+ * `scenario` is what imgenv_world_scenarios would have answered for the record's world while the episode ran: scenario_raw where the
+ * host reset the world, the scenario the placement's policy epoch gives its placement number for IMGENV_EPLOG_SCN_DEVICE, -1 without
+ * a bank.  The handle's CURRENT seed0 and epoch table are used: read before the pool of imgenv_step_autoreset_device is rebuilt for
+ * another spawn cfg. */
+int64_t imgenv_episode_log_read(imgenv_t* h, uint64_t first, int32_t max, imgenv_episode_record* rec, uint64_t* oldest, uint64_t* n_written,
+                                void* stream);
 
 /* ---- action decoding: VelActionWrapper.action (envs/wrapper/base.py:37-66, envs/action/action.py:8-38) and the `speeds` of
  * info (base.py:58) as MultiRobotCleanWrapper masks them (base.py:81-83), for every local robot, on the device ----

@@ -10,7 +10,10 @@ write before; --stack-compare alternates no stack / library stack / torch stack 
 
 --episodes adds the per-robot episode statistics of TestEpisodeWrapper kept by the library (imgenv_episodes_enable);
 --torch-episodes keeps the same figures with EpisodeStats and torch ops on top of a plain VecImageEnv; --episodes-compare
-alternates no statistics / library / torch over several rounds and writes the raw figures.
+alternates no statistics / library / torch over several rounds and writes the raw figures.  --episode-log adds the per-episode
+log on top of the statistics (imgenv_episode_log_enable: one more launch per reset chain); --episode-log-compare alternates no
+statistics / statistics / statistics + log over several rounds -- the device_reset variant runs a reset chain with every step, so
+its difference between the last two is what the log's launch costs a reset chain.
 
 --wrappers table|clip feeds the policy's raw output (indices into a 28-row table, or float rows to be clipped) to
 VecImageEnv(wrappers=True): decode, speeds, normalised pedestrian vectors and close_to_human kept by the library;
@@ -188,7 +191,8 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
             torch_stack=False, episodes=None, wrappers=None):
     """robot-steps/s of VecImageEnv over `steps` steps, after the envs have drifted out of phase.  ``stack`` = (image_batch,
     state_batch, laser_batch): with the library's frame stacks, or (``torch_stack``) the same kept by torch ops on top;
-    ``episodes`` = "library" | "torch": with the per-robot episode statistics, kept by the library or by ``TorchEpisodes``;
+    ``episodes`` = "library" | "torch" | "log": with the per-robot episode statistics, kept by the library or by ``TorchEpisodes``,
+    or the library's with the episode log (a ring of 65536 records) on top;
     ``wrappers`` = (kind, by): kind "table" | "clip", by "none" (pre-decoded actions, nothing enabled) | "library"
     (``wrappers=True`` fed the raw output) | "torch" (``TorchWrappers`` fed the raw output)"""
     import torch
@@ -203,7 +207,8 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
         if wrappers is not None:
             cfg.update(max_ped=10, wrapper=list(WRAPPER_LIST), discrete_action=wrappers[0] == "table", discrete_actions=TABLE28)
         env = VecImageEnv(cfg, env_num=envs, seed=5, native_spawn=bool(native), device_reset=native == "device",
-                          stack=stack is not None and not torch_stack, episode_stats=episodes == "library",
+                          stack=stack is not None and not torch_stack, episode_stats=episodes in ("library", "log"),
+                          episode_log=(1 << 16) if episodes == "log" else 0,
                           wrappers=wrappers is not None and wrappers[1] == "library")
         te = TorchEpisodes(env) if episodes == "torch" else None
         ts = TorchStack(env, stack_depths(stack)) if stack is not None and torch_stack else None
@@ -271,6 +276,8 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
                    first_reset_ms=1e3 * t_reset)
         if episodes is not None:  # (after the clock has stopped: this synchronises)
             res["episodes_counted"] = (te.statistics() if te else env.episode_statistics())["episodes"]
+            if episodes == "log":
+                res["episodes_logged"] = env.episode_log()["n_written"]
         if native is True and stack is None and episodes is None:  # the same steps without the reset half: what NeverStopWrapper costs on top of the step
             env.auto_reset = False
             torch.cuda.synchronize()
@@ -337,6 +344,32 @@ def compare_episodes(args, rounds=3):
             row[mode] = dict(us_per_step_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
         row["added_us_library"] = row["library"]["median"] - row["none"]["median"]
         row["added_us_torch"] = row["torch_episodes"]["median"] - row["none"]["median"]
+        summary.append(row)
+    return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, steps=args.steps, time_max=args.time_max,
+                rounds=rounds, runs=runs, summary=summary)
+
+
+def compare_episode_log(args, rounds=3):
+    """no statistics / statistics / statistics + episode log, alternating, `rounds` times, per reset variant"""
+    natives = (True, "device")
+    modes = (("none", None), ("statistics", "library"), ("log", "log"))
+    runs = []
+    for rnd in range(rounds):
+        for mode, episodes in modes:
+            r = measure(args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max, natives, episodes=episodes)
+            for variant in ("native_spawn", "device_reset"):
+                runs.append(dict(round=rnd, mode=mode, variant=variant, us_per_step=r[variant]["us_per_step"],
+                                 env_resets_per_step=r[variant]["env_resets_per_step"],
+                                 episodes_logged=r[variant].get("episodes_logged")))
+                print(json.dumps(runs[-1]), flush=True)
+    summary = []
+    for variant in ("native_spawn", "device_reset"):
+        row = dict(variant=variant)
+        for mode, _ in modes:
+            v = [r["us_per_step"] for r in runs if r["variant"] == variant and r["mode"] == mode]
+            row[mode] = dict(us_per_step_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
+        row["added_us_statistics"] = row["statistics"]["median"] - row["none"]["median"]
+        row["added_us_log"] = row["log"]["median"] - row["statistics"]["median"]
         summary.append(row)
     return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, steps=args.steps, time_max=args.time_max,
                 rounds=rounds, runs=runs, summary=summary)
@@ -571,6 +604,9 @@ def main():
     ap.add_argument("--torch-episodes", action="store_true", help="the same statistics kept with EpisodeStats and torch ops")
     ap.add_argument("--episodes-compare", action="store_true",
                     help="no statistics / library / torch_episodes, alternating over --rounds rounds")
+    ap.add_argument("--episode-log", action="store_true", help="the statistics and the per-episode log kept by the library")
+    ap.add_argument("--episode-log-compare", action="store_true",
+                    help="no statistics / statistics / statistics + episode log, alternating over --rounds rounds")
     ap.add_argument("--wrappers", default=None, choices=("table", "clip"), help="the policy's raw output decoded by the library (wrappers=True)")
     ap.add_argument("--torch-wrappers", action="store_true", help="with --wrappers: the same kept with torch ops on a plain VecImageEnv")
     ap.add_argument("--wrappers-compare", action="store_true",
@@ -614,6 +650,13 @@ def main():
                 json.dump(res, fh, indent=1)
         print(json.dumps(res["summary"]))
         return
+    if args.episode_log_compare:
+        res = compare_episode_log(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
+        return
     if args.episodes_compare:
         res = compare_episodes(args, args.rounds)
         if args.out:
@@ -631,7 +674,7 @@ def main():
     natives = ("device",) if args.device_only else (False, True, "device")
     stack = tuple(int(v) for v in args.stack.split(",")) if args.stack else None
     print(json.dumps(measure(args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max, natives, stack=stack,
-                             torch_stack=args.torch_stack, episodes="torch" if args.torch_episodes else "library" if args.episodes else None,
+                             torch_stack=args.torch_stack, episodes="torch" if args.torch_episodes else "log" if args.episode_log else "library" if args.episodes else None,
                              wrappers=(args.wrappers, "torch" if args.torch_wrappers else "library") if args.wrappers else None)))
 
 

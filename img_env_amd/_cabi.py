@@ -277,6 +277,39 @@ def make_obs_post_cfg(ped_norm=True, close=True, avg=PED_NORM_AVG, std=PED_NORM_
     return c
 
 
+#: imgenv_final_obs_cfg.fields: name -> IMGENV_FINAL_* bit, in bit order.  The first eleven are fields of imgenv_out.
+FINAL_BITS = {"vector_states": 1, "sensor_maps": 2, "lasers": 4, "ped_vector_states": 8, "ped_maps": 16, "is_collisions": 32,
+              "is_arrives": 64, "step_ds": 128, "ped_min_dists": 256, "view_maps": 512, "lasers_raw": 1024, "stacks": 2048,
+              "ped_vector_norm": 4096}
+FINAL_IMAGE_STATE, FINAL_ALL = 511, 8191
+#: the pointers of imgenv_final_obs_out, in the struct's order
+FINAL_ARRAYS = tuple(list(FINAL_BITS)[:11]) + ("stack_sensor_maps", "stack_vector_states", "stack_lasers", "ped_vector_norm", "final_count")
+FINAL_BLOCK, FINAL_MAX_BLOCKS = 256, 1024  # k_final_obs' launch shape (csrc/launch_plan.h)
+
+
+class FinalObsCfg(C.Structure):
+    _fields_ = [("struct_size", _i32), ("fields", _i32)]
+
+
+class FinalObsOut(C.Structure):
+    _fields_ = [("struct_size", _i32), ("n_local", _i32)] + [(name, C.c_void_p) for name in FINAL_ARRAYS]
+
+
+def make_final_obs_cfg(fields):
+    """``imgenv_final_obs_cfg``: ``fields`` is an int of IMGENV_FINAL_* bits or an iterable of ``FINAL_BITS`` names"""
+    c = FinalObsCfg()
+    c.struct_size = C.sizeof(FinalObsCfg)
+    if isinstance(fields, (int, np.integer)):
+        c.fields = int(fields)
+    else:
+        names = list(fields)
+        unknown = [n for n in names if n not in FINAL_BITS]
+        if unknown:
+            raise ValueError("final observation fields: unknown %s (known: %s)" % (unknown, ", ".join(FINAL_BITS)))
+        c.fields = sum({FINAL_BITS[n] for n in names})
+    return c
+
+
 #: name -> (numpy dtype, shape as a function of the Out header and the world sizes)
 def out_layout(o, n_peds, hp, wp):
     R, B = o.n_local, max(o.n_beams, 1)
@@ -428,6 +461,7 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_episodes_enable", "imgenv_episodes_outputs", "imgenv_episodes_clear",
            "imgenv_episode_log_enable", "imgenv_episode_log_outputs", "imgenv_episode_log_read",
            "imgenv_actions_enable", "imgenv_actions_outputs", "imgenv_actions_decode", "imgenv_obs_post_enable", "imgenv_obs_post_outputs",
+           "imgenv_final_obs_enable", "imgenv_final_obs_outputs",
            "imgenv_maps_add", "imgenv_world_maps_set", "imgenv_maps_policy", "imgenv_map_for_placement", "imgenv_world_maps",
            "imgenv_tracks_add", "imgenv_world_tracks_set", "imgenv_tracks_policy", "imgenv_tracks_for_placement", "imgenv_world_tracks",
            "imgenv_scenarios_add", "imgenv_scenarios_policy", "imgenv_scenario_for_placement", "imgenv_reset_worlds_scenarios",
@@ -494,6 +528,8 @@ def bind(lib):
     lib.imgenv_actions_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.imgenv_obs_post_enable.argtypes = [C.c_void_p, C.POINTER(ObsPostCfg), C.POINTER(ObsPostOut)]
     lib.imgenv_obs_post_outputs.argtypes = [C.c_void_p, C.POINTER(ObsPostOut)]
+    lib.imgenv_final_obs_enable.argtypes = [C.c_void_p, C.POINTER(FinalObsCfg), C.POINTER(FinalObsOut)]
+    lib.imgenv_final_obs_outputs.argtypes = [C.c_void_p, C.POINTER(FinalObsOut)]
     lib.imgenv_maps_add.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
     lib.imgenv_world_maps_set.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
     lib.imgenv_maps_policy.argtypes = [C.c_void_p, C.c_int32]

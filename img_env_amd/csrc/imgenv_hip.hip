@@ -28,6 +28,7 @@
 #include "episode_log.h"
 #include "actions.h"
 #include "obs_post.h"
+#include "final_obs.h"
 #include "map_bank.h"
 #include "spawn_slot.h"
 
@@ -245,6 +246,12 @@ struct imgenv {
     ObsPostDev post;
     imgenv_obs_post_cfg post_cfg;
     imgenv_obs_post_out post_out;
+    // final observations (imgenv_final_obs_enable; csrc/final_obs.h)
+    bool final_on = false;
+    bool obs_exists = false;     // a chain of launches has completed on this handle: its output rows hold an observation
+    FinalObsDev final_dev;
+    imgenv_final_obs_cfg final_cfg;
+    imgenv_final_obs_out final_out;
     bool chain_open = false;  // a chain of launches that hands over through tail_sig / tail_cnt has started and not been completed
     std::vector<RvoObstacles> rvos;  // one obstacle set per world
     int sfm_cap_obs = 0;
@@ -1694,6 +1701,19 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
     DevWorld& d = h->d;
     const PlanHandle& p = h->plan;
     set_tail_fields(h, is_reset, h->elapsed);
+    if (is_reset && h->final_on && h->obs_exists) {
+        // the final observations (final_obs.h), in front of everything of this chain that writes a captured field -- its k_obs
+        // (forked below, behind this launch in stream order), its views and their tails, its k_stack<true> and k_obs_post<true>:
+        // the rows the chain covers, as the last step left them.  What a reset chain has launched before this point (the staged
+        // copies and map restores, k_respawn and the rest of the device-side reset) writes none of them.
+        FinalObsDev fo = h->final_dev;
+        fo.rows = tail_rows(h, 1);
+        const PlanChain cf = chain_facts(h, 1);
+        const int guess = cf.n_dev ? plan_dev_reset(h->plan, h->finished_host[0], 0).guess : 0;
+        const LaunchShape g = plan_final_obs_launch(h->plan, cf, fo.chunks_per_row, guess);
+        k_final_obs<<<dim3(g.grid), dim3(g.block), 0, st>>>(fo);
+        h->launches += 1;
+    }
     if (h->P == 0)
         if (int rc = chain_begin(h, st)) return rc;
     // the rasters: in a step whose move was left to them (imgenv_step_begin: k_move_raster) they come first and the side stream forks
@@ -1832,6 +1852,7 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
     }
     HIPCHK(hipGetLastError());
     h->chain_open = false;
+    h->obs_exists = true;
     return outputs_seal(h, st);
 }
 
@@ -4251,6 +4272,106 @@ extern "C" int imgenv_obs_post_enable(imgenv_t* h, const imgenv_obs_post_cfg* c,
 
 extern "C" int imgenv_obs_post_outputs(imgenv_t* h, imgenv_obs_post_out* out) {
     return feature_outputs(h, &imgenv::post_on, &imgenv::post_out, out, "imgenv_obs_post_enable");
+}
+
+// ---- final observations (include/imgenv.h; the kernel is csrc/final_obs.h) ----
+extern "C" int imgenv_final_obs_enable(imgenv_t* h, const imgenv_final_obs_cfg* c, imgenv_final_obs_out* out) {
+    // (the cfg first, as above)
+    RTRY(enable_args(c, "imgenv_final_obs_cfg", out, "imgenv_final_obs_out"));
+    if (c->fields == 0 || (c->fields & ~IMGENV_FINAL_ALL)) FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields %d", c->fields);
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (h->final_on) {
+        if (c->fields != h->final_cfg.fields)
+            FAIL(IMGENV_EINVAL, "imgenv_final_obs_enable: the handle already keeps final observations of the fields %d", h->final_cfg.fields);
+        if (out) *out = h->final_out;
+        return IMGENV_OK;
+    }
+    const int want = c->fields;
+    if ((want & (IMGENV_FINAL_LASERS | IMGENV_FINAL_LASERS_RAW)) && h->out.n_beams <= 0) FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields: lasers on a handle without use_laser");
+    if ((want & IMGENV_FINAL_VIEW_MAPS) && !h->d.keep_view_maps) FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields: view_maps under IMGENV_FLAG_NO_VIEW_MAPS");
+    if ((want & IMGENV_FINAL_STACKS) && !h->stack_on) FAIL(IMGENV_ESTATE, "IMGENV_FINAL_STACKS before imgenv_stack_enable");
+    if ((want & IMGENV_FINAL_STACKS) && h->stack.n_fields == 0) FAIL(IMGENV_EINVAL, "IMGENV_FINAL_STACKS: no stack of this handle is deeper than 1");
+    if ((want & IMGENV_FINAL_PED_NORM) && !(h->post_on && h->post.norm)) FAIL(IMGENV_ESTATE, "IMGENV_FINAL_PED_NORM before imgenv_obs_post_enable with IMGENV_OBS_PED_NORM");
+    // the sources, always in the working arena, with their row sizes and where the out struct keeps the copy's pointer
+    const imgenv_out& w = h->out;
+    const size_t NC = (size_t)w.view_h * w.view_w, NI = (size_t)w.image_h * w.image_w, B = (size_t)std::max(w.n_beams, 0);
+    const size_t NP = (size_t)h->cfg.ped_image_size[0] * h->cfg.ped_image_size[1];
+    imgenv_final_obs_out o = {};
+    struct Src {
+        int bit;
+        const void* src;
+        size_t row_bytes;
+        void** slot;
+    };
+    const imgenv_stack_out& so = h->stack_out;
+    const Src all[] = {
+        {IMGENV_FINAL_VECTOR_STATES, w.vector_states, (size_t)w.state_dim * 4, (void**)&o.vector_states},
+        {IMGENV_FINAL_SENSOR_MAPS, w.sensor_maps, NI * 2, (void**)&o.sensor_maps},
+        {IMGENV_FINAL_LASERS, w.lasers, B * 8, (void**)&o.lasers},
+        {IMGENV_FINAL_PED_VECTOR_STATES, w.ped_vector_states, (size_t)w.ped_vec_len * 4, (void**)&o.ped_vector_states},
+        {IMGENV_FINAL_PED_MAPS, w.ped_maps, 3 * NP * 4, (void**)&o.ped_maps},
+        {IMGENV_FINAL_IS_COLLISIONS, w.is_collisions, 1, (void**)&o.is_collisions},
+        {IMGENV_FINAL_IS_ARRIVES, w.is_arrives, 1, (void**)&o.is_arrives},
+        {IMGENV_FINAL_STEP_DS, w.step_ds, 8, (void**)&o.step_ds},
+        {IMGENV_FINAL_PED_MIN_DISTS, w.ped_min_dists, 8, (void**)&o.ped_min_dists},
+        {IMGENV_FINAL_VIEW_MAPS, w.view_maps, NC, (void**)&o.view_maps},
+        {IMGENV_FINAL_LASERS_RAW, w.lasers_raw, B * 4, (void**)&o.lasers_raw},
+        // (a stack of depth >= 2 is the library's or the caller's arena, never an alias of imgenv_out)
+        {IMGENV_FINAL_STACKS, so.image_depth >= 2 ? so.sensor_maps : nullptr, (size_t)std::max(so.image_depth, 0) * NI * 2, (void**)&o.stack_sensor_maps},
+        {IMGENV_FINAL_STACKS, so.state_depth >= 2 ? so.vector_states : nullptr, (size_t)std::max(so.state_depth, 0) * w.state_dim * 4, (void**)&o.stack_vector_states},
+        {IMGENV_FINAL_STACKS, so.laser_depth >= 2 ? so.lasers : nullptr, (size_t)std::max(so.laser_depth, 0) * B * 8, (void**)&o.stack_lasers},
+        {IMGENV_FINAL_PED_NORM, h->post.norm, (size_t)w.ped_vec_len * 4, (void**)&o.ped_vector_norm},
+    };
+    static_assert(sizeof(all) / sizeof(all[0]) <= FINAL_MAX_FIELDS, "FINAL_MAX_FIELDS");
+    const Src* sel[FINAL_MAX_FIELDS];
+    size_t row_bytes[FINAL_MAX_FIELDS];
+    int n = 0;
+    for (const Src& s : all) {
+        if (!(want & s.bit) || ((s.bit & (IMGENV_FINAL_STACKS | IMGENV_FINAL_PED_NORM)) && !s.src)) continue;
+        if (!s.src || s.row_bytes == 0) FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields: bit %d names a field of no bytes on this handle", s.bit);
+        sel[n] = &s;
+        row_bytes[n++] = s.row_bytes;
+    }
+    const FinalPlan plan = plan_final_fields(row_bytes, n);
+    // one block: final_count, then the fields, each on a 256-byte boundary; zeroed.  Nothing of the handle changes before it is there.
+    const size_t RL = (size_t)h->RL;
+    size_t off[FINAL_MAX_FIELDS], total = align256(4 * RL);
+    for (int k = 0; k < n; k++) {
+        off[k] = total;
+        total = align256(total + RL * row_bytes[k]);
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    void* block = nullptr;
+    if (hipMalloc(&block, total) != hipSuccess) {
+        (void)hipGetLastError();
+        FAIL(IMGENV_ENOMEM, "no device memory for the final observations (%zu bytes)", total);
+    }
+    const hipError_t filled = hipMemset(block, 0, total);
+    if (filled != hipSuccess) {  // (a device error, not a lack of memory)
+        (void)hipFree(block);
+        FAIL(IMGENV_EDEVICE, "imgenv_final_obs_enable: hipMemset: %s (%s:%d)", hipGetErrorString(filled), __FILE__, __LINE__);
+    }
+    h->allocs.push_back(block);
+    FinalObsDev fo;
+    memset(&fo, 0, sizeof(fo));
+    fo.n_fields = plan.n_fields;
+    fo.chunks_per_row = plan.chunks_per_row;
+    fo.count = (uint32_t*)block;
+    for (int k = 0; k < n; k++) {
+        fo.f[k].dst = (unsigned char*)block + off[k];
+        fo.f[k].src = (const unsigned char*)sel[k]->src;
+        fo.f[k].unit = plan.f[k].unit;
+        fo.f[k].chunks = plan.f[k].chunks;
+        *sel[k]->slot = fo.f[k].dst;
+    }
+    o.final_count = fo.count;
+    h->final_dev = fo;
+    h->final_cfg = *c;
+    return enable_done(h, o, &imgenv::final_out, &imgenv::final_on, out);
+}
+
+extern "C" int imgenv_final_obs_outputs(imgenv_t* h, imgenv_final_obs_out* out) {
+    return feature_outputs(h, &imgenv::final_on, &imgenv::final_out, out, "imgenv_final_obs_enable");
 }
 
 extern "C" int imgenv_cv_resize_u8(int kind, const uint8_t* src, int32_t sh, int32_t sw, uint8_t* dst, int32_t dh, int32_t dw) {

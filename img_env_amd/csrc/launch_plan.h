@@ -32,6 +32,9 @@
 #define EP_BLOCK 256
 #define EP_MAX_BLOCKS 1024
 #define EPLOG_BLOCK 1024    // k_episode_log: ONE workgroup (its records are numbered by a running count), 16 wavefronts
+#define FINAL_BLOCK 256     // k_final_obs: one lane per chunk of a captured row
+#define FINAL_MAX_BLOCKS 1024
+#define FINAL_MAX_FIELDS 16  // 11 fields of imgenv_out, 3 stacks, ped_vector_norm
 #define ACT_BLOCK 256       // k_actions: one lane per local robot
 #define OBS_POST_BLOCK 256  // k_obs_post: one lane per element of a robot's ped_vector row
 #define OBS_POST_MAX_BLOCKS 2048
@@ -409,6 +412,46 @@ inline LaunchShape plan_tail_launch(const PlanHandle& h, const PlanChain& c, siz
 // k_episode_log (episode_log.h), in front of a reset chain's k_episodes<true>: one workgroup whatever the chain covers -- the
 // records take their numbers from a count that runs through the block, chunk by chunk of EPLOG_BLOCK rows
 inline LaunchShape plan_episode_log_launch() { return {1, EPLOG_BLOCK, 0}; }
+
+// ---------------------------------------------------------------------------------------- head of a reset chain: k_final_obs
+// k_final_obs (final_obs.h) copies the rows a reset chain is about to overwrite.  A row of a field is cut into chunks of `unit`
+// bytes, the largest of 16 / 8 / 4 / 2 / 1 that divides the row's size (every base is 256-byte aligned, so a row starts on a
+// multiple of its unit); one lane copies one chunk, a row of the launch is the sum of its fields' chunks.
+struct FinalFieldPlan {
+    uint32_t row_bytes = 0, unit = 1, chunks = 0;
+};
+inline FinalFieldPlan plan_final_field(size_t row_bytes) {
+    FinalFieldPlan f;
+    f.row_bytes = (uint32_t)row_bytes;
+    f.unit = row_bytes % 16 == 0 ? 16 : row_bytes % 8 == 0 ? 8 : row_bytes % 4 == 0 ? 4 : row_bytes % 2 == 0 ? 2 : 1;
+    f.chunks = (uint32_t)(row_bytes / f.unit);
+    return f;
+}
+struct FinalPlan {
+    FinalFieldPlan f[FINAL_MAX_FIELDS];
+    int n_fields = 0;
+    uint32_t chunks_per_row = 0;
+    size_t bytes_per_row = 0;
+};
+// the table of the fields in hand, in the caller's order (n <= FINAL_MAX_FIELDS; fields of no bytes are refused by the caller)
+inline FinalPlan plan_final_fields(const size_t* row_bytes, int n) {
+    FinalPlan p;
+    for (int k = 0; k < n && k < FINAL_MAX_FIELDS; k++) {
+        p.f[p.n_fields] = plan_final_field(row_bytes[k]);
+        p.chunks_per_row += p.f[p.n_fields].chunks;
+        p.bytes_per_row += row_bytes[k];
+        p.n_fields++;
+    }
+    return p;
+}
+// rows x chunks per row in blocks of FINAL_BLOCK, capped; the kernel strides.  The rows are the chain's (every local robot, or Rw
+// per listed world); behind a device-side reset nobody on the host knows the count, and the grid is sized for `dev_guess` worlds --
+// plan_dev_reset's guess from the same stale count its own grids use -- while the kernel reads the count on the device.
+inline LaunchShape plan_final_obs_launch(const PlanHandle& h, const PlanChain& c, uint32_t chunks_per_row, int dev_guess) {
+    size_t rows = (size_t)h.RL;
+    if (c.listed) rows = (size_t)(c.n_dev ? std::min(c.act_nw, std::max(dev_guess, 1)) : c.act_nw) * (size_t)h.Rw;
+    return plan_tail(rows * chunks_per_row, FINAL_BLOCK, FINAL_MAX_BLOCKS);
+}
 
 // ---------------------------------------------------------------------------------------- in front of the chain: k_actions
 // imgenv_actions_decode (actions.h): one lane per local robot, every wavefront whole (the ballot that counts bad rows runs on all

@@ -35,12 +35,14 @@ class VecImageEnv:
     their rows of the returned state are already the new episode's first observation, as with NeverStopWrapper).
     ``wrappers=True``: ``step`` takes the policy's own output (indices or raw float rows) and ``info`` gains ``speeds`` and, with
     pedestrians, ``bool_get_close_to_human`` (of the state handed out: an env that restarted shows its new episode's).
+    ``final_obs=True``: ``info`` gains ``final_observation`` (Gym's: the state the restarted envs' last action led to, in the rows
+    where ``all_down`` is set; other rows hold older captures) and ``final_count``.
     """
 
     def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False,
                  map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3, wrappers=False,
                  ped_tracks=None, tracks_policy="keep", tracks_repeat=1, info_track_sets=False, scenarios=None, scenario_policy="queue",
-                 episode_log=0):
+                 episode_log=0, final_obs=False):
         import torch
         from .world import World
         self.cfg = cfg
@@ -177,6 +179,21 @@ class VecImageEnv:
             self._close = self.ped_total > 0
             if self._ped_norm or self._close:
                 self.world.enable_obs_post(ped_norm=self._ped_norm, close=self._close)
+        # final_obs: Gym's final_observation (imgenv_final_obs_enable).  Every reset first copies the rows it is about to overwrite
+        # -- the observation the env's last action led to, which a trainer needs to bootstrap a time-out -- into arrays of their
+        # own: info["final_observation"] is the state in the form ``step`` hands out (stacks, filter list and normalised pedestrian
+        # vector included) over those arrays, info["final_count"] how often each robot's row has been captured.  With auto_reset
+        # the rows where info["all_down"] is set are this step's; the others hold older captures.  With auto_reset=False the rows
+        # of whatever reset / reset_envs last covered.  One more launch per RESET chain, none per step; nothing synchronises.
+        # Opt-in: False allocates and launches nothing.
+        self.final_obs = bool(final_obs)
+        if self.final_obs:
+            fields = [n for n in list(_cabi.FINAL_BITS)[:9] if n != "lasers" or self.params.get("use_laser")]
+            if self.stack and any(d >= 2 for d in self.world.stack_depths):
+                fields.append("stacks")
+            if self._ped_norm:
+                fields.append("ped_vector_norm")
+            self.world.enable_final_obs(fields)
 
     def episode_tensors(self):
         """the per-robot device tensors of the statistics (``World.episodes``: ``ends`` [6, n], ``episodes``, ``last_episode``,
@@ -233,14 +250,19 @@ class VecImageEnv:
     def __len__(self):
         return self.env_num * self.robot_total
 
-    def _state(self):
+    def _state(self, final=False):
         o = self.world.out
-        ped_vector = self.world.obs_post["ped_vector_norm"] if self._ped_norm else o["ped_vector_states"]
+        if final:  # the same form over the final arrays (a handle without a laser keeps no final lasers: the live placeholder)
+            f = self.world.final_obs
+            o = {name: f.get(name, t) for name, t in o.items()}
+        ped_vector = (f if final else self.world.obs_post)["ped_vector_norm"] if self._ped_norm else o["ped_vector_states"]
         if not self.stack:
             return ImageState(o["vector_states"], o["sensor_maps"], o["is_collisions"], o["is_arrives"], o["lasers"],
                               ped_vector, o["ped_maps"], o["step_ds"], o["ped_min_dists"])
         k = self.world.stack
-        vector_states, sensor_maps, lasers = (k.get(f, o[f]) for f in ("vector_states", "sensor_maps", "lasers"))
+        if final:  # a stack of depth 1 is the field itself, in the stack's shape
+            k = {name: f["stack_" + name] if "stack_" + name in f else o[name].view(t.shape) for name, t in k.items()}
+        vector_states, sensor_maps, lasers = (k.get(f_, o[f_]) for f_ in ("vector_states", "sensor_maps", "lasers"))
         if self._filter == "ObsStateTmp":
             return [sensor_maps, vector_states, o["ped_maps"]]
         if self._filter == "ObsLaserStateTmp":
@@ -287,6 +309,9 @@ class VecImageEnv:
                 info["bool_get_close_to_human"] = self.world.obs_post["close_to_human"]
         if self.info_track_sets:
             info["track_sets"] = self.world.world_tracks()
+        if self.final_obs:
+            info["final_observation"] = self._state(final=True)
+            info["final_count"] = self.world.final_obs["final_count"]
         return info
 
     def _actions(self, actions):

@@ -93,6 +93,7 @@ class World:
         o = _cabi.Out()
         self._check(self.lib.imgenv_outputs(self.h, C.byref(o)), "imgenv_outputs")
         self.n_local = o.n_local
+        self._out_header = o
         base = self.arena.data_ptr()
         self.out = {}
         for name, (dt, shape) in _cabi.out_layout(o, self.n_peds, cfg.ped_image_size[0], cfg.ped_image_size[1]).items():
@@ -117,6 +118,7 @@ class World:
         self.episode_log_capacity = 0
         self.action_outputs = None  # enable_actions()
         self.obs_post = None  # enable_obs_post()
+        self.final_obs = None  # enable_final_obs()
         if self.n_maps > 1:
             rest = self.grids[1:]
             rc = self.lib.imgenv_maps_add(self.h, len(rest), rest.ctypes.data, rest.shape[1], rest.shape[2])
@@ -424,8 +426,35 @@ class World:
                                              "close_to_human": (np.uint8, (R,))}, "imgenv_obs_post_out")
         return self.obs_post
 
+    def enable_final_obs(self, fields=None):
+        """Final observations (``imgenv_final_obs_enable``): from now on every reset -- ``reset``, ``reset_worlds*``,
+        ``step_autoreset``, ``step_autoreset_device`` -- first copies the rows it is about to overwrite, for the robots it covers,
+        into ``self.final_obs``: zero-copy tensors over the library's memory with the names, shapes and dtypes of ``out``'s, plus
+        ``final_count`` int32 ``[R]`` (captures of the row so far).  ``fields``: names of ``_cabi.FINAL_BITS``; None = the
+        ``ImageState`` set (without ``lasers`` on a handle without a laser).  ``"stacks"`` (after ``enable_stack``) adds
+        ``stack_sensor_maps`` / ``stack_vector_states`` / ``stack_lasers`` for the stacks of depth >= 2, shaped as ``self.stack``'s;
+        ``"ped_vector_norm"`` (after ``enable_obs_post``) the normalised pedestrian vector.  One extra launch per reset chain, none
+        per step; nothing synchronises.  Read-only; valid until ``close()``.  ValueError for refused fields or a second call with
+        other ones, RuntimeError for ``"stacks"`` / ``"ped_vector_norm"`` before their own enable call."""
+        if fields is None:
+            fields = [n for n in list(_cabi.FINAL_BITS)[:9] if n != "lasers" or self.cfg.use_laser]
+        c = _cabi.make_final_obs_cfg(fields)
+        fo = _cabi.FinalObsOut()
+        self._call(self.lib.imgenv_final_obs_enable(self.h, C.byref(c), C.byref(fo)), "imgenv_final_obs_enable")
+        if self.final_obs is None:
+            R = fo.n_local
+            lay = _cabi.out_layout(self._out_header, self.n_peds, self.cfg.ped_image_size[0], self.cfg.ped_image_size[1])
+            arrays = {name: lay[name] for name in list(_cabi.FINAL_BITS)[:11]}
+            if self.stack:
+                for name, t in self.stack.items():
+                    arrays["stack_" + name] = (lay[name][0], tuple(t.shape))
+            arrays["ped_vector_norm"] = lay["ped_vector_states"]
+            arrays["final_count"] = (np.int32, (R,))  # (uint32 in the library; torch has no arithmetic on it)
+            self.final_obs = self._views(fo, arrays, "imgenv_final_obs_out")
+        return self.final_obs
+
     def reset(self, layout):
-        """Reset everything.  A handle of several worlds (``n_worlds`` > 1) takes either one batch of all robots and
+        """Reset everything. A handle of several worlds (``n_worlds`` > 1) takes either one batch of all robots and
         pedestrians (world-major) with an obstacle list shared by every world, or a list of one layout per world."""
         if isinstance(layout, (list, tuple)):
             if len(layout) != self.n_worlds:
@@ -612,7 +641,7 @@ class World:
 
     def close(self):
         if getattr(self, "h", None):
-            self.episodes = self.episode_log = self.action_outputs = self.obs_post = None  # (views of memory the handle owns)
+            self.episodes = self.episode_log = self.action_outputs = self.obs_post = self.final_obs = None  # (views of memory the handle owns)
             self.lib.imgenv_destroy(self.h)
             self.h = None
 

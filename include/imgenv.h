@@ -725,6 +725,75 @@ int imgenv_obs_post_enable(imgenv_t* h, const imgenv_obs_post_cfg* cfg, imgenv_o
 /* IMGENV_ESTATE before imgenv_obs_post_enable() */
 int imgenv_obs_post_outputs(imgenv_t* h, imgenv_obs_post_out* out);
 
+/* ---- final observations: what an episode ended on (Gym's final_observation / terminal_observation), kept on the device ----
+ * Every reset hands out the new episode's first observation in the rows of the robots it resets (NeverStopWrapper,
+ * base.py:198-211): the observation the last action led to is written over in place.  A trainer that bootstraps the value of a
+ * truncated episode (TimeLimitWrapper, dones_info == 10) needs it, and behind imgenv_step_autoreset_device the host never learns
+ * which rows were reset.  With this feature every reset chain -- imgenv_reset, imgenv_reset_world(s), their spawn and scenario
+ * variants, imgenv_step_autoreset, imgenv_step_autoreset_device -- starts with ONE extra launch (k_final_obs, csrc/final_obs.h)
+ * that copies the present rows of the selected fields, for the robots that chain covers, into "final" arrays of the same shape
+ * and row numbering, and adds 1 to final_count[row] of each of them.  A step chain launches nothing.  Rows no reset has covered
+ * keep what they held (zero at first); nothing is cleared per step: final_count tells a fresh capture from an old one.  After
+ * imgenv_step_autoreset(_device) the rows with imgenv_out.step_all_down set hold this step's final observation.  The handle's
+ * first chain of launches captures nothing: there is no observation yet.
+ * The copy is taken from the kernels' working arrays, also under IMGENV_FLAG_FULL_REWRITE; the final arrays are no part of
+ * the output arena, so the output guards do not cover them.  Read-only for the caller; stream order as for imgenv_out.
+ * Memory: one more copy of the selected fields, R x the sum of their row sizes + 4 R.  The default set at 48 x 48 views, 360
+ * beams, ped_vec_len 71 and 48 x 48 pedestrian maps is 20 + 4608 + 2880 + 284 + 27648 + 18 = 35458 bytes per robot, 78 % of
+ * it ped_maps. */
+#define IMGENV_FINAL_VECTOR_STATES 1
+#define IMGENV_FINAL_SENSOR_MAPS 2
+#define IMGENV_FINAL_LASERS 4          /* needs use_laser */
+#define IMGENV_FINAL_PED_VECTOR_STATES 8
+#define IMGENV_FINAL_PED_MAPS 16
+#define IMGENV_FINAL_IS_COLLISIONS 32
+#define IMGENV_FINAL_IS_ARRIVES 64
+#define IMGENV_FINAL_STEP_DS 128
+#define IMGENV_FINAL_PED_MIN_DISTS 256
+#define IMGENV_FINAL_VIEW_MAPS 512     /* not with IMGENV_FLAG_NO_VIEW_MAPS */
+#define IMGENV_FINAL_LASERS_RAW 1024   /* needs use_laser */
+#define IMGENV_FINAL_STACKS 2048       /* the stacks of depth >= 2 of imgenv_stack_enable(), whole [K][frame] rows, as the
+                                        * step's push left them and before the reset restarts them */
+#define IMGENV_FINAL_PED_NORM 4096     /* imgenv_obs_post_out.ped_vector_norm */
+#define IMGENV_FINAL_IMAGE_STATE 511   /* the nine fields of ImageState (state.py:4-28): the first nine bits */
+#define IMGENV_FINAL_ALL 8191
+typedef struct imgenv_final_obs_cfg {
+    int32_t struct_size;          /* sizeof(imgenv_final_obs_cfg) */
+    int32_t fields;               /* IMGENV_FINAL_* bits, at least one */
+} imgenv_final_obs_cfg;
+typedef struct imgenv_final_obs_out {
+    int32_t struct_size;          /* on entry 0 or sizeof(imgenv_final_obs_out) */
+    int32_t n_local;              /* R */
+    /* shapes and types as the fields of imgenv_out; NULL where not selected */
+    float* vector_states;
+    uint16_t* sensor_maps;
+    double* lasers;
+    float* ped_vector_states;
+    float* ped_maps;
+    int8_t* is_collisions;
+    uint8_t* is_arrives;
+    double* step_ds;
+    double* ped_min_dists;
+    uint8_t* view_maps;
+    float* lasers_raw;
+    /* IMGENV_FINAL_STACKS: shapes as imgenv_stack_out's; NULL for a field whose depth is below 2 (its stack of depth 1 is the
+     * field itself: select the field) */
+    uint16_t* stack_sensor_maps;
+    float* stack_vector_states;
+    double* stack_lasers;
+    float* ped_vector_norm;       /* IMGENV_FINAL_PED_NORM: [R][1 + 7 max_ped] */
+    uint32_t* final_count;        /* [R] captures of the row so far */
+} imgenv_final_obs_out;
+/* Legal at any time; the memory is the library's and lives until imgenv_destroy().  IMGENV_EINVAL for a wrong struct_size, no
+ * or unknown bits, a field the handle does not produce (LASERS / LASERS_RAW without use_laser, VIEW_MAPS under
+ * IMGENV_FLAG_NO_VIEW_MAPS, STACKS on a handle none of whose stacks is deeper than 1), or a second call whose cfg differs from
+ * the first's (same cfg: nothing changes, same pointers).  IMGENV_ESTATE for STACKS before imgenv_stack_enable() and for
+ * PED_NORM before imgenv_obs_post_enable() with IMGENV_OBS_PED_NORM.  IMGENV_ENOMEM when the arrays cannot be allocated; the
+ * handle is then unchanged.  `out` may be NULL. */
+int imgenv_final_obs_enable(imgenv_t* h, const imgenv_final_obs_cfg* cfg, imgenv_final_obs_out* out);
+/* IMGENV_ESTATE before imgenv_final_obs_enable() */
+int imgenv_final_obs_outputs(imgenv_t* h, imgenv_final_obs_out* out);
+
 /* ---- map bank: several static maps in one handle, one of them per world and episode ----
  * The reference trains one policy over a set of maps: its trainer is started from several YAML files side by side
  * (create_launch.py:57-65, one node per (env_name, env_num) pair), each env process loads its own global_map.map_file

@@ -13,7 +13,8 @@ write before; --stack-compare alternates no stack / library stack / torch stack 
 alternates no statistics / library / torch over several rounds and writes the raw figures.  --episode-log adds the per-episode
 log on top of the statistics (imgenv_episode_log_enable: one more launch per reset chain); --episode-log-compare alternates no
 statistics / statistics / statistics + log over several rounds -- the device_reset variant runs a reset chain with every step, so
-its difference between the last two is what the log's launch costs a reset chain.
+its difference between the last two is what the log's launch costs a reset chain.  --final-obs-compare alternates the final
+observations (VecImageEnv(final_obs=True), imgenv_final_obs_enable: one more launch per reset chain) off / on in the same way.
 
 --wrappers table|clip feeds the policy's raw output (indices into a 28-row table, or float rows to be clipped) to
 VecImageEnv(wrappers=True): decode, speeds, normalised pedestrian vectors and close_to_human kept by the library;
@@ -188,13 +189,14 @@ def stack_depths(stack):
 
 
 def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, natives=(False, True, "device"), stack=None,
-            torch_stack=False, episodes=None, wrappers=None):
+            torch_stack=False, episodes=None, wrappers=None, final_obs=False):
     """robot-steps/s of VecImageEnv over `steps` steps, after the envs have drifted out of phase.  ``stack`` = (image_batch,
     state_batch, laser_batch): with the library's frame stacks, or (``torch_stack``) the same kept by torch ops on top;
     ``episodes`` = "library" | "torch" | "log": with the per-robot episode statistics, kept by the library or by ``TorchEpisodes``,
     or the library's with the episode log (a ring of 65536 records) on top;
     ``wrappers`` = (kind, by): kind "table" | "clip", by "none" (pre-decoded actions, nothing enabled) | "library"
-    (``wrappers=True`` fed the raw output) | "torch" (``TorchWrappers`` fed the raw output)"""
+    (``wrappers=True`` fed the raw output) | "torch" (``TorchWrappers`` fed the raw output); ``final_obs``: with the final
+    observations kept by the library (``VecImageEnv(final_obs=True)``: one more launch per reset chain)"""
     import torch
     from img_env_amd import worldgen
     from img_env_amd.vec_env import VecImageEnv
@@ -209,7 +211,7 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
         env = VecImageEnv(cfg, env_num=envs, seed=5, native_spawn=bool(native), device_reset=native == "device",
                           stack=stack is not None and not torch_stack, episode_stats=episodes in ("library", "log"),
                           episode_log=(1 << 16) if episodes == "log" else 0,
-                          wrappers=wrappers is not None and wrappers[1] == "library")
+                          wrappers=wrappers is not None and wrappers[1] == "library", final_obs=final_obs)
         te = TorchEpisodes(env) if episodes == "torch" else None
         ts = TorchStack(env, stack_depths(stack)) if stack is not None and torch_stack else None
         n = len(env)
@@ -370,6 +372,29 @@ def compare_episode_log(args, rounds=3):
             row[mode] = dict(us_per_step_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
         row["added_us_statistics"] = row["statistics"]["median"] - row["none"]["median"]
         row["added_us_log"] = row["log"]["median"] - row["statistics"]["median"]
+        summary.append(row)
+    return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, steps=args.steps, time_max=args.time_max,
+                rounds=rounds, runs=runs, summary=summary)
+
+
+def compare_final_obs(args, rounds=3):
+    """the final observations off / on, alternating, `rounds` times, per reset variant: the feature-off rounds are the baseline"""
+    natives = (True, "device")
+    runs = []
+    for rnd in range(rounds):
+        for mode in ("off", "on"):
+            r = measure(args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max, natives, final_obs=mode == "on")
+            for variant in ("native_spawn", "device_reset"):
+                runs.append(dict(round=rnd, mode=mode, variant=variant, us_per_step=r[variant]["us_per_step"],
+                                 env_resets_per_step=r[variant]["env_resets_per_step"]))
+                print(json.dumps(runs[-1]), flush=True)
+    summary = []
+    for variant in ("native_spawn", "device_reset"):
+        row = dict(variant=variant)
+        for mode in ("off", "on"):
+            v = [r["us_per_step"] for r in runs if r["variant"] == variant and r["mode"] == mode]
+            row[mode] = dict(us_per_step_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
+        row["added_us"] = row["on"]["median"] - row["off"]["median"]
         summary.append(row)
     return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, steps=args.steps, time_max=args.time_max,
                 rounds=rounds, runs=runs, summary=summary)
@@ -607,6 +632,8 @@ def main():
     ap.add_argument("--episode-log", action="store_true", help="the statistics and the per-episode log kept by the library")
     ap.add_argument("--episode-log-compare", action="store_true",
                     help="no statistics / statistics / statistics + episode log, alternating over --rounds rounds")
+    ap.add_argument("--final-obs-compare", action="store_true",
+                    help="the final observations (VecImageEnv(final_obs=True)) off / on, alternating over --rounds rounds")
     ap.add_argument("--wrappers", default=None, choices=("table", "clip"), help="the policy's raw output decoded by the library (wrappers=True)")
     ap.add_argument("--torch-wrappers", action="store_true", help="with --wrappers: the same kept with torch ops on a plain VecImageEnv")
     ap.add_argument("--wrappers-compare", action="store_true",
@@ -645,6 +672,13 @@ def main():
         return
     if args.wrappers_compare:
         res = compare_wrappers(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
+        return
+    if args.final_obs_compare:
+        res = compare_final_obs(args, args.rounds)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(res, fh, indent=1)

@@ -31,6 +31,7 @@
 #include "final_obs.h"
 #include "map_bank.h"
 #include "spawn_slot.h"
+#include "bank_host.h"
 
 static thread_local char g_err[512] = "";
 #define FAIL(code, ...)                              \
@@ -97,7 +98,6 @@ struct imgenv {
     int* d_map_cur = nullptr;       // [W] map of each world's current episode (nullptr: no bank)
     int* d_map_next = nullptr;      // [W] map each world's next reset starts from
     int maps_policy = 0;            // IMGENV_MAPS_*
-    const int* reset_map_ids = nullptr;  // host-placed resets under BY_PLACEMENT: the maps of the worlds being reset, in list order (for the call in progress)
     // track bank (include/imgenv.h: imgenv_tracks_add; csrc/track_bank.h)
     int n_track_sets = 0, trk_cap = 0;   // sets of the bank (0: none); records per pedestrian in it
     double *d_trk_traj = nullptr, *d_trk_traj_v = nullptr, *d_trk_pose3 = nullptr;
@@ -105,7 +105,6 @@ struct imgenv {
     int *d_trk_cur = nullptr, *d_trk_next = nullptr;  // [W] (nullptr: no bank)
     uint32_t* d_trk_count = nullptr;                  // [W]
     int tracks_policy = 0, tracks_repeat = 1;         // IMGENV_TRACKS_*
-    const int* reset_track_ids = nullptr;  // host-placed resets under BY_PLACEMENT: the sets of the worlds being reset, in list order (for the call in progress)
     std::vector<int> trk_fed, trk_fed_ids;  // the worlds of the reset being staged whose batch brought no tracks, and the host's draw for each (-1: the device resolves)
     // scenario bank (include/imgenv.h: imgenv_scenarios_add; csrc/scenario_bank.h)
     int n_scn = 0, scn_obst = 0;               // episodes of the bank (0: none); obstacles of each
@@ -117,7 +116,6 @@ struct imgenv {
     uint64_t scn_first = 0;
     int* d_scn_world = nullptr;                // [W] the scenario of each world's last HOST reset, -1: not from the bank
     unsigned long long* d_scn_mark = nullptr;  // [W] the placement number the world held at that reset (k_scenario_mark)
-    const int* reset_scn_ids = nullptr;        // imgenv_reset_worlds_scenarios: the scenarios of the worlds being reset, in list order (for the call in progress)
     // which policy the device's placements were filled under: epoch e covers the placement numbers from its start on, the start
     // being the device's count when imgenv_scenarios_policy was queued -- copied on the device, read at imgenv_world_scenarios
     struct ScnEpoch { int policy; uint64_t first; };
@@ -509,6 +507,23 @@ static int dev_upload(imgenv* h, const T** out, const std::vector<T>& v) {
     if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
     *out = p;
     return 0;
+}
+// DevTxn (bank_host.h) over the device: what imgenv_maps_add, imgenv_tracks_add, imgenv_scenarios_add, imgenv_episode_log_enable and
+// imgenv_final_obs_enable allocate through, each committing to h->allocs once everything is there
+struct HipApi {
+    static const char* text(hipError_t e) { return e == hipSuccess ? nullptr : ((void)hipGetLastError(), hipGetErrorString(e)); }
+    static const char* malloc(void** p, size_t bytes) { return text(hipMalloc(p, bytes)); }
+    static const char* free(void* p) { return text(hipFree(p)); }
+    static const char* memset(void* p, int byte, size_t bytes) { return text(hipMemset(p, byte, bytes)); }
+    static const char* memcpy(void* dst, const void* src, size_t bytes, bool from_device) {
+        return text(hipMemcpy(dst, src, bytes, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    }
+};
+// (the "after the first reset" refusals of imgenv_maps_add, imgenv_tracks_add and imgenv_stack_enable)
+static bool any_world_reset(const imgenv* h) {
+    bool any = h->has_reset;
+    for (char r : h->world_ready) any = any || r;
+    return any;
 }
 // inside imgenv_create once the handle exists: a failing HIP call must not leak the handle and what it has allocated so far
 #define HIPCHK_H(expr)                                                                                        \
@@ -2182,7 +2197,7 @@ static int put_world_rvo(imgenv* h, int k) {
 }
 
 // Host half of one world's reset: its obstacles, pedestrians and robots go into the staging chunks.
-static int stage_world(imgenv* h, int k, int q_list, const imgenv_reset_batch* b, hipStream_t st) {
+static int stage_world(imgenv* h, int k, int q_list, const imgenv_reset_batch* b, const ResetChoices& choices, hipStream_t st) {
     DevWorld& d = h->d;
     const int W = h->W, Rw = h->Rw, Pw = h->Pw, P = h->P;
     const int g_lo = k * Rw, p_lo = k * Pw;  // first robot / pedestrian of the world
@@ -2213,7 +2228,7 @@ static int stage_world(imgenv* h, int k, int q_list, const imgenv_reset_batch* b
         if (dataset && !b->ped_traj_v && !fed) FAIL(IMGENV_EINVAL, "dataset scene: ped_traj_v is missing from the reset batch");
         if (fed) {  // (the batch's own pedestrian arrays are ignored; reset_ped's pass over the world writes zeros that the install replaces)
             h->trk_fed.push_back(k);
-            h->trk_fed_ids.push_back(h->reset_track_ids ? h->reset_track_ids[q_list] : -1);
+            h->trk_fed_ids.push_back(choices.track_ids ? choices.track_ids[q_list] : -1);
             memset(h->pin_ped3 + (size_t)q_list * Pw * 3, 0, sizeof(double) * 3 * (size_t)Pw);
         } else if (dataset && h->d_trk_cur) {  // its own tracks: imgenv_world_tracks says -1, the CYCLE count stays
             static const int minus_one = -1;
@@ -2403,7 +2418,7 @@ static TrackSel track_sel(const imgenv* h) {
 }
 
 static int sfm_ahead_drop(imgenv* h, hipStream_t st);
-static int reset_launch(imgenv* h, const int* list, int n, hipStream_t st, int whole) {
+static int reset_launch(imgenv* h, const int* list, int n, const ResetChoices& choices, hipStream_t st, int whole) {
     DevWorld& d = h->d;
     if (int rc = sfm_ahead_drop(h, st)) return rc;  // (a reset writes the live crowd: positions, waypoints)
     if (h->sd_ready) {  // a host-side reset draws obstacles the device-side restore does not know: whole-map restore next time
@@ -2452,10 +2467,10 @@ static int reset_launch(imgenv* h, const int* list, int n, hipStream_t st, int w
         a.n_worlds = d.act_nw;
         a.static_map = h->d_static_map;
         a.maps = map_sel(h);
-        if (h->d_map_cur && h->reset_map_ids) {
+        if (h->d_map_cur && choices.map_ids) {
             unsigned char* ids = nullptr;
             RTRY(stage_room(h, sizeof(int) * (size_t)d.act_nw, &ids));
-            memcpy(ids, h->reset_map_ids, sizeof(int) * (size_t)d.act_nw);
+            memcpy(ids, choices.map_ids, sizeof(int) * (size_t)d.act_nw);
             a.maps.ids = (const int*)ids;
         }
         a.rob3 = h->pin_rob3;
@@ -2488,10 +2503,10 @@ static int reset_launch(imgenv* h, const int* list, int n, hipStream_t st, int w
     if (h->d_scn_world) {  // a handle with a scenario bank: what imgenv_world_scenarios answers for the worlds of this reset
         const int n_mark = list ? n : h->W;
         const int* ids = nullptr;
-        if (h->reset_scn_ids) {
+        if (choices.scn_ids) {
             unsigned char* pi = nullptr;
             RTRY(stage_room(h, sizeof(int) * (size_t)n_mark, &pi));
-            memcpy(pi, h->reset_scn_ids, sizeof(int) * (size_t)n_mark);
+            memcpy(pi, choices.scn_ids, sizeof(int) * (size_t)n_mark);
             ids = (const int*)pi;
         }
         k_scenario_mark<<<dim3((unsigned)((n_mark + 255) / 256)), dim3(256), 0, st>>>(h->d_scn_world, h->d_scn_mark,
@@ -2507,9 +2522,9 @@ static int reset_launch(imgenv* h, const int* list, int n, hipStream_t st, int w
     return rc ? rc : rc_end;
 }
 
-extern "C" int imgenv_reset(imgenv_t* h, const imgenv_reset_batch* b, void* stream) {
+// every world of the handle from one batch; `choices` hold one entry per world (a handle of one world: what its host-placed reset drew)
+static int reset_all(imgenv* h, const imgenv_reset_batch* b, const ResetChoices& choices, hipStream_t st) {
     if (int rc = reset_checks(h, 1, b, h ? h->P : 0)) return rc;
-    hipStream_t st = (hipStream_t)stream;
     if (int rc = outputs_verify(h, st)) return rc;
     RTRY(stage_begin(h));
     RTRY(reset_blocks(h, h->W, nullptr));
@@ -2525,7 +2540,7 @@ extern "C" int imgenv_reset(imgenv_t* h, const imgenv_reset_batch* b, void* stre
             sub.ped_traj = b->ped_traj ? b->ped_traj + (size_t)k * h->Pw * b->ped_traj_cap * 3 : nullptr;
             sub.ped_traj_v = b->ped_traj_v ? b->ped_traj_v + (size_t)k * h->Pw * b->ped_traj_cap * 2 : nullptr;
         }
-        RTRY(stage_world(h, k, k, &sub, st));
+        RTRY(stage_world(h, k, k, &sub, choices, st));
         h->world_epoch[k] = 0;
         h->world_ready[k] = 1;
     }
@@ -2535,26 +2550,20 @@ extern "C" int imgenv_reset(imgenv_t* h, const imgenv_reset_batch* b, void* stre
     }
     h->elapsed = 0;  // TimeLimitWrapper.reset (base.py:229-231)
     h->dev_reset_used = false;  // every world's host copy is current again
-    RTRY(reset_launch(h, nullptr, 0, st, 1));  // no host wait: the copies read the handle's pinned chunks
+    RTRY(reset_launch(h, nullptr, 0, choices, st, 1));  // no host wait: the copies read the handle's pinned chunks
     h->has_reset = true;
     return IMGENV_OK;
 }
 
-extern "C" int imgenv_reset_worlds(imgenv_t* h, int32_t n, const int32_t* worlds, const imgenv_reset_batch* batches, void* stream) {
+extern "C" int imgenv_reset(imgenv_t* h, const imgenv_reset_batch* b, void* stream) { return reset_all(h, b, ResetChoices(), (hipStream_t)stream); }
+
+// the listed worlds, each from its batch; `choices` in list order
+static int reset_worlds(imgenv* h, int n, const int32_t* worlds, const imgenv_reset_batch* batches, const ResetChoices& choices, hipStream_t st) {
     if (n <= 0) return h ? IMGENV_OK : IMGENV_EINVAL;
     if (!worlds) FAIL(IMGENV_EINVAL, "null argument");
     if (int rc = reset_checks(h, n, batches, h ? h->Pw : 0)) return rc;
-    if (h->W == 1) {
-        if (n != 1 || worlds[0] != 0) FAIL(IMGENV_EINVAL, "world out of range (n_worlds 1)");
-        return imgenv_reset(h, batches, stream);
-    }
-    std::vector<char> seen(h->W, 0);
-    for (int q = 0; q < n; q++) {
-        if (worlds[q] < 0 || worlds[q] >= h->W) FAIL(IMGENV_EINVAL, "world %d out of range (n_worlds %d)", worlds[q], h->W);
-        if (seen[worlds[q]]) FAIL(IMGENV_EINVAL, "world %d listed twice", worlds[q]);
-        seen[worlds[q]] = 1;
-    }
-    hipStream_t st = (hipStream_t)stream;
+    if (!world_list_check(h->W, n, worlds, nullptr, 0, nullptr, &g_err)) return IMGENV_EINVAL;
+    if (h->W == 1) return reset_all(h, batches, choices, st);  // (the list is {0}: one entry of every choice)
     if (int rc = outputs_verify(h, st)) return rc;
     static const bool trace = getenv("IMGENV_TRACE_RESET") != nullptr;
     std::chrono::steady_clock::time_point tp[4];
@@ -2564,12 +2573,12 @@ extern "C" int imgenv_reset_worlds(imgenv_t* h, int32_t n, const int32_t* worlds
     h->oinst.clear();
     if (trace) tp[1] = std::chrono::steady_clock::now();
     for (int q = 0; q < n; q++) {
-        RTRY(stage_world(h, worlds[q], q, batches + q, st));
+        RTRY(stage_world(h, worlds[q], q, batches + q, choices, st));
         h->world_epoch[worlds[q]] = h->elapsed;  // its TimeLimitWrapper starts over
         h->world_ready[worlds[q]] = 1;
     }
     if (trace) tp[2] = std::chrono::steady_clock::now();
-    RTRY(reset_launch(h, worlds, n, st, 0));
+    RTRY(reset_launch(h, worlds, n, choices, st, 0));
     if (trace) {
         tp[3] = std::chrono::steady_clock::now();
         auto us = [&](int a_, int b_) { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(tp[b_] - tp[a_]).count() * 1e-3; };
@@ -2585,6 +2594,16 @@ extern "C" int imgenv_reset_worlds(imgenv_t* h, int32_t n, const int32_t* worlds
     for (char r : h->world_ready) all = all && r;
     h->has_reset = all;
     return IMGENV_OK;
+}
+
+extern "C" int imgenv_reset_worlds(imgenv_t* h, int32_t n, const int32_t* worlds, const imgenv_reset_batch* batches, void* stream) {
+    return reset_worlds(h, n, worlds, batches, ResetChoices(), (hipStream_t)stream);
+}
+
+// the draws of n host-placed resets from their seeds (null: seed0 + q) under the handle's BY_PLACEMENT policies
+static PlacementDraws placement_draws(const imgenv* h, int n, const uint64_t* seeds, uint64_t seed0) {
+    return PlacementDraws(n, seeds, seed0, h->d_map_cur && h->maps_policy == IMGENV_MAPS_BY_PLACEMENT ? h->n_maps : 0,
+                          h->d_trk_cur && h->tracks_policy == IMGENV_TRACKS_BY_PLACEMENT ? h->n_track_sets : 0);
 }
 
 static int spawn_cfg_check(const imgenv_spawn_cfg* c) {
@@ -2638,20 +2657,8 @@ extern "C" int imgenv_reset_worlds_spawn(imgenv_t* h, int32_t n, const int32_t* 
         if (const char* why = spawn_world(*cfg, seeds[q], outs[q])) FAIL(IMGENV_EINVAL, "spawn of world %d: %s", worlds[q], why);
         batches[q] = outs[q].batch;
     }
-    std::vector<int> ids;
-    if (h->d_map_cur && h->maps_policy == IMGENV_MAPS_BY_PLACEMENT) {  // the placement's seed also draws the map
-        for (int q = 0; q < n; q++) ids.push_back(map_for_placement(seeds[q], h->n_maps));
-        h->reset_map_ids = ids.data();
-    }
-    std::vector<int> sets;
-    if (h->d_trk_cur && h->tracks_policy == IMGENV_TRACKS_BY_PLACEMENT) {  // ... and the recorded crowd
-        for (int q = 0; q < n; q++) sets.push_back(tracks_for_placement(seeds[q], h->n_track_sets));
-        h->reset_track_ids = sets.data();
-    }
-    const int rc = imgenv_reset_worlds(h, n, worlds, batches.data(), stream);
-    h->reset_map_ids = nullptr;
-    h->reset_track_ids = nullptr;
-    return rc;
+    const PlacementDraws draws = placement_draws(h, n, seeds, 0);  // the placement's seed also draws the map and the recorded crowd
+    return reset_worlds(h, n, worlds, batches.data(), draws.choices(), (hipStream_t)stream);
 }
 
 extern "C" int imgenv_reset_world(imgenv_t* h, int32_t world, const imgenv_reset_batch* b, void* stream) {
@@ -2664,9 +2671,7 @@ extern "C" int32_t imgenv_map_for_placement(uint64_t seed, int32_t n_maps) { ret
 extern "C" int imgenv_maps_add(imgenv_t* h, int32_t n, const uint8_t* maps, int32_t Hg, int32_t Wg) {
     if (!h || !maps || n < 1) FAIL(IMGENV_EINVAL, "null argument or no maps");
     if (h->n_maps > 1) FAIL(IMGENV_ESTATE, "imgenv_maps_add has already been called on this handle");
-    bool any_reset = h->has_reset;
-    for (char r : h->world_ready) any_reset = any_reset || r;
-    if (any_reset) FAIL(IMGENV_ESTATE, "imgenv_maps_add after the first reset");
+    if (any_world_reset(h)) FAIL(IMGENV_ESTATE, "imgenv_maps_add after the first reset");
     if (h->RL != h->R) FAIL(IMGENV_EINVAL, "imgenv_maps_add on a robot shard is not supported");
     if (Hg != h->Hg_in || Wg != h->Wg_in)
         FAIL(IMGENV_EINVAL, "maps of %d x %d pixels, the handle was created with %d x %d: one size per handle", Hg, Wg, h->Hg_in, h->Wg_in);
@@ -2677,59 +2682,34 @@ extern "C" int imgenv_maps_add(imgenv_t* h, int32_t n, const uint8_t* maps, int3
     const bool resize = h->Hg != Hg || h->Wg != Wg || h->cfg.global_resolution != h->cfg.view_resolution;
     DevWorld& d = h->d;
     // everything is allocated and filled before the handle changes: a failure leaves it on its one map
+    DevTxn<HipApi> txn;
     uint8_t* bank = nullptr;
     uint8_t* crops = nullptr;
     int *cur = nullptr, *next = nullptr;
-    auto undo = [&]() { dev_free(h, bank); dev_free(h, crops); dev_free(h, cur); dev_free(h, next); };
-#define MTRY(expr, code)                                                          \
-    do {                                                                          \
-        if (int rc_ = (expr)) { undo(); return (code) ? (code) : rc_; }           \
-    } while (0)
-#define MHIP(expr)                                                                                          \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            snprintf(g_err, sizeof(g_err), "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            undo();                                                                                         \
-            return e_ == hipErrorOutOfMemory ? IMGENV_ENOMEM : IMGENV_EDEVICE;                              \
-        }                                                                                                   \
-    } while (0)
-    {
-        void* p = nullptr;
-        if (hipMalloc(&p, stride * (size_t)n_maps) != hipSuccess) FAIL(IMGENV_ENOMEM, "no device memory for a bank of %d maps", n_maps);
-        h->allocs.push_back(p);
-        bank = (uint8_t*)p;
-    }
-    MHIP(hipMemset(bank, 0, stride * (size_t)n_maps));
-    MHIP(hipMemcpy(bank, h->d_static_map, stride, hipMemcpyDeviceToDevice));  // map 0: the map of imgenv_create
+    txn.room(&bank, stride * (size_t)n_maps, 0);
+    txn.copy(bank, h->d_static_map, stride);  // map 0: the map of imgenv_create
     if (d.crop_map) {
-        void* p = nullptr;
-        if (hipMalloc(&p, (size_t)d.crop_ws * n_maps) != hipSuccess) {
-            undo();
-            FAIL(IMGENV_ENOMEM, "no device memory for the crop images of %d maps", n_maps);
-        }
-        h->allocs.push_back(p);
-        crops = (uint8_t*)p;
-        MHIP(hipMemcpy(crops, d.static_crop, (size_t)d.crop_ws, hipMemcpyDeviceToDevice));
+        txn.room(&crops, (size_t)d.crop_ws * n_maps, 0);
+        txn.copy(crops, d.static_crop, (size_t)d.crop_ws);
     }
     std::vector<uint8_t> resized, tiled;
-    for (int k = 0; k < n; k++) {
+    for (int k = 0; k < n && txn.code() == IMGENV_OK; k++) {
         const uint8_t* src = maps + (size_t)k * G_in;
         if (resize) {  // GridMap::read_image (grid_map.cpp:28-38), as imgenv_create does for the first map
             resized.resize(G);
             cv_resize_u8(false, src, Hg, Wg, resized.data(), h->Hg, h->Wg);
             src = resized.data();
         }
-        MHIP(hipMemcpy(bank + (size_t)(k + 1) * stride, src, G, hipMemcpyHostToDevice));
+        txn.put(bank + (size_t)(k + 1) * stride, src, G);
         if (crops) {
             tile_crop(src, h->Hg, h->Wg, d.crop_wt, (size_t)d.crop_ws, tiled);
-            MHIP(hipMemcpy(crops + (size_t)(k + 1) * d.crop_ws, tiled.data(), tiled.size(), hipMemcpyHostToDevice));
+            txn.put(crops + (size_t)(k + 1) * d.crop_ws, tiled.data(), tiled.size());
         }
     }
-    MTRY(dev_alloc(h, &cur, (size_t)W), IMGENV_ENOMEM);   // (zeroed: every world starts on map 0)
-    MTRY(dev_alloc(h, &next, (size_t)W), IMGENV_ENOMEM);
-#undef MTRY
-#undef MHIP
+    txn.room(&cur, (size_t)W, 0);  // (zeroed: every world starts on map 0)
+    txn.room(&next, (size_t)W, 0);
+    if (txn.code()) FAIL(txn.code(), "imgenv_maps_add: a bank of %d maps: %s", n_maps, txn.error());
+    txn.commit(h->allocs);
     // (nothing has been launched on this handle yet -- no reset has happened -- so the single-map buffers can go)
     dev_free(h, h->d_static_map);
     h->d_static_map = bank;
@@ -2744,33 +2724,37 @@ extern "C" int imgenv_maps_add(imgenv_t* h, int32_t n, const uint8_t* maps, int3
     return IMGENV_OK;
 }
 
-// next[worlds[q]] = ids[q], from page-locked host memory
-__global__ void k_maps_select(int* __restrict__ next, const int* __restrict__ worlds, const int* __restrict__ ids, int n) {
-    const int q = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (q < n) next[worlds[q]] = ids[q];
-}
-
-extern "C" int imgenv_world_maps_set(imgenv_t* h, int32_t n, const int32_t* worlds, const int32_t* map_ids, void* stream) {
-    if (!h || n < 0 || (n > 0 && (!worlds || !map_ids))) FAIL(IMGENV_EINVAL, "null argument");
-    std::vector<char> seen(h->W, 0);
-    for (int q = 0; q < n; q++) {  // everything is checked before anything is applied
-        if (worlds[q] < 0 || worlds[q] >= h->W) FAIL(IMGENV_EINVAL, "world %d out of range (n_worlds %d)", worlds[q], h->W);
-        if (seen[worlds[q]]) FAIL(IMGENV_EINVAL, "world %d listed twice", worlds[q]);
-        seen[worlds[q]] = 1;
-        if (map_ids[q] < 0 || map_ids[q] >= h->n_maps) FAIL(IMGENV_EINVAL, "map %d out of range (the handle holds %d)", map_ids[q], h->n_maps);
-    }
-    if (n == 0 || !h->d_map_next) return IMGENV_OK;  // (one map: every id is 0)
+// imgenv_world_maps_set / imgenv_world_tracks_set behind their checks: next[worlds[q]] = ids[q] for the n > 0 listed worlds, by one
+// small launch on the caller's stream that reads the lists from page-locked memory
+static int world_select(imgenv* h, int* next, int n, const int32_t* worlds, const int32_t* ids, hipStream_t st) {
     HIPCHK(hipSetDevice(h->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
     RTRY(stage_begin(h));
     unsigned char* p = nullptr;
     RTRY(stage_room(h, sizeof(int) * 2 * (size_t)n, &p));
     int* pin = (int*)p;
     memcpy(pin, worlds, sizeof(int) * (size_t)n);
-    memcpy(pin + n, map_ids, sizeof(int) * (size_t)n);
-    k_maps_select<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(h->d_map_next, pin, pin + n, n);
+    memcpy(pin + n, ids, sizeof(int) * (size_t)n);
+    k_world_select<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(next, pin, pin + n, n);
     HIPCHK(hipGetLastError());
     return stage_end(h, st);
+}
+
+// imgenv_world_maps / imgenv_world_tracks: the [W] array `cur` once the stream has drained; a handle without that bank answers `fallback`
+static int world_ids_read(imgenv* h, const int* cur, int fallback, int32_t* out, hipStream_t st) {
+    if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(st));
+    if (int rc = check_device_flags(h)) return rc;
+    if (!cur) std::fill_n(out, h->W, fallback);
+    else HIPCHK(hipMemcpy(out, cur, sizeof(int) * (size_t)h->W, hipMemcpyDeviceToHost));
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_world_maps_set(imgenv_t* h, int32_t n, const int32_t* worlds, const int32_t* map_ids, void* stream) {
+    if (!h || n < 0 || (n > 0 && (!worlds || !map_ids))) FAIL(IMGENV_EINVAL, "null argument");
+    if (!world_list_check(h->W, n, worlds, map_ids, h->n_maps, "map", &g_err)) return IMGENV_EINVAL;  // (before anything is applied)
+    if (n == 0 || !h->d_map_next) return IMGENV_OK;  // (one map: every id is 0)
+    return world_select(h, h->d_map_next, n, worlds, map_ids, (hipStream_t)stream);
 }
 
 extern "C" int imgenv_maps_policy(imgenv_t* h, int32_t policy) {
@@ -2781,39 +2765,17 @@ extern "C" int imgenv_maps_policy(imgenv_t* h, int32_t policy) {
 }
 
 extern "C" int imgenv_world_maps(imgenv_t* h, int32_t* map_ids, void* stream) {
-    if (!h || !map_ids) FAIL(IMGENV_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    if (int rc = check_device_flags(h)) return rc;
-    if (!h->d_map_cur) {
-        for (int k = 0; k < h->W; k++) map_ids[k] = 0;
-        return IMGENV_OK;
-    }
-    HIPCHK(hipMemcpy(map_ids, h->d_map_cur, sizeof(int) * (size_t)h->W, hipMemcpyDeviceToHost));
-    return IMGENV_OK;
+    return world_ids_read(h, h ? h->d_map_cur : nullptr, 0, map_ids, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------- track bank
 extern "C" int32_t imgenv_tracks_for_placement(uint64_t seed, int32_t n_sets) { return tracks_for_placement(seed, n_sets); }
 
-// room on the device that fails softly (imgenv_tracks_add undoes what it has got)
-template <typename T>
-static bool tracks_room(imgenv* h, T** out, size_t n, int fill) {
-    void* p = nullptr;
-    const size_t bytes = sizeof(T) * (n ? n : 1);
-    if (hipMalloc(&p, bytes) != hipSuccess) return false;
-    h->allocs.push_back(p);
-    *out = (T*)p;
-    return hipMemset(p, fill, bytes) == hipSuccess;
-}
-
 extern "C" int imgenv_tracks_add(imgenv_t* h, int32_t n_sets, int32_t cap, const double* ped_pose, const double* ped_traj,
                                  const double* ped_traj_v, const int32_t* ped_traj_len) {
     if (!h || !ped_pose || !ped_traj || !ped_traj_v || !ped_traj_len) FAIL(IMGENV_EINVAL, "null argument");
     if (h->n_track_sets > 0) FAIL(IMGENV_ESTATE, "imgenv_tracks_add has already been called on this handle");
-    bool any_reset = h->has_reset;
-    for (char r : h->world_ready) any_reset = any_reset || r;
-    if (any_reset) FAIL(IMGENV_ESTATE, "imgenv_tracks_add after the first reset");
+    if (any_world_reset(h)) FAIL(IMGENV_ESTATE, "imgenv_tracks_add after the first reset");
     if (h->cfg.ped_scene_type != IMGENV_SCENE_DATASET) FAIL(IMGENV_EINVAL, "imgenv_tracks_add: the pedestrian scene is not IMGENV_SCENE_DATASET");
     if (h->Pw < 1) FAIL(IMGENV_EINVAL, "imgenv_tracks_add: the handle has no pedestrians");
     if (h->RL != h->R) FAIL(IMGENV_EINVAL, "imgenv_tracks_add on a robot shard is not supported");
@@ -2835,24 +2797,25 @@ extern "C" int imgenv_tracks_add(imgenv_t* h, int32_t n_sets, int32_t cap, const
     double *b_traj = nullptr, *b_traj_v = nullptr, *b_pose3 = nullptr, *t_traj = nullptr, *t_traj_v = nullptr;
     int *b_len = nullptr, *cur = nullptr, *next = nullptr;
     uint32_t* count = nullptr;
-    auto undo = [&]() {
-        dev_free(h, b_traj); dev_free(h, b_traj_v); dev_free(h, b_pose3); dev_free(h, t_traj); dev_free(h, t_traj_v);
-        dev_free(h, b_len); dev_free(h, cur); dev_free(h, next); dev_free(h, count);
-    };
-    auto room = [&](auto** out, size_t n, int fill) -> bool { return tracks_room(h, out, n, fill); };
+    DevTxn<HipApi> txn;
     const size_t P = (size_t)h->P, W = (size_t)h->W;
-    const bool ok = room(&b_traj, traj.size(), 0) && room(&b_traj_v, traj_v.size(), 0) && room(&b_pose3, pose3.size(), 0) && room(&b_len, len.size(), 0) &&
-                    room(&cur, W, 0xFF) && room(&next, W, 0) && room(&count, W, 0) &&
-                    (h->traj_cap >= stride || (room(&t_traj, P * stride * 3, 0) && room(&t_traj_v, P * stride * 3, 0))) &&
-                    hipMemcpy(b_traj, traj.data(), 8 * traj.size(), hipMemcpyHostToDevice) == hipSuccess &&
-                    hipMemcpy(b_traj_v, traj_v.data(), 8 * traj_v.size(), hipMemcpyHostToDevice) == hipSuccess &&
-                    hipMemcpy(b_pose3, pose3.data(), 8 * pose3.size(), hipMemcpyHostToDevice) == hipSuccess &&
-                    hipMemcpy(b_len, len.data(), 4 * len.size(), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        undo();
-        FAIL(IMGENV_ENOMEM, "no device memory for a bank of %d track sets", n_sets);
+    txn.room(&b_traj, traj.size(), 0);
+    txn.room(&b_traj_v, traj_v.size(), 0);
+    txn.room(&b_pose3, pose3.size(), 0);
+    txn.room(&b_len, len.size(), 0);
+    txn.room(&cur, W, 0xFF);
+    txn.room(&next, W, 0);
+    txn.room(&count, W, 0);
+    if (h->traj_cap < stride) {
+        txn.room(&t_traj, P * stride * 3, 0);
+        txn.room(&t_traj_v, P * stride * 3, 0);
     }
+    txn.put(b_traj, traj.data(), 8 * traj.size());
+    txn.put(b_traj_v, traj_v.data(), 8 * traj_v.size());
+    txn.put(b_pose3, pose3.data(), 8 * pose3.size());
+    txn.put(b_len, len.data(), 4 * len.size());
+    if (txn.code()) FAIL(txn.code(), "imgenv_tracks_add: a bank of %d track sets: %s", n_sets, txn.error());
+    txn.commit(h->allocs);
     if (t_traj) {  // the per-world tables with room for a set, so that the first reset finds them (no reset has happened: nothing reads the old ones)
         dev_free(h, h->d_traj);
         dev_free(h, h->d_traj_v);
@@ -2873,25 +2836,9 @@ extern "C" int imgenv_tracks_add(imgenv_t* h, int32_t n_sets, int32_t cap, const
 extern "C" int imgenv_world_tracks_set(imgenv_t* h, int32_t n, const int32_t* worlds, const int32_t* set_ids, void* stream) {
     if (!h || n < 0 || (n > 0 && (!worlds || !set_ids))) FAIL(IMGENV_EINVAL, "null argument");
     if (!h->d_trk_next) FAIL(IMGENV_ESTATE, "imgenv_world_tracks_set: the handle has no track bank (imgenv_tracks_add)");
-    std::vector<char> seen(h->W, 0);
-    for (int q = 0; q < n; q++) {  // everything is checked before anything is applied
-        if (worlds[q] < 0 || worlds[q] >= h->W) FAIL(IMGENV_EINVAL, "world %d out of range (n_worlds %d)", worlds[q], h->W);
-        if (seen[worlds[q]]) FAIL(IMGENV_EINVAL, "world %d listed twice", worlds[q]);
-        seen[worlds[q]] = 1;
-        if (set_ids[q] < 0 || set_ids[q] >= h->n_track_sets) FAIL(IMGENV_EINVAL, "track set %d out of range (the handle holds %d)", set_ids[q], h->n_track_sets);
-    }
+    if (!world_list_check(h->W, n, worlds, set_ids, h->n_track_sets, "track set", &g_err)) return IMGENV_EINVAL;  // (before anything is applied)
     if (n == 0) return IMGENV_OK;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
-    RTRY(stage_begin(h));
-    unsigned char* p = nullptr;
-    RTRY(stage_room(h, sizeof(int) * 2 * (size_t)n, &p));
-    int* pin = (int*)p;
-    memcpy(pin, worlds, sizeof(int) * (size_t)n);
-    memcpy(pin + n, set_ids, sizeof(int) * (size_t)n);
-    k_tracks_select<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(h->d_trk_next, pin, pin + n, n);
-    HIPCHK(hipGetLastError());
-    return stage_end(h, st);
+    return world_select(h, h->d_trk_next, n, worlds, set_ids, (hipStream_t)stream);
 }
 
 extern "C" int imgenv_tracks_policy(imgenv_t* h, int32_t policy, int32_t repeat) {
@@ -2909,16 +2856,7 @@ extern "C" int imgenv_tracks_policy(imgenv_t* h, int32_t policy, int32_t repeat)
 }
 
 extern "C" int imgenv_world_tracks(imgenv_t* h, int32_t* set_ids, void* stream) {
-    if (!h || !set_ids) FAIL(IMGENV_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    if (int rc = check_device_flags(h)) return rc;
-    if (!h->d_trk_cur) {
-        for (int k = 0; k < h->W; k++) set_ids[k] = -1;
-        return IMGENV_OK;
-    }
-    HIPCHK(hipMemcpy(set_ids, h->d_trk_cur, sizeof(int) * (size_t)h->W, hipMemcpyDeviceToHost));
-    return IMGENV_OK;
+    return world_ids_read(h, h ? h->d_trk_cur : nullptr, -1, set_ids, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------- scenario bank
@@ -2982,16 +2920,16 @@ extern "C" int imgenv_scenarios_add(imgenv_t* h, int32_t n, int32_t n_obstacles,
     int* scn = nullptr;
     unsigned long long *mark = nullptr, *starts = nullptr;
     const size_t starts_cap = 256;
-    auto room = [&](auto** out, size_t cnt, int fill) -> bool { return tracks_room(h, out, cnt, fill); };
-    const bool ok = room(&da, agents.size(), 0) && room(&dob, obst.size(), 0) && room(&scn, (size_t)h->W, 0xFF) && room(&mark, (size_t)h->W, 0xFF) &&
-                    room(&starts, starts_cap, 0) &&
-                    (agents.empty() || hipMemcpy(da, agents.data(), sizeof(SlotAgent) * agents.size(), hipMemcpyHostToDevice) == hipSuccess) &&
-                    (obst.empty() || hipMemcpy(dob, obst.data(), sizeof(SlotObstacle) * obst.size(), hipMemcpyHostToDevice) == hipSuccess);
-    if (!ok) {  // everything is allocated and filled before the handle changes: a failure leaves it without a bank
-        (void)hipGetLastError();
-        dev_free(h, da); dev_free(h, dob); dev_free(h, scn); dev_free(h, mark); dev_free(h, starts);
-        FAIL(IMGENV_ENOMEM, "no device memory for a bank of %d scenarios", n);
-    }
+    DevTxn<HipApi> txn;  // everything is allocated and filled before the handle changes: a failure leaves it without a bank
+    txn.room(&da, agents.size(), 0);
+    txn.room(&dob, obst.size(), 0);
+    txn.room(&scn, (size_t)h->W, 0xFF);
+    txn.room(&mark, (size_t)h->W, 0xFF);
+    txn.room(&starts, starts_cap, 0);
+    txn.put(da, agents.data(), sizeof(SlotAgent) * agents.size());
+    txn.put(dob, obst.data(), sizeof(SlotObstacle) * obst.size());
+    if (txn.code()) FAIL(txn.code(), "imgenv_scenarios_add: a bank of %d scenarios: %s", n, txn.error());
+    txn.commit(h->allocs);
     h->scn_agents.swap(agents);
     h->scn_obstacles.swap(obst);
     h->d_scn_agents = da; h->d_scn_obst = dob; h->d_scn_world = scn; h->d_scn_mark = mark;
@@ -3039,8 +2977,7 @@ extern "C" int imgenv_scenarios_policy(imgenv_t* h, int32_t policy, uint64_t fir
 extern "C" int imgenv_reset_worlds_scenarios(imgenv_t* h, int32_t n, const int32_t* worlds, const int32_t* ids, void* stream) {
     if (!h || n < 0 || (n > 0 && (!worlds || !ids))) FAIL(IMGENV_EINVAL, "null argument");
     if (h->n_scn < 1) FAIL(IMGENV_ESTATE, "imgenv_reset_worlds_scenarios: the handle has no scenario bank (imgenv_scenarios_add)");
-    for (int q = 0; q < n; q++)
-        if (ids[q] < 0 || ids[q] >= h->n_scn) FAIL(IMGENV_EINVAL, "scenario %d out of range (the handle holds %d)", ids[q], h->n_scn);
+    if (!world_list_check(h->W, n, worlds, ids, h->n_scn, "scenario", &g_err)) return IMGENV_EINVAL;  // (the ids index the bank's host copy below)
     if (n == 0) return IMGENV_OK;
     const int Rw = h->Rw, Pw = h->Pw, O = h->scn_obst, na = Rw + Pw;
     // the batches of imgenv_reset_worlds, out of the bank's host copy (trajectories of two points, as imgenv_spawn lays them out)
@@ -3064,10 +3001,21 @@ extern "C" int imgenv_reset_worlds_scenarios(imgenv_t* h, int32_t n, const int32
         b.ped_traj_len = pl.data() + q * Pw; b.ped_traj = pt.data() + q * Pw * 6;
         b.ped_traj_cap = 2;
     }
-    h->reset_scn_ids = ids;
-    const int rc = imgenv_reset_worlds(h, n, worlds, batches.data(), stream);
-    h->reset_scn_ids = nullptr;
-    return rc;
+    return reset_worlds(h, n, worlds, batches.data(), ResetChoices{nullptr, nullptr, ids}, (hipStream_t)stream);
+}
+
+// Which scenario the device handed out for a placement number (imgenv_world_scenarios, imgenv_episode_log_read): the starts of the
+// policy's epochs, as the device counted them, pulled once per call ...
+static int scenario_starts_pull(const imgenv* h, std::vector<unsigned long long>& starts) {
+    starts.resize(h->scn_epochs.size());
+    HIPCHK(hipMemcpy(starts.data(), h->d_scn_starts, sizeof(unsigned long long) * starts.size(), hipMemcpyDeviceToHost));
+    return IMGENV_OK;
+}
+// ... and the placement under the policy of the epoch it falls into
+static int32_t scenario_of_placement(const imgenv* h, const std::vector<unsigned long long>& starts, uint64_t serial) {
+    const imgenv::ScnEpoch& e = h->scn_epochs[scenario_epoch_of(starts.data(), starts.size(), serial)];
+    const uint64_t seed0 = h->sd_ready ? ((const SpawnDev*)h->sd_storage)->seed0 : 0;
+    return scenario_for_placement(e.policy, seed0, e.first, serial, h->n_scn);
 }
 
 extern "C" int imgenv_world_scenarios(imgenv_t* h, int32_t* ids, void* stream) {
@@ -3079,26 +3027,14 @@ extern "C" int imgenv_world_scenarios(imgenv_t* h, int32_t* ids, void* stream) {
     for (size_t k = 0; k < W; k++) ids[k] = -1;
     if (h->n_scn < 1) return IMGENV_OK;
     std::vector<int> scn(W);
-    std::vector<unsigned long long> mark(W), serial(W, ~0ull), starts(h->scn_epochs.size());
+    std::vector<unsigned long long> mark(W), serial(W, ~0ull), starts;
     HIPCHK(hipMemcpy(scn.data(), h->d_scn_world, sizeof(int) * W, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(mark.data(), h->d_scn_mark, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(starts.data(), h->d_scn_starts, sizeof(unsigned long long) * starts.size(), hipMemcpyDeviceToHost));
-    uint64_t seed0 = 0;
-    if (h->sd_ready) {
-        const SpawnDev& c = *(SpawnDev*)h->sd_storage;
-        HIPCHK(hipMemcpy(serial.data(), c.place_serial, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost));
-        seed0 = c.seed0;
-    }
-    starts[0] = 0;
-    for (size_t k = 0; k < W; k++) {
-        if (serial[k] == mark[k]) {  // the host reset it last (or nobody has)
-            ids[k] = scn[k];
-            continue;
-        }
-        size_t e = starts.size() - 1;  // the device handed placement serial[k] out: under the policy of the epoch it falls into
-        while (e > 0 && starts[e] > serial[k]) e--;
-        ids[k] = scenario_for_placement(h->scn_epochs[e].policy, seed0, h->scn_epochs[e].first, serial[k], h->n_scn);
-    }
+    RTRY(scenario_starts_pull(h, starts));
+    if (h->sd_ready)
+        HIPCHK(hipMemcpy(serial.data(), ((const SpawnDev*)h->sd_storage)->place_serial, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < W; k++)  // (equal: the host reset it last, or nobody has)
+        ids[k] = serial[k] == mark[k] ? scn[k] : scenario_of_placement(h, starts, serial[k]);
     return IMGENV_OK;
 }
 
@@ -3403,19 +3339,8 @@ extern "C" int imgenv_step_autoreset(imgenv_t* h, const float* actions, const im
         for (int q = 0; q < n; q++) batches[q] = use[q]->batch;
         h->spawn_ahead_n = std::min(256, std::max(8, 2 * n));  // twice what this step needed
         if (trace) tp[3] = std::chrono::steady_clock::now();
-        std::vector<int> ids;
-        if (h->d_map_cur && h->maps_policy == IMGENV_MAPS_BY_PLACEMENT) {  // the placement's seed also draws the map
-            for (int q = 0; q < n; q++) ids.push_back(map_for_placement(seed0 + (uint64_t)q, h->n_maps));
-            h->reset_map_ids = ids.data();
-        }
-        std::vector<int> sets;
-        if (h->d_trk_cur && h->tracks_policy == IMGENV_TRACKS_BY_PLACEMENT) {  // ... and the recorded crowd
-            for (int q = 0; q < n; q++) sets.push_back(tracks_for_placement(seed0 + (uint64_t)q, h->n_track_sets));
-            h->reset_track_ids = sets.data();
-        }
-        rc = imgenv_reset_worlds(h, n, worlds.data(), batches.data(), stream);
-        h->reset_map_ids = nullptr;
-        h->reset_track_ids = nullptr;
+        const PlacementDraws draws = placement_draws(h, n, nullptr, seed0);  // the placement's seed also draws the map and the recorded crowd
+        rc = reset_worlds(h, n, worlds.data(), batches.data(), draws.choices(), st);
         if (rc == IMGENV_OK) {
             *n_out = n;
             for (int q = 0; q < n && worlds_out && q < cap; q++) worlds_out[q] = worlds[q];
@@ -3911,9 +3836,7 @@ extern "C" int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgen
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
     RTRY(enable_args(s, "imgenv_stack_cfg", out, "imgenv_stack_out"));
     if (h->stack_on) FAIL(IMGENV_ESTATE, "imgenv_stack_enable has already been called on this handle");
-    bool any_reset = h->has_reset;
-    for (char r : h->world_ready) any_reset = any_reset || r;
-    if (any_reset) FAIL(IMGENV_ESTATE, "imgenv_stack_enable after the first reset");
+    if (any_world_reset(h)) FAIL(IMGENV_ESTATE, "imgenv_stack_enable after the first reset");
     StackPlan p;
     if (int rc = plan_stack(h->cfg, *s, h->RL, p)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
@@ -4028,32 +3951,24 @@ extern "C" int imgenv_episode_log_enable(imgenv_t* h, const imgenv_episode_log_c
         return IMGENV_OK;
     }
     HIPCHK(hipSetDevice(h->cfg.device));
-    // one block: the counter, the ring's placement | f64 | i32 columns, then the per-robot tags (placement | i32); the tags start as
-    // "open before the log was" (all bits set: -1 and ~0), the rest zeroed.  Nothing of the handle changes before both fills are done.
+    // two blocks: the counter and the ring's placement | f64 | i32 columns, zeroed; the per-robot tags (placement | i32), which start
+    // as "open before the log was" (all bits set: -1 and ~0).  Nothing of the handle changes before both are there.
     const size_t C = (size_t)c->capacity, RL = (size_t)h->RL;
-    const size_t ring_bytes = 8 + C * (8 + 8 * EPL_F64_ROWS + 4 * EPL_I32_ROWS), ring_pad = (ring_bytes + 7) & ~(size_t)7;
-    const size_t tag_bytes = RL * (8 + 4 * EPT_ROWS);
-    void* block = nullptr;
-    if (hipMalloc(&block, ring_pad + tag_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        FAIL(IMGENV_ENOMEM, "no device memory for an episode log of %d records", c->capacity);
-    }
-    hipError_t filled = hipMemset(block, 0, ring_pad);
-    if (filled == hipSuccess) filled = hipMemset((unsigned char*)block + ring_pad, 0xFF, tag_bytes);
-    if (filled != hipSuccess) {  // (a device error, not a lack of memory: reported as HIPCHK does, with the block given back)
-        (void)hipFree(block);
-        FAIL(IMGENV_EDEVICE, "imgenv_episode_log_enable: hipMemset: %s (%s:%d)", hipGetErrorString(filled), __FILE__, __LINE__);
-    }
-    h->allocs.push_back(block);
-    unsigned char* b = (unsigned char*)block;
+    const size_t ring_bytes = 8 + C * (8 + 8 * EPL_F64_ROWS + 4 * EPL_I32_ROWS), tag_bytes = RL * (8 + 4 * EPT_ROWS);
+    unsigned char *b = nullptr, *t = nullptr;
+    DevTxn<HipApi> txn;
+    txn.room(&b, ring_bytes, 0);
+    txn.room(&t, tag_bytes, 0xFF);
+    if (txn.code()) FAIL(txn.code(), "imgenv_episode_log_enable: a log of %d records: %s", c->capacity, txn.error());
+    txn.commit(h->allocs);
     EpisodeLogDev g;
     memset(&g, 0, sizeof(g));
     g.n_written = (unsigned long long*)b;
     g.placement = (unsigned long long*)(b + 8);
     g.f64 = (double*)(b + 8 + 8 * C);
     g.i32 = (int32_t*)(b + 8 + 8 * C + 8 * EPL_F64_ROWS * C);
-    g.tag_place = (unsigned long long*)(b + ring_pad);
-    g.tags = (int32_t*)(b + ring_pad + 8 * RL);
+    g.tag_place = (unsigned long long*)t;
+    g.tags = (int32_t*)(t + 8 * RL);
     g.capacity = c->capacity;
     g.W = h->W;
     h->eplog = g;
@@ -4102,13 +4017,8 @@ extern "C" int64_t imgenv_episode_log_read(imgenv_t* h, uint64_t first, int32_t 
     for (int k = 0; k < EPL_F64_ROWS; k++) HIPCHK(pull(cf.data() + (size_t)k * cnt, g.f64 + (size_t)k * C, 8));
     HIPCHK(pull(cp.data(), g.placement, 8));
     // the scenario of a device-placed episode: its placement number under the policy of the epoch it falls into (imgenv_world_scenarios)
-    std::vector<unsigned long long> starts(h->scn_epochs.size());
-    uint64_t seed0 = 0;
-    if (h->n_scn > 0) {
-        HIPCHK(hipMemcpy(starts.data(), h->d_scn_starts, sizeof(unsigned long long) * starts.size(), hipMemcpyDeviceToHost));
-        starts[0] = 0;
-        if (h->sd_ready) seed0 = ((SpawnDev*)h->sd_storage)->seed0;
-    }
+    std::vector<unsigned long long> starts;
+    if (h->n_scn > 0) RTRY(scenario_starts_pull(h, starts));
     for (size_t q = 0; q < cnt; q++) {
         imgenv_episode_record& r = rec[q];
         const int32_t* i = ci.data() + q;
@@ -4119,11 +4029,7 @@ extern "C" int64_t imgenv_episode_log_read(imgenv_t* h, uint64_t first, int32_t 
         r.tracks = i[EPL_TRACKS * cnt];
         int32_t scn = i[EPL_SCENARIO * cnt];
         if (h->n_scn < 1) scn = -1;
-        else if (scn == IMGENV_EPLOG_SCN_DEVICE) {
-            size_t e = starts.size() - 1;
-            while (e > 0 && starts[e] > cp[q]) e--;
-            scn = scenario_for_placement(h->scn_epochs[e].policy, seed0, h->scn_epochs[e].first, cp[q], h->n_scn);
-        }
+        else if (scn == IMGENV_EPLOG_SCN_DEVICE) scn = scenario_of_placement(h, starts, cp[q]);
         r.scenario = scn;
         r.ep_return = cf[EPL_RETURN * cnt + q];
         for (int k = 0; k < 8; k++) r.figures[k] = cf[(EPL_FIG0 + k) * cnt + q];
@@ -4341,17 +4247,10 @@ extern "C" int imgenv_final_obs_enable(imgenv_t* h, const imgenv_final_obs_cfg* 
         total = align256(total + RL * row_bytes[k]);
     }
     HIPCHK(hipSetDevice(h->cfg.device));
-    void* block = nullptr;
-    if (hipMalloc(&block, total) != hipSuccess) {
-        (void)hipGetLastError();
-        FAIL(IMGENV_ENOMEM, "no device memory for the final observations (%zu bytes)", total);
-    }
-    const hipError_t filled = hipMemset(block, 0, total);
-    if (filled != hipSuccess) {  // (a device error, not a lack of memory)
-        (void)hipFree(block);
-        FAIL(IMGENV_EDEVICE, "imgenv_final_obs_enable: hipMemset: %s (%s:%d)", hipGetErrorString(filled), __FILE__, __LINE__);
-    }
-    h->allocs.push_back(block);
+    unsigned char* block = nullptr;
+    DevTxn<HipApi> txn;
+    if (!txn.room(&block, total, 0)) FAIL(txn.code(), "imgenv_final_obs_enable: %s", txn.error());
+    txn.commit(h->allocs);
     FinalObsDev fo;
     memset(&fo, 0, sizeof(fo));
     fo.n_fields = plan.n_fields;

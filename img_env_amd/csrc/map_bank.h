@@ -34,3 +34,12 @@ struct MapSel {
     int n_maps;
     int by_placement;     // IMGENV_MAPS_BY_PLACEMENT: the device-side reset draws the map from the placement's seed
 };
+
+#if defined(__HIPCC__)
+// next[worlds[q]] = ids[q], from page-locked host memory: the scatter of imgenv_world_maps_set and, over the track bank's `next`,
+// of imgenv_world_tracks_set
+__global__ void k_world_select(int* __restrict__ next, const int* __restrict__ worlds, const int* __restrict__ ids, int n) {
+    const int q = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (q < n) next[worlds[q]] = ids[q];
+}
+#endif

@@ -147,10 +147,4 @@ __global__ __launch_bounds__(256) void k_tracks_install(DevWorld w, TrackSel t, 
         }
     }
 }
-
-// next[worlds[q]] = ids[q], from page-locked host memory (imgenv_world_tracks_set)
-__global__ void k_tracks_select(int* __restrict__ next, const int* __restrict__ worlds, const int* __restrict__ ids, int n) {
-    const int q = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (q < n) next[worlds[q]] = ids[q];
-}
 #endif

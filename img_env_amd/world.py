@@ -126,12 +126,10 @@ class World:
                 msg = self.lib.imgenv_last_error().decode()
                 self.close()
                 raise ValueError("imgenv_maps_add: %s" % msg)
-        self._maps_buf = None
+        self._ids_buf = None  # world_maps() / world_tracks() / world_scenarios()
         self.n_track_sets = 0  # tracks_add()
-        self._tracks_buf = None
         self.n_scenarios = 0  # scenarios_add()
         self.scenario_obstacles = 0
-        self._scenarios_buf = None
 
     def scenarios_add(self, layouts):
         """``imgenv_scenarios_add``: the handle's bank of recorded episodes (the reference's ``cfg_type: bag``), once, before the
@@ -161,21 +159,13 @@ class World:
     def reset_worlds_scenarios(self, worlds, ids):
         """``imgenv_reset_worlds_scenarios``: world ``worlds[q]`` starts the bank's episode ``ids[q]`` (a host-side reset; the device's
         placement count does not move).  ValueError for an id or a world out of range."""
-        worlds, ids = [int(k) for k in worlds], [int(k) for k in ids]
-        if len(worlds) != len(ids):
-            raise ValueError("one scenario id per world")
-        n = len(worlds)
-        self._call(self.lib.imgenv_reset_worlds_scenarios(self.h, n, (C.c_int32 * max(n, 1))(*worlds), (C.c_int32 * max(n, 1))(*ids),
-                                                          self._stream()), "imgenv_reset_worlds_scenarios")
+        self._world_ids_set("imgenv_reset_worlds_scenarios", "scenario", worlds, ids)
         return self.out
 
     def world_scenarios(self):
         """``imgenv_world_scenarios``: the scenario each world's current episode came from, -1 where its reset did not come from the
         bank (numpy int32 ``[n_worlds]``); synchronises the stream"""
-        if self._scenarios_buf is None:
-            self._scenarios_buf = (C.c_int32 * self.n_worlds)()
-        self._check(self.lib.imgenv_world_scenarios(self.h, self._scenarios_buf, self._stream()), "imgenv_world_scenarios")
-        return np.array(self._scenarios_buf[:], np.int32)
+        return self._world_ids("imgenv_world_scenarios")
 
     def tracks_add(self, sets):
         """``imgenv_tracks_add``: the handle's bank of recorded crowds (dataset scene), once, before the first reset.  ``sets``: a list
@@ -191,12 +181,7 @@ class World:
         """``imgenv_world_tracks_set``: world ``worlds[q]`` takes set ``ids[q]`` at its next bank-fed reset queued after this call
         (policy "keep"); its running episode is untouched.  ValueError (nothing applied) for an id or a world out of range or a
         world listed twice."""
-        worlds, ids = [int(k) for k in worlds], [int(k) for k in ids]
-        if len(worlds) != len(ids):
-            raise ValueError("one set id per world")
-        n = len(worlds)
-        self._call(self.lib.imgenv_world_tracks_set(self.h, n, (C.c_int32 * max(n, 1))(*worlds), (C.c_int32 * max(n, 1))(*ids), self._stream()),
-                   "imgenv_world_tracks_set")
+        self._world_ids_set("imgenv_world_tracks_set", "set", worlds, ids)
 
     def tracks_policy(self, name, repeat=1):
         """``imgenv_tracks_policy``: "keep" (``set_world_tracks`` alone chooses), "placement" (``_cabi.tracks_for_placement(seed,
@@ -209,30 +194,17 @@ class World:
     def world_tracks(self):
         """``imgenv_world_tracks``: the set each world's current episode replays, -1 where its last reset brought its own tracks
         (numpy int32 ``[n_worlds]``); synchronises the stream"""
-        if self._tracks_buf is None:
-            self._tracks_buf = (C.c_int32 * self.n_worlds)()
-        self._check(self.lib.imgenv_world_tracks(self.h, self._tracks_buf, self._stream()), "imgenv_world_tracks")
-        return np.array(self._tracks_buf[:], np.int32)
+        return self._world_ids("imgenv_world_tracks")
 
     def set_world_maps(self, worlds, ids):
         """``imgenv_world_maps_set``: world ``worlds[q]`` starts from map ``ids[q]`` of the bank at its next reset of any kind
         queued after this call; its current episode is untouched.  ValueError (nothing applied) for an id, a world out of range
         or a world listed twice."""
-        worlds, ids = [int(k) for k in worlds], [int(k) for k in ids]
-        if len(worlds) != len(ids):
-            raise ValueError("one map id per world")
-        n = len(worlds)
-        rc = self.lib.imgenv_world_maps_set(self.h, n, (C.c_int32 * max(n, 1))(*worlds), (C.c_int32 * max(n, 1))(*ids), self._stream())
-        if rc == _cabi.EINVAL:
-            raise ValueError("imgenv_world_maps_set: %s" % self.lib.imgenv_last_error().decode())
-        self._check(rc, "imgenv_world_maps_set")
+        self._world_ids_set("imgenv_world_maps_set", "map", worlds, ids)
 
     def world_maps(self):
         """``imgenv_world_maps``: the map each world's current episode runs on (numpy int32 ``[n_worlds]``); synchronises the stream"""
-        if self._maps_buf is None:
-            self._maps_buf = (C.c_int32 * self.n_worlds)()
-        self._check(self.lib.imgenv_world_maps(self.h, self._maps_buf, self._stream()), "imgenv_world_maps")
-        return np.array(self._maps_buf[:], np.int32)
+        return self._world_ids("imgenv_world_maps")
 
     def set_maps_policy(self, name):
         """``imgenv_maps_policy``: "keep" (``set_world_maps`` alone chooses) or "placement" (every reset that draws its placement
@@ -254,6 +226,22 @@ class World:
     def _stream(self):
         import torch
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _world_ids_set(self, entry, what, worlds, ids):
+        """an entry point that takes a (world, id) list -- the banks' ``*_set`` calls, ``imgenv_reset_worlds_scenarios``: ValueError
+        for a refused list, RuntimeError otherwise"""
+        worlds, ids = [int(k) for k in worlds], [int(k) for k in ids]
+        if len(worlds) != len(ids):
+            raise ValueError("one %s id per world" % what)
+        n = len(worlds)
+        self._call(getattr(self.lib, entry)(self.h, n, (C.c_int32 * max(n, 1))(*worlds), (C.c_int32 * max(n, 1))(*ids), self._stream()), entry)
+
+    def _world_ids(self, entry):
+        """a bank's getter: what each world's current episode runs on, numpy int32 ``[n_worlds]``"""
+        if self._ids_buf is None:
+            self._ids_buf = (C.c_int32 * self.n_worlds)()
+        self._check(getattr(self.lib, entry)(self.h, self._ids_buf, self._stream()), entry)
+        return np.array(self._ids_buf[:], np.int32)
 
     def enable_stack(self, image_batch, state_batch, laser_batch):
         """Device-side StateBatchWrapper (``imgenv_stack_enable``; once, before the first reset): from now on every reset / step

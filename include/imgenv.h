@@ -854,7 +854,7 @@ int imgenv_world_maps(imgenv_t* h, int32_t* map_ids, void* stream);
  * The handle's trajectory tables are allocated here with max(cap, 2) records per pedestrian; a later explicit batch with a longer
  * ped_traj_cap still re-lays them out, the bank keeps its own stride.  IMGENV_EINVAL: the scene is not IMGENV_SCENE_DATASET, the
  * handle has no pedestrians or is a robot shard, n_sets < 1 or cap < 1, a length outside [1, cap], a value that is not finite.
- * IMGENV_ENOMEM when the bank cannot be allocated; the handle is then unchanged. */
+ * IMGENV_ENOMEM when the bank cannot be allocated, IMGENV_EDEVICE when filling it fails; the handle is then unchanged. */
 int imgenv_tracks_add(imgenv_t* h, int32_t n_sets, int32_t cap, const double* ped_pose, const double* ped_traj,
                       const double* ped_traj_v, const int32_t* ped_traj_len);
 /* World worlds[q] takes set set_ids[q] at its NEXT bank-fed reset queued on `stream` after this call (under

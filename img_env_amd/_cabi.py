@@ -310,6 +310,43 @@ def make_final_obs_cfg(fields):
     return c
 
 
+#: imgenv_rollout_cfg.fields: name -> IMGENV_ROLLOUT_* bit, in bit order
+ROLLOUT_BITS = {"sensor_maps": 1, "vector_states": 2, "lasers": 4, "ped_vector_states": 8, "ped_maps": 16, "ped_vector_norm": 32, "stacks": 64}
+ROLLOUT_ALL = 127
+#: the stored observation fields, in the order of imgenv_rollout_out's obs_* and final_* pointers
+ROLLOUT_FIELDS = ("sensor_maps", "vector_states", "lasers", "ped_vector_states", "ped_maps", "ped_vector_norm",
+                  "stack_sensor_maps", "stack_vector_states", "stack_lasers")
+#: the other pointers of imgenv_rollout_out, in the struct's order
+ROLLOUT_SCALARS = ("actions", "rewards", "dones", "is_clean", "dones_info", "final_idx", "final_slot", "final_row", "final_n")
+ROLLOUT_HEADER = ("struct_size", "n_local", "horizon", "final_capacity", "n", "resets")
+ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS, GAE_BLOCK, GAE_MAX_BLOCKS = 256, 1024, 64, 1024  # the launch shapes (csrc/launch_plan.h)
+
+
+class RolloutCfg(C.Structure):
+    _fields_ = [("struct_size", _i32), ("horizon", _i32), ("final_capacity", _i32), ("fields", _i32)]
+
+
+class RolloutOut(C.Structure):
+    _fields_ = ([(name, _i32) for name in ROLLOUT_HEADER] + [("obs_" + name, C.c_void_p) for name in ROLLOUT_FIELDS] +
+                [("final_" + name, C.c_void_p) for name in ROLLOUT_FIELDS] + [(name, C.c_void_p) for name in ROLLOUT_SCALARS])
+
+
+def make_rollout_cfg(horizon, final_capacity, fields):
+    """``imgenv_rollout_cfg``: ``fields`` is an int of IMGENV_ROLLOUT_* bits or an iterable of ``ROLLOUT_BITS`` names"""
+    c = RolloutCfg()
+    c.struct_size = C.sizeof(RolloutCfg)
+    c.horizon, c.final_capacity = int(horizon), int(final_capacity)
+    if isinstance(fields, (int, np.integer)):
+        c.fields = int(fields)
+    else:
+        names = list(fields)
+        unknown = [n for n in names if n not in ROLLOUT_BITS]
+        if unknown:
+            raise ValueError("rollout fields: unknown %s (known: %s)" % (unknown, ", ".join(ROLLOUT_BITS)))
+        c.fields = sum({ROLLOUT_BITS[n] for n in names})
+    return c
+
+
 #: name -> (numpy dtype, shape as a function of the Out header and the world sizes)
 def out_layout(o, n_peds, hp, wp):
     R, B = o.n_local, max(o.n_beams, 1)
@@ -462,6 +499,7 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_episode_log_enable", "imgenv_episode_log_outputs", "imgenv_episode_log_read",
            "imgenv_actions_enable", "imgenv_actions_outputs", "imgenv_actions_decode", "imgenv_obs_post_enable", "imgenv_obs_post_outputs",
            "imgenv_final_obs_enable", "imgenv_final_obs_outputs",
+           "imgenv_rollout_enable", "imgenv_rollout_outputs", "imgenv_rollout_begin", "imgenv_rollout_gae",
            "imgenv_maps_add", "imgenv_world_maps_set", "imgenv_maps_policy", "imgenv_map_for_placement", "imgenv_world_maps",
            "imgenv_tracks_add", "imgenv_world_tracks_set", "imgenv_tracks_policy", "imgenv_tracks_for_placement", "imgenv_world_tracks",
            "imgenv_scenarios_add", "imgenv_scenarios_policy", "imgenv_scenario_for_placement", "imgenv_reset_worlds_scenarios",
@@ -530,6 +568,10 @@ def bind(lib):
     lib.imgenv_obs_post_outputs.argtypes = [C.c_void_p, C.POINTER(ObsPostOut)]
     lib.imgenv_final_obs_enable.argtypes = [C.c_void_p, C.POINTER(FinalObsCfg), C.POINTER(FinalObsOut)]
     lib.imgenv_final_obs_outputs.argtypes = [C.c_void_p, C.POINTER(FinalObsOut)]
+    lib.imgenv_rollout_enable.argtypes = [C.c_void_p, C.POINTER(RolloutCfg), C.POINTER(RolloutOut)]
+    lib.imgenv_rollout_outputs.argtypes = [C.c_void_p, C.POINTER(RolloutOut)]
+    lib.imgenv_rollout_begin.argtypes = [C.c_void_p, C.c_void_p]
+    lib.imgenv_rollout_gae.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.imgenv_maps_add.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
     lib.imgenv_world_maps_set.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
     lib.imgenv_maps_policy.argtypes = [C.c_void_p, C.c_int32]

@@ -29,6 +29,7 @@
 #include "actions.h"
 #include "obs_post.h"
 #include "final_obs.h"
+#include "rollout.h"
 #include "map_bank.h"
 #include "spawn_slot.h"
 #include "bank_host.h"
@@ -250,6 +251,15 @@ struct imgenv {
     FinalObsDev final_dev;
     imgenv_final_obs_cfg final_cfg;
     imgenv_final_obs_out final_out;
+    // rollout storage (imgenv_rollout_enable; csrc/rollout.h)
+    bool roll_on = false;
+    bool roll_begun = false;     // imgenv_rollout_begin has been called: chains store
+    int roll_n = 0;              // the cursor: transitions stored since the last begin
+    uint32_t roll_turn = 0;      // reset chains stored since the last begin
+    RolloutDev roll;
+    size_t roll_row_bytes[ROLLOUT_MAX_FIELDS];
+    imgenv_rollout_cfg roll_cfg;
+    imgenv_rollout_out roll_out;
     bool chain_open = false;  // a chain of launches that hands over through tail_sig / tail_cnt has started and not been completed
     std::vector<RvoObstacles> rvos;  // one obstacle set per world
     int sfm_cap_obs = 0;
@@ -1711,6 +1721,13 @@ static TailRows tail_rows(const imgenv* h, int is_reset) {
     return {h->RL, h->Rw, is_reset ? d.act_list : nullptr, is_reset ? d.act_n_dev : nullptr, d.act_nw};
 }
 
+// A step on a handle whose rollout storage holds its whole horizon: refused by every step entry point before it queues anything
+static int rollout_room(const imgenv* h) {
+    if (h->roll_on && h->roll_begun && h->roll_n >= h->roll_cfg.horizon)
+        FAIL(IMGENV_EINVAL, "rollout full: imgenv_rollout_begin (all %d transitions of the horizon are stored)", h->roll_cfg.horizon);
+    return 0;
+}
+
 // The chain behind the move: side launches, rasters, compose, views, the tails' stacks and statistics -- plan, then launch in stream order
 static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
     DevWorld& d = h->d;
@@ -1864,6 +1881,23 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
         const LaunchShape g = plan_tail_launch(p, c, (size_t)pd.per_row, OBS_POST_BLOCK, OBS_POST_MAX_BLOCKS);
         (is_reset ? k_obs_post<true> : k_obs_post<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(pd);
         h->launches += 1;
+    }
+    if (h->roll_on && h->roll_begun) {
+        // the rollout storage (rollout.h), last -- it reads what k_stack and k_obs_post have just written: a step stores transition
+        // n and the observation it led to in slot n + 1 (rollout_room has refused a step on a full ring), a reset chain moves the
+        // rows of slot n it covers into the final list and stores the new episode's first observation there
+        RolloutDev ro = h->roll;
+        ro.rows = tail_rows(h, is_reset);
+        ro.act_src = h->ep_actions;
+        ro.n = h->roll_n;
+        ro.turn = h->roll_turn;
+        const LaunchShape g = plan_rollout_launch(p, c, ro.chunks_per_row);
+        (is_reset ? k_rollout<true> : k_rollout<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(ro);
+        h->launches += 1;
+        if (is_reset)
+            h->roll_turn += 1;
+        else
+            h->roll_n += 1;
     }
     HIPCHK(hipGetLastError());
     h->chain_open = false;
@@ -3087,6 +3121,7 @@ extern "C" int imgenv_step_begin(imgenv_t* h, const float* actions, void* stream
     if (!h || !actions) FAIL(IMGENV_EINVAL, "null argument");
     if (!h->has_reset) FAIL(IMGENV_ESTATE, "step before reset");
     if (h->obs_forked) FAIL(IMGENV_ESTATE, "imgenv_step_begin twice without imgenv_step_end (reset the handle to recover from an aborted step)");
+    if (int rc = rollout_room(h)) return rc;
     if (int rc = check_device_flags(h)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = outputs_verify(h, st)) return rc;
@@ -3214,6 +3249,7 @@ extern "C" int imgenv_step_begin(imgenv_t* h, const float* actions, void* stream
 extern "C" int imgenv_step_end(imgenv_t* h, void* stream) {
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
     if (!h->has_reset) FAIL(IMGENV_ESTATE, "step before reset");
+    if (int rc = rollout_room(h)) return rc;
     h->elapsed += 1;  // TimeLimitWrapper._elapsed_steps (base.py:224)
     if (h->stamp) {  // this step's stamps get a new tag
         h->stamp_seq += 1;
@@ -3278,7 +3314,7 @@ static int autoreset_checks(imgenv* h, const float* actions, const imgenv_spawn_
         FAIL(IMGENV_EINVAL, "spawn cfg is for %d robots / %d pedestrians, a world of this handle has %d / %d", cfg->n_robots,
              cfg->n_peds, h->Rw, h->Pw);
     if (h->RL != h->R) FAIL(IMGENV_EINVAL, "%s needs all robots of every world on this handle", who);
-    return 0;
+    return rollout_room(h);
 }
 
 extern "C" int imgenv_step_autoreset(imgenv_t* h, const float* actions, const imgenv_spawn_cfg* cfg, uint64_t seed0, int32_t* worlds_out,
@@ -4271,6 +4307,175 @@ extern "C" int imgenv_final_obs_enable(imgenv_t* h, const imgenv_final_obs_cfg* 
 
 extern "C" int imgenv_final_obs_outputs(imgenv_t* h, imgenv_final_obs_out* out) {
     return feature_outputs(h, &imgenv::final_on, &imgenv::final_out, out, "imgenv_final_obs_enable");
+}
+
+// ---- rollout storage (include/imgenv.h; the kernels are csrc/rollout.h) ----
+extern "C" int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* c, imgenv_rollout_out* out) {
+    // (the cfg first, as above)
+    RTRY(enable_args(c, "imgenv_rollout_cfg", out, "imgenv_rollout_out"));
+    if (c->horizon < 1) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.horizon %d: at least 1", c->horizon);
+    if (c->final_capacity < 1) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.final_capacity %d: at least 1", c->final_capacity);
+    if (c->fields == 0 || (c->fields & ~IMGENV_ROLLOUT_ALL)) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d", c->fields);
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (h->roll_on) {
+        const imgenv_rollout_cfg& o = h->roll_cfg;
+        if (c->horizon != o.horizon || c->final_capacity != o.final_capacity || c->fields != o.fields)
+            FAIL(IMGENV_EINVAL, "imgenv_rollout_enable: the handle already keeps a rollout of horizon %d, final_capacity %d, fields %d", o.horizon,
+                 o.final_capacity, o.fields);
+        return out ? imgenv_rollout_outputs(h, out) : IMGENV_OK;
+    }
+    const int want = c->fields;
+    const size_t RL = (size_t)h->RL, T = (size_t)c->horizon, F = (size_t)c->final_capacity;
+    if ((T + 1) * RL > 0x7fffffffu) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.horizon %d: (horizon + 1) x %d robots is beyond 2^31 - 1", c->horizon, h->RL);
+    if ((want & IMGENV_ROLLOUT_LASERS) && h->out.n_beams <= 0) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields: lasers on a handle without use_laser");
+    if ((want & IMGENV_ROLLOUT_STACKS) && !h->stack_on) FAIL(IMGENV_ESTATE, "IMGENV_ROLLOUT_STACKS before imgenv_stack_enable");
+    if ((want & IMGENV_ROLLOUT_STACKS) && h->stack.n_fields == 0) FAIL(IMGENV_EINVAL, "IMGENV_ROLLOUT_STACKS: no stack of this handle is deeper than 1");
+    if ((want & IMGENV_ROLLOUT_PED_NORM) && !(h->post_on && h->post.norm)) FAIL(IMGENV_ESTATE, "IMGENV_ROLLOUT_PED_NORM before imgenv_obs_post_enable with IMGENV_OBS_PED_NORM");
+    // the sources, always in the working arena, with their row sizes and where the out struct keeps the ring's and the final list's pointers
+    const imgenv_out& w = h->out;
+    const size_t NI = (size_t)w.image_h * w.image_w, B = (size_t)std::max(w.n_beams, 0);
+    const size_t NP = (size_t)h->cfg.ped_image_size[0] * h->cfg.ped_image_size[1];
+    imgenv_rollout_out o = {};
+    struct Src {
+        int bit;
+        const void* src;
+        size_t row_bytes;
+        void** ring;
+        void** fin;
+    };
+    const imgenv_stack_out& so = h->stack_out;
+    const Src all[] = {
+        {IMGENV_ROLLOUT_SENSOR_MAPS, w.sensor_maps, NI * 2, (void**)&o.obs_sensor_maps, (void**)&o.final_sensor_maps},
+        {IMGENV_ROLLOUT_VECTOR_STATES, w.vector_states, (size_t)w.state_dim * 4, (void**)&o.obs_vector_states, (void**)&o.final_vector_states},
+        {IMGENV_ROLLOUT_LASERS, w.lasers, B * 8, (void**)&o.obs_lasers, (void**)&o.final_lasers},
+        {IMGENV_ROLLOUT_PED_VECTOR_STATES, w.ped_vector_states, (size_t)w.ped_vec_len * 4, (void**)&o.obs_ped_vector_states, (void**)&o.final_ped_vector_states},
+        {IMGENV_ROLLOUT_PED_MAPS, w.ped_maps, 3 * NP * 4, (void**)&o.obs_ped_maps, (void**)&o.final_ped_maps},
+        {IMGENV_ROLLOUT_PED_NORM, h->post.norm, (size_t)w.ped_vec_len * 4, (void**)&o.obs_ped_vector_norm, (void**)&o.final_ped_vector_norm},
+        // (a stack of depth >= 2 is the library's or the caller's arena, never an alias of imgenv_out)
+        {IMGENV_ROLLOUT_STACKS, so.image_depth >= 2 ? so.sensor_maps : nullptr, (size_t)std::max(so.image_depth, 0) * NI * 2,
+         (void**)&o.obs_stack_sensor_maps, (void**)&o.final_stack_sensor_maps},
+        {IMGENV_ROLLOUT_STACKS, so.state_depth >= 2 ? so.vector_states : nullptr, (size_t)std::max(so.state_depth, 0) * w.state_dim * 4,
+         (void**)&o.obs_stack_vector_states, (void**)&o.final_stack_vector_states},
+        {IMGENV_ROLLOUT_STACKS, so.laser_depth >= 2 ? so.lasers : nullptr, (size_t)std::max(so.laser_depth, 0) * B * 8,
+         (void**)&o.obs_stack_lasers, (void**)&o.final_stack_lasers},
+    };
+    static_assert(sizeof(all) / sizeof(all[0]) <= ROLLOUT_MAX_FIELDS, "ROLLOUT_MAX_FIELDS");
+    const Src* sel[ROLLOUT_MAX_FIELDS];
+    size_t row_bytes[ROLLOUT_MAX_FIELDS];
+    int n = 0;
+    for (const Src& s : all) {
+        if (!(want & s.bit) || (s.bit == IMGENV_ROLLOUT_STACKS && !s.src)) continue;  // (a stack of depth 1 is the field itself)
+        if (!s.src || s.row_bytes == 0) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields: bit %d names a field of no bytes on this handle", s.bit);
+        sel[n] = &s;
+        row_bytes[n++] = s.row_bytes;
+    }
+    // one block, every array on a 256-byte boundary, zeroed; nothing of the handle changes before it is there
+    size_t total = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = total;
+        total = align256(total + bytes);
+        return at;
+    };
+    size_t off_ring[ROLLOUT_MAX_FIELDS], off_fin[ROLLOUT_MAX_FIELDS];
+    for (int k = 0; k < n; k++) {
+        off_ring[k] = carve((T + 1) * RL * row_bytes[k]);
+        off_fin[k] = carve(F * row_bytes[k]);
+    }
+    const size_t off_actions = carve(T * RL * 12), off_rewards = carve(T * RL * 4), off_dones = carve(T * RL), off_clean = carve(T * RL);
+    const size_t off_info = carve(T * RL * 4), off_idx = carve((T + 1) * RL * 4), off_slot = carve(F * 4), off_row = carve(F * 4), off_n = carve(8);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    unsigned char* block = nullptr;
+    DevTxn<HipApi> txn;
+    if (!txn.room(&block, total, 0)) FAIL(txn.code(), "imgenv_rollout_enable: %s", txn.error());
+    txn.commit(h->allocs);
+    RolloutDev ro;
+    memset(&ro, 0, sizeof(ro));
+    ro.n_fields = n;
+    for (int k = 0; k < n; k++) {
+        const FinalFieldPlan f = plan_final_field(row_bytes[k]);
+        ro.f[k].ring = block + off_ring[k];
+        ro.f[k].fin = block + off_fin[k];
+        ro.f[k].src = (const unsigned char*)sel[k]->src;
+        ro.f[k].unit = f.unit;
+        ro.f[k].chunks = f.chunks;
+        ro.chunks_per_row += f.chunks;
+        h->roll_row_bytes[k] = row_bytes[k];
+        *sel[k]->ring = ro.f[k].ring;
+        *sel[k]->fin = ro.f[k].fin;
+    }
+    ro.rew_src = w.step_rewards;  // (the working arena, also under IMGENV_FLAG_FULL_REWRITE)
+    ro.done_src = w.step_dones;
+    ro.clean_src = w.step_is_clean;
+    ro.info_src = w.step_dones_info;
+    o.actions = ro.actions = (float*)(block + off_actions);
+    o.rewards = ro.rewards = (float*)(block + off_rewards);
+    o.dones = ro.dones = block + off_dones;
+    o.is_clean = ro.is_clean = block + off_clean;
+    o.dones_info = ro.dones_info = (int32_t*)(block + off_info);
+    o.final_idx = ro.final_idx = (int32_t*)(block + off_idx);
+    o.final_slot = ro.final_slot = (int32_t*)(block + off_slot);
+    o.final_row = ro.final_row = (int32_t*)(block + off_row);
+    o.final_n = ro.final_n = (uint32_t*)(block + off_n);
+    ro.F = c->final_capacity;
+    o.horizon = c->horizon;
+    o.final_capacity = c->final_capacity;
+    o.n = -1;
+    h->roll = ro;
+    h->roll_cfg = *c;
+    h->roll_begun = false;
+    h->roll_n = 0;
+    h->roll_turn = 0;
+    return enable_done(h, o, &imgenv::roll_out, &imgenv::roll_on, out);
+}
+
+extern "C" int imgenv_rollout_outputs(imgenv_t* h, imgenv_rollout_out* out) {
+    if (int rc = feature_outputs(h, &imgenv::roll_on, &imgenv::roll_out, out, "imgenv_rollout_enable")) return rc;
+    out->n = h->roll_begun ? h->roll_n : -1;
+    out->resets = (int32_t)h->roll_turn;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_rollout_begin(imgenv_t* h, void* stream) {
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->roll_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_enable was not called");
+    if (!h->obs_exists) FAIL(IMGENV_ESTATE, "imgenv_rollout_begin before the first reset: there is no observation yet");
+    if (h->obs_forked) FAIL(IMGENV_ESTATE, "imgenv_rollout_begin between imgenv_step_begin and imgenv_step_end");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t RL = (size_t)h->RL;
+    if (!h->roll_begun || h->roll_n > 0) {
+        // slot n -> slot 0 (the first time: the live arrays -> slot 0): k_rollout's step instantiation with the scalars off
+        RolloutDev ro = h->roll;
+        if (h->roll_begun)
+            for (int k = 0; k < ro.n_fields; k++) ro.f[k].src = ro.f[k].ring + (size_t)h->roll_n * RL * h->roll_row_bytes[k];
+        ro.rewards = nullptr;
+        ro.n = -1;
+        ro.rows = tail_rows(h, 0);
+        const LaunchShape g = plan_rollout_begin_launch(h->plan, ro.chunks_per_row);
+        k_rollout<false><<<dim3(g.grid), dim3(g.block), 0, st>>>(ro);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemsetAsync(h->roll.final_idx, 0xFF, ((size_t)h->roll_cfg.horizon + 1) * RL * 4, st));
+    HIPCHK(hipMemsetAsync(h->roll.final_n, 0, 8, st));
+    h->roll_begun = true;
+    h->roll_n = 0;
+    h->roll_turn = 0;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_rollout_gae(imgenv_t* h, const float* values, const float* final_values, float gamma, float lam, float* adv, float* ret,
+                                  void* stream) {
+    if (!h || !values || !adv || !ret) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->roll_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_enable was not called");
+    if (!h->roll_begun) FAIL(IMGENV_ESTATE, "imgenv_rollout_gae before imgenv_rollout_begin");
+    if (h->roll_n == 0) return IMGENV_OK;  // (no transition yet: every row of adv / ret is left untouched)
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const RolloutDev& ro = h->roll;
+    const RolloutGaeDev g = {ro.rewards, ro.dones, ro.is_clean, ro.dones_info, ro.final_idx, values, final_values, adv, ret, gamma, lam, h->roll_n, ro.F, h->RL};
+    const LaunchShape s = plan_rollout_gae_launch(h->plan);
+    k_rollout_gae<<<dim3(s.grid), dim3(s.block), 0, (hipStream_t)stream>>>(g);
+    HIPCHK(hipGetLastError());
+    return IMGENV_OK;
 }
 
 extern "C" int imgenv_cv_resize_u8(int kind, const uint8_t* src, int32_t sh, int32_t sw, uint8_t* dst, int32_t dh, int32_t dw) {

@@ -35,6 +35,12 @@
 #define FINAL_BLOCK 256     // k_final_obs: one lane per chunk of a captured row
 #define FINAL_MAX_BLOCKS 1024
 #define FINAL_MAX_FIELDS 16  // 11 fields of imgenv_out, 3 stacks, ped_vector_norm
+#define ROLLOUT_BLOCK 256   // k_rollout: one lane per chunk of a stored row
+#define ROLLOUT_MAX_BLOCKS 1024
+#define ROLLOUT_MAX_FIELDS 9  // five single-frame fields, ped_vector_norm, three stacks
+#define GAE_BLOCK 64        // k_rollout_gae: one lane per local robot, one wavefront per block (4096 robots reach 64 CUs)
+#define GAE_MAX_BLOCKS 1024
+#define GAE_BATCH 4         // time steps whose loads a lane issues before it walks their dependent chain
 #define ACT_BLOCK 256       // k_actions: one lane per local robot
 #define OBS_POST_BLOCK 256  // k_obs_post: one lane per element of a robot's ped_vector row
 #define OBS_POST_MAX_BLOCKS 2048
@@ -452,6 +458,19 @@ inline LaunchShape plan_final_obs_launch(const PlanHandle& h, const PlanChain& c
     if (c.listed) rows = (size_t)(c.n_dev ? std::min(c.act_nw, std::max(dev_guess, 1)) : c.act_nw) * (size_t)h.Rw;
     return plan_tail(rows * chunks_per_row, FINAL_BLOCK, FINAL_MAX_BLOCKS);
 }
+
+// ---------------------------------------------------------------------------------------- end of a chain: k_rollout, and k_rollout_gae
+// k_rollout (rollout.h), the last launch of a chain: the rows are the chain tail's (plan_tail_rows), a row's chunks plan_final_field's,
+// one lane per chunk, capped; the kernel strides.  The cap is reached from ROLLOUT_BLOCK x ROLLOUT_MAX_BLOCKS = 262144 chunks on.
+inline LaunchShape plan_rollout_launch(const PlanHandle& h, const PlanChain& c, uint32_t chunks_per_row) {
+    return plan_tail_launch(h, c, chunks_per_row, ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS);
+}
+// imgenv_rollout_begin: every local row, whatever chain came last
+inline LaunchShape plan_rollout_begin_launch(const PlanHandle& h, uint32_t chunks_per_row) {
+    return plan_tail((size_t)h.RL * chunks_per_row, ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS);
+}
+// the advantage pass: one lane per local robot, striding from GAE_BLOCK x GAE_MAX_BLOCKS = 65536 robots on
+inline LaunchShape plan_rollout_gae_launch(const PlanHandle& h) { return plan_tail((size_t)h.RL, GAE_BLOCK, GAE_MAX_BLOCKS); }
 
 // ---------------------------------------------------------------------------------------- in front of the chain: k_actions
 // imgenv_actions_decode (actions.h): one lane per local robot, every wavefront whole (the ballot that counts bad rows runs on all

@@ -37,12 +37,14 @@ class VecImageEnv:
     pedestrians, ``bool_get_close_to_human`` (of the state handed out: an env that restarted shows its new episode's).
     ``final_obs=True``: ``info`` gains ``final_observation`` (Gym's: the state the restarted envs' last action led to, in the rows
     where ``all_down`` is set; other rows hold older captures) and ``final_count``.
+    ``rollout=T``: the trainer's ``[T, n, ...]`` storage and the advantage pass inside the library: ``rollout()``,
+    ``rollout_begin()``, ``rollout_advantages(values, final_values, gamma, lam)``.
     """
 
     def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False,
                  map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3, wrappers=False,
                  ped_tracks=None, tracks_policy="keep", tracks_repeat=1, info_track_sets=False, scenarios=None, scenario_policy="queue",
-                 episode_log=0, final_obs=False):
+                 episode_log=0, final_obs=False, rollout=0, rollout_final=None, rollout_fields=None):
         import torch
         from .world import World
         self.cfg = cfg
@@ -194,6 +196,50 @@ class VecImageEnv:
             if self._ped_norm:
                 fields.append("ped_vector_norm")
             self.world.enable_final_obs(fields)
+        # rollout=T: the trainer's [T, n, ...] storage inside the library (imgenv_rollout_enable).  After reset() every step also
+        # stores its transition (action, reward, done, dones_info, is_clean) in slot t and the state it hands out in slot t + 1 of
+        # rollout()'s tensors, and every reset -- Python spawn, native_spawn, device_reset or the caller's reset_envs -- first moves
+        # the rows it overwrites into a final list of rollout_final entries (default: one per robot and slot), found through
+        # final_idx.  rollout_advantages() is the GAE pass over it.  After T steps ``step`` raises until rollout_begin() starts the
+        # next window from the last slot.  rollout_fields: names of _cabi.ROLLOUT_BITS; None = what the state handed out consists of
+        # -- the single-frame fields (the whole stacks with stack=True, instead of the frames they cover; the normalised pedestrian
+        # vector where the YAML lists StatePedVectorWrapper, instead of the raw one).  One more launch per chain; nothing
+        # synchronises.  Opt-in: 0 allocates and launches nothing.
+        self.rollout_horizon = int(rollout or 0)
+        if self.rollout_horizon > 0:
+            if rollout_fields is None:
+                stacked = {"sensor_maps": 0, "vector_states": 1, "lasers": 2} if self.stack else {}
+                fields = [n for n in list(_cabi.ROLLOUT_BITS)[:5] if (n != "lasers" or self.params.get("use_laser"))
+                          and not (n in stacked and self.world.stack_depths[stacked[n]] >= 2) and not (n == "ped_vector_states" and self._ped_norm)]
+                if self.stack and any(d >= 2 for d in self.world.stack_depths):
+                    fields.append("stacks")
+                if self._ped_norm:
+                    fields.append("ped_vector_norm")
+            else:
+                fields = rollout_fields
+            final = int(rollout_final) if rollout_final is not None else (self.rollout_horizon + 1) * len(self)
+            self.world.enable_rollout(self.rollout_horizon, final, fields)
+
+    def rollout(self):
+        """``{"n": transitions stored, "resets": reset chains stored, **World.rollout}``: the device tensors as they are -- no
+        synchronisation; ordered on the current stream behind the last reset / step.  ``final_n[resets & 1]`` counts the final entries."""
+        if self.rollout_horizon <= 0:
+            raise RuntimeError("VecImageEnv was made without rollout=T")
+        n, resets = self.world.rollout_cursor()
+        return dict(self.world.rollout, n=n, resets=resets)
+
+    def rollout_begin(self):
+        """start the next window: the last slot becomes slot 0 (``imgenv_rollout_begin``)"""
+        if self.rollout_horizon <= 0:
+            raise RuntimeError("VecImageEnv was made without rollout=T")
+        self.world.rollout_begin()
+
+    def rollout_advantages(self, values, final_values=None, gamma=0.99, lam=0.95):
+        """``(adv, ret)`` float32 ``[T, n]`` of the stored transitions (``imgenv_rollout_gae``): ``values`` float32 ``[T + 1, n]``,
+        the value of every slot's state; ``final_values`` float32 ``[rollout_final]`` or None, the value of every final entry"""
+        if self.rollout_horizon <= 0:
+            raise RuntimeError("VecImageEnv was made without rollout=T")
+        return self.world.rollout_gae(values, final_values, gamma, lam)
 
     def episode_tensors(self):
         """the per-robot device tensors of the statistics (``World.episodes``: ``ends`` [6, n], ``episodes``, ``last_episode``,
@@ -271,7 +317,13 @@ class VecImageEnv:
                           ped_vector, o["ped_maps"], o["step_ds"], o["ped_min_dists"])
 
     def reset(self, layouts=None):
-        """every env starts a new episode (ImageEnv.reset per env, yaml_env.py:296-317)"""
+        """every env starts a new episode (ImageEnv.reset per env, yaml_env.py:296-317); with ``rollout=T`` a new window starts"""
+        state = self._reset(layouts)
+        if self.rollout_horizon > 0:
+            self.world.rollout_begin()
+        return state
+
+    def _reset(self, layouts=None):
         if layouts is None and self.n_scenarios:  # env k replays episode k % N; the device continues the queue from env_num on
             self.world.reset_worlds_scenarios(range(self.env_num), [k % self.n_scenarios for k in range(self.env_num)])
             if self.device_reset:

@@ -119,6 +119,7 @@ class World:
         self.action_outputs = None  # enable_actions()
         self.obs_post = None  # enable_obs_post()
         self.final_obs = None  # enable_final_obs()
+        self.rollout = None  # enable_rollout()
         if self.n_maps > 1:
             rest = self.grids[1:]
             rc = self.lib.imgenv_maps_add(self.h, len(rest), rest.ctypes.data, rest.shape[1], rest.shape[2])
@@ -441,6 +442,77 @@ class World:
             self.final_obs = self._views(fo, arrays, "imgenv_final_obs_out")
         return self.final_obs
 
+    def enable_rollout(self, horizon, final_capacity, fields=None):
+        """Rollout storage (``imgenv_rollout_enable``): after ``rollout_begin()`` every step chain also stores its transition and
+        the observation it led to, and every reset chain moves the rows it overwrites into a final list, in ``self.rollout``:
+        zero-copy tensors over the library's memory -- ``obs_<field>`` ``[T + 1, R, ...]`` and ``final_<field>`` ``[F, ...]`` with
+        the row shapes and dtypes of ``out`` / ``stack`` / ``obs_post``, ``actions`` float32 ``[T, R, 3]``, ``rewards`` float32,
+        ``dones`` / ``is_clean`` uint8 and ``dones_info`` int32 ``[T, R]``, ``final_idx`` int32 ``[T + 1, R]``, ``final_slot`` /
+        ``final_row`` int32 ``[F]`` and ``final_n`` int32 ``[2]`` (include/imgenv.h has the semantics).  ``fields``: names of
+        ``_cabi.ROLLOUT_BITS``; None = the five single-frame fields (without ``lasers`` on a handle without a laser).  One extra
+        launch per chain; nothing synchronises.  Read-only; valid until ``close()``.  ValueError for a refused cfg or a second
+        call with another one, RuntimeError for ``"stacks"`` / ``"ped_vector_norm"`` before their own enable call."""
+        if fields is None:
+            fields = [n for n in list(_cabi.ROLLOUT_BITS)[:5] if n != "lasers" or self.cfg.use_laser]
+        c = _cabi.make_rollout_cfg(horizon, final_capacity, fields)
+        ro = _cabi.RolloutOut()
+        self._call(self.lib.imgenv_rollout_enable(self.h, C.byref(c), C.byref(ro)), "imgenv_rollout_enable")
+        if self.rollout is None:
+            R, T, F = ro.n_local, ro.horizon, ro.final_capacity
+            lay = _cabi.out_layout(self._out_header, self.n_peds, self.cfg.ped_image_size[0], self.cfg.ped_image_size[1])
+            rows = {name: lay[name] for name in _cabi.ROLLOUT_FIELDS[:5]}
+            rows["ped_vector_norm"] = lay["ped_vector_states"]
+            for name, t in (self.stack or {}).items():
+                rows["stack_" + name] = (lay[name][0], tuple(t.shape))
+            arrays = {}
+            for name, (dt, shape) in rows.items():  # (shape[0] is R)
+                arrays["obs_" + name] = (dt, (T + 1,) + tuple(shape))
+                arrays["final_" + name] = (dt, (F,) + tuple(shape[1:]))
+            arrays.update(actions=(np.float32, (T, R, 3)), rewards=(np.float32, (T, R)), dones=(np.uint8, (T, R)), is_clean=(np.uint8, (T, R)),
+                          dones_info=(np.int32, (T, R)), final_idx=(np.int32, (T + 1, R)), final_slot=(np.int32, (F,)),
+                          final_row=(np.int32, (F,)), final_n=(np.int32, (2,)))  # (final_n: uint32 in the library)
+            self.rollout = self._views(ro, arrays, "imgenv_rollout_out")
+            self.rollout_horizon, self.rollout_final_capacity = T, F
+        return self.rollout
+
+    def rollout_cursor(self):
+        """``(n, resets)``: the transitions and the reset chains stored since ``rollout_begin()`` (``n`` -1 before the first one);
+        ``rollout["final_n"][resets & 1]`` is the number of final entries so far.  A host-side count: nothing synchronises."""
+        if self.rollout is None:
+            raise RuntimeError("enable_rollout() was not called")
+        ro = _cabi.RolloutOut()
+        self._check(self.lib.imgenv_rollout_outputs(self.h, C.byref(ro)), "imgenv_rollout_outputs")
+        return ro.n, ro.resets
+
+    def rollout_begin(self):
+        """``imgenv_rollout_begin``: slot n becomes slot 0 (the first time: the live observation), ``final_idx`` -1, ``final_n``
+        0 and the cursor 0, ordered on the current stream"""
+        self._check(self.lib.imgenv_rollout_begin(self.h, self._stream()), "imgenv_rollout_begin")
+
+    def rollout_gae(self, values, final_values=None, gamma=0.99, lam=0.95, adv=None, ret=None):
+        """``imgenv_rollout_gae``: advantages and returns of the stored transitions, one launch on the current stream.  ``values``
+        float32 ``[T + 1, R]`` and ``final_values`` float32 ``[F]`` or None are contiguous tensors on the handle's device.  Returns
+        ``(adv, ret)`` float32 ``[T, R]`` (made with zeros unless given); rows ``t >= n`` are left as they are."""
+        import torch
+        if self.rollout is None:
+            raise RuntimeError("enable_rollout() was not called")
+        T, F, R = self.rollout_horizon, self.rollout_final_capacity, self.n_local
+
+        def ok(t, shape):
+            return isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous() and tuple(t.shape) == shape
+        if not ok(values, (T + 1, R)) or (final_values is not None and not ok(final_values, (F,))):
+            raise ValueError("rollout_gae: values float32 [%d, %d] and final_values float32 [%d] or None, contiguous on %s" % (T + 1, R, F, self.device))
+        if adv is None:
+            adv = torch.zeros((T, R), dtype=torch.float32, device=self.device)
+        if ret is None:
+            ret = torch.zeros((T, R), dtype=torch.float32, device=self.device)
+        if not ok(adv, (T, R)) or not ok(ret, (T, R)):
+            raise ValueError("rollout_gae: adv and ret float32 [%d, %d], contiguous on %s" % (T, R, self.device))
+        fv = C.c_void_p(final_values.data_ptr()) if final_values is not None else None
+        self._check(self.lib.imgenv_rollout_gae(self.h, C.c_void_p(values.data_ptr()), fv, float(gamma), float(lam),
+                                                C.c_void_p(adv.data_ptr()), C.c_void_p(ret.data_ptr()), self._stream()), "imgenv_rollout_gae")
+        return adv, ret
+
     def reset(self, layout):
         """Reset everything. A handle of several worlds (``n_worlds`` > 1) takes either one batch of all robots and
         pedestrians (world-major) with an obstacle list shared by every world, or a list of one layout per world."""
@@ -629,7 +701,7 @@ class World:
 
     def close(self):
         if getattr(self, "h", None):
-            self.episodes = self.episode_log = self.action_outputs = self.obs_post = self.final_obs = None  # (views of memory the handle owns)
+            self.episodes = self.episode_log = self.action_outputs = self.obs_post = self.final_obs = self.rollout = None  # (views of memory the handle owns)
             self.lib.imgenv_destroy(self.h)
             self.h = None
 

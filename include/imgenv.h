@@ -794,6 +794,119 @@ int imgenv_final_obs_enable(imgenv_t* h, const imgenv_final_obs_cfg* cfg, imgenv
 /* IMGENV_ESTATE before imgenv_final_obs_enable() */
 int imgenv_final_obs_outputs(imgenv_t* h, imgenv_final_obs_out* out);
 
+/* ---- rollout storage: a trainer's [T, R, ...] arrays kept on the device, and the advantage pass over them ----
+ * The arrays of imgenv_out are working copies: the next step rewrites them and the stacks shift in place, so a trainer copies
+ * every observation field, reward, done, mask and action away after every step.  With this feature the library does that, with ONE
+ * extra launch per chain (k_rollout, csrc/rollout.h: the last launch of the chain, behind the observation post-processing whose
+ * output it may read), and it knows two things a trainer does not: which rows a reset chain has just overwritten -- also behind
+ * imgenv_step_autoreset_device -- and which transitions count (step_is_clean, dones_info).
+ *
+ * R = local robots, T = horizon, F = final_capacity.  Slot s of an obs array is the observation transition s starts from:
+ *   obs_<field>    [T+1][R][row]   the selected fields, shapes and types of a row as in imgenv_out / imgenv_stack_out /
+ *                                  imgenv_obs_post_out; always read from the kernels' working arena, also under
+ *                                  IMGENV_FLAG_FULL_REWRITE
+ *   actions        f32 [T][R][3]   the (v, w, beep) rows the step consumed (the decoded ones where imgenv_actions_decode feeds it)
+ *   rewards        f32 [T][R]      imgenv_out.step_rewards rounded once to float32
+ *   dones, is_clean u8 [T][R]      imgenv_out.step_dones, step_is_clean
+ *   dones_info     i32 [T][R]      imgenv_out.step_dones_info
+ *   final_idx      i32 [T+1][R]    -1, or the entry of the final list that holds what slot s showed for this row before a reset
+ *                                  chain overwrote it (>= F: the entry was dropped)
+ *   final_<field>  [F][row]        the overwritten rows
+ *   final_slot, final_row i32 [F]  where each entry came from
+ *   final_n        u32 [2]         entries so far, dropped ones included: reset chain number k since imgenv_rollout_begin reads
+ *                                  final_n[k & 1] and writes final_n[(k + 1) & 1]; imgenv_rollout_out.resets is k, so the current
+ *                                  count is final_n[resets & 1]
+ * The cursor n (transitions stored) is kept by the host.  Nothing is stored before the first imgenv_rollout_begin().  From then on
+ *   a step chain writes the transition into slot n and the observation it led to into slot n + 1, and n advances;
+ *   a reset chain -- whoever queued it: imgenv_reset, imgenv_reset_world(s) and their variants, imgenv_step_autoreset(_device) --
+ *     moves the rows of slot n it covers into the final list (entries are numbered in the chain's row order) and writes the new
+ *     episode's first observation into slot n.  A row reset twice at the same slot keeps the later entry.
+ * With n == T every step entry point (imgenv_step, _begin, _flags, imgenv_step_autoreset, _device) fails with IMGENV_EINVAL
+ * ("rollout full: imgenv_rollout_begin") before it queues anything.
+ * Memory: (T + 1) R x the selected rows + F x the same + 22 T R + 4 (T + 1) R + 8 F + 8 bytes (each array on a 256-byte
+ * boundary).  The five single-frame fields at 48 x 48 views, 360 beams, ped_vec_len 71 and 48 x 48 pedestrian maps is about 35 KB per robot and slot -- about 18 GB for T = 128 at 4096 robots, 78 % of
+ * it ped_maps: select what the policy reads.  Single frames unless STACKS is selected.  Read-only for the caller; stream order as
+ * for imgenv_out; no part of the output arena. */
+#define IMGENV_ROLLOUT_SENSOR_MAPS 1
+#define IMGENV_ROLLOUT_VECTOR_STATES 2
+#define IMGENV_ROLLOUT_LASERS 4             /* needs use_laser */
+#define IMGENV_ROLLOUT_PED_VECTOR_STATES 8
+#define IMGENV_ROLLOUT_PED_MAPS 16
+#define IMGENV_ROLLOUT_PED_NORM 32          /* imgenv_obs_post_out.ped_vector_norm: needs imgenv_obs_post_enable with IMGENV_OBS_PED_NORM */
+#define IMGENV_ROLLOUT_STACKS 64            /* the whole [K][frame] rows of every stack of depth >= 2 of imgenv_stack_enable() */
+#define IMGENV_ROLLOUT_ALL 127
+typedef struct imgenv_rollout_cfg {
+    int32_t struct_size;          /* sizeof(imgenv_rollout_cfg) */
+    int32_t horizon;              /* T >= 1 */
+    int32_t final_capacity;       /* F >= 1 */
+    int32_t fields;               /* IMGENV_ROLLOUT_* bits, at least one */
+} imgenv_rollout_cfg;
+typedef struct imgenv_rollout_out {
+    int32_t struct_size;          /* on entry 0 or sizeof(imgenv_rollout_out) */
+    int32_t n_local;              /* R */
+    int32_t horizon;              /* T */
+    int32_t final_capacity;       /* F */
+    int32_t n;                    /* the cursor: transitions stored since imgenv_rollout_begin(); -1 before the first one */
+    int32_t resets;               /* reset chains stored since imgenv_rollout_begin() */
+    /* [T+1][R][row]; NULL where not selected (the stacks: where the depth is below 2 -- select the field itself) */
+    uint16_t* obs_sensor_maps;
+    float* obs_vector_states;
+    double* obs_lasers;
+    float* obs_ped_vector_states;
+    float* obs_ped_maps;
+    float* obs_ped_vector_norm;
+    uint16_t* obs_stack_sensor_maps;
+    float* obs_stack_vector_states;
+    double* obs_stack_lasers;
+    /* [F][row], NULL as above */
+    uint16_t* final_sensor_maps;
+    float* final_vector_states;
+    double* final_lasers;
+    float* final_ped_vector_states;
+    float* final_ped_maps;
+    float* final_ped_vector_norm;
+    uint16_t* final_stack_sensor_maps;
+    float* final_stack_vector_states;
+    double* final_stack_lasers;
+    float* actions;
+    float* rewards;
+    uint8_t* dones;
+    uint8_t* is_clean;
+    int32_t* dones_info;
+    int32_t* final_idx;
+    int32_t* final_slot;
+    int32_t* final_row;
+    uint32_t* final_n;
+} imgenv_rollout_out;
+/* Legal at any time; the memory is the library's (allocated all or nothing) and lives until imgenv_destroy().  IMGENV_EINVAL for
+ * a wrong struct_size, horizon < 1, final_capacity < 1, (horizon + 1) x R beyond 2^31 - 1, no or unknown bits, a field the handle
+ * does not produce (LASERS without use_laser, STACKS on a handle none of whose stacks is deeper than 1), or a second call whose cfg
+ * differs from the first's (same cfg: nothing changes, same pointers).  IMGENV_ESTATE for STACKS before imgenv_stack_enable() and
+ * for PED_NORM before imgenv_obs_post_enable() with IMGENV_OBS_PED_NORM.  IMGENV_ENOMEM when the arrays cannot be allocated; the
+ * handle is then unchanged.  `out` may be NULL. */
+int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* cfg, imgenv_rollout_out* out);
+/* the same struct with the cursor (n, resets) of this moment.  IMGENV_ESTATE before imgenv_rollout_enable() */
+int imgenv_rollout_outputs(imgenv_t* h, imgenv_rollout_out* out);
+/* Start (over): one launch copies the rows of slot n into slot 0 -- the first time the live arrays -- then final_idx becomes -1 and
+ * final_n 0 by stream-ordered fills, and n = 0.  Nothing synchronises.  IMGENV_ESTATE before imgenv_rollout_enable() or before a
+ * chain of launches has completed on the handle (there is no observation yet). */
+int imgenv_rollout_begin(imgenv_t* h, void* stream);
+/* Generalised advantage estimation over the n stored transitions, one launch (k_rollout_gae).  DEVICE pointers: `values` f32
+ * [T+1][R], the caller's value estimate of every slot; `final_values` f32 [F], its estimate of every final entry, or NULL; `adv`
+ * and `ret` f32 [T][R], of which rows t >= n are left untouched.  Everything is float32, per row and t = n - 1 .. 0:
+ *   gl = gamma * lam                                                          (once)
+ *   e        = final_idx[t+1][row]
+ *   terminal = dones && dones_info != 10
+ *   nv   = terminal ? 0 : e >= 0 ? ((e < F && final_values) ? final_values[e] : 0) : values[t+1][row]
+ *   cont = (dones || e >= 0) ? 0 : 1
+ *   if (!is_clean) { adv = 0; ret = 0; gae = 0 }
+ *   else { m = gamma * nv; s = rewards + m; delta = s - values[t][row];
+ *          c = gl * gae; c = cont ? c : 0; gae = delta + c; adv = gae; ret = gae + values[t][row] }
+ * A real end bootstraps from nothing; a row whose next slot a reset overwrote (a time-out, or a caller's reset in mid-episode)
+ * from the value of what the reset overwrote; anything else from the next slot, a time-out nobody has reset yet included.
+ * IMGENV_EINVAL for a null values / adv / ret, IMGENV_ESTATE before imgenv_rollout_begin(). */
+int imgenv_rollout_gae(imgenv_t* h, const float* values, const float* final_values, float gamma, float lam, float* adv, float* ret, void* stream);
+
 /* ---- map bank: several static maps in one handle, one of them per world and episode ----
  * The reference trains one policy over a set of maps: its trainer is started from several YAML files side by side
  * (create_launch.py:57-65, one node per (env_name, env_num) pair), each env process loads its own global_map.map_file

@@ -16,6 +16,11 @@ statistics / statistics / statistics + log over several rounds -- the device_res
 its difference between the last two is what the log's launch costs a reset chain.  --final-obs-compare alternates the final
 observations (VecImageEnv(final_obs=True), imgenv_final_obs_enable: one more launch per reset chain) off / on in the same way.
 
+--rollout-compare runs device_reset steps three ways, one process per measurement, alternating over several rounds: no rollout
+storage, the library's (VecImageEnv(rollout=--horizon), imgenv_rollout_enable: one more launch per chain, a new window every
+--horizon steps) and the same arrays kept by torch on top of the first (buf[t].copy_(x) per field and scalar, the final rows taken
+whole from final_obs=True); then the advantage pass (imgenv_rollout_gae) against a torch loop over t for a rollout of 128 steps.
+
 --wrappers table|clip feeds the policy's raw output (indices into a 28-row table, or float rows to be clipped) to
 VecImageEnv(wrappers=True): decode, speeds, normalised pedestrian vectors and close_to_human kept by the library;
 --torch-wrappers keeps the same with torch ops on top of a plain VecImageEnv; --wrappers-compare alternates pre-decoded actions
@@ -612,6 +617,139 @@ def compare_scenarios(args, rounds=3):
                 time_max=args.time_max, rounds=rounds, runs=runs, summary=summary)
 
 
+def torch_gae(r, values, final_values, gamma, lam, n, F):
+    """imgenv_rollout_gae's rule as a torch loop over t (include/imgenv.h), on the ring's tensors"""
+    import torch
+    adv, ret = torch.zeros_like(r["rewards"]), torch.zeros_like(r["rewards"])
+    gae, gl, zero = torch.zeros_like(values[0]), gamma * lam, torch.zeros_like(values[0])
+    for t in range(n - 1, -1, -1):
+        e = r["final_idx"][t + 1]
+        done, has, clean = r["dones"][t] != 0, e >= 0, r["is_clean"][t] != 0
+        terminal = done & (r["dones_info"][t] != 10)
+        kept = torch.where(has & (e < F), final_values[e.clamp(0, F - 1).long()], zero)
+        nv = torch.where(terminal, zero, torch.where(has, kept, values[t + 1]))
+        delta = r["rewards"][t] + gamma * nv - values[t]
+        gae = torch.where(clean, delta + torch.where(done | has, zero, gl * gae), zero)
+        adv[t] = gae
+        ret[t] = torch.where(clean, gae + values[t], zero)
+    return adv, ret
+
+
+def measure_rollout(variant, envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, horizon=32):
+    """us per VecImageEnv.step (device_reset=True) with the rollout kept by nobody ("none"), by the library ("library":
+    ``rollout=horizon``, a new window every ``horizon`` steps) or by torch on top of "none" ("torch": ``buf[t].copy_(x)`` per field and
+    scalar, the final rows and ``all_down`` taken whole from ``final_obs=True`` -- without a host read nobody outside the library
+    knows which rows they are); "gae": the device's advantage pass against ``torch_gae`` over a rollout of 128 steps"""
+    import torch
+    from img_env_amd import worldgen
+    from img_env_amd.vec_env import VecImageEnv
+    grid = worldgen.make_grid(200, 2)
+    cfg = worldgen.make_yaml_cfg(robots, peds, grid, time_max=time_max, n_obstacles=obstacles, seed=5)
+    fields = ("sensor_maps", "vector_states", "lasers", "ped_vector_states", "ped_maps")
+    gae = variant == "gae"
+    T = 128 if gae else horizon
+    n = envs * robots
+    env = VecImageEnv(cfg, env_num=envs, seed=5, device_reset=True, final_obs=variant == "torch",
+                      rollout=T if variant in ("library", "gae") else 0, rollout_final=4 * n if gae else n,
+                      rollout_fields=["vector_states"] if gae else None)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    acts = torch.zeros(16, n, 3, device="cuda")
+    acts[:, :, 0] = torch.rand(16, n, generator=g, device="cuda") * 0.6
+    acts[:, :, 1] = torch.rand(16, n, generator=g, device="cuda") * 1.8 - 0.9
+    buf = None
+    if variant == "torch":
+        o, f = env.world.out, env.world.final_obs
+        buf = {"obs_" + k: torch.zeros((T + 1,) + tuple(o[k].shape), dtype=o[k].dtype, device="cuda") for k in fields}
+        buf.update({"final_" + k: torch.zeros((T,) + tuple(f[k].shape), dtype=f[k].dtype, device="cuda") for k in fields})
+        buf.update(actions=torch.zeros(T, n, 3, device="cuda"), rewards=torch.zeros(T, n, device="cuda"),
+                   dones=torch.zeros(T, n, dtype=torch.uint8, device="cuda"), is_clean=torch.zeros(T, n, dtype=torch.uint8, device="cuda"),
+                   dones_info=torch.zeros(T, n, dtype=torch.int32, device="cuda"), all_down=torch.zeros(T, n, dtype=torch.bool, device="cuda"))
+    cursor = [0]
+
+    def step(a):
+        t = cursor[0]
+        if t == T:  # the next window starts from the last slot
+            if variant == "library":
+                env.rollout_begin()
+            elif buf is not None:
+                for k in fields:
+                    buf["obs_" + k][0].copy_(buf["obs_" + k][T])
+            t = 0
+        _, rew, done, info = env.step(a)
+        if buf is not None:
+            o, f = env.world.out, env.world.final_obs
+            for k in fields:
+                buf["obs_" + k][t + 1].copy_(o[k])
+                buf["final_" + k][t].copy_(f[k])
+            buf["actions"][t].copy_(a)
+            buf["rewards"][t].copy_(rew)
+            buf["dones"][t].copy_(done)
+            buf["is_clean"][t].copy_(info["is_clean"])
+            buf["dones_info"][t].copy_(info["dones_info"])
+            buf["all_down"][t].copy_(info["all_down"])
+        cursor[0] = t + 1
+    env.reset()
+    if gae:
+        for s in range(T):
+            env.step(acts[s % 16])
+        r = env.rollout()
+        F = r["final_row"].shape[0]
+        values, fv = torch.randn(T + 1, n, generator=g, device="cuda"), torch.randn(F, generator=g, device="cuda")
+        res = {}
+        for name, fn in (("device", lambda: env.rollout_advantages(values, fv, 0.99, 0.95)), ("torch", lambda: torch_gae(r, values, fv, 0.99, 0.95, T, F))):
+            fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(20):
+                out = fn()
+            torch.cuda.synchronize()
+            res["us_per_pass_" + name] = 1e6 * (time.perf_counter() - t0) / 20
+            res[name] = out
+        res["max_abs_diff"] = float((res.pop("device")[0] - res.pop("torch")[0]).abs().max())  # (the torch loop's order of operations is its own)
+        env.close()
+        return dict(horizon=T, rows=n, **res)
+    for s in range(time_max + 20):  # the drift phase: past the first wave of time limits
+        step(acts[s % 16])
+    torch.cuda.synchronize()
+    worlds, first = env.world.autoreset_last()
+    placed0, t0 = first + len(worlds), time.perf_counter()
+    for s in range(steps):
+        step(acts[s % 16])
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    worlds, first = env.world.autoreset_last()
+    env.close()
+    return dict(us_per_step=1e6 * dt / steps, env_resets_per_step=(first + len(worlds) - placed0) / steps, horizon=T)
+
+
+def compare_rollout(args, rounds=3):
+    """none / library / torch, alternating, `rounds` times, then the advantage pass once; one process per measurement"""
+    import subprocess
+    base = [sys.executable, os.path.abspath(__file__), "--envs", str(args.envs), "--robots", str(args.robots), "--peds", str(args.peds),
+            "--obstacles", str(args.obstacles), "--steps", str(args.steps), "--time-max", str(args.time_max), "--horizon", str(args.horizon)]
+
+    def one(variant):
+        out = subprocess.run(base + ["--rollout-variant", variant], capture_output=True, text=True, timeout=900)
+        if out.returncode != 0:
+            raise RuntimeError("%s: exit %d\n%s" % (variant, out.returncode, out.stderr[-2000:]))
+        return json.loads(out.stdout.strip().splitlines()[-1])
+    variants, runs = ("none", "library", "torch"), []
+    for rnd in range(rounds):
+        for variant in variants:
+            runs.append(dict(round=rnd, variant=variant, **one(variant)))
+            print(json.dumps(runs[-1]), flush=True)
+    summary = {}
+    for variant in variants:
+        v = [r["us_per_step"] for r in runs if r["variant"] == variant]
+        summary[variant] = dict(us_per_step_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
+    summary["added_us_library"] = summary["library"]["median"] - summary["none"]["median"]
+    summary["added_us_torch"] = summary["torch"]["median"] - summary["none"]["median"]
+    summary["gae"] = one("gae")
+    print(json.dumps(summary["gae"]), flush=True)
+    return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, steps=args.steps, time_max=args.time_max,
+                horizon=args.horizon, rounds=rounds, runs=runs, summary=summary)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
@@ -648,6 +786,11 @@ def main():
     ap.add_argument("--scenarios", type=int, default=500, help="--scenarios-compare: recorded episodes in the list")
     ap.add_argument("--scenarios-variant", default=None, choices=("python_loop", "scenarios", "sampler"), help="one measurement of --scenarios-compare")
     ap.add_argument("--parent-tree", default=None, help="--scenarios-compare: a built checkout of another commit, measured as variant \"parent\"")
+    ap.add_argument("--rollout-compare", action="store_true",
+                    help="device_reset steps with no rollout storage / the library's (rollout=T) / the same arrays kept by torch copies, "
+                         "alternating over --rounds rounds, and the advantage pass against a torch loop; one process per measurement")
+    ap.add_argument("--rollout-variant", default=None, choices=("none", "library", "torch", "gae"), help="one measurement of --rollout-compare")
+    ap.add_argument("--horizon", type=int, default=32, help="--rollout-compare: transitions per window")
     ap.add_argument("--tree", default=None, help="import img_env_amd from this checkout instead of the tool's own")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None, help="--stack-compare / --episodes-compare: also write the JSON here")
@@ -655,6 +798,17 @@ def main():
     if args.scenarios_variant:
         print(json.dumps(measure_scenarios(args.scenarios_variant, args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max,
                                            args.scenarios)))
+        return
+    if args.rollout_variant:
+        print(json.dumps(measure_rollout(args.rollout_variant, args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max,
+                                         args.horizon)))
+        return
+    if args.rollout_compare:
+        res = compare_rollout(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
         return
     if args.scenarios_compare:
         res = compare_scenarios(args, args.rounds)

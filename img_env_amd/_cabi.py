@@ -347,6 +347,64 @@ def make_rollout_cfg(horizon, final_capacity, fields):
     return c
 
 
+#: rollout minibatches (imgenv_rollout_minibatch_enable; csrc/minibatch.h)
+MB_MAX_SCALARS, MB_MAX_BUFFERS = 6, 4
+#: the launch shapes and the shuffle's rounds (csrc/launch_plan.h)
+MB_INDEX_BLOCK, MB_LANE_FLAGS, MB_TILE, MB_SCAN_BLOCK, MB_STATS_BLOCK, MB_STATS_PER_LANE, MB_SHUFFLE_BLOCK, MB_ROUNDS = 256, 16, 4096, 256, 256, 16, 256, 6
+#: the per-transition arrays of imgenv_minibatch_buffer behind its mb_<field> pointers, in the struct's order
+MB_SCALARS = ("mb_actions", "mb_rewards", "mb_dones", "mb_dones_info", "mb_index", "mb_weight", "mb_scalars")
+MB_HEADER = ("struct_size", "n_local", "horizon", "batch", "buffers", "fields")
+#: the handle-wide pointers of imgenv_minibatch_out, in the struct's order
+MB_ARRAYS = ("valid", "order", "valid_n", "norm", "tile_count", "tile_base", "stat_part", "stat_mean")
+
+
+class MinibatchCfg(C.Structure):
+    _fields_ = [("struct_size", _i32), ("batch", _i32), ("buffers", _i32), ("fields", _i32)]
+
+
+class MinibatchBuffer(C.Structure):
+    _fields_ = [("mb_" + name, C.c_void_p) for name in ROLLOUT_FIELDS] + [(name, C.c_void_p) for name in MB_SCALARS]
+
+
+class MinibatchOut(C.Structure):
+    _fields_ = [(name, _i32) for name in MB_HEADER] + [(name, C.c_void_p) for name in MB_ARRAYS] + [("buf", MinibatchBuffer * MB_MAX_BUFFERS)]
+
+
+class MinibatchArgs(C.Structure):
+    _fields_ = [("struct_size", _i32), ("j", _i32), ("buffer", _i32), ("n_scalars", _i32), ("normalise", _i32), ("reserved", _i32),
+                ("scalars", C.c_void_p * MB_MAX_SCALARS), ("norm", C.c_void_p)]
+
+
+def make_minibatch_cfg(batch, buffers=1, fields=0):
+    """``imgenv_minibatch_cfg``: ``fields`` is an int of IMGENV_ROLLOUT_* bits (0: every field the rollout stores) or an iterable
+    of ``ROLLOUT_BITS`` names"""
+    c = MinibatchCfg()
+    c.struct_size = C.sizeof(MinibatchCfg)
+    c.batch, c.buffers = int(batch), int(buffers)
+    if fields is None:
+        fields = 0
+    if isinstance(fields, (int, np.integer)):
+        c.fields = int(fields)
+    else:
+        names = list(fields)
+        unknown = [n for n in names if n not in ROLLOUT_BITS]
+        if unknown:
+            raise ValueError("minibatch fields: unknown %s (known: %s)" % (unknown, ", ".join(ROLLOUT_BITS)))
+        c.fields = sum({ROLLOUT_BITS[n] for n in names})
+    return c
+
+
+def make_minibatch_args(j, buffer=0, scalars=(), normalise=-1, norm=None):
+    """``imgenv_minibatch_args``: ``scalars`` device addresses (ints), ``norm`` one or None"""
+    a = MinibatchArgs()
+    a.struct_size = C.sizeof(MinibatchArgs)
+    a.j, a.buffer, a.n_scalars, a.normalise = int(j), int(buffer), len(scalars), int(normalise)
+    for s, ptr in enumerate(scalars[:MB_MAX_SCALARS]):
+        a.scalars[s] = ptr
+    a.norm = norm
+    return a
+
+
 #: name -> (numpy dtype, shape as a function of the Out header and the world sizes)
 def out_layout(o, n_peds, hp, wp):
     R, B = o.n_local, max(o.n_beams, 1)
@@ -500,6 +558,8 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_actions_enable", "imgenv_actions_outputs", "imgenv_actions_decode", "imgenv_obs_post_enable", "imgenv_obs_post_outputs",
            "imgenv_final_obs_enable", "imgenv_final_obs_outputs",
            "imgenv_rollout_enable", "imgenv_rollout_outputs", "imgenv_rollout_begin", "imgenv_rollout_gae",
+           "imgenv_rollout_minibatch_enable", "imgenv_rollout_minibatch_outputs", "imgenv_rollout_index", "imgenv_rollout_stats",
+           "imgenv_rollout_shuffle", "imgenv_rollout_minibatch",
            "imgenv_maps_add", "imgenv_world_maps_set", "imgenv_maps_policy", "imgenv_map_for_placement", "imgenv_world_maps",
            "imgenv_tracks_add", "imgenv_world_tracks_set", "imgenv_tracks_policy", "imgenv_tracks_for_placement", "imgenv_world_tracks",
            "imgenv_scenarios_add", "imgenv_scenarios_policy", "imgenv_scenario_for_placement", "imgenv_reset_worlds_scenarios",
@@ -572,6 +632,12 @@ def bind(lib):
     lib.imgenv_rollout_outputs.argtypes = [C.c_void_p, C.POINTER(RolloutOut)]
     lib.imgenv_rollout_begin.argtypes = [C.c_void_p, C.c_void_p]
     lib.imgenv_rollout_gae.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.imgenv_rollout_minibatch_enable.argtypes = [C.c_void_p, C.POINTER(MinibatchCfg), C.POINTER(MinibatchOut)]
+    lib.imgenv_rollout_minibatch_outputs.argtypes = [C.c_void_p, C.POINTER(MinibatchOut)]
+    lib.imgenv_rollout_index.argtypes = [C.c_void_p, C.c_void_p]
+    lib.imgenv_rollout_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    lib.imgenv_rollout_shuffle.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.imgenv_rollout_minibatch.argtypes = [C.c_void_p, C.POINTER(MinibatchArgs), C.c_void_p]
     lib.imgenv_maps_add.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
     lib.imgenv_world_maps_set.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
     lib.imgenv_maps_policy.argtypes = [C.c_void_p, C.c_int32]

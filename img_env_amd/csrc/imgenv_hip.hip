@@ -30,6 +30,7 @@
 #include "obs_post.h"
 #include "final_obs.h"
 #include "rollout.h"
+#include "minibatch.h"
 #include "map_bank.h"
 #include "spawn_slot.h"
 #include "bank_host.h"
@@ -260,6 +261,16 @@ struct imgenv {
     size_t roll_row_bytes[ROLLOUT_MAX_FIELDS];
     imgenv_rollout_cfg roll_cfg;
     imgenv_rollout_out roll_out;
+    // rollout minibatches (imgenv_rollout_minibatch_enable; csrc/minibatch.h)
+    bool mb_on = false;
+    uint64_t chain_seq = 0;      // chains (and imgenv_rollout_begin calls) queued on the handle so far
+    bool mb_indexed = false;     // imgenv_rollout_index has run; its generation:
+    int mb_gen_n = 0;
+    uint64_t mb_gen_seq = 0;
+    bool mb_shuffled = false;    // imgenv_rollout_shuffle has run on that index
+    MbGatherDev mb_gather;       // the field table and the ring's scalars; dst pointers are the buffer's (mb_out)
+    imgenv_minibatch_cfg mb_cfg;
+    imgenv_minibatch_out mb_out;
     bool chain_open = false;  // a chain of launches that hands over through tail_sig / tail_cnt has started and not been completed
     std::vector<RvoObstacles> rvos;  // one obstacle set per world
     int sfm_cap_obs = 0;
@@ -1902,6 +1913,7 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
     HIPCHK(hipGetLastError());
     h->chain_open = false;
     h->obs_exists = true;
+    h->chain_seq += 1;
     return outputs_seal(h, st);
 }
 
@@ -4460,6 +4472,7 @@ extern "C" int imgenv_rollout_begin(imgenv_t* h, void* stream) {
     h->roll_begun = true;
     h->roll_n = 0;
     h->roll_turn = 0;
+    h->chain_seq += 1;
     return IMGENV_OK;
 }
 
@@ -4474,6 +4487,219 @@ extern "C" int imgenv_rollout_gae(imgenv_t* h, const float* values, const float*
     const RolloutGaeDev g = {ro.rewards, ro.dones, ro.is_clean, ro.dones_info, ro.final_idx, values, final_values, adv, ret, gamma, lam, h->roll_n, ro.F, h->RL};
     const LaunchShape s = plan_rollout_gae_launch(h->plan);
     k_rollout_gae<<<dim3(s.grid), dim3(s.block), 0, (hipStream_t)stream>>>(g);
+    HIPCHK(hipGetLastError());
+    return IMGENV_OK;
+}
+
+// ---- rollout minibatches (include/imgenv.h; the kernels are csrc/minibatch.h) ----
+extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibatch_cfg* c, imgenv_minibatch_out* out) {
+    // (the cfg first, as above)
+    RTRY(enable_args(c, "imgenv_minibatch_cfg", out, "imgenv_minibatch_out"));
+    if (c->batch < 1) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.batch %d: at least 1", c->batch);
+    if (c->buffers < 1 || c->buffers > IMGENV_MB_MAX_BUFFERS) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.buffers %d: 1 .. %d", c->buffers, IMGENV_MB_MAX_BUFFERS);
+    if (c->fields & ~IMGENV_ROLLOUT_ALL) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d", c->fields);
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->roll_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch_enable before imgenv_rollout_enable");
+    if (h->mb_on) {
+        const imgenv_minibatch_cfg& o = h->mb_cfg;
+        if (c->batch != o.batch || c->buffers != o.buffers || c->fields != o.fields)
+            FAIL(IMGENV_EINVAL, "imgenv_rollout_minibatch_enable: the handle already gathers minibatches of batch %d, buffers %d, fields %d", o.batch,
+                 o.buffers, o.fields);
+        return out ? imgenv_rollout_minibatch_outputs(h, out) : IMGENV_OK;
+    }
+    const int want = c->fields ? c->fields : h->roll_cfg.fields;
+    if (want & ~h->roll_cfg.fields) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: the rollout stores %d", c->fields, h->roll_cfg.fields);
+    // the ring's fields in its own order, each found again by its obs_ pointer
+    const imgenv_rollout_out& ro = h->roll_out;
+    struct Src {
+        int bit;
+        const void* ring;
+        size_t slot;  // of imgenv_minibatch_buffer, in pointers
+    };
+    const Src all[] = {
+        {IMGENV_ROLLOUT_SENSOR_MAPS, ro.obs_sensor_maps, offsetof(imgenv_minibatch_buffer, mb_sensor_maps)},
+        {IMGENV_ROLLOUT_VECTOR_STATES, ro.obs_vector_states, offsetof(imgenv_minibatch_buffer, mb_vector_states)},
+        {IMGENV_ROLLOUT_LASERS, ro.obs_lasers, offsetof(imgenv_minibatch_buffer, mb_lasers)},
+        {IMGENV_ROLLOUT_PED_VECTOR_STATES, ro.obs_ped_vector_states, offsetof(imgenv_minibatch_buffer, mb_ped_vector_states)},
+        {IMGENV_ROLLOUT_PED_MAPS, ro.obs_ped_maps, offsetof(imgenv_minibatch_buffer, mb_ped_maps)},
+        {IMGENV_ROLLOUT_PED_NORM, ro.obs_ped_vector_norm, offsetof(imgenv_minibatch_buffer, mb_ped_vector_norm)},
+        {IMGENV_ROLLOUT_STACKS, ro.obs_stack_sensor_maps, offsetof(imgenv_minibatch_buffer, mb_stack_sensor_maps)},
+        {IMGENV_ROLLOUT_STACKS, ro.obs_stack_vector_states, offsetof(imgenv_minibatch_buffer, mb_stack_vector_states)},
+        {IMGENV_ROLLOUT_STACKS, ro.obs_stack_lasers, offsetof(imgenv_minibatch_buffer, mb_stack_lasers)},
+    };
+    static_assert(sizeof(all) / sizeof(all[0]) <= ROLLOUT_MAX_FIELDS, "ROLLOUT_MAX_FIELDS");
+    const size_t RL = (size_t)h->RL, T = (size_t)h->roll_cfg.horizon, B = (size_t)c->batch, NB = (size_t)c->buffers;
+    const size_t tiles = std::max(plan_mb_tiles(T * RL), plan_mb_stats_tiles(T * RL));
+    MbGatherDev g;
+    memset(&g, 0, sizeof(g));
+    size_t row_bytes[ROLLOUT_MAX_FIELDS], slot[ROLLOUT_MAX_FIELDS];
+    for (int k = 0; k < h->roll.n_fields; k++)
+        for (const Src& s : all) {
+            if (!s.ring || s.ring != (const void*)h->roll.f[k].ring || !(want & s.bit)) continue;
+            MbGatherField& f = g.f[g.n_fields];
+            f.ring = h->roll.f[k].ring;
+            f.unit = h->roll.f[k].unit;
+            f.chunks = h->roll.f[k].chunks;
+            g.chunks_per_row += f.chunks;
+            row_bytes[g.n_fields] = h->roll_row_bytes[k];
+            slot[g.n_fields++] = s.slot;
+        }
+    if (g.n_fields == 0) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: no field of the rollout", c->fields);
+    // one block, every array on a 256-byte boundary, zeroed; nothing of the handle changes before it is there
+    size_t total = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = total;
+        total = align256(total + bytes);
+        return at;
+    };
+    const size_t off_valid = carve(T * RL * 4), off_order = carve(T * RL * 4), off_vn = carve(4), off_norm = carve(8);
+    const size_t off_tc = carve(tiles * 4), off_tb = carve(tiles * 4), off_part = carve(tiles * 8), off_mean = carve(8);
+    size_t off_f[IMGENV_MB_MAX_BUFFERS][ROLLOUT_MAX_FIELDS], off_s[IMGENV_MB_MAX_BUFFERS][7];
+    for (int k = 0; k < g.n_fields; k++)  // (a field's buffers side by side: one strided view covers them)
+        for (size_t b = 0; b < NB; b++) off_f[b][k] = carve(B * row_bytes[k]);
+    const size_t scalar_bytes[7] = {B * 12, B * 4, B, B * 4, B * 4, B * 4, B * 4 * IMGENV_MB_MAX_SCALARS};
+    for (int q = 0; q < 7; q++)
+        for (size_t b = 0; b < NB; b++) off_s[b][q] = carve(scalar_bytes[q]);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    unsigned char* block = nullptr;
+    DevTxn<HipApi> txn;
+    if (!txn.room(&block, total, 0)) FAIL(txn.code(), "imgenv_rollout_minibatch_enable: %s", txn.error());
+    txn.commit(h->allocs);
+    imgenv_minibatch_out o = {};
+    o.horizon = h->roll_cfg.horizon;
+    o.batch = c->batch;
+    o.buffers = c->buffers;
+    o.fields = want;
+    o.valid = (int32_t*)(block + off_valid);
+    o.order = (int32_t*)(block + off_order);
+    o.valid_n = (uint32_t*)(block + off_vn);
+    o.norm = (float*)(block + off_norm);
+    o.tile_count = (int32_t*)(block + off_tc);
+    o.tile_base = (int32_t*)(block + off_tb);
+    o.stat_part = (double*)(block + off_part);
+    o.stat_mean = (double*)(block + off_mean);
+    for (size_t b = 0; b < NB; b++) {
+        imgenv_minibatch_buffer& m = o.buf[b];
+        for (int k = 0; k < g.n_fields; k++) *(void**)((unsigned char*)&m + slot[k]) = block + off_f[b][k];
+        m.mb_actions = (float*)(block + off_s[b][0]);
+        m.mb_rewards = (float*)(block + off_s[b][1]);
+        m.mb_dones = block + off_s[b][2];
+        m.mb_dones_info = (int32_t*)(block + off_s[b][3]);
+        m.mb_index = (int32_t*)(block + off_s[b][4]);
+        m.mb_weight = (float*)(block + off_s[b][5]);
+        m.mb_scalars = (float*)(block + off_s[b][6]);
+    }
+    g.order = o.order;
+    g.B = (uint32_t)c->batch;
+    g.TR = (uint32_t)(T * RL);
+    g.actions = h->roll.actions;
+    g.rewards = h->roll.rewards;
+    g.dones = h->roll.dones;
+    g.dones_info = h->roll.dones_info;
+    for (int k = 0; k < g.n_fields; k++) g.f[k].dst = (unsigned char*)(uintptr_t)slot[k];  // (which pointer of the buffer: mb_gather_args)
+    h->mb_gather = g;
+    h->mb_cfg = *c;
+    h->mb_indexed = h->mb_shuffled = false;
+    return enable_done(h, o, &imgenv::mb_out, &imgenv::mb_on, out);
+}
+
+extern "C" int imgenv_rollout_minibatch_outputs(imgenv_t* h, imgenv_minibatch_out* out) {
+    return feature_outputs(h, &imgenv::mb_on, &imgenv::mb_out, out, "imgenv_rollout_minibatch_enable");
+}
+
+// the index is of this moment: no chain and no imgenv_rollout_begin since
+static int minibatch_fresh(const imgenv* h, const char* who) {
+    if (!h->mb_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch_enable was not called");
+    if (!h->mb_indexed) FAIL(IMGENV_ESTATE, "%s before imgenv_rollout_index", who);
+    if (!h->roll_begun || h->mb_gen_n != h->roll_n || h->mb_gen_seq != h->chain_seq) FAIL(IMGENV_ESTATE, "%s: rollout changed since imgenv_rollout_index", who);
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_rollout_index(imgenv_t* h, void* stream) {
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->mb_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch_enable was not called");
+    if (!h->roll_begun) FAIL(IMGENV_ESTATE, "imgenv_rollout_index before imgenv_rollout_begin");
+    if (h->roll_n == 0) FAIL(IMGENV_ESTATE, "imgenv_rollout_index: no transition is stored yet");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    const imgenv_minibatch_out& o = h->mb_out;
+    const size_t total = (size_t)h->roll_n * (size_t)h->RL;
+    const MbIndexDev d = {h->roll.is_clean, o.valid, o.tile_count, o.tile_base, o.valid_n, (uint32_t)total, (uint32_t)plan_mb_tiles(total)};
+    const LaunchShape tiles = plan_mb_index_launch(total), one = plan_mb_scan_launch();
+    k_mb_count<<<dim3(tiles.grid), dim3(tiles.block), 0, st>>>(d);
+    k_mb_scan<<<dim3(one.grid), dim3(one.block), 0, st>>>(d);
+    k_mb_scatter<<<dim3(tiles.grid), dim3(tiles.block), 0, st>>>(d);
+    HIPCHK(hipGetLastError());
+    h->mb_indexed = true;
+    h->mb_shuffled = false;
+    h->mb_gen_n = h->roll_n;
+    h->mb_gen_seq = h->chain_seq;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_rollout_stats(imgenv_t* h, const float* x, double eps, float* norm_out, void* stream) {
+    if (!h || !x) FAIL(IMGENV_EINVAL, "null argument");
+    if (!(eps >= 0.0)) FAIL(IMGENV_EINVAL, "imgenv_rollout_stats: eps %g", eps);
+    RTRY(minibatch_fresh(h, "imgenv_rollout_stats"));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    const imgenv_minibatch_out& o = h->mb_out;
+    const size_t total = (size_t)h->mb_gen_n * (size_t)h->RL;
+    const MbStatsDev s = {x, o.valid, o.valid_n, o.stat_part, o.stat_mean, norm_out ? norm_out : o.norm, eps, (uint32_t)plan_mb_stats_tiles(total)};
+    const LaunchShape tiles = plan_mb_stats_launch(total), one = plan_mb_stats_final_launch();
+    k_mb_stats<false><<<dim3(tiles.grid), dim3(tiles.block), 0, st>>>(s);
+    k_mb_stats_final<false><<<dim3(one.grid), dim3(one.block), 0, st>>>(s);
+    k_mb_stats<true><<<dim3(tiles.grid), dim3(tiles.block), 0, st>>>(s);
+    k_mb_stats_final<true><<<dim3(one.grid), dim3(one.block), 0, st>>>(s);
+    HIPCHK(hipGetLastError());
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_rollout_shuffle(imgenv_t* h, uint32_t seed_lo, uint32_t seed_hi, void* stream) {
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    RTRY(minibatch_fresh(h, "imgenv_rollout_shuffle"));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const imgenv_minibatch_out& o = h->mb_out;
+    const MbShuffleDev s = {o.valid, o.valid_n, o.order, h->mb_gather.TR, mb_keys(seed_lo, seed_hi)};
+    const LaunchShape g = plan_mb_shuffle_launch(s.TR);
+    k_mb_shuffle<<<dim3(g.grid), dim3(g.block), 0, (hipStream_t)stream>>>(s);
+    HIPCHK(hipGetLastError());
+    h->mb_shuffled = true;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_rollout_minibatch(imgenv_t* h, const imgenv_minibatch_args* a, void* stream) {
+    if (!a) FAIL(IMGENV_EINVAL, "null argument");
+    if (a->struct_size != (int32_t)sizeof(imgenv_minibatch_args))
+        FAIL(IMGENV_EINVAL, "imgenv_minibatch_args.struct_size %d (this library's is %d)", a->struct_size, (int)sizeof(imgenv_minibatch_args));
+    if (a->j < 0) FAIL(IMGENV_EINVAL, "imgenv_minibatch_args.j %d", a->j);
+    if (a->n_scalars < 0 || a->n_scalars > IMGENV_MB_MAX_SCALARS) FAIL(IMGENV_EINVAL, "imgenv_minibatch_args.n_scalars %d: 0 .. %d", a->n_scalars, IMGENV_MB_MAX_SCALARS);
+    if (a->normalise < -1 || a->normalise >= a->n_scalars) FAIL(IMGENV_EINVAL, "imgenv_minibatch_args.normalise %d: -1 or an index below n_scalars %d", a->normalise, a->n_scalars);
+    for (int s = 0; s < a->n_scalars; s++)
+        if (!a->scalars[s]) FAIL(IMGENV_EINVAL, "imgenv_minibatch_args.scalars[%d] is null", s);
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->mb_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch_enable was not called");
+    if (a->buffer < 0 || a->buffer >= h->mb_cfg.buffers) FAIL(IMGENV_EINVAL, "imgenv_minibatch_args.buffer %d: 0 .. %d", a->buffer, h->mb_cfg.buffers - 1);
+    RTRY(minibatch_fresh(h, "imgenv_rollout_minibatch"));
+    if (!h->mb_shuffled) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch before imgenv_rollout_shuffle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const imgenv_minibatch_buffer& m = h->mb_out.buf[a->buffer];
+    MbGatherDev g = h->mb_gather;
+    for (int k = 0; k < g.n_fields; k++) g.f[k].dst = *(unsigned char* const*)((const unsigned char*)&m + (size_t)(uintptr_t)g.f[k].dst);
+    g.first = (size_t)a->j * (size_t)g.B;
+    g.mb_actions = m.mb_actions;
+    g.mb_rewards = m.mb_rewards;
+    g.mb_dones = m.mb_dones;
+    g.mb_dones_info = m.mb_dones_info;
+    g.mb_index = m.mb_index;
+    g.mb_weight = m.mb_weight;
+    g.mb_scalars = m.mb_scalars;
+    for (int s = 0; s < a->n_scalars; s++) g.scalars[s] = a->scalars[s];
+    g.n_scalars = a->n_scalars;
+    g.normalise = a->normalise;
+    g.norm = a->norm ? a->norm : h->mb_out.norm;
+    const LaunchShape s = plan_mb_gather_launch(g.B, g.chunks_per_row);
+    k_rollout_gather<<<dim3(s.grid), dim3(s.block), 0, (hipStream_t)stream>>>(g);
     HIPCHK(hipGetLastError());
     return IMGENV_OK;
 }

@@ -41,6 +41,15 @@
 #define GAE_BLOCK 64        // k_rollout_gae: one lane per local robot, one wavefront per block (4096 robots reach 64 CUs)
 #define GAE_MAX_BLOCKS 1024
 #define GAE_BATCH 4         // time steps whose loads a lane issues before it walks their dependent chain
+#define MB_INDEX_BLOCK 256   // k_mb_count / k_mb_scatter (minibatch.h): one workgroup per tile, a lane per MB_LANE_FLAGS flags
+#define MB_LANE_FLAGS 16     // one 16-byte load of is_clean per lane
+#define MB_TILE (MB_INDEX_BLOCK * MB_LANE_FLAGS)  // 4096 flags
+#define MB_SCAN_BLOCK 256    // k_mb_scan: ONE workgroup, MB_SCAN_BLOCK tile counts per round, a carry from round to round
+#define MB_STATS_BLOCK 256   // k_mb_stats: one workgroup per MB_STATS_TILE positions of the valid list, MB_STATS_PER_LANE per lane
+#define MB_STATS_PER_LANE 16
+#define MB_STATS_TILE (MB_STATS_BLOCK * MB_STATS_PER_LANE)
+#define MB_SHUFFLE_BLOCK 256 // k_mb_shuffle: one lane per position of `order`
+#define MB_ROUNDS 6          // Feistel rounds of the shuffle's permutation
 #define ACT_BLOCK 256       // k_actions: one lane per local robot
 #define OBS_POST_BLOCK 256  // k_obs_post: one lane per element of a robot's ped_vector row
 #define OBS_POST_MAX_BLOCKS 2048
@@ -471,6 +480,24 @@ inline LaunchShape plan_rollout_begin_launch(const PlanHandle& h, uint32_t chunk
 }
 // the advantage pass: one lane per local robot, striding from GAE_BLOCK x GAE_MAX_BLOCKS = 65536 robots on
 inline LaunchShape plan_rollout_gae_launch(const PlanHandle& h) { return plan_tail((size_t)h.RL, GAE_BLOCK, GAE_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------------------------------- behind the window: the minibatch kernels
+// minibatch.h.  The index: one workgroup per tile of MB_TILE flags for the count and the scatter (no cap: 2^31 flags are 2^19
+// workgroups), ONE workgroup for the scan in between.  The statistics: one workgroup per MB_STATS_TILE positions of the valid list
+// (sized for all `flags`: nobody on the host knows how many are valid), ONE for each reduction.  The shuffle: a lane per position
+// of `order`, all T x R of them.  The gather: k_rollout's walk over batch x chunks per row, capped; the kernel strides.
+inline size_t plan_mb_tiles(size_t flags) { return (flags + MB_TILE - 1) / MB_TILE; }
+inline LaunchShape plan_mb_index_launch(size_t flags) { return {(unsigned)std::max<size_t>(1, plan_mb_tiles(flags)), MB_INDEX_BLOCK, 0}; }
+inline LaunchShape plan_mb_scan_launch() { return {1, MB_SCAN_BLOCK, 0}; }
+inline size_t plan_mb_stats_tiles(size_t flags) { return (flags + MB_STATS_TILE - 1) / MB_STATS_TILE; }
+inline LaunchShape plan_mb_stats_launch(size_t flags) { return {(unsigned)std::max<size_t>(1, plan_mb_stats_tiles(flags)), MB_STATS_BLOCK, 0}; }
+inline LaunchShape plan_mb_stats_final_launch() { return {1, MB_STATS_BLOCK, 0}; }
+inline LaunchShape plan_mb_shuffle_launch(size_t positions) {
+    return {(unsigned)std::max<size_t>(1, (positions + MB_SHUFFLE_BLOCK - 1) / MB_SHUFFLE_BLOCK), MB_SHUFFLE_BLOCK, 0};
+}
+inline LaunchShape plan_mb_gather_launch(size_t batch, uint32_t chunks_per_row) {
+    return plan_tail(batch * chunks_per_row, ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS);
+}
 
 // ---------------------------------------------------------------------------------------- in front of the chain: k_actions
 // imgenv_actions_decode (actions.h): one lane per local robot, every wavefront whole (the ballot that counts bad rows runs on all

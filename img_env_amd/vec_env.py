@@ -39,14 +39,18 @@ class VecImageEnv:
     where ``all_down`` is set; other rows hold older captures) and ``final_count``.
     ``rollout=T``: the trainer's ``[T, n, ...]`` storage and the advantage pass inside the library: ``rollout()``,
     ``rollout_begin()``, ``rollout_advantages(values, final_values, gamma, lam)``.
+    ``minibatch=B`` (with ``rollout=T``): the PPO epoch's minibatches gathered by the library, without a host read:
+    ``rollout_minibatches(scalars, seed, normalise)``.
     """
 
     def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False,
                  map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3, wrappers=False,
                  ped_tracks=None, tracks_policy="keep", tracks_repeat=1, info_track_sets=False, scenarios=None, scenario_policy="queue",
-                 episode_log=0, final_obs=False, rollout=0, rollout_final=None, rollout_fields=None):
+                 episode_log=0, final_obs=False, rollout=0, rollout_final=None, rollout_fields=None, minibatch=0, minibatch_buffers=1):
         import torch
         from .world import World
+        if int(minibatch or 0) > 0 and int(rollout or 0) <= 0:
+            raise ValueError("minibatch=B needs rollout=T")
         self.cfg = cfg
         self.env_num = int(env_num if env_num is not None else cfg.get("env_num", 1))
         # ped_tracks: the recorded crowds of ``ped_sim.type: dataset`` as a bank inside the handle (imgenv_tracks_add) -- a list of
@@ -219,6 +223,12 @@ class VecImageEnv:
                 fields = rollout_fields
             final = int(rollout_final) if rollout_final is not None else (self.rollout_horizon + 1) * len(self)
             self.world.enable_rollout(self.rollout_horizon, final, fields)
+        # minibatch=B: the minibatches of a PPO epoch out of that storage (imgenv_rollout_minibatch_enable): the transitions that
+        # count (is_clean), their statistics, a fresh order and the gather of B of them into minibatch_buffers sets of contiguous
+        # tensors -- rollout_minibatches().  Nothing is launched by steps or resets; nothing synchronises.  Opt-in: 0 allocates nothing.
+        self.minibatch_batch = int(minibatch or 0)
+        if self.minibatch_batch > 0:
+            self.world.enable_minibatch(self.minibatch_batch, int(minibatch_buffers))
 
     def rollout(self):
         """``{"n": transitions stored, "resets": reset chains stored, **World.rollout}``: the device tensors as they are -- no
@@ -240,6 +250,39 @@ class VecImageEnv:
         if self.rollout_horizon <= 0:
             raise RuntimeError("VecImageEnv was made without rollout=T")
         return self.world.rollout_gae(values, final_values, gamma, lam)
+
+    def rollout_minibatches(self, scalars, seed, normalise=None, eps=1e-8):
+        """One epoch over the stored transitions that count (``is_clean != 0``), in a fresh order drawn from ``seed``: indexes once,
+        computes the statistics of ``scalars[normalise]`` over exactly those transitions where ``normalise`` names a scalar, shuffles,
+        then yields ``ceil(n * R / B)`` dicts of views -- the ``mb_*`` tensors of ``World.minibatch`` (``mb_<field>``, ``mb_actions``,
+        ``mb_rewards``, ``mb_dones``, ``mb_dones_info``, ``mb_index``, ``mb_weight``) and every scalar under the caller's own name
+        (float32 ``[B]``; the normalised one as ``(x - mean) / sqrt(var + eps)``).  ``scalars``: a dict of up to 6 float32 tensors
+        ``[T, n]`` or ``[T + 1, n]``.  Slots behind the valid list have ``mb_weight`` 0 and zeros everywhere: a loss is
+        ``(per_sample * w).sum() / w.sum().clamp(min=1)``; the trailing minibatches may be all such slots, since nobody on the host
+        knows the count.  The buffers alternate: a dict is valid until ``minibatch_buffers`` further ones have been drawn.
+        Nothing synchronises; everything is ordered on the current stream.  No step or reset while the generator runs."""
+        if self.minibatch_batch <= 0:
+            raise RuntimeError("VecImageEnv was made without minibatch=B")
+        names = list(scalars)
+        if normalise is not None and normalise not in scalars:
+            raise ValueError("normalise: one of the scalars' names")
+        w = self.world
+        n, _ = w.rollout_cursor()
+        w.rollout_index()
+        if normalise is not None:
+            w.rollout_stats(scalars[normalise], eps)
+        w.rollout_shuffle(seed)
+        B, tensors = self.minibatch_batch, [scalars[k] for k in names]
+        return self._minibatches(names, tensors, None if normalise is None else names.index(normalise), -(-n * len(self) // B))
+
+    def _minibatches(self, names, tensors, normalise, count):
+        w = self.world
+        for j in range(count):
+            mb = w.rollout_minibatch(j, j % w.minibatch_buffers, tensors, normalise)
+            rows = mb.pop("mb_scalars")
+            for s, name in enumerate(names):
+                mb[name] = rows[s]
+            yield mb
 
     def episode_tensors(self):
         """the per-robot device tensors of the statistics (``World.episodes``: ``ends`` [6, n], ``episodes``, ``last_episode``,

@@ -120,6 +120,7 @@ class World:
         self.obs_post = None  # enable_obs_post()
         self.final_obs = None  # enable_final_obs()
         self.rollout = None  # enable_rollout()
+        self.minibatch = None  # enable_minibatch()
         if self.n_maps > 1:
             rest = self.grids[1:]
             rc = self.lib.imgenv_maps_add(self.h, len(rest), rest.ctypes.data, rest.shape[1], rest.shape[2])
@@ -473,6 +474,7 @@ class World:
                           final_row=(np.int32, (F,)), final_n=(np.int32, (2,)))  # (final_n: uint32 in the library)
             self.rollout = self._views(ro, arrays, "imgenv_rollout_out")
             self.rollout_horizon, self.rollout_final_capacity = T, F
+            self._rollout_rows = rows
         return self.rollout
 
     def rollout_cursor(self):
@@ -512,6 +514,104 @@ class World:
         self._check(self.lib.imgenv_rollout_gae(self.h, C.c_void_p(values.data_ptr()), fv, float(gamma), float(lam),
                                                 C.c_void_p(adv.data_ptr()), C.c_void_p(ret.data_ptr()), self._stream()), "imgenv_rollout_gae")
         return adv, ret
+
+    def enable_minibatch(self, batch, buffers=1, fields=None):
+        """Minibatches out of the rollout storage (``imgenv_rollout_minibatch_enable``; needs ``enable_rollout`` first):
+        ``self.minibatch`` -- zero-copy tensors over the library's memory: ``mb_<field>`` ``[buffers, B, ...]`` with the row shapes
+        and dtypes of ``rollout["obs_<field>"]``, ``mb_actions`` float32 ``[buffers, B, 3]``, ``mb_rewards`` / ``mb_weight`` float32,
+        ``mb_dones`` uint8, ``mb_dones_info`` / ``mb_index`` int32 ``[buffers, B]``, ``mb_scalars`` float32 ``[buffers, 6, B]``
+        (``t[b]`` is contiguous; the buffers of an array lie 256-byte aligned side by side), and ``valid`` / ``order`` int32
+        ``[T * R]``, ``valid_n`` int32 ``[1]``, ``norm`` float32 ``[2]``.  ``fields``: names of ``_cabi.ROLLOUT_BITS``, a subset
+        of the rollout's; None = all of them.  Nothing is launched; read-only; valid until ``close()``.  ValueError for a refused
+        cfg or a second call with another one, RuntimeError before ``enable_rollout``."""
+        import torch
+        c = _cabi.make_minibatch_cfg(batch, buffers, fields)
+        mo = _cabi.MinibatchOut()
+        self._call(self.lib.imgenv_rollout_minibatch_enable(self.h, C.byref(c), C.byref(mo)), "imgenv_rollout_minibatch_enable")
+        if self.minibatch is None:
+            B, NB, TR = mo.batch, mo.buffers, mo.horizon * mo.n_local
+            views = self._views(mo, {"valid": (np.int32, (TR,)), "order": (np.int32, (TR,)), "valid_n": (np.int32, (1,)),  # (valid_n: uint32 in the library)
+                                     "norm": (np.float32, (2,))}, "imgenv_minibatch_out")
+            rows = {"mb_" + name: (self._rollout_rows[name][0], tuple(self._rollout_rows[name][1][1:]))
+                    for name in _cabi.ROLLOUT_FIELDS if "obs_" + name in (self.rollout or {}) and getattr(mo.buf[0], "mb_" + name)}
+            rows.update(mb_actions=(np.float32, (3,)), mb_rewards=(np.float32, ()), mb_dones=(np.uint8, ()), mb_dones_info=(np.int32, ()),
+                        mb_index=(np.int32, ()), mb_weight=(np.float32, ()))
+            arrays = {name: (dt, (B,) + shape) for name, (dt, shape) in rows.items()}
+            arrays["mb_scalars"] = (np.float32, (_cabi.MB_MAX_SCALARS, B))
+            for name, (dt, shape) in arrays.items():
+                # one view over the array's buffers: buffer b starts (size rounded up to 256 bytes) behind buffer b - 1
+                item = np.dtype(dt).itemsize
+                nbytes = int(np.prod(shape)) * item
+                pitch = (nbytes + 255) // 256 * 256
+                ptrs = [getattr(mo.buf[b], name) for b in range(NB)]
+                if any(ptrs[b] != ptrs[0] + b * pitch for b in range(NB)):
+                    raise RuntimeError("imgenv_minibatch_out.%s: the buffers do not lie side by side" % name)
+                span = self._views(mo.buf[0], {name: (dt, ((NB - 1) * pitch // item + nbytes // item,))}, "imgenv_minibatch_buffer")[name]
+                strides, acc = [], 1
+                for d in reversed(shape):
+                    strides.insert(0, acc)
+                    acc *= d
+                views[name] = torch.as_strided(span, (NB,) + tuple(shape), (pitch // item,) + tuple(strides))
+            self.minibatch = views
+            self.minibatch_batch, self.minibatch_buffers = B, NB
+        return self.minibatch
+
+    def _need_minibatch(self):
+        if self.minibatch is None:
+            raise RuntimeError("enable_minibatch() was not called")
+
+    def rollout_index(self):
+        """``imgenv_rollout_index``: ``minibatch["valid"]`` = the ascending list of the stored transitions ``k = t * R + row`` with
+        ``is_clean != 0``, ``valid_n`` their count; three launches on the current stream, nothing synchronises.  A later step, reset
+        or ``rollout_begin()`` makes the index stale: ``rollout_stats`` / ``_shuffle`` / ``_minibatch`` then raise RuntimeError."""
+        self._need_minibatch()
+        self._check(self.lib.imgenv_rollout_index(self.h, self._stream()), "imgenv_rollout_index")
+
+    def rollout_valid_count(self):
+        """``valid_n`` as a Python int.  SYNCHRONISES: it waits for the stream and reads one word from the device."""
+        self._need_minibatch()
+        return int(self.minibatch["valid_n"].item())
+
+    def _mb_tensor(self, t, what, shapes):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous() and tuple(t.shape) in shapes):
+            raise ValueError("%s: float32 %s, contiguous on %s" % (what, " or ".join(str(list(s)) for s in shapes), self.device))
+        return C.c_void_p(t.data_ptr())
+
+    def rollout_stats(self, x, eps=1e-8, out=None):
+        """``imgenv_rollout_stats``: ``(mean, 1 / sqrt(var + eps))`` of ``x`` float32 ``[T, R]`` over the valid list, accumulated in
+        float64 in a fixed order (two calls give identical bits); ``var`` is the POPULATION variance (divisor V, not torch.std's
+        V - 1).  Into ``out`` float32 ``[2]`` or, None, ``minibatch["norm"]``; returns that tensor.  Four launches."""
+        self._need_minibatch()
+        T, R = self.rollout_horizon, self.n_local
+        xp = self._mb_tensor(x, "rollout_stats: x", [(T, R)])
+        op = self._mb_tensor(out, "rollout_stats: out", [(2,)]) if out is not None else None
+        self._call(self.lib.imgenv_rollout_stats(self.h, xp, float(eps), op, self._stream()), "imgenv_rollout_stats")
+        return out if out is not None else self.minibatch["norm"]
+
+    def rollout_shuffle(self, seed):
+        """``imgenv_rollout_shuffle``: ``minibatch["order"]`` = the valid list in a fresh order drawn from the 64-bit ``seed`` (a
+        keyed bijection evaluated per position: include/imgenv.h), -1 behind ``valid_n``; one launch"""
+        self._need_minibatch()
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._check(self.lib.imgenv_rollout_shuffle(self.h, seed & 0xFFFFFFFF, seed >> 32, self._stream()), "imgenv_rollout_shuffle")
+
+    def rollout_minibatch(self, j, buffer=0, scalars=(), normalise=None, norm=None):
+        """``imgenv_rollout_minibatch``: minibatch ``j`` of the current order into buffer ``buffer``, one launch.  ``scalars``: up
+        to 6 float32 tensors ``[T, R]`` or ``[T + 1, R]``, contiguous on the handle's device, gathered into
+        ``minibatch["mb_scalars"][buffer, s]``; ``normalise``: an index into them whose values become ``(x - norm[0]) * norm[1]``,
+        ``norm`` float32 ``[2]`` or None for ``minibatch["norm"]``.  Slots behind the valid list are zeros with ``mb_index`` -1
+        and ``mb_weight`` 0.  Returns the dict of buffer ``buffer``'s views."""
+        self._need_minibatch()
+        T, R = self.rollout_horizon, self.n_local
+        scalars = list(scalars)
+        if len(scalars) > _cabi.MB_MAX_SCALARS:
+            raise ValueError("rollout_minibatch: at most %d scalars" % _cabi.MB_MAX_SCALARS)
+        ptrs = [self._mb_tensor(t, "rollout_minibatch: scalars[%d]" % s, [(T, R), (T + 1, R)]).value for s, t in enumerate(scalars)]
+        np_ = self._mb_tensor(norm, "rollout_minibatch: norm", [(2,)]).value if norm is not None else None
+        a = _cabi.make_minibatch_args(j, buffer, ptrs, -1 if normalise is None else normalise, np_)
+        self._call(self.lib.imgenv_rollout_minibatch(self.h, C.byref(a), self._stream()), "imgenv_rollout_minibatch")
+        return {name: t[buffer] for name, t in self.minibatch.items() if name.startswith("mb_")}
 
     def reset(self, layout):
         """Reset everything. A handle of several worlds (``n_worlds`` > 1) takes either one batch of all robots and
@@ -701,7 +801,7 @@ class World:
 
     def close(self):
         if getattr(self, "h", None):
-            self.episodes = self.episode_log = self.action_outputs = self.obs_post = self.final_obs = self.rollout = None  # (views of memory the handle owns)
+            self.episodes = self.episode_log = self.action_outputs = self.obs_post = self.final_obs = self.rollout = self.minibatch = None  # (views of memory the handle owns)
             self.lib.imgenv_destroy(self.h)
             self.h = None
 

@@ -907,6 +907,117 @@ int imgenv_rollout_begin(imgenv_t* h, void* stream);
  * IMGENV_EINVAL for a null values / adv / ret, IMGENV_ESTATE before imgenv_rollout_begin(). */
 int imgenv_rollout_gae(imgenv_t* h, const float* values, const float* final_values, float gamma, float lam, float* adv, float* ret, void* stream);
 
+/* ---- rollout minibatches: which stored transitions count, a random order over them, their statistics, the gather ----
+ * Between "T steps collected" and "optimiser step" a trainer finds the transitions that count (is_clean != 0: a frozen robot of
+ * MultiRobotCleanWrapper has advantage 0), normalises its advantages over exactly those, draws a fresh order over them every epoch
+ * and gathers every minibatch into contiguous tensors.  Here all of that is kernels over the ring (csrc/minibatch.h); nothing
+ * reads the device from the host.  k = t * R + row numbers the stored transitions, 0 <= k < n * R (n the cursor).
+ *
+ * All arrays are the library's, one all-or-nothing allocation, each on a 256-byte boundary, no part of the output arena:
+ *   valid        i32 [T R]      imgenv_rollout_index: the k with is_clean[k] != 0, ascending
+ *   valid_n      u32            their count V
+ *   order        i32 [T R]      imgenv_rollout_shuffle: order[p] = valid[pi(p)] for p < V, -1 from V on
+ *   norm         f32 [2]        imgenv_rollout_stats' default target: (mean, 1 / sqrt(var + eps))
+ *   tile_count, tile_base i32 [ceil(T R / 4096)], stat_part f64 [the same], stat_mean f64   scratch of the index and the statistics
+ *   per buffer (imgenv_minibatch_buffer), B = batch:
+ *   mb_<field>   [B][row]       the selected fields' rows, shapes and types as obs_<field>
+ *   mb_actions f32 [B][3], mb_rewards f32 [B], mb_dones u8 [B], mb_dones_info i32 [B]   the ring's scalars of transition k
+ *   mb_index     i32 [B]        k, -1 for a slot behind the valid list
+ *   mb_weight    f32 [B]        1, or 0 for such a slot: a loss is (per_sample * w).sum() / w.sum().clamp(min = 1)
+ *   mb_scalars   f32 [IMGENV_MB_MAX_SCALARS][B]   the caller's arrays at k
+ * The index has a generation: the pair (n, chains queued on the handle so far) at the time of imgenv_rollout_index.  A later step
+ * chain, reset chain or imgenv_rollout_begin makes it stale: imgenv_rollout_stats, _shuffle and _minibatch then fail with
+ * IMGENV_ESTATE ("rollout changed since imgenv_rollout_index") before they queue anything.  Stream order as for imgenv_out: queue
+ * these calls on the stream of the chains, or behind an event of it. */
+#define IMGENV_MB_MAX_SCALARS 6
+#define IMGENV_MB_MAX_BUFFERS 4
+typedef struct imgenv_minibatch_cfg {
+    int32_t struct_size;          /* sizeof(imgenv_minibatch_cfg) */
+    int32_t batch;                /* B >= 1 */
+    int32_t buffers;              /* 1 .. IMGENV_MB_MAX_BUFFERS */
+    int32_t fields;               /* IMGENV_ROLLOUT_* bits, a subset of the rollout's; 0: all of them */
+} imgenv_minibatch_cfg;
+typedef struct imgenv_minibatch_buffer {
+    /* [B][row]; NULL where not selected */
+    uint16_t* mb_sensor_maps;
+    float* mb_vector_states;
+    double* mb_lasers;
+    float* mb_ped_vector_states;
+    float* mb_ped_maps;
+    float* mb_ped_vector_norm;
+    uint16_t* mb_stack_sensor_maps;
+    float* mb_stack_vector_states;
+    double* mb_stack_lasers;
+    float* mb_actions;
+    float* mb_rewards;
+    uint8_t* mb_dones;
+    int32_t* mb_dones_info;
+    int32_t* mb_index;
+    float* mb_weight;
+    float* mb_scalars;
+} imgenv_minibatch_buffer;
+typedef struct imgenv_minibatch_out {
+    int32_t struct_size;          /* on entry 0 or sizeof(imgenv_minibatch_out) */
+    int32_t n_local;              /* R */
+    int32_t horizon;              /* T */
+    int32_t batch;                /* B */
+    int32_t buffers;
+    int32_t fields;               /* the bits in effect */
+    int32_t* valid;
+    int32_t* order;
+    uint32_t* valid_n;
+    float* norm;
+    int32_t* tile_count;
+    int32_t* tile_base;
+    double* stat_part;
+    double* stat_mean;
+    imgenv_minibatch_buffer buf[IMGENV_MB_MAX_BUFFERS];  /* buf[b] all NULL for b >= buffers */
+} imgenv_minibatch_out;
+/* Legal once imgenv_rollout_enable() has been called (IMGENV_ESTATE before).  IMGENV_EINVAL for a wrong struct_size, batch < 1,
+ * buffers outside 1 .. 4, unknown bits, a bit the rollout does not store, or a second call whose cfg differs from the first's
+ * (same cfg: `out` is filled again, nothing changes).  IMGENV_ENOMEM when the arrays cannot be allocated; the handle is then
+ * unchanged.  `out` may be NULL.  Nothing is launched, and no chain of the handle changes. */
+int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibatch_cfg* cfg, imgenv_minibatch_out* out);
+/* IMGENV_ESTATE before imgenv_rollout_minibatch_enable() */
+int imgenv_rollout_minibatch_outputs(imgenv_t* h, imgenv_minibatch_out* out);
+/* valid = the ascending list of every k < n R with is_clean[k] != 0, valid_n = its length: a stable compaction in three launches
+ * (count per tile of 4096 flags, one workgroup's scan of the tile counts, scatter per tile); no workgroup waits for another.
+ * Records the generation.  IMGENV_ESTATE before imgenv_rollout_minibatch_enable(), before imgenv_rollout_begin() or with n == 0. */
+int imgenv_rollout_index(imgenv_t* h, void* stream);
+/* Mean and inverse standard deviation of x -- a DEVICE f32 [T][R] array of the caller, typically adv -- over the valid list, in
+ * float64: mean = sum x / V; then, in a second pass, var = sum (x - mean)^2 / V: the POPULATION variance (divisor V), not the
+ * unbiased one torch.std defaults to.  norm_out (DEVICE f32 [2]; NULL: the library's norm) = ((float)mean, (float)(1 / sqrt(var +
+ * eps))); V == 0: (0, 1); var + eps == 0: (mean, 1).  Four launches, partial sums in a fixed order, no atomics: two runs give
+ * identical bits.  IMGENV_EINVAL for a null x or eps < 0, IMGENV_ESTATE for a stale or missing index. */
+int imgenv_rollout_stats(imgenv_t* h, const float* x, double eps, float* norm_out, void* stream);
+/* order[p] = valid[pi(p)] for p < valid_n (read on the device), -1 for valid_n <= p < T R; one launch.  pi is a cycle-walking,
+ * unbalanced, alternating Feistel network; all arithmetic uint32, wrapping:
+ *   fmix(x): x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16
+ *   key[r] = fmix(seed_lo ^ (r * 0x9E3779B9)) ^ seed_hi, r = 0 .. 5
+ *   V = valid_n; b = max(2, bit_length(V - 1)); hb = b / 2; ha = b - hb; mA = 2^ha - 1; mB = 2^hb - 1
+ *   L = x >> hb; R = x & mB; even r: L ^= fmix(R + key[r]) & mA; odd r: R ^= fmix(L + key[r]) & mB; x = (L << hb) | R;
+ *   the six rounds repeat while x >= V.  V <= 1: the identity.
+ * IMGENV_ESTATE for a stale or missing index. */
+int imgenv_rollout_shuffle(imgenv_t* h, uint32_t seed_lo, uint32_t seed_hi, void* stream);
+typedef struct imgenv_minibatch_args {
+    int32_t struct_size;          /* sizeof(imgenv_minibatch_args) */
+    int32_t j;                    /* minibatch number >= 0: the slots take order[j B .. j B + B - 1] */
+    int32_t buffer;               /* 0 .. buffers - 1 */
+    int32_t n_scalars;            /* 0 .. IMGENV_MB_MAX_SCALARS */
+    int32_t normalise;            /* an index into scalars, or -1 */
+    int32_t reserved;             /* 0 */
+    const float* scalars[IMGENV_MB_MAX_SCALARS];  /* DEVICE f32 arrays indexed by k, row stride R: [T][R] or [T+1][R] */
+    const float* norm;            /* DEVICE f32 [2] for `normalise`; NULL: the library's norm */
+} imgenv_minibatch_args;
+/* Minibatch j into buffer `buffer`, one launch (k_rollout_gather).  Slot i takes k = order[j B + i], -1 from T R on.
+ *   k >= 0: mb_<field>[i] = obs_<field>[k], the ring's actions / rewards / dones / dones_info of k, mb_index = k, mb_weight = 1,
+ *           mb_scalars[s][i] = scalars[s][k], for s == normalise (x - norm[0]) * norm[1] in float32 (two roundings);
+ *   k <  0: every byte of the slot's rows 0, mb_index = -1, mb_weight and every scalar 0.
+ * Rows of mb_scalars from n_scalars on are left as they are.  IMGENV_EINVAL for a wrong struct_size, j < 0, a buffer, n_scalars or
+ * normalise out of range or a null scalars[s]; IMGENV_ESTATE for a stale or missing index or before imgenv_rollout_shuffle() on
+ * this index. */
+int imgenv_rollout_minibatch(imgenv_t* h, const imgenv_minibatch_args* args, void* stream);
+
 /* ---- map bank: several static maps in one handle, one of them per world and episode ----
  * The reference trains one policy over a set of maps: its trainer is started from several YAML files side by side
  * (create_launch.py:57-65, one node per (env_name, env_num) pair), each env process loads its own global_map.map_file

@@ -21,6 +21,11 @@ storage, the library's (VecImageEnv(rollout=--horizon), imgenv_rollout_enable: o
 --horizon steps) and the same arrays kept by torch on top of the first (buf[t].copy_(x) per field and scalar, the final rows taken
 whole from final_obs=True); then the advantage pass (imgenv_rollout_gae) against a torch loop over t for a rollout of 128 steps.
 
+--minibatch-compare times one PPO epoch of minibatches of --batch transitions over a full window of --horizon device_reset steps,
+two ways, one process per measurement, alternating over several rounds: the library's (VecImageEnv(minibatch=B):
+imgenv_rollout_index + _stats + _shuffle and one gather launch per minibatch, no host read) and the same tensors from torch ops on
+the library's ring (nonzero on is_clean, masked mean / std, randperm, one index_select per field and scalar).
+
 --wrappers table|clip feeds the policy's raw output (indices into a 28-row table, or float rows to be clipped) to
 VecImageEnv(wrappers=True): decode, speeds, normalised pedestrian vectors and close_to_human kept by the library;
 --torch-wrappers keeps the same with torch ops on top of a plain VecImageEnv; --wrappers-compare alternates pre-decoded actions
@@ -750,6 +755,97 @@ def compare_rollout(args, rounds=3):
                 horizon=args.horizon, rounds=rounds, runs=runs, summary=summary)
 
 
+def measure_minibatch(variant, envs=1024, robots=4, peds=3, obstacles=2, time_max=100, horizon=32, batch=4096, epochs=5):
+    """us per PPO epoch's worth of minibatches over a full window of ``horizon`` device_reset steps, all five single-frame fields, four
+    caller scalars (adv, ret, values, old log-probabilities), the advantages normalised over the transitions that count:
+    "library": ``VecImageEnv.rollout_minibatches`` (index + statistics + shuffle + one gather per minibatch, no host read);
+    "torch": the same tensors from torch ops on the library's ring -- ``nonzero`` on ``is_clean`` (a host synchronisation), masked
+    mean / std, ``randperm``, one ``index_select`` per field and scalar and minibatch"""
+    import torch
+    from img_env_amd import worldgen
+    from img_env_amd.vec_env import VecImageEnv
+    grid = worldgen.make_grid(200, 2)
+    cfg = worldgen.make_yaml_cfg(robots, peds, grid, time_max=time_max, n_obstacles=obstacles, seed=5)
+    T, n, B = horizon, envs * robots, batch
+    env = VecImageEnv(cfg, env_num=envs, seed=5, device_reset=True, rollout=T, rollout_final=n, minibatch=B if variant == "library" else 0,
+                      minibatch_buffers=2)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    acts = torch.zeros(16, n, 3, device="cuda")
+    acts[:, :, 0] = torch.rand(16, n, generator=g, device="cuda") * 0.6
+    acts[:, :, 1] = torch.rand(16, n, generator=g, device="cuda") * 1.8 - 0.9
+    env.reset()
+    windows = max(1, -(-(time_max + 20) // T))  # past the first wave of time limits, ending on a full window
+    for s in range(windows * T):
+        if s and s % T == 0:
+            env.rollout_begin()
+        env.step(acts[s % 16])
+    values = torch.randn(T + 1, n, generator=g, device="cuda")
+    adv, ret = env.rollout_advantages(values, None, 0.99, 0.95)
+    logp = torch.randn(T, n, generator=g, device="cuda")
+    r = env.rollout()
+    fields = [k[4:] for k in r if k.startswith("obs_")]
+
+    def library(seed):
+        count = 0
+        for mb in env.rollout_minibatches({"adv": adv, "ret": ret, "values": values, "logp": logp}, seed, normalise="adv"):
+            count += 1
+        return count
+
+    def torch_epoch(seed):
+        clean = r["is_clean"][:T].reshape(-1)
+        valid = torch.nonzero(clean).flatten()  # (the host waits here: the size of the result)
+        a = adv.reshape(-1)[valid]
+        mean, inv = a.mean(), torch.rsqrt(a.var(unbiased=False) + 1e-8)
+        order = valid[torch.randperm(valid.numel(), device="cuda", generator=g)]
+        flat = {k: r["obs_" + k].flatten(0, 1) for k in fields}
+        ring = {k: r[k].flatten(0, 1) for k in ("actions", "rewards", "dones", "dones_info")}
+        mine = {"adv": adv.reshape(-1), "ret": ret.reshape(-1), "values": values.reshape(-1), "logp": logp.reshape(-1)}
+        count = 0
+        for j in range(-(-valid.numel() // B)):
+            idx = order[j * B:(j + 1) * B]
+            mb = {k: v.index_select(0, idx) for k, v in flat.items()}
+            mb.update({k: v.index_select(0, idx) for k, v in ring.items()})
+            mb.update({k: v.index_select(0, idx) for k, v in mine.items()})
+            mb["adv"] = (mb["adv"] - mean) * inv
+            count += 1
+        return count
+    fn = library if variant == "library" else torch_epoch
+    fn(0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for e in range(epochs):
+        count = fn(e + 1)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    valid_n = int((r["is_clean"][:T] != 0).sum().item())
+    row_bytes = sum(r["obs_" + k][0, 0].numel() * r["obs_" + k].element_size() for k in fields)
+    env.close()
+    return dict(us_per_epoch=1e6 * dt / epochs, minibatches=count, batch=B, horizon=T, rows=n, transitions=T * n, valid=valid_n,
+                row_bytes=row_bytes, fields=fields)
+
+
+def compare_minibatch(args, rounds=3):
+    """library / torch, alternating, `rounds` times; one process per measurement"""
+    import subprocess
+    base = [sys.executable, os.path.abspath(__file__), "--envs", str(args.envs), "--robots", str(args.robots), "--peds", str(args.peds),
+            "--obstacles", str(args.obstacles), "--time-max", str(args.time_max), "--horizon", str(args.horizon), "--batch", str(args.batch)]
+    variants, runs = ("library", "torch"), []
+    for rnd in range(rounds):
+        for variant in variants:
+            out = subprocess.run(base + ["--minibatch-variant", variant], capture_output=True, text=True, timeout=900)
+            if out.returncode != 0:
+                raise RuntimeError("%s: exit %d\n%s" % (variant, out.returncode, out.stderr[-2000:]))
+            runs.append(dict(round=rnd, variant=variant, **json.loads(out.stdout.strip().splitlines()[-1])))
+            print(json.dumps(runs[-1]), flush=True)
+    summary = {}
+    for variant in variants:
+        v = [x["us_per_epoch"] for x in runs if x["variant"] == variant]
+        summary[variant] = dict(us_per_epoch_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
+    summary["torch_minus_library_us"] = summary["torch"]["median"] - summary["library"]["median"]
+    return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, time_max=args.time_max, horizon=args.horizon,
+                batch=args.batch, rounds=rounds, runs=runs, summary=summary)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
@@ -791,6 +887,11 @@ def main():
                          "alternating over --rounds rounds, and the advantage pass against a torch loop; one process per measurement")
     ap.add_argument("--rollout-variant", default=None, choices=("none", "library", "torch", "gae"), help="one measurement of --rollout-compare")
     ap.add_argument("--horizon", type=int, default=32, help="--rollout-compare: transitions per window")
+    ap.add_argument("--minibatch-compare", action="store_true",
+                    help="one PPO epoch of minibatches over a full window: the library's (VecImageEnv(minibatch=B)) / the same tensors "
+                         "from torch ops, alternating over --rounds rounds; one process per measurement")
+    ap.add_argument("--minibatch-variant", default=None, choices=("library", "torch"), help="one measurement of --minibatch-compare")
+    ap.add_argument("--batch", type=int, default=4096, help="--minibatch-compare: transitions per minibatch")
     ap.add_argument("--tree", default=None, help="import img_env_amd from this checkout instead of the tool's own")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None, help="--stack-compare / --episodes-compare: also write the JSON here")
@@ -798,6 +899,17 @@ def main():
     if args.scenarios_variant:
         print(json.dumps(measure_scenarios(args.scenarios_variant, args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max,
                                            args.scenarios)))
+        return
+    if args.minibatch_variant:
+        print(json.dumps(measure_minibatch(args.minibatch_variant, args.envs, args.robots, args.peds, args.obstacles, args.time_max, args.horizon,
+                                           args.batch)))
+        return
+    if args.minibatch_compare:
+        res = compare_minibatch(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
         return
     if args.rollout_variant:
         print(json.dumps(measure_rollout(args.rollout_variant, args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max,

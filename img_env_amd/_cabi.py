@@ -282,6 +282,7 @@ FINAL_BITS = {"vector_states": 1, "sensor_maps": 2, "lasers": 4, "ped_vector_sta
               "is_arrives": 64, "step_ds": 128, "ped_min_dists": 256, "view_maps": 512, "lasers_raw": 1024, "stacks": 2048,
               "ped_vector_norm": 4096}
 FINAL_IMAGE_STATE, FINAL_ALL = 511, 8191
+FINAL_NORM_STATES = 8192  # IMGENV_FINAL_NORM_STATES: after imgenv_normalise_enable only, not part of FINAL_ALL
 #: the pointers of imgenv_final_obs_out, in the struct's order
 FINAL_ARRAYS = tuple(list(FINAL_BITS)[:11]) + ("stack_sensor_maps", "stack_vector_states", "stack_lasers", "ped_vector_norm", "final_count")
 FINAL_BLOCK, FINAL_MAX_BLOCKS = 256, 1024  # k_final_obs' launch shape (csrc/launch_plan.h)
@@ -295,27 +296,36 @@ class FinalObsOut(C.Structure):
     _fields_ = [("struct_size", _i32), ("n_local", _i32)] + [(name, C.c_void_p) for name in FINAL_ARRAYS]
 
 
+_FINAL_NAMES = dict(FINAL_BITS, norm_states=FINAL_NORM_STATES)
+
+
 def make_final_obs_cfg(fields):
-    """``imgenv_final_obs_cfg``: ``fields`` is an int of IMGENV_FINAL_* bits or an iterable of ``FINAL_BITS`` names"""
+    """``imgenv_final_obs_cfg``: ``fields`` is an int of IMGENV_FINAL_* bits or an iterable of ``FINAL_BITS`` names (and
+    ``"norm_states"``, IMGENV_FINAL_NORM_STATES)"""
     c = FinalObsCfg()
     c.struct_size = C.sizeof(FinalObsCfg)
     if isinstance(fields, (int, np.integer)):
         c.fields = int(fields)
     else:
         names = list(fields)
-        unknown = [n for n in names if n not in FINAL_BITS]
+        unknown = [n for n in names if n not in _FINAL_NAMES]
         if unknown:
             raise ValueError("final observation fields: unknown %s (known: %s)" % (unknown, ", ".join(FINAL_BITS)))
-        c.fields = sum({FINAL_BITS[n] for n in names})
+        c.fields = sum({_FINAL_NAMES[n] for n in names})
     return c
 
 
 #: imgenv_rollout_cfg.fields: name -> IMGENV_ROLLOUT_* bit, in bit order
 ROLLOUT_BITS = {"sensor_maps": 1, "vector_states": 2, "lasers": 4, "ped_vector_states": 8, "ped_maps": 16, "ped_vector_norm": 32, "stacks": 64}
 ROLLOUT_ALL = 127
+#: after imgenv_normalise_enable only, not part of ROLLOUT_ALL: the normalised state (and its stack) as fields; the normalised reward as ``rewards``
+ROLLOUT_NORM_STATES, ROLLOUT_NORM_REWARDS = 128, 256
+_ROLLOUT_NAMES = dict(ROLLOUT_BITS, norm_states=ROLLOUT_NORM_STATES, norm_rewards=ROLLOUT_NORM_REWARDS)
 #: the stored observation fields, in the order of imgenv_rollout_out's obs_* and final_* pointers
 ROLLOUT_FIELDS = ("sensor_maps", "vector_states", "lasers", "ped_vector_states", "ped_maps", "ped_vector_norm",
                   "stack_sensor_maps", "stack_vector_states", "stack_lasers")
+#: ROLLOUT_NORM_STATES' two fields: their ring / final / minibatch pointers are imgenv_normalise_out's (rollout_* / mb_norm_*)
+ROLLOUT_NORM_FIELDS = ("norm_vector_states", "norm_state_stack")
 #: the other pointers of imgenv_rollout_out, in the struct's order
 ROLLOUT_SCALARS = ("actions", "rewards", "dones", "is_clean", "dones_info", "final_idx", "final_slot", "final_row", "final_n")
 ROLLOUT_HEADER = ("struct_size", "n_local", "horizon", "final_capacity", "n", "resets")
@@ -340,10 +350,10 @@ def make_rollout_cfg(horizon, final_capacity, fields):
         c.fields = int(fields)
     else:
         names = list(fields)
-        unknown = [n for n in names if n not in ROLLOUT_BITS]
+        unknown = [n for n in names if n not in _ROLLOUT_NAMES]
         if unknown:
             raise ValueError("rollout fields: unknown %s (known: %s)" % (unknown, ", ".join(ROLLOUT_BITS)))
-        c.fields = sum({ROLLOUT_BITS[n] for n in names})
+        c.fields = sum({_ROLLOUT_NAMES[n] for n in names})
     return c
 
 
@@ -387,11 +397,63 @@ def make_minibatch_cfg(batch, buffers=1, fields=0):
         c.fields = int(fields)
     else:
         names = list(fields)
-        unknown = [n for n in names if n not in ROLLOUT_BITS]
+        unknown = [n for n in names if n not in _ROLLOUT_NAMES]
         if unknown:
             raise ValueError("minibatch fields: unknown %s (known: %s)" % (unknown, ", ".join(ROLLOUT_BITS)))
-        c.fields = sum({ROLLOUT_BITS[n] for n in names})
+        c.fields = sum({_ROLLOUT_NAMES[n] for n in names})
     return c
+
+
+#: running normalisation (imgenv_normalise_enable; csrc/normalise.h)
+NORM_OBS, NORM_REWARD = 1, 2
+NORM_BLOCK, NORM_PER_LANE, NORM_MAX_COLS, NORM_MAX_BLOCKS = 256, 8, 64, 1024  # the launch shapes (csrc/launch_plan.h)
+
+
+class NormaliseCfg(C.Structure):
+    _fields_ = [("struct_size", _i32), ("flags", _i32), ("gamma", C.c_double), ("clip_obs", C.c_double), ("clip_reward", C.c_double),
+                ("eps", C.c_double)]
+
+
+class NormaliseOut(C.Structure):
+    _fields_ = [("struct_size", _i32), ("n_local", _i32), ("state_dim", _i32), ("state_depth", _i32), ("norm_vector_states", C.c_void_p),
+                ("norm_state_stack", C.c_void_p), ("norm_rewards", C.c_void_p), ("stats", C.c_void_p), ("returns", C.c_void_p),
+                ("stats_word", _i32), ("returns_word", _i32), ("training", _i32), ("reserved", _i32),
+                ("rollout_obs_norm_vector_states", C.c_void_p), ("rollout_obs_norm_state_stack", C.c_void_p),
+                ("rollout_final_norm_vector_states", C.c_void_p), ("rollout_final_norm_state_stack", C.c_void_p),
+                ("mb_norm_vector_states", C.c_void_p * 4), ("mb_norm_state_stack", C.c_void_p * 4),  # (MB_MAX_BUFFERS)
+                ("final_norm_vector_states", C.c_void_p), ("final_norm_state_stack", C.c_void_p)]
+
+
+class NormaliseStats(C.Structure):
+    _fields_ = [("struct_size", _i32), ("state_dim", _i32), ("n_rows", _i32), ("reserved", _i32), ("obs_count", C.c_double),
+                ("ret_count", C.c_double), ("ret_mean", C.c_double), ("ret_var", C.c_double), ("obs_mean", C.c_void_p),
+                ("obs_var", C.c_void_p), ("returns", C.c_void_p)]
+
+
+def make_normalise_cfg(obs=True, reward=True, gamma=0.99, clip_obs=10.0, clip_reward=10.0, eps=1e-8):
+    """``imgenv_normalise_cfg`` (the defaults are Stable-Baselines3's VecNormalize's)"""
+    c = NormaliseCfg()
+    c.struct_size = C.sizeof(NormaliseCfg)
+    c.flags = (NORM_OBS if obs else 0) | (NORM_REWARD if reward else 0)
+    c.gamma, c.clip_obs, c.clip_reward, c.eps = float(gamma), float(clip_obs), float(clip_reward), float(eps)
+    return c
+
+
+def make_normalise_stats(state_dim, n_rows, stats=None):
+    """``imgenv_normalise_stats`` over fresh numpy arrays: ``(struct, arrays)``; ``stats``: a dict as ``World.normalise_stats()``
+    returns, copied in"""
+    arrays = {"obs_mean": np.zeros(state_dim, np.float64), "obs_var": np.ones(state_dim, np.float64), "returns": np.zeros(n_rows, np.float64)}
+    s = NormaliseStats()
+    s.struct_size = C.sizeof(NormaliseStats)
+    s.state_dim, s.n_rows = int(state_dim), int(n_rows)
+    s.obs_count = s.ret_count = 1e-4
+    s.ret_var = 1.0
+    if stats is not None:
+        for name, a in arrays.items():
+            a[...] = np.asarray(stats[name], np.float64).reshape(a.shape)
+        s.obs_count, s.ret_count, s.ret_mean, s.ret_var = (float(stats[k]) for k in ("obs_count", "ret_count", "ret_mean", "ret_var"))
+    s.obs_mean, s.obs_var, s.returns = (arrays[k].ctypes.data for k in ("obs_mean", "obs_var", "returns"))
+    return s, arrays
 
 
 def make_minibatch_args(j, buffer=0, scalars=(), normalise=-1, norm=None):
@@ -560,6 +622,8 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_rollout_enable", "imgenv_rollout_outputs", "imgenv_rollout_begin", "imgenv_rollout_gae",
            "imgenv_rollout_minibatch_enable", "imgenv_rollout_minibatch_outputs", "imgenv_rollout_index", "imgenv_rollout_stats",
            "imgenv_rollout_shuffle", "imgenv_rollout_minibatch",
+           "imgenv_normalise_enable", "imgenv_normalise_outputs", "imgenv_normalise_training", "imgenv_normalise_stats_get",
+           "imgenv_normalise_stats_set",
            "imgenv_maps_add", "imgenv_world_maps_set", "imgenv_maps_policy", "imgenv_map_for_placement", "imgenv_world_maps",
            "imgenv_tracks_add", "imgenv_world_tracks_set", "imgenv_tracks_policy", "imgenv_tracks_for_placement", "imgenv_world_tracks",
            "imgenv_scenarios_add", "imgenv_scenarios_policy", "imgenv_scenario_for_placement", "imgenv_reset_worlds_scenarios",
@@ -638,6 +702,11 @@ def bind(lib):
     lib.imgenv_rollout_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
     lib.imgenv_rollout_shuffle.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.imgenv_rollout_minibatch.argtypes = [C.c_void_p, C.POINTER(MinibatchArgs), C.c_void_p]
+    lib.imgenv_normalise_enable.argtypes = [C.c_void_p, C.POINTER(NormaliseCfg), C.POINTER(NormaliseOut)]
+    lib.imgenv_normalise_outputs.argtypes = [C.c_void_p, C.POINTER(NormaliseOut)]
+    lib.imgenv_normalise_training.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.imgenv_normalise_stats_get.argtypes = [C.c_void_p, C.POINTER(NormaliseStats)]
+    lib.imgenv_normalise_stats_set.argtypes = [C.c_void_p, C.POINTER(NormaliseStats)]
     lib.imgenv_maps_add.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
     lib.imgenv_world_maps_set.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
     lib.imgenv_maps_policy.argtypes = [C.c_void_p, C.c_int32]

@@ -34,6 +34,7 @@
 #include "map_bank.h"
 #include "spawn_slot.h"
 #include "bank_host.h"
+#include "normalise.h"
 
 static thread_local char g_err[512] = "";
 #define FAIL(code, ...)                              \
@@ -46,6 +47,13 @@ static thread_local char g_err[512] = "";
         hipError_t e_ = (expr);                                                                        \
         if (e_ != hipSuccess) FAIL(IMGENV_EDEVICE, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+
+// a minibatch buffer's pointers: the public struct and, behind it, those of the normalised fields (imgenv_normalise_out.mb_norm_*)
+struct MbBufferAll {
+    imgenv_minibatch_buffer pub;
+    float* mb_norm_vector_states;
+    float* mb_norm_state_stack;
+};
 
 struct imgenv {
     imgenv_cfg cfg;
@@ -258,7 +266,7 @@ struct imgenv {
     int roll_n = 0;              // the cursor: transitions stored since the last begin
     uint32_t roll_turn = 0;      // reset chains stored since the last begin
     RolloutDev roll;
-    size_t roll_row_bytes[ROLLOUT_MAX_FIELDS];
+    size_t roll_row_bytes[ROLLOUT_TABLE_FIELDS];
     imgenv_rollout_cfg roll_cfg;
     imgenv_rollout_out roll_out;
     // rollout minibatches (imgenv_rollout_minibatch_enable; csrc/minibatch.h)
@@ -283,6 +291,15 @@ struct imgenv {
     size_t t_used = 0;
     double t_ms[IMGENV_K_COUNT] = {0};
     int64_t t_cnt[IMGENV_K_COUNT] = {0};
+    // running normalisation (imgenv_normalise_enable; csrc/normalise.h)
+    bool norm_on = false;
+    bool norm_training = true;   // the chains update the statistics (imgenv_normalise_training)
+    uint32_t norm_turn = 0;      // chains that have moved the statistics: which word of NormDev::stats is read
+    uint32_t norm_ret_turn = 0;  // step chains that have moved the returns: which word of NormDev::returns is read
+    NormDev norm;                // n_obs as enabled; n_ret, cols, update, the turns and the rows are the launch's
+    imgenv_normalise_cfg norm_cfg;
+    imgenv_normalise_out norm_out;
+    MbBufferAll mb_all[IMGENV_MB_MAX_BUFFERS];  // the minibatch buffers' pointers, the normalised fields' included (mb_out.buf holds the public part)
 };
 
 // RCCL is resolved at run time so that single-GPU users do not need it: prefer the copy the process already
@@ -1892,6 +1909,32 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
         const LaunchShape g = plan_tail_launch(p, c, (size_t)pd.per_row, OBS_POST_BLOCK, OBS_POST_MAX_BLOCKS);
         (is_reset ? k_obs_post<true> : k_obs_post<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(pd);
         h->launches += 1;
+    }
+    if (h->norm_on) {
+        // the running normalisation (normalise.h), behind the stacks whose newest frames it reads and in front of the rollout storage
+        // that may store its output: with training on the chain's batch goes into the statistics (a reset chain has no return
+        // column), then every chain applies them to the rows it covers
+        NormDev nd = h->norm;
+        const bool rew = (h->norm_cfg.flags & IMGENV_NORM_REWARD) != 0;
+        nd.rows = tail_rows(h, is_reset);
+        nd.n_ret = !is_reset && rew ? 1 : 0;
+        nd.cols = std::max(1, nd.n_obs + nd.n_ret);
+        nd.update = h->norm_training ? 1 : 0;
+        nd.turn = h->norm_turn;
+        nd.ret_turn = h->norm_ret_turn;
+        const bool stats_move = nd.update && (!is_reset || nd.n_obs > 0);
+        if (stats_move) {
+            const LaunchShape g = plan_norm_part_launch(p, c, nd.cols);
+            (is_reset ? k_norm_part<true> : k_norm_part<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(nd);
+            h->launches += 1;
+            h->norm_turn += 1;
+        }
+        if (!is_reset || nd.n_obs > 0 || (nd.update && rew)) {  // (a reset chain of a reward-only handle in evaluation has nothing to do)
+            const LaunchShape g = plan_norm_apply_launch(p, c, nd.cols);
+            (is_reset ? k_norm_apply<true> : k_norm_apply<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(nd);
+            h->launches += 1;
+        }
+        if (nd.update && nd.n_ret) h->norm_ret_turn += 1;
     }
     if (h->roll_on && h->roll_begun) {
         // the rollout storage (rollout.h), last -- it reads what k_stack and k_obs_post have just written: a step stores transition
@@ -4228,11 +4271,162 @@ extern "C" int imgenv_obs_post_outputs(imgenv_t* h, imgenv_obs_post_out* out) {
     return feature_outputs(h, &imgenv::post_on, &imgenv::post_out, out, "imgenv_obs_post_enable");
 }
 
+// ---- running normalisation (include/imgenv.h; the kernels are csrc/normalise.h) ----
+extern "C" int imgenv_normalise_enable(imgenv_t* h, const imgenv_normalise_cfg* c, imgenv_normalise_out* out) {
+    // (the cfg first, as above)
+    RTRY(enable_args(c, "imgenv_normalise_cfg", out, "imgenv_normalise_out"));
+    if (c->flags == 0 || (c->flags & ~(IMGENV_NORM_OBS | IMGENV_NORM_REWARD))) FAIL(IMGENV_EINVAL, "imgenv_normalise_cfg.flags %d", c->flags);
+    if (!std::isfinite(c->clip_obs) || c->clip_obs <= 0.0) FAIL(IMGENV_EINVAL, "imgenv_normalise_cfg.clip_obs %g: finite and above 0", c->clip_obs);
+    if (!std::isfinite(c->clip_reward) || c->clip_reward <= 0.0) FAIL(IMGENV_EINVAL, "imgenv_normalise_cfg.clip_reward %g: finite and above 0", c->clip_reward);
+    if (!std::isfinite(c->eps) || c->eps <= 0.0) FAIL(IMGENV_EINVAL, "imgenv_normalise_cfg.eps %g: finite and above 0", c->eps);
+    if (!(c->gamma >= 0.0 && c->gamma <= 1.0)) FAIL(IMGENV_EINVAL, "imgenv_normalise_cfg.gamma %g: 0 .. 1", c->gamma);
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (h->norm_on) FAIL(IMGENV_EINVAL, "imgenv_normalise_enable has already been called on this handle");
+    const imgenv_out& w = h->out;
+    const int D = w.state_dim;
+    if (D < 1 || D + 1 > NORM_MAX_COLS) FAIL(IMGENV_EINVAL, "imgenv_normalise_enable: state_dim %d (1 .. %d)", D, NORM_MAX_COLS - 1);
+    const bool obs = (c->flags & IMGENV_NORM_OBS) != 0, rew = (c->flags & IMGENV_NORM_REWARD) != 0;
+    const imgenv_stack_out& so = h->stack_out;
+    const int K = obs && h->stack_on && so.state_depth >= 2 ? so.state_depth : 0;
+    // one block, every array on a 256-byte boundary, zeroed; nothing of the handle changes before it is there
+    const size_t RL = (size_t)h->RL, words = NORM_STATS_WORDS(D);
+    const int cols_step = std::max(1, (obs ? D : 0) + (rew ? 1 : 0)), cols_reset = std::max(1, obs ? D : 0);
+    const size_t tiles = std::max(plan_norm_tiles(RL, cols_step), plan_norm_tiles(RL, cols_reset));
+    size_t total = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = total;
+        total = align256(total + bytes);
+        return at;
+    };
+    const size_t off_stats = carve(2 * words * 8), off_ret = carve(rew ? 2 * RL * 8 : 0), off_part = carve(tiles * (size_t)cols_step * 16), off_pn = carve(tiles * 4);
+    const size_t off_nv = carve(obs ? RL * D * 4 : 0), off_ns = carve((size_t)K * RL * D * 4), off_nr = carve(rew ? RL * 8 : 0);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    unsigned char* block = nullptr;
+    DevTxn<HipApi> txn;
+    if (!txn.room(&block, total, 0)) FAIL(txn.code(), "imgenv_normalise_enable: %s", txn.error());
+    std::vector<double> init(2 * words, 0.0);  // SB3's RunningMeanStd: count 1e-4, mean 0, var 1 -- in both words
+    for (int q = 0; q < 2; q++) {
+        double* s = init.data() + q * words;
+        s[0] = s[1] = 1e-4;
+        s[3] = 1.0;
+        for (int d = 0; d < D; d++) s[4 + D + d] = 1.0;
+    }
+    if (const char* e = HipApi::memcpy(block + off_stats, init.data(), init.size() * 8, false)) FAIL(IMGENV_EDEVICE, "imgenv_normalise_enable: %s", e);
+    txn.commit(h->allocs);
+    NormDev n;
+    memset(&n, 0, sizeof(n));
+    n.vector_states = w.vector_states;  // (the working arena, also under IMGENV_FLAG_FULL_REWRITE)
+    n.state_stack = K ? so.vector_states : nullptr;
+    n.rewards = w.step_rewards;
+    n.is_clean = w.step_is_clean;
+    n.dones = w.step_dones;
+    n.stats = (double*)(block + off_stats);
+    n.returns = rew ? (double*)(block + off_ret) : nullptr;
+    n.part = (double*)(block + off_part);
+    n.part_n = (uint32_t*)(block + off_pn);
+    n.norm_vector_states = obs ? (float*)(block + off_nv) : nullptr;
+    n.norm_state_stack = K ? (float*)(block + off_ns) : nullptr;
+    n.norm_rewards = rew ? (double*)(block + off_nr) : nullptr;
+    n.gamma = c->gamma; n.clip_obs = c->clip_obs; n.clip_reward = c->clip_reward; n.eps = c->eps;
+    n.D = D;
+    n.K = K;
+    n.n_obs = obs ? D : 0;
+    h->norm = n;
+    h->norm_cfg = *c;
+    h->norm_training = true;
+    h->norm_turn = h->norm_ret_turn = 0;
+    imgenv_normalise_out o = {};
+    o.state_dim = D;
+    o.state_depth = K;
+    o.norm_vector_states = n.norm_vector_states;
+    o.norm_state_stack = n.norm_state_stack;
+    o.norm_rewards = n.norm_rewards;
+    o.stats = n.stats;
+    o.returns = n.returns;
+    o.training = 1;
+    return enable_done(h, o, &imgenv::norm_out, &imgenv::norm_on, out);
+}
+
+extern "C" int imgenv_normalise_outputs(imgenv_t* h, imgenv_normalise_out* out) {
+    if (int rc = feature_outputs(h, &imgenv::norm_on, &imgenv::norm_out, out, "imgenv_normalise_enable")) return rc;
+    out->stats_word = (int32_t)(h->norm_turn & 1);
+    out->returns_word = (int32_t)(h->norm_ret_turn & 1);
+    out->training = h->norm_training ? 1 : 0;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_normalise_training(imgenv_t* h, int32_t on, void* stream) {
+    (void)stream;  // (a host-side switch: the chains queued from now on take it by value)
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (!h->norm_on) FAIL(IMGENV_ESTATE, "imgenv_normalise_enable was not called");
+    h->norm_training = on != 0;
+    return IMGENV_OK;
+}
+
+static int normalise_stats_args(const imgenv* h, const imgenv_normalise_stats* s) {
+    if (!h || !s) FAIL(IMGENV_EINVAL, "null argument");
+    if (s->struct_size != (int32_t)sizeof(imgenv_normalise_stats)) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats.struct_size %d (this library's is %d)", s->struct_size, (int)sizeof(imgenv_normalise_stats));
+    if (!h->norm_on) FAIL(IMGENV_ESTATE, "imgenv_normalise_enable was not called");
+    if (s->state_dim != h->norm.D || s->n_rows != h->RL) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats: state_dim %d, n_rows %d (the handle's are %d, %d)", s->state_dim, s->n_rows, h->norm.D, h->RL);
+    if (!s->obs_mean || !s->obs_var) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats: null obs_mean / obs_var");
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_normalise_stats_get(imgenv_t* h, imgenv_normalise_stats* s) {
+    RTRY(normalise_stats_args(h, s));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipDeviceSynchronize());
+    const size_t D = (size_t)h->norm.D, words = NORM_STATS_WORDS(D), RL = (size_t)h->RL;
+    std::vector<double> host(words);
+    HIPCHK(hipMemcpy(host.data(), h->norm.stats + (size_t)(h->norm_turn & 1) * words, words * 8, hipMemcpyDeviceToHost));
+    s->obs_count = host[0]; s->ret_count = host[1]; s->ret_mean = host[2]; s->ret_var = host[3];
+    for (size_t d = 0; d < D; d++) {
+        s->obs_mean[d] = host[4 + d];
+        s->obs_var[d] = host[4 + D + d];
+    }
+    if (s->returns) {
+        if (h->norm.returns)
+            HIPCHK(hipMemcpy(s->returns, h->norm.returns + (size_t)(h->norm_ret_turn & 1) * RL, RL * 8, hipMemcpyDeviceToHost));
+        else
+            std::fill(s->returns, s->returns + RL, 0.0);
+    }
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_normalise_stats_set(imgenv_t* h, const imgenv_normalise_stats* s) {
+    RTRY(normalise_stats_args(h, s));
+    const size_t D = (size_t)h->norm.D, words = NORM_STATS_WORDS(D), RL = (size_t)h->RL;
+    std::vector<double> host(words);
+    host[0] = s->obs_count; host[1] = s->ret_count; host[2] = s->ret_mean; host[3] = s->ret_var;
+    for (size_t d = 0; d < D; d++) {
+        host[4 + d] = s->obs_mean[d];
+        host[4 + D + d] = s->obs_var[d];
+    }
+    for (size_t k = 0; k < words; k++)
+        if (!std::isfinite(host[k])) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats: word %d is not finite", (int)k);
+    if (host[0] <= 0.0 || host[1] <= 0.0) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats: a count of %g / %g (above 0)", host[0], host[1]);
+    if (host[3] < 0.0) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats.ret_var %g", host[3]);
+    for (size_t d = 0; d < D; d++)
+        if (host[4 + D + d] < 0.0) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats.obs_var[%d] %g", (int)d, host[4 + D + d]);
+    if (s->returns)
+        for (size_t r = 0; r < RL; r++)
+            if (!std::isfinite(s->returns[r])) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats.returns[%d] is not finite", (int)r);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(h->norm.stats + (size_t)(h->norm_turn & 1) * words, host.data(), words * 8, hipMemcpyHostToDevice));
+    if (s->returns && h->norm.returns)
+        HIPCHK(hipMemcpy(h->norm.returns + (size_t)(h->norm_ret_turn & 1) * RL, s->returns, RL * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    return IMGENV_OK;
+}
+
 // ---- final observations (include/imgenv.h; the kernel is csrc/final_obs.h) ----
 extern "C" int imgenv_final_obs_enable(imgenv_t* h, const imgenv_final_obs_cfg* c, imgenv_final_obs_out* out) {
     // (the cfg first, as above)
     RTRY(enable_args(c, "imgenv_final_obs_cfg", out, "imgenv_final_obs_out"));
-    if (c->fields == 0 || (c->fields & ~IMGENV_FINAL_ALL)) FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields %d", c->fields);
+    if (c->fields == 0 || (c->fields & ~(IMGENV_FINAL_ALL | IMGENV_FINAL_NORM_STATES))) FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields %d", c->fields);
+    if ((c->fields & IMGENV_FINAL_NORM_STATES) && !(h && h->norm_on && h->norm.norm_vector_states))
+        FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields %d: IMGENV_FINAL_NORM_STATES before imgenv_normalise_enable with IMGENV_NORM_OBS", c->fields);
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
     if (h->final_on) {
         if (c->fields != h->final_cfg.fields)
@@ -4251,6 +4445,7 @@ extern "C" int imgenv_final_obs_enable(imgenv_t* h, const imgenv_final_obs_cfg* 
     const size_t NC = (size_t)w.view_h * w.view_w, NI = (size_t)w.image_h * w.image_w, B = (size_t)std::max(w.n_beams, 0);
     const size_t NP = (size_t)h->cfg.ped_image_size[0] * h->cfg.ped_image_size[1];
     imgenv_final_obs_out o = {};
+    imgenv_normalise_out no = h->norm_out;  // (the normalised fields' pointers are handed out there: this struct keeps its layout)
     struct Src {
         int bit;
         const void* src;
@@ -4275,13 +4470,17 @@ extern "C" int imgenv_final_obs_enable(imgenv_t* h, const imgenv_final_obs_cfg* 
         {IMGENV_FINAL_STACKS, so.state_depth >= 2 ? so.vector_states : nullptr, (size_t)std::max(so.state_depth, 0) * w.state_dim * 4, (void**)&o.stack_vector_states},
         {IMGENV_FINAL_STACKS, so.laser_depth >= 2 ? so.lasers : nullptr, (size_t)std::max(so.laser_depth, 0) * B * 8, (void**)&o.stack_lasers},
         {IMGENV_FINAL_PED_NORM, h->post.norm, (size_t)w.ped_vec_len * 4, (void**)&o.ped_vector_norm},
+        // (normalise.h's arrays; the stack only where the handle keeps one)
+        {IMGENV_FINAL_NORM_STATES, h->norm_on ? h->norm.norm_vector_states : nullptr, (size_t)w.state_dim * 4, (void**)&no.final_norm_vector_states},
+        {IMGENV_FINAL_NORM_STATES, h->norm_on ? h->norm.norm_state_stack : nullptr, (size_t)std::max(h->norm_on ? h->norm.K : 0, 0) * w.state_dim * 4,
+         (void**)&no.final_norm_state_stack},
     };
     static_assert(sizeof(all) / sizeof(all[0]) <= FINAL_MAX_FIELDS, "FINAL_MAX_FIELDS");
     const Src* sel[FINAL_MAX_FIELDS];
     size_t row_bytes[FINAL_MAX_FIELDS];
     int n = 0;
     for (const Src& s : all) {
-        if (!(want & s.bit) || ((s.bit & (IMGENV_FINAL_STACKS | IMGENV_FINAL_PED_NORM)) && !s.src)) continue;
+        if (!(want & s.bit) || ((s.bit & (IMGENV_FINAL_STACKS | IMGENV_FINAL_PED_NORM | IMGENV_FINAL_NORM_STATES)) && !s.src)) continue;
         if (!s.src || s.row_bytes == 0) FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields: bit %d names a field of no bytes on this handle", s.bit);
         sel[n] = &s;
         row_bytes[n++] = s.row_bytes;
@@ -4313,6 +4512,7 @@ extern "C" int imgenv_final_obs_enable(imgenv_t* h, const imgenv_final_obs_cfg* 
     }
     o.final_count = fo.count;
     h->final_dev = fo;
+    if (h->norm_on) h->norm_out = no;
     h->final_cfg = *c;
     return enable_done(h, o, &imgenv::final_out, &imgenv::final_on, out);
 }
@@ -4327,7 +4527,16 @@ extern "C" int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* c, i
     RTRY(enable_args(c, "imgenv_rollout_cfg", out, "imgenv_rollout_out"));
     if (c->horizon < 1) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.horizon %d: at least 1", c->horizon);
     if (c->final_capacity < 1) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.final_capacity %d: at least 1", c->final_capacity);
-    if (c->fields == 0 || (c->fields & ~IMGENV_ROLLOUT_ALL)) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d", c->fields);
+    const int norm_bits = IMGENV_ROLLOUT_NORM_STATES | IMGENV_ROLLOUT_NORM_REWARDS;
+    if (c->fields == 0 || (c->fields & ~(IMGENV_ROLLOUT_ALL | norm_bits))) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d", c->fields);
+    if (c->fields & norm_bits) {
+        if (!(h && h->norm_on)) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d: IMGENV_ROLLOUT_NORM_* before imgenv_normalise_enable", c->fields);
+        if ((c->fields & IMGENV_ROLLOUT_NORM_STATES) && !h->norm.norm_vector_states)
+            FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d: IMGENV_ROLLOUT_NORM_STATES without IMGENV_NORM_OBS", c->fields);
+        if ((c->fields & IMGENV_ROLLOUT_NORM_REWARDS) && !h->norm.norm_rewards)
+            FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d: IMGENV_ROLLOUT_NORM_REWARDS without IMGENV_NORM_REWARD", c->fields);
+        if (!(c->fields & ~IMGENV_ROLLOUT_NORM_REWARDS)) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d: IMGENV_ROLLOUT_NORM_REWARDS selects no field", c->fields);
+    }
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
     if (h->roll_on) {
         const imgenv_rollout_cfg& o = h->roll_cfg;
@@ -4348,6 +4557,7 @@ extern "C" int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* c, i
     const size_t NI = (size_t)w.image_h * w.image_w, B = (size_t)std::max(w.n_beams, 0);
     const size_t NP = (size_t)h->cfg.ped_image_size[0] * h->cfg.ped_image_size[1];
     imgenv_rollout_out o = {};
+    imgenv_normalise_out no = h->norm_out;  // (the normalised fields' ring and final pointers are handed out there)
     struct Src {
         int bit;
         const void* src;
@@ -4370,13 +4580,18 @@ extern "C" int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* c, i
          (void**)&o.obs_stack_vector_states, (void**)&o.final_stack_vector_states},
         {IMGENV_ROLLOUT_STACKS, so.laser_depth >= 2 ? so.lasers : nullptr, (size_t)std::max(so.laser_depth, 0) * B * 8,
          (void**)&o.obs_stack_lasers, (void**)&o.final_stack_lasers},
+        // (normalise.h's arrays; the stack only where the handle keeps one)
+        {IMGENV_ROLLOUT_NORM_STATES, h->norm_on ? h->norm.norm_vector_states : nullptr, (size_t)w.state_dim * 4, (void**)&no.rollout_obs_norm_vector_states,
+         (void**)&no.rollout_final_norm_vector_states},
+        {IMGENV_ROLLOUT_NORM_STATES, h->norm_on ? h->norm.norm_state_stack : nullptr, (size_t)std::max(h->norm_on ? h->norm.K : 0, 0) * w.state_dim * 4,
+         (void**)&no.rollout_obs_norm_state_stack, (void**)&no.rollout_final_norm_state_stack},
     };
-    static_assert(sizeof(all) / sizeof(all[0]) <= ROLLOUT_MAX_FIELDS, "ROLLOUT_MAX_FIELDS");
-    const Src* sel[ROLLOUT_MAX_FIELDS];
-    size_t row_bytes[ROLLOUT_MAX_FIELDS];
+    static_assert(sizeof(all) / sizeof(all[0]) <= ROLLOUT_TABLE_FIELDS, "ROLLOUT_TABLE_FIELDS");
+    const Src* sel[ROLLOUT_TABLE_FIELDS];
+    size_t row_bytes[ROLLOUT_TABLE_FIELDS];
     int n = 0;
     for (const Src& s : all) {
-        if (!(want & s.bit) || (s.bit == IMGENV_ROLLOUT_STACKS && !s.src)) continue;  // (a stack of depth 1 is the field itself)
+        if (!(want & s.bit) || ((s.bit & (IMGENV_ROLLOUT_STACKS | IMGENV_ROLLOUT_NORM_STATES)) && !s.src)) continue;  // (a stack of depth 1 is the field itself)
         if (!s.src || s.row_bytes == 0) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields: bit %d names a field of no bytes on this handle", s.bit);
         sel[n] = &s;
         row_bytes[n++] = s.row_bytes;
@@ -4388,7 +4603,7 @@ extern "C" int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* c, i
         total = align256(total + bytes);
         return at;
     };
-    size_t off_ring[ROLLOUT_MAX_FIELDS], off_fin[ROLLOUT_MAX_FIELDS];
+    size_t off_ring[ROLLOUT_TABLE_FIELDS], off_fin[ROLLOUT_TABLE_FIELDS];
     for (int k = 0; k < n; k++) {
         off_ring[k] = carve((T + 1) * RL * row_bytes[k]);
         off_fin[k] = carve(F * row_bytes[k]);
@@ -4415,7 +4630,8 @@ extern "C" int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* c, i
         *sel[k]->ring = ro.f[k].ring;
         *sel[k]->fin = ro.f[k].fin;
     }
-    ro.rew_src = w.step_rewards;  // (the working arena, also under IMGENV_FLAG_FULL_REWRITE)
+    // (the working arena, also under IMGENV_FLAG_FULL_REWRITE; IMGENV_ROLLOUT_NORM_REWARDS: what k_norm_apply has just written)
+    ro.rew_src = (want & IMGENV_ROLLOUT_NORM_REWARDS) ? h->norm.norm_rewards : w.step_rewards;
     ro.done_src = w.step_dones;
     ro.clean_src = w.step_is_clean;
     ro.info_src = w.step_dones_info;
@@ -4433,6 +4649,7 @@ extern "C" int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* c, i
     o.final_capacity = c->final_capacity;
     o.n = -1;
     h->roll = ro;
+    if (h->norm_on) h->norm_out = no;
     h->roll_cfg = *c;
     h->roll_begun = false;
     h->roll_n = 0;
@@ -4497,7 +4714,8 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
     RTRY(enable_args(c, "imgenv_minibatch_cfg", out, "imgenv_minibatch_out"));
     if (c->batch < 1) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.batch %d: at least 1", c->batch);
     if (c->buffers < 1 || c->buffers > IMGENV_MB_MAX_BUFFERS) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.buffers %d: 1 .. %d", c->buffers, IMGENV_MB_MAX_BUFFERS);
-    if (c->fields & ~IMGENV_ROLLOUT_ALL) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d", c->fields);
+    if (c->fields & ~(IMGENV_ROLLOUT_ALL | IMGENV_ROLLOUT_NORM_STATES)) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d", c->fields);  // (NORM_REWARDS names no field)
+    if ((c->fields & IMGENV_ROLLOUT_NORM_STATES) && !(h && h->norm_on)) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: IMGENV_ROLLOUT_NORM_* before imgenv_normalise_enable", c->fields);
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
     if (!h->roll_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch_enable before imgenv_rollout_enable");
     if (h->mb_on) {
@@ -4507,7 +4725,7 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
                  o.buffers, o.fields);
         return out ? imgenv_rollout_minibatch_outputs(h, out) : IMGENV_OK;
     }
-    const int want = c->fields ? c->fields : h->roll_cfg.fields;
+    const int want = c->fields ? c->fields : (h->roll_cfg.fields & ~IMGENV_ROLLOUT_NORM_REWARDS);
     if (want & ~h->roll_cfg.fields) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: the rollout stores %d", c->fields, h->roll_cfg.fields);
     // the ring's fields in its own order, each found again by its obs_ pointer
     const imgenv_rollout_out& ro = h->roll_out;
@@ -4526,13 +4744,16 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
         {IMGENV_ROLLOUT_STACKS, ro.obs_stack_sensor_maps, offsetof(imgenv_minibatch_buffer, mb_stack_sensor_maps)},
         {IMGENV_ROLLOUT_STACKS, ro.obs_stack_vector_states, offsetof(imgenv_minibatch_buffer, mb_stack_vector_states)},
         {IMGENV_ROLLOUT_STACKS, ro.obs_stack_lasers, offsetof(imgenv_minibatch_buffer, mb_stack_lasers)},
+        // (the normalised fields: their buffers' pointers are imgenv_normalise_out's, kept behind the public struct in MbBufferAll)
+        {IMGENV_ROLLOUT_NORM_STATES, h->norm_on ? h->norm_out.rollout_obs_norm_vector_states : nullptr, offsetof(MbBufferAll, mb_norm_vector_states)},
+        {IMGENV_ROLLOUT_NORM_STATES, h->norm_on ? h->norm_out.rollout_obs_norm_state_stack : nullptr, offsetof(MbBufferAll, mb_norm_state_stack)},
     };
-    static_assert(sizeof(all) / sizeof(all[0]) <= ROLLOUT_MAX_FIELDS, "ROLLOUT_MAX_FIELDS");
+    static_assert(sizeof(all) / sizeof(all[0]) <= ROLLOUT_TABLE_FIELDS, "ROLLOUT_TABLE_FIELDS");
     const size_t RL = (size_t)h->RL, T = (size_t)h->roll_cfg.horizon, B = (size_t)c->batch, NB = (size_t)c->buffers;
     const size_t tiles = std::max(plan_mb_tiles(T * RL), plan_mb_stats_tiles(T * RL));
     MbGatherDev g;
     memset(&g, 0, sizeof(g));
-    size_t row_bytes[ROLLOUT_MAX_FIELDS], slot[ROLLOUT_MAX_FIELDS];
+    size_t row_bytes[ROLLOUT_TABLE_FIELDS], slot[ROLLOUT_TABLE_FIELDS];
     for (int k = 0; k < h->roll.n_fields; k++)
         for (const Src& s : all) {
             if (!s.ring || s.ring != (const void*)h->roll.f[k].ring || !(want & s.bit)) continue;
@@ -4554,7 +4775,7 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
     };
     const size_t off_valid = carve(T * RL * 4), off_order = carve(T * RL * 4), off_vn = carve(4), off_norm = carve(8);
     const size_t off_tc = carve(tiles * 4), off_tb = carve(tiles * 4), off_part = carve(tiles * 8), off_mean = carve(8);
-    size_t off_f[IMGENV_MB_MAX_BUFFERS][ROLLOUT_MAX_FIELDS], off_s[IMGENV_MB_MAX_BUFFERS][7];
+    size_t off_f[IMGENV_MB_MAX_BUFFERS][ROLLOUT_TABLE_FIELDS], off_s[IMGENV_MB_MAX_BUFFERS][7];
     for (int k = 0; k < g.n_fields; k++)  // (a field's buffers side by side: one strided view covers them)
         for (size_t b = 0; b < NB; b++) off_f[b][k] = carve(B * row_bytes[k]);
     const size_t scalar_bytes[7] = {B * 12, B * 4, B, B * 4, B * 4, B * 4, B * 4 * IMGENV_MB_MAX_SCALARS};
@@ -4579,8 +4800,10 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
     o.stat_part = (double*)(block + off_part);
     o.stat_mean = (double*)(block + off_mean);
     for (size_t b = 0; b < NB; b++) {
-        imgenv_minibatch_buffer& m = o.buf[b];
-        for (int k = 0; k < g.n_fields; k++) *(void**)((unsigned char*)&m + slot[k]) = block + off_f[b][k];
+        MbBufferAll& all_b = h->mb_all[b];
+        all_b = MbBufferAll{};
+        imgenv_minibatch_buffer& m = all_b.pub;
+        for (int k = 0; k < g.n_fields; k++) *(void**)((unsigned char*)&all_b + slot[k]) = block + off_f[b][k];
         m.mb_actions = (float*)(block + off_s[b][0]);
         m.mb_rewards = (float*)(block + off_s[b][1]);
         m.mb_dones = block + off_s[b][2];
@@ -4588,6 +4811,11 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
         m.mb_index = (int32_t*)(block + off_s[b][4]);
         m.mb_weight = (float*)(block + off_s[b][5]);
         m.mb_scalars = (float*)(block + off_s[b][6]);
+        o.buf[b] = m;
+        if (h->norm_on) {
+            h->norm_out.mb_norm_vector_states[b] = all_b.mb_norm_vector_states;
+            h->norm_out.mb_norm_state_stack[b] = all_b.mb_norm_state_stack;
+        }
     }
     g.order = o.order;
     g.B = (uint32_t)c->batch;
@@ -4683,9 +4911,10 @@ extern "C" int imgenv_rollout_minibatch(imgenv_t* h, const imgenv_minibatch_args
     RTRY(minibatch_fresh(h, "imgenv_rollout_minibatch"));
     if (!h->mb_shuffled) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch before imgenv_rollout_shuffle");
     HIPCHK(hipSetDevice(h->cfg.device));
-    const imgenv_minibatch_buffer& m = h->mb_out.buf[a->buffer];
+    const MbBufferAll& all_b = h->mb_all[a->buffer];
+    const imgenv_minibatch_buffer& m = all_b.pub;
     MbGatherDev g = h->mb_gather;
-    for (int k = 0; k < g.n_fields; k++) g.f[k].dst = *(unsigned char* const*)((const unsigned char*)&m + (size_t)(uintptr_t)g.f[k].dst);
+    for (int k = 0; k < g.n_fields; k++) g.f[k].dst = *(unsigned char* const*)((const unsigned char*)&all_b + (size_t)(uintptr_t)g.f[k].dst);
     g.first = (size_t)a->j * (size_t)g.B;
     g.mb_actions = m.mb_actions;
     g.mb_rewards = m.mb_rewards;

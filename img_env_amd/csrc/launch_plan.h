@@ -34,10 +34,12 @@
 #define EPLOG_BLOCK 1024    // k_episode_log: ONE workgroup (its records are numbered by a running count), 16 wavefronts
 #define FINAL_BLOCK 256     // k_final_obs: one lane per chunk of a captured row
 #define FINAL_MAX_BLOCKS 1024
-#define FINAL_MAX_FIELDS 16  // 11 fields of imgenv_out, 3 stacks, ped_vector_norm
+#define FINAL_MAX_FIELDS 18  // 11 fields of imgenv_out, 3 stacks, ped_vector_norm, the two normalised states (normalise.h)
 #define ROLLOUT_BLOCK 256   // k_rollout: one lane per chunk of a stored row
 #define ROLLOUT_MAX_BLOCKS 1024
 #define ROLLOUT_MAX_FIELDS 9  // five single-frame fields, ped_vector_norm, three stacks
+#define ROLLOUT_NORM_FIELDS 2  // norm_vector_states, norm_state_stack (normalise.h; their pointers are imgenv_normalise_out's)
+#define ROLLOUT_TABLE_FIELDS (ROLLOUT_MAX_FIELDS + ROLLOUT_NORM_FIELDS)  // what a field table of k_rollout / k_rollout_gather holds: 11
 #define GAE_BLOCK 64        // k_rollout_gae: one lane per local robot, one wavefront per block (4096 robots reach 64 CUs)
 #define GAE_MAX_BLOCKS 1024
 #define GAE_BATCH 4         // time steps whose loads a lane issues before it walks their dependent chain
@@ -50,6 +52,10 @@
 #define MB_STATS_TILE (MB_STATS_BLOCK * MB_STATS_PER_LANE)
 #define MB_SHUFFLE_BLOCK 256 // k_mb_shuffle: one lane per position of `order`
 #define MB_ROUNDS 6          // Feistel rounds of the shuffle's permutation
+#define NORM_BLOCK 256       // k_norm_part / k_norm_apply (normalise.h): four wavefronts, a lane per (row, column)
+#define NORM_PER_LANE 8      // k_norm_part: the rows of a tile whose samples a lane holds in registers
+#define NORM_MAX_COLS 64     // state_dim + 1 (the return) columns at most: the columns of a row lie in one wavefront
+#define NORM_MAX_BLOCKS 1024
 #define ACT_BLOCK 256       // k_actions: one lane per local robot
 #define OBS_POST_BLOCK 256  // k_obs_post: one lane per element of a robot's ped_vector row
 #define OBS_POST_MAX_BLOCKS 2048
@@ -497,6 +503,22 @@ inline LaunchShape plan_mb_shuffle_launch(size_t positions) {
 }
 inline LaunchShape plan_mb_gather_launch(size_t batch, uint32_t chunks_per_row) {
     return plan_tail(batch * chunks_per_row, ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS);
+}
+
+// ---------------------------------------------------------------------------------------- chain tail: k_norm_part, k_norm_apply
+// normalise.h.  A wavefront holds WAVE / cols whole rows, a lane per (row, column); a tile of k_norm_part is what a workgroup's
+// lanes hold NORM_PER_LANE rows deep.  One workgroup per tile of the chain's rows, one per pass of the apply, both capped: the
+// kernels stride over tiles / passes, and over whatever a device-side count turns out to be.
+// (constexpr: the kernels call them too)
+inline constexpr int plan_norm_rows_per_wave(int cols) { return WAVE / (cols > 1 ? cols : 1); }
+inline constexpr size_t plan_norm_tile_rows(int cols) { return (size_t)(NORM_BLOCK / WAVE) * plan_norm_rows_per_wave(cols) * NORM_PER_LANE; }
+inline constexpr size_t plan_norm_tiles(size_t rows, int cols) { return (rows + plan_norm_tile_rows(cols) - 1) / plan_norm_tile_rows(cols); }
+inline LaunchShape plan_norm_part_launch(const PlanHandle& h, const PlanChain& c, int cols) {
+    return {(unsigned)std::min<size_t>(NORM_MAX_BLOCKS, std::max<size_t>(1, plan_norm_tiles(plan_tail_rows(h, c), cols))), NORM_BLOCK, 0};
+}
+inline LaunchShape plan_norm_apply_launch(const PlanHandle& h, const PlanChain& c, int cols) {
+    const size_t per_block = (size_t)(NORM_BLOCK / WAVE) * plan_norm_rows_per_wave(cols);
+    return {(unsigned)std::min<size_t>(NORM_MAX_BLOCKS, std::max<size_t>(1, (plan_tail_rows(h, c) + per_block - 1) / per_block)), NORM_BLOCK, 0};
 }
 
 // ---------------------------------------------------------------------------------------- in front of the chain: k_actions

@@ -39,7 +39,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "launch_plan.h"  // MB_*, ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS, ROLLOUT_MAX_FIELDS
+#include "launch_plan.h"  // MB_*, ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS, ROLLOUT_TABLE_FIELDS
 #include "rollout.h"      // RolloutChunk16 / RolloutChunk8, ROLLOUT_UNROLL
 
 #define MB_MAX_SCALARS 6  // (IMGENV_MB_MAX_SCALARS)
@@ -192,7 +192,7 @@ struct MbGatherField {
     uint32_t unit, chunks;
 };
 struct MbGatherDev {
-    MbGatherField f[ROLLOUT_MAX_FIELDS];
+    MbGatherField f[ROLLOUT_TABLE_FIELDS];
     int32_t n_fields;
     uint32_t chunks_per_row;
     const int32_t* order;     // [T RL]
@@ -224,7 +224,7 @@ TAIL_HD void mb_gather_chunk(const unsigned char* ring, unsigned char* dst, uint
 }
 template <int K>
 TAIL_HD void mb_gather_field(const MbGatherDev& g, uint32_t& c, const unsigned char*& ring, unsigned char*& dst, uint32_t& chunks, uint32_t& unit) {
-    if constexpr (K < ROLLOUT_MAX_FIELDS) {
+    if constexpr (K < ROLLOUT_TABLE_FIELDS) {
         if (K < g.n_fields && c >= chunks) {
             c -= chunks;
             ring = g.f[K].ring; dst = g.f[K].dst; chunks = g.f[K].chunks; unit = g.f[K].unit;

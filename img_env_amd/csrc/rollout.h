@@ -36,7 +36,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "launch_plan.h"  // ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS, ROLLOUT_MAX_FIELDS, GAE_BLOCK, GAE_BATCH
+#include "launch_plan.h"  // ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS, ROLLOUT_TABLE_FIELDS, GAE_BLOCK, GAE_BATCH
 #include "tail_rows.h"
 
 #if defined(__HIPCC__)
@@ -54,7 +54,7 @@ struct RolloutField {
 };
 
 struct RolloutDev {
-    RolloutField f[ROLLOUT_MAX_FIELDS];
+    RolloutField f[ROLLOUT_TABLE_FIELDS];
     int32_t n_fields;
     uint32_t chunks_per_row;  // sum of f[].chunks
     // the transition of a step: the sources ([RL], the working arena's imgenv_out.step_* rows and the step's actions) ...
@@ -109,7 +109,7 @@ TAIL_HD void rollout_chunk(unsigned char* ring, unsigned char* fin, const unsign
 template <int K>
 TAIL_HD void rollout_field(const RolloutDev& ro, uint32_t& c, unsigned char*& ring, unsigned char*& fin, const unsigned char*& src, uint32_t& chunks,
                            uint32_t& unit) {
-    if constexpr (K < ROLLOUT_MAX_FIELDS) {
+    if constexpr (K < ROLLOUT_TABLE_FIELDS) {
         if (K < ro.n_fields && c >= chunks) {
             c -= chunks;
             ring = ro.f[K].ring; fin = ro.f[K].fin; src = ro.f[K].src; chunks = ro.f[K].chunks; unit = ro.f[K].unit;

@@ -41,12 +41,15 @@ class VecImageEnv:
     ``rollout_begin()``, ``rollout_advantages(values, final_values, gamma, lam)``.
     ``minibatch=B`` (with ``rollout=T``): the PPO epoch's minibatches gathered by the library, without a host read:
     ``rollout_minibatches(scalars, seed, normalise)``.
+    ``normalise=dict(...)``: running normalisation of ``vector_states`` and of the reward inside the library (VecNormalize): the
+    state and the reward handed out are the normalised ones, ``info`` gains ``raw_vector_states`` and ``raw_rewards``.
     """
 
     def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False,
                  map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3, wrappers=False,
                  ped_tracks=None, tracks_policy="keep", tracks_repeat=1, info_track_sets=False, scenarios=None, scenario_policy="queue",
-                 episode_log=0, final_obs=False, rollout=0, rollout_final=None, rollout_fields=None, minibatch=0, minibatch_buffers=1):
+                 episode_log=0, final_obs=False, rollout=0, rollout_final=None, rollout_fields=None, minibatch=0, minibatch_buffers=1,
+                 normalise=None):
         import torch
         from .world import World
         if int(minibatch or 0) > 0 and int(rollout or 0) <= 0:
@@ -185,6 +188,18 @@ class VecImageEnv:
             self._close = self.ped_total > 0
             if self._ped_norm or self._close:
                 self.world.enable_obs_post(ped_norm=self._ped_norm, close=self._close)
+        # normalise: Stable-Baselines3's VecNormalize inside the library (imgenv_normalise_enable) -- a dict of obs, reward, gamma,
+        # clip_obs, clip_reward, eps (defaults: True, True, 0.99, 10, 10, 1e-8).  The state's vector_states (and its stack) are then
+        # the normalised arrays and the returned reward the normalised one; info["raw_vector_states"] / info["raw_rewards"] are the
+        # untouched ones.  The running statistics count the robots that are not frozen, also where the device resets the envs;
+        # episode statistics and the episode log keep the raw rewards.  normalise_training(False) freezes them for evaluation,
+        # normalise_stats() / load_normalise_stats() carry them through a checkpoint.  At most two more launches per chain; nothing
+        # synchronises.  Opt-in: None allocates and launches nothing.
+        self.normalise = dict(normalise) if normalise else None
+        self._norm_obs = self._norm_reward = False
+        if self.normalise is not None:
+            self.world.enable_normalise(**self.normalise)
+            self._norm_obs, self._norm_reward = bool(self.normalise.get("obs", True)), bool(self.normalise.get("reward", True))
         # final_obs: Gym's final_observation (imgenv_final_obs_enable).  Every reset first copies the rows it is about to overwrite
         # -- the observation the env's last action led to, which a trainer needs to bootstrap a time-out -- into arrays of their
         # own: info["final_observation"] is the state in the form ``step`` hands out (stacks, filter list and normalised pedestrian
@@ -199,6 +214,8 @@ class VecImageEnv:
                 fields.append("stacks")
             if self._ped_norm:
                 fields.append("ped_vector_norm")
+            if self._norm_obs:
+                fields.append("norm_states")
             self.world.enable_final_obs(fields)
         # rollout=T: the trainer's [T, n, ...] storage inside the library (imgenv_rollout_enable).  After reset() every step also
         # stores its transition (action, reward, done, dones_info, is_clean) in slot t and the state it hands out in slot t + 1 of
@@ -219,8 +236,13 @@ class VecImageEnv:
                     fields.append("stacks")
                 if self._ped_norm:
                     fields.append("ped_vector_norm")
+                if self._norm_obs:  # (the normalised state instead of the raw one)
+                    fields = [n for n in fields if n != "vector_states"]
             else:
                 fields = rollout_fields
+            if self.normalise is not None:  # the two bits follow the handle's normalisation: the ring holds what ``step`` hands out
+                bits = (_cabi.ROLLOUT_NORM_STATES if self._norm_obs else 0) | (_cabi.ROLLOUT_NORM_REWARDS if self._norm_reward else 0)
+                fields = (int(fields) if isinstance(fields, (int, np.integer)) else _cabi.make_rollout_cfg(1, 1, fields).fields) | bits
             final = int(rollout_final) if rollout_final is not None else (self.rollout_horizon + 1) * len(self)
             self.world.enable_rollout(self.rollout_horizon, final, fields)
         # minibatch=B: the minibatches of a PPO epoch out of that storage (imgenv_rollout_minibatch_enable): the transitions that
@@ -345,12 +367,17 @@ class VecImageEnv:
             f = self.world.final_obs
             o = {name: f.get(name, t) for name, t in o.items()}
         ped_vector = (f if final else self.world.obs_post)["ped_vector_norm"] if self._ped_norm else o["ped_vector_states"]
+        norm = (f if final else self.world.normalise) if self._norm_obs else None
+        if norm is not None:  # normalise: the state's vector_states is the normalised array
+            o = dict(o, vector_states=norm["norm_vector_states"])
         if not self.stack:
             return ImageState(o["vector_states"], o["sensor_maps"], o["is_collisions"], o["is_arrives"], o["lasers"],
                               ped_vector, o["ped_maps"], o["step_ds"], o["ped_min_dists"])
         k = self.world.stack
         if final:  # a stack of depth 1 is the field itself, in the stack's shape
             k = {name: f["stack_" + name] if "stack_" + name in f else o[name].view(t.shape) for name, t in k.items()}
+        if norm is not None and "vector_states" in k:  # ... and so is its stack (depth 1: the normalised array itself)
+            k = dict(k, vector_states=norm["norm_state_stack"] if "norm_state_stack" in norm else o["vector_states"].view(k["vector_states"].shape))
         vector_states, sensor_maps, lasers = (k.get(f_, o[f_]) for f_ in ("vector_states", "sensor_maps", "lasers"))
         if self._filter == "ObsStateTmp":
             return [sensor_maps, vector_states, o["ped_maps"]]
@@ -407,7 +434,28 @@ class VecImageEnv:
         if self.final_obs:
             info["final_observation"] = self._state(final=True)
             info["final_count"] = self.world.final_obs["final_count"]
+        if self._norm_obs:
+            info["raw_vector_states"] = self.world.out["vector_states"]
         return info
+
+    def _rewards(self, rewards, info):
+        """normalise: the reward handed out is the normalised one (library-owned, rewritten by the next step)"""
+        if not self._norm_reward:
+            return rewards
+        info["raw_rewards"] = rewards
+        return self.world.normalise["norm_rewards"]
+
+    def normalise_training(self, on):
+        """True: steps and resets update the running statistics (the default); False: they only apply them (evaluation)"""
+        self.world.normalise_training(on)
+
+    def normalise_stats(self):
+        """the running statistics and returns as a dict of host values (``World.normalise_stats``); synchronises"""
+        return self.world.normalise_stats()
+
+    def load_normalise_stats(self, stats):
+        """what ``normalise_stats()`` returned, of this env or another one of the same shape; synchronises"""
+        self.world.load_normalise_stats(stats)
 
     def _actions(self, actions):
         if self.wrappers:  # the policy's output: indices [n] or float rows [n, act_dim], decoded on the device
@@ -424,13 +472,13 @@ class VecImageEnv:
         self._episodes += len(finished)
         info = {"dones_info": o["step_dones_info"], "is_clean": o["step_is_clean"], "arrive": o["step_is_arrives"],
                 "collision": o["step_is_collisions"], "all_down": self._all_down, "reset_envs": finished}
-        return self._state(), o["step_rewards"], o["step_dones"], self._info(info)
+        return self._state(), self._rewards(o["step_rewards"], info), o["step_dones"], self._info(info)
 
     def _step_device(self, actions):
         o = self.world.step_autoreset_device(self._actions(actions), self._spawn_cfg, self._device_seed0)
         info = {"dones_info": o["step_dones_info"], "is_clean": o["step_is_clean"], "arrive": o["step_is_arrives"],
                 "collision": o["step_is_collisions"], "all_down": self._all_down, "reset_envs": None}
-        return self._state(), o["step_rewards"], o["step_dones"], self._info(info)
+        return self._state(), self._rewards(o["step_rewards"], info), o["step_dones"], self._info(info)
 
     def step(self, actions):
         import torch
@@ -453,7 +501,7 @@ class VecImageEnv:
                 info["arrive"], info["collision"] = o["is_arrives"].clone(), o["is_collisions"].clone()
                 self.reset_envs(finished)
                 info["reset_envs"] = finished
-        return self._state(), rewards, dones, self._info(info)
+        return self._state(), self._rewards(rewards, info), dones, self._info(info)
 
     def world_maps(self):
         """the map each env's current episode runs on (numpy int32 ``[env_num]``); synchronises the stream"""

@@ -6,6 +6,7 @@ world.  All simulation work happens in ``csrc/libimgenv_hip.so``.
 """
 import ctypes as C
 import os
+import types
 
 import numpy as np
 
@@ -121,6 +122,7 @@ class World:
         self.final_obs = None  # enable_final_obs()
         self.rollout = None  # enable_rollout()
         self.minibatch = None  # enable_minibatch()
+        self.normalise = None  # enable_normalise()
         if self.n_maps > 1:
             rest = self.grids[1:]
             rc = self.lib.imgenv_maps_add(self.h, len(rest), rest.ctypes.data, rest.shape[1], rest.shape[2])
@@ -416,6 +418,61 @@ class World:
                                              "close_to_human": (np.uint8, (R,))}, "imgenv_obs_post_out")
         return self.obs_post
 
+    def enable_normalise(self, obs=True, reward=True, gamma=0.99, clip_obs=10.0, clip_reward=10.0, eps=1e-8):
+        """Running normalisation of ``vector_states`` and of the reward on the device (``imgenv_normalise_enable``; Stable-Baselines3's
+        VecNormalize): from now on every chain also keeps ``self.normalise`` -- zero-copy tensors over the library's memory:
+        ``norm_vector_states`` float32 ``[R, state_dim]`` and, after ``enable_stack`` with a state stack of depth >= 2,
+        ``norm_state_stack`` float32 ``[R, K * state_dim]`` (``obs``); ``norm_rewards`` float64 ``[R]`` (``reward``); and the state
+        itself, ``stats`` float64 ``[2, 4 + 2 state_dim]`` and ``returns`` float64 ``[2, R]``, whose current words
+        ``normalise_words()`` names.  Frozen robots count for nothing; a reset chain's rows count with their first observation.
+        At most two launches per chain; nothing synchronises.  Call it after ``enable_stack`` and before ``enable_final_obs`` /
+        ``enable_rollout`` with the normalised fields.  ValueError for a refused cfg or a second call."""
+        c = _cabi.make_normalise_cfg(obs, reward, gamma, clip_obs, clip_reward, eps)
+        no = _cabi.NormaliseOut()
+        self._call(self.lib.imgenv_normalise_enable(self.h, C.byref(c), C.byref(no)), "imgenv_normalise_enable")
+        R, D, K = no.n_local, no.state_dim, no.state_depth
+        self.normalise = self._views(no, {"norm_vector_states": (np.float32, (R, D)), "norm_state_stack": (np.float32, (R, K * D)),
+                                          "norm_rewards": (np.float64, (R,)), "stats": (np.float64, (2, 4 + 2 * D)),
+                                          "returns": (np.float64, (2, R))}, "imgenv_normalise_out")
+        self._norm_dims = (D, K)
+        return self.normalise
+
+    def _need_normalise(self):
+        if self.normalise is None:
+            raise RuntimeError("enable_normalise() was not called")
+
+    def _normalise_out(self):
+        self._need_normalise()
+        no = _cabi.NormaliseOut()
+        self._check(self.lib.imgenv_normalise_outputs(self.h, C.byref(no)), "imgenv_normalise_outputs")
+        return no
+
+    def normalise_words(self):
+        """``(stats_word, returns_word, training)``: which word of ``normalise["stats"]`` / ``["returns"]`` is current (host-side
+        counts: nothing synchronises)"""
+        no = self._normalise_out()
+        return no.stats_word, no.returns_word, bool(no.training)
+
+    def normalise_training(self, on):
+        """``imgenv_normalise_training``: True -- the chains from now on update the statistics; False -- they only apply them"""
+        self._need_normalise()
+        self._check(self.lib.imgenv_normalise_training(self.h, 1 if on else 0, self._stream()), "imgenv_normalise_training")
+
+    def normalise_stats(self):
+        """``imgenv_normalise_stats_get``: a dict of ``obs_count``, ``obs_mean`` / ``obs_var`` float64 ``[state_dim]``, ``ret_count``,
+        ``ret_mean``, ``ret_var`` and ``returns`` float64 ``[R]`` on the host, for a checkpoint.  SYNCHRONISES the device."""
+        self._need_normalise()
+        s, arrays = _cabi.make_normalise_stats(self._norm_dims[0], self.n_local)
+        self._call(self.lib.imgenv_normalise_stats_get(self.h, C.byref(s)), "imgenv_normalise_stats_get")
+        return dict(arrays, obs_count=s.obs_count, ret_count=s.ret_count, ret_mean=s.ret_mean, ret_var=s.ret_var)
+
+    def load_normalise_stats(self, stats):
+        """``imgenv_normalise_stats_set``: what ``normalise_stats()`` returned (of this handle or of a trainer's) becomes what the
+        next chain reads.  SYNCHRONISES the device.  ValueError for a refused value or another ``state_dim`` / ``R``."""
+        self._need_normalise()
+        s, arrays = _cabi.make_normalise_stats(self._norm_dims[0], self.n_local, stats)
+        self._call(self.lib.imgenv_normalise_stats_set(self.h, C.byref(s)), "imgenv_normalise_stats_set")
+
     def enable_final_obs(self, fields=None):
         """Final observations (``imgenv_final_obs_enable``): from now on every reset -- ``reset``, ``reset_worlds*``,
         ``step_autoreset``, ``step_autoreset_device`` -- first copies the rows it is about to overwrite, for the robots it covers,
@@ -425,7 +482,8 @@ class World:
         ``stack_sensor_maps`` / ``stack_vector_states`` / ``stack_lasers`` for the stacks of depth >= 2, shaped as ``self.stack``'s;
         ``"ped_vector_norm"`` (after ``enable_obs_post``) the normalised pedestrian vector.  One extra launch per reset chain, none
         per step; nothing synchronises.  Read-only; valid until ``close()``.  ValueError for refused fields or a second call with
-        other ones, RuntimeError for ``"stacks"`` / ``"ped_vector_norm"`` before their own enable call."""
+        other ones, RuntimeError for ``"stacks"`` / ``"ped_vector_norm"`` before their own enable call.  ``"norm_states"`` (after
+        ``enable_normalise``, ValueError before it) adds ``norm_vector_states`` / ``norm_state_stack``."""
         if fields is None:
             fields = [n for n in list(_cabi.FINAL_BITS)[:9] if n != "lasers" or self.cfg.use_laser]
         c = _cabi.make_final_obs_cfg(fields)
@@ -441,6 +499,11 @@ class World:
             arrays["ped_vector_norm"] = lay["ped_vector_states"]
             arrays["final_count"] = (np.int32, (R,))  # (uint32 in the library; torch has no arithmetic on it)
             self.final_obs = self._views(fo, arrays, "imgenv_final_obs_out")
+            if self.normalise is not None:  # "norm_states": the two fields' pointers are imgenv_normalise_out's
+                extra = {"final_" + name: (np.float32, tuple(self.normalise[name].shape)) for name in _cabi.ROLLOUT_NORM_FIELDS
+                         if name in self.normalise}
+                for name, t in self._views(self._normalise_out(), extra, "imgenv_normalise_out").items():
+                    self.final_obs[name[len("final_"):]] = t
         return self.final_obs
 
     def enable_rollout(self, horizon, final_capacity, fields=None):
@@ -452,7 +515,9 @@ class World:
         ``final_row`` int32 ``[F]`` and ``final_n`` int32 ``[2]`` (include/imgenv.h has the semantics).  ``fields``: names of
         ``_cabi.ROLLOUT_BITS``; None = the five single-frame fields (without ``lasers`` on a handle without a laser).  One extra
         launch per chain; nothing synchronises.  Read-only; valid until ``close()``.  ValueError for a refused cfg or a second
-        call with another one, RuntimeError for ``"stacks"`` / ``"ped_vector_norm"`` before their own enable call."""
+        call with another one, RuntimeError for ``"stacks"`` / ``"ped_vector_norm"`` before their own enable call.  After
+        ``enable_normalise``: ``"norm_states"`` stores ``norm_vector_states`` (and ``norm_state_stack``) like any field,
+        ``"norm_rewards"`` makes ``rewards`` the normalised ones (ValueError before it)."""
         if fields is None:
             fields = [n for n in list(_cabi.ROLLOUT_BITS)[:5] if n != "lasers" or self.cfg.use_laser]
         c = _cabi.make_rollout_cfg(horizon, final_capacity, fields)
@@ -473,6 +538,16 @@ class World:
                           dones_info=(np.int32, (T, R)), final_idx=(np.int32, (T + 1, R)), final_slot=(np.int32, (F,)),
                           final_row=(np.int32, (F,)), final_n=(np.int32, (2,)))  # (final_n: uint32 in the library)
             self.rollout = self._views(ro, arrays, "imgenv_rollout_out")
+            if self.normalise is not None:  # "norm_states": the two fields' pointers are imgenv_normalise_out's
+                no, extra = self._normalise_out(), {}
+                for name in _cabi.ROLLOUT_NORM_FIELDS:
+                    if name in self.normalise and getattr(no, "rollout_obs_" + name):
+                        shape = tuple(self.normalise[name].shape)
+                        rows[name] = (np.float32, shape)
+                        extra["rollout_obs_" + name] = (np.float32, (T + 1,) + shape)
+                        extra["rollout_final_" + name] = (np.float32, (F,) + shape[1:])
+                for name, t in self._views(no, extra, "imgenv_normalise_out").items():
+                    self.rollout[name[len("rollout_"):]] = t
             self.rollout_horizon, self.rollout_final_capacity = T, F
             self._rollout_rows = rows
         return self.rollout
@@ -534,6 +609,13 @@ class World:
                                      "norm": (np.float32, (2,))}, "imgenv_minibatch_out")
             rows = {"mb_" + name: (self._rollout_rows[name][0], tuple(self._rollout_rows[name][1][1:]))
                     for name in _cabi.ROLLOUT_FIELDS if "obs_" + name in (self.rollout or {}) and getattr(mo.buf[0], "mb_" + name)}
+            norm_ptrs = {}  # the normalised fields' buffers: imgenv_normalise_out.mb_norm_*
+            if self.normalise is not None:
+                no = self._normalise_out()
+                for name in _cabi.ROLLOUT_NORM_FIELDS:
+                    if getattr(no, "mb_" + name)[0]:
+                        rows["mb_" + name] = (np.float32, tuple(self._rollout_rows[name][1][1:]))
+                        norm_ptrs["mb_" + name] = [getattr(no, "mb_" + name)[b] for b in range(NB)]
             rows.update(mb_actions=(np.float32, (3,)), mb_rewards=(np.float32, ()), mb_dones=(np.uint8, ()), mb_dones_info=(np.int32, ()),
                         mb_index=(np.int32, ()), mb_weight=(np.float32, ()))
             arrays = {name: (dt, (B,) + shape) for name, (dt, shape) in rows.items()}
@@ -543,10 +625,11 @@ class World:
                 item = np.dtype(dt).itemsize
                 nbytes = int(np.prod(shape)) * item
                 pitch = (nbytes + 255) // 256 * 256
-                ptrs = [getattr(mo.buf[b], name) for b in range(NB)]
+                ptrs = norm_ptrs.get(name) or [getattr(mo.buf[b], name) for b in range(NB)]
                 if any(ptrs[b] != ptrs[0] + b * pitch for b in range(NB)):
                     raise RuntimeError("imgenv_minibatch_out.%s: the buffers do not lie side by side" % name)
-                span = self._views(mo.buf[0], {name: (dt, ((NB - 1) * pitch // item + nbytes // item,))}, "imgenv_minibatch_buffer")[name]
+                first = types.SimpleNamespace(**{name: ptrs[0]}) if name in norm_ptrs else mo.buf[0]
+                span = self._views(first, {name: (dt, ((NB - 1) * pitch // item + nbytes // item,))}, "imgenv_minibatch_buffer")[name]
                 strides, acc = [], 1
                 for d in reversed(shape):
                     strides.insert(0, acc)
@@ -802,6 +885,7 @@ class World:
     def close(self):
         if getattr(self, "h", None):
             self.episodes = self.episode_log = self.action_outputs = self.obs_post = self.final_obs = self.rollout = self.minibatch = None  # (views of memory the handle owns)
+            self.normalise = None
             self.lib.imgenv_destroy(self.h)
             self.h = None
 

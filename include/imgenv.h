@@ -757,6 +757,9 @@ int imgenv_obs_post_outputs(imgenv_t* h, imgenv_obs_post_out* out);
 #define IMGENV_FINAL_PED_NORM 4096     /* imgenv_obs_post_out.ped_vector_norm */
 #define IMGENV_FINAL_IMAGE_STATE 511   /* the nine fields of ImageState (state.py:4-28): the first nine bits */
 #define IMGENV_FINAL_ALL 8191
+#define IMGENV_FINAL_NORM_STATES 8192  /* imgenv_normalise_out.norm_vector_states and, where it exists, norm_state_stack: needs
+                                        * imgenv_normalise_enable() with IMGENV_NORM_OBS first (IMGENV_EINVAL otherwise); not part
+                                        * of IMGENV_FINAL_ALL */
 typedef struct imgenv_final_obs_cfg {
     int32_t struct_size;          /* sizeof(imgenv_final_obs_cfg) */
     int32_t fields;               /* IMGENV_FINAL_* bits, at least one */
@@ -835,6 +838,11 @@ int imgenv_final_obs_outputs(imgenv_t* h, imgenv_final_obs_out* out);
 #define IMGENV_ROLLOUT_PED_NORM 32          /* imgenv_obs_post_out.ped_vector_norm: needs imgenv_obs_post_enable with IMGENV_OBS_PED_NORM */
 #define IMGENV_ROLLOUT_STACKS 64            /* the whole [K][frame] rows of every stack of depth >= 2 of imgenv_stack_enable() */
 #define IMGENV_ROLLOUT_ALL 127
+/* the two below need imgenv_normalise_enable() first (IMGENV_EINVAL otherwise) and are not part of IMGENV_ROLLOUT_ALL */
+#define IMGENV_ROLLOUT_NORM_STATES 128      /* imgenv_normalise_out.norm_vector_states and, where it exists, norm_state_stack (IMGENV_NORM_OBS);
+                                             * the ring's pointers are imgenv_normalise_out.rollout_* / mb_norm_* */
+#define IMGENV_ROLLOUT_NORM_REWARDS 256     /* `rewards` holds imgenv_normalise_out.norm_rewards instead of step_rewards (IMGENV_NORM_REWARD);
+                                             * selects no field of its own: at least one other bit is needed */
 typedef struct imgenv_rollout_cfg {
     int32_t struct_size;          /* sizeof(imgenv_rollout_cfg) */
     int32_t horizon;              /* T >= 1 */
@@ -1017,6 +1025,89 @@ typedef struct imgenv_minibatch_args {
  * normalise out of range or a null scalars[s]; IMGENV_ESTATE for a stale or missing index or before imgenv_rollout_shuffle() on
  * this index. */
 int imgenv_rollout_minibatch(imgenv_t* h, const imgenv_minibatch_args* args, void* stream);
+
+/* ---- running normalisation of the observation vector and of the reward (Stable-Baselines3's VecNormalize / RunningMeanStd) ----
+ * Off by default: a handle that never calls imgenv_normalise_enable() launches what it launched before.  With it every chain ends
+ * with at most two more launches (k_norm_part, k_norm_apply; csrc/normalise.h has the order of every sum), behind the stacks and
+ * the observation post-processing and in front of the rollout storage, which may store their output.
+ * State, float64, the library's: obs_count, obs_mean[state_dim], obs_var[state_dim]; ret_count, ret_mean, ret_var; returns[R], the
+ * running discounted return of each robot's open episode.  Initial values: counts 1e-4, means 0, variances 1, returns 0.
+ *   a step chain, training on:  returns[r] = returns[r] * gamma + step_rewards[r] for the rows with step_is_clean != 0; the batch --
+ *     those rows' vector_states (float32 promoted) and new returns -- is reduced to (c, mean, M2) and merged into the running
+ *     triples (Chan: delta = bm - mean; tot = count + c; mean += delta * c / tot; var = (var * count + M2 + delta * delta * count *
+ *     c / tot) / tot); an empty batch leaves every bit; afterwards returns[r] = 0 where step_dones[r] is set;
+ *   a reset chain, training on: the batch is the vector_states of the rows it covers, all of them; their returns become 0; the
+ *     return statistics and norm_rewards are untouched;
+ *   every chain, with the updated statistics, for the rows it covers (a step: all, frozen or not):
+ *     norm_vector_states[r][d] = (float)clamp((x - obs_mean[d]) / sqrt(obs_var[d] + eps), -clip_obs, clip_obs), every frame of a
+ *     state stack of depth >= 2 likewise into norm_state_stack (zero padding is normalised like any value; only the newest frame
+ *     enters the statistics), and on a step norm_rewards[r] = clamp(step_rewards[r] / sqrt(ret_var + eps), -clip_reward, clip_reward);
+ *   training off (imgenv_normalise_training): only the last item; no statistic and no return changes.
+ * Every sum is taken in a fixed order without atomics: two runs give identical bits.  The arrays are no part of the output arena;
+ * read-only for the caller; stream order as for imgenv_out. */
+#define IMGENV_NORM_OBS 1
+#define IMGENV_NORM_REWARD 2
+typedef struct imgenv_normalise_cfg {
+    int32_t struct_size;          /* sizeof(imgenv_normalise_cfg) */
+    int32_t flags;                /* IMGENV_NORM_OBS | IMGENV_NORM_REWARD, at least one */
+    double gamma;                 /* the returns' discount, 0 .. 1 (SB3: 0.99) */
+    double clip_obs, clip_reward; /* > 0 (SB3: 10, 10) */
+    double eps;                   /* > 0 (SB3: 1e-8) */
+} imgenv_normalise_cfg;
+typedef struct imgenv_normalise_out {
+    int32_t struct_size;          /* on entry 0 or sizeof(imgenv_normalise_out) */
+    int32_t n_local;              /* R */
+    int32_t state_dim;
+    int32_t state_depth;          /* K of norm_state_stack, 0 without one */
+    float* norm_vector_states;    /* [R][state_dim]; NULL without IMGENV_NORM_OBS */
+    float* norm_state_stack;      /* [R][K][state_dim]; NULL without IMGENV_NORM_OBS or where imgenv_stack_enable() -- called BEFORE
+                                   * imgenv_normalise_enable() -- keeps no state stack of depth >= 2 */
+    double* norm_rewards;         /* [R]; NULL without IMGENV_NORM_REWARD */
+    double* stats;                /* [2][4 + 2 state_dim]: obs_count | ret_count | ret_mean | ret_var | obs_mean | obs_var; the
+                                   * word of this moment is stats_word (a host-side count, as imgenv_rollout_out.n) */
+    double* returns;              /* [2][R]; the word of this moment is returns_word; NULL without IMGENV_NORM_REWARD */
+    int32_t stats_word, returns_word;
+    int32_t training, reserved;
+    /* IMGENV_ROLLOUT_NORM_STATES, once imgenv_rollout_enable() / imgenv_rollout_minibatch_enable() have run (NULL before; ask
+     * imgenv_normalise_outputs() again): the ring's [T+1][R][row] and final list's [F][row] arrays of the two fields, and each
+     * minibatch buffer's [B][row] -- imgenv_rollout_out and imgenv_minibatch_buffer keep their layout */
+    float* rollout_obs_norm_vector_states;
+    float* rollout_obs_norm_state_stack;
+    float* rollout_final_norm_vector_states;
+    float* rollout_final_norm_state_stack;
+    float* mb_norm_vector_states[IMGENV_MB_MAX_BUFFERS];
+    float* mb_norm_state_stack[IMGENV_MB_MAX_BUFFERS];
+    /* IMGENV_FINAL_NORM_STATES, once imgenv_final_obs_enable() has run: [R][row] captures; imgenv_final_obs_out keeps its layout */
+    float* final_norm_vector_states;
+    float* final_norm_state_stack;
+} imgenv_normalise_out;
+/* host arrays for checkpoints: obs_mean / obs_var [state_dim], returns [n_rows] are the caller's (returns may be NULL) */
+typedef struct imgenv_normalise_stats {
+    int32_t struct_size;          /* sizeof(imgenv_normalise_stats) */
+    int32_t state_dim, n_rows, reserved;  /* must equal the handle's state_dim and R */
+    double obs_count, ret_count, ret_mean, ret_var;
+    double* obs_mean;
+    double* obs_var;
+    double* returns;
+} imgenv_normalise_stats;
+/* Legal at any time, after imgenv_stack_enable() where the normalised stack is wanted; the memory is the library's.  IMGENV_EINVAL
+ * for a wrong struct_size, no or unknown flags, a clip or eps that is not finite or not positive, gamma outside [0, 1], state_dim
+ * + 1 > 64, or a second call (enabling twice).  A robot-sharded handle (robot_begin / robot_end) may enable it: its statistics are over
+ * its LOCAL rows only -- every rank keeps its own, nothing is exchanged -- and a listed reset chain on it stays refused with
+ * IMGENV_EINVAL before anything is queued (imgenv_step_autoreset_device: "needs all robots of every world on this handle";
+ * csrc/tail_rows.h), which leaves every statistic and return as it was.  Training starts on.  `out` may be NULL. */
+int imgenv_normalise_enable(imgenv_t* h, const imgenv_normalise_cfg* cfg, imgenv_normalise_out* out);
+/* the same struct with the words of this moment.  IMGENV_ESTATE before imgenv_normalise_enable() */
+int imgenv_normalise_outputs(imgenv_t* h, imgenv_normalise_out* out);
+/* on != 0: the chains queued from now on update the statistics; 0: they only apply them (evaluation).  A host-side switch: nothing
+ * is launched, `stream` is unused.  IMGENV_ESTATE before imgenv_normalise_enable() */
+int imgenv_normalise_training(imgenv_t* h, int32_t on, void* stream);
+/* The statistics and the returns of this moment into / out of host memory.  Both SYNCHRONISE the device.  _set makes the next
+ * chain read the given values (a checkpoint, or a trainer's statistics handed to an evaluation handle); the normalised arrays
+ * change with that chain, not before.  IMGENV_EINVAL for a wrong struct_size, state_dim or n_rows, null obs_mean / obs_var, or
+ * (_set) a count, variance or return that is not finite, a count <= 0 or a variance < 0; IMGENV_ESTATE before imgenv_normalise_enable(). */
+int imgenv_normalise_stats_get(imgenv_t* h, imgenv_normalise_stats* stats);
+int imgenv_normalise_stats_set(imgenv_t* h, const imgenv_normalise_stats* stats);
 
 /* ---- map bank: several static maps in one handle, one of them per world and episode ----
  * The reference trains one policy over a set of maps: its trainer is started from several YAML files side by side

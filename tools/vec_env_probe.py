@@ -15,6 +15,8 @@ log on top of the statistics (imgenv_episode_log_enable: one more launch per res
 statistics / statistics / statistics + log over several rounds -- the device_reset variant runs a reset chain with every step, so
 its difference between the last two is what the log's launch costs a reset chain.  --final-obs-compare alternates the final
 observations (VecImageEnv(final_obs=True), imgenv_final_obs_enable: one more launch per reset chain) off / on in the same way.
+--normalise-compare alternates, with the device-side reset, the running normalisation of vector_states and rewards off / kept by
+the library (VecImageEnv(normalise={...}), imgenv_normalise_enable: two more launches per chain) / kept by TorchNormalise's torch ops.
 
 --rollout-compare runs device_reset steps three ways, one process per measurement, alternating over several rounds: no rollout
 storage, the library's (VecImageEnv(rollout=--horizon), imgenv_rollout_enable: one more launch per chain, a new window every
@@ -193,20 +195,58 @@ class TorchWrappers:
         return speeds, norm, close
 
 
+class TorchNormalise:
+    """VecNormalize's bookkeeping with torch ops on the arrays ``step`` hands out, as a trainer would write it: float64 running
+    mean / variance of vector_states and of the discounted returns over the rows that count, the normalised copies, no host
+    read.  (It cannot see the rows a device-side reset restarted: their first observations never enter its statistics.)"""
+
+    def __init__(self, env, gamma=0.99, clip_obs=10.0, clip_reward=10.0, eps=1e-8):
+        import torch
+        n, D = len(env), env.world.out["vector_states"].shape[1]
+        f64 = dict(dtype=torch.float64, device="cuda")
+        self.o = [torch.full((), 1e-4, **f64), torch.zeros(D, **f64), torch.ones(D, **f64)]
+        self.r = [torch.full((), 1e-4, **f64), torch.zeros((), **f64), torch.ones((), **f64)]
+        self.returns = torch.zeros(n, **f64)
+        self.gamma, self.clip_obs, self.clip_reward, self.eps = gamma, clip_obs, clip_reward, eps
+
+    @staticmethod
+    def _update(s, x, w):
+        c = w.sum()
+        bm = (x * w).sum(0) / c.clamp(min=1)
+        m2 = (((x - bm) ** 2) * w).sum(0)
+        delta, tot = bm - s[1], s[0] + c
+        s[1] = s[1] + delta * c / tot
+        s[2] = (s[2] * s[0] + m2 + delta * delta * s[0] * c / tot) / tot
+        s[0] = tot
+
+    def push(self, state, rew, dones, info):
+        import torch
+        w = info["is_clean"].to(torch.float64)
+        x = state.vector_states.to(torch.float64)
+        self.returns = torch.where(w > 0, self.returns * self.gamma + rew, self.returns)
+        self._update(self.o, x, w[:, None])
+        self._update(self.r, self.returns, w)
+        self.returns = torch.where(dones > 0, torch.zeros_like(self.returns), self.returns)
+        obs = ((x - self.o[1]) / torch.sqrt(self.o[2] + self.eps)).clamp(-self.clip_obs, self.clip_obs).float()
+        return obs, (rew / torch.sqrt(self.r[2] + self.eps)).clamp(-self.clip_reward, self.clip_reward)
+
+
 def stack_depths(stack):
     """(image, state, laser) YAML keys -> effective depths (base.py:103-105)"""
     return (max(stack[0], 0), max(stack[1], 0), max(stack[2], 1) if stack[2] >= 0 else 0)
 
 
 def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, natives=(False, True, "device"), stack=None,
-            torch_stack=False, episodes=None, wrappers=None, final_obs=False):
+            torch_stack=False, episodes=None, wrappers=None, final_obs=False, normalise=None):
     """robot-steps/s of VecImageEnv over `steps` steps, after the envs have drifted out of phase.  ``stack`` = (image_batch,
     state_batch, laser_batch): with the library's frame stacks, or (``torch_stack``) the same kept by torch ops on top;
     ``episodes`` = "library" | "torch" | "log": with the per-robot episode statistics, kept by the library or by ``TorchEpisodes``,
     or the library's with the episode log (a ring of 65536 records) on top;
     ``wrappers`` = (kind, by): kind "table" | "clip", by "none" (pre-decoded actions, nothing enabled) | "library"
     (``wrappers=True`` fed the raw output) | "torch" (``TorchWrappers`` fed the raw output); ``final_obs``: with the final
-    observations kept by the library (``VecImageEnv(final_obs=True)``: one more launch per reset chain)"""
+    observations kept by the library (``VecImageEnv(final_obs=True)``: one more launch per reset chain); ``normalise`` =
+    "library" | "torch": with the running normalisation of vector_states and rewards, kept by the library
+    (``VecImageEnv(normalise={})``) or by ``TorchNormalise``"""
     import torch
     from img_env_amd import worldgen
     from img_env_amd.vec_env import VecImageEnv
@@ -221,7 +261,9 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
         env = VecImageEnv(cfg, env_num=envs, seed=5, native_spawn=bool(native), device_reset=native == "device",
                           stack=stack is not None and not torch_stack, episode_stats=episodes in ("library", "log"),
                           episode_log=(1 << 16) if episodes == "log" else 0,
-                          wrappers=wrappers is not None and wrappers[1] == "library", final_obs=final_obs)
+                          wrappers=wrappers is not None and wrappers[1] == "library", final_obs=final_obs,
+                          normalise=dict(obs=True, reward=True) if normalise == "library" else None)
+        tn = TorchNormalise(env) if normalise == "torch" else None
         te = TorchEpisodes(env) if episodes == "torch" else None
         ts = TorchStack(env, stack_depths(stack)) if stack is not None and torch_stack else None
         n = len(env)
@@ -248,6 +290,10 @@ def measure(envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, n
 
         def step(a):
             nonlocal kept
+            if tn is not None:
+                res = env.step(a)
+                kept = tn.push(res[0], res[1], res[2], res[3])
+                return res
             if tw is None:
                 return env.step(a)
             a = tw.action(a)
@@ -408,6 +454,26 @@ def compare_final_obs(args, rounds=3):
         summary.append(row)
     return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, steps=args.steps, time_max=args.time_max,
                 rounds=rounds, runs=runs, summary=summary)
+
+
+def compare_normalise(args, rounds=3):
+    """the running normalisation off / kept by the library / kept with torch ops, alternating, `rounds` times in one process, with
+    the device-side reset: the feature-off rounds are the baseline"""
+    runs = []
+    for rnd in range(rounds):
+        for mode in ("off", "library", "torch"):
+            r = measure(args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max, ("device",),
+                        normalise=None if mode == "off" else mode)["device_reset"]
+            runs.append(dict(round=rnd, mode=mode, variant="device_reset", us_per_step=r["us_per_step"], env_resets_per_step=r["env_resets_per_step"]))
+            print(json.dumps(runs[-1]), flush=True)
+    row = dict(variant="device_reset")
+    for mode in ("off", "library", "torch"):
+        v = [r["us_per_step"] for r in runs if r["mode"] == mode]
+        row[mode] = dict(us_per_step_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
+    row["added_us_library"] = row["library"]["median"] - row["off"]["median"]
+    row["added_us_torch"] = row["torch"]["median"] - row["off"]["median"]
+    return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, steps=args.steps, time_max=args.time_max,
+                rounds=rounds, runs=runs, summary=[row])
 
 
 def compare_wrappers(args, rounds=3):
@@ -872,6 +938,8 @@ def main():
     ap.add_argument("--torch-wrappers", action="store_true", help="with --wrappers: the same kept with torch ops on a plain VecImageEnv")
     ap.add_argument("--wrappers-compare", action="store_true",
                     help="pre-decoded actions / library / torch, alternating over --rounds rounds, table and clip")
+    ap.add_argument("--normalise-compare", action="store_true",
+                    help="running normalisation off / library / torch ops, alternating over --rounds rounds, device-side reset")
     ap.add_argument("--tracks-compare", action="store_true",
                     help="dataset scene: explicit track batches from a Python loop / native_spawn with a track bank / device_reset with "
                          "it, alternating over --rounds rounds (use --peds 10)")
@@ -938,6 +1006,13 @@ def main():
         return
     if args.wrappers_compare:
         res = compare_wrappers(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
+        return
+    if args.normalise_compare:
+        res = compare_normalise(args, args.rounds)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(res, fh, indent=1)

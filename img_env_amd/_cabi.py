@@ -259,6 +259,37 @@ def make_actions_cfg(table=None, clip=None, n_cols=2):
     return c, keep
 
 
+#: the policy head (imgenv_policy_enable; csrc/policy.h)
+POLICY_CATEGORICAL, POLICY_GAUSSIAN = 0, 1
+POLICY_STORE = 1  # imgenv_policy_cfg.flags
+POLICY_DETERMINISTIC, POLICY_LOG_STD_PER_ROW, POLICY_NO_STORE, POLICY_VALUE_ONLY = 1, 2, 4, 8  # imgenv_policy_args.flags
+#: imgenv_policy_out's arrays, in the struct's order
+POLICY_ARRAYS = ("index", "raw", "logp", "entropy", "pol_raw", "pol_logp", "pol_value")
+
+
+class PolicyCfg(C.Structure):
+    _fields_ = [("struct_size", _i32), ("kind", _i32), ("flags", _i32), ("reserved", _i32), ("seed", C.c_uint64)]
+
+
+class PolicyOut(C.Structure):
+    _fields_ = [("struct_size", _i32), ("n_local", _i32), ("n_params", _i32), ("horizon", _i32)] + [(name, C.c_void_p) for name in POLICY_ARRAYS]
+
+
+class PolicyArgs(C.Structure):
+    _fields_ = [("struct_size", _i32), ("flags", _i32), ("draw", C.c_uint64), ("params", C.c_void_p), ("log_std", C.c_void_p),
+                ("values", C.c_void_p)]
+
+
+def make_policy_cfg(kind, seed=0, store=False):
+    """``imgenv_policy_cfg``: ``kind`` is POLICY_CATEGORICAL / POLICY_GAUSSIAN or "categorical" / "gaussian" """
+    c = PolicyCfg()
+    c.struct_size = C.sizeof(PolicyCfg)
+    c.kind = {"categorical": POLICY_CATEGORICAL, "gaussian": POLICY_GAUSSIAN}.get(kind, kind)
+    c.flags = POLICY_STORE if store else 0
+    c.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return c
+
+
 class ObsPostCfg(C.Structure):
     _fields_ = [("struct_size", _i32), ("flags", _i32), ("avg", _f64 * 7), ("std", _f64 * 7), ("close_dist", _f64)]
 
@@ -618,6 +649,7 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_episodes_enable", "imgenv_episodes_outputs", "imgenv_episodes_clear",
            "imgenv_episode_log_enable", "imgenv_episode_log_outputs", "imgenv_episode_log_read",
            "imgenv_actions_enable", "imgenv_actions_outputs", "imgenv_actions_decode", "imgenv_obs_post_enable", "imgenv_obs_post_outputs",
+           "imgenv_policy_enable", "imgenv_policy_outputs", "imgenv_policy_sample",
            "imgenv_final_obs_enable", "imgenv_final_obs_outputs",
            "imgenv_rollout_enable", "imgenv_rollout_outputs", "imgenv_rollout_begin", "imgenv_rollout_gae",
            "imgenv_rollout_minibatch_enable", "imgenv_rollout_minibatch_outputs", "imgenv_rollout_index", "imgenv_rollout_stats",
@@ -688,6 +720,9 @@ def bind(lib):
     lib.imgenv_actions_enable.argtypes = [C.c_void_p, C.POINTER(ActionsCfg), C.POINTER(ActionsOut)]
     lib.imgenv_actions_outputs.argtypes = [C.c_void_p, C.POINTER(ActionsOut)]
     lib.imgenv_actions_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.imgenv_policy_enable.argtypes = [C.c_void_p, C.POINTER(PolicyCfg), C.POINTER(PolicyOut)]
+    lib.imgenv_policy_outputs.argtypes = [C.c_void_p, C.POINTER(PolicyOut)]
+    lib.imgenv_policy_sample.argtypes = [C.c_void_p, C.POINTER(PolicyArgs), C.c_void_p]
     lib.imgenv_obs_post_enable.argtypes = [C.c_void_p, C.POINTER(ObsPostCfg), C.POINTER(ObsPostOut)]
     lib.imgenv_obs_post_outputs.argtypes = [C.c_void_p, C.POINTER(ObsPostOut)]
     lib.imgenv_final_obs_enable.argtypes = [C.c_void_p, C.POINTER(FinalObsCfg), C.POINTER(FinalObsOut)]

@@ -27,6 +27,7 @@
 #include "episodes.h"
 #include "episode_log.h"
 #include "actions.h"
+#include "policy.h"
 #include "obs_post.h"
 #include "final_obs.h"
 #include "rollout.h"
@@ -248,7 +249,12 @@ struct imgenv {
     imgenv_actions_cfg act_cfg;  // (its table pointer is not kept: act_table is the copy)
     std::vector<float> act_table;
     imgenv_actions_out act_out;
-    int decode_launches = 0;     // k_actions launches since the last step: they count with the step that consumes them
+    int decode_launches = 0;     // k_actions / k_policy launches since the last step: they count with the step that consumes them
+    // the policy head (include/imgenv.h: imgenv_policy_enable; csrc/policy.h)
+    bool pol_on = false;
+    PolicyDev pol;               // what every launch shares; params, draw, flags and the slot's pointers are the call's
+    imgenv_policy_cfg pol_cfg;
+    imgenv_policy_out pol_out;
     // observation post-processing (imgenv_obs_post_enable; csrc/obs_post.h)
     bool post_on = false;
     ObsPostDev post;
@@ -4215,6 +4221,124 @@ extern "C" int imgenv_actions_decode(imgenv_t* h, const void* raw, int32_t dtype
     k_actions_for(dtype, h->act_cfg.mode)<<<dim3(g.grid), dim3(g.block), 0, (hipStream_t)stream>>>(a);
     HIPCHK(hipGetLastError());
     h->decode_launches += 1;
+    return IMGENV_OK;
+}
+
+// ---- the policy head (include/imgenv.h; the kernels are csrc/policy.h) ----
+extern "C" int imgenv_policy_enable(imgenv_t* h, const imgenv_policy_cfg* c, imgenv_policy_out* out) {
+    // (the cfg first, as above)
+    RTRY(enable_args(c, "imgenv_policy_cfg", out, "imgenv_policy_out"));
+    if (c->kind != IMGENV_POLICY_CATEGORICAL && c->kind != IMGENV_POLICY_GAUSSIAN) FAIL(IMGENV_EINVAL, "imgenv_policy_cfg.kind %d", c->kind);
+    if (c->flags & ~IMGENV_POLICY_STORE) FAIL(IMGENV_EINVAL, "imgenv_policy_cfg.flags %d", c->flags);
+    if (c->reserved != 0) FAIL(IMGENV_EINVAL, "imgenv_policy_cfg.reserved %d", c->reserved);
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (h->pol_on) {
+        const imgenv_policy_cfg& o = h->pol_cfg;
+        if (c->kind != o.kind || c->flags != o.flags || c->seed != o.seed)
+            FAIL(IMGENV_EINVAL, "imgenv_policy_enable: the handle already has a policy head with another cfg");
+        if (out) *out = h->pol_out;
+        return IMGENV_OK;
+    }
+    if (!h->act_on) FAIL(IMGENV_ESTATE, "imgenv_policy_enable before imgenv_actions_enable");
+    const bool cat = c->kind == IMGENV_POLICY_CATEGORICAL;
+    if (h->act_cfg.mode != (cat ? IMGENV_ACTIONS_TABLE : IMGENV_ACTIONS_CLIP))
+        FAIL(IMGENV_EINVAL, "imgenv_policy_enable: a %s head needs imgenv_actions_enable in %s mode", cat ? "categorical" : "Gaussian", cat ? "TABLE" : "CLIP");
+    const bool store = (c->flags & IMGENV_POLICY_STORE) != 0;
+    if (store && !h->roll_on) FAIL(IMGENV_ESTATE, "imgenv_policy_enable: IMGENV_POLICY_STORE before imgenv_rollout_enable");
+    const size_t RL = (size_t)h->RL, T = store ? (size_t)h->roll_cfg.horizon : 0;
+    const int n_params = cat ? h->act_cfg.n_table : h->act_cfg.n_cols;
+    const size_t cols = cat ? 1 : (size_t)n_params;
+    // one block, every array on a 256-byte boundary, zeroed; nothing of the handle changes before it is there
+    size_t total = 0;
+    auto carve = [&](size_t bytes) {
+        const size_t at = total;
+        total = align256(total + bytes);
+        return at;
+    };
+    const size_t off_index = carve(cat ? RL * 4 : 0), off_raw = carve(cat ? 0 : RL * cols * 4), off_logp = carve(RL * 4), off_ent = carve(RL * 4);
+    const size_t off_praw = carve(cols * T * RL * 4), off_plogp = carve(T * RL * 4), off_pvalue = carve(store ? (T + 1) * RL * 4 : 0);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    unsigned char* block = nullptr;
+    DevTxn<HipApi> txn;
+    if (!txn.room(&block, total, 0)) FAIL(txn.code(), "imgenv_policy_enable: %s", txn.error());
+    txn.commit(h->allocs);
+    imgenv_policy_out o = {};
+    o.n_params = n_params;
+    o.horizon = (int32_t)T;
+    if (cat) o.index = (int32_t*)(block + off_index);
+    else o.raw = (float*)(block + off_raw);
+    o.logp = (float*)(block + off_logp);
+    o.entropy = (float*)(block + off_ent);
+    if (store) {
+        o.pol_raw = (float*)(block + off_praw);
+        o.pol_logp = (float*)(block + off_plogp);
+        o.pol_value = (float*)(block + off_pvalue);
+    }
+    PolicyDev p;
+    memset(&p, 0, sizeof(p));
+    const ActionsDev& a = h->act;
+    p.table = a.table; p.actions = a.actions; p.speeds = a.speeds; p.n_bad = a.n_bad; p.clean_state = a.clean_state;
+    for (int i = 0; i < 3; i++) { p.lo[i] = a.lo[i]; p.hi[i] = a.hi[i]; }
+    p.index = o.index; p.raw = o.raw; p.logp = o.logp; p.entropy = o.entropy;
+    p.st_col = T * RL;
+    p.g0 = (unsigned long long)h->r0;
+    p.seed_lo = (uint32_t)c->seed; p.seed_hi = (uint32_t)(c->seed >> 32);
+    p.A = cat ? n_params : 0; p.C = cat ? 0 : n_params; p.RL = h->RL;
+    h->pol = p;
+    h->pol_cfg = *c;
+    return enable_done(h, o, &imgenv::pol_out, &imgenv::pol_on, out);
+}
+
+extern "C" int imgenv_policy_outputs(imgenv_t* h, imgenv_policy_out* out) {
+    return feature_outputs(h, &imgenv::pol_on, &imgenv::pol_out, out, "imgenv_policy_enable");
+}
+
+typedef void (*PolicyKernel)(const PolicyDev);
+static PolicyKernel k_policy_cat_for(int G) {
+    PolicyKernel k = nullptr;
+    pick([&](auto g) { k = k_policy_cat<decltype(g)::value>; }, OneOf<1, 4, 16, 64>{G});
+    return k;
+}
+extern "C" int imgenv_policy_sample(imgenv_t* h, const imgenv_policy_args* g, void* stream) {
+    if (!h || !g) FAIL(IMGENV_EINVAL, "null argument");
+    if (g->struct_size != (int32_t)sizeof(imgenv_policy_args)) FAIL(IMGENV_EINVAL, "imgenv_policy_args.struct_size %d (this library's is %d)", g->struct_size, (int)sizeof(imgenv_policy_args));
+    const int32_t known = IMGENV_POLICY_DETERMINISTIC | IMGENV_POLICY_LOG_STD_PER_ROW | IMGENV_POLICY_NO_STORE | IMGENV_POLICY_VALUE_ONLY;
+    if (g->flags & ~known) FAIL(IMGENV_EINVAL, "imgenv_policy_args.flags %d", g->flags);
+    if (!h->pol_on) FAIL(IMGENV_ESTATE, "imgenv_policy_enable was not called");
+    if (!h->has_reset) FAIL(IMGENV_ESTATE, "imgenv_policy_sample before the first reset");
+    const bool cat = h->pol_cfg.kind == IMGENV_POLICY_CATEGORICAL, value_only = (g->flags & IMGENV_POLICY_VALUE_ONLY) != 0;
+    const bool stores = (h->pol_cfg.flags & IMGENV_POLICY_STORE) && !(g->flags & IMGENV_POLICY_NO_STORE);
+    auto misaligned = [](const void* p) { return (uintptr_t)p % 4 != 0; };
+    if (value_only) {
+        if (g->flags != IMGENV_POLICY_VALUE_ONLY) FAIL(IMGENV_EINVAL, "imgenv_policy_args.flags %d: IMGENV_POLICY_VALUE_ONLY stands alone", g->flags);
+        if (!(h->pol_cfg.flags & IMGENV_POLICY_STORE)) FAIL(IMGENV_ESTATE, "imgenv_policy_sample: IMGENV_POLICY_VALUE_ONLY on a head without IMGENV_POLICY_STORE");
+        if (!g->values || misaligned(g->values)) FAIL(IMGENV_EINVAL, "imgenv_policy_args.values is null or misaligned");
+    } else {
+        if (!g->params || misaligned(g->params)) FAIL(IMGENV_EINVAL, "imgenv_policy_args.params is null or misaligned");
+        if (!cat && (!g->log_std || misaligned(g->log_std))) FAIL(IMGENV_EINVAL, "imgenv_policy_args.log_std is null or misaligned");
+        if (cat && (g->flags & IMGENV_POLICY_LOG_STD_PER_ROW)) FAIL(IMGENV_EINVAL, "imgenv_policy_args.flags: IMGENV_POLICY_LOG_STD_PER_ROW on a categorical head");
+        if (g->values && misaligned(g->values)) FAIL(IMGENV_EINVAL, "imgenv_policy_args.values is misaligned");
+    }
+    PolicyDev p = h->pol;
+    if (stores || value_only) {
+        // the slot: the rollout cursor as the host holds it (the state the window's next transition starts from)
+        const int n = h->roll_begun ? h->roll_n : -1, T = h->roll_cfg.horizon;
+        if (n < 0 || n > T || (n == T && !value_only))
+            FAIL(IMGENV_ESTATE, "imgenv_policy_sample: slot %d of a window of %d (imgenv_rollout_begin starts the next one)", n, T);
+        const size_t at = (size_t)n * (size_t)h->RL;
+        if (!value_only) { p.st_raw = h->pol_out.pol_raw + at; p.st_logp = h->pol_out.pol_logp + at; }
+        p.st_value = h->pol_out.pol_value + at;
+    }
+    p.params = g->params; p.log_std = g->log_std; p.values = g->values;
+    p.draw_lo = (uint32_t)g->draw; p.draw_hi = (uint32_t)(g->draw >> 32);
+    p.det = (g->flags & IMGENV_POLICY_DETERMINISTIC) ? 1 : 0;
+    p.ls_per_row = (g->flags & IMGENV_POLICY_LOG_STD_PER_ROW) ? 1 : 0;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const LaunchShape s = plan_policy_launch(h->plan, value_only ? 0 : p.A);
+    const PolicyKernel k = value_only ? k_policy_value : cat ? k_policy_cat_for(plan_policy_group(p.A)) : k_policy_gauss;
+    k<<<dim3(s.grid), dim3(s.block), 0, (hipStream_t)stream>>>(p);
+    HIPCHK(hipGetLastError());
+    if (!value_only) h->decode_launches += 1;  // (the values-only call belongs to no step)
     return IMGENV_OK;
 }
 

@@ -57,6 +57,8 @@
 #define NORM_MAX_COLS 64     // state_dim + 1 (the return) columns at most: the columns of a row lie in one wavefront
 #define NORM_MAX_BLOCKS 1024
 #define ACT_BLOCK 256       // k_actions: one lane per local robot
+#define POL_BLOCK 256       // k_policy (policy.h): a group of 1, 4, 16 or 64 lanes per local robot
+#define POL_REG 16          // logits a lane of k_policy keeps in registers; a longer block of the row is re-read
 #define OBS_POST_BLOCK 256  // k_obs_post: one lane per element of a robot's ped_vector row
 #define OBS_POST_MAX_BLOCKS 2048
 #define TRACKS_BLOCK 256    // k_tracks_install: one workgroup per world of the chain
@@ -525,6 +527,16 @@ inline LaunchShape plan_norm_apply_launch(const PlanHandle& h, const PlanChain& 
 // imgenv_actions_decode (actions.h): one lane per local robot, every wavefront whole (the ballot that counts bad rows runs on all
 // 64 lanes), no cap and no stride: 2^19 robots are 2048 blocks
 inline LaunchShape plan_actions_launch(const PlanHandle& h) { return {(unsigned)((h.RL + ACT_BLOCK - 1) / ACT_BLOCK), ACT_BLOCK, 0}; }
+// imgenv_policy_sample (policy.h).  Categorical over A logits: a group of G lanes per local robot, the smallest of 1, 4, 16, 64 that
+// leaves a lane at most POL_REG logits (which it then keeps in registers); from A = 1025 on G stays 64 and the lanes re-read
+// their ceil(A / 64) logits.  A group never straddles a wavefront (G divides 64) and every wavefront is whole.  Gaussian and the
+// values-only call: one lane per robot (n_logits 0).
+inline constexpr int plan_policy_group(int n_logits) { return n_logits <= POL_REG ? 1 : n_logits <= 4 * POL_REG ? 4 : n_logits <= 16 * POL_REG ? 16 : 64; }
+inline constexpr int plan_policy_per_lane(int n_logits) { return (n_logits + plan_policy_group(n_logits) - 1) / plan_policy_group(n_logits); }
+inline LaunchShape plan_policy_launch(const PlanHandle& h, int n_logits) {
+    const size_t lanes = (size_t)h.RL * (size_t)plan_policy_group(n_logits);
+    return {(unsigned)((lanes + POL_BLOCK - 1) / POL_BLOCK), POL_BLOCK, 0};
+}
 
 // ---------------------------------------------------------------------------------------- resets
 // Device half of a host-side reset, for every world or the n worlds listed: one upload launch (segment copies | map restore |

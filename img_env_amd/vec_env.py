@@ -43,17 +43,23 @@ class VecImageEnv:
     ``rollout_minibatches(scalars, seed, normalise)``.
     ``normalise=dict(...)``: running normalisation of ``vector_states`` and of the reward inside the library (VecNormalize): the
     state and the reward handed out are the normalised ones, ``info`` gains ``raw_vector_states`` and ``raw_rewards``.
+    ``policy=dict(seed=s)`` (with ``wrappers=True``): the action sampled from the network's logits (or mean and log-std) inside
+    the library: ``policy_sample(...)``, ``policy_step(...)``, ``policy_value(values)``, ``policy_draw``.
     """
 
     def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False,
                  map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3, wrappers=False,
                  ped_tracks=None, tracks_policy="keep", tracks_repeat=1, info_track_sets=False, scenarios=None, scenario_policy="queue",
                  episode_log=0, final_obs=False, rollout=0, rollout_final=None, rollout_fields=None, minibatch=0, minibatch_buffers=1,
-                 normalise=None):
+                 normalise=None, policy=None):
         import torch
         from .world import World
         if int(minibatch or 0) > 0 and int(rollout or 0) <= 0:
             raise ValueError("minibatch=B needs rollout=T")
+        if policy is not None and not wrappers:
+            raise ValueError("policy=dict(seed=s) needs wrappers=True")
+        if policy is not None and set(policy) - {"seed"}:
+            raise ValueError("policy: unknown %s (known: seed)" % sorted(set(policy) - {"seed"}))
         self.cfg = cfg
         self.env_num = int(env_num if env_num is not None else cfg.get("env_num", 1))
         # ped_tracks: the recorded crowds of ``ped_sim.type: dataset`` as a bank inside the handle (imgenv_tracks_add) -- a list of
@@ -251,6 +257,60 @@ class VecImageEnv:
         self.minibatch_batch = int(minibatch or 0)
         if self.minibatch_batch > 0:
             self.world.enable_minibatch(self.minibatch_batch, int(minibatch_buffers))
+        # policy=dict(seed=s) (with wrappers=True): the hop from the network's output to the action inside the library
+        # (imgenv_policy_enable) -- categorical over cfg["discrete_actions"] where discrete_action is True, a diagonal Gaussian over
+        # cfg["continuous_actions"] where not.  policy_sample() draws the action from logits / mean and log_std with a counter-based
+        # generator keyed by (seed, policy_draw, robot), hands out its log-probability and entropy and leaves the decoded rows
+        # where ``step`` would have put them; policy_step() is that and the step in one call; with rollout=T the action, its
+        # log-probability and the value are kept in the window's slot (rollout()["pol_raw" | "pol_logp" | "pol_value"]) and
+        # policy_value() adds the bootstrap value.  One launch instead of the decode's; nothing synchronises.  Opt-in: None
+        # allocates and launches nothing.
+        self.policy = dict(policy) if policy is not None else None
+        self.policy_draw = 0  # the next call's draw number: part of a checkpoint, settable
+        self._sampled = None
+        if self.policy is not None:
+            self._policy_cat = bool(cfg.get("discrete_action"))
+            self.world.enable_policy("categorical" if self._policy_cat else "gaussian", int(self.policy.get("seed", 0)),
+                                     store=self.rollout_horizon > 0)
+
+    def _need_policy(self):
+        if self.policy is None:
+            raise RuntimeError("VecImageEnv was made without policy=dict(seed=s)")
+
+    def policy_sample(self, logits=None, mean=None, log_std=None, values=None, deterministic=False, store=True):
+        """The action of every robot from the network's output: ``logits`` float32 ``[n, A]`` (discrete_action: True) or ``mean``
+        ``[n, C]`` and ``log_std`` ``[C]`` / ``[n, C]``; ``values`` float32 ``[n]`` or None is kept with it where ``rollout=T``
+        stores (``store=False``: an evaluation call that leaves the window alone).  Returns ``dict(actions, index | raw, logp,
+        entropy)``: library-owned tensors, rewritten by the next call.  Uses draw number ``policy_draw`` and advances it."""
+        self._need_policy()
+        if (logits is None) != (not self._policy_cat):
+            raise ValueError("policy_sample: %s" % ("logits" if self._policy_cat else "mean and log_std"))
+        w = self.world
+        actions = w.policy_sample(logits if self._policy_cat else mean, log_std, values, draw=self.policy_draw,
+                                  deterministic=deterministic, store=store)
+        self.policy_draw += 1
+        key = "index" if self._policy_cat else "raw"
+        return {"actions": actions, key: w.policy[key], "logp": w.policy["logp"], "entropy": w.policy["entropy"]}
+
+    def policy_step(self, logits=None, mean=None, log_std=None, values=None, deterministic=False):
+        """``policy_sample`` and ``step`` on the sampled actions, without a second decode: ``step``'s tuple, ``info["policy"]`` is
+        what ``policy_sample`` returns"""
+        sampled = self.policy_sample(logits, mean, log_std, values, deterministic)
+        self._sampled = sampled["actions"]
+        try:
+            state, rewards, dones, info = self.step(None)
+        finally:
+            self._sampled = None
+        info["policy"] = sampled
+        return state, rewards, dones, info
+
+    def policy_value(self, values):
+        """``values`` float32 ``[n]`` into ``rollout()["pol_value"][t]``, t the transitions stored so far: after the window's last
+        step, the bootstrap value of the state it led to (``IMGENV_POLICY_VALUE_ONLY``)"""
+        self._need_policy()
+        if self.rollout_horizon <= 0:
+            raise RuntimeError("VecImageEnv was made without rollout=T")
+        self.world.policy_value(values)
 
     def rollout(self):
         """``{"n": transitions stored, "resets": reset chains stored, **World.rollout}``: the device tensors as they are -- no
@@ -258,7 +318,10 @@ class VecImageEnv:
         if self.rollout_horizon <= 0:
             raise RuntimeError("VecImageEnv was made without rollout=T")
         n, resets = self.world.rollout_cursor()
-        return dict(self.world.rollout, n=n, resets=resets)
+        out = dict(self.world.rollout, n=n, resets=resets)
+        if self.policy is not None:  # the policy head's columns of the same window
+            out.update({k: t for k, t in self.world.policy.items() if k.startswith("pol_")})
+        return out
 
     def rollout_begin(self):
         """start the next window: the last slot becomes slot 0 (``imgenv_rollout_begin``)"""
@@ -458,6 +521,8 @@ class VecImageEnv:
         self.world.load_normalise_stats(stats)
 
     def _actions(self, actions):
+        if self._sampled is not None:  # policy_step: the policy head has already written the decoded rows
+            return self._sampled
         if self.wrappers:  # the policy's output: indices [n] or float rows [n, act_dim], decoded on the device
             return self.world.decode_actions(actions)
         if isinstance(actions, (list, tuple)) and len(actions) and isinstance(actions[0], ContinuousAction):

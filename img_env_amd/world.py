@@ -118,6 +118,7 @@ class World:
         self.episode_log = None  # enable_episode_log()
         self.episode_log_capacity = 0
         self.action_outputs = None  # enable_actions()
+        self.policy = None  # enable_policy()
         self.obs_post = None  # enable_obs_post()
         self.final_obs = None  # enable_final_obs()
         self.rollout = None  # enable_rollout()
@@ -401,6 +402,82 @@ class World:
         self._raw_actions = raw
         self._call(self.lib.imgenv_actions_decode(self.h, C.c_void_p(raw.data_ptr()), code, self._stream()), "imgenv_actions_decode")
         return self.action_outputs["actions"]
+
+    def enable_policy(self, kind, seed=0, store=False):
+        """The policy head (``imgenv_policy_enable``; needs ``enable_actions`` first -- a table for ``"categorical"``, clip ranges
+        for ``"gaussian"`` -- and, with ``store``, ``enable_rollout``).  ``self.policy`` maps ``index`` int32 ``[R]`` (categorical)
+        or ``raw`` float32 ``[R, C]`` (Gaussian), ``logp`` and ``entropy`` float32 ``[R]`` and, with ``store``, ``pol_raw`` float32
+        ``[C', T, R]``, ``pol_logp`` ``[T, R]`` and ``pol_value`` ``[T + 1, R]`` to zero-copy tensors over the library's memory,
+        filled by ``policy_sample``.  Read-only; valid until ``close()``.  ValueError for a refused cfg or a second call with
+        another one, RuntimeError before ``enable_actions`` / ``enable_rollout``."""
+        c = _cabi.make_policy_cfg(kind, seed, store)
+        po = _cabi.PolicyOut()
+        self._call(self.lib.imgenv_policy_enable(self.h, C.byref(c), C.byref(po)), "imgenv_policy_enable")
+        if self.policy is None:
+            R, n, T = po.n_local, po.n_params, po.horizon
+            cat = c.kind == _cabi.POLICY_CATEGORICAL
+            arrays = dict(index=(np.int32, (R,)), raw=(np.float32, (R, n)), logp=(np.float32, (R,)), entropy=(np.float32, (R,)),
+                          pol_raw=(np.float32, (1 if cat else n, T, R)), pol_logp=(np.float32, (T, R)), pol_value=(np.float32, (T + 1, R)))
+            self.policy = self._views(po, arrays, "imgenv_policy_out")
+            self._pol_cat, self._pol_params, self._pol_store = cat, n, bool(store)
+            self._pol_keep = None
+        return self.policy
+
+    def _pol_tensor(self, t, shapes, what):
+        import torch
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor):
+            t = torch.as_tensor(np.ascontiguousarray(t, np.float32), device=self.device)
+        if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+            t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(t.shape) not in shapes:
+            raise ValueError("policy_sample: %s float32 %s" % (what, " or ".join(str(list(s)) for s in shapes)))
+        return t
+
+    def policy_sample(self, params, log_std=None, values=None, draw=0, deterministic=False, store=True):
+        """``imgenv_policy_sample``: ``params`` -- logits float32 ``[R, A]`` or means ``[R, C]`` -- with ``log_std`` float32 ``[C]``
+        or ``[R, C]`` (Gaussian) and ``values`` float32 ``[R]`` or None become the sampled action (``deterministic``: the mode) of
+        draw number ``draw`` in ``self.policy`` and its decoded rows in ``action_outputs``; ``action_outputs["actions"]`` is
+        returned and goes to any step call on the same stream.  One launch, ordered on the current stream.  With a storing head
+        the call also writes the rollout window's slot unless ``store`` is False."""
+        if self.policy is None:
+            raise RuntimeError("policy_sample failed (%d): enable_policy was not called" % _cabi.ESTATE)
+        R, n = self.n_local, self._pol_params
+        a = _cabi.PolicyArgs()
+        a.struct_size = C.sizeof(_cabi.PolicyArgs)
+        params = self._pol_tensor(params, [(R, n)], "logits" if self._pol_cat else "mean")
+        values = self._pol_tensor(values, [(R,)], "values")
+        if params is None:
+            raise ValueError("policy_sample: %s is missing" % ("logits" if self._pol_cat else "mean"))
+        a.flags = (_cabi.POLICY_DETERMINISTIC if deterministic else 0) | (0 if store or not self._pol_store else _cabi.POLICY_NO_STORE)
+        if not self._pol_cat:
+            log_std = self._pol_tensor(log_std, [(n,), (R, n)], "log_std")
+            if log_std is None:
+                raise ValueError("policy_sample: log_std is missing")
+            if log_std.dim() == 2:
+                a.flags |= _cabi.POLICY_LOG_STD_PER_ROW
+            a.log_std = log_std.data_ptr()
+        a.draw = int(draw) & 0xFFFFFFFFFFFFFFFF
+        a.params = params.data_ptr()
+        a.values = values.data_ptr() if values is not None else None
+        # (kept until the next sample: the launch reads them in stream order, a tensor made here from host data must outlive it)
+        self._pol_keep = (params, log_std, values)
+        self._call(self.lib.imgenv_policy_sample(self.h, C.byref(a), self._stream()), "imgenv_policy_sample")
+        return self.action_outputs["actions"]
+
+    def policy_value(self, values):
+        """the ``IMGENV_POLICY_VALUE_ONLY`` call: ``values`` float32 ``[R]`` into ``policy["pol_value"][n]``, n the rollout
+        cursor -- the bootstrap value where n is T"""
+        if self.policy is None:
+            raise RuntimeError("policy_value failed (%d): enable_policy was not called" % _cabi.ESTATE)
+        a = _cabi.PolicyArgs()
+        a.struct_size = C.sizeof(_cabi.PolicyArgs)
+        values = self._pol_tensor(values, [(self.n_local,)], "values")
+        a.flags = _cabi.POLICY_VALUE_ONLY
+        a.values = values.data_ptr() if values is not None else None
+        self._pol_value_keep = values
+        self._call(self.lib.imgenv_policy_sample(self.h, C.byref(a), self._stream()), "imgenv_policy_sample")
 
     def enable_obs_post(self, ped_norm=True, close=None, avg=_cabi.PED_NORM_AVG, std=_cabi.PED_NORM_STD, close_dist=_cabi.CLOSE_DIST):
         """Device-side StatePedVectorWrapper and ``bool_get_close_to_human`` (``imgenv_obs_post_enable``): from now on every reset /
@@ -885,7 +962,7 @@ class World:
     def close(self):
         if getattr(self, "h", None):
             self.episodes = self.episode_log = self.action_outputs = self.obs_post = self.final_obs = self.rollout = self.minibatch = None  # (views of memory the handle owns)
-            self.normalise = None
+            self.normalise = self.policy = None
             self.lib.imgenv_destroy(self.h)
             self.h = None
 

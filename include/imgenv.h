@@ -693,6 +693,90 @@ int imgenv_actions_outputs(imgenv_t* h, imgenv_actions_out* out);
  * misaligned `raw`, an unknown dtype, or integer `raw` in CLIP mode. */
 int imgenv_actions_decode(imgenv_t* h, const void* raw, int32_t dtype, void* stream);
 
+/* ---- the policy head: sample the action from the policy's distribution, on the device ----
+ * A policy emits neither an index nor a raw row: it emits logits over the YAML's discrete_actions, or a mean and a log-std over
+ * its continuous_actions.  With the policy head enabled, imgenv_policy_sample queues ONE launch (k_policy_*, csrc/policy.h) on the
+ * caller's stream that draws the action (or takes the mode), computes its log-probability and the distribution's entropy, decodes
+ * it into the handle-owned imgenv_actions_out.actions / speeds exactly as imgenv_actions_decode would have decoded the drawn index
+ * / the drawn raw row, adds the bad rows to imgenv_actions_out.n_bad, and -- with IMGENV_POLICY_STORE -- keeps the action, its
+ * log-probability and the caller's value estimate in the slot of the rollout window the next transition starts from.  Ordering,
+ * ownership and the imgenv_step_launches accounting (one launch, counted with the step that follows) are imgenv_actions_decode's.
+ * Opt-in: a handle that never enables it launches exactly what it launched before.
+ *
+ * Random numbers: Philox4x32-10, stateless.  counter = (g lo, g hi, draw lo, draw hi) with g = robot_begin + r the GLOBAL robot
+ * number -- a robot shard draws what the whole world draws -- key = (seed lo, seed hi); `seed` is the cfg's, `draw` the caller's
+ * (one per call: the library keeps no generator state).  u = float(x0 >> 8) * 2^-24, in [0, 1).
+ *
+ * CATEGORICAL (needs imgenv_actions_enable in TABLE mode), per local robot row of A = n_table float32 logits, float32 throughout:
+ *   a -inf logit is a masked action and is legal.  A NaN, a +inf or a row without a finite logit is a bad row: actions (0, 0, 0),
+ *   index -1, logp 0, entropy 0, counted in n_bad.  Otherwise, with m = max_k l_k: e_k = expf(l_k - m) (0 where masked),
+ *   s = sum e_k, logp_k = (l_k - m) - logf(s), entropy = -sum over e_k > 0 of (e_k / s) logp_k.  The draw: target = u s; index =
+ *   the smallest k with e_k > 0 whose inclusive cumulative sum exceeds target; if none does (u s rounded up to s), the largest k
+ *   with e_k > 0.  A masked action is never chosen.  DETERMINISTIC: the smallest k with l_k == m.  The order of every sum and of
+ *   the cumulative sum is fixed (csrc/policy.h states it; it depends on A alone): two runs give identical bits.
+ * GAUSSIAN (needs CLIP mode), C = n_cols independent normals per row: sigma = expf(log_std); u1 = float((x0 >> 8) + 1) * 2^-24,
+ *   u2 = float(x1 >> 8) * 2^-24, rho = sqrtf(-2 logf(u1)), z0 = rho cosf(2 pi u2), z1 = rho sinf(2 pi u2); column 2 takes z0 of a
+ *   second block whose counter has draw hi ^ 0x80000000.  raw = mean + sigma z; logp = sum_c (-0.5 z^2 - log_std - 0.5 ln 2 pi),
+ *   the log-probability of the UNCLIPPED sample; entropy = sum_c (0.5 + 0.5 ln 2 pi + log_std).  DETERMINISTIC: z = 0.  A mean,
+ *   log_std, sigma or raw that is not finite makes a bad row: raw 0, actions (0, 0, 0), logp 0, entropy 0, counted.  actions =
+ *   the CLIP rule of imgenv_actions_decode on raw.
+ * STORE (cfg.flags; needs imgenv_rollout_enable first): pol_raw / pol_logp / pol_value are [.][T][R] arrays in the layout
+ *   imgenv_minibatch_args.scalars takes (row stride R), a separate all-or-nothing allocation.  A sample without NO_STORE writes
+ *   slot n = the rollout cursor at the time of the call (imgenv_rollout_out.n, the host's); pol_value[n] only where `values` is
+ *   given.  n < 0 (before imgenv_rollout_begin) or n >= T is IMGENV_ESTATE; n == T is legal for VALUE_ONLY alone, which copies
+ *   `values` into pol_value[n] -- the bootstrap value of the window's last state -- and does nothing else (it is no part of a step
+ *   and is not counted in imgenv_step_launches).  Nothing is queued on failure. */
+#define IMGENV_POLICY_CATEGORICAL 0      /* needs imgenv_actions_enable in TABLE mode: A = n_table logits per robot */
+#define IMGENV_POLICY_GAUSSIAN    1      /* needs CLIP mode: C = n_cols (2 or 3) independent normals per robot */
+#define IMGENV_POLICY_STORE       1      /* cfg.flags: keep the policy columns in the rollout ring (needs imgenv_rollout_enable) */
+#define IMGENV_POLICY_DETERMINISTIC   1  /* args.flags: the mode instead of a draw */
+#define IMGENV_POLICY_LOG_STD_PER_ROW 2  /* args.flags: log_std is [R][C] instead of [C] */
+#define IMGENV_POLICY_NO_STORE        4  /* args.flags: this call does not touch the ring (evaluation between windows) */
+#define IMGENV_POLICY_VALUE_ONLY      8  /* args.flags: only values -> pol_value[n] (the bootstrap slot, n == T allowed) */
+typedef struct imgenv_policy_cfg {
+    int32_t struct_size;          /* sizeof(imgenv_policy_cfg) */
+    int32_t kind;                 /* IMGENV_POLICY_CATEGORICAL | IMGENV_POLICY_GAUSSIAN */
+    int32_t flags;                /* 0 | IMGENV_POLICY_STORE */
+    int32_t reserved;             /* 0 */
+    uint64_t seed;                /* the Philox key */
+} imgenv_policy_cfg;
+/* Device pointers, R = robot_end - robot_begin local robots; owned by the handle, valid until imgenv_destroy(), contents valid once
+ * the stream work of the last imgenv_policy_sample has completed, READ-ONLY for the caller. */
+typedef struct imgenv_policy_out {
+    int32_t struct_size;          /* on entry 0 or sizeof(imgenv_policy_out) */
+    int32_t n_local;              /* R */
+    int32_t n_params;             /* A or C */
+    int32_t horizon;              /* T or 0 */
+    int32_t* index;               /* [R]        CATEGORICAL: the action drawn, -1 for a bad row; NULL for GAUSSIAN */
+    float* raw;                   /* [R][C]     GAUSSIAN: the unclipped sample (what PPO's loss needs); NULL for CATEGORICAL */
+    float* logp;                  /* [R] */
+    float* entropy;               /* [R] */
+    float* pol_raw;               /* [C'][T][R] STORE only: C' = 1 (the index as float32, exact up to 4096; -1 bad) or C */
+    float* pol_logp;              /* [T][R]     STORE only */
+    float* pol_value;             /* [T+1][R]   STORE only */
+} imgenv_policy_out;
+typedef struct imgenv_policy_args {
+    int32_t struct_size;          /* sizeof(imgenv_policy_args) */
+    int32_t flags;                /* IMGENV_POLICY_DETERMINISTIC | _LOG_STD_PER_ROW | _NO_STORE, or _VALUE_ONLY alone */
+    uint64_t draw;                /* the draw number: the caller's, a new one for every call that must differ */
+    const float* params;          /* DEVICE f32: logits [R][A] | mean [R][C] */
+    const float* log_std;         /* DEVICE f32 [C] or [R][C]; GAUSSIAN only */
+    const float* values;          /* DEVICE f32 [R] or NULL */
+} imgenv_policy_args;
+/* Legal once imgenv_actions_enable() has been called (IMGENV_ESTATE before it; with IMGENV_POLICY_STORE also before
+ * imgenv_rollout_enable()).  IMGENV_EINVAL for a wrong struct_size, an unknown kind or flag, reserved != 0, a kind the handle's
+ * action mode does not serve (CATEGORICAL needs TABLE, GAUSSIAN needs CLIP), or a second call whose cfg differs from the first's
+ * (same cfg: nothing changes, same pointers).  IMGENV_ENOMEM leaves the handle as it was.  `out` may be NULL. */
+int imgenv_policy_enable(imgenv_t* h, const imgenv_policy_cfg* cfg, imgenv_policy_out* out);
+/* IMGENV_ESTATE before imgenv_policy_enable() */
+int imgenv_policy_outputs(imgenv_t* h, imgenv_policy_out* out);
+/* The pointers of `args` are DEVICE pointers, contiguous, 4-byte aligned, valid until the launch has run.  IMGENV_ESTATE before
+ * imgenv_policy_enable() or before the first reset, for a storing call outside the window (see STORE above) and for VALUE_ONLY on a
+ * head without IMGENV_POLICY_STORE; IMGENV_EINVAL for a wrong struct_size, an unknown flag, VALUE_ONLY beside another flag,
+ * LOG_STD_PER_ROW on a categorical head, a null or misaligned params (log_std for GAUSSIAN, values for VALUE_ONLY) or a
+ * misaligned values. */
+int imgenv_policy_sample(imgenv_t* h, const imgenv_policy_args* args, void* stream);
+
 /* ---- observation post-processing: StatePedVectorWrapper (envs/wrapper/base.py:19-34) and InfoLogWrapper's
  * bool_get_close_to_human (base.py:250-252) for every local robot, on the device ----
  * One extra launch at the end of every chain (k_obs_post, csrc/obs_post.h; behind the stacks and the episode statistics): a step

@@ -17,6 +17,9 @@ its difference between the last two is what the log's launch costs a reset chain
 observations (VecImageEnv(final_obs=True), imgenv_final_obs_enable: one more launch per reset chain) off / on in the same way.
 --normalise-compare alternates, with the device-side reset, the running normalisation of vector_states and rewards off / kept by
 the library (VecImageEnv(normalise={...}), imgenv_normalise_enable: two more launches per chain) / kept by TorchNormalise's torch ops.
+--policy-compare alternates, with the device-side reset, wrappers=True and rollout=--horizon, the hop from logits over 11 actions
+to the stepped env done by the policy head (VecImageEnv(policy={...}).policy_step: one launch instead of the decode's) / by
+torch.distributions.Categorical (sample, log_prob, entropy, three stores into [T, n] tensors, then step on the indices).
 
 --rollout-compare runs device_reset steps three ways, one process per measurement, alternating over several rounds: no rollout
 storage, the library's (VecImageEnv(rollout=--horizon), imgenv_rollout_enable: one more launch per chain, a new window every
@@ -503,6 +506,83 @@ def compare_wrappers(args, rounds=3):
                 rounds=rounds, runs=runs, summary=summary)
 
 
+POLICY_TABLE = [[v, w] for v in (0.0, 0.3, 0.6) for w in (-0.9, 0.0, 0.9)] + [[0.15, 0.0], [0.45, 0.0]]  # 11 actions
+
+
+def measure_policy(variant, envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, horizon=32):
+    """us per step of ``VecImageEnv(..., wrappers=True, rollout=horizon)`` with the device-side reset, from logits over 11 discrete
+    actions to the stepped env, with the sample, its log-probability and entropy and the [T, n] action / log-prob / value columns
+    kept by the library ("library": ``policy=dict(seed=s)``, ``policy_step``) or by torch ("torch": ``torch.distributions.Categorical``
+    -- sample, log_prob, entropy -- three ``buf[t].copy_`` and ``step`` on the sampled indices).  A new window every ``horizon`` steps."""
+    import torch
+    from img_env_amd import worldgen
+    from img_env_amd.vec_env import VecImageEnv
+    grid = worldgen.make_grid(200, 2)
+    cfg = worldgen.make_yaml_cfg(robots, peds, grid, time_max=time_max, n_obstacles=obstacles, seed=5)
+    cfg.update(discrete_action=True, discrete_actions=POLICY_TABLE)
+    T, n, A = horizon, envs * robots, len(POLICY_TABLE)
+    env = VecImageEnv(cfg, env_num=envs, seed=5, device_reset=True, wrappers=True, rollout=T, rollout_final=n,
+                      policy=dict(seed=7) if variant == "library" else None)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    logits = torch.randn(16, n, A, generator=g, device="cuda")
+    values = torch.randn(16, n, generator=g, device="cuda")
+    buf = None
+    if variant == "torch":
+        buf = dict(act=torch.zeros(T, n, device="cuda"), logp=torch.zeros(T, n, device="cuda"), value=torch.zeros(T + 1, n, device="cuda"))
+    cursor, launches = [0], [0]
+
+    def step(s):
+        t = cursor[0]
+        if t == T:
+            env.rollout_begin()
+            t = 0
+        l, v = logits[s % 16], values[s % 16]
+        if variant == "library":
+            env.policy_step(logits=l, values=v)
+        else:
+            dist = torch.distributions.Categorical(logits=l)
+            a = dist.sample()
+            logp, ent = dist.log_prob(a), dist.entropy()  # noqa: F841 (the entropy is what the loss takes; computed, not stored)
+            buf["act"][t].copy_(a)
+            buf["logp"][t].copy_(logp)
+            buf["value"][t].copy_(v)
+            env.step(a)
+        cursor[0] = t + 1
+    env.reset()
+    for s in range(time_max + 20):  # the drift phase: past the first wave of time limits
+        step(s)
+    launches[0] = env.world.launches()
+    torch.cuda.synchronize()
+    worlds, first = env.world.autoreset_last()
+    placed0, t0 = first + len(worlds), time.perf_counter()
+    for s in range(steps):
+        step(s)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    worlds, first = env.world.autoreset_last()
+    env.close()
+    return dict(us_per_step=1e6 * dt / steps, env_resets_per_step=(first + len(worlds) - placed0) / steps, horizon=T, actions=A,
+                step_launches=launches[0])
+
+
+def compare_policy(args, rounds=3):
+    """the policy head against torch.distributions on the same commit, alternating, `rounds` times in one process"""
+    runs = []
+    for rnd in range(rounds):
+        for variant in ("library", "torch"):
+            r = measure_policy(variant, args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max, args.horizon)
+            runs.append(dict(round=rnd, variant=variant, **r))
+            print(json.dumps(runs[-1]), flush=True)
+    summary = {}
+    for variant in ("library", "torch"):
+        v = [r["us_per_step"] for r in runs if r["variant"] == variant]
+        summary[variant] = dict(us_per_step_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v),
+                                step_launches=[r["step_launches"] for r in runs if r["variant"] == variant][0])
+    summary["torch_minus_library_us"] = summary["torch"]["median"] - summary["library"]["median"]
+    return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, steps=args.steps, time_max=args.time_max,
+                horizon=args.horizon, rounds=rounds, runs=runs, summary=summary)
+
+
 def track_sets(n_sets, peds, records, dt, seed=3, box=(3.0, 22.0)):
     """n_sets recorded crowds of `peds` straight walks of `records` records each: [peds, records, 5] rows (x, y, yaw, vx, vy)"""
     import numpy as np
@@ -936,6 +1016,8 @@ def main():
                     help="the final observations (VecImageEnv(final_obs=True)) off / on, alternating over --rounds rounds")
     ap.add_argument("--wrappers", default=None, choices=("table", "clip"), help="the policy's raw output decoded by the library (wrappers=True)")
     ap.add_argument("--torch-wrappers", action="store_true", help="with --wrappers: the same kept with torch ops on a plain VecImageEnv")
+    ap.add_argument("--policy-compare", action="store_true",
+                    help="logits -> sampled action -> step: the policy head (policy_step) / torch.distributions, alternating over --rounds rounds")
     ap.add_argument("--wrappers-compare", action="store_true",
                     help="pre-decoded actions / library / torch, alternating over --rounds rounds, table and clip")
     ap.add_argument("--normalise-compare", action="store_true",
@@ -1006,6 +1088,13 @@ def main():
         return
     if args.wrappers_compare:
         res = compare_wrappers(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
+        return
+    if args.policy_compare:
+        res = compare_policy(args, args.rounds)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(res, fh, indent=1)

@@ -75,6 +75,7 @@ struct imgenv {
     std::vector<float> pmax;
     DevWorld d;
     PlanHandle plan;  // what the launch rules (launch_plan.h) read of this handle: plan_facts
+    int raster_pack = -1;  // IMGENV_RASTER_PACK when the handle was created (measurement switch; -1: unset, the plan's rule)
     std::vector<void*> allocs;
     unsigned char* arena = nullptr;
     bool own_arena = false;
@@ -644,6 +645,11 @@ static auto k_move_raster_for(const PlanHandle& p, int nw) {
     pick([&](auto P2, auto LM, auto NW) { k = k_move_raster<P2(), LM(), NW()>; }, p.pow2, OneOf<0, 1, 2>{p.layer}, OneOf<1, 4>{nw});
     return k;
 }
+static auto k_raster_pack_for(const PlanHandle& p, int rpw) {
+    decltype(&k_raster_pack<true, 2>) k = nullptr;
+    pick([&](auto P2, auto RPW) { k = k_raster_pack<P2(), RPW()>; }, p.pow2, OneOf<2, 4>{rpw});
+    return k;
+}
 static auto k_remote_for(const PlanHandle& p) { return p.pow2 ? k_remote<true> : k_remote<false>; }
 static auto k_view_for(const PlanHandle& p, int nw) {
     decltype(&k_view<true, true, true, 1>) k = nullptr;
@@ -676,6 +682,12 @@ static void plan_facts(imgenv* h) {
     p.obs_E = h->obs_E; p.n_sub = h->n_sub; p.relation = d.relation; p.scene = h->cfg.ped_scene_type;
     p.early = h->early; p.gates_work = h->gates_work;
     p.Gs = h->Gs; p.box_cells = d.box_cells;
+    p.robot_classes = (int)h->rcls.size(); p.pack_rows = true; p.pack_bitmap_cells = 0; p.pack_force = h->raster_pack;
+    for (const RobotClassHost& k : h->rcls) {  // (plan_raster_pack)
+        const int side = 2 * k.box_rad + 1, bside = side - 4;
+        p.pack_rows = p.pack_rows && !k.fp_rows.empty() && side * side <= d.box_cells;
+        p.pack_bitmap_cells = std::max(p.pack_bitmap_cells, bside * bside);
+    }
     p.big_max_crop = h->big_max_crop; p.big_full_chunks = h->big_full_chunks; p.big_tap_chunks_dyn = h->big_tap_chunks_dyn;
     p.big_bits_in_lds = h->big_bits_in_lds; p.crop_map = d.crop_map != nullptr;
     p.img_w = d.img_w; p.img_h = d.img_h; p.resize = d.resize != 0; p.keep_view_maps = d.keep_view_maps != 0;
@@ -707,6 +719,8 @@ static int lds_attributes(imgenv* h) {
     }
     for (int nw : {1, 2, 4, 8})
         if (int rc = allow((const void*)k_view_for(p, nw), p.lds_view)) return rc;
+    for (int rpw : {2, 4})
+        if (int rc = allow((const void*)k_raster_pack_for(p, rpw), plan_raster_pack_lds(p, rpw))) return rc;
     return allow((const void*)k_obs_for(p), p.lds_obs);
 }
 
@@ -785,6 +799,10 @@ extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, i
     imgenv* h = new imgenv();
     h->cfg = *cfg;
     h->serial = getenv("IMGENV_SERIAL") && getenv("IMGENV_SERIAL")[0] == '1';  // (profiling aid: no side streams, clean per-kernel timings)
+    if (const char* e = getenv("IMGENV_RASTER_PACK")) {  // (measurement switch, per handle: 0 never, 2 / 4 that many robots per wavefront)
+        const int v = atoi(e);
+        h->raster_pack = v == 2 || v == 4 ? v : 0;
+    }
     h->geom = g;
     h->R = cfg->n_robots;
     h->P = cfg->n_peds;
@@ -1730,7 +1748,12 @@ static int launch_obs(imgenv* h, hipStream_t st) {
 static int launch_rasters(imgenv* h, hipStream_t st, int is_reset, bool moved, bool local_only, bool from_begin = false) {
     DevWorld& d = h->d;
     const PlanHandle& p = h->plan;
-    const RasterPlan r = plan_rasters(p, chain_facts(h, is_reset, moved, local_only));
+    const PlanChain c = chain_facts(h, is_reset, moved, local_only);
+    if (const RasterPackPlan k = plan_raster_pack(p, c); k.rpw) {  // (the id and name stay k_raster's: bench.py --full prices kernels by them)
+        TIMED(h, IMGENV_K_RASTER, st, (k_raster_pack_for(p, k.rpw)<<<dim3(k.launch.grid), dim3(k.launch.block), k.launch.lds, st>>>(d)));
+        return 0;
+    }
+    const RasterPlan r = plan_rasters(p, c);
     const int keep_ng = d.act_ng;
     if (local_only) {
         d.act_ng = h->RL;

@@ -4,6 +4,7 @@
 //                                        write-back, leg gait (img_env.cpp:344-358) or the recorded trajectory (361-386)
 //   k_sfm          1 workgroup / world   libpedsim crowd step (pedscene only)
 //   k_raster       1 wave / ped + robot  view_ped + the shared robot-owner layers (img_env.cpp:594-629)
+//   k_raster_pack  1 wave / 2 or 4 robots  k_raster's SUM-mode step of a big handle (launch_plan.h: plan_raster_pack); 1 wave / ped
 //   k_compose      1 thread / 4 cells    composed layer = obstacles + peds + robot owners (k_compose_tiles: only the 8 x 8 tiles
 //                                        the rasters touched, for big or many maps)
 //   k_view         1 wave / robot        Agent::view: collision, crop, laser, stamp (agent.cpp:356-509)
@@ -1913,6 +1914,176 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu((LM =
         RASTER_MARK(12);  // the block's pedestrian
     }
     if (b < w.RL) WAVE_DONE(2);
+}
+
+// k_raster's SUM-mode step of a big whole-world handle (launch_plan.h: plan_raster_pack) with RPW robots per wavefront: what
+// bounds that launch is the number of wavefront slots it has to wait for -- one robot per wavefront is 8192 of them at the
+// headline shape, two rounds even on an empty chip -- while a robot keeps a dozen of the 64 lanes busy (35 lattice rows, a box
+// of 7 x 7 cells, a list of a dozen entries, a bitmap of 3 x 3).  The lanes are cut into RPW segments of SEG = 64 / RPW, each
+// with an LDS box of its own, and a segment does for its robot what raster_robot<POW2, 2, 1> does, lattice rows only: the loop
+// bounds are the wavefront's, ballots are cut down to the segment where they decide something about one robot.  A robot with an
+// uncertified row is left untouched -- cached pose included -- and drawn by the whole wavefront through raster_robot behind the
+// others: that function stays the definition and the only home of the literal sample walk.  All robots of the handle share one
+// class (the plan's rule): its record is read with a scalar index.
+// Blocks [0, ceil(n_g / RPW)): robots RPW b .. RPW b + RPW - 1 (the last block may hold fewer); the n_p blocks behind: a pedestrian each.
+template <bool POW2, int RPW>
+__global__ __launch_bounds__(WAVE) void k_raster_pack(DevWorld w) {
+    constexpr int SEG = WAVE / RPW;
+    static_assert(RPW == 2 || RPW == 4, "segments of 32 or 16 lanes");
+    constexpr unsigned long long SEG_MASK = (1ull << SEG) - 1ull;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int b = blockIdx.x;
+    WAVE_T0();
+    __builtin_amdgcn_s_setprio(3);  // (critical chain: see k_integrate)
+    if (b == 0 && threadIdx.x == 0) w.counters[1] = 0;  // (as k_raster)
+    const int n_g = w.act_ng, n_rb = (n_g + RPW - 1) / RPW;
+    if (b >= n_rb) {
+        const int j = b - n_rb;
+        if (j < w.act_np) {
+            RASTER_MARK_BEGIN();
+            raster_ped_sum<POW2, 1>(w, j, w.pc[w.ped_cls[j]], (uint32_t*)smem);
+            RASTER_MARK(12);  // the block's pedestrian
+        }
+        return;
+    }
+    RASTER_MARK_BEGIN();
+    const int lane = lane_id(), seg = lane / SEG, sl = lane - seg * SEG, sh = seg * SEG;
+    const bool valid = RPW * b + seg < n_g;
+    const int i = min(RPW * b + seg, n_g - 1) + w.act_g0, l = i - w.r0;
+    const RobotClassDev k = robot_class(w, __builtin_amdgcn_readfirstlane(w.robot_cls[RPW * b + w.act_g0]));
+    const double* r = w.rec + (size_t)i * IMGENV_RECORD_DOUBLES;
+    const double rx = r[0], ry = r[1], rth = r[2];
+    const double res = w.res, inv = w.inv_res;
+    const int rad = k.box_rad, side = 2 * rad + 1, ncell = side * side;
+    const int world = world_of_robot(w, i);
+    const uint32_t cell0 = (uint32_t)world * w.Gs;
+    const bool alone = (w.W > 1 ? w.Rw : w.R) == 1;
+    // _step_robot tail: setRobotPos for every robot (raster_robot), before anything can return
+    if (sl == 0 && valid && w.relation == 1 && w.scene == IMGENV_SCENE_PEDSIM) {
+        double* p = w.sfm.p + 3 * ((size_t)world * w.sfm.n + w.sfm.n_peds + (size_t)(i - world * w.Rw));
+        p[0] = rx;
+        p[1] = ry;
+        p[2] = 1.0;
+    }
+    // a robot that has not moved since its cell list was made: its counts and its list stand
+    double* cached = w.fp_pose + 3 * (size_t)l;
+    const int n_cached = w.fp_n[l];
+    const bool moved = valid && !(n_cached >= 0 && cached[0] == rx && cached[1] == ry && cached[2] == rth);
+    if (!__any(moved)) {
+        WAVE_DONE(2);
+        return;
+    }
+    RASTER_MARK(5);  // pose, cached-list test
+    uint32_t* box = (uint32_t*)smem + (size_t)seg * (w.box_cells + 4);  // (the words behind a box: raster_robot's flags)
+    for (int q = sl; q < ncell; q += SEG) box[q] = 0;
+    __syncthreads();
+    const int cm = w2m_t<POW2>(rx, res, inv), cn = w2m_t<POW2>(ry, res, inv);
+    bool bad = false;
+    {   // the lattice rows of the footprint (fp_rows.h), one per lane of the segment
+        const Tf2 bw = tf_from_pose_sc(rx, ry, r[5], r[6]);
+        const FpRowsPose P = fpr_pose(bw.m00, bw.m01, bw.m10, bw.m11, bw.ox, bw.oy, k.fp_cy, res);
+        for (int r0 = 0; r0 < k.n_rows; r0 += SEG) {  // wave-uniform trip count
+            const int ri = r0 + sl;
+            const bool act = moved && ri < k.n_rows;
+            const FpRow row = k.rows[min(ri, k.n_rows - 1)];
+            FpAxis ax, ay;
+            const bool ok = fpr_row(P, row, ax, ay);
+            bad |= act & !ok;
+            const bool use = act & ok;
+            const int cx = use ? ax.cnt : 0, cy = use ? ay.cnt : 0;
+            // (the wavefront's largest step counts, whichever segment has them: scalar loop bounds, constant register indices)
+            const int cxw = (int)__any(cx >= 1) + (int)__any(cx >= 2) + (int)__any(cx >= 3) + (int)__any(cx >= 4);
+            const int cyw = (int)__any(cy >= 1) + (int)__any(cy >= 2) + (int)__any(cy >= 3) + (int)__any(cy >= 4);
+#pragma unroll
+            for (int a = 0; a <= FPR_MAXC; a++) {
+                if (a > cxw) break;
+#pragma unroll
+                for (int c = 0; c <= FPR_MAXC; c++) {
+                    if (c > cyw) break;
+                    int m, n;
+                    uint32_t last;
+                    const bool has = fpr_piece(row, ax, ay, a, c, m, n, last) & use;
+                    if (has && m >= 0 && m < w.Hg && n >= 0 && n < w.Wg) {
+                        const int dm = m - cm + rad, dn = n - cn + rad;
+                        if (dm >= 0 && dm < side && dn >= 0 && dn < side) atomicMax(&box[dm * side + dn], last);
+                        else bad = true;  // (cannot happen: raster_robot)
+                    }
+                }
+            }
+        }
+    }
+    // a robot with an uncertified row in any lane of its segment is left to raster_robot (below)
+    const unsigned long long bad_lanes = __ballot(bad);
+    const bool go = moved && ((bad_lanes >> sh) & SEG_MASK) == 0ull;
+    __syncthreads();
+    RASTER_MARK(6);  // footprint rows into the LDS boxes
+    // -- nothing global has been written for a moved robot up to here --
+    if (go && sl == 0) {
+        cached[0] = rx;
+        cached[1] = ry;
+        cached[2] = rth;
+    }
+    // the covered cells as a bitmap into the record's eighth double (raster_robot: the box without its margin of two cells)
+    const int brad = rad - 2, bside = 2 * brad + 1;
+    const int bm_ = sl / bside, bn_ = sl - bm_ * bside;
+    const unsigned long long fp_bits = (__ballot(sl < bside * bside && box[(bm_ + 2) * side + bn_ + 2] != 0u) >> sh) & SEG_MASK;
+    if (go && sl == 0) ((unsigned long long*)w.rec)[(size_t)i * IMGENV_RECORD_DOUBLES + 7] = fp_bits;
+    uint2* list = w.fp_cells + (size_t)l * w.fp_cap;
+    const uint32_t sum_word = sum_robot_word(w, sum_self_id(w, i));
+    if (!alone) {
+        // the cells the robot counted itself on so far: still under its footprint -> marked in the box, left behind -> its word comes off
+        const int n_old = go ? max(n_cached, 0) : 0;
+        for (int e0 = 0; __any(e0 < n_old); e0 += SEG) {
+            const int e = e0 + sl;
+            if (e < n_old) {
+                const uint32_t c = list[e].x, rel = c - cell0;
+                const int m = (int)(((unsigned long long)rel * w.sum_wg_magic) >> 40), n = (int)rel - m * w.Wg;
+                const int dm = m - cm + rad, dn = n - cn + rad;
+                const bool inb = dm >= 0 && dm < side && dn >= 0 && dn < side;
+                const uint32_t v = inb ? box[dm * side + dn] : 0u;
+                if (v) atomicOr(&box[dm * side + dn], 0x80000000u);
+                else atomicAdd(&w.cell[c], 0u - sum_word);
+            }
+        }
+        __syncthreads();
+    }
+    int n_out = 0;
+    for (int b0 = 0; b0 < ncell; b0 += SEG) {  // wave-uniform trip count (ballots inside)
+        const int q = b0 + sl;
+        uint32_t last = go && q < ncell ? box[q] : 0u;
+        const bool counted = (last >> 31) != 0u;
+        last &= 0x7FFFFFFFu;
+        const bool in = last != 0u;
+        const int qm = q / side;
+        const uint32_t c = cell0 + (uint32_t)(cm - rad + qm) * (uint32_t)w.Wg + (uint32_t)(cn - rad + (q - qm * side));
+        if (in && !counted && !alone) {  // a cell the robot has just entered (the count-overflow flag: raster_robot)
+            const uint32_t before = atomicAdd(&w.cell[c], sum_word);
+            const uint32_t rc_mask = (1u << (w.sum_id_shift - w.sum_rc_shift)) - 1u;
+            if (((before >> w.sum_rc_shift) & rc_mask) == rc_mask) w.err[6] = 9;
+        }
+        // the new (cell, last sample) list, compacted with the segment's part of the ballot: raster_robot's order
+        const unsigned long long mask = (__ballot(in) >> sh) & SEG_MASK;
+        const int pos = n_out + __popcll(mask & ((1ull << sl) - 1ull));
+        if (in && pos < w.fp_cap) list[pos] = make_uint2(c, last);
+        n_out += __popcll(mask);
+    }
+    RASTER_MARK(7);  // boxes -> counts + cell lists
+    if (go && sl == 0) {
+        w.fp_n[l] = n_out <= w.fp_cap ? n_out : -1;
+        if (w.sum_shard && __popcll(fp_bits) != n_out) w.err[6] = 10;  // (as raster_robot)
+    }
+    // the robots left untouched above, one after the other, by the whole wavefront (the boxes are free by now)
+    const unsigned long long redo = __ballot(moved && !go);
+    if (redo != 0ull) {
+        const Region g = grid_region(w);
+#pragma nounroll
+        for (int s = 0; s < RPW; s++) {
+            if (((redo >> (s * SEG)) & SEG_MASK) == 0ull) continue;  // uniform
+            __syncthreads();
+            raster_robot<POW2, 2, 1>(w, RPW * b + s + w.act_g0, k, (uint32_t*)smem, g);
+        }
+    }
+    WAVE_DONE(2);
 }
 
 // k_integrate and k_raster as ONE launch, for steps of handles that leave the chip room (imgenv_step on at most 4096 robots, all of

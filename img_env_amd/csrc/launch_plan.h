@@ -117,6 +117,12 @@ struct PlanHandle {
     bool early = false, gates_work = false;
     size_t Gs = 0;                                              // cells of one world's grid layer
     int box_cells = 0;                                          // the rasters' LDS box
+    // plan_raster_pack: robot classes of the handle; every one has lattice rows and a box within box_cells; the largest footprint
+    // bitmap (cells); IMGENV_RASTER_PACK as the handle's creation found it (-1: unset)
+    int robot_classes = 0;
+    bool pack_rows = false;
+    int pack_bitmap_cells = 0;
+    int pack_force = -1;
     int big_max_crop = 1, big_full_chunks = 1, big_tap_chunks_dyn = 0;
     bool big_bits_in_lds = true, crop_map = false;
     int img_w = 0, img_h = 0;
@@ -277,6 +283,40 @@ inline RasterPlan plan_rasters(const PlanHandle& h, const PlanChain& c) {
     r.move = c.moved;
     r.move_peds = plan_peds_move(h) ? 1 : 0;
     r.launch = {(unsigned)(r.split || r.move ? r.n_g + r.n_p : n_blocks), (unsigned)(r.nw * WAVE), 4 * (size_t)h.box_cells + 16};
+    return r;
+}
+
+// k_raster_pack<pow2, RPW> in place of k_raster: RPW robots per wavefront, 64 / RPW lanes and an LDS box each, the pedestrians in
+// the blocks behind.  plan_rasters stays the plan of everything this refuses.  What it takes: SUM counts of a handle that owns its
+// whole world, a step over every world (no reset, no world list, no device-side count, the move not fused), ONE robot class --
+// the kernel reads the class record with a scalar index -- that has lattice rows, a box within the handle's and a footprint
+// bitmap of at most 64 / RPW cells, and RPW boxes of LDS that leave a compute unit its 32 wavefronts.
+struct RasterPackPlan {
+    int rpw = 0;         // 0: not packed (k_raster / k_move_raster as plan_rasters says)
+    LaunchShape launch;  // k_raster_pack <pow2, rpw>
+};
+inline size_t plan_raster_pack_lds(const PlanHandle& h, int rpw) { return (size_t)rpw * (4 * (size_t)h.box_cells + 16); }
+inline bool plan_raster_pack_fits(const PlanHandle& h, int rpw) {
+    return (rpw == 2 || rpw == 4) && h.layer == LAYER_SUM && !h.sharded && !h.sum_shard && h.RL == h.R && h.robot_classes == 1 &&
+           h.pack_rows && h.pack_bitmap_cells >= 1 && h.pack_bitmap_cells <= WAVE / rpw &&
+           LDS_MAX / ((plan_raster_pack_lds(h, rpw) + 1279) / 1280 * 1280) >= 32;
+}
+inline RasterPackPlan plan_raster_pack(const PlanHandle& h, const PlanChain& c) {
+    RasterPackPlan r;
+    if (c.is_reset || c.listed || c.n_dev || c.moved || c.local_only || c.act_ng != h.R || c.act_ng < 1) return r;
+    // The size rule: the launches plan_rasters calls neither small nor roomy (more blocks than the chip holds wavefronts: the
+    // headline's 8192 + 200), where packing turns two rounds of wavefronts into one.
+    // RPW: four.  The headline step, one box, the switch at 0 / 2 / 4 interleaved three times (profiles/raster_pack_ab.txt):
+    // 87.8 / 87.6 / 88.0 us with k_raster, 85.8 / 85.2 / 85.7 with two robots per wavefront, 83.1 / 83.7 / 83.6 with four.
+    // Not where only two fit (a bitmap of more than 16 cells: cfg-5, where the step is k_obs' 205 us whatever the rasters do --
+    // 279.9-280.9 us per step with k_raster, 281.0-281.9 with two per wavefront), and not beside a social-force crowd (cfg-4, whose
+    // k_sfm shares the chip with the rasters: 104.1 / 104.2 / 105.1 us with k_raster, 111.1 / 111.3 / 102.3 packed).
+    const bool big = c.act_ng + c.act_np > 8192 && h.scene != IMGENV_SCENE_PEDSIM;
+    int want = big && plan_raster_pack_fits(h, 4) ? 4 : 0;
+    if (h.pack_force >= 0) want = h.pack_force;  // IMGENV_RASTER_PACK (measurement switch): 0 never, 2 / 4 on every eligible chain
+    if (want == 0 || !plan_raster_pack_fits(h, want)) return r;
+    r.rpw = want;
+    r.launch = {(unsigned)((c.act_ng + want - 1) / want + c.act_np), WAVE, plan_raster_pack_lds(h, want)};
     return r;
 }
 

@@ -20,6 +20,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "field_rows.h"
 #include "launch_plan.h"  // FINAL_BLOCK, FINAL_MAX_BLOCKS, FINAL_MAX_FIELDS
 #include "tail_rows.h"
 
@@ -38,30 +39,10 @@ struct FinalObsDev {
     TailRows rows;            // the robots of the reset chain in hand
 };
 
-struct alignas(16) FinalChunk16 {
-    uint32_t v[4];
-};
-struct alignas(8) FinalChunk8 {
-    uint32_t v[2];
-};
-
 template <typename T>
 TAIL_HD void final_obs_copy(unsigned char* dst, const unsigned char* src, uint32_t chunks, size_t row, uint32_t c) {
     const size_t at = row * (size_t)chunks + c;
     ((T*)dst)[at] = ((const T*)src)[at];
-}
-
-// the field chunk `c` of a row falls into, from field K on: while it lies behind the field in hand, step to the next one (k_stack's
-// nested ifs, written once: every index is a constant)
-template <int K>
-TAIL_HD void final_obs_field(const FinalObsDev& fo, uint32_t& c, unsigned char*& dst, const unsigned char*& src, uint32_t& chunks, uint32_t& unit) {
-    if constexpr (K < FINAL_MAX_FIELDS) {
-        if (K < fo.n_fields && c >= chunks) {
-            c -= chunks;
-            dst = fo.f[K].dst; src = fo.f[K].src; chunks = fo.f[K].chunks; unit = fo.f[K].unit;
-            final_obs_field<K + 1>(fo, c, dst, src, chunks, unit);
-        }
-    }
 }
 
 // item t of the launch:chunk t % chunks_per_row of the (t / chunks_per_row)-th covered row
@@ -70,18 +51,8 @@ TAIL_HD void final_obs_item(const FinalObsDev& fo, bool listed, size_t t) {
     uint32_t c = (uint32_t)(t - m * fo.chunks_per_row);
     const size_t row = tail_rows_row(fo.rows, listed, m);
     if (c == 0) fo.count[row] += 1;  // (one lane per row and launch: no atomic)
-    // (member by member with constant indices: selects on scalar kernel arguments, no indexed copy of the struct)
-    unsigned char* dst = fo.f[0].dst;
-    const unsigned char* src = fo.f[0].src;
-    uint32_t chunks = fo.f[0].chunks, unit = fo.f[0].unit;
-    final_obs_field<1>(fo, c, dst, src, chunks, unit);
-    switch (unit) {
-        case 16: final_obs_copy<FinalChunk16>(dst, src, chunks, row, c); break;
-        case 8: final_obs_copy<FinalChunk8>(dst, src, chunks, row, c); break;
-        case 4: final_obs_copy<uint32_t>(dst, src, chunks, row, c); break;
-        case 2: final_obs_copy<uint16_t>(dst, src, chunks, row, c); break;
-        default: final_obs_copy<uint8_t>(dst, src, chunks, row, c); break;
-    }
+    const FinalField f = field_walk(fo.f, fo.n_fields, c);
+    field_dispatch(f.unit, [&](auto chunk) { final_obs_copy<typename decltype(chunk)::type>(f.dst, f.src, f.chunks, row, c); });
 }
 
 #if defined(__HIPCC__)

@@ -21,6 +21,7 @@
 #include "cv_resize.h"
 #include "spawn_host.h"
 #include "launch_plan.h"
+#include "obs_fields.h"
 #include "kernels.h"
 #include "world.h"
 #include "stack.h"
@@ -274,6 +275,7 @@ struct imgenv {
     uint32_t roll_turn = 0;      // reset chains stored since the last begin
     RolloutDev roll;
     size_t roll_row_bytes[ROLLOUT_TABLE_FIELDS];
+    int roll_field_id[ROLLOUT_TABLE_FIELDS];  // which field (obs_fields.h) entry k of roll.f is
     imgenv_rollout_cfg roll_cfg;
     imgenv_rollout_out roll_out;
     // rollout minibatches (imgenv_rollout_minibatch_enable; csrc/minibatch.h)
@@ -452,9 +454,7 @@ extern "C" const char* imgenv_last_error(void) { return g_err; }
 struct OutField {
     size_t offset, bytes;
 };
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct ArenaPlan {
+struct ArenaPlan {  // (align256: launch_plan.h)
     size_t total = 0;
     size_t off[40];
     int n = 0;
@@ -3908,6 +3908,14 @@ static int enable_done(imgenv* h, Out o, Out imgenv::*stored, bool imgenv::*on, 
     if (out) *out = o;
     return IMGENV_OK;
 }
+// a feature's one block (launch_plan.h has the layouts): `total` zeroed bytes that the handle owns from here on
+static int feature_block(imgenv* h, size_t total, const char* enable_name, unsigned char** block) {
+    HIPCHK(hipSetDevice(h->cfg.device));
+    DevTxn<HipApi> txn;
+    if (!txn.room(block, total, 0)) FAIL(txn.code(), "%s: %s", enable_name, txn.error());
+    txn.commit(h->allocs);
+    return IMGENV_OK;
+}
 template <typename Out>
 static int feature_outputs(imgenv* h, bool imgenv::*on, Out imgenv::*stored, Out* out, const char* enable_name) {
     if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
@@ -3917,27 +3925,12 @@ static int feature_outputs(imgenv* h, bool imgenv::*on, Out imgenv::*stored, Out
 }
 
 // ---- observation stacks (include/imgenv.h; the kernel is csrc/stack.h) ----
-struct StackPlan {
-    int depth[3];          // effective depths: sensor_maps, vector_states, lasers (0 = not stacked)
-    size_t frame_bytes[3];
-    size_t off[3], total;  // carve-outs of the fields of depth >= 2
-};
-static int plan_stack(const imgenv_cfg& c, const imgenv_stack_cfg& s, int RL, StackPlan& p) {
-    const int B = make_view_geom(c).B;
-    p.depth[0] = s.image_batch > 0 ? s.image_batch : 0;
-    p.depth[1] = s.state_batch > 0 ? s.state_batch : 0;
-    p.depth[2] = s.laser_batch >= 0 && B > 0 ? std::max(s.laser_batch, 1) : 0;
+// the cfg's refusals, then launch_plan.h's plan_stack
+static int stack_plan(const imgenv_cfg& c, const imgenv_stack_cfg& s, int RL, StackPlan& p) {
     if (s.image_batch < 0 || s.state_batch < 0) FAIL(IMGENV_EINVAL, "image_batch / state_batch must be >= 0");
     if (s.image_batch > IMGENV_STACK_MAX_DEPTH || s.state_batch > IMGENV_STACK_MAX_DEPTH || s.laser_batch > IMGENV_STACK_MAX_DEPTH)
         FAIL(IMGENV_EINVAL, "a stack depth above IMGENV_STACK_MAX_DEPTH (%d)", IMGENV_STACK_MAX_DEPTH);
-    p.frame_bytes[0] = (size_t)c.image_size[0] * (size_t)c.image_size[1] * 2;
-    p.frame_bytes[1] = (size_t)c.state_dim * 4;
-    p.frame_bytes[2] = (size_t)B * 8;
-    p.total = 0;
-    for (int k = 0; k < 3; k++) {
-        p.off[k] = p.total;
-        if (p.depth[k] >= 2) p.total = align256(p.total + (size_t)RL * p.depth[k] * p.frame_bytes[k]);
-    }
+    p = plan_stack((size_t)c.image_size[0] * (size_t)c.image_size[1], c.state_dim, make_view_geom(c).B, s.image_batch, s.state_batch, s.laser_batch, (size_t)RL);
     return IMGENV_OK;
 }
 
@@ -3947,7 +3940,7 @@ extern "C" int64_t imgenv_stack_bytes(const imgenv_cfg* cfg, const imgenv_stack_
     int r0, r1;
     if (shard_of(*cfg, r0, r1)) FAIL(IMGENV_EINVAL, "bad robot shard");
     StackPlan p;
-    if (int rc = plan_stack(*cfg, *s, r1 - r0, p)) return rc;
+    if (int rc = stack_plan(*cfg, *s, r1 - r0, p)) return rc;
     return (int64_t)p.total;
 }
 
@@ -3958,7 +3951,7 @@ extern "C" int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgen
     if (h->stack_on) FAIL(IMGENV_ESTATE, "imgenv_stack_enable has already been called on this handle");
     if (any_world_reset(h)) FAIL(IMGENV_ESTATE, "imgenv_stack_enable after the first reset");
     StackPlan p;
-    if (int rc = plan_stack(h->cfg, *s, h->RL, p)) return rc;
+    if (int rc = stack_plan(h->cfg, *s, h->RL, p)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     unsigned char* base = nullptr;
     if (p.total > 0) {
@@ -3984,9 +3977,11 @@ extern "C" int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgen
         StackField& f = sd.f[sd.n_fields++];
         f.stack = ptr[k];
         f.frame = work[k];
-        f.frame_bytes = (uint32_t)p.frame_bytes[k];
-        f.unit = f.frame_bytes % 16 == 0 ? 16 : f.frame_bytes % 8 == 0 ? 8 : f.frame_bytes % 4 == 0 ? 4 : 2;
-        f.chunks = f.frame_bytes / f.unit;
+        // (a frame is whole float16, float32 or float64 words: its size is even, and the rule never answers the unit 1 k_stack leaves out)
+        const FinalFieldPlan fp = plan_final_field(p.frame_bytes[k]);
+        f.frame_bytes = fp.row_bytes;
+        f.unit = fp.unit;
+        f.chunks = fp.chunks;
         f.depth = p.depth[k];
         sd.chunks_per_robot += f.chunks;
     }
@@ -4272,19 +4267,11 @@ extern "C" int imgenv_policy_enable(imgenv_t* h, const imgenv_policy_cfg* c, img
     const int n_params = cat ? h->act_cfg.n_table : h->act_cfg.n_cols;
     const size_t cols = cat ? 1 : (size_t)n_params;
     // one block, every array on a 256-byte boundary, zeroed; nothing of the handle changes before it is there
-    size_t total = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = total;
-        total = align256(total + bytes);
-        return at;
-    };
-    const size_t off_index = carve(cat ? RL * 4 : 0), off_raw = carve(cat ? 0 : RL * cols * 4), off_logp = carve(RL * 4), off_ent = carve(RL * 4);
-    const size_t off_praw = carve(cols * T * RL * 4), off_plogp = carve(T * RL * 4), off_pvalue = carve(store ? (T + 1) * RL * 4 : 0);
-    HIPCHK(hipSetDevice(h->cfg.device));
+    Carve cv;
+    const size_t off_index = cv.take(cat ? RL * 4 : 0), off_raw = cv.take(cat ? 0 : RL * cols * 4), off_logp = cv.take(RL * 4), off_ent = cv.take(RL * 4);
+    const size_t off_praw = cv.take(cols * T * RL * 4), off_plogp = cv.take(T * RL * 4), off_pvalue = cv.take(store ? (T + 1) * RL * 4 : 0);
     unsigned char* block = nullptr;
-    DevTxn<HipApi> txn;
-    if (!txn.room(&block, total, 0)) FAIL(txn.code(), "imgenv_policy_enable: %s", txn.error());
-    txn.commit(h->allocs);
+    RTRY(feature_block(h, cv.total, "imgenv_policy_enable", &block));
     imgenv_policy_out o = {};
     o.n_params = n_params;
     o.horizon = (int32_t)T;
@@ -4436,21 +4423,12 @@ extern "C" int imgenv_normalise_enable(imgenv_t* h, const imgenv_normalise_cfg* 
     const imgenv_stack_out& so = h->stack_out;
     const int K = obs && h->stack_on && so.state_depth >= 2 ? so.state_depth : 0;
     // one block, every array on a 256-byte boundary, zeroed; nothing of the handle changes before it is there
-    const size_t RL = (size_t)h->RL, words = NORM_STATS_WORDS(D);
-    const int cols_step = std::max(1, (obs ? D : 0) + (rew ? 1 : 0)), cols_reset = std::max(1, obs ? D : 0);
-    const size_t tiles = std::max(plan_norm_tiles(RL, cols_step), plan_norm_tiles(RL, cols_reset));
-    size_t total = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = total;
-        total = align256(total + bytes);
-        return at;
-    };
-    const size_t off_stats = carve(2 * words * 8), off_ret = carve(rew ? 2 * RL * 8 : 0), off_part = carve(tiles * (size_t)cols_step * 16), off_pn = carve(tiles * 4);
-    const size_t off_nv = carve(obs ? RL * D * 4 : 0), off_ns = carve((size_t)K * RL * D * 4), off_nr = carve(rew ? RL * 8 : 0);
+    const size_t words = NORM_STATS_WORDS(D);
+    const NormaliseLayout l = plan_normalise_layout((size_t)h->RL, D, K, obs, rew);
     HIPCHK(hipSetDevice(h->cfg.device));
     unsigned char* block = nullptr;
     DevTxn<HipApi> txn;
-    if (!txn.room(&block, total, 0)) FAIL(txn.code(), "imgenv_normalise_enable: %s", txn.error());
+    if (!txn.room(&block, l.total, 0)) FAIL(txn.code(), "imgenv_normalise_enable: %s", txn.error());
     std::vector<double> init(2 * words, 0.0);  // SB3's RunningMeanStd: count 1e-4, mean 0, var 1 -- in both words
     for (int q = 0; q < 2; q++) {
         double* s = init.data() + q * words;
@@ -4458,7 +4436,7 @@ extern "C" int imgenv_normalise_enable(imgenv_t* h, const imgenv_normalise_cfg* 
         s[3] = 1.0;
         for (int d = 0; d < D; d++) s[4 + D + d] = 1.0;
     }
-    if (const char* e = HipApi::memcpy(block + off_stats, init.data(), init.size() * 8, false)) FAIL(IMGENV_EDEVICE, "imgenv_normalise_enable: %s", e);
+    if (const char* e = HipApi::memcpy(block + l.stats, init.data(), init.size() * 8, false)) FAIL(IMGENV_EDEVICE, "imgenv_normalise_enable: %s", e);
     txn.commit(h->allocs);
     NormDev n;
     memset(&n, 0, sizeof(n));
@@ -4467,13 +4445,13 @@ extern "C" int imgenv_normalise_enable(imgenv_t* h, const imgenv_normalise_cfg* 
     n.rewards = w.step_rewards;
     n.is_clean = w.step_is_clean;
     n.dones = w.step_dones;
-    n.stats = (double*)(block + off_stats);
-    n.returns = rew ? (double*)(block + off_ret) : nullptr;
-    n.part = (double*)(block + off_part);
-    n.part_n = (uint32_t*)(block + off_pn);
-    n.norm_vector_states = obs ? (float*)(block + off_nv) : nullptr;
-    n.norm_state_stack = K ? (float*)(block + off_ns) : nullptr;
-    n.norm_rewards = rew ? (double*)(block + off_nr) : nullptr;
+    n.stats = (double*)(block + l.stats);
+    n.returns = rew ? (double*)(block + l.returns) : nullptr;
+    n.part = (double*)(block + l.part);
+    n.part_n = (uint32_t*)(block + l.part_n);
+    n.norm_vector_states = obs ? (float*)(block + l.norm_vector_states) : nullptr;
+    n.norm_state_stack = K ? (float*)(block + l.norm_state_stack) : nullptr;
+    n.norm_rewards = rew ? (double*)(block + l.norm_rewards) : nullptr;
     n.gamma = c->gamma; n.clip_obs = c->clip_obs; n.clip_reward = c->clip_reward; n.eps = c->eps;
     n.D = D;
     n.K = K;
@@ -4567,6 +4545,32 @@ extern "C" int imgenv_normalise_stats_set(imgenv_t* h, const imgenv_normalise_st
     return IMGENV_OK;
 }
 
+// ---- the fields a feature can copy rows of (csrc/obs_fields.h) ----
+// the catalogue of this handle: the sources are always in the working arena
+static void handle_obs_fields(const imgenv* h, ObsField (&f)[OBSF_COUNT]) {
+    ObsFacts a = {};
+    a.out = h->out;
+    a.ped_image_size[0] = h->cfg.ped_image_size[0];
+    a.ped_image_size[1] = h->cfg.ped_image_size[1];
+    a.stack = h->stack_out;
+    a.ped_vector_norm = h->post.norm;
+    if (h->norm_on) {  // (normalise.h's arrays; the stack only where the handle keeps one)
+        a.norm_vector_states = h->norm.norm_vector_states;
+        a.norm_state_stack = h->norm.norm_state_stack;
+        a.norm_K = h->norm.K;
+    }
+    obs_fields(a, f);
+}
+// the fields of a feature's `list` that `want` names, in the list's order: sel[], their row sizes and their count in n
+template <typename L, int N>
+static int select_obs_fields(const ObsField (&f)[OBSF_COUNT], const L (&list)[N], int want, const char* cfg_name, const L* (&sel)[N], size_t* row_bytes, int& n) {
+    int bad_bit = 0;
+    n = obs_fields_select(f, list, want, sel, &bad_bit);
+    if (n < 0) FAIL(IMGENV_EINVAL, "%s.fields: bit %d names a field of no bytes on this handle", cfg_name, bad_bit);
+    for (int k = 0; k < n; k++) row_bytes[k] = f[sel[k]->id].row_bytes;
+    return IMGENV_OK;
+}
+
 // ---- final observations (include/imgenv.h; the kernel is csrc/final_obs.h) ----
 extern "C" int imgenv_final_obs_enable(imgenv_t* h, const imgenv_final_obs_cfg* c, imgenv_final_obs_out* out) {
     // (the cfg first, as above)
@@ -4587,72 +4591,52 @@ extern "C" int imgenv_final_obs_enable(imgenv_t* h, const imgenv_final_obs_cfg* 
     if ((want & IMGENV_FINAL_STACKS) && !h->stack_on) FAIL(IMGENV_ESTATE, "IMGENV_FINAL_STACKS before imgenv_stack_enable");
     if ((want & IMGENV_FINAL_STACKS) && h->stack.n_fields == 0) FAIL(IMGENV_EINVAL, "IMGENV_FINAL_STACKS: no stack of this handle is deeper than 1");
     if ((want & IMGENV_FINAL_PED_NORM) && !(h->post_on && h->post.norm)) FAIL(IMGENV_ESTATE, "IMGENV_FINAL_PED_NORM before imgenv_obs_post_enable with IMGENV_OBS_PED_NORM");
-    // the sources, always in the working arena, with their row sizes and where the out struct keeps the copy's pointer
-    const imgenv_out& w = h->out;
-    const size_t NC = (size_t)w.view_h * w.view_w, NI = (size_t)w.image_h * w.image_w, B = (size_t)std::max(w.n_beams, 0);
-    const size_t NP = (size_t)h->cfg.ped_image_size[0] * h->cfg.ped_image_size[1];
+    // the fields in the block's order, with where the out struct keeps the copy's pointer
     imgenv_final_obs_out o = {};
     imgenv_normalise_out no = h->norm_out;  // (the normalised fields' pointers are handed out there: this struct keeps its layout)
-    struct Src {
-        int bit;
-        const void* src;
-        size_t row_bytes;
+    struct Slot {
+        int bit, id;
         void** slot;
     };
-    const imgenv_stack_out& so = h->stack_out;
-    const Src all[] = {
-        {IMGENV_FINAL_VECTOR_STATES, w.vector_states, (size_t)w.state_dim * 4, (void**)&o.vector_states},
-        {IMGENV_FINAL_SENSOR_MAPS, w.sensor_maps, NI * 2, (void**)&o.sensor_maps},
-        {IMGENV_FINAL_LASERS, w.lasers, B * 8, (void**)&o.lasers},
-        {IMGENV_FINAL_PED_VECTOR_STATES, w.ped_vector_states, (size_t)w.ped_vec_len * 4, (void**)&o.ped_vector_states},
-        {IMGENV_FINAL_PED_MAPS, w.ped_maps, 3 * NP * 4, (void**)&o.ped_maps},
-        {IMGENV_FINAL_IS_COLLISIONS, w.is_collisions, 1, (void**)&o.is_collisions},
-        {IMGENV_FINAL_IS_ARRIVES, w.is_arrives, 1, (void**)&o.is_arrives},
-        {IMGENV_FINAL_STEP_DS, w.step_ds, 8, (void**)&o.step_ds},
-        {IMGENV_FINAL_PED_MIN_DISTS, w.ped_min_dists, 8, (void**)&o.ped_min_dists},
-        {IMGENV_FINAL_VIEW_MAPS, w.view_maps, NC, (void**)&o.view_maps},
-        {IMGENV_FINAL_LASERS_RAW, w.lasers_raw, B * 4, (void**)&o.lasers_raw},
-        // (a stack of depth >= 2 is the library's or the caller's arena, never an alias of imgenv_out)
-        {IMGENV_FINAL_STACKS, so.image_depth >= 2 ? so.sensor_maps : nullptr, (size_t)std::max(so.image_depth, 0) * NI * 2, (void**)&o.stack_sensor_maps},
-        {IMGENV_FINAL_STACKS, so.state_depth >= 2 ? so.vector_states : nullptr, (size_t)std::max(so.state_depth, 0) * w.state_dim * 4, (void**)&o.stack_vector_states},
-        {IMGENV_FINAL_STACKS, so.laser_depth >= 2 ? so.lasers : nullptr, (size_t)std::max(so.laser_depth, 0) * B * 8, (void**)&o.stack_lasers},
-        {IMGENV_FINAL_PED_NORM, h->post.norm, (size_t)w.ped_vec_len * 4, (void**)&o.ped_vector_norm},
-        // (normalise.h's arrays; the stack only where the handle keeps one)
-        {IMGENV_FINAL_NORM_STATES, h->norm_on ? h->norm.norm_vector_states : nullptr, (size_t)w.state_dim * 4, (void**)&no.final_norm_vector_states},
-        {IMGENV_FINAL_NORM_STATES, h->norm_on ? h->norm.norm_state_stack : nullptr, (size_t)std::max(h->norm_on ? h->norm.K : 0, 0) * w.state_dim * 4,
-         (void**)&no.final_norm_state_stack},
+    const Slot list[] = {
+        {IMGENV_FINAL_VECTOR_STATES, OBSF_VECTOR_STATES, (void**)&o.vector_states},
+        {IMGENV_FINAL_SENSOR_MAPS, OBSF_SENSOR_MAPS, (void**)&o.sensor_maps},
+        {IMGENV_FINAL_LASERS, OBSF_LASERS, (void**)&o.lasers},
+        {IMGENV_FINAL_PED_VECTOR_STATES, OBSF_PED_VECTOR_STATES, (void**)&o.ped_vector_states},
+        {IMGENV_FINAL_PED_MAPS, OBSF_PED_MAPS, (void**)&o.ped_maps},
+        {IMGENV_FINAL_IS_COLLISIONS, OBSF_IS_COLLISIONS, (void**)&o.is_collisions},
+        {IMGENV_FINAL_IS_ARRIVES, OBSF_IS_ARRIVES, (void**)&o.is_arrives},
+        {IMGENV_FINAL_STEP_DS, OBSF_STEP_DS, (void**)&o.step_ds},
+        {IMGENV_FINAL_PED_MIN_DISTS, OBSF_PED_MIN_DISTS, (void**)&o.ped_min_dists},
+        {IMGENV_FINAL_VIEW_MAPS, OBSF_VIEW_MAPS, (void**)&o.view_maps},
+        {IMGENV_FINAL_LASERS_RAW, OBSF_LASERS_RAW, (void**)&o.lasers_raw},
+        {IMGENV_FINAL_STACKS, OBSF_STACK_SENSOR_MAPS, (void**)&o.stack_sensor_maps},
+        {IMGENV_FINAL_STACKS, OBSF_STACK_VECTOR_STATES, (void**)&o.stack_vector_states},
+        {IMGENV_FINAL_STACKS, OBSF_STACK_LASERS, (void**)&o.stack_lasers},
+        {IMGENV_FINAL_PED_NORM, OBSF_PED_VECTOR_NORM, (void**)&o.ped_vector_norm},
+        {IMGENV_FINAL_NORM_STATES, OBSF_NORM_VECTOR_STATES, (void**)&no.final_norm_vector_states},
+        {IMGENV_FINAL_NORM_STATES, OBSF_NORM_STATE_STACK, (void**)&no.final_norm_state_stack},
     };
-    static_assert(sizeof(all) / sizeof(all[0]) <= FINAL_MAX_FIELDS, "FINAL_MAX_FIELDS");
-    const Src* sel[FINAL_MAX_FIELDS];
+    static_assert(sizeof(list) / sizeof(list[0]) <= FINAL_MAX_FIELDS, "FINAL_MAX_FIELDS");
+    ObsField fields[OBSF_COUNT];
+    handle_obs_fields(h, fields);
+    const Slot* sel[sizeof(list) / sizeof(list[0])];
     size_t row_bytes[FINAL_MAX_FIELDS];
     int n = 0;
-    for (const Src& s : all) {
-        if (!(want & s.bit) || ((s.bit & (IMGENV_FINAL_STACKS | IMGENV_FINAL_PED_NORM | IMGENV_FINAL_NORM_STATES)) && !s.src)) continue;
-        if (!s.src || s.row_bytes == 0) FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields: bit %d names a field of no bytes on this handle", s.bit);
-        sel[n] = &s;
-        row_bytes[n++] = s.row_bytes;
-    }
+    RTRY(select_obs_fields(fields, list, want, "imgenv_final_obs_cfg", sel, row_bytes, n));
     const FinalPlan plan = plan_final_fields(row_bytes, n);
-    // one block: final_count, then the fields, each on a 256-byte boundary; zeroed.  Nothing of the handle changes before it is there.
-    const size_t RL = (size_t)h->RL;
-    size_t off[FINAL_MAX_FIELDS], total = align256(4 * RL);
-    for (int k = 0; k < n; k++) {
-        off[k] = total;
-        total = align256(total + RL * row_bytes[k]);
-    }
-    HIPCHK(hipSetDevice(h->cfg.device));
+    // one zeroed block (launch_plan.h).  Nothing of the handle changes before it is there.
+    const FinalObsLayout l = plan_final_obs_layout(row_bytes, n, (size_t)h->RL);
     unsigned char* block = nullptr;
-    DevTxn<HipApi> txn;
-    if (!txn.room(&block, total, 0)) FAIL(txn.code(), "imgenv_final_obs_enable: %s", txn.error());
-    txn.commit(h->allocs);
+    RTRY(feature_block(h, l.total, "imgenv_final_obs_enable", &block));
     FinalObsDev fo;
     memset(&fo, 0, sizeof(fo));
     fo.n_fields = plan.n_fields;
     fo.chunks_per_row = plan.chunks_per_row;
-    fo.count = (uint32_t*)block;
+    fo.count = (uint32_t*)(block + l.count);
     for (int k = 0; k < n; k++) {
-        fo.f[k].dst = (unsigned char*)block + off[k];
-        fo.f[k].src = (const unsigned char*)sel[k]->src;
+        fo.f[k].dst = block + l.field[k];
+        fo.f[k].src = (const unsigned char*)fields[sel[k]->id].src;
         fo.f[k].unit = plan.f[k].unit;
         fo.f[k].chunks = plan.f[k].chunks;
         *sel[k]->slot = fo.f[k].dst;
@@ -4699,81 +4683,52 @@ extern "C" int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* c, i
     if ((want & IMGENV_ROLLOUT_STACKS) && !h->stack_on) FAIL(IMGENV_ESTATE, "IMGENV_ROLLOUT_STACKS before imgenv_stack_enable");
     if ((want & IMGENV_ROLLOUT_STACKS) && h->stack.n_fields == 0) FAIL(IMGENV_EINVAL, "IMGENV_ROLLOUT_STACKS: no stack of this handle is deeper than 1");
     if ((want & IMGENV_ROLLOUT_PED_NORM) && !(h->post_on && h->post.norm)) FAIL(IMGENV_ESTATE, "IMGENV_ROLLOUT_PED_NORM before imgenv_obs_post_enable with IMGENV_OBS_PED_NORM");
-    // the sources, always in the working arena, with their row sizes and where the out struct keeps the ring's and the final list's pointers
+    // the fields in the block's order, with where the out struct keeps the ring's and the final list's pointers
     const imgenv_out& w = h->out;
-    const size_t NI = (size_t)w.image_h * w.image_w, B = (size_t)std::max(w.n_beams, 0);
-    const size_t NP = (size_t)h->cfg.ped_image_size[0] * h->cfg.ped_image_size[1];
     imgenv_rollout_out o = {};
     imgenv_normalise_out no = h->norm_out;  // (the normalised fields' ring and final pointers are handed out there)
-    struct Src {
-        int bit;
-        const void* src;
-        size_t row_bytes;
+    struct Slot {
+        int bit, id;
         void** ring;
         void** fin;
     };
-    const imgenv_stack_out& so = h->stack_out;
-    const Src all[] = {
-        {IMGENV_ROLLOUT_SENSOR_MAPS, w.sensor_maps, NI * 2, (void**)&o.obs_sensor_maps, (void**)&o.final_sensor_maps},
-        {IMGENV_ROLLOUT_VECTOR_STATES, w.vector_states, (size_t)w.state_dim * 4, (void**)&o.obs_vector_states, (void**)&o.final_vector_states},
-        {IMGENV_ROLLOUT_LASERS, w.lasers, B * 8, (void**)&o.obs_lasers, (void**)&o.final_lasers},
-        {IMGENV_ROLLOUT_PED_VECTOR_STATES, w.ped_vector_states, (size_t)w.ped_vec_len * 4, (void**)&o.obs_ped_vector_states, (void**)&o.final_ped_vector_states},
-        {IMGENV_ROLLOUT_PED_MAPS, w.ped_maps, 3 * NP * 4, (void**)&o.obs_ped_maps, (void**)&o.final_ped_maps},
-        {IMGENV_ROLLOUT_PED_NORM, h->post.norm, (size_t)w.ped_vec_len * 4, (void**)&o.obs_ped_vector_norm, (void**)&o.final_ped_vector_norm},
-        // (a stack of depth >= 2 is the library's or the caller's arena, never an alias of imgenv_out)
-        {IMGENV_ROLLOUT_STACKS, so.image_depth >= 2 ? so.sensor_maps : nullptr, (size_t)std::max(so.image_depth, 0) * NI * 2,
-         (void**)&o.obs_stack_sensor_maps, (void**)&o.final_stack_sensor_maps},
-        {IMGENV_ROLLOUT_STACKS, so.state_depth >= 2 ? so.vector_states : nullptr, (size_t)std::max(so.state_depth, 0) * w.state_dim * 4,
-         (void**)&o.obs_stack_vector_states, (void**)&o.final_stack_vector_states},
-        {IMGENV_ROLLOUT_STACKS, so.laser_depth >= 2 ? so.lasers : nullptr, (size_t)std::max(so.laser_depth, 0) * B * 8,
-         (void**)&o.obs_stack_lasers, (void**)&o.final_stack_lasers},
-        // (normalise.h's arrays; the stack only where the handle keeps one)
-        {IMGENV_ROLLOUT_NORM_STATES, h->norm_on ? h->norm.norm_vector_states : nullptr, (size_t)w.state_dim * 4, (void**)&no.rollout_obs_norm_vector_states,
-         (void**)&no.rollout_final_norm_vector_states},
-        {IMGENV_ROLLOUT_NORM_STATES, h->norm_on ? h->norm.norm_state_stack : nullptr, (size_t)std::max(h->norm_on ? h->norm.K : 0, 0) * w.state_dim * 4,
-         (void**)&no.rollout_obs_norm_state_stack, (void**)&no.rollout_final_norm_state_stack},
+    const Slot list[] = {
+        {IMGENV_ROLLOUT_SENSOR_MAPS, OBSF_SENSOR_MAPS, (void**)&o.obs_sensor_maps, (void**)&o.final_sensor_maps},
+        {IMGENV_ROLLOUT_VECTOR_STATES, OBSF_VECTOR_STATES, (void**)&o.obs_vector_states, (void**)&o.final_vector_states},
+        {IMGENV_ROLLOUT_LASERS, OBSF_LASERS, (void**)&o.obs_lasers, (void**)&o.final_lasers},
+        {IMGENV_ROLLOUT_PED_VECTOR_STATES, OBSF_PED_VECTOR_STATES, (void**)&o.obs_ped_vector_states, (void**)&o.final_ped_vector_states},
+        {IMGENV_ROLLOUT_PED_MAPS, OBSF_PED_MAPS, (void**)&o.obs_ped_maps, (void**)&o.final_ped_maps},
+        {IMGENV_ROLLOUT_PED_NORM, OBSF_PED_VECTOR_NORM, (void**)&o.obs_ped_vector_norm, (void**)&o.final_ped_vector_norm},
+        {IMGENV_ROLLOUT_STACKS, OBSF_STACK_SENSOR_MAPS, (void**)&o.obs_stack_sensor_maps, (void**)&o.final_stack_sensor_maps},
+        {IMGENV_ROLLOUT_STACKS, OBSF_STACK_VECTOR_STATES, (void**)&o.obs_stack_vector_states, (void**)&o.final_stack_vector_states},
+        {IMGENV_ROLLOUT_STACKS, OBSF_STACK_LASERS, (void**)&o.obs_stack_lasers, (void**)&o.final_stack_lasers},
+        {IMGENV_ROLLOUT_NORM_STATES, OBSF_NORM_VECTOR_STATES, (void**)&no.rollout_obs_norm_vector_states, (void**)&no.rollout_final_norm_vector_states},
+        {IMGENV_ROLLOUT_NORM_STATES, OBSF_NORM_STATE_STACK, (void**)&no.rollout_obs_norm_state_stack, (void**)&no.rollout_final_norm_state_stack},
     };
-    static_assert(sizeof(all) / sizeof(all[0]) <= ROLLOUT_TABLE_FIELDS, "ROLLOUT_TABLE_FIELDS");
-    const Src* sel[ROLLOUT_TABLE_FIELDS];
+    static_assert(sizeof(list) / sizeof(list[0]) <= ROLLOUT_TABLE_FIELDS, "ROLLOUT_TABLE_FIELDS");
+    ObsField fields[OBSF_COUNT];
+    handle_obs_fields(h, fields);
+    const Slot* sel[sizeof(list) / sizeof(list[0])];
     size_t row_bytes[ROLLOUT_TABLE_FIELDS];
     int n = 0;
-    for (const Src& s : all) {
-        if (!(want & s.bit) || ((s.bit & (IMGENV_ROLLOUT_STACKS | IMGENV_ROLLOUT_NORM_STATES)) && !s.src)) continue;  // (a stack of depth 1 is the field itself)
-        if (!s.src || s.row_bytes == 0) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields: bit %d names a field of no bytes on this handle", s.bit);
-        sel[n] = &s;
-        row_bytes[n++] = s.row_bytes;
-    }
-    // one block, every array on a 256-byte boundary, zeroed; nothing of the handle changes before it is there
-    size_t total = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = total;
-        total = align256(total + bytes);
-        return at;
-    };
-    size_t off_ring[ROLLOUT_TABLE_FIELDS], off_fin[ROLLOUT_TABLE_FIELDS];
-    for (int k = 0; k < n; k++) {
-        off_ring[k] = carve((T + 1) * RL * row_bytes[k]);
-        off_fin[k] = carve(F * row_bytes[k]);
-    }
-    const size_t off_actions = carve(T * RL * 12), off_rewards = carve(T * RL * 4), off_dones = carve(T * RL), off_clean = carve(T * RL);
-    const size_t off_info = carve(T * RL * 4), off_idx = carve((T + 1) * RL * 4), off_slot = carve(F * 4), off_row = carve(F * 4), off_n = carve(8);
-    HIPCHK(hipSetDevice(h->cfg.device));
+    RTRY(select_obs_fields(fields, list, want, "imgenv_rollout_cfg", sel, row_bytes, n));
+    // one zeroed block (launch_plan.h); nothing of the handle changes before it is there
+    const RolloutLayout l = plan_rollout_layout(row_bytes, n, RL, T, F);
     unsigned char* block = nullptr;
-    DevTxn<HipApi> txn;
-    if (!txn.room(&block, total, 0)) FAIL(txn.code(), "imgenv_rollout_enable: %s", txn.error());
-    txn.commit(h->allocs);
+    RTRY(feature_block(h, l.total, "imgenv_rollout_enable", &block));
     RolloutDev ro;
     memset(&ro, 0, sizeof(ro));
     ro.n_fields = n;
     for (int k = 0; k < n; k++) {
         const FinalFieldPlan f = plan_final_field(row_bytes[k]);
-        ro.f[k].ring = block + off_ring[k];
-        ro.f[k].fin = block + off_fin[k];
-        ro.f[k].src = (const unsigned char*)sel[k]->src;
+        ro.f[k].ring = block + l.ring[k];
+        ro.f[k].fin = block + l.fin[k];
+        ro.f[k].src = (const unsigned char*)fields[sel[k]->id].src;
         ro.f[k].unit = f.unit;
         ro.f[k].chunks = f.chunks;
         ro.chunks_per_row += f.chunks;
         h->roll_row_bytes[k] = row_bytes[k];
+        h->roll_field_id[k] = sel[k]->id;
         *sel[k]->ring = ro.f[k].ring;
         *sel[k]->fin = ro.f[k].fin;
     }
@@ -4782,15 +4737,15 @@ extern "C" int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* c, i
     ro.done_src = w.step_dones;
     ro.clean_src = w.step_is_clean;
     ro.info_src = w.step_dones_info;
-    o.actions = ro.actions = (float*)(block + off_actions);
-    o.rewards = ro.rewards = (float*)(block + off_rewards);
-    o.dones = ro.dones = block + off_dones;
-    o.is_clean = ro.is_clean = block + off_clean;
-    o.dones_info = ro.dones_info = (int32_t*)(block + off_info);
-    o.final_idx = ro.final_idx = (int32_t*)(block + off_idx);
-    o.final_slot = ro.final_slot = (int32_t*)(block + off_slot);
-    o.final_row = ro.final_row = (int32_t*)(block + off_row);
-    o.final_n = ro.final_n = (uint32_t*)(block + off_n);
+    o.actions = ro.actions = (float*)(block + l.actions);
+    o.rewards = ro.rewards = (float*)(block + l.rewards);
+    o.dones = ro.dones = block + l.dones;
+    o.is_clean = ro.is_clean = block + l.is_clean;
+    o.dones_info = ro.dones_info = (int32_t*)(block + l.dones_info);
+    o.final_idx = ro.final_idx = (int32_t*)(block + l.final_idx);
+    o.final_slot = ro.final_slot = (int32_t*)(block + l.final_slot);
+    o.final_row = ro.final_row = (int32_t*)(block + l.final_row);
+    o.final_n = ro.final_n = (uint32_t*)(block + l.final_n);
     ro.F = c->final_capacity;
     o.horizon = c->horizon;
     o.final_capacity = c->final_capacity;
@@ -4874,90 +4829,74 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
     }
     const int want = c->fields ? c->fields : (h->roll_cfg.fields & ~IMGENV_ROLLOUT_NORM_REWARDS);
     if (want & ~h->roll_cfg.fields) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: the rollout stores %d", c->fields, h->roll_cfg.fields);
-    // the ring's fields in its own order, each found again by its obs_ pointer
-    const imgenv_rollout_out& ro = h->roll_out;
-    struct Src {
-        int bit;
-        const void* ring;
-        size_t slot;  // of imgenv_minibatch_buffer, in pointers
+    // what the ring keeps, as a catalogue, and the buffers' fields in the ring's own order (imgenv_rollout_enable's list)
+    ObsField ring[OBSF_COUNT] = {};
+    for (int k = 0; k < h->roll.n_fields; k++) ring[h->roll_field_id[k]] = {h->roll.f[k].ring, h->roll_row_bytes[k]};
+    struct Slot {
+        int bit, id;
+        size_t slot;  // of MbBufferAll, in bytes
     };
-    const Src all[] = {
-        {IMGENV_ROLLOUT_SENSOR_MAPS, ro.obs_sensor_maps, offsetof(imgenv_minibatch_buffer, mb_sensor_maps)},
-        {IMGENV_ROLLOUT_VECTOR_STATES, ro.obs_vector_states, offsetof(imgenv_minibatch_buffer, mb_vector_states)},
-        {IMGENV_ROLLOUT_LASERS, ro.obs_lasers, offsetof(imgenv_minibatch_buffer, mb_lasers)},
-        {IMGENV_ROLLOUT_PED_VECTOR_STATES, ro.obs_ped_vector_states, offsetof(imgenv_minibatch_buffer, mb_ped_vector_states)},
-        {IMGENV_ROLLOUT_PED_MAPS, ro.obs_ped_maps, offsetof(imgenv_minibatch_buffer, mb_ped_maps)},
-        {IMGENV_ROLLOUT_PED_NORM, ro.obs_ped_vector_norm, offsetof(imgenv_minibatch_buffer, mb_ped_vector_norm)},
-        {IMGENV_ROLLOUT_STACKS, ro.obs_stack_sensor_maps, offsetof(imgenv_minibatch_buffer, mb_stack_sensor_maps)},
-        {IMGENV_ROLLOUT_STACKS, ro.obs_stack_vector_states, offsetof(imgenv_minibatch_buffer, mb_stack_vector_states)},
-        {IMGENV_ROLLOUT_STACKS, ro.obs_stack_lasers, offsetof(imgenv_minibatch_buffer, mb_stack_lasers)},
+    const Slot list[] = {
+        {IMGENV_ROLLOUT_SENSOR_MAPS, OBSF_SENSOR_MAPS, offsetof(imgenv_minibatch_buffer, mb_sensor_maps)},
+        {IMGENV_ROLLOUT_VECTOR_STATES, OBSF_VECTOR_STATES, offsetof(imgenv_minibatch_buffer, mb_vector_states)},
+        {IMGENV_ROLLOUT_LASERS, OBSF_LASERS, offsetof(imgenv_minibatch_buffer, mb_lasers)},
+        {IMGENV_ROLLOUT_PED_VECTOR_STATES, OBSF_PED_VECTOR_STATES, offsetof(imgenv_minibatch_buffer, mb_ped_vector_states)},
+        {IMGENV_ROLLOUT_PED_MAPS, OBSF_PED_MAPS, offsetof(imgenv_minibatch_buffer, mb_ped_maps)},
+        {IMGENV_ROLLOUT_PED_NORM, OBSF_PED_VECTOR_NORM, offsetof(imgenv_minibatch_buffer, mb_ped_vector_norm)},
+        {IMGENV_ROLLOUT_STACKS, OBSF_STACK_SENSOR_MAPS, offsetof(imgenv_minibatch_buffer, mb_stack_sensor_maps)},
+        {IMGENV_ROLLOUT_STACKS, OBSF_STACK_VECTOR_STATES, offsetof(imgenv_minibatch_buffer, mb_stack_vector_states)},
+        {IMGENV_ROLLOUT_STACKS, OBSF_STACK_LASERS, offsetof(imgenv_minibatch_buffer, mb_stack_lasers)},
         // (the normalised fields: their buffers' pointers are imgenv_normalise_out's, kept behind the public struct in MbBufferAll)
-        {IMGENV_ROLLOUT_NORM_STATES, h->norm_on ? h->norm_out.rollout_obs_norm_vector_states : nullptr, offsetof(MbBufferAll, mb_norm_vector_states)},
-        {IMGENV_ROLLOUT_NORM_STATES, h->norm_on ? h->norm_out.rollout_obs_norm_state_stack : nullptr, offsetof(MbBufferAll, mb_norm_state_stack)},
+        {IMGENV_ROLLOUT_NORM_STATES, OBSF_NORM_VECTOR_STATES, offsetof(MbBufferAll, mb_norm_vector_states)},
+        {IMGENV_ROLLOUT_NORM_STATES, OBSF_NORM_STATE_STACK, offsetof(MbBufferAll, mb_norm_state_stack)},
     };
-    static_assert(sizeof(all) / sizeof(all[0]) <= ROLLOUT_TABLE_FIELDS, "ROLLOUT_TABLE_FIELDS");
-    const size_t RL = (size_t)h->RL, T = (size_t)h->roll_cfg.horizon, B = (size_t)c->batch, NB = (size_t)c->buffers;
-    const size_t tiles = std::max(plan_mb_tiles(T * RL), plan_mb_stats_tiles(T * RL));
+    static_assert(sizeof(list) / sizeof(list[0]) <= ROLLOUT_TABLE_FIELDS, "ROLLOUT_TABLE_FIELDS");
+    const Slot* sel[sizeof(list) / sizeof(list[0])];
+    size_t row_bytes[ROLLOUT_TABLE_FIELDS];
+    int n = 0;
+    RTRY(select_obs_fields(ring, list, want, "imgenv_minibatch_cfg", sel, row_bytes, n));
+    if (n == 0) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: no field of the rollout", c->fields);
+    // one zeroed block (launch_plan.h); nothing of the handle changes before it is there
+    const size_t RL = (size_t)h->RL, T = (size_t)h->roll_cfg.horizon, NB = (size_t)c->buffers;
+    const MinibatchLayout l = plan_minibatch_layout(row_bytes, n, RL, T, (size_t)c->batch, NB);
+    unsigned char* block = nullptr;
+    RTRY(feature_block(h, l.total, "imgenv_rollout_minibatch_enable", &block));
     MbGatherDev g;
     memset(&g, 0, sizeof(g));
-    size_t row_bytes[ROLLOUT_TABLE_FIELDS], slot[ROLLOUT_TABLE_FIELDS];
-    for (int k = 0; k < h->roll.n_fields; k++)
-        for (const Src& s : all) {
-            if (!s.ring || s.ring != (const void*)h->roll.f[k].ring || !(want & s.bit)) continue;
-            MbGatherField& f = g.f[g.n_fields];
-            f.ring = h->roll.f[k].ring;
-            f.unit = h->roll.f[k].unit;
-            f.chunks = h->roll.f[k].chunks;
-            g.chunks_per_row += f.chunks;
-            row_bytes[g.n_fields] = h->roll_row_bytes[k];
-            slot[g.n_fields++] = s.slot;
-        }
-    if (g.n_fields == 0) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: no field of the rollout", c->fields);
-    // one block, every array on a 256-byte boundary, zeroed; nothing of the handle changes before it is there
-    size_t total = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = total;
-        total = align256(total + bytes);
-        return at;
-    };
-    const size_t off_valid = carve(T * RL * 4), off_order = carve(T * RL * 4), off_vn = carve(4), off_norm = carve(8);
-    const size_t off_tc = carve(tiles * 4), off_tb = carve(tiles * 4), off_part = carve(tiles * 8), off_mean = carve(8);
-    size_t off_f[IMGENV_MB_MAX_BUFFERS][ROLLOUT_TABLE_FIELDS], off_s[IMGENV_MB_MAX_BUFFERS][7];
-    for (int k = 0; k < g.n_fields; k++)  // (a field's buffers side by side: one strided view covers them)
-        for (size_t b = 0; b < NB; b++) off_f[b][k] = carve(B * row_bytes[k]);
-    const size_t scalar_bytes[7] = {B * 12, B * 4, B, B * 4, B * 4, B * 4, B * 4 * IMGENV_MB_MAX_SCALARS};
-    for (int q = 0; q < 7; q++)
-        for (size_t b = 0; b < NB; b++) off_s[b][q] = carve(scalar_bytes[q]);
-    HIPCHK(hipSetDevice(h->cfg.device));
-    unsigned char* block = nullptr;
-    DevTxn<HipApi> txn;
-    if (!txn.room(&block, total, 0)) FAIL(txn.code(), "imgenv_rollout_minibatch_enable: %s", txn.error());
-    txn.commit(h->allocs);
+    g.n_fields = n;
+    for (int k = 0; k < n; k++) {
+        const FinalFieldPlan f = plan_final_field(row_bytes[k]);  // (the ring's own chunking)
+        g.f[k].ring = (const unsigned char*)ring[sel[k]->id].src;
+        g.f[k].dst = (unsigned char*)(uintptr_t)sel[k]->slot;  // (which pointer of the buffer: mb_gather_args)
+        g.f[k].unit = f.unit;
+        g.f[k].chunks = f.chunks;
+        g.chunks_per_row += f.chunks;
+    }
     imgenv_minibatch_out o = {};
     o.horizon = h->roll_cfg.horizon;
     o.batch = c->batch;
     o.buffers = c->buffers;
     o.fields = want;
-    o.valid = (int32_t*)(block + off_valid);
-    o.order = (int32_t*)(block + off_order);
-    o.valid_n = (uint32_t*)(block + off_vn);
-    o.norm = (float*)(block + off_norm);
-    o.tile_count = (int32_t*)(block + off_tc);
-    o.tile_base = (int32_t*)(block + off_tb);
-    o.stat_part = (double*)(block + off_part);
-    o.stat_mean = (double*)(block + off_mean);
+    o.valid = (int32_t*)(block + l.valid);
+    o.order = (int32_t*)(block + l.order);
+    o.valid_n = (uint32_t*)(block + l.valid_n);
+    o.norm = (float*)(block + l.norm);
+    o.tile_count = (int32_t*)(block + l.tile_count);
+    o.tile_base = (int32_t*)(block + l.tile_base);
+    o.stat_part = (double*)(block + l.stat_part);
+    o.stat_mean = (double*)(block + l.stat_mean);
     for (size_t b = 0; b < NB; b++) {
         MbBufferAll& all_b = h->mb_all[b];
         all_b = MbBufferAll{};
         imgenv_minibatch_buffer& m = all_b.pub;
-        for (int k = 0; k < g.n_fields; k++) *(void**)((unsigned char*)&all_b + slot[k]) = block + off_f[b][k];
-        m.mb_actions = (float*)(block + off_s[b][0]);
-        m.mb_rewards = (float*)(block + off_s[b][1]);
-        m.mb_dones = block + off_s[b][2];
-        m.mb_dones_info = (int32_t*)(block + off_s[b][3]);
-        m.mb_index = (int32_t*)(block + off_s[b][4]);
-        m.mb_weight = (float*)(block + off_s[b][5]);
-        m.mb_scalars = (float*)(block + off_s[b][6]);
+        for (int k = 0; k < n; k++) *(void**)((unsigned char*)&all_b + sel[k]->slot) = block + l.field[b][k];
+        m.mb_actions = (float*)(block + l.scalar[b][MB_S_ACTIONS]);
+        m.mb_rewards = (float*)(block + l.scalar[b][MB_S_REWARDS]);
+        m.mb_dones = block + l.scalar[b][MB_S_DONES];
+        m.mb_dones_info = (int32_t*)(block + l.scalar[b][MB_S_DONES_INFO]);
+        m.mb_index = (int32_t*)(block + l.scalar[b][MB_S_INDEX]);
+        m.mb_weight = (float*)(block + l.scalar[b][MB_S_WEIGHT]);
+        m.mb_scalars = (float*)(block + l.scalar[b][MB_S_SCALARS]);
         o.buf[b] = m;
         if (h->norm_on) {
             h->norm_out.mb_norm_vector_states[b] = all_b.mb_norm_vector_states;
@@ -4971,7 +4910,6 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
     g.rewards = h->roll.rewards;
     g.dones = h->roll.dones;
     g.dones_info = h->roll.dones_info;
-    for (int k = 0; k < g.n_fields; k++) g.f[k].dst = (unsigned char*)(uintptr_t)slot[k];  // (which pointer of the buffer: mb_gather_args)
     h->mb_gather = g;
     h->mb_cfg = *c;
     h->mb_indexed = h->mb_shuffled = false;

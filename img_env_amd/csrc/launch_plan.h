@@ -563,6 +563,129 @@ inline LaunchShape plan_norm_apply_launch(const PlanHandle& h, const PlanChain& 
     return {(unsigned)std::min<size_t>(NORM_MAX_BLOCKS, std::max<size_t>(1, (plan_tail_rows(h, c) + per_block - 1) / per_block)), NORM_BLOCK, 0};
 }
 
+// ---------------------------------------------------------------------------------------- the features' device blocks
+// A feature's arrays live in ONE zeroed allocation, every array on a 256-byte boundary (so a row of any field starts on a multiple
+// of its unit).  The layouts are fixed here, device-free: the enable functions of imgenv_hip.hip allocate `total` bytes and hand
+// out block + offset; tests/host/field_rows_check.cpp pins every offset.
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct Carve {
+    size_t total = 0;
+    size_t take(size_t bytes) {  // the offset of the next array (one of no bytes takes no room: its offset is the next one's)
+        const size_t at = total;
+        total = align256(total + bytes);
+        return at;
+    }
+};
+
+// imgenv_stack_enable: the stacks of sensor_maps, vector_states, lasers, [RL][depth][frame]; a field of depth < 2 takes no room
+struct StackPlan {
+    int depth[3];          // effective depths (0 = not stacked)
+    size_t frame_bytes[3];
+    size_t off[3], total;
+};
+inline StackPlan plan_stack(size_t image_cells, int state_dim, int beams, int image_batch, int state_batch, int laser_batch, size_t RL) {
+    StackPlan p;
+    p.depth[0] = image_batch > 0 ? image_batch : 0;
+    p.depth[1] = state_batch > 0 ? state_batch : 0;
+    p.depth[2] = laser_batch >= 0 && beams > 0 ? std::max(laser_batch, 1) : 0;
+    p.frame_bytes[0] = image_cells * 2;
+    p.frame_bytes[1] = (size_t)state_dim * 4;
+    p.frame_bytes[2] = (size_t)beams * 8;
+    Carve c;
+    for (int k = 0; k < 3; k++) p.off[k] = c.take(p.depth[k] >= 2 ? RL * p.depth[k] * p.frame_bytes[k] : 0);
+    p.total = c.total;
+    return p;
+}
+
+// imgenv_final_obs_enable: final_count [RL], then the n selected fields [RL][row bytes] in the caller's order
+struct FinalObsLayout {
+    size_t count, field[FINAL_MAX_FIELDS], total;
+};
+inline FinalObsLayout plan_final_obs_layout(const size_t* row_bytes, int n, size_t RL) {
+    FinalObsLayout l = {};
+    Carve c;
+    l.count = c.take(4 * RL);
+    for (int k = 0; k < n; k++) l.field[k] = c.take(RL * row_bytes[k]);
+    l.total = c.total;
+    return l;
+}
+
+// imgenv_rollout_enable (rollout.h has the shapes): per selected field its ring and its final list, then the transitions' arrays
+struct RolloutLayout {
+    size_t ring[ROLLOUT_TABLE_FIELDS], fin[ROLLOUT_TABLE_FIELDS];
+    size_t actions, rewards, dones, is_clean, dones_info, final_idx, final_slot, final_row, final_n, total;
+};
+inline RolloutLayout plan_rollout_layout(const size_t* row_bytes, int n, size_t RL, size_t T, size_t F) {
+    RolloutLayout l = {};
+    Carve c;
+    for (int k = 0; k < n; k++) {
+        l.ring[k] = c.take((T + 1) * RL * row_bytes[k]);
+        l.fin[k] = c.take(F * row_bytes[k]);
+    }
+    l.actions = c.take(T * RL * 12);
+    l.rewards = c.take(T * RL * 4);
+    l.dones = c.take(T * RL);
+    l.is_clean = c.take(T * RL);
+    l.dones_info = c.take(T * RL * 4);
+    l.final_idx = c.take((T + 1) * RL * 4);
+    l.final_slot = c.take(F * 4);
+    l.final_row = c.take(F * 4);
+    l.final_n = c.take(8);
+    l.total = c.total;
+    return l;
+}
+
+// imgenv_rollout_minibatch_enable (minibatch.h): the index, the statistics' scratch, then per gathered field and per scalar array
+// its `buffers` copies side by side (one strided view covers a field's buffers)
+enum { MB_S_ACTIONS, MB_S_REWARDS, MB_S_DONES, MB_S_DONES_INFO, MB_S_INDEX, MB_S_WEIGHT, MB_S_SCALARS, MB_S_COUNT };
+struct MinibatchLayout {
+    size_t valid, order, valid_n, norm, tile_count, tile_base, stat_part, stat_mean;
+    size_t field[IMGENV_MB_MAX_BUFFERS][ROLLOUT_TABLE_FIELDS], scalar[IMGENV_MB_MAX_BUFFERS][MB_S_COUNT], total;
+};
+inline MinibatchLayout plan_minibatch_layout(const size_t* row_bytes, int n, size_t RL, size_t T, size_t batch, size_t buffers) {
+    MinibatchLayout l = {};
+    const size_t tiles = std::max(plan_mb_tiles(T * RL), plan_mb_stats_tiles(T * RL)), B = batch;
+    Carve c;
+    l.valid = c.take(T * RL * 4);
+    l.order = c.take(T * RL * 4);
+    l.valid_n = c.take(4);
+    l.norm = c.take(8);
+    l.tile_count = c.take(tiles * 4);
+    l.tile_base = c.take(tiles * 4);
+    l.stat_part = c.take(tiles * 8);
+    l.stat_mean = c.take(8);
+    for (int k = 0; k < n; k++)
+        for (size_t b = 0; b < buffers; b++) l.field[b][k] = c.take(B * row_bytes[k]);
+    const size_t scalar_bytes[MB_S_COUNT] = {B * 12, B * 4, B, B * 4, B * 4, B * 4, B * 4 * IMGENV_MB_MAX_SCALARS};
+    for (int q = 0; q < MB_S_COUNT; q++)
+        for (size_t b = 0; b < buffers; b++) l.scalar[b][q] = c.take(scalar_bytes[q]);
+    l.total = c.total;
+    return l;
+}
+
+// imgenv_normalise_enable (normalise.h): D = state_dim, K = the depth of the normalised state stack (0: none), obs / rew = the
+// cfg's IMGENV_NORM_OBS / IMGENV_NORM_REWARD.  An array the flags leave out has no bytes.
+#define NORM_STATS_WORDS(D) (4 + 2 * (size_t)(D))
+struct NormaliseLayout {
+    size_t stats, returns, part, part_n, norm_vector_states, norm_state_stack, norm_rewards, total;
+};
+inline NormaliseLayout plan_normalise_layout(size_t RL, int D, int K, bool obs, bool rew) {
+    NormaliseLayout l = {};
+    // (the columns of a step's launch -- the observed states and the return -- and of a reset chain's)
+    const int cols_step = std::max(1, (obs ? D : 0) + (rew ? 1 : 0)), cols_reset = std::max(1, obs ? D : 0);
+    const size_t tiles = std::max(plan_norm_tiles(RL, cols_step), plan_norm_tiles(RL, cols_reset));
+    Carve c;
+    l.stats = c.take(2 * NORM_STATS_WORDS(D) * 8);
+    l.returns = c.take(rew ? 2 * RL * 8 : 0);
+    l.part = c.take(tiles * (size_t)cols_step * 16);
+    l.part_n = c.take(tiles * 4);
+    l.norm_vector_states = c.take(obs ? RL * D * 4 : 0);
+    l.norm_state_stack = c.take((size_t)K * RL * D * 4);
+    l.norm_rewards = c.take(rew ? RL * 8 : 0);
+    l.total = c.total;
+    return l;
+}
+
 // ---------------------------------------------------------------------------------------- in front of the chain: k_actions
 // imgenv_actions_decode (actions.h): one lane per local robot, every wavefront whole (the ballot that counts bad rows runs on all
 // 64 lanes), no cap and no stride: 2^19 robots are 2048 blocks

@@ -39,8 +39,9 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "field_rows.h"   // FieldChunk16
 #include "launch_plan.h"  // MB_*, ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS, ROLLOUT_TABLE_FIELDS
-#include "rollout.h"      // RolloutChunk16 / RolloutChunk8, ROLLOUT_UNROLL
+#include "rollout.h"      // ROLLOUT_UNROLL
 
 #define MB_MAX_SCALARS 6  // (IMGENV_MB_MAX_SCALARS)
 
@@ -65,7 +66,7 @@ struct MbIndexDev {
 TAIL_HD uint32_t mb_flags16(const uint8_t* clean, size_t total, size_t first) {
     uint32_t mask = 0;
     if (first + MB_LANE_FLAGS <= total) {
-        const RolloutChunk16 q = *(const RolloutChunk16*)(clean + first);
+        const FieldChunk16 q = *(const FieldChunk16*)(clean + first);
         const uint32_t w[4] = MB_WORDS(q);
         ROLLOUT_UNROLL
         for (int i = 0; i < 4; i++) {
@@ -222,16 +223,6 @@ TAIL_HD void mb_gather_chunk(const unsigned char* ring, unsigned char* dst, uint
     if (k >= 0) v = ((const T*)ring)[(size_t)k * chunks + c];
     ((T*)dst)[i * (size_t)chunks + c] = v;
 }
-template <int K>
-TAIL_HD void mb_gather_field(const MbGatherDev& g, uint32_t& c, const unsigned char*& ring, unsigned char*& dst, uint32_t& chunks, uint32_t& unit) {
-    if constexpr (K < ROLLOUT_TABLE_FIELDS) {
-        if (K < g.n_fields && c >= chunks) {
-            c -= chunks;
-            ring = g.f[K].ring; dst = g.f[K].dst; chunks = g.f[K].chunks; unit = g.f[K].unit;
-            mb_gather_field<K + 1>(g, c, ring, dst, chunks, unit);
-        }
-    }
-}
 template <int S>
 TAIL_HD void mb_gather_scalars(const MbGatherDev& g, int32_t k, size_t i) {
     if constexpr (S < MB_MAX_SCALARS) {
@@ -275,17 +266,8 @@ TAIL_HD void mb_gather_item(const MbGatherDev& g, size_t t) {
         g.mb_weight[i] = k >= 0 ? 1.0f : 0.0f;
         mb_gather_scalars<0>(g, k, i);
     }
-    const unsigned char* ring = g.f[0].ring;
-    unsigned char* dst = g.f[0].dst;
-    uint32_t chunks = g.f[0].chunks, unit = g.f[0].unit;
-    mb_gather_field<1>(g, c, ring, dst, chunks, unit);
-    switch (unit) {
-        case 16: mb_gather_chunk<RolloutChunk16>(ring, dst, chunks, k, i, c); break;
-        case 8: mb_gather_chunk<RolloutChunk8>(ring, dst, chunks, k, i, c); break;
-        case 4: mb_gather_chunk<uint32_t>(ring, dst, chunks, k, i, c); break;
-        case 2: mb_gather_chunk<uint16_t>(ring, dst, chunks, k, i, c); break;
-        default: mb_gather_chunk<uint8_t>(ring, dst, chunks, k, i, c); break;
-    }
+    const MbGatherField f = field_walk(g.f, g.n_fields, c);
+    field_dispatch(f.unit, [&](auto chunk) { mb_gather_chunk<typename decltype(chunk)::type>(f.ring, f.dst, f.chunks, k, i, c); });
 }
 
 #if defined(__HIPCC__)

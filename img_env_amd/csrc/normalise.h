@@ -45,12 +45,11 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "launch_plan.h"  // NORM_*
+#include "launch_plan.h"  // NORM_*, NORM_STATS_WORDS
 #include "rollout.h"      // ROLLOUT_UNROLL
 #include "tail_rows.h"
 
 #define NORM_WAVES (NORM_BLOCK / WAVE)
-#define NORM_STATS_WORDS(D) (4 + 2 * (size_t)(D))
 
 struct NormDev {
     // what a chain has just written (the working arena's imgenv_out rows, imgenv_stack_out's state stack)

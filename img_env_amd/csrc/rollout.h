@@ -21,8 +21,8 @@
 // pointing at slot n: the copy of slot n into slot 0.
 //
 // A row of a field is cut into chunks of 16 / 8 / 4 / 2 / 1 bytes (launch_plan.h: plan_final_field), one lane per chunk, a flat
-// grid-stride loop over rows x chunks per row, the field table by value in the arguments and selected with constant indices, as in
-// final_obs.h.  No LDS, no scratch.
+// grid-stride loop over rows x chunks per row, the field table by value in the arguments and selected with constant indices
+// (field_rows.h).  No LDS, no scratch.
 //
 // Algorithmic bytes per row: a step reads and writes the selected rows once, + 12 + 8 + 1 + 1 + 4 read and 12 + 4 + 1 + 1 + 4 written;
 // a reset chain reads the live rows and (e < F) slot n's, writes both, + 4 (+ 8) for the index.
@@ -36,6 +36,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "field_rows.h"
 #include "launch_plan.h"  // ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS, ROLLOUT_TABLE_FIELDS, GAE_BLOCK, GAE_BATCH
 #include "tail_rows.h"
 
@@ -79,19 +80,6 @@ struct RolloutDev {
     TailRows rows;            // the robots of the chain in hand
 };
 
-#if defined(__HIPCC__)
-// (vector types: a struct of four words held across the second load was given a private array, which the compiler put into LDS)
-typedef uint4 RolloutChunk16;
-typedef uint2 RolloutChunk8;
-#else
-struct alignas(16) RolloutChunk16 {
-    uint32_t v[4];
-};
-struct alignas(8) RolloutChunk8 {
-    uint32_t v[2];
-};
-#endif
-
 // chunk c of `row`: a step stores the live chunk in `slot`; a reset chain first moves what the slot holds into final entry e (`keep`)
 template <typename T, bool RESTART>
 TAIL_HD void rollout_chunk(unsigned char* ring, unsigned char* fin, const unsigned char* src, uint32_t chunks, size_t at_ring, size_t row,
@@ -103,19 +91,6 @@ TAIL_HD void rollout_chunk(unsigned char* ring, unsigned char* fin, const unsign
         ((T*)fin)[e * (size_t)chunks + c] = old;
     }
     *at = live;
-}
-
-// the field chunk `c` of a row falls into, from field K on (final_obs.h's walk: every index is a constant)
-template <int K>
-TAIL_HD void rollout_field(const RolloutDev& ro, uint32_t& c, unsigned char*& ring, unsigned char*& fin, const unsigned char*& src, uint32_t& chunks,
-                           uint32_t& unit) {
-    if constexpr (K < ROLLOUT_TABLE_FIELDS) {
-        if (K < ro.n_fields && c >= chunks) {
-            c -= chunks;
-            ring = ro.f[K].ring; fin = ro.f[K].fin; src = ro.f[K].src; chunks = ro.f[K].chunks; unit = ro.f[K].unit;
-            rollout_field<K + 1>(ro, c, ring, fin, src, chunks, unit);
-        }
-    }
 }
 
 // item t of a launch: chunk t % chunks_per_row of the (t / chunks_per_row)-th covered row.  `base`: final_n[turn & 1] (RESTART)
@@ -149,19 +124,10 @@ TAIL_HD void rollout_item(const RolloutDev& ro, bool listed, uint32_t base, size
             ro.dones_info[at] = info;
         }
     }
-    // (member by member with constant indices: selects on scalar kernel arguments, no indexed copy of the struct)
-    unsigned char* ring = ro.f[0].ring;
-    unsigned char* fin = ro.f[0].fin;
-    const unsigned char* src = ro.f[0].src;
-    uint32_t chunks = ro.f[0].chunks, unit = ro.f[0].unit;
-    rollout_field<1>(ro, c, ring, fin, src, chunks, unit);
-    switch (unit) {
-        case 16: rollout_chunk<RolloutChunk16, RESTART>(ring, fin, src, chunks, at_ring, row, e, keep, c); break;
-        case 8: rollout_chunk<RolloutChunk8, RESTART>(ring, fin, src, chunks, at_ring, row, e, keep, c); break;
-        case 4: rollout_chunk<uint32_t, RESTART>(ring, fin, src, chunks, at_ring, row, e, keep, c); break;
-        case 2: rollout_chunk<uint16_t, RESTART>(ring, fin, src, chunks, at_ring, row, e, keep, c); break;
-        default: rollout_chunk<uint8_t, RESTART>(ring, fin, src, chunks, at_ring, row, e, keep, c); break;
-    }
+    const RolloutField f = field_walk(ro.f, ro.n_fields, c);
+    field_dispatch(f.unit, [&](auto chunk) {
+        rollout_chunk<typename decltype(chunk)::type, RESTART>(f.ring, f.fin, f.src, f.chunks, at_ring, row, e, keep, c);
+    });
 }
 
 // one thread of a reset chain's launch: the entries so far, into the word the NEXT reset chain reads

@@ -17,6 +17,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "field_rows.h"
 #include "launch_plan.h"  // STACK_BLOCK, STACK_MAX_BLOCKS
 #include "tail_rows.h"
 
@@ -27,7 +28,7 @@ struct StackField {
     unsigned char* stack;        // [RL][depth][frame_bytes]
     const unsigned char* frame;  // [RL][frame_bytes]: the field's imgenv_out array in the working arena
     uint32_t frame_bytes;
-    uint32_t unit;               // 16 | 8 | 4 | 2: the largest power of two dividing frame_bytes (both bases are 256-byte aligned)
+    uint32_t unit;               // 16 | 8 | 4 | 2: plan_final_field's, never 1 (both bases are 256-byte aligned)
     uint32_t chunks;             // frame_bytes / unit
     int32_t depth;               // >= 2
 };
@@ -74,24 +75,9 @@ __global__ __launch_bounds__(STACK_BLOCK) void k_stack(const StackDev sd) {
         const size_t m = t / sd.chunks_per_robot;
         uint32_t c = (uint32_t)(t - m * sd.chunks_per_robot);
         const size_t row = tail_rows_row(sd.rows, listed, m);
-        // (member by member: selects on scalar kernel arguments, no indexed copy of the struct)
-        unsigned char* stack = sd.f[0].stack;
-        const unsigned char* frame = sd.f[0].frame;
-        uint32_t chunks = sd.f[0].chunks, unit = sd.f[0].unit;
-        int K = sd.f[0].depth;
-        if (sd.n_fields > 1 && c >= chunks) {
-            c -= chunks;
-            stack = sd.f[1].stack; frame = sd.f[1].frame; chunks = sd.f[1].chunks; unit = sd.f[1].unit; K = sd.f[1].depth;
-            if (sd.n_fields > 2 && c >= chunks) {
-                c -= chunks;
-                stack = sd.f[2].stack; frame = sd.f[2].frame; chunks = sd.f[2].chunks; unit = sd.f[2].unit; K = sd.f[2].depth;
-            }
-        }
-        switch (unit) {
-            case 16: stack_chunk<uint4, RESTART>(stack, frame, chunks, K, row, c); break;
-            case 8: stack_chunk<uint2, RESTART>(stack, frame, chunks, K, row, c); break;
-            case 4: stack_chunk<uint32_t, RESTART>(stack, frame, chunks, K, row, c); break;
-            default: stack_chunk<uint16_t, RESTART>(stack, frame, chunks, K, row, c); break;
-        }
+        const StackField f = field_walk(sd.f, sd.n_fields, c);
+        field_dispatch<2>(f.unit, [&](auto chunk) {
+            stack_chunk<typename decltype(chunk)::type, RESTART>(f.stack, f.frame, f.chunks, f.depth, row, c);
+        });
     }
 }

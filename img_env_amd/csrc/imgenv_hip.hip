@@ -21,6 +21,8 @@
 #include "cv_resize.h"
 #include "spawn_host.h"
 #include "launch_plan.h"
+#include "out_fields.h"
+#include "create_plan.h"
 #include "obs_fields.h"
 #include "kernels.h"
 #include "world.h"
@@ -451,74 +453,13 @@ extern "C" int32_t imgenv_abi_version(void) { return IMGENV_ABI_VERSION; }
 extern "C" const char* imgenv_last_error(void) { return g_err; }
 
 // ---------------------------------------------------------------------------------------- arena
-struct OutField {
-    size_t offset, bytes;
-};
-struct ArenaPlan {  // (align256: launch_plan.h)
-    size_t total = 0;
-    size_t off[40];
-    int n = 0;
-    size_t add(size_t bytes) {
-        off[n] = total;
-        total = align256(total + (bytes ? bytes : 1));
-        return off[n++];
-    }
-};
-
-static void plan_arena(const imgenv_cfg& c, const ViewGeom& g, int RL, ArenaPlan& p) {
-    const size_t R = (size_t)RL, NC = (size_t)g.Hv * g.Wv, B = (size_t)(g.B > 0 ? g.B : 1);
-    const size_t PV = 1 + (size_t)c.ped_vec_dim * c.max_ped, NP = (size_t)c.ped_image_size[0] * c.ped_image_size[1];
-    const size_t P = (size_t)(c.n_peds > 0 ? c.n_peds : 1);
-    p.add(R * c.state_dim * 4);  // 0 vector_states
-    p.add(R * NC);               // 1 view_maps
-    p.add(R * (size_t)c.image_size[0] * (size_t)c.image_size[1] * 2);  // 2 sensor_maps [image_h][image_w] f16
-    p.add(R * B * 4);            // 3 lasers_raw
-    p.add(R * B * 8);            // 4 lasers
-    p.add(R * PV * 4);           // 5 ped_vector_states
-    p.add(R * 3 * NP * 4);       // 6 ped_maps
-    p.add(R);                    // 7 is_collisions
-    p.add(R);                    // 8 is_arrives
-    p.add(R * 8);                // 9 step_ds
-    p.add(R * 8);                // 10 ped_min_dists
-    p.add(R * 4);                // 11 base_rewards
-    p.add(R);                    // 12 base_dones
-    p.add(R * 8);                // 13 rewards
-    p.add(R);                    // 14 dones
-    p.add(R * 4);                // 15 dones_info
-    p.add(R);                    // 16 is_clean
-    p.add(R * 24);               // 17 robot_pose
-    p.add(P * 32);               // 18 ped_state
-    p.add(16);                   // 19 counters
-    p.add((size_t)c.n_robots * IMGENV_RECORD_DOUBLES * 8);  // 20 records
-    p.add(R * 8);                // 21 paper_rewards
-    p.add(R * 8);                // 22 step_rewards
-    p.add(R);                    // 23 step_dones
-    p.add(R * 4);                // 24 step_dones_info
-    p.add(R);                    // 25 step_is_clean
-    p.add(R);                    // 26 step_is_arrives
-    p.add(R);                    // 27 step_is_collisions
-    p.add(R);                    // 28 step_all_down
-    const bool extras = (c.flags & IMGENV_FLAG_AGENT_STATE_EXTRAS) != 0;
-    p.add(extras ? R * B * 4 : 0);  // 29 hits_x
-    p.add(extras ? R * B * 4 : 0);  // 30 hits_y
-    p.add(extras ? R * IMGENV_ANGULAR_BINS * 4 : 0);  // 31 angular_map
-}
-
-static int shard_of(const imgenv_cfg& c, int& r0, int& r1) {
-    r0 = c.robot_begin;
-    r1 = c.robot_end;
-    if (r0 == 0 && r1 == 0) r1 = c.n_robots;
-    if (r0 < 0 || r1 > c.n_robots || r0 >= r1) return -1;
-    return 0;
-}
-
+// (the arrays, their order and their sizes: out_fields.h)
 extern "C" int64_t imgenv_arena_bytes(const imgenv_cfg* cfg) {
     if (!cfg || cfg->struct_size != (int32_t)sizeof(imgenv_cfg)) return -1;
     int r0, r1;
     if (shard_of(*cfg, r0, r1)) return -1;
-    ArenaPlan p;
-    plan_arena(*cfg, make_view_geom(*cfg), r1 - r0, p);
-    return (int64_t)p.total;
+    const ViewGeom g = make_view_geom(*cfg);
+    return (int64_t)plan_arena(out_facts(*cfg, g.Hv, g.Wv, g.B, r1 - r0)).total;
 }
 
 // ---------------------------------------------------------------------------------------- helpers
@@ -570,23 +511,10 @@ static bool any_world_reset(const imgenv* h) {
     for (char r : h->world_ready) any = any || r;
     return any;
 }
-// inside imgenv_create once the handle exists: a failing HIP call must not leak the handle and what it has allocated so far
-#define HIPCHK_H(expr)                                                                                        \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess) {                                                                               \
-            snprintf(g_err, sizeof(g_err), "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            imgenv_destroy(h);                                                                                \
-            return IMGENV_EDEVICE;                                                                            \
-        }                                                                                                     \
-    } while (0)
-#define TRY(expr)              \
-    do {                       \
-        int rc_ = (expr);      \
-        if (rc_) {             \
-            imgenv_destroy(h); \
-            return rc_;        \
-        }                      \
+// (an error inside a create phase or a reset is handed up: imgenv_create destroys the half-built handle, a reset leaves it alive)
+#define RTRY(expr)                   \
+    do {                             \
+        if (int rc_ = (expr)) return rc_; \
     } while (0)
 
 extern "C" void imgenv_destroy(imgenv_t* h) {
@@ -733,192 +661,134 @@ static void tile_crop(const uint8_t* map, int Hg, int Wg, uint32_t wt, size_t cr
 }
 
 // ---------------------------------------------------------------------------------------- create
-extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, int32_t Hg, int32_t Wg,
-                             imgenv_t** out) {
-    if (!cfg || !static_map || !out) FAIL(IMGENV_EINVAL, "null argument");
-    if (cfg->abi_version != IMGENV_ABI_VERSION || cfg->struct_size != (int32_t)sizeof(imgenv_cfg))
-        FAIL(IMGENV_EINVAL, "imgenv_cfg ABI mismatch (version %d size %d, want %d %d)", cfg->abi_version,
-             cfg->struct_size, IMGENV_ABI_VERSION, (int)sizeof(imgenv_cfg));
-    if (cfg->n_robots < 1 || cfg->n_peds < 0 || Hg < 1 || Wg < 1) FAIL(IMGENV_EINVAL, "bad sizes");
-    const int W = cfg->n_worlds > 1 ? cfg->n_worlds : 1;
-    if (cfg->n_robots % W || cfg->n_peds % W)
-        FAIL(IMGENV_EINVAL, "n_robots %d and n_peds %d must be multiples of n_worlds %d", cfg->n_robots, cfg->n_peds, W);
-    if (cfg->n_peds / W > cfg->max_ped)
-        FAIL(IMGENV_EINVAL, "n_peds %d > max_ped %d (IndexError in yaml_env.py:401)", cfg->n_peds / W, cfg->max_ped);
-    if (cfg->n_peds / W > 65000) FAIL(IMGENV_EINVAL, "more than 65000 pedestrians in one world unsupported");
-    if (W > 1 && (((size_t)Hg * Wg + 15) & ~(size_t)15) * (size_t)W >= ((size_t)1 << 32))
-        FAIL(IMGENV_EINVAL, "n_worlds x map cells must stay below 2^32");
-    if (cfg->n_robots >= (int)OWNER_MULTI) FAIL(IMGENV_EINVAL, "more than 2^24 - 3 robots unsupported");
-    if (cfg->image_size[0] < 1 || cfg->image_size[1] < 1) FAIL(IMGENV_EINVAL, "bad image_size");
-    if (cfg->state_dim < 3 || cfg->state_dim > 5) FAIL(IMGENV_EINVAL, "state_dim must be 3, 4 or 5");
-    if (cfg->ped_vec_dim != 7) FAIL(IMGENV_EINVAL, "ped_vec_dim must be 7");
-    if (cfg->ped_scene_type == IMGENV_SCENE_PEDSIM) {
-        const int n_sfm = (cfg->n_peds + (cfg->relation_ped_robo == 1 ? cfg->n_robots : 0)) / W;  // one crowd (one PedScene) per world
-        if (cfg->relation_ped_robo == 1 && cfg->n_robots / W > 8)
-            FAIL(IMGENV_EINVAL, "pedscene with relation_ped_robo=1 and more than 8 robots: the reference node recurses forever in "
-                                "Ttree::addAgent (all robot Tagents start at (0,0,0), ped_tree.cpp:65-96)");
-        if (n_sfm > SFM_MAX_AGENTS) FAIL(IMGENV_EINVAL, "pedscene crowds larger than %d agents are not supported", SFM_MAX_AGENTS);
-    }
-    int r0, r1;
-    if (shard_of(*cfg, r0, r1)) FAIL(IMGENV_EINVAL, "bad robot shard [%d,%d)", cfg->robot_begin, cfg->robot_end);
-    // The lottery only ever has an effect in the ERVO scene (rs_ / ps_ are ignored by the others, img_env.cpp:343).
-    const bool beep_on = cfg->ped_scene_type == IMGENV_SCENE_ERVO && cfg->n_peds > 0 && cfg->beep_r > 0 && cfg->ped_ca_p > 0;
-    if (beep_on && r1 - r0 != cfg->n_robots)
-        FAIL(IMGENV_EINVAL, "beep_r / ped_ca_p > 0 in a robot shard: the beep lottery needs every robot's action on every rank");
-    if (W > 1 && r1 - r0 != cfg->n_robots)
-        FAIL(IMGENV_EINVAL, "n_worlds > 1 cannot be combined with a robot shard: give each rank whole worlds (its own handle)");
-    const ViewGeom g = make_view_geom(*cfg);
-    if (g.Hv < 1 || g.Wv < 1 || g.Hv > 4096 || g.Wv > 4096) FAIL(IMGENV_EINVAL, "view of %d x %d cells unsupported", g.Hv, g.Wv);
-    if (g.B > 65535) FAIL(IMGENV_EINVAL, "more than 65535 beams unsupported");
-    // cv2.resize(view, (image_size[0], image_size[1]), INTER_CUBIC) (yaml_env.py:431-438): dsize = (width, height)
-    const bool view_resize = cfg->image_size[0] != g.Wv || cfg->image_size[1] != g.Hv;
-    // GridMap::read_image (grid_map.cpp:28-38): the image is resized (INTER_LINEAR) to the view resolution
-    std::vector<uint8_t> resized_map;
-    int Hg_in = Hg, Wg_in = Wg;
-    if (cfg->global_resolution != cfg->view_resolution) {
-        const double resolution_ = (double)cfg->global_resolution, view_res = (double)cfg->view_resolution;
-        const double w2d = floor(Wg * resolution_ / view_res), h2d = floor(Hg * resolution_ / view_res);  // (range-checked before the cast)
-        if (!(w2d >= 1 && h2d >= 1 && w2d * h2d < 2147483648.0)) FAIL(IMGENV_EINVAL, "the map would be resized to %.0f x %.0f cells", h2d, w2d);
-        const int w2 = (int)w2d, h2 = (int)h2d;
-        resized_map.resize((size_t)w2 * h2);
-        cv_resize_u8(false, static_map, Hg, Wg, resized_map.data(), h2, w2);
-        static_map = resized_map.data();
-        Hg_in = Hg;
-        Wg_in = Wg;
-        Hg = h2;
-        Wg = w2;
-        // the kernels index the worlds' copies of a layer with 32 bits: checked again on the grid the handle really works on
-        if (W > 1 && (((size_t)Hg * Wg + 15) & ~(size_t)15) * (size_t)W >= ((size_t)1 << 32))
-            FAIL(IMGENV_EINVAL, "n_worlds x map cells must stay below 2^32 (the map is resized to %d x %d cells)", Hg, Wg);
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) FAIL(IMGENV_EDEVICE, "no HIP device available");
-    if (cfg->device < 0 || cfg->device >= ndev) FAIL(IMGENV_EDEVICE, "device %d out of range (%d)", cfg->device, ndev);
-    HIPCHK(hipSetDevice(cfg->device));
+// imgenv_create checks its arguments and plans (create_plan.h, out_fields.h: nothing of the device), then runs the phases below in
+// order on the new handle.  A phase that fails returns its code; imgenv_create alone destroys the half-built handle, and
+// imgenv_destroy copes with whatever the phases got to.  No allocation may change size, fill value or place in the order: the
+// order decides the addresses.
 
-    imgenv* h = new imgenv();
-    h->cfg = *cfg;
-    h->serial = getenv("IMGENV_SERIAL") && getenv("IMGENV_SERIAL")[0] == '1';  // (profiling aid: no side streams, clean per-kernel timings)
-    if (const char* e = getenv("IMGENV_RASTER_PACK")) {  // (measurement switch, per handle: 0 never, 2 / 4 that many robots per wavefront)
-        const int v = atoi(e);
-        h->raster_pack = v == 2 || v == 4 ? v : 0;
-    }
-    h->geom = g;
-    h->R = cfg->n_robots;
-    h->P = cfg->n_peds;
-    h->r0 = r0;
-    h->r1 = r1;
-    h->RL = r1 - r0;
-    h->Hg = Hg;
-    h->Wg = Wg;
-    h->Hg_in = Hg_in;
-    h->Wg_in = Wg_in;
-    h->map_stride = ((size_t)Hg * Wg + 15) & ~(size_t)15;
-    h->W = W;
-    h->Rw = h->R / W;
-    h->Pw = h->P / W;
-    h->Gs = W > 1 ? (((size_t)Hg * Wg + 15) & ~(size_t)15) : (size_t)Hg * Wg;
-    h->world_epoch.assign(W, 0);
-    h->world_ready.assign(W, 0);
-    h->rvos.resize(W);
-    const bool rvo = (cfg->ped_scene_type == IMGENV_SCENE_RVO || cfg->ped_scene_type == IMGENV_SCENE_ERVO);
-    h->NA = rvo ? h->P + (cfg->relation_ped_robo == 1 ? h->R : 0) : 0;
-    h->static_map.assign(static_map, static_map + (size_t)Hg * Wg);
-    const int R = h->R, P = h->P, RL = h->RL;
+// n zeroed ints of page-locked host memory that the device writes through (no copy, no sync to read them), and the device's pointer
+static int mapped_ints(size_t n, volatile int** host, int** dev) {
+    HIPCHK(hipHostMalloc((void**)host, n * sizeof(int), hipHostMallocMapped));
+    memset((void*)*host, 0, n * sizeof(int));
+    HIPCHK(hipHostGetDevicePointer((void**)dev, (void*)*host, 0));
+    return 0;
+}
+static int chain_event(hipEvent_t* e) {
+    HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming | hipEventDisableSystemFence));
+    return 0;
+}
+// world 0's copy of a layer to the other worlds: log2(W) device copies instead of W uploads
+static int copy_to_worlds(uint8_t* layer, size_t stride, int W) {
+    for (size_t filled = 1; filled < (size_t)W; filled *= 2)
+        HIPCHK(hipMemcpy(layer + filled * stride, layer, std::min(filled, (size_t)W - filled) * stride, hipMemcpyDeviceToDevice));
+    return 0;
+}
 
-    // classes
+// the robots' and pedestrians' classes (shape, size, sensor) and their host tables
+static int create_classes(imgenv* h, const imgenv_cfg& c, const CreateArgs& a) {
+    CreateMsg msg;
+    if (int rc = create_check_shapes(c, msg)) FAIL(rc, "%s", msg);
+    const int R = c.n_robots, P = c.n_peds;
+    h->cfg = c;
+    h->geom = a.g;
     h->robot_cls.resize(R);
     h->rsl.resize(R);
     for (int i = 0; i < R; i++) {
-        const int shape = cfg->robot_shape[i];
-        if (shape != IMGENV_SHAPE_CIRCLE && shape != IMGENV_SHAPE_RECTANGLE) {
-            delete h;
-            FAIL(IMGENV_EINVAL, "robot %d: unsupported shape %d", i, shape);
-        }
+        const int shape = c.robot_shape[i];
         int found = -1;
-        for (size_t c = 0; c < h->rcls.size(); c++)
-            if (h->rcls[c].shape == shape && !memcmp(h->rcls[c].size, cfg->robot_size + 4 * i, 16) &&
-                !memcmp(h->rcls[c].sensor, cfg->robot_sensor_cfg + 2 * i, 8))
-                found = (int)c;
+        for (size_t q = 0; q < h->rcls.size(); q++)
+            if (h->rcls[q].shape == shape && !memcmp(h->rcls[q].size, c.robot_size + 4 * i, 16) &&
+                !memcmp(h->rcls[q].sensor, c.robot_sensor_cfg + 2 * i, 8))
+                found = (int)q;
         if (found < 0) {
             RobotClassHost k;
             k.shape = shape;
-            memcpy(k.size, cfg->robot_size + 4 * i, 16);
-            memcpy(k.sensor, cfg->robot_sensor_cfg + 2 * i, 8);
+            memcpy(k.size, c.robot_size + 4 * i, 16);
+            memcpy(k.sensor, c.robot_sensor_cfg + 2 * i, 8);
             // tiled kernels (view_big.h): where k_view cannot run (its packing -- decided in build_robot_class -- or a shrunk
             // sensor_map) and on request.  (Measured on BASELINE cfg-5's 96 x 96 views, 8192 robots beside k_obs<16>: k_view
             // 471 us per step, the tiled kernels 531 -- the same instruction count in three launches; k_view stays the default
             // wherever it can run.)
-            const bool tiled = view_resize || ((cfg->flags & IMGENV_FLAG_VIEW_TILED) && !(cfg->flags & IMGENV_FLAG_VIEW_WAVE));
-            build_robot_class(k, g, tiled, (cfg->flags & IMGENV_FLAG_AGENT_STATE_EXTRAS) != 0);
+            const bool tiled = a.view_resize || ((c.flags & IMGENV_FLAG_VIEW_TILED) && !(c.flags & IMGENV_FLAG_VIEW_WAVE));
+            build_robot_class(k, a.g, tiled, (c.flags & IMGENV_FLAG_AGENT_STATE_EXTRAS) != 0);
             h->rcls.push_back(std::move(k));
             found = (int)h->rcls.size() - 1;
         }
         h->robot_cls[i] = found;
-        h->rsl[i] = cfg->robot_size_last ? cfg->robot_size_last[i] : 0.0;
+        h->rsl[i] = c.robot_size_last ? c.robot_size_last[i] : 0.0;
     }
     h->ped_cls.resize(P);
     h->pmax.resize(P);
-    std::vector<double> pr_round(P);
-    std::vector<float> pr32(P);
     for (int j = 0; j < P; j++) {
         int found = -1;
-        for (size_t c = 0; c < h->pcls.size(); c++)
-            if (h->pcls[c].shape == cfg->ped_shape[j] && !memcmp(h->pcls[c].size, cfg->ped_size + 6 * j, 24)) found = (int)c;
+        for (size_t q = 0; q < h->pcls.size(); q++)
+            if (h->pcls[q].shape == c.ped_shape[j] && !memcmp(h->pcls[q].size, c.ped_size + 6 * j, 24)) found = (int)q;
         if (found < 0) {
             PedClassHost k;
-            k.shape = cfg->ped_shape[j];
-            memcpy(k.size, cfg->ped_size + 6 * j, 24);
-            build_ped_class(k, g.res);
+            k.shape = c.ped_shape[j];
+            memcpy(k.size, c.ped_size + 6 * j, 24);
+            build_ped_class(k, a.g.res);
             h->pcls.push_back(std::move(k));
             found = (int)h->pcls.size() - 1;
         }
         h->ped_cls[j] = found;
-        h->pmax[j] = cfg->ped_max_speed[j];
-        pr32[j] = (float)h->pcls[found].sizes[2];
-        pr_round[j] = py_round2((double)pr32[j]);
+        h->pmax[j] = c.ped_max_speed[j];
     }
     h->cfg.robot_shape = nullptr; h->cfg.robot_size = nullptr; h->cfg.robot_sensor_cfg = nullptr;
     h->cfg.ped_shape = nullptr; h->cfg.ped_size = nullptr; h->cfg.ped_max_speed = nullptr;
     h->cfg.robot_size_last = nullptr;
+    return 0;
+}
+
+// what the plan says, into the handle and the kernels' DevWorld (no device call)
+static void create_facts(imgenv* h, const CreatePlan& p, const uint8_t* static_map, int Hg_in, int Wg_in) {
+    const imgenv_cfg& c = h->cfg;
+    const ViewGeom& g = h->geom;
+    const int W = p.W;
+    h->serial = p.serial;  // (profiling aid: no side streams, clean per-kernel timings)
+    if (const char* e = getenv("IMGENV_RASTER_PACK")) {  // (measurement switch, per handle: 0 never, 2 / 4 that many robots per wavefront)
+        const int v = atoi(e);
+        h->raster_pack = v == 2 || v == 4 ? v : 0;
+    }
+    h->R = p.R; h->P = p.P; h->r0 = p.r0; h->r1 = p.r1; h->RL = p.RL; h->NA = p.NA;
+    h->Hg = p.Hg; h->Wg = p.Wg; h->Hg_in = Hg_in; h->Wg_in = Wg_in;
+    h->map_stride = align16(p.G);
+    h->W = W; h->Rw = p.Rw; h->Pw = p.Pw; h->Gs = p.Gs;
+    h->world_epoch.assign(W, 0);
+    h->world_ready.assign(W, 0);
+    h->rvos.resize(W);
+    h->wobst.assign((size_t)4 * W, 0);
+    h->static_map.assign(static_map, static_map + p.G);
+    h->pow2 = p.pow2; h->n_sub = p.n_sub;
+    h->stamp = p.layer.stamp; h->sum = p.layer.sum;
+    h->big_view = p.big_view; h->big_full_chunks = p.big_full_chunks; h->big_bits_in_lds = p.big_bits_in_lds;
+    h->PP = p.PP; h->obs_E = p.obs_E;
+    h->lds_view = p.lds_view; h->lds_obs = p.lds_obs; h->lds_view_big = p.lds_view_big;
+    static_assert(PM_CAP * 2 <= WAVE * 7 * 4, "the touched-cell list reuses the staging buffer");
+    h->sfm_ahead = p.sfm_ahead; h->early = p.early;
+    h->arena_bytes = p.arena.total;
 
     DevWorld& d = h->d;
     memset(&d, 0, sizeof(d));
-    d.R = R; d.RL = RL; d.r0 = r0; d.P = P; d.NA = h->NA;
-    d.W = W; d.Rw = h->Rw; d.Pw = h->Pw; d.Gs = (uint32_t)h->Gs;
-    d.act_list = nullptr; d.act_nw = W; d.act_nl = RL; d.act_ng = R; d.act_np = P;
-    d.act_cells = W > 1 ? h->Gs * W : h->Gs;
-    d.Hg = Hg; d.Wg = Wg; d.Hv = g.Hv; d.Wv = g.Wv; d.B = g.B;
-    d.Hp = cfg->ped_image_size[0]; d.Wp = cfg->ped_image_size[1];
-    d.SD = cfg->state_dim; d.PV = 1 + cfg->ped_vec_dim * cfg->max_ped;
-    d.scene = cfg->ped_scene_type; d.relation = cfg->relation_ped_robo; d.ktype = cfg->robot_ktype;
-    d.use_laser = cfg->use_laser ? 1 : 0; d.laser_norm = cfg->laser_norm; d.time_max = cfg->time_max;
+    d.R = p.R; d.RL = p.RL; d.r0 = p.r0; d.P = p.P; d.NA = p.NA;
+    d.W = W; d.Rw = p.Rw; d.Pw = p.Pw; d.Gs = (uint32_t)p.Gs;
+    d.act_list = nullptr; d.act_nw = W; d.act_nl = p.RL; d.act_ng = p.R; d.act_np = p.P;
+    d.act_cells = W > 1 ? p.Gs * W : p.Gs;
+    d.Hg = p.Hg; d.Wg = p.Wg; d.Hv = g.Hv; d.Wv = g.Wv; d.B = g.B;
+    d.Hp = c.ped_image_size[0]; d.Wp = c.ped_image_size[1];
+    d.SD = c.state_dim; d.PV = 1 + c.ped_vec_dim * c.max_ped;
+    d.scene = c.ped_scene_type; d.relation = c.relation_ped_robo; d.ktype = c.robot_ktype;
+    d.use_laser = c.use_laser ? 1 : 0; d.laser_norm = c.laser_norm; d.time_max = c.time_max;
     d.res = g.res; d.inv_res = 1.0 / g.res;
-    {
-        int e = 0;
-        h->pow2 = (frexp(g.res, &e) == 0.5);  // exact power of two: x * (1/res) == x / res bit for bit
-        d.wv_magic = (uint32_t)((0x100000000ull + (uint64_t)g.Wv - 1) / (uint64_t)g.Wv);
-    }
-    d.step_hz = (double)cfg->step_hz; d.laser_max = cfg->laser_max;
-    d.laser_out_nohit = cfg->laser_norm ? (double)6.0f / (double)cfg->laser_max : (double)6.0f;
-    d.ped_safety_space = cfg->ped_safety_space; d.ped_image_r = cfg->ped_image_r;
-    d.ped_image_r2 = pow(cfg->ped_image_r, 2.0);        // self.ped_image_r ** 2 (yaml_env.py:425)
-    {   // while (cur_control <= step_hz) { ...; cur_control += 0.05; } with the loop's own fp64 accumulation
-        double cur = 0;
-        h->n_sub = 0;
-        while (cur <= d.step_hz && h->n_sub < (1 << 20)) {
-            h->n_sub++;
-            cur += 0.05;
-        }
-    }
-    d.ped_res = 6.0 / cfg->ped_image_size[0];            // yaml_env.py:164
-    {
-        int e = 0;
-        d.ped_inv_res = frexp(d.ped_res, &e) == 0.5 ? 1.0 / d.ped_res : 0.0;
-    }
+    d.wv_magic = p.wv_magic;
+    d.step_hz = (double)c.step_hz; d.laser_max = c.laser_max;
+    d.laser_out_nohit = c.laser_norm ? (double)6.0f / (double)c.laser_max : (double)6.0f;
+    d.ped_safety_space = c.ped_safety_space; d.ped_image_r = c.ped_image_r;
+    d.ped_image_r2 = pow(c.ped_image_r, 2.0);        // self.ped_image_r ** 2 (yaml_env.py:425)
+    d.ped_res = p.ped_res; d.ped_inv_res = p.ped_inv_res;
     d.view_base = g.view_base; d.base_view = g.base_view;
     {   // SpeedLimiter(msg) (speed_limit.cpp:56-65): max_jerk <- msg.min_jerk, min_jerk uninitialised (0 here)
-        const imgenv_limiter& v = cfg->limiter_v; const imgenv_limiter& ww = cfg->limiter_w;
+        const imgenv_limiter& v = c.limiter_v; const imgenv_limiter& ww = c.limiter_w;
         d.lv_has_v = v.has_velocity_limits; d.lv_has_a = v.has_acceleration_limits; d.lv_has_j = v.has_jerk_limits;
         d.lv_min_v = v.min_velocity; d.lv_max_v = v.max_velocity; d.lv_min_a = v.min_acceleration;
         d.lv_max_a = v.max_acceleration; d.lv_min_j = 0.0; d.lv_max_j = v.min_jerk;
@@ -926,655 +796,552 @@ extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, i
         d.lw_min_v = ww.min_velocity; d.lw_max_v = ww.max_velocity; d.lw_min_a = ww.min_acceleration;
         d.lw_max_a = ww.max_acceleration; d.lw_min_j = 0.0; d.lw_max_j = ww.min_jerk;
     }
-    const size_t G = (size_t)Hg * Wg, Gp = W > 1 ? h->Gs * W : ((G + 15) & ~(size_t)15);
+    const LayerPlan& l = p.layer;
+    d.layer_sum = l.sum ? 1 : 0; d.sum_shard = l.sum_shard ? 1 : 0;
+    d.sum_pc_mask = l.sum_pc_mask; d.sum_rc_shift = l.sum_rc_shift; d.sum_id_shift = l.sum_id_shift; d.sum_wg_magic = l.sum_wg_magic;
+    d.rm_rad = l.rm_rad;
+    d.stamp_tag = 1;
+    d.resize = p.view_resize ? 1 : 0;
+    d.img_w = c.image_size[0];
+    d.img_h = c.image_size[1];
+    d.keep_view_maps = (c.flags & IMGENV_FLAG_NO_VIEW_MAPS) ? 0 : 1;
+    d.big_words = p.big_words; d.big_hit_stride = p.big_hit_stride;
+    d.big_bits_in_lds = p.big_view && p.big_bits_in_lds ? 1 : 0;
+    d.pd_cap = p.pd_cap; d.ped_box_cells = p.pd_cap;
+    d.box_cells = p.box_cells; d.fp_cap = p.fp_cap;
+    d.sharded = p.RL != p.R;
+    d.region_margin = p.region_margin;
+    d.beep_on = p.beep_on ? 1 : 0;
+    d.beep_r = c.beep_r;
+    d.ped_ca_p = (double)c.ped_ca_p;
+    d.state_in_integrate = p.P == 0 ? 1 : 0;
+    d.view_max_dist32 = c.view_max_dist;
+    d.obs_passes = p.obs_passes;
+    d.hit_stride = p.hit_stride;
+}
 
-    // grids (one copy per world)
-    TRY(dev_alloc(h, &h->d_obs_map, Gp));
-    HIPCHK_H(hipMemcpy(h->d_obs_map, static_map, G, hipMemcpyHostToDevice));
-    for (size_t filled = 1; filled < (size_t)W; filled *= 2)  // the other worlds' copies: log2(W) device copies instead of W uploads
-        HIPCHK_H(hipMemcpy(h->d_obs_map + filled * h->Gs, h->d_obs_map, std::min(filled, (size_t)W - filled) * h->Gs, hipMemcpyDeviceToDevice));
-    TRY(dev_alloc(h, &h->d_static_map, (G + 15) & ~(size_t)15));
-    HIPCHK_H(hipMemcpy(h->d_static_map, static_map, G, hipMemcpyHostToDevice));
-    TRY(dev_alloc(h, &h->d_world_epoch, W));
+// grids (one copy per world) and the class layer in the plan's mode
+static int create_grid_layers(imgenv* h, const CreatePlan& p) {
+    DevWorld& d = h->d;
+    const int W = p.W;
+    RTRY(dev_alloc(h, &h->d_obs_map, p.Gp));
+    HIPCHK(hipMemcpy(h->d_obs_map, h->static_map.data(), p.G, hipMemcpyHostToDevice));
+    RTRY(copy_to_worlds(h->d_obs_map, h->Gs, W));
+    RTRY(dev_alloc(h, &h->d_static_map, align16(p.G)));
+    HIPCHK(hipMemcpy(h->d_static_map, h->static_map.data(), p.G, hipMemcpyHostToDevice));
+    RTRY(dev_alloc(h, &h->d_world_epoch, W));
     d.world_epoch = h->d_world_epoch;
-    h->wobst.assign((size_t)4 * W, 0);
-    TRY(dev_alloc(h, &h->d_wobst, (size_t)4 * W));
+    RTRY(dev_alloc(h, &h->d_wobst, (size_t)4 * W));
     d.obst_base = h->d_wobst; d.node_base = h->d_wobst + W; d.n_obst_w = h->d_wobst + 2 * W; d.oroot_w = h->d_wobst + 3 * W;
     d.obs_map = h->d_obs_map;
-    {   // How is the class layer kept up to date?  Composed: the rasters fill two owner layers and a pedestrian layer with
-        // fire-and-forget atomics and k_compose merges (and re-arms) them every step -- 14 bytes a cell, every cell of every
-        // world.  Stamped: the rasters merge their stamps straight onto the class layer (compare-and-swap) and stamps expire
-        // by their step tag -- nothing per cell, but slower rasters and a slightly longer decode in k_view.  Composed wins
-        // where the agents cover a good part of the map (the headline world: 0.133 against 0.138 ms per step), stamped
-        // where the maps are much larger than what the agents touch (8192 one-robot worlds: 52 against 43 M robot-steps/s).
-        const size_t cells = (size_t)Hg * Wg * W;
-        h->stamp = plan_layer_stamp(RL == R, cells, R, P, cfg->flags);  // (where each wins, measured: launch_plan.h)
-        // ... and where the owner layers + k_compose used to be the answer, the counting layer is (round 5: no pass over every cell
-        // of every world per step, a robot that covers the same cells as a step ago issues no atomic at all) -- wherever it can
-        // run: every footprint fits the rasters' LDS box, views through k_view, and the word has room for the counts: 3 bits of
-        // base class, as many pedestrian bits as a world has pedestrians, the robot's index within its world, and at least 6 bits
-        // of robot count.  A robot SHARD (round 6; world.h: sum_shard) numbers its own robots 1 .. RL in the index field and needs
-        // every footprint's box to fit a 64-bit bitmap, which is how the other ranks' robots arrive.
-        auto bits = [](int v) { int b = 0; while ((1 << b) <= v) b++; return b; };  // bits to count up to v
-        const bool shard = RL != R;
-        const int id_bits = shard ? bits(RL) : std::max(1, bits(h->Rw - 1)), pc_bits = bits(h->Pw);
-        bool fits = G < ((size_t)1 << 24) && 3 + pc_bits + 6 + id_bits <= 32;
-        for (const RobotClassHost& k : h->rcls)
-            fits = fits && !k.big && (2 * k.box_rad + 1) * (2 * k.box_rad + 1) <= RASTER_BOX_CELLS &&
-                   (!shard || (2 * k.box_rad - 3) * (2 * k.box_rad - 3) <= WAVE);  // (the bitmap: the box without its margin of two cells)
-        for (const PedClassHost& k : h->pcls) fits = fits && (2 * k.box_rad + 1) * (2 * k.box_rad + 1) <= RASTER_BOX_CELLS;
-        const bool want_sum = (cfg->flags & IMGENV_FLAG_LAYER_SUM) != 0 || (!h->stamp && !(cfg->flags & IMGENV_FLAG_COMPOSE_DENSE));
-        h->sum = want_sum && fits;
-        if (h->sum) {
-            h->stamp = false;
-            d.layer_sum = 1;
-            d.sum_shard = shard ? 1 : 0;
-            d.sum_pc_mask = (1u << pc_bits) - 1u;
-            d.sum_rc_shift = 3u + (uint32_t)pc_bits;
-            d.sum_id_shift = 32u - (uint32_t)id_bits;
-            d.sum_wg_magic = (((unsigned long long)1 << 40) + (unsigned long long)Wg - 1) / (unsigned long long)Wg;
-        }
-    }
-    d.stamp_tag = 1;
     if (d.sum_shard) {
-        d.rm_rad = h->rcls[0].box_rad - 2;
-        for (const RobotClassHost& k : h->rcls)
-            if (k.box_rad - 2 != d.rm_rad) d.rm_rad = -1;
-        TRY(dev_alloc(h, &d.rm_bits, (size_t)R));
-        TRY(dev_alloc(h, &d.rm_center, (size_t)R));
+        RTRY(dev_alloc(h, &d.rm_bits, (size_t)p.R));
+        RTRY(dev_alloc(h, &d.rm_center, (size_t)p.R));
     }
     if (!h->stamp && !h->sum) {
-        TRY(dev_alloc(h, &d.ped_layer, Gp));
-        TRY(dev_alloc(h, &d.own_lo, Gp, 0xFF));
-        TRY(dev_alloc(h, &d.own_hi, Gp));
+        RTRY(dev_alloc(h, &d.ped_layer, p.Gp));
+        RTRY(dev_alloc(h, &d.own_lo, p.Gp, 0xFF));
+        RTRY(dev_alloc(h, &d.own_hi, p.Gp));
     }
-    TRY(dev_alloc(h, &d.cell, Gp));
-    TRY(dev_alloc(h, &d.seg_tag, Gp / 64 + 2));
-    d.crop_map = nullptr;
+    RTRY(dev_alloc(h, &d.cell, p.Gp));
+    RTRY(dev_alloc(h, &d.seg_tag, p.Gp / 64 + 2));
+    return 0;
+}
 
-    // class tables
-    size_t max_stride = WAVE;
-    {
-        std::vector<RobotClassDev> rc(h->rcls.size());
-        for (size_t c = 0; c < h->rcls.size(); c++) {
-            const RobotClassHost& k = h->rcls[c];
-            RobotClassDev& o = rc[c];
-            o.n_fp = k.fp.n();
-            {
-                std::vector<double2> fp(k.fp.n());
-                for (int q = 0; q < k.fp.n(); q++) fp[q] = make_double2(k.fp.x[q], k.fp.y[q]);
-                TRY(dev_upload(h, &o.fp, fp));
-            }
-            TRY(dev_upload(h, &o.fov_bits, k.fov_bits));
-            TRY(dev_upload(h, &o.stamp_bits, k.stamp_bits));
-            o.ray_maxlen = k.ray_maxlen;
-            o.ray_stride = k.ray_stride;
-            o.ray_kpad = k.ray_kpad;
-            if (!k.ok) {
-                imgenv_destroy(h);
-                FAIL(IMGENV_EINVAL, "laser ray tables overflow their packing (too many beams x view cells)");
-            }
-            TRY(dev_upload(h, &o.ray_rows, k.ray_rows));
-            TRY(dev_upload(h, &o.ray_len, k.ray_len));
-            TRY(dev_upload(h, &o.ray_dist, k.ray_dist));
-            if (!k.big) {  // what k_view needs of a beam's first hit, per (step, beam): the host's IEEE division = the device's
-                std::vector<uint32_t> fin(4 * k.ray_dist.size());
-                for (size_t q = 0; q < k.ray_dist.size(); q++) {
-                    const float hd = k.ray_dist[q];
-                    const double out = cfg->laser_norm ? (double)hd / (double)cfg->laser_max : (double)hd;
-                    fin[4 * q] = k.ray_run[q];
-                    memcpy(&fin[4 * q + 1], &hd, 4);
-                    memcpy(&fin[4 * q + 2], &out, 8);
-                }
-                const uint32_t* fin_dev = nullptr;
-                TRY(dev_upload(h, &fin_dev, fin));
-                o.ray_fin = (const uint4*)fin_dev;
-            }
-            TRY(dev_upload(h, &o.ray_run, k.ray_run));
-            if (!k.ray_hx.empty()) {
-                TRY(dev_upload(h, &o.ray_hx, k.ray_hx));
-                TRY(dev_upload(h, &o.ray_hy, k.ray_hy));
-                TRY(dev_upload(h, &o.bin_start, k.bin_start));
-            }
-            TRY(dev_upload(h, &o.inv_pack, k.inv_pack));
-            TRY(dev_upload(h, &o.inv_ent, k.inv_ent));
-            TRY(dev_upload(h, &o.top_ent, k.top_ent));
-            TRY(dev_upload(h, &o.dyn_groups, k.dyn_groups));
-            o.n_dyn = (int)k.dyn_groups.size();
-            TRY(dev_upload(h, &o.all_groups, k.all_groups));
-            {
-                const uint32_t* cells2 = nullptr;
-                TRY(dev_upload(h, &cells2, k.inv_cell));
-                o.inv_cell = (const uint2*)cells2;
-            }
-            o.big = k.big ? 1 : 0;
-            h->big_view = h->big_view || k.big;
-            o.box_rad = k.box_rad;
-            o.n_rows = (int)k.fp_rows.size();
-            o.rows = nullptr;
-            o.fp_cy = k.fp_cy;
-            if (o.n_rows) TRY(dev_upload(h, &o.rows, k.fp_rows));
-            max_stride = std::max(max_stride, (size_t)k.ray_stride);
+// the classes' tables on the device, and what the kernels read per robot / pedestrian of its class
+static int create_class_tables(imgenv* h, const CreatePlan& p) {
+    DevWorld& d = h->d;
+    const imgenv_cfg& c = h->cfg;
+    std::vector<RobotClassDev> rc(h->rcls.size());
+    for (size_t q = 0; q < h->rcls.size(); q++) {
+        const RobotClassHost& k = h->rcls[q];
+        RobotClassDev& o = rc[q];
+        o.n_fp = k.fp.n();
+        {
+            std::vector<double2> fp(k.fp.n());
+            for (int s = 0; s < k.fp.n(); s++) fp[s] = make_double2(k.fp.x[s], k.fp.y[s]);
+            RTRY(dev_upload(h, &o.fp, fp));
         }
-        if (rc.size() > RC_INLINE || h->pcls.size() > PC_INLINE) {
-            imgenv_destroy(h);
-            FAIL(IMGENV_EINVAL, "more than %d robot or %d pedestrian classes (shape, size, sensor) in one world", RC_INLINE, PC_INLINE);
+        RTRY(dev_upload(h, &o.fov_bits, k.fov_bits));
+        RTRY(dev_upload(h, &o.stamp_bits, k.stamp_bits));
+        o.ray_maxlen = k.ray_maxlen;
+        o.ray_stride = k.ray_stride;
+        o.ray_kpad = k.ray_kpad;
+        RTRY(dev_upload(h, &o.ray_rows, k.ray_rows));
+        RTRY(dev_upload(h, &o.ray_len, k.ray_len));
+        RTRY(dev_upload(h, &o.ray_dist, k.ray_dist));
+        if (!k.big) {  // what k_view needs of a beam's first hit, per (step, beam): the host's IEEE division = the device's
+            std::vector<uint32_t> fin(4 * k.ray_dist.size());
+            for (size_t s = 0; s < k.ray_dist.size(); s++) {
+                const float hd = k.ray_dist[s];
+                const double out = c.laser_norm ? (double)hd / (double)c.laser_max : (double)hd;
+                fin[4 * s] = k.ray_run[s];
+                memcpy(&fin[4 * s + 1], &hd, 4);
+                memcpy(&fin[4 * s + 2], &out, 8);
+            }
+            const uint32_t* fin_dev = nullptr;
+            RTRY(dev_upload(h, &fin_dev, fin));
+            o.ray_fin = (const uint4*)fin_dev;
         }
-        for (size_t c = 0; c < rc.size(); c++) d.rc[c] = rc[c];
-        TRY(dev_upload(h, &d.rc_mem, rc));
-        std::vector<PedClassDev> pc(h->pcls.size());
-        for (size_t c = 0; c < h->pcls.size(); c++) {
-            const PedClassHost& k = h->pcls[c];
-            PedClassDev& o = pc[c];
-            memset(&o, 0, sizeof(o));
-            o.shape = k.shape;
-            o.n_bbox = k.bbox.n();
-            o.n_left = k.left.n();
-            o.n_right = k.right.n();
-            TRY(dev_upload(h, &o.bx, k.bbox.x));
-            TRY(dev_upload(h, &o.by, k.bbox.y));
-            TRY(dev_upload(h, &o.lx, k.left.x));
-            TRY(dev_upload(h, &o.ly, k.left.y));
-            TRY(dev_upload(h, &o.rx, k.right.x));
-            TRY(dev_upload(h, &o.ry, k.right.y));
-            memcpy(o.sizes, k.sizes, sizeof(o.sizes));
-            o.box_rad = k.box_rad;
-            o.n_brows = (int)k.bbox_rows.size(); o.n_lrows = (int)k.left_rows.size(); o.n_rrows = (int)k.right_rows.size();
-            o.bbox_cy = k.bbox_cy;
-            if (o.n_brows) TRY(dev_upload(h, &o.brows, k.bbox_rows));
-            if (o.n_lrows) TRY(dev_upload(h, &o.lrows, k.left_rows));
-            if (o.n_rrows) TRY(dev_upload(h, &o.rrows, k.right_rows));
+        RTRY(dev_upload(h, &o.ray_run, k.ray_run));
+        if (!k.ray_hx.empty()) {
+            RTRY(dev_upload(h, &o.ray_hx, k.ray_hx));
+            RTRY(dev_upload(h, &o.ray_hy, k.ray_hy));
+            RTRY(dev_upload(h, &o.bin_start, k.bin_start));
         }
-        for (size_t c = 0; c < pc.size(); c++) d.pc[c] = pc[c];
-        if (pc.empty()) pc.resize(1);
-        TRY(dev_upload(h, &d.pc_mem, pc));
+        RTRY(dev_upload(h, &o.inv_pack, k.inv_pack));
+        RTRY(dev_upload(h, &o.inv_ent, k.inv_ent));
+        RTRY(dev_upload(h, &o.top_ent, k.top_ent));
+        RTRY(dev_upload(h, &o.dyn_groups, k.dyn_groups));
+        o.n_dyn = (int)k.dyn_groups.size();
+        RTRY(dev_upload(h, &o.all_groups, k.all_groups));
+        {
+            const uint32_t* cells2 = nullptr;
+            RTRY(dev_upload(h, &cells2, k.inv_cell));
+            o.inv_cell = (const uint2*)cells2;
+        }
+        o.big = k.big ? 1 : 0;
+        o.box_rad = k.box_rad;
+        o.n_rows = (int)k.fp_rows.size();
+        o.rows = nullptr;
+        o.fp_cy = k.fp_cy;
+        if (o.n_rows) RTRY(dev_upload(h, &o.rows, k.fp_rows));
     }
-    TRY(dev_upload(h, &d.robot_cls, h->robot_cls));
-    TRY(dev_upload(h, &d.ped_cls, h->ped_cls));
-    TRY(dev_upload(h, &d.robot_size_last, h->rsl));
-    TRY(dev_upload(h, &d.ped_r_round, pr_round));
-    TRY(dev_upload(h, &d.ped_r32, pr32));
-    {
-        std::vector<uint16_t> lut(256);
-        for (int v = 0; v < 256; v++) lut[v] = f32_to_f16((float)v / 255.0f);  // numpy: f16(f32(v)/255)
-        TRY(dev_upload(h, &d.f16_lut, lut));
+    for (size_t q = 0; q < rc.size(); q++) d.rc[q] = rc[q];
+    RTRY(dev_upload(h, &d.rc_mem, rc));
+    std::vector<PedClassDev> pc(h->pcls.size());
+    for (size_t q = 0; q < h->pcls.size(); q++) {
+        const PedClassHost& k = h->pcls[q];
+        PedClassDev& o = pc[q];
+        memset(&o, 0, sizeof(o));
+        o.shape = k.shape;
+        o.n_bbox = k.bbox.n();
+        o.n_left = k.left.n();
+        o.n_right = k.right.n();
+        RTRY(dev_upload(h, &o.bx, k.bbox.x));
+        RTRY(dev_upload(h, &o.by, k.bbox.y));
+        RTRY(dev_upload(h, &o.lx, k.left.x));
+        RTRY(dev_upload(h, &o.ly, k.left.y));
+        RTRY(dev_upload(h, &o.rx, k.right.x));
+        RTRY(dev_upload(h, &o.ry, k.right.y));
+        memcpy(o.sizes, k.sizes, sizeof(o.sizes));
+        o.box_rad = k.box_rad;
+        o.n_brows = (int)k.bbox_rows.size(); o.n_lrows = (int)k.left_rows.size(); o.n_rrows = (int)k.right_rows.size();
+        o.bbox_cy = k.bbox_cy;
+        if (o.n_brows) RTRY(dev_upload(h, &o.brows, k.bbox_rows));
+        if (o.n_lrows) RTRY(dev_upload(h, &o.lrows, k.left_rows));
+        if (o.n_rrows) RTRY(dev_upload(h, &o.rrows, k.right_rows));
     }
-    d.resize = view_resize ? 1 : 0;
-    d.img_w = cfg->image_size[0];
-    d.img_h = cfg->image_size[1];
+    for (size_t q = 0; q < pc.size(); q++) d.pc[q] = pc[q];
+    if (pc.empty()) pc.resize(1);
+    RTRY(dev_upload(h, &d.pc_mem, pc));
+    RTRY(dev_upload(h, &d.robot_cls, h->robot_cls));
+    RTRY(dev_upload(h, &d.ped_cls, h->ped_cls));
+    RTRY(dev_upload(h, &d.robot_size_last, h->rsl));
+    std::vector<double> pr_round(p.P);
+    std::vector<float> pr32(p.P);
+    for (int j = 0; j < p.P; j++) {
+        pr32[j] = (float)h->pcls[h->ped_cls[j]].sizes[2];
+        pr_round[j] = py_round2((double)pr32[j]);
+    }
+    RTRY(dev_upload(h, &d.ped_r_round, pr_round));
+    RTRY(dev_upload(h, &d.ped_r32, pr32));
+    std::vector<uint16_t> lut(256);
+    for (int v = 0; v < 256; v++) lut[v] = f32_to_f16((float)v / 255.0f);  // numpy: f16(f32(v)/255)
+    RTRY(dev_upload(h, &d.f16_lut, lut));
+    return 0;
+}
+
+// the shrunk sensor_map's axis tables, and what the tiled kernels of view_big.h need
+static int create_view_tables(imgenv* h, const CreatePlan& p) {
+    DevWorld& d = h->d;
+    const ViewGeom& g = h->geom;
+    const int W = p.W, Hg = p.Hg, Wg = p.Wg, RL = p.RL;
     CvAxis ax, ay;
-    if (view_resize) {  // axis tables of the bicubic shrink (csrc/cv_resize.h)
+    if (p.view_resize) {  // axis tables of the bicubic shrink (csrc/cv_resize.h)
         ax = cv_axis(g.Wv, d.img_w, true, true);
         ay = cv_axis(g.Hv, d.img_h, true, false);
-        TRY(dev_upload(h, &d.rs_xofs, ax.ofs));
-        TRY(dev_upload(h, &d.rs_alpha, ax.coef));
-        TRY(dev_upload(h, &d.rs_yofs, ay.ofs));
-        TRY(dev_upload(h, &d.rs_beta, ay.coef));
+        RTRY(dev_upload(h, &d.rs_xofs, ax.ofs));
+        RTRY(dev_upload(h, &d.rs_alpha, ax.coef));
+        RTRY(dev_upload(h, &d.rs_yofs, ay.ofs));
+        RTRY(dev_upload(h, &d.rs_beta, ay.coef));
     }
-    d.keep_view_maps = (cfg->flags & IMGENV_FLAG_NO_VIEW_MAPS) ? 0 : 1;
-    if (h->big_view) {  // view_big.h: tiled crop bitmap + hit words per local robot, static tables per class
-        if (h->stamp && G < ((size_t)1 << 24)) {  // view_big.h: the map as k_crop_big wants it (world.h)
-            const uint32_t wt = (uint32_t)(Wg + 7) / 8, ht = (uint32_t)(Hg + 7) / 8;
-            d.crop_wt = wt;
-            d.crop_ws = wt * ht * 64;
-            d.crop_magic = (((unsigned long long)1 << 40) + (unsigned long long)Wg - 1) / (unsigned long long)Wg;
-            for (int m = 0; m < Hg; m++)  // (the multiply-shift division is exact on this map: row starts and row ends)
-                for (int e = 0; e < 2; e++) {
-                    const unsigned long long cl = (unsigned long long)m * Wg + (e ? Wg - 1 : 0);
-                    if ((int)((cl * d.crop_magic) >> 40) != m) {
-                        imgenv_destroy(h);
-                        FAIL(IMGENV_EINVAL, "internal: row of cell %llu by multiply-shift", cl);
-                    }
-                }
-            std::vector<uint8_t> tiled;
-            tile_crop(static_map, Hg, Wg, wt, (size_t)d.crop_ws, tiled);
-            uint8_t* sc = nullptr;
-            TRY(dev_alloc(h, &sc, (size_t)d.crop_ws));
-            HIPCHK_H(hipMemcpy(sc, tiled.data(), tiled.size(), hipMemcpyHostToDevice));
-            d.static_crop = sc;
-            TRY(dev_alloc(h, &d.crop_map, (size_t)d.crop_ws * W));
-            HIPCHK_H(hipMemcpy(d.crop_map, sc, (size_t)d.crop_ws, hipMemcpyDeviceToDevice));
-            for (size_t filled = 1; filled < (size_t)W; filled *= 2)
-                HIPCHK_H(hipMemcpy(d.crop_map + filled * d.crop_ws, d.crop_map, std::min(filled, (size_t)W - filled) * d.crop_ws, hipMemcpyDeviceToDevice));
-        }
-        std::vector<BigClassDev> bc(h->rcls.size());
-        int max_crop = 1;
-        for (size_t c = 0; c < h->rcls.size(); c++) {
-            RobotClassHost& k = h->rcls[c];
-            BigClassDev& o = bc[c];
-            memset(&o, 0, sizeof(o));
-            if (!k.big) {
-                imgenv_destroy(h);
-                FAIL(IMGENV_EINVAL, "robot classes with and without big views in one world");
+    if (!h->big_view) return 0;
+    // view_big.h: tiled crop bitmap + hit words per local robot, static tables per class
+    if (h->stamp && p.G < ((size_t)1 << 24)) {  // view_big.h: the map as k_crop_big wants it (world.h)
+        const uint32_t wt = (uint32_t)(Wg + 7) / 8, ht = (uint32_t)(Hg + 7) / 8;
+        d.crop_wt = wt;
+        d.crop_ws = wt * ht * 64;
+        d.crop_magic = (((unsigned long long)1 << 40) + (unsigned long long)Wg - 1) / (unsigned long long)Wg;
+        for (int m = 0; m < Hg; m++)  // (the multiply-shift division is exact on this map: row starts and row ends)
+            for (int e = 0; e < 2; e++) {
+                const unsigned long long cl = (unsigned long long)m * Wg + (e ? Wg - 1 : 0);
+                if ((int)((cl * d.crop_magic) >> 40) != m) FAIL(IMGENV_EINVAL, "internal: row of cell %llu by multiply-shift", cl);
             }
-            o.ta = k.big_ta;
-            o.tb = k.big_tb;
-            o.n_crop = k.n_crop;
-            max_crop = std::max(max_crop, o.n_crop);
-            TRY(dev_upload(h, &o.crop_tiles, k.crop_tiles));
-            TRY(dev_upload(h, &o.crop_masks, k.crop_masks));
-            TRY(dev_upload(h, &o.cells, k.big_cells));
-            TRY(dev_upload(h, &o.ray_end, k.ray_end));
-            {
-                const uint32_t* p2 = nullptr;
-                TRY(dev_upload(h, &p2, k.big_inv));
-                o.inv = (const uint2*)p2;
-            }
-            if (view_resize) {
-                build_big_taps(k, g, ax.ofs, ay.ofs);
-                const uint32_t* p2i = nullptr;
-                TRY(dev_upload(h, &o.tap_top, k.tap_top));
-                TRY(dev_upload(h, &p2i, k.tap_inv));
-                o.tap_inv = (const uint2*)p2i;
-                TRY(dev_upload(h, &o.tap_addr, k.tap_addr));
-                TRY(dev_upload(h, &o.tap_chunks, k.tap_chunks));
-                o.n_tap_chunks = (int)k.tap_chunks.size();
-                h->big_tap_chunks_dyn = std::max(h->big_tap_chunks_dyn, o.n_tap_chunks);
-                std::vector<uint32_t>().swap(k.tap_top);
-                std::vector<uint32_t>().swap(k.tap_inv);
-                std::vector<uint32_t>().swap(k.tap_addr);
-            }
-        }
-        for (size_t c = 0; c < bc.size(); c++) d.big[c] = bc[c];
-        const size_t tiles = (size_t)h->rcls[0].big_ta * h->rcls[0].big_tb;
-        d.big_words = (int)((tiles * 2 + 1 + 3) & ~(size_t)3);  // + the always-free word the padded path entries point at
-        d.big_hit_stride = (g.B + 3 + 3) & ~3;  // B hit words, the dummy beam, the flag, the collision code
-        TRY(dev_alloc(h, &d.big_bits, (size_t)RL * 2 * d.big_words));
-        TRY(dev_alloc(h, &d.big_hit, (size_t)RL * d.big_hit_stride));
-        // cells no crop tile covers lie outside the field of view for good: "unknown" in plane 1 (read without the laser only)
-        if (!cfg->use_laser)
-            HIPCHK_H(hipMemset2D(d.big_bits + d.big_words, (size_t)8 * d.big_words, 0xFF, (size_t)4 * d.big_words, (size_t)RL));
-        h->big_max_crop = max_crop;
-        h->big_full_chunks = (int)(((size_t)g.Hv * g.Wv + VBF_T * 4 - 1) / (VBF_T * 4));
+        std::vector<uint8_t> tiled;
+        tile_crop(h->static_map.data(), Hg, Wg, wt, (size_t)d.crop_ws, tiled);
+        uint8_t* sc = nullptr;
+        RTRY(dev_alloc(h, &sc, (size_t)d.crop_ws));
+        HIPCHK(hipMemcpy(sc, tiled.data(), tiled.size(), hipMemcpyHostToDevice));
+        d.static_crop = sc;
+        RTRY(dev_alloc(h, &d.crop_map, (size_t)d.crop_ws * W));
+        HIPCHK(hipMemcpy(d.crop_map, sc, (size_t)d.crop_ws, hipMemcpyDeviceToDevice));
+        RTRY(copy_to_worlds(d.crop_map, d.crop_ws, W));
     }
+    std::vector<BigClassDev> bc(h->rcls.size());
+    int max_crop = 1;
+    for (size_t q = 0; q < h->rcls.size(); q++) {
+        RobotClassHost& k = h->rcls[q];
+        BigClassDev& o = bc[q];
+        memset(&o, 0, sizeof(o));
+        o.ta = k.big_ta;
+        o.tb = k.big_tb;
+        o.n_crop = k.n_crop;
+        max_crop = std::max(max_crop, o.n_crop);
+        RTRY(dev_upload(h, &o.crop_tiles, k.crop_tiles));
+        RTRY(dev_upload(h, &o.crop_masks, k.crop_masks));
+        RTRY(dev_upload(h, &o.cells, k.big_cells));
+        RTRY(dev_upload(h, &o.ray_end, k.ray_end));
+        {
+            const uint32_t* p2 = nullptr;
+            RTRY(dev_upload(h, &p2, k.big_inv));
+            o.inv = (const uint2*)p2;
+        }
+        if (p.view_resize) {
+            build_big_taps(k, g, ax.ofs, ay.ofs);
+            const uint32_t* p2i = nullptr;
+            RTRY(dev_upload(h, &o.tap_top, k.tap_top));
+            RTRY(dev_upload(h, &p2i, k.tap_inv));
+            o.tap_inv = (const uint2*)p2i;
+            RTRY(dev_upload(h, &o.tap_addr, k.tap_addr));
+            RTRY(dev_upload(h, &o.tap_chunks, k.tap_chunks));
+            o.n_tap_chunks = (int)k.tap_chunks.size();
+            h->big_tap_chunks_dyn = std::max(h->big_tap_chunks_dyn, o.n_tap_chunks);
+            std::vector<uint32_t>().swap(k.tap_top);
+            std::vector<uint32_t>().swap(k.tap_inv);
+            std::vector<uint32_t>().swap(k.tap_addr);
+        }
+    }
+    for (size_t q = 0; q < bc.size(); q++) d.big[q] = bc[q];
+    RTRY(dev_alloc(h, &d.big_bits, (size_t)RL * 2 * d.big_words));
+    RTRY(dev_alloc(h, &d.big_hit, (size_t)RL * d.big_hit_stride));
+    // cells no crop tile covers lie outside the field of view for good: "unknown" in plane 1 (read without the laser only)
+    if (!h->cfg.use_laser)
+        HIPCHK(hipMemset2D(d.big_bits + d.big_words, (size_t)8 * d.big_words, 0xFF, (size_t)4 * d.big_words, (size_t)RL));
+    h->big_max_crop = max_crop;
+    return 0;
+}
 
-    // robot / ped state
-    TRY(dev_alloc(h, &d.gx, RL)); TRY(dev_alloc(h, &d.gy, RL));
-    TRY(dev_alloc(h, &d.l0v, RL)); TRY(dev_alloc(h, &d.l0w, RL)); TRY(dev_alloc(h, &d.l1v, RL)); TRY(dev_alloc(h, &d.l1w, RL));
-    TRY(dev_alloc(h, &d.world_target, RL));
-    TRY(dev_alloc(h, &d.is_coll, RL)); TRY(dev_alloc(h, &d.is_arr, RL)); TRY(dev_alloc(h, &d.py_done, RL));
-    TRY(dev_alloc(h, &d.clean_state, RL, 1));
-    TRY(dev_alloc(h, &d.tmp_dist, RL));
-    TRY(dev_alloc(h, &d.pm_cells, (size_t)RL * PM_CAP));
-    TRY(dev_alloc(h, &d.pm_n, RL));  // 0: the arena starts zeroed, nothing to clear
-    {   // k_raster's LDS box and the per-robot footprint cell lists (classes with a huge footprint go without)
-        int box = 1, cap = 1;
-        for (const RobotClassHost& k : h->rcls) {
-            const int side = 2 * k.box_rad + 1;
-            if (side * side > RASTER_BOX_CELLS) continue;
-            box = std::max(box, side * side);
-            cap = std::max(cap, std::min(side * side, k.fp.n()));
-        }
-        if (h->sum) {  // the pedestrians' boxes share the rasters' LDS, and every pedestrian keeps the list of the cells it counts itself on
-            int pbox = 1;
-            for (const PedClassHost& k : h->pcls) pbox = std::max(pbox, (2 * k.box_rad + 1) * (2 * k.box_rad + 1));
-            d.pd_cap = pbox;
-            d.ped_box_cells = pbox;
-            box = std::max(box, pbox);
-            TRY(dev_alloc(h, &d.pd_cells, (size_t)(P > 0 ? P : 1) * pbox));
-            TRY(dev_alloc(h, &d.pd_n, P > 0 ? P : 1));
-        }
-        d.box_cells = box;
-        d.fp_cap = cap;
-        TRY(dev_alloc(h, &d.bbox, 4));
-        d.sharded = RL != R;
-        int max_rad = 0;
-        for (const RobotClassHost& k : h->rcls) max_rad = std::max(max_rad, k.box_rad);
-        d.region_margin = (int)ceil(0.5 * sqrt((double)g.Hv * g.Hv + (double)g.Wv * g.Wv)) + max_rad + 3;
-        TRY(dev_alloc(h, &d.fp_cells, (size_t)RL * cap));
-        TRY(dev_alloc(h, &d.fp_n, RL, 0xFF));  // -1 until the first raster
-        TRY(dev_alloc(h, &d.fp_pose, (size_t)RL * 3));
+// robot / pedestrian / RVO state, the beep lottery, the flags the device raises
+static int create_agents(imgenv* h, const CreatePlan& p) {
+    DevWorld& d = h->d;
+    const int R = p.R, P = p.P, RL = p.RL, NA = p.NA, W = p.W;
+    RTRY(dev_alloc(h, &d.gx, RL)); RTRY(dev_alloc(h, &d.gy, RL));
+    RTRY(dev_alloc(h, &d.l0v, RL)); RTRY(dev_alloc(h, &d.l0w, RL)); RTRY(dev_alloc(h, &d.l1v, RL)); RTRY(dev_alloc(h, &d.l1w, RL));
+    RTRY(dev_alloc(h, &d.world_target, RL));
+    RTRY(dev_alloc(h, &d.is_coll, RL)); RTRY(dev_alloc(h, &d.is_arr, RL)); RTRY(dev_alloc(h, &d.py_done, RL));
+    RTRY(dev_alloc(h, &d.clean_state, RL, 1));
+    RTRY(dev_alloc(h, &d.tmp_dist, RL));
+    RTRY(dev_alloc(h, &d.pm_cells, (size_t)RL * PM_CAP));
+    RTRY(dev_alloc(h, &d.pm_n, RL));  // 0: the arena starts zeroed, nothing to clear
+    if (h->sum) {  // every pedestrian keeps the list of the cells it counts itself on
+        RTRY(dev_alloc(h, &d.pd_cells, (size_t)(P > 0 ? P : 1) * d.pd_cap));
+        RTRY(dev_alloc(h, &d.pd_n, P > 0 ? P : 1));
     }
-    TRY(dev_alloc(h, &d.ppx, P)); TRY(dev_alloc(h, &d.ppy, P)); TRY(dev_alloc(h, &d.pyaw, P));
-    TRY(dev_alloc(h, &d.plx, P)); TRY(dev_alloc(h, &d.ply, P)); TRY(dev_alloc(h, &d.pvx, P)); TRY(dev_alloc(h, &d.pvy, P));
-    TRY(dev_alloc(h, &d.prem, P)); TRY(dev_alloc(h, &d.llx, P)); TRY(dev_alloc(h, &d.lly, P));
-    TRY(dev_alloc(h, &d.rlx, P)); TRY(dev_alloc(h, &d.rly, P));
-    TRY(dev_alloc(h, &d.pstate, P)); TRY(dev_alloc(h, &d.ptraj_idx, P));
-    TRY(dev_alloc(h, &h->d_traj_len, P));
+    RTRY(dev_alloc(h, &d.bbox, 4));
+    RTRY(dev_alloc(h, &d.fp_cells, (size_t)RL * d.fp_cap));
+    RTRY(dev_alloc(h, &d.fp_n, RL, 0xFF));  // -1 until the first raster
+    RTRY(dev_alloc(h, &d.fp_pose, (size_t)RL * 3));
+    RTRY(dev_alloc(h, &d.ppx, P)); RTRY(dev_alloc(h, &d.ppy, P)); RTRY(dev_alloc(h, &d.pyaw, P));
+    RTRY(dev_alloc(h, &d.plx, P)); RTRY(dev_alloc(h, &d.ply, P)); RTRY(dev_alloc(h, &d.pvx, P)); RTRY(dev_alloc(h, &d.pvy, P));
+    RTRY(dev_alloc(h, &d.prem, P)); RTRY(dev_alloc(h, &d.llx, P)); RTRY(dev_alloc(h, &d.lly, P));
+    RTRY(dev_alloc(h, &d.rlx, P)); RTRY(dev_alloc(h, &d.rly, P));
+    RTRY(dev_alloc(h, &d.pstate, P)); RTRY(dev_alloc(h, &d.ptraj_idx, P));
+    RTRY(dev_alloc(h, &h->d_traj_len, P));
     d.ptraj_len = h->d_traj_len;
-    const int NA = h->NA;
-    TRY(dev_alloc(h, &d.apx, NA)); TRY(dev_alloc(h, &d.apy, NA)); TRY(dev_alloc(h, &d.avx, NA)); TRY(dev_alloc(h, &d.avy, NA));
-    TRY(dev_alloc(h, &d.anvx, NA)); TRY(dev_alloc(h, &d.anvy, NA));
-    TRY(dev_alloc(h, &d.near_n, P)); TRY(dev_alloc(h, &d.near_list, (size_t)(P > 0 ? P : 1) * ORCA_NEAR_CAP));
+    RTRY(dev_alloc(h, &d.apx, NA)); RTRY(dev_alloc(h, &d.apy, NA)); RTRY(dev_alloc(h, &d.avx, NA)); RTRY(dev_alloc(h, &d.avy, NA));
+    RTRY(dev_alloc(h, &d.anvx, NA)); RTRY(dev_alloc(h, &d.anvy, NA));
+    RTRY(dev_alloc(h, &d.near_n, P)); RTRY(dev_alloc(h, &d.near_list, (size_t)(P > 0 ? P : 1) * ORCA_NEAR_CAP));
     {
         std::vector<float> ms(NA > 0 ? NA : 1, 0.6f);  // robots: maxSpeed 0.6 (rvoscene.h:63)
         for (int j = 0; j < P && j < NA; j++) ms[j] = (float)(double)h->pmax[j];
-        TRY(dev_upload(h, &d.amax_speed, ms));
+        RTRY(dev_upload(h, &d.amax_speed, ms));
     }
-    d.beep_on = beep_on ? 1 : 0;
-    d.beep_r = cfg->beep_r;
-    d.ped_ca_p = (double)cfg->ped_ca_p;
-    if (beep_on) {  // one rand() stream per world = per node process of the reference, as a fresh process starts it
+    if (p.beep_on) {  // one rand() stream per world = per node process of the reference, as a fresh process starts it
         uint32_t s0[31];
         beep_initial_state(s0);
         std::vector<uint32_t> st((size_t)31 * W);
         for (int k = 0; k < W; k++) memcpy(&st[(size_t)31 * k], s0, sizeof(s0));
         const uint32_t* up = nullptr;
-        TRY(dev_upload(h, &up, st));
+        RTRY(dev_upload(h, &up, st));
         d.beep_state = const_cast<uint32_t*>(up);
-        TRY(dev_upload(h, &d.beep_coef, beep_coefficients(BEEP_T)));
-        TRY(dev_alloc(h, &d.beep_flag, R));
-        TRY(dev_alloc(h, &d.beep_xy, R));
+        RTRY(dev_upload(h, &d.beep_coef, beep_coefficients(BEEP_T)));
+        RTRY(dev_alloc(h, &d.beep_flag, R));
+        RTRY(dev_alloc(h, &d.beep_xy, R));
     }
-    {   // the finished-world list of imgenv_step_autoreset: written by k_finished straight into page-locked host memory
-        int* f = nullptr;
-        HIPCHK_H(hipHostMalloc((void**)&f, (size_t)(1 + W) * sizeof(int), hipHostMallocMapped));
-        memset(f, 0, (size_t)(1 + W) * sizeof(int));
-        h->finished_host = f;
-        int* dev = nullptr;
-        HIPCHK_H(hipHostGetDevicePointer((void**)&dev, f, 0));
-        d.finished = dev;
-    }
-    {   // overflow flags live in page-locked host memory the device writes through: no copy, no sync to read them
-        int* e = nullptr;
-        HIPCHK_H(hipHostMalloc((void**)&e, 8 * sizeof(int), hipHostMallocMapped));
-        memset(e, 0, 8 * sizeof(int));
-        h->err_host = e;
-        int* dev = nullptr;
-        HIPCHK_H(hipHostGetDevicePointer((void**)&dev, e, 0));
-        d.err = dev;
-        d.sfm.err = dev + 4;
-    }
-    if (cfg->ped_scene_type == IMGENV_SCENE_PEDSIM) {  // PedScene(): Tscene(0,10,10,10), addPed, addRobot (pedscene.h:17-80)
-        // one crowd per world (the reference: one node process = one PedScene per env), every array W slices back to back;
-        // every world starts as a fresh process does: the same default-seeded draws
-        SfmDev& f = d.sfm;
-        const int Pw = h->Pw, Rw = h->Rw;
-        const int n = Pw + (cfg->relation_ped_robo == 1 ? Rw : 0), n1 = n ? n : 1;
-        f.n = n; f.n_peds = Pw; f.n_obs = 0; f.W = W;
-        f.cap_nodes = W > 1 ? 2048 : 16384;  // (libpedsim's tree only ever grows: a crowd that outgrows its pool raises the overflow flag)
-        f.cap_obs = 0;
-        PedsimRng rng;
-        std::vector<double> p0((size_t)n1 * 3, 0.0), vmax(n1, 0.0);
-        std::vector<SfmNode> nodes(f.cap_nodes);
-        std::vector<int> treehash(n1, 0);
-        int n_nodes = 0, err = 0;
-        sfm_q_new(nodes.data(), &n_nodes, f.cap_nodes, 0, 10, 10, 10);
-        // every Tagent() draws its vmax (peds then robots, also robots that stay outside the scene)
-        for (int a = 0; a < n; a++) {
-            vmax[a] = rng.normal_fresh(1.2, 0.2);
-            if (a < Pw) {
-                p0[3 * a] = rng.glibc_rand() / 2147483647.0 * 10.0;
-                p0[3 * a + 1] = rng.glibc_rand() / 2147483647.0 * 10.0;
-                vmax[a] = (double)h->pmax[a];
-            }
-            sfm_add_agent(nodes.data(), &n_nodes, f.cap_nodes, treehash.data(), p0.data(), a, &err);
-        }
-        if (err) {
-            imgenv_destroy(h);
-            FAIL(IMGENV_EINVAL, "pedscene quadtree construction overflowed (%d)", err);
-        }
-        const size_t Wn = (size_t)W * n1;
-        TRY(dev_alloc(h, &f.p, Wn * 3));
-        TRY(dev_alloc(h, &f.v, Wn * 3));
-        TRY(dev_alloc(h, &f.vmax, Wn)); TRY(dev_alloc(h, &f.wpx, Wn * SFM_MAX_WP));
-        TRY(dev_alloc(h, &f.wpy, Wn * SFM_MAX_WP)); TRY(dev_alloc(h, &f.wpr, Wn * SFM_MAX_WP));
-        TRY(dev_alloc(h, &f.dq, Wn * SFM_MAX_WP)); TRY(dev_alloc(h, &f.dq_n, Wn));
-        TRY(dev_alloc(h, &f.dest, Wn, 0xFF)); TRY(dev_alloc(h, &f.last, Wn, 0xFF));  // -1
-        TRY(dev_alloc(h, &f.nodes, (size_t)W * f.cap_nodes)); TRY(dev_alloc(h, &f.n_nodes, W)); TRY(dev_alloc(h, &f.treehash, Wn));
-        TRY(dev_alloc(h, &f.pair_f, (size_t)W * n1 * n1 * 3)); TRY(dev_alloc(h, &f.pair_code, (size_t)W * n1 * n1));
-        TRY(dev_alloc(h, &f.g_nb, (size_t)W * SFM_MAX_AGENTS * (SFM_MAX_AGENTS / 32))); TRY(dev_alloc(h, &f.g_sh, (size_t)W * 4 * SFM_MAX_AGENTS));
-        if (W > 1) {  // room for every world's obstacle segments up front (a slice cannot grow without moving the others)
-            f.cap_obs = 64;
-            int* nobs = nullptr;
-            TRY(dev_alloc(h, &f.obs, (size_t)W * f.cap_obs * 4));
-            TRY(dev_alloc(h, &nobs, W));
-            f.n_obs_w = nobs;
-            h->sfm_cap_obs = f.cap_obs;
-            h->sfm_nobs_w.assign(W, 0);
-        }
-        f.p_out = f.p; f.v_out = f.v; f.dq_out = f.dq; f.dest_out = f.dest; f.last_out = f.last;  // (a step in place)
-        f.nodes_out = f.nodes; f.n_nodes_out = f.n_nodes; f.treehash_out = f.treehash;
-        h->sfm_ahead = cfg->relation_ped_robo != 1 && n > 0 && !h->serial;
-        if (h->sfm_ahead) {
-            SfmDev& o = h->sfm_other;
-            o = f;
-            TRY(dev_alloc(h, &o.p, Wn * 3)); TRY(dev_alloc(h, &o.v, Wn * 3));
-            TRY(dev_alloc(h, &o.dq, Wn * SFM_MAX_WP)); TRY(dev_alloc(h, &o.dest, Wn, 0xFF)); TRY(dev_alloc(h, &o.last, Wn, 0xFF));
-            TRY(dev_alloc(h, &o.nodes, (size_t)W * f.cap_nodes)); TRY(dev_alloc(h, &o.n_nodes, W)); TRY(dev_alloc(h, &o.treehash, Wn));
-            HIPCHK_H(hipStreamCreateWithFlags(&h->sfm_stream, hipStreamNonBlocking));
-            HIPCHK_H(hipEventCreateWithFlags(&h->ev_sfm, hipEventDisableTiming | hipEventDisableSystemFence));
-            HIPCHK_H(hipEventCreateWithFlags(&h->ev_sfm_in[0], hipEventDisableTiming | hipEventDisableSystemFence));
-            HIPCHK_H(hipEventCreateWithFlags(&h->ev_sfm_in[1], hipEventDisableTiming | hipEventDisableSystemFence));
-        }
-        for (int k = 0; k < W; k++) {
-            HIPCHK_H(hipMemcpy(f.p + (size_t)k * n1 * 3, p0.data(), sizeof(double) * 3 * n1, hipMemcpyHostToDevice));
-            HIPCHK_H(hipMemcpy(f.vmax + (size_t)k * n1, vmax.data(), sizeof(double) * n1, hipMemcpyHostToDevice));
-            HIPCHK_H(hipMemcpy(f.nodes + (size_t)k * f.cap_nodes, nodes.data(), sizeof(SfmNode) * n_nodes, hipMemcpyHostToDevice));
-            HIPCHK_H(hipMemcpy(f.n_nodes + k, &n_nodes, sizeof(int), hipMemcpyHostToDevice));
-            HIPCHK_H(hipMemcpy(f.treehash + (size_t)k * n1, treehash.data(), sizeof(int) * n1, hipMemcpyHostToDevice));
-        }
-    }
-    TRY(dev_alloc(h, &d.prof, 16 + 12 * (size_t)RL));
-    d.state_in_integrate = P == 0 ? 1 : 0;
-    TRY(dev_alloc(h, &d.tail_sig, RL));
-    TRY(dev_alloc(h, &d.tail_cnt, (size_t)(RL + WAVE - 1) / WAVE * TAIL_CNT_STRIDE));
-    TRY(dev_alloc(h, &d.dbg, 32));  // phase sums | per-wave (start, end, hw id, -) of k_view and k_obs
+    // the finished-world list of imgenv_step_autoreset: written by k_finished straight into page-locked host memory
+    RTRY(mapped_ints((size_t)(1 + W), &h->finished_host, &d.finished));
+    // overflow flags live in page-locked host memory the device writes through: no copy, no sync to read them
+    RTRY(mapped_ints(8, &h->err_host, &d.err));
+    d.sfm.err = d.err + 4;
+    return 0;
+}
 
-    // output arena
-    ArenaPlan plan;
-    plan_arena(*cfg, g, RL, plan);
-    const bool full_rewrite = (cfg->flags & IMGENV_FLAG_FULL_REWRITE) != 0;
-    h->arena_bytes = plan.total;
-    if (full_rewrite && RL != R) {  // (a shard's caller all-gathers the records in place: that buffer cannot be a copy)
-        imgenv_destroy(h);
-        FAIL(IMGENV_EINVAL, "IMGENV_FLAG_FULL_REWRITE is not available in a robot shard");
+// the social-force crowd: PedScene(): Tscene(0,10,10,10), addPed, addRobot (pedscene.h:17-80)
+static int create_crowd(imgenv* h, const CreatePlan& p) {
+    const imgenv_cfg& c = h->cfg;
+    if (c.ped_scene_type != IMGENV_SCENE_PEDSIM) return 0;
+    // one crowd per world (the reference: one node process = one PedScene per env), every array W slices back to back;
+    // every world starts as a fresh process does: the same default-seeded draws
+    SfmDev& f = h->d.sfm;
+    const int Pw = p.Pw, Rw = p.Rw, W = p.W;
+    const int n = Pw + (c.relation_ped_robo == 1 ? Rw : 0), n1 = n ? n : 1;
+    f.n = n; f.n_peds = Pw; f.n_obs = 0; f.W = W;
+    f.cap_nodes = W > 1 ? 2048 : 16384;  // (libpedsim's tree only ever grows: a crowd that outgrows its pool raises the overflow flag)
+    f.cap_obs = 0;
+    PedsimRng rng;
+    std::vector<double> p0((size_t)n1 * 3, 0.0), vmax(n1, 0.0);
+    std::vector<SfmNode> nodes(f.cap_nodes);
+    std::vector<int> treehash(n1, 0);
+    int n_nodes = 0, err = 0;
+    sfm_q_new(nodes.data(), &n_nodes, f.cap_nodes, 0, 10, 10, 10);
+    // every Tagent() draws its vmax (peds then robots, also robots that stay outside the scene)
+    for (int a = 0; a < n; a++) {
+        vmax[a] = rng.normal_fresh(1.2, 0.2);
+        if (a < Pw) {
+            p0[3 * a] = rng.glibc_rand() / 2147483647.0 * 10.0;
+            p0[3 * a + 1] = rng.glibc_rand() / 2147483647.0 * 10.0;
+            vmax[a] = (double)h->pmax[a];
+        }
+        sfm_add_agent(nodes.data(), &n_nodes, f.cap_nodes, treehash.data(), p0.data(), a, &err);
     }
-    if (cfg->out_arena && cfg->out_arena_bytes < (int64_t)plan.total) {
-        imgenv_destroy(h);
-        FAIL(IMGENV_EINVAL, "out_arena too small: %lld < %zu", (long long)cfg->out_arena_bytes, plan.total);
+    if (err) FAIL(IMGENV_EINVAL, "pedscene quadtree construction overflowed (%d)", err);
+    const size_t Wn = (size_t)W * n1;
+    RTRY(dev_alloc(h, &f.p, Wn * 3));
+    RTRY(dev_alloc(h, &f.v, Wn * 3));
+    RTRY(dev_alloc(h, &f.vmax, Wn)); RTRY(dev_alloc(h, &f.wpx, Wn * SFM_MAX_WP));
+    RTRY(dev_alloc(h, &f.wpy, Wn * SFM_MAX_WP)); RTRY(dev_alloc(h, &f.wpr, Wn * SFM_MAX_WP));
+    RTRY(dev_alloc(h, &f.dq, Wn * SFM_MAX_WP)); RTRY(dev_alloc(h, &f.dq_n, Wn));
+    RTRY(dev_alloc(h, &f.dest, Wn, 0xFF)); RTRY(dev_alloc(h, &f.last, Wn, 0xFF));  // -1
+    RTRY(dev_alloc(h, &f.nodes, (size_t)W * f.cap_nodes)); RTRY(dev_alloc(h, &f.n_nodes, W)); RTRY(dev_alloc(h, &f.treehash, Wn));
+    RTRY(dev_alloc(h, &f.pair_f, (size_t)W * n1 * n1 * 3)); RTRY(dev_alloc(h, &f.pair_code, (size_t)W * n1 * n1));
+    RTRY(dev_alloc(h, &f.g_nb, (size_t)W * SFM_MAX_AGENTS * (SFM_MAX_AGENTS / 32))); RTRY(dev_alloc(h, &f.g_sh, (size_t)W * 4 * SFM_MAX_AGENTS));
+    if (W > 1) {  // room for every world's obstacle segments up front (a slice cannot grow without moving the others)
+        f.cap_obs = 64;
+        int* nobs = nullptr;
+        RTRY(dev_alloc(h, &f.obs, (size_t)W * f.cap_obs * 4));
+        RTRY(dev_alloc(h, &nobs, W));
+        f.n_obs_w = nobs;
+        h->sfm_cap_obs = f.cap_obs;
+        h->sfm_nobs_w.assign(W, 0);
     }
-    if (full_rewrite) {  // the caller's arena (or a second allocation) only ever receives copies; the kernels work on a private one
-        if (cfg->out_arena) {
-            h->pub_arena = (unsigned char*)cfg->out_arena;
+    f.p_out = f.p; f.v_out = f.v; f.dq_out = f.dq; f.dest_out = f.dest; f.last_out = f.last;  // (a step in place)
+    f.nodes_out = f.nodes; f.n_nodes_out = f.n_nodes; f.treehash_out = f.treehash;
+    if (h->sfm_ahead) {
+        SfmDev& o = h->sfm_other;
+        o = f;
+        RTRY(dev_alloc(h, &o.p, Wn * 3)); RTRY(dev_alloc(h, &o.v, Wn * 3));
+        RTRY(dev_alloc(h, &o.dq, Wn * SFM_MAX_WP)); RTRY(dev_alloc(h, &o.dest, Wn, 0xFF)); RTRY(dev_alloc(h, &o.last, Wn, 0xFF));
+        RTRY(dev_alloc(h, &o.nodes, (size_t)W * f.cap_nodes)); RTRY(dev_alloc(h, &o.n_nodes, W)); RTRY(dev_alloc(h, &o.treehash, Wn));
+        HIPCHK(hipStreamCreateWithFlags(&h->sfm_stream, hipStreamNonBlocking));
+        RTRY(chain_event(&h->ev_sfm));
+        RTRY(chain_event(&h->ev_sfm_in[0]));
+        RTRY(chain_event(&h->ev_sfm_in[1]));
+    }
+    for (int k = 0; k < W; k++) {
+        HIPCHK(hipMemcpy(f.p + (size_t)k * n1 * 3, p0.data(), sizeof(double) * 3 * n1, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(f.vmax + (size_t)k * n1, vmax.data(), sizeof(double) * n1, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(f.nodes + (size_t)k * f.cap_nodes, nodes.data(), sizeof(SfmNode) * n_nodes, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(f.n_nodes + k, &n_nodes, sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(f.treehash + (size_t)k * n1, treehash.data(), sizeof(int) * n1, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+// the chain's scratch, the output arena (out_fields.h has its arrays) and the guards over it
+static int create_outputs(imgenv* h, const CreatePlan& p) {
+    DevWorld& d = h->d;
+    const imgenv_cfg& c = h->cfg;
+    const ViewGeom& g = h->geom;
+    const ArenaLayout& lay = p.arena;
+    const int RL = p.RL;
+    RTRY(dev_alloc(h, &d.prof, 16 + 12 * (size_t)RL));
+    RTRY(dev_alloc(h, &d.tail_sig, RL));
+    RTRY(dev_alloc(h, &d.tail_cnt, (size_t)(RL + WAVE - 1) / WAVE * TAIL_CNT_STRIDE));
+    RTRY(dev_alloc(h, &d.dbg, 32));  // phase sums | per-wave (start, end, hw id, -) of k_view and k_obs
+
+    if (p.full_rewrite) {  // the caller's arena (or a second allocation) only ever receives copies; the kernels work on a private one
+        if (c.out_arena) {
+            h->pub_arena = (unsigned char*)c.out_arena;
         } else {
-            void* p = nullptr;
-            if (hipMalloc(&p, plan.total) != hipSuccess) {
-                imgenv_destroy(h);
-                FAIL(IMGENV_ENOMEM, "hipMalloc(%zu) for the public output arena failed", plan.total);
-            }
-            h->pub_arena = (unsigned char*)p;
+            void* pub = nullptr;
+            if (hipMalloc(&pub, lay.total) != hipSuccess) FAIL(IMGENV_ENOMEM, "hipMalloc(%zu) for the public output arena failed", lay.total);
+            h->pub_arena = (unsigned char*)pub;
             h->own_pub = true;
         }
-        HIPCHK_H(hipMemset(h->pub_arena, 0, plan.total));
+        HIPCHK(hipMemset(h->pub_arena, 0, lay.total));
     }
-    if (cfg->out_arena && !full_rewrite) {
-        h->arena = (unsigned char*)cfg->out_arena;
+    if (c.out_arena && !p.full_rewrite) {
+        h->arena = (unsigned char*)c.out_arena;
     } else {
-        void* p = nullptr;
-        hipError_t e = hipMalloc(&p, plan.total);
-        if (e != hipSuccess) {
-            imgenv_destroy(h);
-            FAIL(IMGENV_ENOMEM, "hipMalloc(%zu) for the output arena failed: %s", plan.total, hipGetErrorString(e));
-        }
-        h->arena = (unsigned char*)p;
+        void* own = nullptr;
+        hipError_t e = hipMalloc(&own, lay.total);
+        if (e != hipSuccess) FAIL(IMGENV_ENOMEM, "hipMalloc(%zu) for the output arena failed: %s", lay.total, hipGetErrorString(e));
+        h->arena = (unsigned char*)own;
         h->own_arena = true;
     }
-    HIPCHK_H(hipMemset(h->arena, 0, plan.total));
+    HIPCHK(hipMemset(h->arena, 0, lay.total));
     unsigned char* A = h->arena;
     imgenv_out& o = h->out;
     o.struct_size = (int32_t)sizeof(imgenv_out);
-    o.n_local = RL; o.view_h = g.Hv; o.view_w = g.Wv; o.n_beams = g.B; o.state_dim = cfg->state_dim; o.ped_vec_len = d.PV;
-    o.image_h = d.img_h; o.image_w = d.img_w; o.grid_h = Hg; o.grid_w = Wg;
-    o.vector_states = (float*)(A + plan.off[0]);
-    o.view_maps = (uint8_t*)(A + plan.off[1]);
-    o.sensor_maps = (uint16_t*)(A + plan.off[2]);
-    o.lasers_raw = (float*)(A + plan.off[3]);
-    o.lasers = (double*)(A + plan.off[4]);
-    o.ped_vector_states = (float*)(A + plan.off[5]);
-    o.ped_maps = (float*)(A + plan.off[6]);
-    o.is_collisions = (int8_t*)(A + plan.off[7]);
-    o.is_arrives = (uint8_t*)(A + plan.off[8]);
-    o.step_ds = (double*)(A + plan.off[9]);
-    o.ped_min_dists = (double*)(A + plan.off[10]);
-    o.base_rewards = (int32_t*)(A + plan.off[11]);
-    o.base_dones = (uint8_t*)(A + plan.off[12]);
-    o.rewards = (double*)(A + plan.off[13]);
-    o.dones = (uint8_t*)(A + plan.off[14]);
-    o.dones_info = (int32_t*)(A + plan.off[15]);
-    o.is_clean = (uint8_t*)(A + plan.off[16]);
-    o.robot_pose = (double*)(A + plan.off[17]);
-    o.ped_state = (double*)(A + plan.off[18]);
-    o.counters = (int32_t*)(A + plan.off[19]);
-    d.rec = (double*)(A + plan.off[20]);
-    o.paper_rewards = (double*)(A + plan.off[21]);
-    d.paper_rewards = o.paper_rewards;
-    o.step_rewards = (double*)(A + plan.off[22]);
-    o.step_dones = (uint8_t*)(A + plan.off[23]);
-    o.step_dones_info = (int32_t*)(A + plan.off[24]);
-    o.step_is_clean = (uint8_t*)(A + plan.off[25]);
-    o.step_is_arrives = (uint8_t*)(A + plan.off[26]);
-    o.step_is_collisions = (int8_t*)(A + plan.off[27]);
-    o.step_all_down = (uint8_t*)(A + plan.off[28]);
-    d.step_all_down = o.step_all_down;
-    if ((cfg->flags & IMGENV_FLAG_AGENT_STATE_EXTRAS) && g.B > 0) {
-        o.hits_x = (float*)(A + plan.off[29]);
-        o.hits_y = (float*)(A + plan.off[30]);
-        o.angular_map = (float*)(A + plan.off[31]);
-    } else {
-        o.hits_x = o.hits_y = o.angular_map = nullptr;
-    }
-    d.hits_x = o.hits_x; d.hits_y = o.hits_y; d.angular_map = o.angular_map;
-    d.view_max_dist32 = cfg->view_max_dist;
-    d.step_rewards = o.step_rewards; d.step_dones = o.step_dones; d.step_dones_info = o.step_dones_info;
-    d.step_is_clean = o.step_is_clean; d.step_is_arrives = o.step_is_arrives; d.step_is_collisions = o.step_is_collisions;
-    d.vector_states = o.vector_states; d.view_maps = o.view_maps; d.sensor_maps = o.sensor_maps;
-    d.lasers_raw = o.lasers_raw; d.lasers = o.lasers; d.ped_vector_states = o.ped_vector_states;
-    d.ped_maps = o.ped_maps; d.is_collisions = o.is_collisions; d.is_arrives = o.is_arrives;
-    d.step_ds = o.step_ds; d.ped_min_dists = o.ped_min_dists; d.base_rewards = o.base_rewards;
-    d.base_dones = o.base_dones; d.rewards = o.rewards; d.dones = o.dones; d.dones_info = o.dones_info;
-    d.is_clean = o.is_clean; d.robot_pose = o.robot_pose; d.ped_state = o.ped_state; d.counters = o.counters;
+    o.n_local = RL; o.view_h = g.Hv; o.view_w = g.Wv; o.n_beams = g.B; o.state_dim = c.state_dim; o.ped_vec_len = d.PV;
+    o.image_h = d.img_h; o.image_w = d.img_w; o.grid_h = p.Hg; o.grid_w = p.Wg;
+    // every array's pointer into imgenv_out and, under the same name, into DevWorld (the records: DevWorld alone)
+    const bool extras = p.out.extras && p.out.has_beams;
+#define OUT_PTR(name, bytes) d.name = o.name = (decltype(o.name))(A + lay.off[OUTF_##name]);
+#define OUT_PTR_EXTRA(name, bytes) d.name = o.name = extras ? (decltype(o.name))(A + lay.off[OUTF_##name]) : nullptr;
+#define OUT_PTR_HIDDEN(name, bytes) d.rec = (double*)(A + lay.off[OUTF_##name]);
+    OUT_FIELDS(OUT_PTR, OUT_PTR_EXTRA, OUT_PTR_HIDDEN)
+#undef OUT_PTR
+#undef OUT_PTR_EXTRA
+#undef OUT_PTR_HIDDEN
     {   // NearbyPed starts at +inf and is never re-initialised (reset_helper.py:85-99); is_clean starts True
         std::vector<double> inf(RL, INFINITY);
-        HIPCHK_H(hipMemcpy(o.ped_min_dists, inf.data(), sizeof(double) * RL, hipMemcpyHostToDevice));
-        HIPCHK_H(hipMemset(o.is_clean, 1, RL));
+        HIPCHK(hipMemcpy(o.ped_min_dists, inf.data(), sizeof(double) * RL, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(o.is_clean, 1, RL));
     }
-    if (full_rewrite) {  // the same struct with every pointer moved into the public arena
+    if (p.full_rewrite) {  // the same struct with every pointer moved into the public arena
         h->pub_out = o;
         const ptrdiff_t shift = h->pub_arena - h->arena;
-        for (void** f : {(void**)&h->pub_out.vector_states, (void**)&h->pub_out.view_maps, (void**)&h->pub_out.sensor_maps, (void**)&h->pub_out.lasers_raw,
-                         (void**)&h->pub_out.lasers, (void**)&h->pub_out.ped_vector_states, (void**)&h->pub_out.ped_maps, (void**)&h->pub_out.is_collisions,
-                         (void**)&h->pub_out.is_arrives, (void**)&h->pub_out.step_ds, (void**)&h->pub_out.ped_min_dists, (void**)&h->pub_out.base_rewards,
-                         (void**)&h->pub_out.base_dones, (void**)&h->pub_out.rewards, (void**)&h->pub_out.paper_rewards, (void**)&h->pub_out.dones,
-                         (void**)&h->pub_out.dones_info, (void**)&h->pub_out.is_clean, (void**)&h->pub_out.robot_pose, (void**)&h->pub_out.ped_state,
-                         (void**)&h->pub_out.counters, (void**)&h->pub_out.step_rewards, (void**)&h->pub_out.step_dones, (void**)&h->pub_out.step_dones_info,
-                         (void**)&h->pub_out.step_is_clean, (void**)&h->pub_out.step_is_arrives, (void**)&h->pub_out.step_is_collisions,
-                         (void**)&h->pub_out.step_all_down, (void**)&h->pub_out.hits_x, (void**)&h->pub_out.hits_y, (void**)&h->pub_out.angular_map})
-            if (*f) *f = (unsigned char*)*f + shift;
+#define OUT_SHIFT(name, bytes) \
+    if (o.name) h->pub_out.name = (decltype(o.name))((unsigned char*)o.name + shift);
+#define OUT_STAYS(name, bytes)
+        OUT_FIELDS(OUT_SHIFT, OUT_SHIFT, OUT_STAYS)
+#undef OUT_SHIFT
+#undef OUT_STAYS
     }
-    if (cfg->flags & (IMGENV_FLAG_CHECK_OUTPUTS | IMGENV_FLAG_CHECK_OUTPUTS_FIRST)) {  // every array of imgenv_out (not the records: the caller's exchange writes those)
-        if (!(cfg->flags & IMGENV_FLAG_CHECK_OUTPUTS)) h->guard_left = IMGENV_CHECK_FIRST_CALLS;
-        static const char* const names[32] = {"vector_states", "view_maps", "sensor_maps", "lasers_raw", "lasers", "ped_vector_states", "ped_maps",
-                                              "is_collisions", "is_arrives", "step_ds", "ped_min_dists", "base_rewards", "base_dones", "rewards", "dones",
-                                              "dones_info", "is_clean", "robot_pose", "ped_state", "counters", "records", "paper_rewards", "step_rewards",
-                                              "step_dones", "step_dones_info", "step_is_clean", "step_is_arrives", "step_is_collisions", "step_all_down",
-                                              "hits_x", "hits_y", "angular_map"};
+    if (c.flags & (IMGENV_FLAG_CHECK_OUTPUTS | IMGENV_FLAG_CHECK_OUTPUTS_FIRST)) {  // every array of imgenv_out (not the records: the caller's exchange writes those)
+        if (!(c.flags & IMGENV_FLAG_CHECK_OUTPUTS)) h->guard_left = IMGENV_CHECK_FIRST_CALLS;
+        OutFieldRow rows[OUTF_COUNT];
+        out_field_rows(p.out, rows);
         std::vector<OutSpan> spans;
         int blocks = 0;
-        for (int q = 0; q < plan.n; q++) {
-            const size_t bytes = (q + 1 < plan.n ? plan.off[q + 1] : plan.total) - plan.off[q];  // (the padding up to the next array is zero and stays zero)
-            if (q == 20 || (q >= 29 && !o.hits_x)) continue;
+        for (int q = 0; q < OUTF_COUNT; q++) {
+            if (!rows[q].guarded || !out_field_exists(p.out, rows[q])) continue;
             OutSpan sp;
-            sp.p = A + plan.off[q];
-            sp.bytes = bytes;
+            sp.p = A + lay.off[q];
+            sp.bytes = lay.slot(q);  // (the padding up to the next array is zero and stays zero)
             sp.first_block = blocks;
-            blocks += (int)((bytes + OUT_SUM_CHUNK - 1) / OUT_SUM_CHUNK);
-            h->span_name[spans.size()] = names[q];
+            blocks += (int)((sp.bytes + OUT_SUM_CHUNK - 1) / OUT_SUM_CHUNK);
+            h->span_name[spans.size()] = rows[q].name;
             spans.push_back(sp);
         }
         h->n_spans = (int)spans.size();
         h->span_blocks = blocks;
         const OutSpan* up = nullptr;
-        TRY(dev_upload(h, &up, spans));
+        RTRY(dev_upload(h, &up, spans));
         h->d_spans = const_cast<OutSpan*>(up);
-        TRY(dev_alloc(h, &h->d_sums, 2 * (size_t)h->n_spans));
+        RTRY(dev_alloc(h, &h->d_sums, 2 * (size_t)h->n_spans));
         h->guard_check = true;
     }
-    h->PP = plan_obs_slots(h->Pw);  // sort slots of k_obs: a power of two, 64 * E of them in registers up to 1024 pedestrians
-    h->obs_E = plan_obs_E(h->PP);
+    return 0;
+}
+
+// what the observation kernel keeps between steps, and the snapshots of an early-observation step
+static int create_obs_state(imgenv* h, const CreatePlan& p) {
+    DevWorld& d = h->d;
+    const int RL = p.RL, P = p.P;
     if (h->obs_E >= 2) {
         // last step's pedestrian order per robot (k_obs): any permutation of the slots will do to start from
         std::vector<uint16_t> ident((size_t)h->PP);
         for (int q = 0; q < h->PP; q++) ident[q] = q < h->Pw ? (uint16_t)q : (uint16_t)0xFFFF;
-        TRY(dev_alloc(h, &d.obs_ord, (size_t)RL * h->PP));
+        RTRY(dev_alloc(h, &d.obs_ord, (size_t)RL * h->PP));
         std::vector<uint16_t> all((size_t)RL * h->PP);
         for (int r = 0; r < RL; r++) memcpy(&all[(size_t)r * h->PP], ident.data(), sizeof(uint16_t) * (size_t)h->PP);
-        HIPCHK_H(hipMemcpy(d.obs_ord, all.data(), sizeof(uint16_t) * all.size(), hipMemcpyHostToDevice));
-        // (measured: 200 pedestrians 1 pass 101.8, 2-5 passes 94-96 us per headline step; 1000 pedestrians 1 / 3 / 6 / 12 passes 316 / 303 / 282 / 282 us per cfg-5 step, 294 with the full sort every step)
-        d.obs_passes = h->obs_E >= 8 ? 6 : 3;
+        HIPCHK(hipMemcpy(d.obs_ord, all.data(), sizeof(uint16_t) * all.size(), hipMemcpyHostToDevice));
     }
-    const size_t NC = (size_t)g.Hv * g.Wv;
-    max_stride += 4;  // + the dummy beam of view cells that no beam crosses (kept a multiple of 16 bytes)
-    d.hit_stride = (int)max_stride;
-    h->lds_view = plan_lds_view(NC, max_stride, g.Wv);
-    static_assert(PM_CAP * 2 <= WAVE * 7 * 4, "the touched-cell list reuses the staging buffer");
-    h->lds_obs = plan_lds_obs(h->obs_E, h->PP, h->Pw);
-    if (h->big_view) {  // k_beams_big: the occupied plane of the crop bitmap; k_taps_big: the hit words
-        h->big_bits_in_lds = plan_big_bits_in_lds((size_t)d.big_words);
-        h->lds_view_big = plan_lds_view_big((size_t)d.big_words);
-        h->lds_view = 16;
-        d.big_bits_in_lds = h->big_bits_in_lds ? 1 : 0;
-        if (taps_lds_bytes(g.B) > LDS_MAX) {
-            imgenv_destroy(h);
-            FAIL(IMGENV_EINVAL, "the hit words of %d beams do not fit the 160 KiB LDS", g.B);
-        }
+    if (h->cfg.ped_scene_type == IMGENV_SCENE_PEDSIM)
+        HIPCHK(hipFuncSetAttribute((const void*)k_sfm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(SfmNode) * SFM_LDS_NODES)));
+    // The early k_obs (where: plan_early_obs) always waits behind the GATE (world.h: sync): it reads the step's actions and REWRITES
+    // output arrays, so it must run behind everything the caller queued on its stream in front of the step -- a policy that writes the actions, a
+    // copy of the last observation into a replay buffer, FULL_REWRITE's own copy.  (Rounds 4-5 also had an ungated variant for
+    // callers that promised complete actions, IMGENV_STEP_ACTIONS_READY; it only waited for the last chain's views, which does
+    // not cover readers of the outputs -- and measured the same as the gate, 92.0 against 92.3 us per step.  Dropped in round 6.)
+    if (h->early) {
+        RTRY(dev_alloc(h, &d.sync, 8));
+        RTRY(dev_alloc(h, &h->rec_snap[0], (size_t)RL * IMGENV_RECORD_DOUBLES));
+        RTRY(dev_alloc(h, &h->rec_snap[1], (size_t)RL * IMGENV_RECORD_DOUBLES));
+        RTRY(dev_alloc(h, &h->ped_snap[0], (size_t)(h->NA > 0 ? P : 1)));
+        RTRY(dev_alloc(h, &h->ped_snap[1], (size_t)(h->NA > 0 ? P : 1)));
     }
-    if (h->lds_view > LDS_MAX || h->lds_obs > LDS_MAX) {
-        imgenv_destroy(h);
-        FAIL(IMGENV_EINVAL, "view (%zu B) or pedestrian list (%zu B) does not fit the 160 KiB LDS", h->lds_view, h->lds_obs);
-    }
-    if (cfg->ped_scene_type == IMGENV_SCENE_PEDSIM)
-        HIPCHK_H(hipFuncSetAttribute((const void*)k_sfm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(SfmNode) * SFM_LDS_NODES)));
-    {   // early-observation steps: worlds owned whole, an ORCA crowd that nothing but the solve moves (no beep lottery), no
-        // limiter history to carry, views through k_view -- the headline shape and cfg-5; everything else keeps k_obs behind the move
-        const bool limiters = cfg->limiter_v.has_velocity_limits || cfg->limiter_v.has_acceleration_limits || cfg->limiter_v.has_jerk_limits ||
-                              cfg->limiter_w.has_velocity_limits || cfg->limiter_w.has_acceleration_limits || cfg->limiter_w.has_jerk_limits;
-        // The early k_obs always waits behind the GATE (world.h: sync): it reads the step's actions and REWRITES output arrays, so it
-        // must run behind everything the caller queued on its stream in front of the step -- a policy that writes the actions, a
-        // copy of the last observation into a replay buffer, FULL_REWRITE's own copy.  (Rounds 4-5 also had an ungated variant for
-        // callers that promised complete actions, IMGENV_STEP_ACTIONS_READY; it only waited for the last chain's views, which does
-        // not cover readers of the outputs -- and measured the same as the gate, 92.0 against 92.3 us per step.  Dropped in round 6.)
-        // ... or a social-force crowd that is stepped a step ahead (sfm_ahead): its arrays are published in front of the move and
-        // stand still during the step, so the early k_obs reads them as they are (obs_early = 2); the gate also says that the
-        // publishing is done
-        // (robot shards too, since round 6: k_obs reads the rank's own robots' snapshots and the replicated pedestrians')
-        h->early = !h->serial && P > 0 && (h->NA > 0 || h->sfm_ahead) && !d.beep_on && !limiters && !h->big_view &&
-                   plan_integrate_fits(h->n_sub);
-        if (h->early) {
-            TRY(dev_alloc(h, &d.sync, 8));
-            TRY(dev_alloc(h, &h->rec_snap[0], (size_t)RL * IMGENV_RECORD_DOUBLES));
-            TRY(dev_alloc(h, &h->rec_snap[1], (size_t)RL * IMGENV_RECORD_DOUBLES));
-            TRY(dev_alloc(h, &h->ped_snap[0], (size_t)(h->NA > 0 ? P : 1)));
-            TRY(dev_alloc(h, &h->ped_snap[1], (size_t)(h->NA > 0 ? P : 1)));
-        }
-    }
-    HIPCHK_H(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
+    return 0;
+}
+
+// side streams, the gate probe, the chain's events, the launch rules' facts and the kernels' LDS
+static int create_streams(imgenv* h, const CreatePlan& p) {
+    DevWorld& d = h->d;
+    HIPCHK(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
     // (Round 6 tried the observation's stream on a subset of the compute units, hipExtStreamCreateWithCUMask, so that the move's
     // successors find free units at once: such a stream is a BLOCKING one -- it serialises against a caller on the null stream, 95 ->
     // 213 us per step whatever the mask -- and beside a caller on a stream of its own 24 / 28 / 16 of an XCD's 32 units cost 99.2 /
     // 99.5 / 108.3 us against 95.5: the step is bound by the instructions it issues, not by where they run.  docs/HISTORY.md)
-    HIPCHK_H(hipStreamCreateWithFlags(&h->side2, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(&h->side2, hipStreamNonBlocking));
     if (h->early) {  // gates (world.h: sync) only where kernels of two streams really run side by side: k_gate_probe
         static int gates_work = -1;  // (per process)
         if (gates_work < 0) {
             k_gate_probe<<<dim3(1), dim3(WAVE), 0, h->side2>>>(d.sync + 2);
             k_gate_probe_set<<<dim3(1), dim3(1), 0, h->side>>>(d.sync + 2);
-            HIPCHK_H(hipStreamSynchronize(h->side2));
-            HIPCHK_H(hipStreamSynchronize(h->side));
+            HIPCHK(hipStreamSynchronize(h->side2));
+            HIPCHK(hipStreamSynchronize(h->side));
             uint32_t verdict = 0;
-            HIPCHK_H(hipMemcpy(&verdict, d.sync + 3, sizeof(verdict), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(&verdict, d.sync + 3, sizeof(verdict), hipMemcpyDeviceToHost));
             gates_work = verdict == 1u ? 1 : 0;
         }
         h->gates_work = gates_work == 1;
     }
-    d.view_prio = (P == 0 || (h->early && h->gates_work && h->NA > 0 && h->obs_E >= 1 && h->obs_E <= 4)) ? 1 : 0;  // (world.h)
-    HIPCHK_H(hipEventCreateWithFlags(&h->ev_fork2, hipEventDisableTiming | hipEventDisableSystemFence));
-    HIPCHK_H(hipEventCreateWithFlags(&h->ev_join2, hipEventDisableTiming | hipEventDisableSystemFence));
-    HIPCHK_H(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming | hipEventDisableSystemFence));
-    HIPCHK_H(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming | hipEventDisableSystemFence));
+    d.view_prio = (p.P == 0 || (h->early && h->gates_work && h->NA > 0 && h->obs_E >= 1 && h->obs_E <= 4)) ? 1 : 0;  // (world.h)
+    RTRY(chain_event(&h->ev_fork2));
+    RTRY(chain_event(&h->ev_join2));
+    RTRY(chain_event(&h->ev_fork));
+    RTRY(chain_event(&h->ev_join));
     plan_facts(h);
-    TRY(lds_attributes(h));
-    HIPCHK_H(hipDeviceSynchronize());
+    RTRY(lds_attributes(h));
+    HIPCHK(hipDeviceSynchronize());
+    return 0;
+}
+
+extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, int32_t Hg, int32_t Wg,
+                             imgenv_t** out) {
+    CreateMsg msg;
+    CreateArgs a;
+    if (int rc = create_check_args(cfg, static_map != nullptr, out != nullptr, Hg, Wg, a, msg)) FAIL(rc, "%s", msg);
+    const int Hg_in = Hg, Wg_in = Wg;
+    if (int rc = create_grid_size(*cfg, a.W, Hg, Wg, msg)) FAIL(rc, "%s", msg);
+    std::vector<uint8_t> resized_map;
+    if (cfg->global_resolution != cfg->view_resolution) {  // GridMap::read_image (grid_map.cpp:28-38)
+        resized_map.resize((size_t)Hg * Wg);
+        cv_resize_u8(false, static_map, Hg_in, Wg_in, resized_map.data(), Hg, Wg);
+        static_map = resized_map.data();
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) FAIL(IMGENV_EDEVICE, "no HIP device available");
+    if (cfg->device < 0 || cfg->device >= ndev) FAIL(IMGENV_EDEVICE, "device %d out of range (%d)", cfg->device, ndev);
+    HIPCHK(hipSetDevice(cfg->device));
+    const bool serial = getenv("IMGENV_SERIAL") && getenv("IMGENV_SERIAL")[0] == '1';
+
+    imgenv* h = new imgenv();
+    CreatePlan plan;
+    int rc = create_classes(h, *cfg, a);
+    if (!rc && (rc = plan_create(*cfg, a, Hg, Wg, serial, h->rcls, h->pcls, plan, msg))) snprintf(g_err, sizeof(g_err), "%s", msg);
+    if (!rc) create_facts(h, plan, static_map, Hg_in, Wg_in);
+    static int (*const phases[])(imgenv*, const CreatePlan&) = {create_grid_layers, create_class_tables, create_view_tables, create_agents,
+                                                                create_crowd,       create_outputs,      create_obs_state,   create_streams};
+    for (auto phase : phases)
+        if (!rc) rc = phase(h, plan);
+    if (rc) {  // the one owner of the half-built handle
+        imgenv_destroy(h);
+        return rc;
+    }
     *out = h;
     return IMGENV_OK;
 }
@@ -2091,12 +1858,6 @@ static int stage_end(imgenv* h, hipStream_t st) {
     h->gen_pending[h->gen] = true;
     return 0;
 }
-
-// (errors inside reset leave the handle alive)
-#define RTRY(expr)                   \
-    do {                             \
-        if (int rc_ = (expr)) return rc_; \
-    } while (0)
 
 // a launch covers every world (list == nullptr) or the robots, pedestrians and cells of the n listed worlds
 static void set_active(imgenv* h, const int* list, int n) {

@@ -1588,7 +1588,6 @@ __device__ __forceinline__ void raster_ped(const DevWorld& w, int j, const PedCl
     }
 }
 
-#define RASTER_BOX_CELLS 2048  // LDS box of a robot raster: up to 45 x 45 cells
 
 // view_robot's inner loop (img_env.cpp:624-628) for ALL robots at once: instead of stamping every
 // other robot into a private copy of the grid per robot (O(R * Hg*Wg + R^2 * F)), each robot records

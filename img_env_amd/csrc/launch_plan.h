@@ -70,6 +70,10 @@
 #define ORCA_GROUP_MAX 4
 #define ORCA_ROW 16
 #define SFM_MAX_AGENTS 256
+#define OWNER_MULTI 0xFFFFFEu  // 24-bit owner field of the composed layer: several robots cover the cell
+#define RC_INLINE 6           // distinct robot classes (shape, size, sensor) per world, carried in the kernel arguments
+#define PC_INLINE 4           // distinct pedestrian classes per world
+#define RASTER_BOX_CELLS 2048  // LDS box of a robot raster: up to 45 x 45 cells
 
 enum { LAYER_COMPOSED = 0, LAYER_STAMP = 1, LAYER_SUM = 2 };  // the class layer's mode (world.h), as the kernels take it
 

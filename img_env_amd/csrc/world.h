@@ -4,13 +4,10 @@
 #include <stdint.h>
 
 #include "fp_rows.h"
-#include "launch_plan.h"  // WAVE, STAMP_TAGS, STAMP_MAX_ROBOTS, ORCA_NEAR_CAP: the constants the launch rules share
+#include "launch_plan.h"  // WAVE, STAMP_TAGS, STAMP_MAX_ROBOTS, ORCA_NEAR_CAP, OWNER_MULTI, RC_INLINE, PC_INLINE: the constants the launch rules share
 #include "sfm.h"
 #include "tfm.h"
 
-#define OWNER_MULTI 0xFFFFFEu  // 24-bit owner field of the composed layer: several robots cover the cell
-#define RC_INLINE 6           // distinct robot classes (shape, size, sensor) per world, carried in the kernel arguments
-#define PC_INLINE 4           // distinct pedestrian classes per world
 #define BEEP_T 256            // rand() values one round of k_beep produces
 
 // composed class layer byte (k_compose): low 3 bits = base class, bit 3 = "some robot covers it"

@@ -149,29 +149,39 @@ struct imgenv {
     int big_max_crop = 1, big_full_chunks = 1;
     // early-observation steps (world.h): k_obs is launched with the step, beside the move (k_move_raster), from snapshots
     bool early = false;             // the handle can run them (IMGENV_EARLY_OBS=0 in the environment switches them off)
-    float4* ped_snap[2] = {nullptr, nullptr};
-    unsigned orca_seq = 0;          // k_orca launches so far: launch q writes ped_snap[q & 1]
-    double* rec_snap[2] = {nullptr, nullptr};
-    unsigned view_seq = 0;          // k_view launches over every world so far: launch q writes rec_snap[q & 1]
-    bool early_step = false;
-    // an event that only has to say "this kernel is done" rides on the kernel's own dispatch packet (hipExtLaunchKernelGGL's stop
-    // event): a hipEventRecord behind the kernel is a packet of its own, and the caller's stream pays ~6 us for each
-    uint32_t gate_seq = 0;       // early steps so far: each one's k_obs waits behind a gate (world.h: sync) for its number
-    // the social-force crowd a step AHEAD (sfm.h: SfmDev *_out): crowds that ignore the robots (relation_ped_robo = 0) depend on
+    float4* ped_snap[2] = {nullptr, nullptr};  // behind k_orca: launch q over every world writes ped_snap[q & 1] (plan_snap_turn)
+    double* rec_snap[2] = {nullptr, nullptr};  // behind k_view, likewise
+    // What a step hands from imgenv_step_begin to the end of its chain, and a chain to the next one.  What launch_views and
+    // imgenv_step_begin do with it is decided in launch_plan.h ("ordering"; DESIGN.md §4 has the side wiring as a table); an
+    // abandoned step is recovered by step_recover alone.  Per member: who sets it / who clears it / what it means while set.
+    struct StepState {
+        bool in_step = false;      // imgenv_step_flags, around its imgenv_step_begin / the same / begin and end are one call: the move may be left to the chain
+        const float* actions = nullptr;  // step_entry / never (the caller keeps them until the chain's end) / the step's actions: a fused move and the tails read them
+        bool move_pending = false; // imgenv_step_begin (StepPlan::fuse_move) / launch_views / the chain's raster launch does the move (k_move_raster)
+        bool fork_on_move = false; // step_move (StepPlan::fork_on_move) / launch_obs, early_obs / ev_fork went out on k_integrate's packet: not recorded again
+        bool obs_forked = false;   // launch_obs, early_obs / launch_side, step_recover / the step's k_obs is in flight on its stream
+        bool early = false;        // early_obs / launch_views / that k_obs went out in front of the move: a solve on its stream waits for ev_fork
+        bool chain_open = false;   // chain_begin, early_obs / launch_views' end / tail_sig, tail_cnt may hold bits: the next chain_begin clears them first
+        uint32_t gate_seq = 0;     // imgenv_step_begin counts the early steps / never / the number k_integrate opens the gate with and k_gate waits for (world.h: sync)
+        unsigned orca_seq = 0;     // launch_side counts k_orca over every world / never / ped_snap's turn; 0: no snapshot yet
+        unsigned view_seq = 0;     // launch_compose_views counts k_view over every world / never / rec_snap's turn
+    } step;
+    // The social-force crowd a step AHEAD (sfm.h: SfmDev *_out): crowds that ignore the robots (relation_ped_robo = 0) depend on
     // nothing of a step, so k_sfm for step t + 1 runs on a stream of its own underneath step t's rasters and views, reads the
     // crowd as it is and leaves the next state in a second set of arrays; step t + 1 swaps the sets and only publishes
-    // (k_sfm_publish).  A reset in between drops what was computed ahead.
-    bool sfm_ahead = false;        // the handle can do that
-    bool sfm_ahead_valid = false;  // the other set holds the state of the next step (computed or being computed on sfm_stream)
-    int sfm_steps_since_reset = 0;
-    SfmDev sfm_other;              // the other set of the arrays a step writes (its p / v / dq / dest / last / nodes / n_nodes / treehash)
-    hipStream_t sfm_stream = nullptr;
-    hipEvent_t ev_sfm = nullptr;
-    hipEvent_t ev_sfm_in[2] = {nullptr, nullptr};  // behind a step's last access to the crowd's sets on the caller's stream, by step parity
-    int sfm_par = 0;
-    int sfm_ahead_wait = -1;  // >= 0: this imgenv_step_begin still owes the crowd's launch ahead, behind ev_sfm_in[that]
+    // (k_sfm_publish).  A reset in between drops what was computed ahead.  plan_crowd_step decides, step_crowd executes.
+    struct CrowdAhead {
+        bool can = false;          // create_facts (CreatePlan::sfm_ahead) / imgenv_step_autoreset_device, for good: its kernels reset crowds unseen / the handle does that
+        bool valid = false;        // sfm_launch_ahead / sfm_ahead_drop / `other` holds the next step's state (computed or being computed on `stream`)
+        int steps_since_reset = 0; // step_crowd counts / sfm_ahead_drop / 0: the next step launches nothing ahead
+        int par = 0;               // step_crowd flips / never / which ev_in the next step leaves
+        int wait = -1;             // step_crowd / sfm_launch_ahead / >= 0: this imgenv_step_begin still owes the launch ahead, behind ev_in[wait]
+        SfmDev other;              // the other set of the arrays a step writes (sfm_swap_sets)
+        hipStream_t stream = nullptr;
+        hipEvent_t ev = nullptr;   // behind the launch ahead
+        hipEvent_t ev_in[2] = {nullptr, nullptr};  // behind a step's last access to the crowd's sets on the caller's stream, by step parity
+    } crowd;
     bool gates_work = false;     // k_gate_probe's verdict: kernels of two streams run side by side in this process
-    bool fork_on_move = false;   // ev_fork went out with this step's k_integrate
     bool sum = false;        // SUM mode of the class layer (world.h): base class + counts kept by the agents themselves, no k_compose
     bool stamp = false;      // STAMP mode of the class layer (world.h) instead of two owner layers + k_compose
     uint32_t stamp_seq = 0;  // steps so far: the stamps of a step carry tag stamp_seq % STAMP_TAGS + 1
@@ -201,10 +211,6 @@ struct imgenv {
     std::unordered_map<uint64_t, std::unique_ptr<SpawnOut>> spawn_ahead;
     uint64_t spawn_ahead_cfg = 0;  // fingerprint of the spawn cfg the placements were drawn from
     int spawn_ahead_n = 8;
-    bool obs_forked = false;  // k_obs of the current step is already in flight (launched by step_begin)
-    // imgenv_step on a handle of at most 4096 robots, all local: the move is left to the raster launch (k_move_raster)
-    bool in_step = false, move_pending = false;
-    const float* move_actions = nullptr;
     double trace_acc[4] = {0, 0, 0, 0};  // IMGENV_TRACE_RESET: host time inside imgenv_step_autoreset
     long trace_calls = 0, trace_resets = 0;
     // device-side auto-reset (csrc/spawn_device.h): pool of placements drawn ahead on a side stream
@@ -241,7 +247,6 @@ struct imgenv {
     imgenv_episodes_cfg ep_cfg;
     imgenv_episodes_out ep_out;
     size_t ep_clear_bytes = 0;   // what imgenv_episodes_clear zeroes, from ep.f on
-    const float* ep_actions = nullptr;  // the actions of the step in progress (the caller keeps them until the chain's end)
     // episode log (include/imgenv.h: imgenv_episode_log_enable; csrc/episode_log.h)
     bool eplog_on = false;
     unsigned long long* d_place_serial = nullptr;  // SpawnDev::place_serial of the present pool (valid while sd_ready)
@@ -290,7 +295,6 @@ struct imgenv {
     MbGatherDev mb_gather;       // the field table and the ring's scalars; dst pointers are the buffer's (mb_out)
     imgenv_minibatch_cfg mb_cfg;
     imgenv_minibatch_out mb_out;
-    bool chain_open = false;  // a chain of launches that hands over through tail_sig / tail_cnt has started and not been completed
     std::vector<RvoObstacles> rvos;  // one obstacle set per world
     int sfm_cap_obs = 0;
     std::vector<int> sfm_nobs_w;  // pedscene, several worlds: obstacle segments of each world's crowd
@@ -540,12 +544,12 @@ extern "C" void imgenv_destroy(imgenv_t* h) {
         (void)hipStreamSynchronize(h->side3);
         (void)hipStreamDestroy(h->side3);
     }
-    if (h->sfm_stream) {
-        (void)hipStreamSynchronize(h->sfm_stream);
-        (void)hipStreamDestroy(h->sfm_stream);
+    if (h->crowd.stream) {
+        (void)hipStreamSynchronize(h->crowd.stream);
+        (void)hipStreamDestroy(h->crowd.stream);
     }
-    if (h->ev_sfm) (void)hipEventDestroy(h->ev_sfm);
-    for (hipEvent_t e : h->ev_sfm_in)
+    if (h->crowd.ev) (void)hipEventDestroy(h->crowd.ev);
+    for (hipEvent_t e : h->crowd.ev_in)
         if (e) (void)hipEventDestroy(e);
     if (h->ev_fill) (void)hipEventDestroy(h->ev_fill);
     if (h->ev_consumed) (void)hipEventDestroy(h->ev_consumed);
@@ -630,8 +634,8 @@ static PlanChain chain_facts(const imgenv* h, int is_reset, bool moved = false, 
     c.is_reset = is_reset != 0; c.moved = moved; c.local_only = local_only;
     c.stamp_seq = h->stamp_seq;
     c.orca_cap = std::max(h->cap_obst, d.n_obst);
-    c.chain_open = h->chain_open; c.orca_ran = h->orca_seq > 0; c.view_ran = h->view_seq > 0; c.in_step = h->in_step;
-    c.comm = h->comm != nullptr; c.crowd_ahead = h->sfm_ahead; c.early_off = early_off;
+    c.chain_open = h->step.chain_open; c.orca_ran = h->step.orca_seq > 0; c.view_ran = h->step.view_seq > 0; c.in_step = h->step.in_step;
+    c.comm = h->comm != nullptr; c.crowd_ahead = h->crowd.can; c.early_off = early_off;
     return c;
 }
 // every variant of this handle that wants more than the default 64 KiB of LDS is allowed it
@@ -765,7 +769,7 @@ static void create_facts(imgenv* h, const CreatePlan& p, const uint8_t* static_m
     h->PP = p.PP; h->obs_E = p.obs_E;
     h->lds_view = p.lds_view; h->lds_obs = p.lds_obs; h->lds_view_big = p.lds_view_big;
     static_assert(PM_CAP * 2 <= WAVE * 7 * 4, "the touched-cell list reuses the staging buffer");
-    h->sfm_ahead = p.sfm_ahead; h->early = p.early;
+    h->crowd.can = p.sfm_ahead; h->early = p.early;
     h->arena_bytes = p.arena.total;
 
     DevWorld& d = h->d;
@@ -1137,16 +1141,16 @@ static int create_crowd(imgenv* h, const CreatePlan& p) {
     }
     f.p_out = f.p; f.v_out = f.v; f.dq_out = f.dq; f.dest_out = f.dest; f.last_out = f.last;  // (a step in place)
     f.nodes_out = f.nodes; f.n_nodes_out = f.n_nodes; f.treehash_out = f.treehash;
-    if (h->sfm_ahead) {
-        SfmDev& o = h->sfm_other;
+    if (h->crowd.can) {
+        SfmDev& o = h->crowd.other;
         o = f;
         RTRY(dev_alloc(h, &o.p, Wn * 3)); RTRY(dev_alloc(h, &o.v, Wn * 3));
         RTRY(dev_alloc(h, &o.dq, Wn * SFM_MAX_WP)); RTRY(dev_alloc(h, &o.dest, Wn, 0xFF)); RTRY(dev_alloc(h, &o.last, Wn, 0xFF));
         RTRY(dev_alloc(h, &o.nodes, (size_t)W * f.cap_nodes)); RTRY(dev_alloc(h, &o.n_nodes, W)); RTRY(dev_alloc(h, &o.treehash, Wn));
-        HIPCHK(hipStreamCreateWithFlags(&h->sfm_stream, hipStreamNonBlocking));
-        RTRY(chain_event(&h->ev_sfm));
-        RTRY(chain_event(&h->ev_sfm_in[0]));
-        RTRY(chain_event(&h->ev_sfm_in[1]));
+        HIPCHK(hipStreamCreateWithFlags(&h->crowd.stream, hipStreamNonBlocking));
+        RTRY(chain_event(&h->crowd.ev));
+        RTRY(chain_event(&h->crowd.ev_in[0]));
+        RTRY(chain_event(&h->crowd.ev_in[1]));
     }
     for (int k = 0; k < W; k++) {
         HIPCHK(hipMemcpy(f.p + (size_t)k * n1 * 3, p0.data(), sizeof(double) * 3 * n1, hipMemcpyHostToDevice));
@@ -1444,11 +1448,11 @@ static void set_tail_fields(imgenv* h, int is_reset, int tail_elapsed) {
 // itself re-zeroes them.  A chain that was abandoned half-way (an error between imgenv_step_begin and imgenv_step_end, a failing
 // launch) leaves stale bits behind: the next chain clears the words first.
 static int chain_begin(imgenv* h, hipStream_t st) {
-    if (h->chain_open) {
+    if (h->step.chain_open) {
         HIPCHK(hipMemsetAsync(h->d.tail_sig, 0, sizeof(unsigned long long) * (size_t)h->RL, st));
         HIPCHK(hipMemsetAsync(h->d.tail_cnt, 0, sizeof(int) * (size_t)(h->RL + WAVE - 1) / WAVE * TAIL_CNT_STRIDE, st));
     }
-    h->chain_open = true;
+    h->step.chain_open = true;
     return 0;
 }
 
@@ -1489,6 +1493,16 @@ static int outputs_verify(imgenv* h, hipStream_t st) {
     return 0;
 }
 
+// Recovery from a step that was begun and never ended (the caller's exchange failed in between), at the reset that follows: its
+// k_obs is in flight on a side stream and will still arrive at the tails' hand-over words; wait for it, the reset's first chain
+// then clears them (StepState::chain_open is still set).  Nothing else of StepState is touched.
+static int step_recover(imgenv* h) {
+    if (!h->step.obs_forked) return 0;
+    if (h->side2) HIPCHK(hipStreamSynchronize(h->side2));
+    h->step.obs_forked = false;
+    return 0;
+}
+
 static int launch_obs_kernel(imgenv* h, hipStream_t s_obs) {
     DevWorld& d = h->d;
     const LaunchShape o = plan_obs(h->plan, chain_facts(h, 0));
@@ -1502,12 +1516,12 @@ static int launch_obs(imgenv* h, hipStream_t st) {
     const bool overlap = !h->serial;
     hipStream_t s_obs = overlap ? h->side2 : st;
     if (overlap) {
-        if (!h->fork_on_move) HIPCHK(hipEventRecord(h->ev_fork, st));
-        h->fork_on_move = false;
+        if (!h->step.fork_on_move) HIPCHK(hipEventRecord(h->ev_fork, st));
+        h->step.fork_on_move = false;
         HIPCHK(hipStreamWaitEvent(s_obs, h->ev_fork, 0));
     }
     if (int rc = launch_obs_kernel(h, s_obs)) return rc;
-    h->obs_forked = true;
+    h->step.obs_forked = true;
     return 0;
 }
 
@@ -1531,7 +1545,7 @@ static int launch_rasters(imgenv* h, hipStream_t st, int is_reset, bool moved, b
     // (imgenv_step_end has counted the step when it launches this; imgenv_step_begin has not yet)
     const int step_now = from_begin ? h->elapsed : h->elapsed - 1;
     if (r.move)
-        TIMED(h, IMGENV_K_MOVE_RASTER, st, (k_move_raster_for(p, r.nw)<<<gr, br, r.launch.lds, st>>>(d, h->move_actions, h->n_sub, step_now, r.move_peds)));
+        TIMED(h, IMGENV_K_MOVE_RASTER, st, (k_move_raster_for(p, r.nw)<<<gr, br, r.launch.lds, st>>>(d, h->step.actions, h->n_sub, step_now, r.move_peds)));
     else
         TIMED(h, IMGENV_K_RASTER, st, (k_raster_for(p, r.nw)<<<gr, br, r.launch.lds, st>>>(d, is_reset, r.split)));
     d.act_ng = keep_ng;
@@ -1552,205 +1566,154 @@ static int rollout_room(const imgenv* h) {
     return 0;
 }
 
-// The chain behind the move: side launches, rasters, compose, views, the tails' stacks and statistics -- plan, then launch in stream order
-static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
+// ---- the chain behind the move (launch_views): what its phases share -- the chain's facts and plans, made once
+struct ChainPlans {
+    int is_reset;
+    bool moved;  // the move was left to this chain's raster launch (k_move_raster)
+    PlanChain c;
+    SidePlan s;
+    SideWiring w;
+    ViewPlan v;
+};
+static hipStream_t stream_of(const imgenv* h, int on, hipStream_t st) { return on == ON_SIDE ? h->side : on == ON_SIDE2 ? h->side2 : st; }
+template <typename T>
+static T* snap_buf(T* (&buf)[2], int k) { return k < 0 ? nullptr : buf[k]; }
+// rasters, compose and view count as three launches whatever the layer mode and the view's kind make of them: imgenv_step_launches
+// is compared between handles as it is
+static constexpr int CHAIN_FIXED_LAUNCHES = 3;
+
+// 1. The final observations (final_obs.h), in front of everything of this chain that writes a captured field -- its k_obs (forked
+// behind this launch in stream order), its views and their tails, its k_stack<true> and k_obs_post<true>: the rows the chain
+// covers, as the last step left them.  What a reset chain has launched before this point (the staged copies and map restores,
+// k_respawn and the rest of the device-side reset) writes none of them.
+static int launch_final_obs(imgenv* h, hipStream_t st) {
+    FinalObsDev fo = h->final_dev;
+    fo.rows = tail_rows(h, 1);
+    const PlanChain cf = chain_facts(h, 1);
+    const int guess = cf.n_dev ? plan_dev_reset(h->plan, h->finished_host[0], 0).guess : 0;
+    const LaunchShape g = plan_final_obs_launch(h->plan, cf, fo.chunks_per_row, guess);
+    k_final_obs<<<dim3(g.grid), dim3(g.block), 0, st>>>(fo);
+    h->launches += 1;
+    return 0;
+}
+
+// 2. A robot shard in SUM mode has drawn its own robots in imgenv_step_begin, in front of the exchange, and takes the other ranks'
+// from their records now, right behind it; "the records are complete" for the side streams rides on this kernel's dispatch packet
+// (a hipEventRecord behind the exchange is a packet of its own on the caller's stream: ~6 us)
+static int launch_remote(imgenv* h, hipStream_t st, const ChainPlans& k) {
+    const hipEvent_t ev = k.w.fork2_on_remote ? h->ev_fork2 : nullptr;
+    TIMED(h, IMGENV_K_REMOTE, st, (hipExtLaunchKernelGGL(k_remote_for(h->plan), dim3(k.s.remote.grid), dim3(k.s.remote.block), 0, st, nullptr, ev, 0, h->d)));
+    h->launches += 1;
+    return 0;
+}
+
+// 3. Beside the rasters, compose and view run the pedestrian half of the observation (unless it went out with the step) and the
+// next step's _step_ped_normal solve (img_env.cpp:304-343), on the streams and behind the events plan_side_wiring names; both
+// need poses only.
+static int launch_side(imgenv* h, hipStream_t st, const ChainPlans& k) {
+    DevWorld& d = h->d;
+    const SidePlan& s = k.s;
+    const SideWiring& w = k.w;
+    hipStream_t s_orca = stream_of(h, w.solve_on, st), s_obs = stream_of(h, w.obs_on, st);
+    if (!h->step.obs_forked) RTRY(launch_obs(h, st));
+    h->step.obs_forked = false;
+    if (w.record_fork2) HIPCHK(hipEventRecord(h->ev_fork2, st));
+    if (w.solve_waits) HIPCHK(hipStreamWaitEvent(s_orca, w.solve_waits == WAIT_FORK2 ? h->ev_fork2 : h->ev_fork, 0));
+    if (!s.fold_side) {
+        k_side_robots<<<dim3(s.robots.grid), dim3(s.robots.block), 0, s_orca>>>(d, k.is_reset, s.rvo_agents, s.slices);
+        h->launches += 1;
+    }
+    if (s.orca) {
+        const SnapTurn t = plan_snap_turn(h->step.orca_seq, h->early, k.c.listed);
+        d.ped_snap_out = snap_buf(h->ped_snap, t.out);
+        d.ped_snap_out2 = snap_buf(h->ped_snap, t.out2);
+        TIMED(h, IMGENV_K_ORCA, s_orca, (k_orca<<<dim3(s.orca_blocks), dim3(WAVE), orca_lds_bytes(s.L), s_orca>>>(d, s.L)));
+        if (t.advance) h->step.orca_seq += 1;
+        h->launches += 1;
+    }
+    if (w.join) {
+        HIPCHK(hipEventRecord(h->ev_join, s_orca));
+        HIPCHK(hipStreamWaitEvent(s_obs, h->ev_join, 0));
+    }
+    if (w.join2) HIPCHK(hipEventRecord(h->ev_join2, s_obs));
+    return 0;
+}
+
+// 6. Compose, then the views: view_big.h's crop -> beams -> the shrunk sensor_map -> the full view, only where it is an output --
+// or k_view, which also leaves the snapshot the next early k_obs reads.  No launch for the per-robot scalars: the k_view / k_obs
+// wavefront that completes a group of 64 robots runs them (tail_group); the last kernel commits the robots' new is_collision_.
+static int launch_compose_views(imgenv* h, hipStream_t st, const ChainPlans& k) {
     DevWorld& d = h->d;
     const PlanHandle& p = h->plan;
-    set_tail_fields(h, is_reset, h->elapsed);
-    if (is_reset && h->final_on && h->obs_exists) {
-        // the final observations (final_obs.h), in front of everything of this chain that writes a captured field -- its k_obs
-        // (forked below, behind this launch in stream order), its views and their tails, its k_stack<true> and k_obs_post<true>:
-        // the rows the chain covers, as the last step left them.  What a reset chain has launched before this point (the staged
-        // copies and map restores, k_respawn and the rest of the device-side reset) writes none of them.
-        FinalObsDev fo = h->final_dev;
-        fo.rows = tail_rows(h, 1);
-        const PlanChain cf = chain_facts(h, 1);
-        const int guess = cf.n_dev ? plan_dev_reset(h->plan, h->finished_host[0], 0).guess : 0;
-        const LaunchShape g = plan_final_obs_launch(h->plan, cf, fo.chunks_per_row, guess);
-        k_final_obs<<<dim3(g.grid), dim3(g.block), 0, st>>>(fo);
-        h->launches += 1;
-    }
-    if (h->P == 0)
-        if (int rc = chain_begin(h, st)) return rc;
-    // the rasters: in a step whose move was left to them (imgenv_step_begin: k_move_raster) they come first and the side stream forks
-    // behind them, otherwise behind the side launches; a robot shard in SUM mode has drawn its own robots in imgenv_step_begin, in
-    // front of the exchange, and takes the other ranks' from their records now (k_remote)
-    const bool moved = h->move_pending;
-    h->move_pending = false;
-    const PlanChain c = chain_facts(h, is_reset, moved);
-    const SidePlan s = plan_side(p, c);
-    const ViewPlan v = plan_views(p, c);
-    auto rasters = [&]() -> int {
-        if (!s.remote_only) return launch_rasters(h, st, is_reset, moved, false);
-        return 0;  // (k_remote went out in front of the side launches: below)
-    };
-    if (s.remote_only) {
-        // the other ranks' robots, right behind the exchange; "the records are complete" for the side streams rides on this kernel's
-        // dispatch packet (a hipEventRecord behind the exchange is a packet of its own on the caller's stream: ~6 us)
-        const hipEvent_t ev = s.side_reads_all && !h->serial ? h->ev_fork2 : nullptr;
-        TIMED(h, IMGENV_K_REMOTE, st, (hipExtLaunchKernelGGL(k_remote_for(p), dim3(s.remote.grid), dim3(s.remote.block), 0, st, nullptr, ev, 0, d)));
-        h->launches += 1;
-    }
-    if (moved)
-        if (int rc = rasters()) return rc;
-    if (h->P > 0) {
-        // One fork and one join per step on the caller's stream (every event operation costs it a ~6 us dependency
-        // bubble).  Beside the rasters, compose and view run, on two side streams (one for handles of at most 4096 robots:
-        // plan_side), the pedestrian half of the observation and the next step's _step_ped_normal solve (img_env.cpp:304-343);
-        // both need poses only.  The observation stream finally waits for the solve, so its join event covers both.
-        hipStream_t s_orca = s.overlap ? (s.one_side ? h->side2 : h->side) : st;
-        if (!h->obs_forked)
-            if (int rc = launch_obs(h, st)) return rc;
-        h->obs_forked = false;
-        hipStream_t s_obs = s.overlap ? h->side2 : st;
-        if (h->early_step && s.one_side) HIPCHK(hipStreamWaitEvent(s_orca, h->ev_fork, 0));  // (k_obs went out with the step, in front of the move: the solve waits for it)
-        if (s.overlap && !s.one_side) {
-            if (d.sharded && s.side_reads_all) {  // the solve needs every rank's robots: a second fork behind the exchange
-                if (!s.remote_only) HIPCHK(hipEventRecord(h->ev_fork2, st));  // (k_remote carries it otherwise)
-                HIPCHK(hipStreamWaitEvent(s_orca, h->ev_fork2, 0));
-            } else {
-                HIPCHK(hipStreamWaitEvent(s_orca, h->ev_fork, 0));
-            }
-        }
-        if (!s.fold_side) {
-            k_side_robots<<<dim3(s.robots.grid), dim3(s.robots.block), 0, s_orca>>>(d, is_reset, s.rvo_agents, s.slices);
-            h->launches += 1;
-        }
-        if (s.orca) {
-            // (world.h: what the next step's early k_obs reads.  A launch over every world writes one buffer and the next one the
-            // other; a launch over some worlds -- a reset chain, nothing else is in flight -- writes both and does not take a turn)
-            const bool partial = d.act_list != nullptr;
-            d.ped_snap_out = h->early ? h->ped_snap[h->orca_seq & 1] : nullptr;
-            d.ped_snap_out2 = h->early && partial ? h->ped_snap[(h->orca_seq + 1) & 1] : nullptr;
-            TIMED(h, IMGENV_K_ORCA, s_orca, (k_orca<<<dim3(s.orca_blocks), dim3(WAVE), orca_lds_bytes(s.L), s_orca>>>(d, s.L)));
-            if (!partial) h->orca_seq += 1;
-            h->launches += 1;
-        }
-        if (s.overlap) {
-            if (!s.one_side) {
-                HIPCHK(hipEventRecord(h->ev_join, s_orca));
-                HIPCHK(hipStreamWaitEvent(s_obs, h->ev_join, 0));
-            }
-            HIPCHK(hipEventRecord(h->ev_join2, s_obs));
-        }
-    }
-    if (s.state) {
-        k_state<<<dim3(s.state_shape.grid), dim3(s.state_shape.block), 0, st>>>(d);
-        h->launches += 1;
-    }
-    if (!moved)
-        if (int rc = rasters()) return rc;
-    if (p.layer == LAYER_COMPOSED) TIMED(h, IMGENV_K_COMPOSE, st, (k_compose<<<dim3(plan_compose_blocks(p, c)), dim3(256), 0, st>>>(d)));
-    if (p.big_view) {  // view_big.h: crop -> beams -> the shrunk sensor_map -> the full view, only where it is an output
-        TIMED(h, IMGENV_K_CROP, st, (k_crop_big_for(v.crop_sel)<<<dim3(v.crop.grid), dim3(v.crop.block), 0, st>>>(d, v.crop_chunks, c.act_nl, v.tpw)));
-        TIMED(h, IMGENV_K_VIEW, st, (k_beams_big_for(p)<<<dim3(v.beams.grid), dim3(v.beams.block), v.beams.lds, st>>>(d, v.quarters, v.qpw)));
-        // the last kernel of the chain commits the robots' new is_collision_
-        if (v.taps)
-            TIMED(h, IMGENV_K_TAPS, st, (k_taps_big<<<dim3(v.taps_shape.grid), dim3(v.taps_shape.block), v.taps_shape.lds, st>>>(d, v.tap_wgs, v.full ? 0 : 1, v.listed ? 1 : 0)));
-        if (v.full)
-            TIMED(h, IMGENV_K_FULLVIEW, st, (k_fullview_big<<<dim3(v.fullview.grid), dim3(v.fullview.block), v.fullview.lds, st>>>(d, h->big_full_chunks, 1)));
-        h->launches += (v.taps ? 1 : 0) + (v.full ? 1 : 0);
-    } else {
-        {   // (world.h: what the next step's early k_obs reads; turns as for ped_snap)
-            const bool partial = d.act_list != nullptr;
-            d.rec_snap_out = h->early ? h->rec_snap[h->view_seq & 1] : nullptr;
-            d.rec_snap_out2 = h->early && partial ? h->rec_snap[(h->view_seq + 1) & 1] : nullptr;
-            if (!partial) h->view_seq += 1;
-        }
+    const ViewPlan& v = k.v;
+    if (p.layer == LAYER_COMPOSED) TIMED(h, IMGENV_K_COMPOSE, st, (k_compose<<<dim3(plan_compose_blocks(p, k.c)), dim3(256), 0, st>>>(d)));
+    if (!p.big_view) {
+        const SnapTurn t = plan_snap_turn(h->step.view_seq, h->early, k.c.listed);
+        d.rec_snap_out = snap_buf(h->rec_snap, t.out);
+        d.rec_snap_out2 = snap_buf(h->rec_snap, t.out2);
+        if (t.advance) h->step.view_seq += 1;
         TIMED(h, IMGENV_K_VIEW, st, (hipExtLaunchKernelGGL(k_view_for(p, v.nw), dim3(v.view.grid), dim3(v.view.block), (uint32_t)v.view.lds, st, nullptr, nullptr, 0, d)));
+        return 0;
     }
-    // no launch for the per-robot scalars: the k_view / k_obs wavefront that completes a group of 64 robots runs them
-    // (tail_group).  The caller's stream ends the step behind both side streams
-    h->early_step = false;
-    if (h->P > 0 && !h->serial) HIPCHK(hipStreamWaitEvent(st, h->ev_join2, 0));
-    h->launches += 3;
-    if (h->stack_on && h->stack.n_fields > 0) {
-        // the observation stacks (stack.h), behind the join of the side streams and in front of the seal: a step pushes every local
-        // robot's new frames, a reset chain restarts the stacks of the robots it covers (plan_tail_rows)
-        StackDev sd = h->stack;
-        sd.rows = tail_rows(h, is_reset);
-        const LaunchShape g = plan_tail_launch(p, c, sd.chunks_per_robot, STACK_BLOCK, STACK_MAX_BLOCKS);
-        (is_reset ? k_stack<true> : k_stack<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(sd);
+    TIMED(h, IMGENV_K_CROP, st, (k_crop_big_for(v.crop_sel)<<<dim3(v.crop.grid), dim3(v.crop.block), 0, st>>>(d, v.crop_chunks, k.c.act_nl, v.tpw)));
+    TIMED(h, IMGENV_K_VIEW, st, (k_beams_big_for(p)<<<dim3(v.beams.grid), dim3(v.beams.block), v.beams.lds, st>>>(d, v.quarters, v.qpw)));
+    if (v.taps)
+        TIMED(h, IMGENV_K_TAPS, st, (k_taps_big<<<dim3(v.taps_shape.grid), dim3(v.taps_shape.block), v.taps_shape.lds, st>>>(d, v.tap_wgs, v.full ? 0 : 1, v.listed ? 1 : 0)));
+    if (v.full)
+        TIMED(h, IMGENV_K_FULLVIEW, st, (k_fullview_big<<<dim3(v.fullview.grid), dim3(v.fullview.block), v.fullview.lds, st>>>(d, h->big_full_chunks, 1)));
+    h->launches += (v.taps ? 1 : 0) + (v.full ? 1 : 0);
+    return 0;
+}
+
+// 8. The tails of the optional features, on the caller's stream behind the join of the side streams and in front of the seal; each
+// is a no-op unless its feature is on, and stands with its feature's enable function.  A step covers every local robot, a reset
+// chain the robots of its list (tail_rows).  The order is who reads whose output: the stacks push the chain's new frames; the
+// episode log reads the state the episodes' fold then closes; obs_post behind them (k_stack<true>'s cases); the normalisation
+// reads the stacks' newest frames; the rollout storage, last, stores what k_stack, k_obs_post and the normalisation have written.
+static void tail_stack(imgenv* h, hipStream_t st, const ChainPlans& k);
+static void tail_episodes(imgenv* h, hipStream_t st, const ChainPlans& k);
+static void tail_obs_post(imgenv* h, hipStream_t st, const ChainPlans& k);
+static void tail_normalise(imgenv* h, hipStream_t st, const ChainPlans& k);
+static void tail_rollout(imgenv* h, hipStream_t st, const ChainPlans& k);
+static void launch_tails(imgenv* h, hipStream_t st, const ChainPlans& k) {
+    tail_stack(h, st, k);
+    tail_episodes(h, st, k);
+    tail_obs_post(h, st, k);
+    tail_normalise(h, st, k);
+    tail_rollout(h, st, k);
+}
+
+// The chain behind the move -- plan, then launch in stream order.  The rasters come first in a step whose move was left to them
+// (imgenv_step_begin: k_move_raster; the side stream forks behind them), otherwise behind the side launches; k_remote has drawn a
+// SUM shard's.
+static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
+    set_tail_fields(h, is_reset, h->elapsed);
+    if (is_reset && h->final_on && h->obs_exists) RTRY(launch_final_obs(h, st));
+    if (h->P == 0) RTRY(chain_begin(h, st));
+    ChainPlans k;
+    k.is_reset = is_reset;
+    k.moved = h->step.move_pending;
+    h->step.move_pending = false;
+    k.c = chain_facts(h, is_reset, k.moved);
+    k.s = plan_side(h->plan, k.c);
+    k.w = plan_side_wiring(k.s, h->plan, h->step.early);
+    k.v = plan_views(h->plan, k.c);
+    const bool rasters = !k.s.remote_only;
+    if (k.s.remote_only) RTRY(launch_remote(h, st, k));
+    if (rasters && k.moved) RTRY(launch_rasters(h, st, is_reset, true, false));
+    if (h->P > 0) RTRY(launch_side(h, st, k));
+    if (k.s.state) {  // 4. no side streams: after a reset Agent::get_state gets its own small launch
+        k_state<<<dim3(k.s.state_shape.grid), dim3(k.s.state_shape.block), 0, st>>>(h->d);
         h->launches += 1;
     }
-    if (h->ep_on) {
-        // the episode statistics (episodes.h), in the same place: a step's command, reward and is_clean go into every local robot's
-        // open episode, a reset chain folds the episodes of the robots it covers by the last step's dones_info (grid as for k_stack)
-        EpisodesDev ed = h->ep;
-        ed.actions = h->ep_actions;
-        ed.rows = tail_rows(h, is_reset);
-        if (is_reset && h->eplog_on) {
-            // the episode log (episode_log.h), in front of the fold whose state it reads: one record per episode this chain closes,
-            // and the tags of the episodes it opens -- from the words the chain's earlier launches have written (the banks' pointers
-            // are taken here: a bank or the device-side reset's pool may have come, or been rebuilt, after the log was enabled)
-            EpisodeLogDev lg = h->eplog;
-            lg.map_cur = h->d_map_cur;
-            lg.trk_cur = h->d_trk_cur;
-            lg.scn_world = h->d_scn_world;
-            lg.scn_mark = h->d_scn_mark;
-            lg.place_serial = h->sd_ready ? h->d_place_serial : nullptr;
-            const LaunchShape gl = plan_episode_log_launch();
-            k_episode_log<<<dim3(gl.grid), dim3(gl.block), 0, st>>>(ed, lg);
-            h->launches += 1;
-        }
-        const LaunchShape g = plan_tail_launch(p, c, 1, EP_BLOCK, EP_MAX_BLOCKS);
-        (is_reset ? k_episodes<true> : k_episodes<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(ed);
-        h->launches += 1;
-    }
-    if (h->post_on) {
-        // the normalised pedestrian vectors and close_to_human (obs_post.h), last: of every local robot after a step, of the robots
-        // a reset chain covers (k_stack<true>'s cases)
-        ObsPostDev pd = h->post;
-        pd.rows = tail_rows(h, is_reset);
-        const LaunchShape g = plan_tail_launch(p, c, (size_t)pd.per_row, OBS_POST_BLOCK, OBS_POST_MAX_BLOCKS);
-        (is_reset ? k_obs_post<true> : k_obs_post<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(pd);
-        h->launches += 1;
-    }
-    if (h->norm_on) {
-        // the running normalisation (normalise.h), behind the stacks whose newest frames it reads and in front of the rollout storage
-        // that may store its output: with training on the chain's batch goes into the statistics (a reset chain has no return
-        // column), then every chain applies them to the rows it covers
-        NormDev nd = h->norm;
-        const bool rew = (h->norm_cfg.flags & IMGENV_NORM_REWARD) != 0;
-        nd.rows = tail_rows(h, is_reset);
-        nd.n_ret = !is_reset && rew ? 1 : 0;
-        nd.cols = std::max(1, nd.n_obs + nd.n_ret);
-        nd.update = h->norm_training ? 1 : 0;
-        nd.turn = h->norm_turn;
-        nd.ret_turn = h->norm_ret_turn;
-        const bool stats_move = nd.update && (!is_reset || nd.n_obs > 0);
-        if (stats_move) {
-            const LaunchShape g = plan_norm_part_launch(p, c, nd.cols);
-            (is_reset ? k_norm_part<true> : k_norm_part<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(nd);
-            h->launches += 1;
-            h->norm_turn += 1;
-        }
-        if (!is_reset || nd.n_obs > 0 || (nd.update && rew)) {  // (a reset chain of a reward-only handle in evaluation has nothing to do)
-            const LaunchShape g = plan_norm_apply_launch(p, c, nd.cols);
-            (is_reset ? k_norm_apply<true> : k_norm_apply<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(nd);
-            h->launches += 1;
-        }
-        if (nd.update && nd.n_ret) h->norm_ret_turn += 1;
-    }
-    if (h->roll_on && h->roll_begun) {
-        // the rollout storage (rollout.h), last -- it reads what k_stack and k_obs_post have just written: a step stores transition
-        // n and the observation it led to in slot n + 1 (rollout_room has refused a step on a full ring), a reset chain moves the
-        // rows of slot n it covers into the final list and stores the new episode's first observation there
-        RolloutDev ro = h->roll;
-        ro.rows = tail_rows(h, is_reset);
-        ro.act_src = h->ep_actions;
-        ro.n = h->roll_n;
-        ro.turn = h->roll_turn;
-        const LaunchShape g = plan_rollout_launch(p, c, ro.chunks_per_row);
-        (is_reset ? k_rollout<true> : k_rollout<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(ro);
-        h->launches += 1;
-        if (is_reset)
-            h->roll_turn += 1;
-        else
-            h->roll_n += 1;
-    }
-    HIPCHK(hipGetLastError());
-    h->chain_open = false;
+    if (rasters && !k.moved) RTRY(launch_rasters(h, st, is_reset, false, false));
+    RTRY(launch_compose_views(h, st, k));
+    h->step.early = false;
+    if (k.w.join2) HIPCHK(hipStreamWaitEvent(st, h->ev_join2, 0));  // 7. the caller's stream ends the chain behind both side streams
+    h->launches += CHAIN_FIXED_LAUNCHES;
+    launch_tails(h, st, k);
+    HIPCHK(hipGetLastError());  // 9. finish and seal
+    h->step.chain_open = false;
     h->obs_exists = true;
     h->chain_seq += 1;
     return outputs_seal(h, st);
@@ -2243,12 +2206,7 @@ static int reset_checks(imgenv* h, int n, const imgenv_reset_batch* b, int peds_
                     FAIL(IMGENV_EINVAL, "reset batch %d, ped %d: bad trajectory length %d", q, j, b[q].ped_traj_len[j]);
         }
     }
-    if (h->obs_forked) {
-        // a step that was begun and never ended (the caller's exchange failed in between): its k_obs is in flight on a side
-        // stream and will still arrive at the tails' hand-over words; wait for it, the reset's first chain then clears them
-        if (h->side2) HIPCHK(hipStreamSynchronize(h->side2));
-        h->obs_forked = false;
-    }
+    RTRY(step_recover(h));
     HIPCHK(hipSetDevice(h->cfg.device));
     if (int rc = check_device_flags(h)) {  // report what the abandoned episode raised, then start clean
         for (int q = 0; q < 8; q++) h->err_host[q] = 0;
@@ -2922,10 +2880,7 @@ extern "C" int imgenv_world_scenarios(imgenv_t* h, int32_t* ids, void* stream) {
 // the pedestrians' arrays
 static int launch_sfm(imgenv* h, hipStream_t s, const SfmDev* out, int publish) {
     DevWorld d = h->d;
-    if (out) {
-        d.sfm.p_out = out->p; d.sfm.v_out = out->v; d.sfm.dq_out = out->dq; d.sfm.dest_out = out->dest; d.sfm.last_out = out->last;
-        d.sfm.nodes_out = out->nodes; d.sfm.n_nodes_out = out->n_nodes; d.sfm.treehash_out = out->treehash;
-    }
+    if (out) sfm_write_into(d.sfm, *out);
     const int n_sfm = d.sfm.n, n_pairs = n_sfm * n_sfm;  // (of one world's crowd; a workgroup per world)
     const unsigned nw = (unsigned)h->W, pb = (unsigned)((n_pairs + SFM_MAX_AGENTS - 1) / SFM_MAX_AGENTS);
     if (n_pairs <= 4096) {  // small crowd: one launch
@@ -2945,148 +2900,138 @@ static int launch_sfm(imgenv* h, hipStream_t s, const SfmDev* out, int publish) 
 // Something is about to write the live crowd on stream st (a reset, a step in place, a device-side auto-reset): what was computed
 // ahead is dropped, and the writer waits for the launch that may still be reading the live set
 static int sfm_ahead_drop(imgenv* h, hipStream_t st) {
-    if (h->sfm_ahead_valid) HIPCHK(hipStreamWaitEvent(st, h->ev_sfm, 0));
-    h->sfm_ahead_valid = false;
-    h->sfm_steps_since_reset = 0;
+    if (h->crowd.valid) HIPCHK(hipStreamWaitEvent(st, h->crowd.ev, 0));
+    h->crowd.valid = false;
+    h->crowd.steps_since_reset = 0;
     return 0;
 }
 
 // the social-force crowd's step AHEAD, on its own stream (see imgenv_step_begin): queued once the step's own first kernels are out
 static int sfm_launch_ahead(imgenv* h) {
-    if (h->sfm_ahead_wait < 0) return 0;
-    HIPCHK(hipStreamWaitEvent(h->sfm_stream, h->ev_sfm_in[h->sfm_ahead_wait], 0));
-    h->sfm_ahead_wait = -1;
-    if (int rc = launch_sfm(h, h->sfm_stream, &h->sfm_other, 0)) return rc;
-    HIPCHK(hipEventRecord(h->ev_sfm, h->sfm_stream));
-    h->sfm_ahead_valid = true;
+    if (h->crowd.wait < 0) return 0;
+    HIPCHK(hipStreamWaitEvent(h->crowd.stream, h->crowd.ev_in[h->crowd.wait], 0));
+    h->crowd.wait = -1;
+    if (int rc = launch_sfm(h, h->crowd.stream, &h->crowd.other, 0)) return rc;
+    HIPCHK(hipEventRecord(h->crowd.ev, h->crowd.stream));
+    h->crowd.valid = true;
     return 0;
 }
 
-extern "C" int imgenv_step_begin(imgenv_t* h, const float* actions, void* stream) {
+// 1. Entry: what a step may not follow, the device's flags, the output guard; then the step's hand-over starts
+static int step_entry(imgenv* h, const float* actions, hipStream_t st) {
     if (!h || !actions) FAIL(IMGENV_EINVAL, "null argument");
     if (!h->has_reset) FAIL(IMGENV_ESTATE, "step before reset");
-    if (h->obs_forked) FAIL(IMGENV_ESTATE, "imgenv_step_begin twice without imgenv_step_end (reset the handle to recover from an aborted step)");
-    if (int rc = rollout_room(h)) return rc;
-    if (int rc = check_device_flags(h)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = outputs_verify(h, st)) return rc;
+    if (h->step.obs_forked) FAIL(IMGENV_ESTATE, "imgenv_step_begin twice without imgenv_step_end (reset the handle to recover from an aborted step)");
+    RTRY(rollout_room(h));
+    RTRY(check_device_flags(h));
+    RTRY(outputs_verify(h, st));
     // (from here on the step's own kernels write output arrays; the chain's end seals them again.  A step that is begun and never
     // ended -- the caller's exchange failed -- must not read as "the caller wrote into imgenv_out" at the reset that recovers it)
     h->guard_sealed = false;
-    h->ep_actions = actions;
-    DevWorld& d = h->d;
+    h->step.actions = actions;
     h->launches = h->decode_launches;  // (imgenv_actions_decode in front of this step)
     h->decode_launches = 0;
-    // _step_ped_normal (img_env.cpp:304-359): the ORCA solve for this step ran on the side stream during the previous
-    // step's views and was joined at the end of that step; its velocities are applied by k_integrate's pedestrian blocks
-    if (h->cfg.ped_scene_type == IMGENV_SCENE_PEDSIM && h->d.sfm.n > 0) {  // PedScene::step + write-back (img_env.cpp:343-358)
-        if (h->sfm_ahead) {
-            // a crowd that ignores the robots: this step's state was computed during the last step (launch_sfm below) -- swap the
-            // two sets and publish -- or, right behind a reset, is computed now, in place; then the NEXT step's goes out on its stream
-            // Ordering against the caller's stream.  The launch ahead (below) reads the live set and WRITES the other one -- the set
-            // that was live a step ago, which THAT step's k_sfm_publish (or in-place step) touched on the caller's stream.  Nothing else
-            // orders the crowd's stream behind the caller's: a host that queues steps faster than the device drains them (an
-            // asynchronous trainer, bench.py's timed loop) would let the crowd run several steps ahead and overwrite a set before it has
-            // been published (rounds 3-5 did).  So every step leaves an event behind its access to the sets on the caller's stream,
-            // by step parity, and the launch ahead waits for the LAST step's -- this step's publish only reads the live set, as the
-            // launch ahead does, so the crowd may run up to one step ahead of the caller's stream -- or for this step's own when it
-            // wrote the live set in place.
-            const int cur = h->sfm_par;
-            h->sfm_par ^= 1;
-            bool in_place = false;
-            if (h->sfm_ahead_valid) {
-                SfmDev& a = h->d.sfm;
-                SfmDev& b = h->sfm_other;
-                std::swap(a.p, b.p); std::swap(a.v, b.v); std::swap(a.dq, b.dq); std::swap(a.dest, b.dest); std::swap(a.last, b.last);
-                std::swap(a.nodes, b.nodes); std::swap(a.n_nodes, b.n_nodes); std::swap(a.treehash, b.treehash);
-                a.p_out = a.p; a.v_out = a.v; a.dq_out = a.dq; a.dest_out = a.dest; a.last_out = a.last;
-                a.nodes_out = a.nodes; a.n_nodes_out = a.n_nodes; a.treehash_out = a.treehash;
-                HIPCHK(hipStreamWaitEvent(st, h->ev_sfm, 0));
-                // (the event rides on the kernel's dispatch packet: a hipEventRecord behind it is a packet of its own, ~6 us of the caller's stream)
-                hipExtLaunchKernelGGL(k_sfm_publish, dim3((unsigned)h->W), dim3(SFM_MAX_AGENTS), 0, st, nullptr, h->ev_sfm_in[cur], 0, d);
-                h->launches += 1;
-            } else {
-                if (int rc = launch_sfm(h, st, nullptr, 1)) return rc;
-                HIPCHK(hipEventRecord(h->ev_sfm_in[cur], st));
-                in_place = true;
-            }
-            // (not in the first step behind a reset: a handle whose worlds are reset every other step -- many small worlds with
-            // their own time limits -- would compute ahead what the next reset drops, and make that reset wait for it)
-            // (queued at the END of this call, behind the step's own first launches: its five host calls in front of the move were
-            // ~25 us in which the caller's stream sat idle -- sfm_launch_ahead)
-            h->sfm_ahead_wait = h->sfm_steps_since_reset >= 1 ? (in_place ? cur : cur ^ 1) : -1;
-            h->sfm_steps_since_reset += 1;
-        } else {
-            if (int rc = sfm_ahead_drop(h, st)) return rc;
-            if (int rc = launch_sfm(h, st, nullptr, 1)) return rc;
-        }
+    return 0;
+}
+
+// 2. PedScene::step + write-back (img_env.cpp:343-358) of a social-force crowd, as plan_crowd_step says (launch_plan.h has the
+// ordering against the caller's stream).  A crowd that ignores the robots: this step's state was computed during the last step
+// (sfm_launch_ahead) -- swap the two sets and publish -- or, right behind a reset, is computed now, in place; then the NEXT step's
+// goes out on its stream, at the END of imgenv_step_begin, behind the step's own first launches (its five host calls in front of
+// the move were ~25 us in which the caller's stream sat idle).
+static int step_crowd(imgenv* h, hipStream_t st) {
+    imgenv::CrowdAhead& c = h->crowd;
+    if (!c.can) {  // a crowd that cannot run ahead steps in place and leaves nothing
+        RTRY(sfm_ahead_drop(h, st));
+        return launch_sfm(h, st, nullptr, 1);
     }
-    if (d.beep_on) {  // beep lottery + ERVO's evacuation term on top of the velocities the solve left (img_env.cpp:323-343)
+    const CrowdStep k = plan_crowd_step(c.can, c.valid, c.steps_since_reset, c.par);
+    c.par = k.par_next;
+    if (k.swap) {
+        sfm_swap_sets(h->d.sfm, c.other);
+        sfm_write_into(h->d.sfm, h->d.sfm);
+        HIPCHK(hipStreamWaitEvent(st, c.ev, 0));
+        // (the event rides on the kernel's dispatch packet: a hipEventRecord behind it is a packet of its own, ~6 us of the caller's stream)
+        hipExtLaunchKernelGGL(k_sfm_publish, dim3((unsigned)h->W), dim3(SFM_MAX_AGENTS), 0, st, nullptr, c.ev_in[k.leaves], 0, h->d);
+        h->launches += 1;
+    } else {
+        RTRY(launch_sfm(h, st, nullptr, 1));
+        HIPCHK(hipEventRecord(c.ev_in[k.leaves], st));
+    }
+    c.wait = k.ahead_waits;
+    c.steps_since_reset += 1;
+    return 0;
+}
+
+// 4. _step_robot (img_env.cpp:388-410) in a launch of its own: k_integrate, the fork of the side streams right behind it on its
+// dispatch packet, and in an early step the gate's number -- or its serial form where the sub-steps do not fit the LDS table
+static int step_move(imgenv* h, const float* actions, hipStream_t st, const StepPlan& sp) {
+    DevWorld& d = h->d;
+    h->step.fork_on_move = sp.fork_on_move;
+    if (!sp.serial_move)
+        TIMED(h, IMGENV_K_INTEGRATE, st, (hipExtLaunchKernelGGL(k_integrate, dim3(sp.move.grid), dim3(sp.move.block), 0, st, nullptr,
+                                                               sp.fork_on_move ? h->ev_fork : nullptr, 0, d, actions, sp.nb_robot, h->n_sub, h->elapsed,
+                                                               sp.early_step ? h->step.gate_seq : 0u)));
+    else
+        TIMED(h, IMGENV_K_INTEGRATE, st, (k_integrate_serial<<<dim3(sp.move.grid), dim3(sp.move.block), 0, st>>>(d, actions, sp.nb_robot, h->elapsed)));
+    return 0;
+}
+
+// 5. k_obs beside the move instead of behind it (world.h): it needs nothing of this step but the actions.  It waits behind a gate
+// that opens when the caller's stream reaches the move (k_gate): everything queued there in front of the step is then complete
+// -- whoever writes the actions, whoever still reads the last step's outputs, the last chain's views.  Queued BEHIND the move --
+// a gate must follow the kernel that opens it in queue order; what the caller's stream forks behind the move is the solve alone.
+static int early_obs(imgenv* h, const float* actions, hipStream_t st) {
+    DevWorld& d = h->d;
+    h->step.chain_open = true;
+    if (!h->step.fork_on_move) HIPCHK(hipEventRecord(h->ev_fork, st));
+    h->step.fork_on_move = false;
+    k_gate<<<dim3(1), dim3(WAVE), 0, h->side2>>>(d.sync, h->step.gate_seq, d.err);
+    h->launches += 1;
+    d.obs_early = h->NA == 0 ? 2 : 1;  // (2: the pedestrians are live -- a social-force crowd a step ahead: see imgenv_create)
+    d.obs_actions = actions; d.obs_n_sub = h->n_sub;
+    d.ped_snap_in = h->ped_snap[plan_snap_in(h->step.orca_seq)];
+    d.rec_snap_in = h->rec_snap[plan_snap_in(h->step.view_seq)];
+    const int rc = launch_obs_kernel(h, h->side2);
+    d.obs_early = 0;
+    if (rc) return rc;
+    h->step.obs_forked = true;
+    h->step.early = true;
+    return 0;
+}
+
+// The step up to the exchange: the crowd, the beep, the move in its three shapes (plan_step), the observation.  _step_ped_normal
+// (img_env.cpp:304-359): the ORCA solve for this step ran on the side stream during the previous step's views and was joined at
+// the end of that step; its velocities are applied by the move's pedestrian blocks.
+extern "C" int imgenv_step_begin(imgenv_t* h, const float* actions, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    RTRY(step_entry(h, actions, st));
+    DevWorld& d = h->d;
+    if (h->cfg.ped_scene_type == IMGENV_SCENE_PEDSIM && d.sfm.n > 0) RTRY(step_crowd(h, st));
+    if (d.beep_on) {  // 3. beep lottery + ERVO's evacuation term on top of the velocities the solve left (img_env.cpp:323-343)
         k_beep<<<dim3(h->W), dim3(BEEP_T), 0, st>>>(d, actions);
         k_evac<<<dim3(h->P), dim3(WAVE), 0, st>>>(d);
         h->launches += 2;
     }
-    // _step_robot (img_env.cpp:388-410): the move in a launch of its own, or left to the raster launch; k_obs behind it or, in an
-    // early-observation step (world.h), with it on its side stream, behind a gate that opens when the caller's stream reaches the move
     const StepPlan sp = plan_step(h->plan, chain_facts(h, 0));
-    const bool early_step = sp.early_step, live_peds = h->NA == 0;  // (a social-force crowd a step ahead: see imgenv_create)
-    if (early_step) h->gate_seq += 1;
-    // k_obs beside the move instead of behind it (world.h): it needs nothing of this step but the actions.  It waits behind a gate
-    // that opens when the caller's stream reaches the move (k_gate): everything queued there in front of the step is then complete
-    // -- whoever writes the actions, whoever still reads the last step's outputs, the last chain's views.  Queued BEHIND the move --
-    // a gate must follow the kernel that opens it in queue order; what the caller's stream forks behind the move is the solve alone.
-    auto early_obs = [&]() -> int {
-        h->chain_open = true;
-        if (!h->fork_on_move) HIPCHK(hipEventRecord(h->ev_fork, st));
-        h->fork_on_move = false;
-        k_gate<<<dim3(1), dim3(WAVE), 0, h->side2>>>(d.sync, h->gate_seq, d.err);
-        h->launches += 1;
-        d.obs_early = live_peds ? 2 : 1;
-        d.obs_actions = actions;
-        d.obs_n_sub = h->n_sub;
-        d.ped_snap_in = h->ped_snap[(h->orca_seq - 1) & 1];
-        d.rec_snap_in = h->rec_snap[(h->view_seq - 1) & 1];
-        const int rc = launch_obs_kernel(h, h->side2);
-        d.obs_early = 0;
-        if (rc) return rc;
-        h->obs_forked = true;
-        h->early_step = true;
-        return 0;
-    };
-    if (sp.sum_shard_now) {  // k_move_raster over the shard's own robots and the pedestrians, now (in front of the exchange); the observation behind it
-        h->move_actions = actions;
-        if (int rc = launch_rasters(h, st, 0, true, true, true)) return rc;
-        h->launches += 1;
-        set_tail_fields(h, 0, h->elapsed + 1);
-        if (h->P > 0)
-            if (int rc = launch_obs(h, st)) return rc;
-        HIPCHK(hipGetLastError());
+    if (sp.early_step) h->step.gate_seq += 1;
+    if (sp.sum_shard_now) {  // k_move_raster over the shard's own robots and the pedestrians, now (in front of the exchange)
+        RTRY(launch_rasters(h, st, 0, true, true, true));
+    } else if (sp.fuse_move) {  // k_move_raster, launched by launch_views (the fork of the side stream with it)
+        h->step.move_pending = true;
         return sfm_launch_ahead(h);
+    } else {
+        RTRY(step_move(h, actions, st, sp));
     }
-    if (sp.fuse_move) {  // k_move_raster, launched by launch_views (the fork of the side stream with it)
-        h->move_pending = true;
-        h->move_actions = actions;
-        return sfm_launch_ahead(h);
-    }
-    // (the fork of the side streams follows right behind the move, on its dispatch packet)
-    h->fork_on_move = sp.fork_on_move;
-    if (!sp.serial_move)
-        TIMED(h, IMGENV_K_INTEGRATE, st, (hipExtLaunchKernelGGL(k_integrate, dim3(sp.move.grid), dim3(sp.move.block), 0, st, nullptr,
-                                                               sp.fork_on_move ? h->ev_fork : nullptr, 0, d, actions, sp.nb_robot, h->n_sub, h->elapsed,
-                                                               early_step ? h->gate_seq : 0u)));
-    else
-        TIMED(h, IMGENV_K_INTEGRATE, st, (k_integrate_serial<<<dim3(sp.move.grid), dim3(sp.move.block), 0, st>>>(d, actions, sp.nb_robot, h->elapsed)));
     h->launches += 1;
     set_tail_fields(h, 0, h->elapsed + 1);  // imgenv_step_end counts the step; k_obs goes out before that
-    if (early_step) {
-        if (int rc = early_obs()) return rc;
-    } else if (h->P > 0) {
-        if (int rc = launch_obs(h, st)) return rc;
-    }
+    if (sp.early_step)
+        RTRY(early_obs(h, actions, st));
+    else if (h->P > 0)
+        RTRY(launch_obs(h, st));
     // a robot shard in SUM mode (world.h: sum_shard) draws its own robots -- and the pedestrians -- NOW, in front of the exchange:
     // their records then carry the cells they cover to the other ranks
-    if (d.sum_shard)
-        if (int rc = launch_rasters(h, st, 0, false, true, true)) return rc;
+    if (d.sum_shard && !sp.sum_shard_now) RTRY(launch_rasters(h, st, 0, false, true, true));
     HIPCHK(hipGetLastError());
     return sfm_launch_ahead(h);
 }
@@ -3107,9 +3052,9 @@ extern "C" int imgenv_step(imgenv_t* h, const float* actions, void* stream) { re
 
 extern "C" int imgenv_step_flags(imgenv_t* h, const float* actions, uint32_t flags, void* stream) {
     (void)flags;  // (IMGENV_STEP_ACTIONS_READY: accepted, and since round 6 without effect -- include/imgenv.h)
-    if (h) h->in_step = true;  // (begin and end in one call: the actions outlive the move whoever launches it)
+    if (h) h->step.in_step = true;  // (begin and end in one call: the actions outlive the move whoever launches it)
     const int rc_begin = imgenv_step_begin(h, actions, stream);
-    if (h) h->in_step = false;
+    if (h) h->step.in_step = false;
     if (rc_begin) return rc_begin;
     if (h->comm) {  // the one exchange of a robot-sharded world: records of all robots, in place
         const size_t count = (size_t)h->RL * IMGENV_RECORD_DOUBLES;
@@ -3506,11 +3451,11 @@ static int autoreset_device_chain(imgenv* h, const float* actions, hipStream_t s
 extern "C" int imgenv_step_autoreset_device(imgenv_t* h, const float* actions, const imgenv_spawn_cfg* cfg, uint64_t seed0, void* stream) {
     if (int rc = autoreset_checks(h, actions, cfg, "imgenv_step_autoreset_device")) return rc;
     if (!h->has_reset) FAIL(IMGENV_ESTATE, "step before reset");
-    if (h->obs_forked) FAIL(IMGENV_ESTATE, "imgenv_step_autoreset_device between imgenv_step_begin and imgenv_step_end");
+    if (h->step.obs_forked) FAIL(IMGENV_ESTATE, "imgenv_step_autoreset_device between imgenv_step_begin and imgenv_step_end");
     hipStream_t st = (hipStream_t)stream;
-    if (h->sfm_ahead) {  // kernels reset finished worlds here, crowds included, without the host knowing which: the crowd steps in place
+    if (h->crowd.can) {  // kernels reset finished worlds here, crowds included, without the host knowing which: the crowd steps in place
         if (int rc = sfm_ahead_drop(h, st)) return rc;
-        h->sfm_ahead = false;
+        h->crowd.can = false;
     }
     if (h->scn_policy != IMGENV_SCENARIOS_OFF && (cfg->n_robots != h->Rw || cfg->n_peds != h->Pw || cfg->n_obstacles != h->scn_obst))
         FAIL(IMGENV_EINVAL, "imgenv_step_autoreset_device: the spawn cfg has %d robots / %d pedestrians / %d obstacles, the scenario bank %d / %d / %d",
@@ -3753,6 +3698,16 @@ extern "C" int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgen
     return enable_done(h, o, &imgenv::stack_out, &imgenv::stack_on, out);
 }
 
+// the chain's tail (launch_tails): a step pushes every local robot's new frames, a reset chain restarts the stacks of the robots it covers
+static void tail_stack(imgenv* h, hipStream_t st, const ChainPlans& k) {
+    if (!h->stack_on || h->stack.n_fields <= 0) return;
+    StackDev sd = h->stack;
+    sd.rows = tail_rows(h, k.is_reset);
+    const LaunchShape g = plan_tail_launch(h->plan, k.c, sd.chunks_per_robot, STACK_BLOCK, STACK_MAX_BLOCKS);
+    (k.is_reset ? k_stack<true> : k_stack<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(sd);
+    h->launches += 1;
+}
+
 extern "C" int imgenv_stack_outputs(imgenv_t* h, imgenv_stack_out* out) {
     return feature_outputs(h, &imgenv::stack_on, &imgenv::stack_out, out, "imgenv_stack_enable");
 }
@@ -3796,6 +3751,28 @@ extern "C" int imgenv_episodes_enable(imgenv_t* h, const imgenv_episodes_cfg* c,
     o.last_episode = e.i + EPI_LAST_EPISODE * RL; o.last_return = e.f + EPF_LAST_RETURN * RL;
     o.open_f64 = e.f; o.open_steps = e.i + EPI_TMP_STEPS * RL; o.open_len = e.i + EPI_LEN * RL; o.open = e.i + EPI_OPEN * RL;
     return enable_done(h, o, &imgenv::ep_out, &imgenv::ep_on, out);
+}
+
+// the chain's tail (launch_tails): a step's command, reward and is_clean go into every local robot's open episode, a reset chain
+// folds the episodes of the robots it covers by the last step's dones_info.  In front of that fold the episode log
+// (episode_log.h): one record per episode this chain closes, and the tags of the episodes it opens -- from the words the chain's
+// earlier launches have written (the banks' pointers are taken here: they may have come, or been rebuilt, after the log's enable)
+static void tail_episodes(imgenv* h, hipStream_t st, const ChainPlans& k) {
+    if (!h->ep_on) return;
+    EpisodesDev ed = h->ep;
+    ed.actions = h->step.actions;
+    ed.rows = tail_rows(h, k.is_reset);
+    if (k.is_reset && h->eplog_on) {
+        EpisodeLogDev lg = h->eplog;
+        lg.map_cur = h->d_map_cur; lg.trk_cur = h->d_trk_cur; lg.scn_world = h->d_scn_world; lg.scn_mark = h->d_scn_mark;
+        lg.place_serial = h->sd_ready ? h->d_place_serial : nullptr;
+        const LaunchShape gl = plan_episode_log_launch();
+        k_episode_log<<<dim3(gl.grid), dim3(gl.block), 0, st>>>(ed, lg);
+        h->launches += 1;
+    }
+    const LaunchShape g = plan_tail_launch(h->plan, k.c, 1, EP_BLOCK, EP_MAX_BLOCKS);
+    (k.is_reset ? k_episodes<true> : k_episodes<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(ed);
+    h->launches += 1;
 }
 
 extern "C" int imgenv_episodes_outputs(imgenv_t* h, imgenv_episodes_out* out) {
@@ -4162,6 +4139,17 @@ extern "C" int imgenv_obs_post_enable(imgenv_t* h, const imgenv_obs_post_cfg* c,
     return enable_done(h, o, &imgenv::post_out, &imgenv::post_on, out);
 }
 
+// the chain's tail (launch_tails): the normalised pedestrian vectors and close_to_human of every local robot after a step, of the
+// robots a reset chain covers
+static void tail_obs_post(imgenv* h, hipStream_t st, const ChainPlans& k) {
+    if (!h->post_on) return;
+    ObsPostDev pd = h->post;
+    pd.rows = tail_rows(h, k.is_reset);
+    const LaunchShape g = plan_tail_launch(h->plan, k.c, (size_t)pd.per_row, OBS_POST_BLOCK, OBS_POST_MAX_BLOCKS);
+    (k.is_reset ? k_obs_post<true> : k_obs_post<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(pd);
+    h->launches += 1;
+}
+
 extern "C" int imgenv_obs_post_outputs(imgenv_t* h, imgenv_obs_post_out* out) {
     return feature_outputs(h, &imgenv::post_on, &imgenv::post_out, out, "imgenv_obs_post_enable");
 }
@@ -4231,6 +4219,28 @@ extern "C" int imgenv_normalise_enable(imgenv_t* h, const imgenv_normalise_cfg* 
     o.returns = n.returns;
     o.training = 1;
     return enable_done(h, o, &imgenv::norm_out, &imgenv::norm_on, out);
+}
+
+// the chain's tail (launch_tails): what plan_norm_chain says of this chain -- the batch into the statistics, the statistics onto the rows
+static void tail_normalise(imgenv* h, hipStream_t st, const ChainPlans& k) {
+    if (!h->norm_on) return;
+    NormDev nd = h->norm;
+    const NormChain n = plan_norm_chain(h->norm_training, (h->norm_cfg.flags & IMGENV_NORM_REWARD) != 0, nd.n_obs, k.is_reset != 0);
+    nd.rows = tail_rows(h, k.is_reset);
+    nd.n_ret = n.n_ret; nd.cols = n.cols; nd.update = n.update;
+    nd.turn = h->norm_turn; nd.ret_turn = h->norm_ret_turn;
+    if (n.part) {
+        const LaunchShape g = plan_norm_part_launch(h->plan, k.c, nd.cols);
+        (k.is_reset ? k_norm_part<true> : k_norm_part<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(nd);
+        h->launches += 1;
+    }
+    if (n.apply) {
+        const LaunchShape g = plan_norm_apply_launch(h->plan, k.c, nd.cols);
+        (k.is_reset ? k_norm_apply<true> : k_norm_apply<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(nd);
+        h->launches += 1;
+    }
+    if (n.turn) h->norm_turn += 1;
+    if (n.ret_turn) h->norm_ret_turn += 1;
 }
 
 extern "C" int imgenv_normalise_outputs(imgenv_t* h, imgenv_normalise_out* out) {
@@ -4520,6 +4530,25 @@ extern "C" int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* c, i
     return enable_done(h, o, &imgenv::roll_out, &imgenv::roll_on, out);
 }
 
+// the chain's tail (launch_tails), once imgenv_rollout_begin has been called: a step stores transition n and the observation it
+// led to in slot n + 1 (rollout_room has refused a step on a full ring), a reset chain moves the rows of slot n it covers into the
+// final list and stores the new episode's first observation there
+static void tail_rollout(imgenv* h, hipStream_t st, const ChainPlans& k) {
+    if (!h->roll_on || !h->roll_begun) return;
+    RolloutDev ro = h->roll;
+    ro.rows = tail_rows(h, k.is_reset);
+    ro.act_src = h->step.actions;
+    ro.n = h->roll_n;
+    ro.turn = h->roll_turn;
+    const LaunchShape g = plan_rollout_launch(h->plan, k.c, ro.chunks_per_row);
+    (k.is_reset ? k_rollout<true> : k_rollout<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(ro);
+    h->launches += 1;
+    if (k.is_reset)
+        h->roll_turn += 1;
+    else
+        h->roll_n += 1;
+}
+
 extern "C" int imgenv_rollout_outputs(imgenv_t* h, imgenv_rollout_out* out) {
     if (int rc = feature_outputs(h, &imgenv::roll_on, &imgenv::roll_out, out, "imgenv_rollout_enable")) return rc;
     out->n = h->roll_begun ? h->roll_n : -1;
@@ -4531,7 +4560,7 @@ extern "C" int imgenv_rollout_begin(imgenv_t* h, void* stream) {
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
     if (!h->roll_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_enable was not called");
     if (!h->obs_exists) FAIL(IMGENV_ESTATE, "imgenv_rollout_begin before the first reset: there is no observation yet");
-    if (h->obs_forked) FAIL(IMGENV_ESTATE, "imgenv_rollout_begin between imgenv_step_begin and imgenv_step_end");
+    if (h->step.obs_forked) FAIL(IMGENV_ESTATE, "imgenv_rollout_begin between imgenv_step_begin and imgenv_step_end");
     HIPCHK(hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;
     const size_t RL = (size_t)h->RL;
@@ -4788,7 +4817,7 @@ extern "C" int imgenv_cv_resize_u8(int kind, const uint8_t* src, int32_t sh, int
 extern "C" int imgenv_step_launches(imgenv_t* h) { return h ? h->launches : 0; }
 extern "C" int imgenv_layer_mode(imgenv_t* h) {
     if (!h) return -1;
-    return h->plan.layer | (h->d.sum_shard ? 4 : 0) | (h->early && h->gates_work ? 8 : 0) | (h->sfm_ahead ? 16 : 0);
+    return h->plan.layer | (h->d.sum_shard ? 4 : 0) | (h->early && h->gates_work ? 8 : 0) | (h->crowd.can ? 16 : 0);
 }
 
 // debug: read (and clear) the per-phase cycle counters of IMGENV_PHASE_PROFILE builds

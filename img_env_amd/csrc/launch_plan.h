@@ -2,7 +2,9 @@
 // and LDS size, decided from plain facts about the handle (fixed at imgenv_create) and about the chain of launches in hand.
 // Nothing of HIP in here: plain C++17, compiled by g++ for tests/host/launch_plan_check.cpp, which pins every threshold
 // below with its two neighbours.  The launch functions of imgenv_hip.hip build the facts, ask for a plan and issue the
-// launches in stream order; what is launched at what shape is decided here, the ordering (forks, joins, gates) there.
+// launches in stream order; what is launched at what shape is decided here, and so are the ordering's decisions (which stream,
+// which event, which buffer takes the turn: "ordering" below, pinned by tests/host/step_chain_check.cpp) -- the host code only
+// executes them.
 //
 // Also the one home of the constants that both the kernels and these rules read, and of `pick`, the step from a plan's
 // runtime selector to a template instantiation.
@@ -396,6 +398,97 @@ inline SidePlan plan_side(const PlanHandle& h, const PlanChain& c) {
 // were measured in round 6 and LOSE: cfg-5 277 -> 325 us per step, 321 with two, 406 with eight: the step is bound by the
 // instructions it issues, k_obs beside k_view, not by this kernel's occupancy.  docs/HISTORY.md)
 inline LaunchShape plan_obs(const PlanHandle& h, const PlanChain& c) { return {(unsigned)c.act_nl, WAVE, h.lds_obs}; }
+
+// ---------------------------------------------------------------------------------------- ordering (launch_views, imgenv_step_begin)
+// The side wiring of a chain with pedestrians: one fork and one join per step on the caller's stream (every event operation costs
+// it a ~6 us dependency bubble).  The observation's stream finally waits for the solve, so its join event covers both.
+enum { ON_CALLER = 0, ON_SIDE = 1, ON_SIDE2 = 2 };      // a stream: the caller's, imgenv::side, imgenv::side2
+enum { WAIT_NONE = 0, WAIT_FORK = 1, WAIT_FORK2 = 2 };  // what a side launch waits for: nothing, ev_fork, ev_fork2
+struct SideWiring {
+    int solve_on = ON_CALLER, obs_on = ON_CALLER;  // k_side_robots + k_orca; k_obs
+    // the solve's wait: ev_fork where it has a stream of its own -- or shares the observation's and that went out with the step, in
+    // front of the move (an early step) --, ev_fork2 where it needs every rank's robots: a second fork behind the exchange ...
+    int solve_waits = WAIT_NONE;
+    bool record_fork2 = false;     // ... recorded on the caller's stream in front of the wait,
+    bool fork2_on_remote = false;  // or riding on k_remote's dispatch packet (a robot shard in SUM mode)
+    bool join = false;             // ev_join behind the solve, the observation's stream waits for it
+    bool join2 = false;            // ev_join2 behind the observation; the caller's stream waits for it behind the views
+};
+inline SideWiring plan_side_wiring(const SidePlan& s, const PlanHandle& h, bool early_step) {
+    SideWiring w;
+    w.fork2_on_remote = s.remote_only && s.side_reads_all && !h.serial;
+    if (!s.overlap) return w;
+    w.solve_on = s.one_side ? ON_SIDE2 : ON_SIDE;
+    w.obs_on = ON_SIDE2;
+    if (s.one_side)
+        w.solve_waits = early_step ? WAIT_FORK : WAIT_NONE;  // (behind k_obs in its stream otherwise)
+    else
+        w.solve_waits = h.sharded && s.side_reads_all ? WAIT_FORK2 : WAIT_FORK;
+    w.record_fork2 = w.solve_waits == WAIT_FORK2 && !s.remote_only;
+    w.join = !s.one_side;
+    w.join2 = true;
+    return w;
+}
+
+// The snapshots the next step's early k_obs reads (world.h: ped_snap behind k_orca, rec_snap behind k_view).  A launch over every
+// world writes one buffer and the next one the other; a launch over a world list -- a reset chain, nothing else is in flight --
+// writes both and does not take a turn.  -1: no buffer.  An early step reads what the last turn wrote.
+struct SnapTurn {
+    int out = -1, out2 = -1;
+    bool advance = false;
+};
+inline SnapTurn plan_snap_turn(unsigned seq, bool early, bool listed) {
+    return {early ? (int)(seq & 1) : -1, early && listed ? (int)((seq + 1) & 1) : -1, !listed};
+}
+inline int plan_snap_in(unsigned seq) { return (int)((seq - 1) & 1); }
+
+// The running normalisation of a chain (normalise.h): with training on the chain's batch goes into the statistics -- a reset
+// chain has no return column -- then every chain applies them to the rows it covers (a reset chain of a reward-only handle in
+// evaluation has nothing to do).
+struct NormChain {
+    int n_ret = 0, cols = 1, update = 0;  // NormDev's fields of this launch
+    bool part = false, apply = false;     // k_norm_part, k_norm_apply
+    bool turn = false, ret_turn = false;  // norm_turn / norm_ret_turn advance
+};
+inline NormChain plan_norm_chain(bool training, bool reward, int n_obs, bool is_reset) {
+    NormChain n;
+    n.n_ret = !is_reset && reward ? 1 : 0;
+    n.cols = std::max(1, n_obs + n.n_ret);
+    n.update = training ? 1 : 0;
+    n.part = n.turn = training && (!is_reset || n_obs > 0);
+    n.apply = !is_reset || n_obs > 0 || (training && reward);
+    n.ret_turn = training && n.n_ret;
+    return n;
+}
+
+// A step of the social-force crowd (sfm.h).  A crowd that runs a step ahead (imgenv_hip.hip: CrowdAhead, step_crowd): this step's
+// state is in the other set -- swap the sets and publish -- or, behind a reset, is computed now, in place.
+// Ordering against the caller's stream.  The launch ahead reads the live set and WRITES the other one -- the set that was live a
+// step ago, which THAT step's k_sfm_publish (or in-place step) touched on the caller's stream.  Nothing else orders the crowd's
+// stream behind the caller's: a host that queues steps faster than the device drains them (an asynchronous trainer, bench.py's
+// timed loop) would let the crowd run several steps ahead and overwrite a set before it has been published (rounds 3-5 did).  So
+// every step leaves an event behind its access to the sets on the caller's stream, by step parity (ev_in[leaves]), and the launch
+// ahead waits for the LAST step's -- this step's publish only reads the live set, as the launch ahead does, so the crowd may run
+// up to one step ahead of the caller's stream -- or for this step's own when it wrote the live set in place.
+// No launch ahead in the first step behind a reset: a handle whose worlds are reset every other step -- many small worlds with
+// their own time limits -- would compute ahead what the next reset drops, and make that reset wait for it.
+// A crowd that cannot run ahead steps in place and leaves nothing.
+struct CrowdStep {
+    bool swap = false;     // swap the sets and k_sfm_publish; otherwise k_sfm in place
+    int leaves = -1;       // CrowdAhead::ev_in[.] recorded behind this step's access (-1: none)
+    int ahead_waits = -1;  // CrowdAhead::ev_in[.] the launch ahead waits for (-1: no launch ahead)
+    int par_next = 0;
+};
+inline CrowdStep plan_crowd_step(bool ahead, bool ahead_valid, int steps_since_reset, int par) {
+    CrowdStep k;
+    k.par_next = par;
+    if (!ahead) return k;
+    k.swap = ahead_valid;
+    k.leaves = par;
+    k.par_next = par ^ 1;
+    if (steps_since_reset >= 1) k.ahead_waits = k.swap ? par ^ 1 : par;
+    return k;
+}
 
 // ---------------------------------------------------------------------------------------- views (launch_views)
 struct ViewPlan {

@@ -76,6 +76,15 @@ struct SfmDev {  // one crowd, or W of them back to back (one per world of a mul
     SfmNode* nodes_out;
     int *n_nodes_out, *treehash_out;
 };
+// (host) the eight arrays a step writes: a step writes `to`'s set -- f's own: in place -- and two records trade their sets
+inline void sfm_write_into(SfmDev& f, const SfmDev& to) {
+    f.p_out = to.p; f.v_out = to.v; f.dq_out = to.dq; f.dest_out = to.dest; f.last_out = to.last;
+    f.nodes_out = to.nodes; f.n_nodes_out = to.n_nodes; f.treehash_out = to.treehash;
+}
+inline void sfm_swap_sets(SfmDev& a, SfmDev& b) {
+    std::swap(a.p, b.p); std::swap(a.v, b.v); std::swap(a.dq, b.dq); std::swap(a.dest, b.dest); std::swap(a.last, b.last);
+    std::swap(a.nodes, b.nodes); std::swap(a.n_nodes, b.n_nodes); std::swap(a.treehash, b.treehash);
+}
 
 #if defined(__HIPCC__)
 // crowd k of a multi-world handle: the same record with every array moved on to its slice

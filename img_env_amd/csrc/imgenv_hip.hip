@@ -23,6 +23,7 @@
 #include "launch_plan.h"
 #include "out_fields.h"
 #include "create_plan.h"
+#include "reset_plan.h"
 #include "obs_fields.h"
 #include "kernels.h"
 #include "world.h"
@@ -89,22 +90,45 @@ struct imgenv {
     int cap_obst = 0, cap_nodes = 0;
     double* d_traj = nullptr;
     double* d_traj_v = nullptr;  // dataset scene
-    // the robots / pedestrians of the reset being staged, in list order, in page-locked memory the reset kernel reads
-    double *pin_rob3 = nullptr, *pin_ped3 = nullptr;
-    void* pin_rr = nullptr;
-    int* pin_list = nullptr;
-    // pinned host staging of imgenv_reset: copies are truly asynchronous and reset never waits for the stream
+    // IMGENV_TRACE_RESET: where the host's time goes inside a reset entry point, by phase, reported every 200 calls of this handle
+    struct ResetTrace {
+        double acc[4] = {0, 0, 0, 0};
+        long calls = 0, worlds = 0;
+        static bool on() {
+            static const bool set = getenv("IMGENV_TRACE_RESET") != nullptr;
+            return set;
+        }
+        static double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+        bool add(const double* us, int phases, int n_worlds) {  // a call's microseconds by phase; true: time to report
+            for (int q = 0; q < phases; q++) acc[q] += us[q];
+            worlds += n_worlds;
+            return ++calls % 200 == 0;
+        }
+    };
+    // The host-side reset in flight (reset_all / reset_worlds: prepare, refuse, commit -- DESIGN.md §8; its device-free half is
+    // reset_plan.h).  Everything a reset uploads goes through page-locked chunks and reaches the device in ONE launch; nothing here
+    // means anything between two resets except the chunks, the vectors' capacity and the trace.  Per member: who sets it / who
+    // clears it / what it means while set.
     struct Chunk { unsigned char* p; size_t cap, used; };
     // STAGE_GENS generations of chunks, used round-robin: a reset only ever waits for the reset STAGE_GENS calls back (the
     // host may run several steps ahead of the device; waiting for the previous reset would drain that queue every time)
     static constexpr int STAGE_GENS = 4;
-    std::vector<Chunk> stage_gen[STAGE_GENS];
-    hipEvent_t ev_gen[STAGE_GENS] = {nullptr, nullptr, nullptr, nullptr};
-    bool gen_pending[STAGE_GENS] = {false, false, false, false};
-    int gen = 0;
-    struct StageSegHost { void* dst; const void* src; size_t bytes; };
-    std::vector<StageSegHost> segs;  // copies queued for the next stage_flush
-    size_t seg_max = 0;
+    struct ResetStage {
+        std::vector<ResetWorld> worlds;  // reset_prepare / the next reset_prepare / what each listed world's batch brings, in list order; commit swaps the RVO sets out
+        std::vector<Chunk> chunks[STAGE_GENS];  // stage_room adds one / imgenv_destroy / page-locked memory of generation g; stage_begin empties the one it takes
+        hipEvent_t ev_gen[STAGE_GENS] = {nullptr, nullptr, nullptr, nullptr};  // stage_begin creates, stage_end records / imgenv_destroy / behind the launches that read generation g
+        bool gen_pending[STAGE_GENS] = {false, false, false, false};  // stage_end / stage_begin, having waited for ev_gen[g] / the device may still read generation g
+        int gen = 0;                  // stage_begin advances / never / the generation this reset stages into
+        std::vector<StageSeg> segs;   // stage_seg / stage_begin, reset_apply behind its launch / the copies k_reset_apply makes
+        size_t seg_max = 0;           // stage_seg / with segs / the largest of them (ResetPlan::per_seg)
+        double *rob3 = nullptr, *ped3 = nullptr;  // reset_blocks / never (they point into this generation) / robot and pedestrian rows in list order, read by k_reset_apply
+        ResetRobot* rr = nullptr;     // likewise: goals of the local robots
+        int* list = nullptr;          // likewise: the listed worlds (nullptr: every world)
+        std::vector<int> fed, fed_ids;  // stage_world_peds / reset_blocks, reset_tracks behind its launch / the bank-fed worlds of this reset and the host's draw for each (-1: the device resolves)
+        ObstInst* d_inst = nullptr;   // reset_obstacles grows it / never / device room for the obstacle instances of one reset
+        size_t cap_inst = 0;
+        ResetTrace trace;             // reset_worlds / never
+    } rs;
     uint8_t* d_static_map = nullptr;  // the map every reset starts from; with a bank (imgenv_maps_add) [n_maps][map_stride], map 0 first
     // map bank (include/imgenv.h: imgenv_maps_add; csrc/map_bank.h)
     int Hg_in = 0, Wg_in = 0;       // the size of the map as imgenv_create received it (before the load-time resize)
@@ -120,7 +144,6 @@ struct imgenv {
     int *d_trk_cur = nullptr, *d_trk_next = nullptr;  // [W] (nullptr: no bank)
     uint32_t* d_trk_count = nullptr;                  // [W]
     int tracks_policy = 0, tracks_repeat = 1;         // IMGENV_TRACKS_*
-    std::vector<int> trk_fed, trk_fed_ids;  // the worlds of the reset being staged whose batch brought no tracks, and the host's draw for each (-1: the device resolves)
     // scenario bank (include/imgenv.h: imgenv_scenarios_add; csrc/scenario_bank.h)
     int n_scn = 0, scn_obst = 0;               // episodes of the bank (0: none); obstacles of each
     std::vector<SlotAgent> scn_agents;         // [n_scn][Rw + Pw] the host copy (imgenv_reset_worlds_scenarios, checkers)
@@ -137,10 +160,6 @@ struct imgenv {
     std::vector<ScnEpoch> scn_epochs;
     unsigned long long* d_scn_starts = nullptr;  // [scn_starts_cap]
     size_t scn_starts_cap = 0;
-    struct ObstInstHost { double x, y, sh, ch, cx, cy, r; int m0, m1, n0, n1, shape, world; };
-    std::vector<ObstInstHost> oinst;  // obstacles of the reset being staged
-    void* d_oinst = nullptr;
-    size_t cap_oinst = 0;
     int* d_act_list = nullptr;
     bool big_view = false;   // the view is beyond k_view's packing, or shrunk by cv2.resize: the kernels of view_big.h
     int big_tap_chunks_dyn = 0;  // k_taps_big workgroups per robot in a step (the largest list of any class: BigClassDev::tap_chunks)
@@ -185,8 +204,6 @@ struct imgenv {
     bool sum = false;        // SUM mode of the class layer (world.h): base class + counts kept by the agents themselves, no k_compose
     bool stamp = false;      // STAMP mode of the class layer (world.h) instead of two owner layers + k_compose
     uint32_t stamp_seq = 0;  // steps so far: the stamps of a step carry tag stamp_seq % STAMP_TAGS + 1
-    std::vector<double> tmp_d1;  // scratch of stage_world
-    std::vector<int> tmp_i0;
     int* d_traj_len = nullptr;
     int traj_cap = 0;
     int elapsed = 0;
@@ -211,21 +228,22 @@ struct imgenv {
     std::unordered_map<uint64_t, std::unique_ptr<SpawnOut>> spawn_ahead;
     uint64_t spawn_ahead_cfg = 0;  // fingerprint of the spawn cfg the placements were drawn from
     int spawn_ahead_n = 8;
-    double trace_acc[4] = {0, 0, 0, 0};  // IMGENV_TRACE_RESET: host time inside imgenv_step_autoreset
-    long trace_calls = 0, trace_resets = 0;
-    // device-side auto-reset (csrc/spawn_device.h): pool of placements drawn ahead on a side stream
-    bool sd_ready = false, dev_reset_used = false;
-    int fill_due = 0;  // calls until the placement pool is refilled again (SPAWN_FILL_PERIOD)
-    bool fill_pending = false;  // ev_fill has been recorded behind a k_spawn_fill that nothing has waited for yet
-    bool wobst_all = false;  // the per-world RVO table has to be uploaded as a whole (its slices moved)
+    ResetTrace trace_autoreset;  // imgenv_step_autoreset / never
+    // Device-side auto-reset (csrc/spawn_device.h): a pool of placements drawn ahead on a side stream.  Per member: who sets it /
+    // who clears it / what it means while set.
+    struct DevReset {
+        bool ready = false;         // spawn_device_setup / the same, while another spawn cfg rebuilds the pool / `pool` is built and its first fill queued
+        bool used = false;          // imgenv_step_autoreset_device / reset_all / kernels have reset worlds: h->rvos and the host's wobst no longer say what the device holds
+        int fill_due = 0;           // autoreset_device_chain (SPAWN_FILL_PERIOD), counting down / set-up, refresh, imgenv_scenarios_policy: 0 / calls until the pool is refilled
+        bool fill_pending = false;  // launch_pool_fill / autoreset_device_chain, having made the stream wait / ev_fill is behind a fill nothing has waited for yet
+        int act_hint = 0;           // imgenv_step_autoreset_device / never / robots the reset chain is expected to cover (picks the small-launch kernel variants)
+        uint64_t fp = 0;            // imgenv_step_autoreset_device / never / fingerprint of the spawn cfg the pool was built from
+        hipStream_t side3 = nullptr;  // spawn_device_setup / imgenv_destroy / the fills' stream
+        hipEvent_t ev_fill = nullptr, ev_consumed = nullptr;  // likewise / behind a fill; behind the chain that consumed placements
+        SpawnDev pool = {};         // spawn_device_setup builds, spawn_dev_refresh re-aims / never / what every kernel of the chain gets by value (valid while ready)
+    } dev;
     // (The chain as a replayed hipGraph was measured in round 4 and dropped in round 6: this runtime issues a replayed graph node
     // by node, 222 us of host time per step against 195 us for the same ~25 plain launches -- docs/HISTORY.md.)
-    int act_hint = 0;  // device-side auto-reset: robots the reset chain is expected to cover (picks the small-launch kernel variants)
-    uint64_t sd_fp = 0;
-    hipStream_t side3 = nullptr;
-    hipEvent_t ev_fill = nullptr, ev_consumed = nullptr;
-    void* sd_storage = nullptr;  // SpawnDev (defined behind the kernels)
-    void (*sd_delete)(void*) = nullptr;
     // output guards (include/imgenv.h: IMGENV_FLAG_CHECK_OUTPUTS / IMGENV_FLAG_FULL_REWRITE)
     unsigned char* pub_arena = nullptr;  // FULL_REWRITE: what imgenv_outputs hands out -- a copy of the working arena made at the end of every chain
     bool own_pub = false;
@@ -249,7 +267,6 @@ struct imgenv {
     size_t ep_clear_bytes = 0;   // what imgenv_episodes_clear zeroes, from ep.f on
     // episode log (include/imgenv.h: imgenv_episode_log_enable; csrc/episode_log.h)
     bool eplog_on = false;
-    unsigned long long* d_place_serial = nullptr;  // SpawnDev::place_serial of the present pool (valid while sd_ready)
     EpisodeLogDev eplog;
     imgenv_episode_log_out eplog_out;
     // action decoding (include/imgenv.h: imgenv_actions_enable; csrc/actions.h)
@@ -537,12 +554,12 @@ extern "C" void imgenv_destroy(imgenv_t* h) {
     if (h->err_host) (void)hipHostFree((void*)h->err_host);
     if (h->finished_host) (void)hipHostFree((void*)h->finished_host);
     for (int g = 0; g < imgenv::STAGE_GENS; g++) {
-        for (auto& c : h->stage_gen[g]) (void)hipHostFree(c.p);
-        if (h->ev_gen[g]) (void)hipEventDestroy(h->ev_gen[g]);
+        for (auto& c : h->rs.chunks[g]) (void)hipHostFree(c.p);
+        if (h->rs.ev_gen[g]) (void)hipEventDestroy(h->rs.ev_gen[g]);
     }
-    if (h->side3) {
-        (void)hipStreamSynchronize(h->side3);
-        (void)hipStreamDestroy(h->side3);
+    if (h->dev.side3) {
+        (void)hipStreamSynchronize(h->dev.side3);
+        (void)hipStreamDestroy(h->dev.side3);
     }
     if (h->crowd.stream) {
         (void)hipStreamSynchronize(h->crowd.stream);
@@ -551,9 +568,8 @@ extern "C" void imgenv_destroy(imgenv_t* h) {
     if (h->crowd.ev) (void)hipEventDestroy(h->crowd.ev);
     for (hipEvent_t e : h->crowd.ev_in)
         if (e) (void)hipEventDestroy(e);
-    if (h->ev_fill) (void)hipEventDestroy(h->ev_fill);
-    if (h->ev_consumed) (void)hipEventDestroy(h->ev_consumed);
-    if (h->sd_storage && h->sd_delete) h->sd_delete(h->sd_storage);
+    if (h->dev.ev_fill) (void)hipEventDestroy(h->dev.ev_fill);
+    if (h->dev.ev_consumed) (void)hipEventDestroy(h->dev.ev_consumed);
     if (h->ev_fork2) (void)hipEventDestroy(h->ev_fork2);
     if (h->ev_join2) (void)hipEventDestroy(h->ev_join2);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -630,7 +646,7 @@ static PlanChain chain_facts(const imgenv* h, int is_reset, bool moved = false, 
     const DevWorld& d = h->d;
     PlanChain c;
     c.act_ng = d.act_ng; c.act_np = d.act_np; c.act_nl = d.act_nl; c.act_nw = d.act_nw; c.act_cells = d.act_cells;
-    c.listed = d.act_list != nullptr; c.n_dev = d.act_n_dev != nullptr; c.act_hint = h->act_hint;
+    c.listed = d.act_list != nullptr; c.n_dev = d.act_n_dev != nullptr; c.act_hint = h->dev.act_hint;
     c.is_reset = is_reset != 0; c.moved = moved; c.local_only = local_only;
     c.stamp_seq = h->stamp_seq;
     c.orca_cap = std::max(h->cap_obst, d.n_obst);
@@ -1351,11 +1367,6 @@ extern "C" int imgenv_create(const imgenv_cfg* cfg, const uint8_t* static_map, i
 }
 
 // ---------------------------------------------------------------------------------------- reset
-struct ResetRobot {  // per local robot
-    double gx, gy;
-    Tf2 world_target;
-};
-
 // the t-th robot of a reset (list order): pose3 / rr hold the reset's robots in that order, in page-locked host memory
 __device__ __forceinline__ void reset_robot(const DevWorld& w, const int* list, int t, const double* __restrict__ pose3,
                                             const ResetRobot* __restrict__ rr, int whole) {
@@ -1720,12 +1731,7 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
 }
 
 // ---- pinned staging for reset: everything a reset uploads goes through page-locked chunks owned by the handle and
-// reaches the device in ONE launch (a table of segments), however many worlds the reset covers ----
-struct StageSeg {
-    unsigned char* dst;
-    const unsigned char* src;
-    size_t bytes;
-};
+// reaches the device in ONE launch (a table of segments: StageSeg, reset_plan.h), however many worlds the reset covers ----
 // a kernel pulls the bytes out of the page-locked chunks: unlike hipMemcpyAsync (which was seen to block the host for
 // several milliseconds on a busy stream once a copy exceeds a few hundred KB) a launch never waits
 __device__ __forceinline__ void copy_segment(const StageSeg g, size_t t, size_t stride) {
@@ -1738,9 +1744,6 @@ __device__ __forceinline__ void copy_segment(const StageSeg g, size_t t, size_t 
     } else {
         for (size_t q = t; q < g.bytes; q += stride) g.dst[q] = g.src[q];
     }
-}
-__global__ __launch_bounds__(256) void k_stage_copy(const StageSeg* __restrict__ table, int per_seg) {
-    copy_segment(table[blockIdx.x / per_seg], (size_t)(blockIdx.x % per_seg) * blockDim.x + threadIdx.x, (size_t)per_seg * blockDim.x);
 }
 
 // Everything of a reset that only depends on the staged bytes, in ONE launch (each dependent launch of the reset chain
@@ -1762,21 +1765,22 @@ struct ResetArgs {
     MapSel maps;  // map bank: which map of static_map[n_maps][stride] each world starts from (csrc/map_bank.h)
 };
 static int stage_begin(imgenv* h) {
-    h->gen = (h->gen + 1) % imgenv::STAGE_GENS;
-    const int g = h->gen;
-    if (!h->ev_gen[g]) HIPCHK(hipEventCreateWithFlags(&h->ev_gen[g], hipEventDisableTiming));
-    if (h->gen_pending[g]) {  // the copies of the reset STAGE_GENS calls ago (long finished in practice) still own these chunks
-        HIPCHK(hipEventSynchronize(h->ev_gen[g]));
-        h->gen_pending[g] = false;
+    imgenv::ResetStage& s = h->rs;
+    s.gen = (s.gen + 1) % imgenv::STAGE_GENS;
+    const int g = s.gen;
+    if (!s.ev_gen[g]) HIPCHK(hipEventCreateWithFlags(&s.ev_gen[g], hipEventDisableTiming));
+    if (s.gen_pending[g]) {  // the copies of the reset STAGE_GENS calls ago (long finished in practice) still own these chunks
+        HIPCHK(hipEventSynchronize(s.ev_gen[g]));
+        s.gen_pending[g] = false;
     }
-    for (auto& c : h->stage_gen[g]) c.used = 0;
-    h->segs.clear();
-    h->seg_max = 0;
+    for (auto& c : s.chunks[g]) c.used = 0;
+    s.segs.clear();
+    s.seg_max = 0;
     return 0;
 }
 static int stage_room(imgenv* h, size_t bytes, unsigned char** out) {
     imgenv::Chunk* use = nullptr;
-    std::vector<imgenv::Chunk>& chunks = h->stage_gen[h->gen];
+    std::vector<imgenv::Chunk>& chunks = h->rs.chunks[h->rs.gen];
     for (auto& c : chunks)
         if (c.cap - c.used >= bytes) {
             use = &c;
@@ -1793,32 +1797,36 @@ static int stage_room(imgenv* h, size_t bytes, unsigned char** out) {
     if (use->used > use->cap) use->used = use->cap;
     return 0;
 }
-static int stage_put(imgenv* h, void* dst, const void* src, size_t bytes) {
-    if (bytes == 0) return 0;
+// page-locked room for n elements that k_reset_apply copies to dst; the caller fills *out
+template <typename T>
+static int stage_seg(imgenv* h, T* dst, size_t n, T** out) {
     unsigned char* p = nullptr;
-    if (int rc = stage_room(h, bytes, &p)) return rc;
-    memcpy(p, src, bytes);
-    h->segs.push_back(imgenv::StageSegHost{dst, p, bytes});
-    h->seg_max = std::max(h->seg_max, bytes);
+    if (int rc = stage_room(h, sizeof(T) * n, &p)) return rc;
+    *out = (T*)p;
+    if (n == 0) return 0;
+    h->rs.segs.push_back(StageSeg{(unsigned char*)dst, p, sizeof(T) * n});
+    h->rs.seg_max = std::max(h->rs.seg_max, sizeof(T) * n);
     return 0;
 }
-// launch the copies queued so far
-static int stage_flush(imgenv* h, hipStream_t st) {
-    if (h->segs.empty()) return 0;
-    static_assert(sizeof(imgenv::StageSegHost) == sizeof(StageSeg), "layout");
-    unsigned char* table = nullptr;
-    if (int rc = stage_room(h, h->segs.size() * sizeof(StageSeg), &table)) return rc;
-    memcpy(table, h->segs.data(), h->segs.size() * sizeof(StageSeg));
-    const int per_seg = (int)std::min<size_t>((h->seg_max / 16 + 255) / 256 + 1, 16);
-    k_stage_copy<<<dim3((unsigned)(h->segs.size() * per_seg)), dim3(256), 0, st>>>((const StageSeg*)table, per_seg);
-    HIPCHK(hipGetLastError());
-    h->segs.clear();
-    h->seg_max = 0;
+template <typename T, typename S>
+static int stage_put(imgenv* h, T* dst, const S* src, size_t bytes) {
+    if (bytes == 0) return 0;
+    unsigned char* p = nullptr;
+    if (int rc = stage_seg(h, (unsigned char*)dst, bytes, &p)) return rc;
+    memcpy(p, src, bytes);
+    return 0;
+}
+// n ints in page-locked room of their own, for a kernel to read in place
+static int stage_ints(imgenv* h, const int* src, size_t n, int** out) {
+    unsigned char* p = nullptr;
+    if (int rc = stage_room(h, sizeof(int) * n, &p)) return rc;
+    memcpy(p, src, sizeof(int) * n);
+    *out = (int*)p;
     return 0;
 }
 static int stage_end(imgenv* h, hipStream_t st) {
-    HIPCHK(hipEventRecord(h->ev_gen[h->gen], st));
-    h->gen_pending[h->gen] = true;
+    HIPCHK(hipEventRecord(h->rs.ev_gen[h->rs.gen], st));
+    h->rs.gen_pending[h->rs.gen] = true;
     return 0;
 }
 
@@ -1901,13 +1909,7 @@ __global__ __launch_bounds__(256) void k_reset_apply(DevWorld w, ResetArgs a) {
 // agent.cpp:285-327) writes unless the cell holds 0 / 1 / 2 -- and only ever writes 0, so the order does not matter.
 // One workgroup per obstacle.  Its footprint samples (agent.cpp:18-30, 51-62: a 0.01 m lattice, for circles the points within
 // the radius) are generated on the fly from the lattice bounds the host computed: random obstacle radii (EnvPos draws a fresh
-// one per episode, reset_helper.py:131-133) then cost nothing -- no per-size sample list to upload, cache or free.
-struct ObstInst {
-    double x, y, sh, ch;  // pose; sin / cos of yaw/2, evaluated on the host
-    double cx, cy, r;     // circle: centre offset and radius (sizes[0..2]); rectangle: unused
-    int m0, m1, n0, n1;   // lattice range: circle -bb..bb with bb = ceil(r / 0.01); rectangle floor(min / 0.01)..ceil(max / 0.01)
-    int shape, world;
-};
+// one per episode, reset_helper.py:131-133) then cost nothing -- no per-size sample list to upload, cache or free (ObstInst, reset_plan.h).
 template <bool POW2>
 __global__ __launch_bounds__(256) void k_reset_obstacles(DevWorld w, const ObstInst* __restrict__ inst, int stamp, const int* n_dev, int per_world, int parts,
                                                         ObstInst* keep, int* keep_valid) {
@@ -1958,285 +1960,6 @@ __global__ __launch_bounds__(256) void k_reset_obstacles(DevWorld w, const ObstI
 static auto k_reset_obstacles_for(const PlanHandle& p) { return p.pow2 ? k_reset_obstacles<true> : k_reset_obstacles<false>; }
 static auto k_restore_maps_dev_for(const PlanHandle& p) { return p.pow2 ? k_restore_maps_dev<true> : k_restore_maps_dev<false>; }
 
-// the obstacle list of one world's reset batch: instances for k_reset_obstacles, the RVO polygons with their BSP
-// (RVOScene::addObs + processObs, rvoscene.h:19-26, img_env.cpp:283) and the social-force segments (pedscene.h:22-26)
-static int world_obstacles(imgenv* h, int k, const imgenv_reset_batch* b, std::vector<double>& sfm_obs) {
-    RvoObstacles& rvo = h->rvos[k];
-    rvo.clear();
-    for (int q = 0; q < b->n_obstacles; q++) {
-        const int shape = b->obs_shape[q];
-        double sizes[4];
-        for (int j = 0; j < 4; j++) sizes[j] = (double)b->obs_size[4 * q + j];
-        const double* p = b->obs_pose + 4 * q;
-        const double yaw = tf_yaw_from_quaternion_zw(p[2], p[3]);
-        if (shape != IMGENV_SHAPE_CIRCLE && shape != IMGENV_SHAPE_RECTANGLE) FAIL(IMGENV_EINVAL, "obstacle %d: unsupported shape %d", q, shape);
-        imgenv::ObstInstHost oi;
-        oi.x = p[0]; oi.y = p[1]; oi.sh = sin(yaw * 0.5); oi.ch = cos(yaw * 0.5);
-        oi.world = k;
-        oi.shape = shape;
-        oi.cx = sizes[0]; oi.cy = sizes[1]; oi.r = sizes[2];
-        if (shape == IMGENV_SHAPE_CIRCLE) {  // init_shape_circle (agent.cpp:18-30)
-            const int bb = (int)ceil(sizes[2] / 0.01);
-            oi.m0 = oi.n0 = -bb;
-            oi.m1 = oi.n1 = bb;
-        } else {                             // init_shape_rectangle (agent.cpp:51-62)
-            oi.m0 = (int)floor(sizes[0] / 0.01); oi.m1 = (int)ceil(sizes[1] / 0.01);
-            oi.n0 = (int)floor(sizes[2] / 0.01); oi.n1 = (int)ceil(sizes[3] / 0.01);
-        }
-        if ((long long)(oi.m1 - oi.m0 + 1) * (long long)(oi.n1 - oi.n0 + 1) > (1ll << 26) || oi.m1 < oi.m0 || oi.n1 < oi.n0)
-            FAIL(IMGENV_EINVAL, "obstacle %d: degenerate or oversized footprint", q);
-        h->oinst.push_back(oi);
-        const Tf2 bw = tf_from_pose_sc(p[0], p[1], oi.sh, oi.ch);
-        double pax, pay, pbx, pby;
-        get_corners(shape, sizes, bw, pax, pay, pbx, pby);
-        if (!b->ignore_obstacle && h->cfg.ped_scene_type == IMGENV_SCENE_PEDSIM) {  // PedScene::addObs: the segment pa -> pb
-            sfm_obs.push_back(pax); sfm_obs.push_back(pay); sfm_obs.push_back(pbx); sfm_obs.push_back(pby);
-        }
-        if (!b->ignore_obstacle && h->NA > 0) {  // RVOScene::addObs
-            const float v[8] = {(float)pax, (float)pay, (float)pax, (float)pby, (float)pbx, (float)pby, (float)pbx, (float)pay};
-            rvo.add(v, 4);
-        }
-    }
-    rvo.process();
-    return 0;
-}
-
-// obstacle segments and their BSP of world k: a slice of cap_obst / cap_nodes entries per world
-static int put_world_rvo(imgenv* h, int k) {
-    static_assert(sizeof(RvoObstHost) == sizeof(RvoObstDev) && sizeof(RvoNodeHost) == sizeof(RvoNodeDev), "layout");
-    const RvoObstacles& r = h->rvos[k];
-    bool all = false;
-    if (h->dev_reset_used && ((int)r.ob.size() > h->cap_obst || (int)r.nodes.size() > h->cap_nodes))
-        FAIL(IMGENV_ESTATE, "world %d: more RVO obstacle vertices than the handle has room for, after imgenv_step_autoreset_device has taken over "
-                            "the per-world obstacle tables (reset every world with imgenv_reset first)", k);
-    if ((int)r.ob.size() > h->cap_obst) {
-        h->cap_obst = (int)r.ob.size() * 2;
-        if (int rc = dev_alloc(h, &h->d_obst, (size_t)h->cap_obst * h->W)) return rc;
-        all = true;
-    }
-    if ((int)r.nodes.size() > h->cap_nodes) {
-        h->cap_nodes = (int)r.nodes.size() * 2;
-        if (int rc = dev_alloc(h, &h->d_nodes, (size_t)h->cap_nodes * h->W)) return rc;
-        all = true;
-    }
-    if (all) h->wobst_all = true;  // every world's slice moved: the whole per-world table goes up with this reset
-    for (int q = all ? 0 : k; q < (all ? h->W : k + 1); q++) {  // a grown array is refilled from the host copies
-        const RvoObstacles& rq = h->rvos[q];
-        if (!rq.ob.empty()) RTRY(stage_put(h, h->d_obst + (size_t)q * h->cap_obst, rq.ob.data(), sizeof(RvoObstDev) * rq.ob.size()));
-        if (!rq.nodes.empty()) RTRY(stage_put(h, h->d_nodes + (size_t)q * h->cap_nodes, rq.nodes.data(), sizeof(RvoNodeDev) * rq.nodes.size()));
-        h->wobst[q] = q * h->cap_obst;
-        h->wobst[h->W + q] = q * h->cap_nodes;
-        h->wobst[2 * h->W + q] = (int)rq.ob.size();
-        h->wobst[3 * h->W + q] = rq.root;
-    }
-    DevWorld& d = h->d;
-    d.obst = h->d_obst;
-    d.onodes = h->d_nodes;
-    d.n_obst = (int)h->rvos[0].ob.size();  // (W > 1: the kernels read the per-world table instead)
-    d.n_onodes = (int)h->rvos[0].nodes.size();
-    d.oroot = h->rvos[0].root;
-    return 0;
-}
-
-// Host half of one world's reset: its obstacles, pedestrians and robots go into the staging chunks.
-static int stage_world(imgenv* h, int k, int q_list, const imgenv_reset_batch* b, const ResetChoices& choices, hipStream_t st) {
-    DevWorld& d = h->d;
-    const int W = h->W, Rw = h->Rw, Pw = h->Pw, P = h->P;
-    const int g_lo = k * Rw, p_lo = k * Pw;  // first robot / pedestrian of the world
-    std::vector<double> sfm_obs;
-    RTRY(world_obstacles(h, k, b, sfm_obs));
-    RTRY(put_world_rvo(h, k));
-    if (h->cfg.ped_scene_type == IMGENV_SCENE_PEDSIM) {
-        const int nob = (int)sfm_obs.size() / 4;
-        if (W > 1) {  // world k's slice and count
-            if (nob > h->sfm_cap_obs) FAIL(IMGENV_EINVAL, "world %d: more than %d obstacles in a pedscene world of a multi-world handle", k, h->sfm_cap_obs);
-            if (nob) RTRY(stage_put(h, d.sfm.obs + (size_t)k * d.sfm.cap_obs * 4, sfm_obs.data(), sizeof(double) * sfm_obs.size()));
-            h->sfm_nobs_w[k] = nob;
-            RTRY(stage_put(h, const_cast<int*>(d.sfm.n_obs_w) + k, &h->sfm_nobs_w[k], sizeof(int)));
-        } else {
-            if (nob > h->sfm_cap_obs) {
-                h->sfm_cap_obs = nob * 2;
-                if (int rc = dev_alloc(h, &d.sfm.obs, (size_t)h->sfm_cap_obs * 4)) return rc;
-                d.sfm.cap_obs = h->sfm_cap_obs;
-            }
-            if (nob) RTRY(stage_put(h, d.sfm.obs, sfm_obs.data(), sizeof(double) * sfm_obs.size()));
-            d.sfm.n_obs = nob;
-        }
-    }
-    // pedestrians (img_env.cpp:220-250)
-    if (Pw > 0) {
-        const bool dataset = h->cfg.ped_scene_type == IMGENV_SCENE_DATASET;
-        const bool fed = dataset && h->d_trk_cur && !b->ped_traj_v;  // bank-fed: k_tracks_install brings this world's pedestrians
-        if (dataset && !b->ped_traj_v && !fed) FAIL(IMGENV_EINVAL, "dataset scene: ped_traj_v is missing from the reset batch");
-        if (fed) {  // (the batch's own pedestrian arrays are ignored; reset_ped's pass over the world writes zeros that the install replaces)
-            h->trk_fed.push_back(k);
-            h->trk_fed_ids.push_back(choices.track_ids ? choices.track_ids[q_list] : -1);
-            memset(h->pin_ped3 + (size_t)q_list * Pw * 3, 0, sizeof(double) * 3 * (size_t)Pw);
-        } else if (dataset && h->d_trk_cur) {  // its own tracks: imgenv_world_tracks says -1, the CYCLE count stays
-            static const int minus_one = -1;
-            RTRY(stage_put(h, h->d_trk_cur + k, &minus_one, sizeof(int)));
-        }
-        if (!fed && b->ped_traj_cap > h->traj_cap) {  // longer trajectories than any before: re-lay the table out (other worlds keep theirs)
-            RTRY(stage_flush(h, st));  // (queued copies aim at the old table)
-            const int old_cap = h->traj_cap;
-            double *old_t = h->d_traj, *old_v = h->d_traj_v;
-            h->traj_cap = b->ped_traj_cap;
-            if (int rc = dev_alloc(h, &h->d_traj, (size_t)P * h->traj_cap * 3)) return rc;
-            if (dataset)
-                if (int rc = dev_alloc(h, &h->d_traj_v, (size_t)P * h->traj_cap * 3)) return rc;
-            if (W > 1 && old_cap > 0) {
-                const size_t n = (size_t)P * old_cap * 3;
-                k_restride3<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(h->d_traj, old_t, P, old_cap, h->traj_cap);
-                if (dataset) k_restride3<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(h->d_traj_v, old_v, P, old_cap, h->traj_cap);
-            }
-        }
-        double* ped3 = h->pin_ped3 + (size_t)q_list * Pw * 3;
-        std::vector<int>& tlen = h->tmp_i0;
-        std::vector<double>& traj = h->tmp_d1;
-        tlen.resize(Pw);
-        traj.assign(fed ? 0 : (size_t)Pw * h->traj_cap * 3, 0.0);
-        for (int j = 0; j < Pw && !fed; j++) {
-            const double* p = b->ped_pose + 4 * j;
-            ped3[3 * j] = p[0];
-            ped3[3 * j + 1] = p[1];
-            ped3[3 * j + 2] = tf_yaw_from_quaternion_zw(p[2], p[3]);
-            tlen[j] = b->ped_traj_len[j];
-            if (tlen[j] < 1 || tlen[j] > b->ped_traj_cap) FAIL(IMGENV_EINVAL, "ped %d: bad trajectory length %d", p_lo + j, tlen[j]);
-            for (int q = 0; q < tlen[j]; q++)
-                memcpy(&traj[((size_t)j * h->traj_cap + q) * 3], b->ped_traj + ((size_t)j * b->ped_traj_cap + q) * 3, 24);
-        }
-        if (!fed) {
-            RTRY(stage_put(h, h->d_traj + (size_t)p_lo * h->traj_cap * 3, traj.data(), traj.size() * 8));
-            RTRY(stage_put(h, h->d_traj_len + p_lo, tlen.data(), sizeof(int) * Pw));
-        }
-        if (fed) {
-            d.ptraj_v = h->d_traj_v;
-        } else if (dataset) {  // trajectory_v (img_env.cpp:246-247) + the yaw _step_ped_dataset derives from it, with the host's libm
-            std::vector<double>& tv = h->tmp_d1;
-            tv.assign((size_t)Pw * h->traj_cap * 3, 0.0);
-            for (int j = 0; j < Pw; j++)
-                for (int q = 0; q < tlen[j]; q++) {
-                    const double* v = b->ped_traj_v + ((size_t)j * b->ped_traj_cap + q) * 2;
-                    double* o = &tv[((size_t)j * h->traj_cap + q) * 3];
-                    o[0] = v[0];
-                    o[1] = v[1];
-                    o[2] = atan2(v[1], v[0]);
-                }
-            RTRY(stage_put(h, h->d_traj_v + (size_t)p_lo * h->traj_cap * 3, tv.data(), tv.size() * 8));
-            d.ptraj_v = h->d_traj_v;
-        }
-        if (h->cfg.ped_scene_type == IMGENV_SCENE_PEDSIM) {  // PedScene::setWayPoint (pedscene.h:38-46): [goal r=1, trajectory r=z]
-            // (this world's pedestrians: the first Pw agents of its crowd)
-            std::vector<double> wx((size_t)Pw * SFM_MAX_WP, 0.0), wy(wx), wr(wx);
-            std::vector<int> dq((size_t)Pw * SFM_MAX_WP, 0), dqn(Pw, 0), dest(Pw, 0), last(Pw, -1);
-            for (int j = 0; j < Pw; j++) {
-                int nw = 0;
-                wx[(size_t)j * SFM_MAX_WP] = b->ped_goal[2 * j];
-                wy[(size_t)j * SFM_MAX_WP] = b->ped_goal[2 * j + 1];
-                wr[(size_t)j * SFM_MAX_WP] = 1.0;
-                nw = 1;
-                for (int q = 0; q < tlen[j] && nw < SFM_MAX_WP; q++, nw++) {
-                    const double* tp = b->ped_traj + ((size_t)j * b->ped_traj_cap + q) * 3;
-                    wx[(size_t)j * SFM_MAX_WP + nw] = tp[0];
-                    wy[(size_t)j * SFM_MAX_WP + nw] = tp[1];
-                    wr[(size_t)j * SFM_MAX_WP + nw] = tp[2];
-                }
-                for (int q = 0; q < nw; q++) dq[(size_t)j * SFM_MAX_WP + q] = q;
-                dqn[j] = nw;
-                dest[j] = 0;  // addWaypoint leaves destination = waypoints.front() without popping it (ped_agent.cpp:97-100)
-            }
-            const SfmDev& f = d.sfm;
-            const size_t a0 = (size_t)k * f.n;  // first agent of world k's crowd
-            RTRY(stage_put(h, f.wpx + a0 * SFM_MAX_WP, wx.data(), wx.size() * 8));
-            RTRY(stage_put(h, f.wpy + a0 * SFM_MAX_WP, wy.data(), wy.size() * 8));
-            RTRY(stage_put(h, f.wpr + a0 * SFM_MAX_WP, wr.data(), wr.size() * 8));
-            RTRY(stage_put(h, f.dq + a0 * SFM_MAX_WP, dq.data(), dq.size() * 4));
-            RTRY(stage_put(h, f.dq_n + a0, dqn.data(), dqn.size() * 4));
-            RTRY(stage_put(h, f.dest + a0, dest.data(), dest.size() * 4));
-            RTRY(stage_put(h, f.last + a0, last.data(), last.size() * 4));
-        }
-        d.ptraj = h->d_traj;
-        d.traj_cap = h->traj_cap;
-    }
-    // robots (img_env.cpp:252-282)
-    const int l_lo = W > 1 ? g_lo : 0, n_l = W > 1 ? Rw : h->RL;  // local robots of this world (a shard exists for W == 1 only)
-    double* rob3 = h->pin_rob3 + (size_t)q_list * Rw * 5;
-    ResetRobot* rr = (ResetRobot*)h->pin_rr + (size_t)q_list * n_l;
-    for (int i = 0; i < Rw; i++) {
-        const double* p = b->robot_pose + 4 * i;
-        const double yaw = tf_yaw_from_quaternion_zw(p[2], p[3]);
-        rob3[5 * i] = p[0];
-        rob3[5 * i + 1] = p[1];
-        rob3[5 * i + 2] = yaw;
-        rob3[5 * i + 3] = sin(yaw * 0.5);
-        rob3[5 * i + 4] = cos(yaw * 0.5);
-        const int l = g_lo + i - h->r0;
-        if (l >= 0 && l < h->RL) {  // set_goal (agent.cpp:144-154)
-            ResetRobot& q = rr[l - l_lo];
-            q.gx = b->robot_goal[2 * i];
-            q.gy = b->robot_goal[2 * i + 1];
-            q.world_target = tf_inverse(tf_from_pose(q.gx, q.gy, yaw));
-        }
-    }
-    return 0;
-}
-
-// everything that can be wrong with the batches is found here, BEFORE any of them touches the handle's state: a reset
-// that fails part-way would leave host and device copies of the earlier worlds out of step
-static int reset_checks(imgenv* h, int n, const imgenv_reset_batch* b, int peds_per_batch) {
-    if (!h || !b) FAIL(IMGENV_EINVAL, "null argument");
-    for (int q = 0; q < n; q++) {
-        if (b[q].struct_size != (int32_t)sizeof(imgenv_reset_batch)) FAIL(IMGENV_EINVAL, "reset batch ABI mismatch");
-        // (bank-fed: a dataset handle with a track bank takes the pedestrians of a batch without ped_traj_v from the bank, and the
-        // batch's own pedestrian arrays are ignored)
-        const bool fed = h->d_trk_cur && h->cfg.ped_scene_type == IMGENV_SCENE_DATASET && !b[q].ped_traj_v;
-        if (b[q].n_obstacles < 0 || (h->P > 0 && !fed && b[q].ped_traj_cap < 1)) FAIL(IMGENV_EINVAL, "bad reset batch");
-        if (b[q].n_obstacles > 0 && (!b[q].obs_shape || !b[q].obs_size || !b[q].obs_pose)) FAIL(IMGENV_EINVAL, "reset batch %d: null obstacle arrays", q);
-        if (!b[q].robot_pose || !b[q].robot_goal) FAIL(IMGENV_EINVAL, "reset batch %d: null robot arrays", q);
-        for (int o = 0; o < b[q].n_obstacles; o++)
-            if (b[q].obs_shape[o] != IMGENV_SHAPE_CIRCLE && b[q].obs_shape[o] != IMGENV_SHAPE_RECTANGLE)
-                FAIL(IMGENV_EINVAL, "reset batch %d, obstacle %d: unsupported shape %d", q, o, b[q].obs_shape[o]);
-        if (peds_per_batch > 0 && !fed) {
-            if (!b[q].ped_pose || !b[q].ped_traj_len || !b[q].ped_traj) FAIL(IMGENV_EINVAL, "reset batch %d: null pedestrian arrays", q);
-            if (h->cfg.ped_scene_type == IMGENV_SCENE_DATASET && !b[q].ped_traj_v)
-                FAIL(IMGENV_EINVAL, "dataset scene: ped_traj_v is missing from the reset batch");
-            if (h->cfg.ped_scene_type == IMGENV_SCENE_PEDSIM && !b[q].ped_goal) FAIL(IMGENV_EINVAL, "pedscene: ped_goal is missing from the reset batch");
-            for (int j = 0; j < peds_per_batch; j++)
-                if (b[q].ped_traj_len[j] < 1 || b[q].ped_traj_len[j] > b[q].ped_traj_cap)
-                    FAIL(IMGENV_EINVAL, "reset batch %d, ped %d: bad trajectory length %d", q, j, b[q].ped_traj_len[j]);
-        }
-    }
-    RTRY(step_recover(h));
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc = check_device_flags(h)) {  // report what the abandoned episode raised, then start clean
-        for (int q = 0; q < 8; q++) h->err_host[q] = 0;
-        return rc;
-    }
-    if (!h->d_act_list) RTRY(dev_alloc(h, &h->d_act_list, (size_t)h->W));
-    return 0;
-}
-
-// page-locked blocks for the robots / pedestrians of the n worlds of this reset, in list order (read by k_reset_apply)
-static int reset_blocks(imgenv* h, int n, const int* list) {
-    unsigned char* p = nullptr;
-    const size_t n_local = h->W > 1 ? (size_t)n * h->Rw : (size_t)h->RL;
-    RTRY(stage_room(h, sizeof(double) * 5 * n * h->Rw, &p));
-    h->pin_rob3 = (double*)p;
-    RTRY(stage_room(h, sizeof(ResetRobot) * std::max<size_t>(n_local, 1), &p));
-    h->pin_rr = p;
-    RTRY(stage_room(h, sizeof(double) * 3 * std::max<size_t>((size_t)n * h->Pw, 1), &p));
-    h->pin_ped3 = (double*)p;
-    h->pin_list = nullptr;
-    h->trk_fed.clear();
-    h->trk_fed_ids.clear();
-    if (list) {
-        RTRY(stage_room(h, sizeof(int) * n, &p));
-        h->pin_list = (int*)p;
-        memcpy(h->pin_list, list, sizeof(int) * n);
-    }
-    return 0;
-}
-
 static MapSel map_sel(const imgenv* h) {
     MapSel m;
     m.cur = h->d_map_cur; m.next = h->d_map_next; m.ids = nullptr;
@@ -2254,13 +1977,194 @@ static TrackSel track_sel(const imgenv* h) {
     return t;
 }
 
-static int sfm_ahead_drop(imgenv* h, hipStream_t st);
-static int reset_launch(imgenv* h, const int* list, int n, const ResetChoices& choices, hipStream_t st, int whole) {
+// ---- a host-side reset: prepare (reset_plan.h: what every listed world's batch brings, nothing of the handle written), refuse
+// (every refusal of the path, before the handle or the device is touched), commit (grow once, stage every destination once, launch)
+static ResetFacts reset_facts(const imgenv* h) {
+    ResetFacts f;
+    f.W = h->W; f.Rw = h->Rw; f.Pw = h->Pw; f.r0 = h->r0; f.RL = h->RL; f.NA = h->NA;
+    f.scene = h->cfg.ped_scene_type;
+    f.track_bank = h->d_trk_cur != nullptr;
+    f.dev_reset_used = h->dev.used;
+    f.cap_obst = h->cap_obst; f.cap_nodes = h->cap_nodes; f.sfm_cap_obs = h->sfm_cap_obs; f.traj_cap = h->traj_cap;
+    f.sfm_n = h->d.sfm.n; f.sfm_per_world = h->d.sfm.n_obs_w != nullptr; f.has_traj = h->d_traj != nullptr;
+    return f;
+}
+// world k's share of a whole-handle batch: its robots and pedestrians (world-major numbering), one obstacle list for all
+static imgenv_reset_batch world_batch(const imgenv* h, const imgenv_reset_batch* b, int k) {
+    imgenv_reset_batch sub = *b;
+    sub.robot_pose = b->robot_pose + (size_t)4 * k * h->Rw;
+    sub.robot_goal = b->robot_goal + (size_t)2 * k * h->Rw;
+    if (h->P > 0) {
+        sub.ped_pose = b->ped_pose ? b->ped_pose + (size_t)4 * k * h->Pw : nullptr;  // (null: a bank-fed batch, reset_check_batches)
+        sub.ped_goal = b->ped_goal ? b->ped_goal + (size_t)2 * k * h->Pw : nullptr;
+        sub.ped_traj_len = b->ped_traj_len ? b->ped_traj_len + (size_t)k * h->Pw : nullptr;
+        sub.ped_traj = b->ped_traj ? b->ped_traj + (size_t)k * h->Pw * b->ped_traj_cap * 3 : nullptr;
+        sub.ped_traj_v = b->ped_traj_v ? b->ped_traj_v + (size_t)k * h->Pw * b->ped_traj_cap * 2 : nullptr;
+    }
+    return sub;
+}
+// prepare + refuse.  worlds == nullptr: every world of the handle from the one batch
+static int reset_prepare(imgenv* h, const ResetFacts& f, int n, const int32_t* worlds, const imgenv_reset_batch* batches) {
+    h->rs.worlds.resize((size_t)n);
+    for (int q = 0; q < n; q++) reset_prepare_world(f, worlds ? worlds[q] : q, batches[worlds ? q : 0], h->rs.worlds[q]);
+    return reset_check_worlds(f, h->rs.worlds.data(), n, g_err);
+}
+// what a reset asks of the handle and the device before it commits
+static int reset_device_ready(imgenv* h, hipStream_t st) {
+    RTRY(step_recover(h));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = check_device_flags(h)) {  // report what the abandoned episode raised, then start clean
+        for (int q = 0; q < 8; q++) h->err_host[q] = 0;
+        return rc;
+    }
+    if (!h->d_act_list) RTRY(dev_alloc(h, &h->d_act_list, (size_t)h->W));
+    return outputs_verify(h, st);
+}
+
+// page-locked blocks for the robots / pedestrians of the n worlds of this reset, in list order (read by k_reset_apply)
+static int reset_blocks(imgenv* h, int n, const int* list) {
+    imgenv::ResetStage& s = h->rs;
+    unsigned char* p = nullptr;
+    const size_t n_local = h->W > 1 ? (size_t)n * h->Rw : (size_t)h->RL;
+    RTRY(stage_room(h, sizeof(double) * 5 * n * h->Rw, &p));
+    s.rob3 = (double*)p;
+    RTRY(stage_room(h, sizeof(ResetRobot) * std::max<size_t>(n_local, 1), &p));
+    s.rr = (ResetRobot*)p;
+    RTRY(stage_room(h, sizeof(double) * 3 * std::max<size_t>((size_t)n * h->Pw, 1), &p));
+    s.ped3 = (double*)p;
+    s.list = nullptr;
+    s.fed.clear();
+    s.fed_ids.clear();
+    if (list) RTRY(stage_ints(h, list, (size_t)n, &s.list));
+    return 0;
+}
+
+// commit, 1: the tables grow once, before the first segment is queued (reset_growth)
+static int reset_grow(imgenv* h, const ResetGrowth& g, hipStream_t st) {
     DevWorld& d = h->d;
-    if (int rc = sfm_ahead_drop(h, st)) return rc;  // (a reset writes the live crowd: positions, waypoints)
-    if (h->sd_ready) {  // a host-side reset draws obstacles the device-side restore does not know: whole-map restore next time
+    if (g.cap_obst != h->cap_obst) {
+        RTRY(dev_alloc(h, &h->d_obst, (size_t)g.cap_obst * h->W));
+        h->cap_obst = g.cap_obst;
+    }
+    if (g.cap_nodes != h->cap_nodes) {
+        RTRY(dev_alloc(h, &h->d_nodes, (size_t)g.cap_nodes * h->W));
+        h->cap_nodes = g.cap_nodes;
+    }
+    if (g.sfm_moved) {
+        RTRY(dev_alloc(h, &d.sfm.obs, (size_t)g.sfm_cap_obs * 4));
+        h->sfm_cap_obs = d.sfm.cap_obs = g.sfm_cap_obs;
+    }
+    if (g.traj_moved) {  // longer trajectories than any before: the table is laid out again (the worlds not listed keep theirs)
+        const bool dataset = h->cfg.ped_scene_type == IMGENV_SCENE_DATASET;
+        const int old_cap = h->traj_cap;
+        double *old_t = h->d_traj, *old_v = h->d_traj_v;
+        RTRY(dev_alloc(h, &h->d_traj, (size_t)h->P * g.traj_cap * 3));
+        if (dataset) RTRY(dev_alloc(h, &h->d_traj_v, (size_t)h->P * g.traj_cap * 3));
+        h->traj_cap = g.traj_cap;
+        if (h->W > 1 && old_cap > 0) {
+            const size_t n = (size_t)h->P * old_cap * 3;
+            k_restride3<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(h->d_traj, old_t, h->P, old_cap, h->traj_cap);
+            if (dataset) k_restride3<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(h->d_traj_v, old_v, h->P, old_cap, h->traj_cap);
+        }
+    }
+    return 0;
+}
+// commit, 2: the prepared obstacle sets become the handle's (swapped, not copied) and the slices of reset_rvo_worlds go up, each once
+static int stage_rvo(imgenv* h, const int* list, int n, const ResetGrowth& g) {
+    static_assert(sizeof(RvoObstHost) == sizeof(RvoObstDev) && sizeof(RvoNodeHost) == sizeof(RvoNodeDev), "layout");
+    for (int q = 0; q < n; q++) std::swap(h->rvos[h->rs.worlds[q].world], h->rs.worlds[q].rvo);
+    for (int k : reset_rvo_worlds(h->W, g, list, n)) {
+        const RvoObstacles& r = h->rvos[k];
+        if (!r.ob.empty()) RTRY(stage_put(h, h->d_obst + (size_t)k * h->cap_obst, r.ob.data(), sizeof(RvoObstDev) * r.ob.size()));
+        if (!r.nodes.empty()) RTRY(stage_put(h, h->d_nodes + (size_t)k * h->cap_nodes, r.nodes.data(), sizeof(RvoNodeDev) * r.nodes.size()));
+        rvo_table_put(h->wobst, h->W, k, h->cap_obst, h->cap_nodes, r);
+    }
+    DevWorld& d = h->d;
+    d.obst = h->d_obst;
+    d.onodes = h->d_nodes;
+    d.n_obst = (int)h->rvos[0].ob.size();  // (W > 1: the kernels read the per-world table instead)
+    d.n_onodes = (int)h->rvos[0].nodes.size();
+    d.oroot = h->rvos[0].root;
+    return 0;
+}
+// commit, 3: one world's rows.  The social-force segments of its crowd ...
+static int stage_world_crowd(imgenv* h, const ResetWorld& w) {
+    if (h->cfg.ped_scene_type != IMGENV_SCENE_PEDSIM) return 0;
+    DevWorld& d = h->d;
+    const int k = w.world, nob = (int)w.sfm_obs.size() / 4;
+    if (h->W > 1) {  // world k's slice and count
+        if (nob) RTRY(stage_put(h, d.sfm.obs + (size_t)k * d.sfm.cap_obs * 4, w.sfm_obs.data(), sizeof(double) * w.sfm_obs.size()));
+        h->sfm_nobs_w[k] = nob;
+        RTRY(stage_put(h, const_cast<int*>(d.sfm.n_obs_w) + k, &h->sfm_nobs_w[k], sizeof(int)));
+    } else {
+        if (nob) RTRY(stage_put(h, d.sfm.obs, w.sfm_obs.data(), sizeof(double) * w.sfm_obs.size()));
+        d.sfm.n_obs = nob;
+    }
+    return 0;
+}
+// ... its pedestrians (img_env.cpp:220-250), written straight into the page-locked rows ...
+static int stage_world_peds(imgenv* h, const ResetWorld& w, int q_list, const imgenv_reset_batch* b, const ResetChoices& choices) {
+    DevWorld& d = h->d;
+    const int k = w.world, Pw = h->Pw, p_lo = k * Pw, cap = h->traj_cap;
+    const bool dataset = h->cfg.ped_scene_type == IMGENV_SCENE_DATASET;
+    double* ped3 = h->rs.ped3 + (size_t)q_list * Pw * 3;
+    if (w.fed) {  // k_tracks_install brings this world's pedestrians (the batch's own pedestrian arrays are ignored)
+        h->rs.fed.push_back(k);
+        h->rs.fed_ids.push_back(choices.track_ids ? choices.track_ids[q_list] : -1);
+        reset_ped_rows(Pw, *b, true, cap, ped3, nullptr, nullptr);
+    } else {
+        if (dataset && h->d_trk_cur) {  // its own tracks: imgenv_world_tracks says -1, the CYCLE count stays
+            static const int minus_one = -1;
+            RTRY(stage_put(h, h->d_trk_cur + k, &minus_one, sizeof(int)));
+        }
+        double* traj = nullptr;
+        int* tlen = nullptr;
+        RTRY(stage_seg(h, h->d_traj + (size_t)p_lo * cap * 3, (size_t)Pw * cap * 3, &traj));
+        RTRY(stage_seg(h, h->d_traj_len + p_lo, (size_t)Pw, &tlen));
+        reset_ped_rows(Pw, *b, false, cap, ped3, tlen, traj);
+        if (dataset) {
+            double* tv = nullptr;
+            RTRY(stage_seg(h, h->d_traj_v + (size_t)p_lo * cap * 3, (size_t)Pw * cap * 3, &tv));
+            reset_traj_v_rows(Pw, *b, cap, tv);
+        }
+    }
+    if (w.fed || dataset) d.ptraj_v = h->d_traj_v;
+    d.ptraj = h->d_traj;
+    d.traj_cap = cap;
+    return 0;
+}
+// ... the waypoint deques of a pedscene crowd (this world's pedestrians: the first Pw agents of its crowd) ...
+static int stage_world_waypoints(imgenv* h, int k, const imgenv_reset_batch* b) {
+    const SfmDev& f = h->d.sfm;
+    const size_t a0 = (size_t)k * f.n, n = (size_t)h->Pw * SFM_MAX_WP;  // first agent of world k's crowd
+    WaypointRows o;
+    RTRY(stage_seg(h, f.wpx + a0 * SFM_MAX_WP, n, &o.wx));
+    RTRY(stage_seg(h, f.wpy + a0 * SFM_MAX_WP, n, &o.wy));
+    RTRY(stage_seg(h, f.wpr + a0 * SFM_MAX_WP, n, &o.wr));
+    RTRY(stage_seg(h, f.dq + a0 * SFM_MAX_WP, n, &o.dq));
+    RTRY(stage_seg(h, f.dq_n + a0, (size_t)h->Pw, &o.dq_n));
+    RTRY(stage_seg(h, f.dest + a0, (size_t)h->Pw, &o.dest));
+    RTRY(stage_seg(h, f.last + a0, (size_t)h->Pw, &o.last));
+    reset_waypoint_rows(h->Pw, *b, o);
+    return 0;
+}
+// ... and its robots (img_env.cpp:252-282); `epoch`: h->elapsed at this reset (its TimeLimitWrapper starts over)
+static int stage_world(imgenv* h, const ResetFacts& f, const ResetWorld& w, int q_list, const imgenv_reset_batch* b, const ResetChoices& choices, int epoch) {
+    RTRY(stage_world_crowd(h, w));
+    if (h->Pw > 0) RTRY(stage_world_peds(h, w, q_list, b, choices));
+    if (h->Pw > 0 && h->cfg.ped_scene_type == IMGENV_SCENE_PEDSIM) RTRY(stage_world_waypoints(h, w.world, b));
+    const size_t n_l = h->W > 1 ? h->Rw : h->RL;  // local robots of this world (a shard exists for W == 1 only)
+    reset_robot_rows(f, w.world, *b, h->rs.rob3 + (size_t)q_list * h->Rw * 5, h->rs.rr + (size_t)q_list * n_l);
+    h->world_epoch[w.world] = epoch;
+    h->world_ready[w.world] = 1;
+    return 0;
+}
+
+// commit, 4: the small tables of the listed worlds (nullptr: of every world)
+static int reset_stage_tables(imgenv* h, const int* list, int n, bool whole_wobst) {
+    if (h->dev.ready) {  // a host-side reset draws obstacles the device-side restore does not know: whole-map restore next time
         static const std::vector<int> zeros(1 << 16, 0);
-        SpawnDev& c = *(SpawnDev*)h->sd_storage;
+        const SpawnDev& c = h->dev.pool;
         if (!list) {
             for (int k0 = 0; k0 < h->W; k0 += (int)zeros.size())
                 RTRY(stage_put(h, c.w_inst_valid + k0, zeros.data(), sizeof(int) * (size_t)std::min<int>((int)zeros.size(), h->W - k0)));
@@ -2268,8 +2172,7 @@ static int reset_launch(imgenv* h, const int* list, int n, const ResetChoices& c
             for (int q = 0; q < n; q++) RTRY(stage_put(h, c.w_inst_valid + list[q], zeros.data(), sizeof(int)));
         }
     }
-    if (!list || h->wobst_all) RTRY(stage_put(h, h->d_wobst, h->wobst.data(), sizeof(int) * h->wobst.size()));
-    h->wobst_all = false;
+    if (!list || whole_wobst) RTRY(stage_put(h, h->d_wobst, h->wobst.data(), sizeof(int) * h->wobst.size()));  // (every slice moved: the whole table)
     if (!list) {
         RTRY(stage_put(h, h->d_world_epoch, h->world_epoch.data(), sizeof(int) * h->W));
     } else {  // only the listed worlds' entries: the device-side auto-reset keeps the others' up to date itself
@@ -2280,114 +2183,148 @@ static int reset_launch(imgenv* h, const int* list, int n, const ResetChoices& c
         }
     }
     if (list) RTRY(stage_put(h, h->d_act_list, list, sizeof(int) * n));  // for the launches after k_reset_apply
-    const size_t n_inst = h->oinst.size();
-    if (n_inst > h->cap_oinst) {
-        h->cap_oinst = n_inst * 2;
-        unsigned char* raw = nullptr;
-        RTRY(dev_alloc(h, &raw, h->cap_oinst * sizeof(ObstInst)));
-        h->d_oinst = raw;
+    return 0;
+}
+// the obstacle instances of every prepared world, back to back: one segment
+static int reset_stage_obstacles(imgenv* h, int n, size_t* n_inst_out) {
+    imgenv::ResetStage& s = h->rs;
+    size_t n_inst = 0;
+    for (int q = 0; q < n; q++) n_inst += s.worlds[q].inst.size();
+    if (n_inst > s.cap_inst) {
+        RTRY(dev_alloc(h, &s.d_inst, n_inst * 2));
+        s.cap_inst = n_inst * 2;
     }
-    static_assert(sizeof(imgenv::ObstInstHost) == sizeof(ObstInst), "layout");
-    if (n_inst) RTRY(stage_put(h, h->d_oinst, h->oinst.data(), n_inst * sizeof(ObstInst)));
-    h->oinst.clear();
-    set_active(h, list ? h->d_act_list : nullptr, n);
-    const ResetPlan rp = plan_reset(h->plan, chain_facts(h, 1), h->segs.size(), h->seg_max, n_inst);
-    {   // one launch: segment copies | map restore | robot state | pedestrian state
-        ResetArgs a;
-        unsigned char* table = nullptr;
-        RTRY(stage_room(h, std::max<size_t>(h->segs.size(), 1) * sizeof(StageSeg), &table));
-        memcpy(table, h->segs.data(), h->segs.size() * sizeof(StageSeg));
-        a.table = (const StageSeg*)table;
-        a.n_seg = (int)h->segs.size();
-        a.per_seg = rp.per_seg;
-        a.list = h->pin_list;
-        a.n_worlds = d.act_nw;
-        a.static_map = h->d_static_map;
-        a.maps = map_sel(h);
-        if (h->d_map_cur && choices.map_ids) {
-            unsigned char* ids = nullptr;
-            RTRY(stage_room(h, sizeof(int) * (size_t)d.act_nw, &ids));
-            memcpy(ids, choices.map_ids, sizeof(int) * (size_t)d.act_nw);
-            a.maps.ids = (const int*)ids;
-        }
-        a.rob3 = h->pin_rob3;
-        a.rr = (const ResetRobot*)h->pin_rr;
-        a.ped3 = h->pin_ped3;
-        a.n_robots = d.act_ng;
-        a.n_peds = d.act_np;
-        a.whole = whole;
-        a.stamp = h->plan.layer;
-        k_reset_apply<<<dim3(rp.apply.grid), dim3(rp.apply.block), 0, st>>>(d, a);
-        h->segs.clear();
-        h->seg_max = 0;
+    ObstInst* at = nullptr;
+    if (n_inst) RTRY(stage_seg(h, s.d_inst, n_inst, &at));
+    for (int q = 0; q < n && n_inst; at += s.worlds[q].inst.size(), q++) std::copy(s.worlds[q].inst.begin(), s.worlds[q].inst.end(), at);
+    *n_inst_out = n_inst;
+    return 0;
+}
+// one launch: segment copies | map restore | robot state | pedestrian state
+static int reset_apply(imgenv* h, const ResetPlan& rp, const ResetChoices& choices, hipStream_t st, int whole) {
+    imgenv::ResetStage& s = h->rs;
+    const DevWorld& d = h->d;
+    ResetArgs a;
+    unsigned char* table = nullptr;
+    RTRY(stage_room(h, std::max<size_t>(s.segs.size(), 1) * sizeof(StageSeg), &table));
+    memcpy(table, s.segs.data(), s.segs.size() * sizeof(StageSeg));
+    a.table = (const StageSeg*)table;
+    a.n_seg = (int)s.segs.size();
+    a.per_seg = rp.per_seg;
+    a.list = s.list;
+    a.n_worlds = d.act_nw;
+    a.static_map = h->d_static_map;
+    a.maps = map_sel(h);
+    if (h->d_map_cur && choices.map_ids) {
+        int* ids = nullptr;
+        RTRY(stage_ints(h, choices.map_ids, (size_t)d.act_nw, &ids));
+        a.maps.ids = ids;
     }
-    if (n_inst)
-        k_reset_obstacles_for(h->plan)<<<dim3(rp.obstacles.grid), dim3(rp.obstacles.block), 0, st>>>(d, (const ObstInst*)h->d_oinst, h->plan.layer, nullptr, 0, 1, nullptr, nullptr);
-    if (d.sharded) k_reset_bbox<<<dim3(rp.bbox.grid), dim3(rp.bbox.block), 0, st>>>(d, h->pin_rob3);
-    const int n_fed = (int)h->trk_fed.size();
-    if (n_fed > 0) {  // the worlds whose batch brought no tracks take their set of the bank: behind the staged copies, in front of the rasters
-        unsigned char* pl = nullptr;
-        RTRY(stage_room(h, sizeof(int) * 2 * (size_t)n_fed, &pl));
-        int* fed_list = (int*)pl;
-        memcpy(fed_list, h->trk_fed.data(), sizeof(int) * (size_t)n_fed);
-        memcpy(fed_list + n_fed, h->trk_fed_ids.data(), sizeof(int) * (size_t)n_fed);
-        const TracksPlan tp = plan_tracks_install(h->plan, n_fed, false, 0, h->trk_cap);
-        k_tracks_install<<<dim3(tp.install.grid), dim3(tp.install.block), 0, st>>>(d, track_sel(h), fed_list, nullptr, n_fed, fed_list + n_fed, nullptr, nullptr,
-                                                                                 0ull, h->d_traj, h->d_traj_v, h->d_traj_len, h->traj_cap);
-        h->trk_fed.clear();
-        h->trk_fed_ids.clear();
-    }
-    if (h->d_scn_world) {  // a handle with a scenario bank: what imgenv_world_scenarios answers for the worlds of this reset
-        const int n_mark = list ? n : h->W;
-        const int* ids = nullptr;
-        if (choices.scn_ids) {
-            unsigned char* pi = nullptr;
-            RTRY(stage_room(h, sizeof(int) * (size_t)n_mark, &pi));
-            memcpy(pi, choices.scn_ids, sizeof(int) * (size_t)n_mark);
-            ids = (const int*)pi;
-        }
-        k_scenario_mark<<<dim3((unsigned)((n_mark + 255) / 256)), dim3(256), 0, st>>>(h->d_scn_world, h->d_scn_mark,
-                                                                                      h->sd_ready ? ((SpawnDev*)h->sd_storage)->place_serial : nullptr,
-                                                                                      list ? h->pin_list : nullptr, ids, n_mark);
-    }
-    HIPCHK(hipGetLastError());
-    h->launches = 2 + (n_fed > 0 ? 1 : 0) + (h->d_scn_world ? 1 : 0);
-    const int rc = launch_views(h, st, 1);
+    a.rob3 = s.rob3;
+    a.rr = s.rr;
+    a.ped3 = s.ped3;
+    a.n_robots = d.act_ng;
+    a.n_peds = d.act_np;
+    a.whole = whole;
+    a.stamp = h->plan.layer;
+    k_reset_apply<<<dim3(rp.apply.grid), dim3(rp.apply.block), 0, st>>>(d, a);
+    s.segs.clear();
+    s.seg_max = 0;
+    return 0;
+}
+// the worlds whose batch brought no tracks take their set of the bank: behind the staged copies, in front of the rasters
+static int reset_tracks(imgenv* h, hipStream_t st) {
+    imgenv::ResetStage& s = h->rs;
+    const int n_fed = (int)s.fed.size();
+    s.fed.insert(s.fed.end(), s.fed_ids.begin(), s.fed_ids.end());  // [worlds | ids]
+    int* fed_list = nullptr;
+    RTRY(stage_ints(h, s.fed.data(), s.fed.size(), &fed_list));
+    const TracksPlan tp = plan_tracks_install(h->plan, n_fed, false, 0, h->trk_cap);
+    k_tracks_install<<<dim3(tp.install.grid), dim3(tp.install.block), 0, st>>>(h->d, track_sel(h), fed_list, nullptr, n_fed, fed_list + n_fed, nullptr, nullptr,
+                                                                             0ull, h->d_traj, h->d_traj_v, h->d_traj_len, h->traj_cap);
+    s.fed.clear();
+    s.fed_ids.clear();
+    return 0;
+}
+// a handle with a scenario bank: what imgenv_world_scenarios answers for the worlds of this reset
+static int reset_scenario_mark(imgenv* h, const int* list, int n, const ResetChoices& choices, hipStream_t st) {
+    const int n_mark = list ? n : h->W;
+    int* ids = nullptr;
+    if (choices.scn_ids) RTRY(stage_ints(h, choices.scn_ids, (size_t)n_mark, &ids));
+    k_scenario_mark<<<dim3((unsigned)((n_mark + 255) / 256)), dim3(256), 0, st>>>(h->d_scn_world, h->d_scn_mark, h->dev.ready ? h->dev.pool.place_serial : nullptr,
+                                                                                  list ? h->rs.list : nullptr, ids, n_mark);
+    return 0;
+}
+// The one bracket of a reset chain: while `body` runs, the handle's launches cover the listed worlds (a device pointer; n_dev: the
+// list's length lives on the device and n is its capacity), afterwards every world again -- however body ends.
+template <typename Body>
+static int with_active(imgenv* h, const int* list, int n, const int* n_dev, Body&& body) {
+    set_active(h, list, n);
+    h->d.act_n_dev = n_dev;
+    const int rc = body();
     set_active(h, nullptr, 0);
+    h->d.act_n_dev = nullptr;
+    return rc;
+}
+
+static int sfm_ahead_drop(imgenv* h, hipStream_t st);
+// commit, 5: the launches
+static int reset_launch(imgenv* h, const int* list, int n, bool whole_wobst, const ResetChoices& choices, hipStream_t st, int whole) {
+    if (int rc = sfm_ahead_drop(h, st)) return rc;  // (a reset writes the live crowd: positions, waypoints)
+    RTRY(reset_stage_tables(h, list, n, whole_wobst));
+    size_t n_inst = 0;
+    RTRY(reset_stage_obstacles(h, list ? n : h->W, &n_inst));
+    const int rc = with_active(h, list ? h->d_act_list : nullptr, n, nullptr, [&]() -> int {
+        const DevWorld& d = h->d;
+        const ResetPlan rp = plan_reset(h->plan, chain_facts(h, 1), h->rs.segs.size(), h->rs.seg_max, n_inst);
+        RTRY(reset_apply(h, rp, choices, st, whole));
+        if (n_inst)
+            k_reset_obstacles_for(h->plan)<<<dim3(rp.obstacles.grid), dim3(rp.obstacles.block), 0, st>>>(d, h->rs.d_inst, h->plan.layer, nullptr, 0, 1, nullptr, nullptr);
+        if (d.sharded) k_reset_bbox<<<dim3(rp.bbox.grid), dim3(rp.bbox.block), 0, st>>>(d, h->rs.rob3);
+        const bool fed = !h->rs.fed.empty();
+        if (fed) RTRY(reset_tracks(h, st));
+        if (h->d_scn_world) RTRY(reset_scenario_mark(h, list, n, choices, st));
+        HIPCHK(hipGetLastError());
+        h->launches = 2 + (fed ? 1 : 0) + (h->d_scn_world ? 1 : 0);
+        return launch_views(h, st, 1);
+    });
     // k_reset_apply is in flight and reads this generation's page-locked chunks: mark them pending whatever came after
     const int rc_end = stage_end(h, st);
     return rc ? rc : rc_end;
 }
+// commit: the n prepared worlds (list == nullptr: every world, world k from its share of the one batch)
+static int reset_commit(imgenv* h, const ResetFacts& f, int n, const int32_t* list, const imgenv_reset_batch* batches, const ResetChoices& choices,
+                        hipStream_t st, double* stage_us) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const ResetGrowth g = reset_growth(f, h->rs.worlds.data(), n);
+    RTRY(reset_grow(h, g, st));
+    RTRY(stage_rvo(h, list, n, g));
+    for (int q = 0; q < n; q++) {
+        const imgenv_reset_batch sub = list ? batches[q] : world_batch(h, batches, q);
+        RTRY(stage_world(h, f, h->rs.worlds[q], q, &sub, choices, list ? h->elapsed : 0));
+    }
+    if (!list) {
+        if (h->d.sharded) {
+            const uint32_t init[4] = {BBOX_INIT_MIN, BBOX_INIT_MIN, BBOX_INIT_MAX, BBOX_INIT_MAX};
+            RTRY(stage_put(h, h->d.bbox, init, sizeof(init)));
+        }
+        h->elapsed = 0;  // TimeLimitWrapper.reset (base.py:229-231)
+        h->dev.used = false;  // every world's host copy is current again
+    }
+    if (stage_us) *stage_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    return reset_launch(h, list, list ? n : 0, g.rvo_moved, choices, st, list ? 0 : 1);  // no host wait: the copies read the handle's pinned chunks
+}
 
 // every world of the handle from one batch; `choices` hold one entry per world (a handle of one world: what its host-placed reset drew)
 static int reset_all(imgenv* h, const imgenv_reset_batch* b, const ResetChoices& choices, hipStream_t st) {
-    if (int rc = reset_checks(h, 1, b, h ? h->P : 0)) return rc;
-    if (int rc = outputs_verify(h, st)) return rc;
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    const ResetFacts f = reset_facts(h);
+    RTRY(reset_check_batches(f, 1, b, h->P, g_err));
+    RTRY(reset_prepare(h, f, h->W, nullptr, b));
+    RTRY(reset_device_ready(h, st));
     RTRY(stage_begin(h));
     RTRY(reset_blocks(h, h->W, nullptr));
-    h->oinst.clear();
-    for (int k = 0; k < h->W; k++) {
-        imgenv_reset_batch sub = *b;  // world k's robots and pedestrians (world-major numbering); one obstacle list for all
-        sub.robot_pose = b->robot_pose + (size_t)4 * k * h->Rw;
-        sub.robot_goal = b->robot_goal + (size_t)2 * k * h->Rw;
-        if (h->P > 0) {
-            sub.ped_pose = b->ped_pose ? b->ped_pose + (size_t)4 * k * h->Pw : nullptr;  // (null: a bank-fed batch, reset_checks)
-            sub.ped_goal = b->ped_goal ? b->ped_goal + (size_t)2 * k * h->Pw : nullptr;
-            sub.ped_traj_len = b->ped_traj_len ? b->ped_traj_len + (size_t)k * h->Pw : nullptr;
-            sub.ped_traj = b->ped_traj ? b->ped_traj + (size_t)k * h->Pw * b->ped_traj_cap * 3 : nullptr;
-            sub.ped_traj_v = b->ped_traj_v ? b->ped_traj_v + (size_t)k * h->Pw * b->ped_traj_cap * 2 : nullptr;
-        }
-        RTRY(stage_world(h, k, k, &sub, choices, st));
-        h->world_epoch[k] = 0;
-        h->world_ready[k] = 1;
-    }
-    if (h->d.sharded) {
-        const uint32_t init[4] = {BBOX_INIT_MIN, BBOX_INIT_MIN, BBOX_INIT_MAX, BBOX_INIT_MAX};
-        RTRY(stage_put(h, h->d.bbox, init, sizeof(init)));
-    }
-    h->elapsed = 0;  // TimeLimitWrapper.reset (base.py:229-231)
-    h->dev_reset_used = false;  // every world's host copy is current again
-    RTRY(reset_launch(h, nullptr, 0, choices, st, 1));  // no host wait: the copies read the handle's pinned chunks
+    RTRY(reset_commit(h, f, h->W, nullptr, b, choices, st, nullptr));
     h->has_reset = true;
     return IMGENV_OK;
 }
@@ -2397,35 +2334,29 @@ extern "C" int imgenv_reset(imgenv_t* h, const imgenv_reset_batch* b, void* stre
 // the listed worlds, each from its batch; `choices` in list order
 static int reset_worlds(imgenv* h, int n, const int32_t* worlds, const imgenv_reset_batch* batches, const ResetChoices& choices, hipStream_t st) {
     if (n <= 0) return h ? IMGENV_OK : IMGENV_EINVAL;
-    if (!worlds) FAIL(IMGENV_EINVAL, "null argument");
-    if (int rc = reset_checks(h, n, batches, h ? h->Pw : 0)) return rc;
+    if (!h || !worlds) FAIL(IMGENV_EINVAL, "null argument");
+    const ResetFacts f = reset_facts(h);
+    RTRY(reset_check_batches(f, n, batches, h->Pw, g_err));
     if (!world_list_check(h->W, n, worlds, nullptr, 0, nullptr, &g_err)) return IMGENV_EINVAL;
     if (h->W == 1) return reset_all(h, batches, choices, st);  // (the list is {0}: one entry of every choice)
-    if (int rc = outputs_verify(h, st)) return rc;
-    static const bool trace = getenv("IMGENV_TRACE_RESET") != nullptr;
-    std::chrono::steady_clock::time_point tp[4];
-    if (trace) tp[0] = std::chrono::steady_clock::now();
+    const bool trace = imgenv::ResetTrace::on();
+    double us[3] = {0, 0, 0}, t[3] = {0, 0, 0};  // begin, stage worlds (prepare included), launches
+    if (trace) t[0] = imgenv::ResetTrace::now_us();
+    RTRY(reset_prepare(h, f, n, worlds, batches));
+    if (trace) t[1] = imgenv::ResetTrace::now_us();
+    RTRY(reset_device_ready(h, st));
     RTRY(stage_begin(h));
     RTRY(reset_blocks(h, n, worlds));
-    h->oinst.clear();
-    if (trace) tp[1] = std::chrono::steady_clock::now();
-    for (int q = 0; q < n; q++) {
-        RTRY(stage_world(h, worlds[q], q, batches + q, choices, st));
-        h->world_epoch[worlds[q]] = h->elapsed;  // its TimeLimitWrapper starts over
-        h->world_ready[worlds[q]] = 1;
-    }
-    if (trace) tp[2] = std::chrono::steady_clock::now();
-    RTRY(reset_launch(h, worlds, n, choices, st, 0));
+    if (trace) t[2] = imgenv::ResetTrace::now_us();
+    RTRY(reset_commit(h, f, n, worlds, batches, choices, st, &us[1]));
     if (trace) {
-        tp[3] = std::chrono::steady_clock::now();
-        auto us = [&](int a_, int b_) { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(tp[b_] - tp[a_]).count() * 1e-3; };
-        static double acc[3] = {0, 0, 0};
-        static long calls = 0, worlds_n = 0;
-        acc[0] += us(0, 1); acc[1] += us(1, 2); acc[2] += us(2, 3);
-        calls++; worlds_n += n;
-        if (calls % 200 == 0)
+        us[0] = t[2] - t[1];
+        us[2] = imgenv::ResetTrace::now_us() - t[2] - us[1];
+        us[1] += t[1] - t[0];
+        imgenv::ResetTrace& tr = h->rs.trace;
+        if (tr.add(us, 3, n))
             fprintf(stderr, "[imgenv_reset_worlds] %ld calls, %.1f worlds/call: begin %.1f us, stage worlds %.1f us, launches %.1f us per call\n",
-                    calls, (double)worlds_n / calls, acc[0] / calls, acc[1] / calls, acc[2] / calls);
+                    tr.calls, (double)tr.worlds / tr.calls, tr.acc[0] / tr.calls, tr.acc[1] / tr.calls, tr.acc[2] / tr.calls);
     }
     bool all = true;
     for (char r : h->world_ready) all = all && r;
@@ -2701,16 +2632,12 @@ extern "C" int32_t imgenv_scenario_for_placement(int32_t policy, uint64_t seed0,
     return scenario_for_placement(policy, seed0, first, n, n_scenarios);
 }
 
-// RVO obstacle vertices / BSP nodes a pool slot of the device-side reset has room for, whatever the handle's own tables hold
-// (spawn_device_setup only ever raises it to the handle's capacity)
-static int spawn_slot_cap(int nob) { return std::max(16, std::min(SPAWN_BSP_CAP, 16 * std::max(nob, 1))); }
-
 extern "C" int imgenv_scenarios_add(imgenv_t* h, int32_t n, int32_t n_obstacles, const double* robot_pose, const double* robot_goal,
                                     const double* ped_pose, const double* ped_goal, const double* ped_traj, const int32_t* ped_traj_len,
                                     const int32_t* obs_shape, const float* obs_size, const double* obs_pose) {
     if (!h || !robot_pose || !robot_goal) FAIL(IMGENV_EINVAL, "null argument");
     if (h->n_scn > 0) FAIL(IMGENV_ESTATE, "imgenv_scenarios_add has already been called on this handle");
-    if (h->sd_ready) FAIL(IMGENV_ESTATE, "imgenv_scenarios_add after the first imgenv_step_autoreset_device");
+    if (h->dev.ready) FAIL(IMGENV_ESTATE, "imgenv_scenarios_add after the first imgenv_step_autoreset_device");
     if (h->RL != h->R) FAIL(IMGENV_EINVAL, "imgenv_scenarios_add on a robot shard is not supported");
     const int Rw = h->Rw, Pw = h->Pw, na = Rw + Pw, O = n_obstacles;
     if (n < 1 || n > (1 << 24)) FAIL(IMGENV_EINVAL, "imgenv_scenarios_add: %d scenarios", n);
@@ -2739,10 +2666,9 @@ extern "C" int imgenv_scenarios_add(imgenv_t* h, int32_t n, int32_t n_obstacles,
                 const SlotObstacle& o = obst[(size_t)s * O + q];
                 const double sizes[4] = {(double)o.size[0], (double)o.size[1], (double)o.size[2], (double)o.size[3]};
                 const double yaw = tf_yaw_from_quaternion_zw(o.qz, o.qw);
-                const Tf2 bw = tf_from_pose_sc(o.x, o.y, sin(yaw * 0.5), cos(yaw * 0.5));
-                double pax, pay, pbx, pby;
-                get_corners(o.shape, sizes, bw, pax, pay, pbx, pby);
-                const float v[8] = {(float)pax, (float)pay, (float)pax, (float)pby, (float)pbx, (float)pby, (float)pbx, (float)pay};
+                double seg[4];
+                float v[8];
+                obstacle_polygon(o.shape, sizes, o.x, o.y, sin(yaw * 0.5), cos(yaw * 0.5), seg, v);
                 rvo.add(v, 4);
             }
             rvo.process();
@@ -2785,13 +2711,13 @@ extern "C" int imgenv_scenarios_policy(imgenv_t* h, int32_t policy, uint64_t fir
         FAIL(IMGENV_EINVAL, "unknown scenario policy %d", policy);
     if (h->n_scn < 1) FAIL(IMGENV_ESTATE, "imgenv_scenarios_policy: the handle has no scenario bank (imgenv_scenarios_add)");
     hipStream_t st = (hipStream_t)stream;
-    if (h->sd_ready) {
+    if (h->dev.ready) {
         // The pool's slots were drawn under the old policy and must not be handed out: every slot loses its serial on the caller's
         // stream and the next chain's fill -- forced, behind this on the chain's event -- draws them again (spawn_dev_refresh's
         // stride path does the same).  The placements from the device's present count on belong to the new policy: the count is
         // copied on the device, for imgenv_world_scenarios.  Nothing here waits for the device.
         HIPCHK(hipSetDevice(h->cfg.device));
-        SpawnDev& c = *(SpawnDev*)h->sd_storage;
+        SpawnDev& c = h->dev.pool;
         if (h->scn_epochs.size() >= h->scn_starts_cap) {  // (every 256th switch and rarer: the log doubles; the old block lives until imgenv_destroy)
             unsigned long long* grown = nullptr;
             RTRY(dev_alloc(h, &grown, h->scn_starts_cap * 2));
@@ -2802,7 +2728,7 @@ extern "C" int imgenv_scenarios_policy(imgenv_t* h, int32_t policy, uint64_t fir
         HIPCHK(hipMemcpyAsync(h->d_scn_starts + h->scn_epochs.size(), c.consumed, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
         h->scn_epochs.push_back(imgenv::ScnEpoch{policy, first});
         HIPCHK(hipMemsetAsync(c.slot_serial, 0xFF, sizeof(unsigned long long) * (size_t)c.S, st));
-        h->fill_due = 0;
+        h->dev.fill_due = 0;
     } else {  // no pool yet: its first fill takes the policy, from placement 0
         h->scn_epochs.assign(1, imgenv::ScnEpoch{policy, first});
     }
@@ -2851,7 +2777,7 @@ static int scenario_starts_pull(const imgenv* h, std::vector<unsigned long long>
 // ... and the placement under the policy of the epoch it falls into
 static int32_t scenario_of_placement(const imgenv* h, const std::vector<unsigned long long>& starts, uint64_t serial) {
     const imgenv::ScnEpoch& e = h->scn_epochs[scenario_epoch_of(starts.data(), starts.size(), serial)];
-    const uint64_t seed0 = h->sd_ready ? ((const SpawnDev*)h->sd_storage)->seed0 : 0;
+    const uint64_t seed0 = h->dev.ready ? h->dev.pool.seed0 : 0;
     return scenario_for_placement(e.policy, seed0, e.first, serial, h->n_scn);
 }
 
@@ -2868,8 +2794,8 @@ extern "C" int imgenv_world_scenarios(imgenv_t* h, int32_t* ids, void* stream) {
     HIPCHK(hipMemcpy(scn.data(), h->d_scn_world, sizeof(int) * W, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(mark.data(), h->d_scn_mark, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost));
     RTRY(scenario_starts_pull(h, starts));
-    if (h->sd_ready)
-        HIPCHK(hipMemcpy(serial.data(), ((const SpawnDev*)h->sd_storage)->place_serial, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost));
+    if (h->dev.ready)
+        HIPCHK(hipMemcpy(serial.data(), h->dev.pool.place_serial, sizeof(unsigned long long) * W, hipMemcpyDeviceToHost));
     for (size_t k = 0; k < W; k++)  // (equal: the host reset it last, or nobody has)
         ids[k] = serial[k] == mark[k] ? scn[k] : scenario_of_placement(h, starts, serial[k]);
     return IMGENV_OK;
@@ -3112,11 +3038,9 @@ extern "C" int imgenv_step_autoreset(imgenv_t* h, const float* actions, const im
     if (!n_out) FAIL(IMGENV_EINVAL, "null argument");
     if (int rc = autoreset_checks(h, actions, cfg, "imgenv_step_autoreset")) return rc;
     *n_out = 0;
-    static const bool trace = getenv("IMGENV_TRACE_RESET") != nullptr;  // where the host's time goes, every 200 calls
-    double* acc = h->trace_acc;
-    long &calls = h->trace_calls, &resets = h->trace_resets;
-    std::chrono::steady_clock::time_point tp[5];
-    if (trace) tp[0] = std::chrono::steady_clock::now();
+    const bool trace = imgenv::ResetTrace::on();  // where the host's time goes, every 200 calls
+    double tp[5] = {0, 0, 0, 0, 0};
+    if (trace) tp[0] = imgenv::ResetTrace::now_us();
     if (int rc = imgenv_step(h, actions, stream)) return rc;
     hipStream_t st = (hipStream_t)stream;
     k_finished<<<dim3(1), dim3(1024), 0, st>>>(h->d);
@@ -3135,9 +3059,9 @@ extern "C" int imgenv_step_autoreset(imgenv_t* h, const float* actions, const im
             if (spawn_world(*cfg, seed0 + (uint64_t)q, *slot)) slot->batch.struct_size = 0;  // could not be placed: reported if used
         }
     }
-    if (trace) tp[1] = std::chrono::steady_clock::now();
+    if (trace) tp[1] = imgenv::ResetTrace::now_us();
     HIPCHK(hipStreamSynchronize(st));  // NeverStopWrapper reads the dones here too (base.py:205)
-    if (trace) tp[2] = std::chrono::steady_clock::now();
+    if (trace) tp[2] = imgenv::ResetTrace::now_us();
     const int n = h->finished_host[0];
     if (n < 0 || n > h->W) FAIL(IMGENV_EDEVICE, "finished-world list is corrupt (%d)", n);
     int rc = IMGENV_OK;
@@ -3164,7 +3088,7 @@ extern "C" int imgenv_step_autoreset(imgenv_t* h, const float* actions, const im
         std::vector<imgenv_reset_batch> batches((size_t)n);
         for (int q = 0; q < n; q++) batches[q] = use[q]->batch;
         h->spawn_ahead_n = std::min(256, std::max(8, 2 * n));  // twice what this step needed
-        if (trace) tp[3] = std::chrono::steady_clock::now();
+        if (trace) tp[3] = imgenv::ResetTrace::now_us();
         const PlacementDraws draws = placement_draws(h, n, nullptr, seed0);  // the placement's seed also draws the map and the recorded crowd
         rc = reset_worlds(h, n, worlds.data(), batches.data(), draws.choices(), st);
         if (rc == IMGENV_OK) {
@@ -3173,17 +3097,16 @@ extern "C" int imgenv_step_autoreset(imgenv_t* h, const float* actions, const im
             for (int q = 0; q < n; q++) h->spawn_ahead.erase(seed0 + (uint64_t)q);  // consumed
         }
     } else if (trace) {
-        tp[3] = std::chrono::steady_clock::now();
+        tp[3] = imgenv::ResetTrace::now_us();
     }
     if (trace) {
-        tp[4] = std::chrono::steady_clock::now();
-        for (int q = 0; q < 4; q++) acc[q] += std::chrono::duration<double, std::micro>(tp[q + 1] - tp[q]).count();
-        resets += n;
-        if (++calls % 200 == 0) {
+        tp[4] = imgenv::ResetTrace::now_us();
+        const double us[4] = {tp[1] - tp[0], tp[2] - tp[1], tp[3] - tp[2], tp[4] - tp[3]};
+        imgenv::ResetTrace& tr = h->trace_autoreset;
+        if (tr.add(us, 4, n))
             fprintf(stderr, "[imgenv_step_autoreset] %ld calls, %.1f worlds reset/call: step launches + placements ahead %.1f us, wait for the device %.1f us, "
-                            "finished list %.1f us, reset launches %.1f us per call\n", calls, (double)resets / calls, acc[0] / calls, acc[1] / calls,
-                    acc[2] / calls, acc[3] / calls);
-        }
+                            "finished list %.1f us, reset launches %.1f us per call\n", tr.calls, (double)tr.worlds / tr.calls, tr.acc[0] / tr.calls,
+                    tr.acc[1] / tr.calls, tr.acc[2] / tr.calls, tr.acc[3] / tr.calls);
     }
     return rc;
 }
@@ -3198,50 +3121,71 @@ static int launch_pool_fill(imgenv* h, const SpawnDev& c) {
         ScenarioSel b;
         b.agents = h->d_scn_agents; b.obst = h->d_scn_obst;
         b.n = h->n_scn; b.policy = h->scn_policy; b.first = (unsigned long long)h->scn_first;
-        k_scenario_fill<<<dim3(c.S), dim3(WAVE), 0, h->side3>>>(c, b);
+        k_scenario_fill<<<dim3(c.S), dim3(WAVE), 0, h->dev.side3>>>(c, b);
     } else {
-        k_spawn_fill<<<dim3(c.S), dim3(WAVE), 0, h->side3>>>(c);
+        k_spawn_fill<<<dim3(c.S), dim3(WAVE), 0, h->dev.side3>>>(c);
     }
-    HIPCHK(hipEventRecord(h->ev_fill, h->side3));
-    h->fill_pending = true;
+    HIPCHK(hipEventRecord(h->dev.ev_fill, h->dev.side3));
+    h->dev.fill_pending = true;
     return 0;
 }
 
-static int spawn_device_setup(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t seed0, hipStream_t st) {
+// The device arrays a pool owns besides its three cfg uploads, in allocation order: `each` gets the pointer, its element count and
+// its fill byte.  Allocation and free both walk this list.
+template <typename Each>
+static int pool_arrays(SpawnDev& c, int W, Each&& each) {
+    const size_t S = (size_t)c.S, na = (size_t)std::max(c.n_robots + c.n_peds, 1), nob = (size_t)std::max(c.n_obstacles, 1), Wz = (size_t)W;
+    RTRY(each(c.slot_serial, S, 0xFF));
+    RTRY(each(c.consumed, (size_t)2, 0));
+    RTRY(each(c.slot_status, S, 0));
+    RTRY(each(c.s_agents, S * na, 0));
+    RTRY(each(c.s_obst, S * nob, 0));
+    RTRY(each(c.s_inst, S * nob, 0));
+    RTRY(each(c.s_rvo, S * c.cap_o, 0));
+    RTRY(each(c.s_nodes, S * c.cap_n, 0));
+    RTRY(each(c.s_rvo_n, S * 4, 0));
+    RTRY(each(c.s_seg, S * nob * 4, 0));
+    RTRY(each(c.fin_list, Wz, 0));
+    RTRY(each(c.fin_n, (size_t)1, 0));
+    RTRY(each(c.inst_out, Wz * nob, 0));
+    RTRY(each(c.place_agents, Wz * na, 0));
+    RTRY(each(c.place_obst, Wz * nob, 0));
+    RTRY(each(c.place_serial, Wz, 0xFF));
+    RTRY(each(c.w_inst, Wz * nob, 0));
+    RTRY(each(c.w_inst_valid, Wz, 0));
+    return 0;
+}
+// SpawnDev travels by value with every launch: its copies of the handle's pointers and strides are taken from the handle here,
+// at set-up and whenever a host-side reset has re-laid a table (spawn_dev_refresh)
+static void pool_aim(const imgenv* h, SpawnDev& c) {
+    c.world_epoch = h->d_world_epoch;
+    c.n_obst_w = h->d_wobst + 2 * (size_t)h->W;
+    c.oroot_w = h->d_wobst + 3 * (size_t)h->W;
+    c.w_obst = h->d_obst;
+    c.w_nodes = h->d_nodes;
+    c.traj = h->d_traj;
+    c.traj_len = h->d_traj_len;
+    c.traj_cap = h->traj_cap;
+}
+// another spawn cfg: the old pool goes (a curriculum that alternates cfgs would otherwise grow until imgenv_destroy)
+static int pool_free(imgenv* h, hipStream_t st) {
+    HIPCHK(hipStreamSynchronize(h->dev.side3));
+    HIPCHK(hipStreamSynchronize(st));
+    h->dev.ready = false;
+    h->dev.fill_pending = false;
+    SpawnDev o = h->dev.pool;
+    DevSpawnAgent* oa = (DevSpawnAgent*)o.agents; DevSpawnObstacle* oo = (DevSpawnObstacle*)o.obstacles; double* om = (double*)o.multi;
+    dev_free(h, oa); dev_free(h, oo); dev_free(h, om);
+    return pool_arrays(o, h->W, [&](auto*& p, size_t, int) { return dev_free(h, p), 0; });
+}
+// the spawn cfg as the kernels read it, and the pool's own arrays (spawn_pool_check has passed)
+static int pool_build(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t seed0) {
+    SpawnDev& c = h->dev.pool;
     const int na = cfg->n_robots + cfg->n_peds, nob = cfg->n_obstacles;
-    if (na > SPAWN_MAX_AGENTS || nob > SPAWN_MAX_OBST)
-        FAIL(IMGENV_EINVAL, "device-side auto-reset places at most %d agents and %d obstacles per world", SPAWN_MAX_AGENTS, SPAWN_MAX_OBST);
-    if (h->cfg.ped_scene_type == IMGENV_SCENE_DATASET && !h->d_trk_cur)  // (with a track bank the chain's k_tracks_install brings them)
-        FAIL(IMGENV_EINVAL, "device-side auto-reset: dataset scenes (recorded crowds come with the reset call) are reset by the host (imgenv_step_autoreset)");
-    const bool sfm = h->cfg.ped_scene_type == IMGENV_SCENE_PEDSIM && h->d.sfm.n > 0;
-    if (sfm && (h->W < 2 || !h->d.sfm.n_obs_w))
-        FAIL(IMGENV_EINVAL, "device-side auto-reset of a pedscene world needs a handle of several worlds (n_worlds > 1: the per-world crowd tables)");
-    if (sfm && !cfg->ignore_obstacle && nob > h->sfm_cap_obs)
-        FAIL(IMGENV_EINVAL, "device-side auto-reset: %d obstacles, a pedscene world of this handle has room for %d", nob, h->sfm_cap_obs);
-    if (h->Pw > 0 && (h->traj_cap < 2 || !h->d_traj)) FAIL(IMGENV_ESTATE, "device-side auto-reset: reset every world once first (trajectories of two points)");
-    if (!h->sd_storage) {
-        h->sd_storage = new SpawnDev();
-        h->sd_delete = [](void* p) { delete (SpawnDev*)p; };
-    }
-    SpawnDev& c = *(SpawnDev*)h->sd_storage;
-    const bool rebuilt = h->sd_ready;
-    if (h->sd_ready) {  // another spawn cfg: the old pool goes (a curriculum that alternates cfgs would otherwise grow until imgenv_destroy)
-        HIPCHK(hipStreamSynchronize(h->side3));
-        HIPCHK(hipStreamSynchronize(st));
-        h->sd_ready = false;
-        h->fill_pending = false;
-        SpawnDev o = c;
-        DevSpawnAgent* oa = (DevSpawnAgent*)o.agents; DevSpawnObstacle* oo = (DevSpawnObstacle*)o.obstacles; double* om = (double*)o.multi;
-        dev_free(h, oa); dev_free(h, oo); dev_free(h, om);
-        dev_free(h, o.slot_serial); dev_free(h, o.consumed); dev_free(h, o.slot_status); dev_free(h, o.s_agents); dev_free(h, o.s_obst);
-        dev_free(h, o.s_inst); dev_free(h, o.s_rvo); dev_free(h, o.s_nodes); dev_free(h, o.s_rvo_n); dev_free(h, o.s_seg);
-        dev_free(h, o.fin_list); dev_free(h, o.fin_n); dev_free(h, o.inst_out); dev_free(h, o.place_agents); dev_free(h, o.place_obst);
-        dev_free(h, o.place_serial); dev_free(h, o.w_inst); dev_free(h, o.w_inst_valid);
-    }
     memset(&c, 0, sizeof(c));
     c.n_robots = cfg->n_robots; c.n_peds = cfg->n_peds; c.n_obstacles = nob; c.go_back = cfg->go_back; c.ignore_obstacle = cfg->ignore_obstacle;
     c.rvo = h->NA > 0 ? 1 : 0;
-    c.sfm = sfm ? 1 : 0;
+    c.sfm = h->cfg.ped_scene_type == IMGENV_SCENE_PEDSIM && h->d.sfm.n > 0 ? 1 : 0;
     c.clearance = cfg->clearance; c.target_min_dist = cfg->target_min_dist; c.circle0 = cfg->circle_ranges[0]; c.circle1 = cfg->circle_ranges[1];
     std::vector<DevSpawnAgent> ag((size_t)(na ? na : 1));
     std::vector<double> multi;
@@ -3253,12 +3197,10 @@ static int spawn_device_setup(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t s
         memcpy(o.begin, g.begin, sizeof(o.begin));
         memcpy(o.target, g.target, sizeof(o.target));
         if (g.begin_type == IMGENV_POSE_RANGE_MULTI) {
-            if (g.n_begin_multi < 1 || !g.begin_multi) FAIL(IMGENV_EINVAL, "range_multi start without ranges");
             o.begin_multi = (int)(multi.size() / 6); o.n_begin_multi = g.n_begin_multi;
             multi.insert(multi.end(), g.begin_multi, g.begin_multi + 6 * (size_t)g.n_begin_multi);
         }
         if (g.target_type == IMGENV_POSE_RANGE_MULTI) {
-            if (g.n_target_multi < 1 || !g.target_multi) FAIL(IMGENV_EINVAL, "range_multi target without ranges");
             o.target_multi = (int)(multi.size() / 6); o.n_target_multi = g.n_target_multi;
             multi.insert(multi.end(), g.target_multi, g.target_multi + 6 * (size_t)g.n_target_multi);
         }
@@ -3273,30 +3215,16 @@ static int spawn_device_setup(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t s
     RTRY(dev_upload(h, &c.agents, ag));
     RTRY(dev_upload(h, &c.obstacles, ob));
     RTRY(dev_upload(h, &c.multi, multi));
-    const int W = h->W, S = (SPAWN_FILL_PERIOD + 2) * std::max(64, W);  // every world can need a placement in a single step; see SPAWN_FILL_PERIOD
-    c.S = S;
+    c.S = spawn_pool_slots(h->W);
     c.seed0 = seed0;
-    c.cap_o = std::max(16, std::min(SPAWN_BSP_CAP, 16 * std::max(nob, 1)));
-    c.cap_n = c.cap_o;
-    RTRY(dev_alloc(h, &c.slot_serial, (size_t)S, 0xFF));
-    RTRY(dev_alloc(h, &c.consumed, 2));
-    RTRY(dev_alloc(h, &c.slot_status, (size_t)S));
-    RTRY(dev_alloc(h, &c.s_agents, (size_t)S * (na ? na : 1)));
-    RTRY(dev_alloc(h, &c.s_obst, (size_t)S * (nob ? nob : 1)));
-    RTRY(dev_alloc(h, &c.s_inst, (size_t)S * (nob ? nob : 1)));
-    RTRY(dev_alloc(h, &c.s_rvo, (size_t)S * c.cap_o));
-    RTRY(dev_alloc(h, &c.s_nodes, (size_t)S * c.cap_n));
-    RTRY(dev_alloc(h, &c.s_rvo_n, (size_t)S * 4));
-    RTRY(dev_alloc(h, &c.s_seg, (size_t)S * (nob ? nob : 1) * 4));
-    RTRY(dev_alloc(h, &c.fin_list, (size_t)W));
-    RTRY(dev_alloc(h, &c.fin_n, 1));
-    RTRY(dev_alloc(h, &c.inst_out, (size_t)W * (nob ? nob : 1)));
-    RTRY(dev_alloc(h, &c.place_agents, (size_t)W * (na ? na : 1)));
-    RTRY(dev_alloc(h, &c.place_obst, (size_t)W * (nob ? nob : 1)));
-    RTRY(dev_alloc(h, &c.place_serial, (size_t)W, 0xFF));
-    RTRY(dev_alloc(h, &c.w_inst, (size_t)W * (nob ? nob : 1)));
-    RTRY(dev_alloc(h, &c.w_inst_valid, (size_t)W));
-    // the per-world RVO tables take over from the host's copies: room for any placement's polygons in every world
+    c.cap_o = c.cap_n = spawn_slot_cap(nob);
+    return pool_arrays(c, h->W, [&](auto*& p, size_t n, int fill) { return dev_alloc(h, &p, n, fill); });
+}
+// the per-world RVO tables take over from the host's copies: room for any placement's polygons in every world, and one stride for
+// the worlds' slices and the slots'
+static int pool_take_rvo(imgenv* h, hipStream_t st) {
+    SpawnDev& c = h->dev.pool;
+    const int W = h->W;
     if (h->NA > 0 && (h->cap_obst < c.cap_o || h->cap_nodes < c.cap_n)) {
         HIPCHK(hipStreamSynchronize(st));
         const int co = std::max(h->cap_obst, c.cap_o), cn = std::max(h->cap_nodes, c.cap_n);
@@ -3313,10 +3241,7 @@ static int spawn_device_setup(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t s
             if ((int)rq.ob.size() > co || (int)rq.nodes.size() > cn) FAIL(IMGENV_ESTATE, "world %d holds more RVO obstacle vertices than a placement can have", q);
             std::copy(rq.ob.begin(), rq.ob.end(), all_o.begin() + (size_t)q * co);
             std::copy(rq.nodes.begin(), rq.nodes.end(), all_n.begin() + (size_t)q * cn);
-            h->wobst[q] = q * co;
-            h->wobst[h->W + q] = q * cn;
-            h->wobst[2 * h->W + q] = (int)rq.ob.size();
-            h->wobst[3 * h->W + q] = rq.root;
+            rvo_table_put(h->wobst, W, q, co, cn, rq);
         }
         HIPCHK(hipMemcpy(no, all_o.data(), sizeof(RvoObstDev) * all_o.size(), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(nn, all_n.data(), sizeof(RvoNodeDev) * all_n.size(), hipMemcpyHostToDevice));
@@ -3326,53 +3251,54 @@ static int spawn_device_setup(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t s
         h->d_obst = no; h->d_nodes = nn; h->cap_obst = co; h->cap_nodes = cn;
         h->d.obst = no; h->d.onodes = nn;
     }
-    c.cap_o = h->NA > 0 ? h->cap_obst : c.cap_o;  // the worlds' slices and the slots' share one stride
-    c.cap_n = h->NA > 0 ? h->cap_nodes : c.cap_n;
     if (h->NA > 0) {  // (slot arrays were sized with the smaller capacity: again with the handle's)
+        c.cap_o = h->cap_obst;
+        c.cap_n = h->cap_nodes;
         dev_free(h, c.s_rvo);
         dev_free(h, c.s_nodes);
-        RTRY(dev_alloc(h, &c.s_rvo, (size_t)S * c.cap_o));
-        RTRY(dev_alloc(h, &c.s_nodes, (size_t)S * c.cap_n));
+        RTRY(dev_alloc(h, &c.s_rvo, (size_t)c.S * c.cap_o));
+        RTRY(dev_alloc(h, &c.s_nodes, (size_t)c.S * c.cap_n));
     }
-    c.world_epoch = h->d_world_epoch;
-    c.n_obst_w = h->d_wobst + 2 * (size_t)W;
-    c.oroot_w = h->d_wobst + 3 * (size_t)W;
-    c.w_obst = h->d_obst;
-    c.w_nodes = h->d_nodes;
-    c.traj = h->d_traj;
-    c.traj_len = h->d_traj_len;
-    c.traj_cap = h->traj_cap;
-    if (!h->side3) {
-        HIPCHK(hipStreamCreateWithFlags(&h->side3, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_fill, hipEventDisableTiming | hipEventDisableSystemFence));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_consumed, hipEventDisableTiming | hipEventDisableSystemFence));
+    return 0;
+}
+// check, free the old pool, build, take over the RVO tables, first fill
+static int spawn_device_setup(imgenv* h, const imgenv_spawn_cfg* cfg, uint64_t seed0, hipStream_t st) {
+    RTRY(spawn_pool_check(reset_facts(h), *cfg, g_err));
+    const bool rebuilt = h->dev.ready;
+    if (rebuilt) RTRY(pool_free(h, st));
+    RTRY(pool_build(h, cfg, seed0));
+    RTRY(pool_take_rvo(h, st));
+    pool_aim(h, h->dev.pool);
+    if (!h->dev.side3) {
+        HIPCHK(hipStreamCreateWithFlags(&h->dev.side3, hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&h->dev.ev_fill, hipEventDisableTiming | hipEventDisableSystemFence));
+        HIPCHK(hipEventCreateWithFlags(&h->dev.ev_consumed, hipEventDisableTiming | hipEventDisableSystemFence));
     }
     HIPCHK(hipStreamSynchronize(st));  // (set-up only: the uploads above were synchronous copies)
     if (h->n_scn > 0 && rebuilt) {  // a new pool numbers its placements from 0 again: one epoch of the present policy, and no world's
         h->scn_epochs.assign(1, imgenv::ScnEpoch{h->scn_policy, h->scn_first});  // placement number means anything any more
-        HIPCHK(hipMemset(h->d_scn_world, 0xFF, sizeof(int) * (size_t)W));
-        HIPCHK(hipMemset(h->d_scn_mark, 0xFF, sizeof(unsigned long long) * (size_t)W));
+        HIPCHK(hipMemset(h->d_scn_world, 0xFF, sizeof(int) * (size_t)h->W));
+        HIPCHK(hipMemset(h->d_scn_mark, 0xFF, sizeof(unsigned long long) * (size_t)h->W));
     }
-    RTRY(launch_pool_fill(h, c));  // (the next chain waits for this fill in front of its k_respawn, whatever fill_due says)
-    h->fill_due = 0;
-    h->d_place_serial = c.place_serial;
-    h->sd_ready = true;
+    RTRY(launch_pool_fill(h, h->dev.pool));  // (the next chain waits for this fill in front of its k_respawn, whatever fill_due says)
+    h->dev.fill_due = 0;
+    h->dev.ready = true;
     return 0;
 }
 
-// A host-side reset between two device-side steps may have re-laid the tables k_respawn writes into: stage_world grows the
-// trajectory table when a batch brings longer waypoint lists, put_world_rvo the per-world RVO slices (after imgenv_reset has
+// A host-side reset between two device-side steps may have re-laid the tables k_respawn writes into: reset_grow lays the
+// trajectory table out again when a batch brings longer waypoint lists, and the per-world RVO slices (after imgenv_reset has
 // handed them back to the host).  SpawnDev travels by value with every launch, so its copies of those pointers and strides are
 // simply taken from the handle again; a changed RVO stride also moves the pool's slot arrays (slots and worlds share one
 // stride), whose placements are then drawn again.
 static int spawn_dev_refresh(imgenv* h, hipStream_t st) {
-    SpawnDev& c = *(SpawnDev*)h->sd_storage;
+    SpawnDev& c = h->dev.pool;
     const bool stride = h->NA > 0 && (c.cap_o != h->cap_obst || c.cap_n != h->cap_nodes);
     const bool moved = c.traj != h->d_traj || c.traj_len != h->d_traj_len || c.traj_cap != h->traj_cap ||
                        (h->NA > 0 && (c.w_obst != h->d_obst || c.w_nodes != h->d_nodes));
     if (!stride && !moved) return 0;
     if (stride) {
-        HIPCHK(hipStreamSynchronize(h->side3));  // (a fill in flight writes the old slot arrays)
+        HIPCHK(hipStreamSynchronize(h->dev.side3));  // (a fill in flight writes the old slot arrays)
         HIPCHK(hipStreamSynchronize(st));
         c.cap_o = h->cap_obst;
         c.cap_n = h->cap_nodes;
@@ -3381,38 +3307,32 @@ static int spawn_dev_refresh(imgenv* h, hipStream_t st) {
         RTRY(dev_alloc(h, &c.s_rvo, (size_t)c.S * c.cap_o));
         RTRY(dev_alloc(h, &c.s_nodes, (size_t)c.S * c.cap_n));
         HIPCHK(hipMemsetAsync(c.slot_serial, 0xFF, sizeof(unsigned long long) * (size_t)c.S, st));  // every slot is drawn again (the chain's own fill, behind this on st's event)
-        h->fill_due = 0;
+        h->dev.fill_due = 0;
     }
-    c.w_obst = h->d_obst;
-    c.w_nodes = h->d_nodes;
-    c.n_obst_w = h->d_wobst + 2 * (size_t)h->W;
-    c.oroot_w = h->d_wobst + 3 * (size_t)h->W;
-    c.traj = h->d_traj;
-    c.traj_len = h->d_traj_len;
-    c.traj_cap = h->traj_cap;
+    pool_aim(h, c);
     return 0;
 }
 
 // one step + the reset of whatever it finished, everything queued on `st` and the handle's side streams (all joined again)
 static int autoreset_device_chain(imgenv* h, const float* actions, hipStream_t st) {
-    SpawnDev& c = *(SpawnDev*)h->sd_storage;
+    SpawnDev& c = h->dev.pool;
     DevWorld& d = h->d;
     const int W = h->W, nob = c.n_obstacles;
     // the pool, underneath the step: the slots whose placements earlier steps handed out -- on every SPAWN_FILL_PERIOD-th call
     // (two event operations and a launch less on the others: each costs the caller's stream a dependency bubble and the host a call)
-    const bool fill = h->fill_due <= 0;
+    const bool fill = h->dev.fill_due <= 0;
     if (fill) {
-        HIPCHK(hipEventRecord(h->ev_consumed, st));
-        HIPCHK(hipStreamWaitEvent(h->side3, h->ev_consumed, 0));
+        HIPCHK(hipEventRecord(h->dev.ev_consumed, st));
+        HIPCHK(hipStreamWaitEvent(h->dev.side3, h->dev.ev_consumed, 0));
         RTRY(launch_pool_fill(h, c));
-        h->fill_due = SPAWN_FILL_PERIOD;
+        h->dev.fill_due = SPAWN_FILL_PERIOD;
     }
-    h->fill_due -= 1;
+    h->dev.fill_due -= 1;
     if (int rc = imgenv_step(h, actions, st)) return rc;
     k_finished_dev<<<dim3(1), dim3(1024), 0, st>>>(d, c);
     // (also the set-up's fill, which runs on the side stream whatever this call's fill_due was: k_respawn must not meet half-drawn slots)
-    if (h->fill_pending) HIPCHK(hipStreamWaitEvent(st, h->ev_fill, 0));
-    h->fill_pending = false;
+    if (h->dev.fill_pending) HIPCHK(hipStreamWaitEvent(st, h->dev.ev_fill, 0));
+    h->dev.fill_pending = false;
     const MapSel maps = map_sel(h);
     k_respawn<<<dim3(W), dim3(WAVE), 0, st>>>(d, c, h->elapsed, maps);
     if (h->d_trk_cur) {  // recorded crowds: every placed world takes its set of the bank (over the sampler's pedestrians, as init_ped_dataset does)
@@ -3437,15 +3357,10 @@ static int autoreset_device_chain(imgenv* h, const float* actions, hipStream_t s
         if (h->stamp_seq % STAMP_TAGS == 0) k_cell_base<<<dim3(plan_compose_blocks(p, chain_facts(h, 1))), dim3(256), 0, st>>>(d);
     }
     // the launches behind: sized for every world, the list and its length read from device memory
-    set_active(h, c.fin_list, W);
-    d.act_n_dev = c.fin_n;
     d.ptraj = h->d_traj;
     d.traj_cap = h->traj_cap;
     h->launches += 4;
-    const int rc = launch_views(h, st, 1);
-    set_active(h, nullptr, 0);
-    d.act_n_dev = nullptr;
-    return rc;
+    return with_active(h, c.fin_list, W, c.fin_n, [&] { return launch_views(h, st, 1); });
 }
 
 extern "C" int imgenv_step_autoreset_device(imgenv_t* h, const float* actions, const imgenv_spawn_cfg* cfg, uint64_t seed0, void* stream) {
@@ -3461,15 +3376,15 @@ extern "C" int imgenv_step_autoreset_device(imgenv_t* h, const float* actions, c
         FAIL(IMGENV_EINVAL, "imgenv_step_autoreset_device: the spawn cfg has %d robots / %d pedestrians / %d obstacles, the scenario bank %d / %d / %d",
              cfg->n_robots, cfg->n_peds, cfg->n_obstacles, h->Rw, h->Pw, h->scn_obst);
     const uint64_t fp = spawn_cfg_fingerprint(*cfg);
-    if (!h->sd_ready || fp != h->sd_fp) {  // the first call fixes seed0: the k-th world reset from now on takes placement seed0 + k
+    if (!h->dev.ready || fp != h->dev.fp) {  // the first call fixes seed0: the k-th world reset from now on takes placement seed0 + k
         if (int rc = spawn_device_setup(h, cfg, seed0, st)) return rc;
-        h->sd_fp = fp;
+        h->dev.fp = fp;
     }
     if (int rc = spawn_dev_refresh(h, st)) return rc;
     if (!h->d_act_list) RTRY(dev_alloc(h, &h->d_act_list, (size_t)h->W));
-    h->act_hint = plan_act_hint(h->plan, h->finished_host[0]);  // (page-locked, written by k_finished_dev; stale by a step or two: a hint only)
+    h->dev.act_hint = plan_act_hint(h->plan, h->finished_host[0]);  // (page-locked, written by k_finished_dev; stale by a step or two: a hint only)
     const int rc = autoreset_device_chain(h, actions, st);
-    if (rc == IMGENV_OK) h->dev_reset_used = true;
+    if (rc == IMGENV_OK) h->dev.used = true;
     return rc;
 }
 
@@ -3477,10 +3392,10 @@ extern "C" int imgenv_step_autoreset_device(imgenv_t* h, const float* actions, c
 // reset, ascending (up to cap of them), their number, and the placement number the first of them took.
 extern "C" int imgenv_autoreset_last(imgenv_t* h, int32_t* worlds_out, int32_t cap, int32_t* n_out, uint64_t* first_placement, void* stream) {
     if (!h || !n_out) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->sd_ready) FAIL(IMGENV_ESTATE, "no imgenv_step_autoreset_device yet");
+    if (!h->dev.ready) FAIL(IMGENV_ESTATE, "no imgenv_step_autoreset_device yet");
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     if (int rc = check_device_flags(h)) return rc;
-    SpawnDev& c = *(SpawnDev*)h->sd_storage;
+    SpawnDev& c = h->dev.pool;
     const int n = h->finished_host[0];
     *n_out = n;
     for (int q = 0; q < n && worlds_out && q < cap; q++) worlds_out[q] = h->finished_host[1 + q];
@@ -3497,10 +3412,10 @@ extern "C" int imgenv_autoreset_last(imgenv_t* h, int32_t* worlds_out, int32_t c
 extern "C" int imgenv_world_placement(imgenv_t* h, int32_t world, uint64_t* placement, double* robot_pose, double* robot_goal, double* ped_pose,
                                       double* ped_goal, double* ped_traj, int32_t* ped_traj_len, int32_t* obs_shape, float* obs_size, double* obs_pose) {
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->sd_ready) FAIL(IMGENV_ESTATE, "no imgenv_step_autoreset_device yet");
+    if (!h->dev.ready) FAIL(IMGENV_ESTATE, "no imgenv_step_autoreset_device yet");
     if (world < 0 || world >= h->W) FAIL(IMGENV_EINVAL, "world out of range");
     HIPCHK(hipDeviceSynchronize());
-    SpawnDev& c = *(SpawnDev*)h->sd_storage;
+    SpawnDev& c = h->dev.pool;
     const int nr = c.n_robots, np = c.n_peds, na = nr + np, nob = c.n_obstacles;
     unsigned long long serial = 0;
     HIPCHK(hipMemcpy(&serial, c.place_serial + world, sizeof(serial), hipMemcpyDeviceToHost));
@@ -3765,7 +3680,7 @@ static void tail_episodes(imgenv* h, hipStream_t st, const ChainPlans& k) {
     if (k.is_reset && h->eplog_on) {
         EpisodeLogDev lg = h->eplog;
         lg.map_cur = h->d_map_cur; lg.trk_cur = h->d_trk_cur; lg.scn_world = h->d_scn_world; lg.scn_mark = h->d_scn_mark;
-        lg.place_serial = h->sd_ready ? h->d_place_serial : nullptr;
+        lg.place_serial = h->dev.ready ? h->dev.pool.place_serial : nullptr;
         const LaunchShape gl = plan_episode_log_launch();
         k_episode_log<<<dim3(gl.grid), dim3(gl.block), 0, st>>>(ed, lg);
         h->launches += 1;

@@ -42,7 +42,7 @@ MAP_BANK_HD static inline int32_t scenario_for_placement(int32_t policy, uint64_
 #define SCENARIO_BAD_QUATERNION 2  // qz = qw = 0
 #define SCENARIO_BAD_TRAJ_LEN 3    // ped_traj_len outside 0..2
 #define SCENARIO_BAD_SHAPE 4       // an obstacle that is neither a circle nor a rectangle
-#define SCENARIO_BAD_FOOTPRINT 5   // an obstacle whose footprint lattice is empty or beyond 2^26 samples (world_obstacles' bound)
+#define SCENARIO_BAD_FOOTPRINT 5   // an obstacle whose footprint lattice is empty or beyond 2^26 samples (obstacle_footprint_ok's bound)
 
 static inline const char* scenario_error_text(int code) {
     switch (code) {

@@ -18,61 +18,11 @@
 // imgenv_spawn_slot() reads a placement back for checkers.
 #pragma once
 
-#include "spawn_slot.h"  // SPAWN_MAX_AGENTS, SPAWN_MAX_OBST, SPAWN_BSP_CAP, SlotAgent, SlotObstacle (plain C++: the scenario bank's host half shares them)
+#include "spawn_slot.h"  // SPAWN_MAX_AGENTS, SPAWN_MAX_OBST, SPAWN_BSP_CAP, SPAWN_FILL_PERIOD, SlotAgent, SlotObstacle (plain C++: the scenario bank's host half shares them)
+#include "world.h"       // SpawnDev
 
 #define SPAWN_LIST_CAP 6144   // arena of the BSP's per-node vertex lists
 #define SPAWN_GUARD 200000    // draws before a placement is given up (the host gives up after 2e7: a kernel must not spin that long)
-#define SPAWN_FILL_PERIOD 2    // the pool is refilled on every second call; it holds 4 W placements: a refill sees the count of
-                              // two steps ago at worst, and up to W worlds can finish on each of the steps until the next one
-
-struct DevSpawnAgent {
-    int begin_type, target_type;
-    double begin[6], target[6];
-    double module_size;
-    int begin_multi, n_begin_multi, target_multi, n_target_multi;  // offsets (in boxes of 6 doubles) into SpawnDev::multi
-};
-struct DevSpawnObstacle {
-    int shape, pose_type;
-    double size_range[4];
-    double pose[6];
-};
-struct SpawnDev {
-    int n_robots, n_peds, n_obstacles, go_back, ignore_obstacle, rvo;  // rvo: the world has RVO agents (obstacle polygons + BSP wanted)
-    double clearance, target_min_dist, circle0, circle1;
-    const DevSpawnAgent* agents;
-    const DevSpawnObstacle* obstacles;
-    const double* multi;
-    int S;                             // pool slots
-    unsigned long long seed0;
-    unsigned long long* slot_serial;   // [S] placement number a slot holds, ~0 = none
-    unsigned long long* consumed;      // [0] placements handed out so far, [1] the same before this step's worlds took theirs
-    int* slot_status;                  // [S] 0 fine, else why the placement failed
-    SlotAgent* s_agents;               // [S][n_robots + n_peds]
-    SlotObstacle* s_obst;              // [S][n_obstacles]
-    ObstInst* s_inst;                  // [S][n_obstacles] (world unset)
-    RvoObstDev* s_rvo;                 // [S][cap_o]
-    RvoNodeDev* s_nodes;               // [S][cap_n]
-    int* s_rvo_n;                      // [S][4] obstacles, nodes, root
-    double* s_seg;                     // [S][n_obstacles][4] pedscene: the obstacles as PedScene::addObs takes them, a segment pa -> pb each (pedscene.h:24-30)
-    int sfm;                           // the worlds run libpedsim crowds
-    int cap_o, cap_n;
-    int* fin_list;                     // [W] finished worlds of this step, ascending
-    int* fin_n;                        // [1]
-    ObstInst* inst_out;                // [W][n_obstacles] instances of the worlds being reset, for k_reset_obstacles
-    SlotAgent* place_agents;           // [W][n_robots + n_peds] the placement each world currently runs (imgenv_world_placement)
-    SlotObstacle* place_obst;          // [W][n_obstacles]
-    unsigned long long* place_serial;  // [W] its number
-    ObstInst* w_inst;                  // [W][n_obstacles] the obstacles drawn on each world's map ...
-    int* w_inst_valid;                 // [W] ... where the device knows them (k_restore_maps_dev puts only their cells back)
-    int* world_epoch;                  // [W] (writable alias of DevWorld::world_epoch)
-    int* n_obst_w;                     // [W] writable aliases of the per-world RVO table
-    int* oroot_w;
-    RvoObstDev* w_obst;                // [W][cap_o]
-    RvoNodeDev* w_nodes;               // [W][cap_n]
-    double* traj;                      // [P][traj_cap][3]
-    int* traj_len;                     // [P]
-    int traj_cap;
-};
 
 struct DevRng {  // xoshiro256** seeded through splitmix64 (csrc/spawn_host.h SpawnRng)
     unsigned long long s[4];

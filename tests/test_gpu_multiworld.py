@@ -339,3 +339,126 @@ def test_pedscene_worlds_above_64_agents_use_the_spread_pair_terms(worlds):
     fails, _, _ = _run(World, OracleWorld, W=2, Rw=1, Pw=69, steps=5, resets={2: [1]}, seed=73, scene="pedscene", grid_size=88,
                        n_obstacles=2, relation_ped_robo=1, clearance=0.45)
     assert not fails, fails[:3]
+
+
+def _step_all(gpu, cpus, rng, Rw, Pw, steps, where, fails, extra=()):
+    """`steps` steps of the handle and of one oracle per world (`extra`: further oracles that get world 0's actions)"""
+    W = len(cpus)
+    for s in range(steps):
+        a = random_actions(rng, W * Rw)
+        gpu.step(a)
+        for k, c in enumerate(cpus):
+            c.step(a[k * Rw:(k + 1) * Rw])
+        for c in extra:
+            c.step(a[:Rw])
+        _compare_all(gpu, cpus, Rw, Pw, (where, s), fails)
+
+
+def _with_longer_trajectories(lay, rng, cap):
+    """`lay` with waypoint lists of up to `cap` points (the first pedestrian's is full)"""
+    Pw = len(lay.ped_pose)
+    traj = np.zeros((Pw, cap, 3))
+    lens = rng.integers(1, cap + 1, Pw).astype(np.int32)
+    lens[0] = cap
+    for j in range(Pw):
+        for q in range(lens[j]):
+            traj[j, q, :2] = lay.ped_pose[j, :2] + rng.uniform(-2.0, 2.0, 2)
+    lay.ped_traj, lay.ped_traj_len = traj, lens
+    return lay
+
+
+def test_refused_list_reset_leaves_the_handle_untouched(worlds):
+    """reset_worlds([0, 1], [A, B]) is refused because of B (a rectangle with reversed x-extent): nothing of A may stay behind in the
+    handle.  A later reset of world 2 outgrows the obstacle slices, so every world's slice is refilled from the host's copies -- were
+    world 0's copy A's by then, its pedestrians would avoid obstacles of a layout that was never applied.  A is world 0's own layout
+    plus a square on each pedestrian's way to its next waypoint, 0.6 m ahead; that an oracle which does get A's obstacles leaves
+    ped_state's bar within these steps is checked here, on the CPU."""
+    import copy
+    World, OracleWorld = worlds
+    from img_env_amd import _cabi
+    W, Rw, Pw = 3, 2, 3
+    grid, params, _ = small_world(Rw, Pw, seed=71)
+    lays = [small_world(Rw, Pw, seed=71 + 100 * k)[2] for k in range(W)]
+    A = copy.deepcopy(lays[0])
+    way = A.ped_traj[:, 0, :2] - A.ped_pose[:, :2]  # (the first waypoint of a pedestrian's list is where it walks to)
+    at = A.ped_pose[:, :2] + 0.6 * way / np.linalg.norm(way, axis=1, keepdims=True)
+    assert (np.linalg.norm(way, axis=1) > 1.0).all() and (np.linalg.norm(at - A.ped_pose[:, :2], axis=1) < 1.0).all()
+    A.obs_shape = np.full(Pw, _cabi.SHAPE_RECTANGLE, np.int32)
+    A.obs_size = np.tile(np.array([-0.15, 0.15, -0.15, 0.15], np.float32), (Pw, 1))
+    A.obs_pose = np.concatenate([at, np.tile([0.0, 1.0], (Pw, 1))], axis=1)
+    B = copy.deepcopy(lays[1])
+    B.obs_shape = np.array([_cabi.SHAPE_RECTANGLE], np.int32)
+    B.obs_size = np.array([[0.15, -0.15, -0.15, 0.15]], np.float32)
+    B.obs_pose = B.obs_pose[:1].copy()
+    gpu = World(_stack_params(params, W), grid)
+    cpus = [OracleWorld(params, grid) for _ in range(W)]
+    told = OracleWorld(params, grid)  # world 0 as it would be with A's obstacles
+    fails = []
+    try:
+        gpu.reset(lays)
+        for c, lay in zip(cpus, lays):
+            c.reset(lay)
+        told.reset(A)
+        _compare_all(gpu, cpus, Rw, Pw, "reset", fails)
+        with pytest.raises(RuntimeError, match="degenerate or oversized"):
+            gpu.reset_worlds([0, 1], [A, B])
+        rng = np.random.default_rng(71)
+        _step_all(gpu, cpus, rng, Rw, Pw, 1, "after the refusal", fails, extra=[told])
+        big = small_world(Rw, Pw, seed=979, n_obstacles=14)[2]
+        gpu.reset_world(2, big)
+        cpus[2].reset(big)
+        _compare_all(gpu, cpus, Rw, Pw, "world 2 grows the slices", fails)
+        seen = False
+        for s in range(10):
+            _step_all(gpu, cpus, rng, Rw, Pw, 1, ("after the growth", s), fails, extra=[told])
+            seen = seen or bool(compare({"ped_state": told.snapshot()["ped_state"]}, cpus[0].snapshot(), ("ped_state",)))
+        assert seen, "A's obstacles do not move world 0's pedestrians out of ped_state's bar: the test could not tell"
+        assert not fails, fails[:3]
+    finally:
+        gpu.close()
+        for c in cpus + [told]:
+            c.close()
+
+
+def test_list_reset_grows_tables_in_its_first_world(worlds):
+    """reset_worlds([0, 2]) whose FIRST world outgrows the obstacle slices and the trajectory table (14 obstacles, 7-point lists) while
+    the second brings 6 obstacles and 4-point lists and world 1 keeps what it has: every slice and every trajectory row must reach the
+    re-laid tables exactly once.  Then a whole-handle reset whose 40 shared obstacles outgrow the slices again."""
+    World, OracleWorld = worlds
+    W, Rw, Pw = 3, 2, 3
+    grid, params, _ = small_world(Rw, Pw, seed=81)
+    lays = [small_world(Rw, Pw, seed=81 + 100 * k, n_obstacles=1)[2] for k in range(W)]
+    gpu = World(_stack_params(params, W), grid)
+    cpus = [OracleWorld(params, grid) for _ in range(W)]
+    fails = []
+    try:
+        gpu.reset(lays)
+        for c, lay in zip(cpus, lays):
+            c.reset(lay)
+        rng = np.random.default_rng(81)
+        _step_all(gpu, cpus, rng, Rw, Pw, 2, "first episode", fails)
+        new0 = _with_longer_trajectories(small_world(Rw, Pw, seed=881, n_obstacles=14)[2], rng, 7)
+        new2 = _with_longer_trajectories(small_world(Rw, Pw, seed=882, n_obstacles=6)[2], rng, 4)
+        gpu.reset_worlds([0, 2], [new0, new2])
+        cpus[0].reset(new0)
+        cpus[2].reset(new2)
+        _compare_all(gpu, cpus, Rw, Pw, "list reset", fails)
+        _step_all(gpu, cpus, rng, Rw, Pw, 10, "after the list reset", fails)
+        shared = small_world(Rw, Pw, seed=883, n_obstacles=40)[2]
+        whole = [small_world(Rw, Pw, seed=884 + k)[2] for k in range(W)]
+        for lay in whole:
+            lay.obs_shape, lay.obs_size, lay.obs_pose = shared.obs_shape, shared.obs_size, shared.obs_pose
+        b = [lay.as_batch() for lay in whole]
+        big = dict(b[0])
+        for f in ("robot_pose", "robot_goal", "ped_pose", "ped_goal", "ped_traj", "ped_traj_len"):
+            big[f] = np.concatenate([x[f] for x in b], axis=0)
+        gpu.reset(big)
+        for c, lay in zip(cpus, whole):
+            c.reset(lay)
+        _compare_all(gpu, cpus, Rw, Pw, "whole reset", fails)
+        _step_all(gpu, cpus, rng, Rw, Pw, 5, "after the whole reset", fails)
+        assert not fails, fails[:3]
+    finally:
+        gpu.close()
+        for c in cpus:
+            c.close()

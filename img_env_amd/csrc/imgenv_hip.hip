@@ -80,6 +80,7 @@ struct imgenv {
     DevWorld d;
     PlanHandle plan;  // what the launch rules (launch_plan.h) read of this handle: plan_facts
     int raster_pack = -1;  // IMGENV_RASTER_PACK when the handle was created (measurement switch; -1: unset, the plan's rule)
+    int obs_room = -1;     // IMGENV_OBS_ROOM when the handle was created (measurement switch, plan_obs_lds; -1: unset, the plan's rule)
     std::vector<void*> allocs;
     unsigned char* arena = nullptr;
     bool own_arena = false;
@@ -631,6 +632,7 @@ static void plan_facts(imgenv* h) {
     p.early = h->early; p.gates_work = h->gates_work;
     p.Gs = h->Gs; p.box_cells = d.box_cells;
     p.robot_classes = (int)h->rcls.size(); p.pack_rows = true; p.pack_bitmap_cells = 0; p.pack_force = h->raster_pack;
+    p.obs_room_force = h->obs_room;
     for (const RobotClassHost& k : h->rcls) {  // (plan_raster_pack)
         const int side = 2 * k.box_rad + 1, bside = side - 4;
         p.pack_rows = p.pack_rows && !k.fp_rows.empty() && side * side <= d.box_cells;
@@ -669,7 +671,10 @@ static int lds_attributes(imgenv* h) {
         if (int rc = allow((const void*)k_view_for(p, nw), p.lds_view)) return rc;
     for (int rpw : {2, 4})
         if (int rc = allow((const void*)k_raster_pack_for(p, rpw), plan_raster_pack_lds(p, rpw))) return rc;
-    return allow((const void*)k_obs_for(p), p.lds_obs);
+    // (k_obs beside packed rasters asks for more than it uses, plan_obs_lds: the size of a whole-handle early step)
+    PlanChain whole;
+    whole.act_ng = p.R; whole.act_np = p.P; whole.act_nl = p.RL;
+    return allow((const void*)k_obs_for(p), std::max(p.lds_obs, plan_obs(p, whole, true).lds));
 }
 
 // view_big.h's one-byte-per-cell summary of a static map (world.h: crop_map), in 8 x 8 tiles
@@ -770,6 +775,8 @@ static void create_facts(imgenv* h, const CreatePlan& p, const uint8_t* static_m
         const int v = atoi(e);
         h->raster_pack = v == 2 || v == 4 ? v : 0;
     }
+    if (const char* e = getenv("IMGENV_OBS_ROOM"))  // (measurement switch, per handle: 0 off, else the workgroups per compute unit k_obs leaves the packed rasters)
+        h->obs_room = std::max(atoi(e), 0);
     h->R = p.R; h->P = p.P; h->r0 = p.r0; h->r1 = p.r1; h->RL = p.RL; h->NA = p.NA;
     h->Hg = p.Hg; h->Wg = p.Wg; h->Hg_in = Hg_in; h->Wg_in = Wg_in;
     h->map_stride = align16(p.G);
@@ -1514,9 +1521,9 @@ static int step_recover(imgenv* h) {
     return 0;
 }
 
-static int launch_obs_kernel(imgenv* h, hipStream_t s_obs) {
+static int launch_obs_kernel(imgenv* h, hipStream_t s_obs, bool early_step = false) {
     DevWorld& d = h->d;
-    const LaunchShape o = plan_obs(h->plan, chain_facts(h, 0));
+    const LaunchShape o = plan_obs(h->plan, chain_facts(h, 0), early_step);
     TIMED(h, IMGENV_K_OBS, s_obs, (k_obs_for(h->plan)<<<dim3(o.grid), dim3(o.block), o.lds, s_obs>>>(d, h->PP)));
     h->launches += 1;
     return 0;
@@ -2918,7 +2925,7 @@ static int early_obs(imgenv* h, const float* actions, hipStream_t st) {
     d.obs_actions = actions; d.obs_n_sub = h->n_sub;
     d.ped_snap_in = h->ped_snap[plan_snap_in(h->step.orca_seq)];
     d.rec_snap_in = h->rec_snap[plan_snap_in(h->step.view_seq)];
-    const int rc = launch_obs_kernel(h, h->side2);
+    const int rc = launch_obs_kernel(h, h->side2, true);
     d.obs_early = 0;
     if (rc) return rc;
     h->step.obs_forked = true;

@@ -345,9 +345,11 @@ __device__ __forceinline__ void tail_arrive_obs(const DevWorld& w, int t, int l,
             p_[3] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) | (wave_ph_ & 0xFFFFFFFF00000000ull); \
         }                                                                                 \
     } while (0)
+#define WAVE_FLAG() wave_ph_ |= 1ull << 63  // (kernels without phase marks: the top bit of the fourth mark says "special", k_raster_pack's redo)
 #else
 #define WAVE_T0() (void)0
 #define WAVE_DONE(base) (void)0
+#define WAVE_FLAG() (void)0
 #endif
 #ifdef IMGENV_PHASE_PROFILE
 #define PHASE_BEGIN() long long ph_t_ = clock64(); WAVE_T0()
@@ -1925,6 +1927,9 @@ __global__ __launch_bounds__(WAVE * NW) __attribute__((amdgpu_waves_per_eu((LM =
 // others: that function stays the definition and the only home of the literal sample walk.  All robots of the handle share one
 // class (the plan's rule): its record is read with a scalar index.
 // Blocks [0, ceil(n_g / RPW)): robots RPW b .. RPW b + RPW - 1 (the last block may hold fewer); the n_p blocks behind: a pedestrian each.
+// (The pedestrians' blocks in front of the robots', and raster_ped_sum asking for its list at its entry as the robots' path does,
+// were measured and do not pay: alone 84.1-84.4 against 83.6-84.0 us per headline step, with everything else 80.0-80.5 against
+// 80.5-80.6: profiles/raster_chain_ab.txt.)
 template <bool POW2, int RPW>
 __global__ __launch_bounds__(WAVE) void k_raster_pack(DevWorld w) {
     constexpr int SEG = WAVE / RPW;
@@ -1943,15 +1948,27 @@ __global__ __launch_bounds__(WAVE) void k_raster_pack(DevWorld w) {
             raster_ped_sum<POW2, 1>(w, j, w.pc[w.ped_cls[j]], (uint32_t*)smem);
             RASTER_MARK(12);  // the block's pedestrian
         }
+        if (b < w.RL) WAVE_DONE(2);  // (the timeline has a record per local robot; the robots' blocks are always within them)
         return;
     }
     RASTER_MARK_BEGIN();
     const int lane = lane_id(), seg = lane / SEG, sl = lane - seg * SEG, sh = seg * SEG;
     const bool valid = RPW * b + seg < n_g;
     const int i = min(RPW * b + seg, n_g - 1) + w.act_g0, l = i - w.r0;
-    const RobotClassDev k = robot_class(w, __builtin_amdgcn_readfirstlane(w.robot_cls[RPW * b + w.act_g0]));
+    // Every address that the block and segment index decide is asked for here, in front of the first wait: the class index, the
+    // record's pose words, the cached pose and list length, the first SEG entries of the old cell list (nobody else writes this
+    // robot's list) and, once the class index is back, the first lattice rows -- the `moved` test, the class fetch, the rows and the
+    // old-list walk would otherwise each pay a round trip of their own, one behind the other.
+    const int cls_v = w.robot_cls[RPW * b + w.act_g0];
     const double* r = w.rec + (size_t)i * IMGENV_RECORD_DOUBLES;
-    const double rx = r[0], ry = r[1], rth = r[2];
+    const double rx = r[0], ry = r[1], rth = r[2], rs = r[5], rc = r[6];
+    double* cached = w.fp_pose + 3 * (size_t)l;
+    const double c_x = cached[0], c_y = cached[1], c_th = cached[2];
+    const int n_cached = w.fp_n[l];
+    uint2* list = w.fp_cells + (size_t)l * w.fp_cap;
+    const uint32_t old0 = list[min(sl, w.fp_cap - 1)].x;
+    const RobotClassDev k = robot_class(w, __builtin_amdgcn_readfirstlane(cls_v));
+    const FpRow row0 = k.rows[min(sl, k.n_rows - 1)];
     const double res = w.res, inv = w.inv_res;
     const int rad = k.box_rad, side = 2 * rad + 1, ncell = side * side;
     const int world = world_of_robot(w, i);
@@ -1965,9 +1982,7 @@ __global__ __launch_bounds__(WAVE) void k_raster_pack(DevWorld w) {
         p[2] = 1.0;
     }
     // a robot that has not moved since its cell list was made: its counts and its list stand
-    double* cached = w.fp_pose + 3 * (size_t)l;
-    const int n_cached = w.fp_n[l];
-    const bool moved = valid && !(n_cached >= 0 && cached[0] == rx && cached[1] == ry && cached[2] == rth);
+    const bool moved = valid && !(n_cached >= 0 && c_x == rx && c_y == ry && c_th == rth);
     if (!__any(moved)) {
         WAVE_DONE(2);
         return;
@@ -1979,12 +1994,12 @@ __global__ __launch_bounds__(WAVE) void k_raster_pack(DevWorld w) {
     const int cm = w2m_t<POW2>(rx, res, inv), cn = w2m_t<POW2>(ry, res, inv);
     bool bad = false;
     {   // the lattice rows of the footprint (fp_rows.h), one per lane of the segment
-        const Tf2 bw = tf_from_pose_sc(rx, ry, r[5], r[6]);
+        const Tf2 bw = tf_from_pose_sc(rx, ry, rs, rc);
         const FpRowsPose P = fpr_pose(bw.m00, bw.m01, bw.m10, bw.m11, bw.ox, bw.oy, k.fp_cy, res);
         for (int r0 = 0; r0 < k.n_rows; r0 += SEG) {  // wave-uniform trip count
             const int ri = r0 + sl;
             const bool act = moved && ri < k.n_rows;
-            const FpRow row = k.rows[min(ri, k.n_rows - 1)];
+            const FpRow row = r0 == 0 ? row0 : k.rows[min(ri, k.n_rows - 1)];
             FpAxis ax, ay;
             const bool ok = fpr_row(P, row, ax, ay);
             bad |= act & !ok;
@@ -2027,7 +2042,6 @@ __global__ __launch_bounds__(WAVE) void k_raster_pack(DevWorld w) {
     const int bm_ = sl / bside, bn_ = sl - bm_ * bside;
     const unsigned long long fp_bits = (__ballot(sl < bside * bside && box[(bm_ + 2) * side + bn_ + 2] != 0u) >> sh) & SEG_MASK;
     if (go && sl == 0) ((unsigned long long*)w.rec)[(size_t)i * IMGENV_RECORD_DOUBLES + 7] = fp_bits;
-    uint2* list = w.fp_cells + (size_t)l * w.fp_cap;
     const uint32_t sum_word = sum_robot_word(w, sum_self_id(w, i));
     if (!alone) {
         // the cells the robot counted itself on so far: still under its footprint -> marked in the box, left behind -> its word comes off
@@ -2035,7 +2049,7 @@ __global__ __launch_bounds__(WAVE) void k_raster_pack(DevWorld w) {
         for (int e0 = 0; __any(e0 < n_old); e0 += SEG) {
             const int e = e0 + sl;
             if (e < n_old) {
-                const uint32_t c = list[e].x, rel = c - cell0;
+                const uint32_t c = e0 == 0 ? old0 : list[e].x, rel = c - cell0;
                 const int m = (int)(((unsigned long long)rel * w.sum_wg_magic) >> 40), n = (int)rel - m * w.Wg;
                 const int dm = m - cm + rad, dn = n - cn + rad;
                 const bool inb = dm >= 0 && dm < side && dn >= 0 && dn < side;
@@ -2081,6 +2095,7 @@ __global__ __launch_bounds__(WAVE) void k_raster_pack(DevWorld w) {
             __syncthreads();
             raster_robot<POW2, 2, 1>(w, RPW * b + s + w.act_g0, k, (uint32_t*)smem, g);
         }
+        WAVE_FLAG();  // (the timeline tells a redo wavefront from the others)
     }
     WAVE_DONE(2);
 }

@@ -129,6 +129,7 @@ struct PlanHandle {
     bool pack_rows = false;
     int pack_bitmap_cells = 0;
     int pack_force = -1;
+    int obs_room_force = -1;                                    // plan_obs_lds: IMGENV_OBS_ROOM as the handle's creation found it (-1: unset)
     int big_max_crop = 1, big_full_chunks = 1, big_tap_chunks_dyn = 0;
     bool big_bits_in_lds = true, crop_map = false;
     int img_w = 0, img_h = 0;
@@ -397,7 +398,37 @@ inline SidePlan plan_side(const PlanHandle& h, const PlanChain& c) {
 // (four wavefronts per robot for 513 .. 1024 pedestrians -- three times the occupancy, a third of the LDS per wavefront --
 // were measured in round 6 and LOSE: cfg-5 277 -> 325 us per step, 321 with two, 406 with eight: the step is bound by the
 // instructions it issues, k_obs beside k_view, not by this kernel's occupancy.  docs/HISTORY.md)
-inline LaunchShape plan_obs(const PlanHandle& h, const PlanChain& c) { return {(unsigned)c.act_nl, WAVE, h.lds_obs}; }
+//
+// Room for the packed rasters beside an early k_obs: k_obs goes out first and fills the chip -- its 4.4 KB of LDS round up to four
+// 1280-byte granules, 32 wavefronts of it are a compute unit's whole 160 KiB -- and the raster launch behind it (2048 + 200
+// wavefronts at the headline shape, nine per compute unit) gets a wavefront slot, registers and LDS only as k_obs' wavefronts
+// retire.  A k_obs workgroup that asks for more LDS than it uses keeps fewer of itself on a compute unit.  plan_obs_lds answers
+// the smallest size, in granules, at which a compute unit full of k_obs workgroups still has `room` wavefront slots AND `room`
+// times the raster's LDS free; lds_obs itself where nothing is packed behind the observation (raster_blocks 0), where the switch
+// says 0, or where no size does it.  What a compute unit holds is floor(128 granules / size), so the steps are coarse: with the
+// headline's sizes (four granules, one per raster workgroup) room 1-3 gives five granules (25 k_obs workgroups, three granules
+// left over), room 4-8 ten (12 and 8), room 9 thirteen (9 and 11).
+// room_force: IMGENV_OBS_ROOM as the handle's creation found it (measurement switch; -1: unset, the rule's own value).
+// The rule's own value: OBS_ROOM_RULE workgroups, the first step.  The headline step, one box, the switch at 0 / 2 / 4 / 9 interleaved
+// three times (profiles/raster_chain_ab.txt): 82.0 / 82.5 / 81.3 us per step with k_obs as it was, 79.8 / 80.0 / 80.3 at five
+// granules (k_obs itself 32.6 -> 37.4 us by HIP events, the step ends earlier all the same), 96.2 / 96.4 / 96.5 at ten and
+// 105.3 / 105.3 / 104.2 at thirteen, where k_obs (51-53 and 70-72 us) has become the step's longest chain.
+#define OBS_ROOM_RULE 2
+inline size_t plan_obs_lds(size_t lds_obs, unsigned raster_blocks, size_t raster_lds, int room_force) {
+    const int room = room_force >= 0 ? room_force : OBS_ROOM_RULE;
+    if (raster_blocks == 0 || room <= 0 || room >= 32) return lds_obs;
+    const size_t cu = LDS_MAX / 1280, need = (size_t)room * ((raster_lds + 1279) / 1280);
+    for (size_t g = std::max<size_t>((lds_obs + 1279) / 1280, 1); g <= cu; g++) {
+        const size_t n = std::min<size_t>(cu / g, 32);  // k_obs workgroups (one wavefront each) a compute unit holds at this size
+        if (32 - n >= (size_t)room && cu - n * g >= need) return g * 1280;
+    }
+    return lds_obs;
+}
+// (early_step: plan_step's, of the step this observation belongs to -- the rasters it shares the chip with are that step's)
+inline LaunchShape plan_obs(const PlanHandle& h, const PlanChain& c, bool early_step = false) {
+    const RasterPackPlan k = early_step ? plan_raster_pack(h, c) : RasterPackPlan{};
+    return {(unsigned)c.act_nl, WAVE, plan_obs_lds(h.lds_obs, k.rpw ? k.launch.grid : 0u, k.launch.lds, h.obs_room_force)};
+}
 
 // ---------------------------------------------------------------------------------------- ordering (launch_views, imgenv_step_begin)
 // The side wiring of a chain with pedestrians: one fork and one join per step on the caller's stream (every event operation costs

@@ -13,7 +13,9 @@ sys.path.insert(0, ROOT)
 import __graft_entry__ as g  # noqa: E402
 
 so = os.path.join(g.CSRC, "libimgenv_hip_tl.so")
-subprocess.check_call(g.hip_command(so, ["-DIMGENV_WAVE_TIMELINE"] + os.environ.get("IMGENV_TL_FLAGS", "").split()))  # (IMGENV_TL_FLAGS: more -D switches)
+_flags = ["-DIMGENV_WAVE_TIMELINE"] + os.environ.get("IMGENV_TL_FLAGS", "").split()  # (IMGENV_TL_FLAGS: more -D switches)
+if g._built_id(so) != g.source_id(_flags):  # (a library of this tree and these flags that is already there is used as it is)
+    subprocess.check_call(g.hip_command(so, _flags))
 from img_env_amd import _cabi, worldgen  # noqa: E402
 _cabi.library_path = lambda: so
 import torch  # noqa: E402
@@ -54,6 +56,10 @@ for name, rec in (("k_view", buf[:4 * R].reshape(R, 4)), ("k_obs", buf[4 * R:8 *
     if not (t1 > 0).any():
         continue  # (not launched on this handle)
     ok = (t1 > 0) & (t0 > t0.max() - 6000)  # this launch only (60 us back from the last start): frozen robots keep an older record
+    special = (rec[:, 3] >> np.uint64(63)) != 0  # WAVE_FLAG: k_raster_pack's redo wavefronts (no phase marks in that kernel)
+    if name == "k_raster":
+        rec = rec.copy()
+        rec[:, 3] &= np.uint64((1 << 63) - 1)
     xc = (rec[:, 3] & 0xF).astype(np.int64)
     print("   per-XCC first start (ticks): " + " ".join(str(int(t0[ok & (xc == x)].min() - t0[ok].min())) for x in sorted(set(xc[ok].tolist()))))
     base = t0[ok].min()
@@ -62,6 +68,12 @@ for name, rec in (("k_view", buf[:4 * R].reshape(R, 4)), ("k_obs", buf[4 * R:8 *
     print("%s: %d waves, span %.1f us; wave life us: min %.1f p10 %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f" % (
         name, ok.sum(), e.max(), d.min(), *np.percentile(d, [10, 50, 90, 99]), d.max()))
     print("   starts us: p10 %.1f p50 %.1f p90 %.1f max %.1f" % (*np.percentile(s, [10, 50, 90]), s.max()))
+    if name == "k_raster" and CFG == "cfg3":  # who ends the launch: k_raster_pack<., 4> there (launch_plan.h: plan_raster_pack), the robots' blocks in front, a pedestrian each behind
+        blk, n_rb = np.flatnonzero(ok), (R + 3) // 4
+        last, ped = int(blk[np.argmax(e)]), blk >= n_rb
+        kind = "pedestrian" if last >= n_rb else "redo" if special[last] else "robot"
+        print("   last wavefront to end: block %d (%s), start %.1f end %.1f us; pedestrian blocks: %d, last of them ends %s; redo wavefronts: %d" % (
+            last, kind, s[np.argmax(e)], e.max(), int(ped.sum()), "%.1f" % e[ped].max() if ped.any() else "-", int(special[ok].sum())))
     print("   starts histogram (5 us bins): " + " ".join(str(int(x)) for x in np.histogram(s, bins=np.arange(0, s.max() + 5, 5))[0]))
     ts = np.linspace(0, e.max(), 11)[1:-1]
     print("   resident waves at " + " ".join("%.0fus:%d" % (t, ((s <= t) & (e > t)).sum()) for t in ts))

@@ -290,6 +290,36 @@ def make_policy_cfg(kind, seed=0, store=False):
     return c
 
 
+#: PPO's loss (imgenv_policy_loss_enable; csrc/policy_loss.h)
+PLOSS_CLIP_VALUE = 1  # imgenv_policy_loss_args.flags, beside POLICY_LOG_STD_PER_ROW
+#: imgenv_policy_loss_out's arrays, in the struct's order
+PLOSS_ARRAYS = ("logp", "entropy", "ratio", "pg", "vl", "d_params", "d_log_std", "d_log_std_shared", "d_values", "stats", "n_bad", "inv_w")
+#: the entries of stats
+PLOSS_STATS = ("loss", "pg_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "weight_sum")
+
+
+class PolicyLossCfg(C.Structure):
+    _fields_ = [("struct_size", _i32), ("max_rows", _i32), ("reserved", _i32 * 2)]
+
+
+class PolicyLossOut(C.Structure):
+    _fields_ = [("struct_size", _i32), ("n_params", _i32), ("max_rows", _i32), ("reserved", _i32)] + [(name, C.c_void_p) for name in PLOSS_ARRAYS]
+
+
+class PolicyLossArgs(C.Structure):
+    _fields_ = [("struct_size", _i32), ("flags", _i32), ("rows", _i32), ("reserved", _i32), ("params", C.c_void_p), ("log_std", C.c_void_p),
+                ("values", C.c_void_p), ("action", C.c_void_p * 3), ("old_logp", C.c_void_p), ("old_value", C.c_void_p), ("adv", C.c_void_p),
+                ("ret", C.c_void_p), ("weight", C.c_void_p), ("clip", _f32), ("clip_vf", _f32), ("vf_coef", _f32), ("ent_coef", _f32)]
+
+
+def make_policy_loss_cfg(max_rows):
+    """``imgenv_policy_loss_cfg``"""
+    c = PolicyLossCfg()
+    c.struct_size = C.sizeof(PolicyLossCfg)
+    c.max_rows = int(max_rows)
+    return c
+
+
 class ObsPostCfg(C.Structure):
     _fields_ = [("struct_size", _i32), ("flags", _i32), ("avg", _f64 * 7), ("std", _f64 * 7), ("close_dist", _f64)]
 
@@ -650,6 +680,7 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_episode_log_enable", "imgenv_episode_log_outputs", "imgenv_episode_log_read",
            "imgenv_actions_enable", "imgenv_actions_outputs", "imgenv_actions_decode", "imgenv_obs_post_enable", "imgenv_obs_post_outputs",
            "imgenv_policy_enable", "imgenv_policy_outputs", "imgenv_policy_sample",
+           "imgenv_policy_loss_enable", "imgenv_policy_loss_outputs", "imgenv_policy_loss",
            "imgenv_final_obs_enable", "imgenv_final_obs_outputs",
            "imgenv_rollout_enable", "imgenv_rollout_outputs", "imgenv_rollout_begin", "imgenv_rollout_gae",
            "imgenv_rollout_minibatch_enable", "imgenv_rollout_minibatch_outputs", "imgenv_rollout_index", "imgenv_rollout_stats",
@@ -723,6 +754,9 @@ def bind(lib):
     lib.imgenv_policy_enable.argtypes = [C.c_void_p, C.POINTER(PolicyCfg), C.POINTER(PolicyOut)]
     lib.imgenv_policy_outputs.argtypes = [C.c_void_p, C.POINTER(PolicyOut)]
     lib.imgenv_policy_sample.argtypes = [C.c_void_p, C.POINTER(PolicyArgs), C.c_void_p]
+    lib.imgenv_policy_loss_enable.argtypes = [C.c_void_p, C.POINTER(PolicyLossCfg), C.POINTER(PolicyLossOut)]
+    lib.imgenv_policy_loss_outputs.argtypes = [C.c_void_p, C.POINTER(PolicyLossOut)]
+    lib.imgenv_policy_loss.argtypes = [C.c_void_p, C.POINTER(PolicyLossArgs), C.c_void_p]
     lib.imgenv_obs_post_enable.argtypes = [C.c_void_p, C.POINTER(ObsPostCfg), C.POINTER(ObsPostOut)]
     lib.imgenv_obs_post_outputs.argtypes = [C.c_void_p, C.POINTER(ObsPostOut)]
     lib.imgenv_final_obs_enable.argtypes = [C.c_void_p, C.POINTER(FinalObsCfg), C.POINTER(FinalObsOut)]

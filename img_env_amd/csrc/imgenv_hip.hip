@@ -32,6 +32,7 @@
 #include "episode_log.h"
 #include "actions.h"
 #include "policy.h"
+#include "policy_loss.h"
 #include "obs_post.h"
 #include "final_obs.h"
 #include "rollout.h"
@@ -282,6 +283,11 @@ struct imgenv {
     PolicyDev pol;               // what every launch shares; params, draw, flags and the slot's pointers are the call's
     imgenv_policy_cfg pol_cfg;
     imgenv_policy_out pol_out;
+    // PPO's loss (include/imgenv.h: imgenv_policy_loss_enable; csrc/policy_loss.h)
+    bool ploss_on = false;
+    PlossDev ploss;              // what every call shares: the handle's arrays; inputs, coefficients and rows are the call's
+    imgenv_policy_loss_cfg ploss_cfg;
+    imgenv_policy_loss_out ploss_out;
     // observation post-processing (imgenv_obs_post_enable; csrc/obs_post.h)
     bool post_on = false;
     ObsPostDev post;
@@ -4009,6 +4015,105 @@ extern "C" int imgenv_policy_sample(imgenv_t* h, const imgenv_policy_args* g, vo
     k<<<dim3(s.grid), dim3(s.block), 0, (hipStream_t)stream>>>(p);
     HIPCHK(hipGetLastError());
     if (!value_only) h->decode_launches += 1;  // (the values-only call belongs to no step)
+    return IMGENV_OK;
+}
+
+// ---- PPO's loss (include/imgenv.h; the kernels are csrc/policy_loss.h) ----
+extern "C" int imgenv_policy_loss_enable(imgenv_t* h, const imgenv_policy_loss_cfg* c, imgenv_policy_loss_out* out) {
+    // (the cfg first, as above)
+    RTRY(enable_args(c, "imgenv_policy_loss_cfg", out, "imgenv_policy_loss_out"));
+    if (c->max_rows < 1) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_cfg.max_rows %d (at least 1)", c->max_rows);
+    if (c->reserved[0] != 0 || c->reserved[1] != 0) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_cfg.reserved");
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    if (h->ploss_on) {
+        if (c->max_rows != h->ploss_cfg.max_rows) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_enable: the handle already has a policy loss with another cfg");
+        if (out) *out = h->ploss_out;
+        return IMGENV_OK;
+    }
+    if (!h->pol_on) FAIL(IMGENV_ESTATE, "imgenv_policy_loss_enable before imgenv_policy_enable");
+    const bool cat = h->pol_cfg.kind == IMGENV_POLICY_CATEGORICAL;
+    const size_t B = (size_t)c->max_rows, n = (size_t)(cat ? h->pol.A : h->pol.C);
+    const size_t n_rec = plan_policy_loss_launch(c->max_rows, cat ? h->pol.A : 0).grid;
+    // one block, every array on a 256-byte boundary, zeroed; nothing of the handle changes before it is there
+    Carve cv;
+    const size_t off_logp = cv.take(B * 4), off_ent = cv.take(B * 4), off_ratio = cv.take(B * 4), off_pg = cv.take(B * 4), off_vl = cv.take(B * 4);
+    const size_t off_dp = cv.take(B * n * 4), off_dls = cv.take(cat ? 0 : B * n * 4), off_dlss = cv.take(cat ? 0 : n * 4), off_dv = cv.take(B * 4);
+    const size_t off_stats = cv.take(8 * 4), off_bad = cv.take(4), off_invw = cv.take(4);
+    const size_t off_m = cv.take(cat ? B * 4 : 0), off_ls = cv.take(cat ? B * 4 : 0), off_gu = cv.take(B * 4), off_w = cv.take(B * 4);
+    const size_t off_rec = cv.take(n_rec * PLOSS_REC * 8);
+    unsigned char* block = nullptr;
+    RTRY(feature_block(h, cv.total, "imgenv_policy_loss_enable", &block));
+    imgenv_policy_loss_out o = {};
+    o.struct_size = (int32_t)sizeof(o);
+    o.n_params = (int32_t)n;
+    o.max_rows = c->max_rows;
+    o.logp = (float*)(block + off_logp); o.entropy = (float*)(block + off_ent); o.ratio = (float*)(block + off_ratio);
+    o.pg = (float*)(block + off_pg); o.vl = (float*)(block + off_vl);
+    o.d_params = (float*)(block + off_dp);
+    if (!cat) { o.d_log_std = (float*)(block + off_dls); o.d_log_std_shared = (float*)(block + off_dlss); }
+    o.d_values = (float*)(block + off_dv);
+    o.stats = (float*)(block + off_stats); o.n_bad = (int32_t*)(block + off_bad); o.inv_w = (float*)(block + off_invw);
+    PlossDev p;
+    memset(&p, 0, sizeof(p));
+    p.logp = o.logp; p.entropy = o.entropy; p.ratio = o.ratio; p.pg = o.pg; p.vl = o.vl;
+    p.d_params = o.d_params; p.d_log_std = o.d_log_std; p.d_log_std_shared = o.d_log_std_shared; p.d_values = o.d_values;
+    p.stats = o.stats; p.n_bad = o.n_bad; p.inv_W = o.inv_w;
+    if (cat) { p.row_m = (float*)(block + off_m); p.row_log_s = (float*)(block + off_ls); }
+    p.row_gu = (float*)(block + off_gu); p.row_w = (float*)(block + off_w);
+    p.rec = (double*)(block + off_rec);
+    p.A = h->pol.A; p.C = h->pol.C;
+    h->ploss = p;
+    h->ploss_cfg = *c;
+    h->ploss_out = o;
+    h->ploss_on = true;
+    if (out) *out = o;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_policy_loss_outputs(imgenv_t* h, imgenv_policy_loss_out* out) {
+    return feature_outputs(h, &imgenv::ploss_on, &imgenv::ploss_out, out, "imgenv_policy_loss_enable");
+}
+
+typedef void (*PlossKernel)(const PlossDev);
+static void k_ploss_cat_for(int G, PlossKernel& rows, PlossKernel& grad) {
+    pick([&](auto g) { rows = k_ploss_cat<decltype(g)::value>; grad = k_ploss_grad_cat<decltype(g)::value>; }, OneOf<1, 4, 16, 64>{G});
+}
+extern "C" int imgenv_policy_loss(imgenv_t* h, const imgenv_policy_loss_args* g, void* stream) {
+    if (!h || !g) FAIL(IMGENV_EINVAL, "null argument");
+    if (g->struct_size != (int32_t)sizeof(imgenv_policy_loss_args)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.struct_size %d (this library's is %d)", g->struct_size, (int)sizeof(imgenv_policy_loss_args));
+    if (g->flags & ~(IMGENV_PLOSS_CLIP_VALUE | IMGENV_POLICY_LOG_STD_PER_ROW)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.flags %d", g->flags);
+    if (g->reserved != 0) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.reserved %d", g->reserved);
+    if (!h->ploss_on) FAIL(IMGENV_ESTATE, "imgenv_policy_loss_enable was not called");
+    if (g->rows < 1 || g->rows > h->ploss_cfg.max_rows) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.rows %d (1 .. %d)", g->rows, h->ploss_cfg.max_rows);
+    const bool cat = h->pol_cfg.kind == IMGENV_POLICY_CATEGORICAL, clip_value = (g->flags & IMGENV_PLOSS_CLIP_VALUE) != 0;
+    if (cat && (g->flags & IMGENV_POLICY_LOG_STD_PER_ROW)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.flags: IMGENV_POLICY_LOG_STD_PER_ROW on a categorical head");
+    auto missing = [](const void* p) { return !p || (uintptr_t)p % 4 != 0; };
+    if (missing(g->params) || missing(g->values) || missing(g->old_logp) || missing(g->adv) || missing(g->ret) || missing(g->weight))
+        FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args: params, values, old_logp, adv, ret or weight is null or misaligned");
+    if (!cat && missing(g->log_std)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.log_std is null or misaligned");
+    if (clip_value && missing(g->old_value)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.old_value is null or misaligned");
+    for (int c = 0; c < (cat ? 1 : h->ploss.C); c++)
+        if (missing(g->action[c])) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.action[%d] is null or misaligned", c);
+    if (!(g->clip >= 0.0f)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.clip %g", (double)g->clip);
+    if (clip_value && !(g->clip_vf >= 0.0f)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.clip_vf %g", (double)g->clip_vf);
+    PlossDev p = h->ploss;
+    p.params = g->params; p.log_std = g->log_std; p.values = g->values;
+    for (int c = 0; c < 3; c++) p.action[c] = g->action[c];
+    p.old_logp = g->old_logp; p.old_value = g->old_value; p.adv = g->adv; p.ret = g->ret; p.weight = g->weight;
+    p.clip = g->clip; p.clip_vf = g->clip_vf; p.vf_coef = g->vf_coef; p.ent_coef = g->ent_coef;
+    p.B = g->rows;
+    p.clip_value = clip_value ? 1 : 0;
+    p.ls_per_row = (g->flags & IMGENV_POLICY_LOG_STD_PER_ROW) ? 1 : 0;
+    const LaunchShape s = plan_policy_loss_launch(p.B, cat ? p.A : 0);
+    p.n_rec = (int32_t)s.grid;
+    PlossKernel rows = k_ploss_gauss, grad = k_ploss_grad_gauss;
+    if (cat) k_ploss_cat_for(plan_policy_group(p.A), rows, grad);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const hipStream_t st = (hipStream_t)stream;
+    rows<<<dim3(s.grid), dim3(s.block), 0, st>>>(p);
+    k_ploss_fold<<<dim3(1), dim3(PLOSS_FOLD_BLOCK), 0, st>>>(p);
+    grad<<<dim3(s.grid), dim3(s.block), 0, st>>>(p);
+    HIPCHK(hipGetLastError());
     return IMGENV_OK;
 }
 

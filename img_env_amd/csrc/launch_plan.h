@@ -828,6 +828,13 @@ inline LaunchShape plan_policy_launch(const PlanHandle& h, int n_logits) {
     const size_t lanes = (size_t)h.RL * (size_t)plan_policy_group(n_logits);
     return {(unsigned)((lanes + POL_BLOCK - 1) / POL_BLOCK), POL_BLOCK, 0};
 }
+// imgenv_policy_loss (policy_loss.h): the same groups over the B rows of a minibatch instead of the handle's robots, for the row
+// launch and the gradient launch alike (Gaussian: n_logits 0); the row launch leaves one record per workgroup, which is what
+// k_ploss_fold's single wavefront folds
+inline LaunchShape plan_policy_loss_launch(int rows, int n_logits) {
+    const size_t lanes = (size_t)rows * (size_t)plan_policy_group(n_logits);
+    return {(unsigned)((lanes + POL_BLOCK - 1) / POL_BLOCK), POL_BLOCK, 0};
+}
 
 // ---------------------------------------------------------------------------------------- resets
 // Device half of a host-side reset, for every world or the n worlds listed: one upload launch (segment copies | map restore |

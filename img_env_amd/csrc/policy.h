@@ -238,10 +238,11 @@ __device__ __forceinline__ void pol_write_actions(const PolicyDev& a, int r, flo
     a.speeds[(size_t)r * 2 + 1] = clean ? w : 0.0f;
 }
 
+// the cross-lane folds of a group, in the order stated at the top: m and bad (xor butterfly), the lanes' sums and their
+// Hillis-Steele scan; every lane of the group leaves with the row's m, bad and s and with its own X.  k_ploss_cat
+// (policy_loss.h) calls the same two functions, which is what makes its log-probabilities the sampler's bit for bit.
 template <int G, class Row>
-__device__ __forceinline__ void pol_cat_group(const PolicyDev& a, const Row& row, int r, int j, int k0, bool live) {
-    float m;
-    int bad;
+__device__ __forceinline__ void pol_group_sums(const Row& row, int j, float& m, int& bad, float& X, float& s) {
     pol_lane_max(row, m, bad);
     if constexpr (G > 1) {
         POL_UNROLL
@@ -252,7 +253,8 @@ __device__ __forceinline__ void pol_cat_group(const PolicyDev& a, const Row& row
         }
     }
     bad |= m == -INFINITY ? 1 : 0;
-    float P = pol_lane_sum(row, m), X = 0.0f;
+    float P = pol_lane_sum(row, m);
+    X = 0.0f;
     if constexpr (G > 1) {
         POL_UNROLL
         for (int d = 1; d < G; d <<= 1) {
@@ -263,22 +265,38 @@ __device__ __forceinline__ void pol_cat_group(const PolicyDev& a, const Row& row
         X = j ? X : 0.0f;
         P = __shfl(P, G - 1, G);
     }
+    s = P;
+}
+// the entropy's xor butterfly over the lanes' sums
+template <int G>
+__device__ __forceinline__ float pol_group_entropy(float H) {
+    if constexpr (G > 1) {
+        POL_UNROLL
+        for (int d = 1; d < G; d <<= 1) H = H + __shfl_xor(H, d, G);
+    }
+    return H;
+}
+
+template <int G, class Row>
+__device__ __forceinline__ void pol_cat_group(const PolicyDev& a, const Row& row, int r, int j, int k0, bool live) {
+    float m, X, P;
+    int bad;
+    pol_group_sums<G>(row, j, m, bad, X, P);
     const float s = P, log_s = logf(s);
     uint32_t x[4];
     pol_draw(a.g0 + (unsigned long long)r, a.draw_lo, a.draw_hi, a.seed_lo, a.seed_hi, 0, x);
     const float target = pol_u01(x[0]) * s;
     const PolLanePick pk = pol_lane_pick(row, k0, m, X, s, log_s, target, a.det != 0);
     int cand = pk.cand, last = pk.last;
-    float H = pk.ent;
     if constexpr (G > 1) {
         POL_UNROLL
         for (int d = 1; d < G; d <<= 1) {
             const int oc = __shfl_xor(cand, d, G), ol = __shfl_xor(last, d, G);
             cand = oc < cand ? oc : cand;
             last = ol > last ? ol : last;
-            H = H + __shfl_xor(H, d, G);
         }
     }
+    const float H = pol_group_entropy<G>(pk.ent);
     const bool found = cand != INT_MAX;
     const int idx = found ? cand : last;
     bad |= idx < 0 ? 1 : 0;  // (no e_k > 0 in a row with a finite maximum: expf(0) is 1, so this cannot be -- but the table is never read at -1)

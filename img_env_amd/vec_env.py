@@ -27,6 +27,35 @@ def stack_params(params, env_num):
     return p
 
 
+_LOSS_FN = []
+
+
+def _loss_function():
+    """the ``torch.autograd.Function`` behind ``VecImageEnv.policy_loss`` (made once: torch is imported late): forward runs the
+    library's three launches and returns ``stats[0]``, backward scales the library's gradients by the incoming one"""
+    if not _LOSS_FN:
+        import torch
+
+        class PolicyLoss(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, run, fresh, params, values, log_std=None):
+                out = run(params.detach(), values.detach(), None if log_std is None else log_std.detach())
+                ctx.out, ctx.fresh, ctx.serial = out, fresh, fresh(None)
+                ctx.shapes = (params.shape, values.shape, None if log_std is None else log_std.shape)
+                return out["stats"][0].clone()
+
+            @staticmethod
+            def backward(ctx, grad):
+                ctx.fresh(ctx.serial)
+                out, (ps, vs, lss) = ctx.out, ctx.shapes
+                grads = [None, None, (out["d_params"] * grad).reshape(ps), (out["d_values"] * grad).reshape(vs)]
+                if lss is not None:
+                    grads.append((out["d_log_std_shared" if len(lss) == 1 else "d_log_std"] * grad).reshape(lss))
+                return tuple(grads)
+        _LOSS_FN.append(PolicyLoss)
+    return _LOSS_FN[0]
+
+
 class VecImageEnv:
     """``reset() -> ImageState``; ``step(actions) -> (ImageState, rewards, dones, info)`` over ``env_num * robot_total`` robots.
 
@@ -44,7 +73,8 @@ class VecImageEnv:
     ``normalise=dict(...)``: running normalisation of ``vector_states`` and of the reward inside the library (VecNormalize): the
     state and the reward handed out are the normalised ones, ``info`` gains ``raw_vector_states`` and ``raw_rewards``.
     ``policy=dict(seed=s)`` (with ``wrappers=True``): the action sampled from the network's logits (or mean and log-std) inside
-    the library: ``policy_sample(...)``, ``policy_step(...)``, ``policy_value(values)``, ``policy_draw``.
+    the library: ``policy_sample(...)``, ``policy_step(...)``, ``policy_value(values)``, ``policy_draw``.  ``policy=dict(seed=s,
+    loss=True)`` (with ``minibatch=B``) adds PPO's loss and its gradients on the device: ``policy_loss(mb, ...)``.
     """
 
     def __init__(self, cfg, env_num=None, seed=None, auto_reset=True, native_spawn=False, device_reset=False, stack=False,
@@ -58,8 +88,10 @@ class VecImageEnv:
             raise ValueError("minibatch=B needs rollout=T")
         if policy is not None and not wrappers:
             raise ValueError("policy=dict(seed=s) needs wrappers=True")
-        if policy is not None and set(policy) - {"seed"}:
-            raise ValueError("policy: unknown %s (known: seed)" % sorted(set(policy) - {"seed"}))
+        if policy is not None and set(policy) - {"seed", "loss"}:
+            raise ValueError("policy: unknown %s (known: seed, loss)" % sorted(set(policy) - {"seed", "loss"}))
+        if policy is not None and policy.get("loss") and not minibatch:
+            raise ValueError("policy=dict(loss=True) needs minibatch=B")
         self.cfg = cfg
         self.env_num = int(env_num if env_num is not None else cfg.get("env_num", 1))
         # ped_tracks: the recorded crowds of ``ped_sim.type: dataset`` as a bank inside the handle (imgenv_tracks_add) -- a list of
@@ -272,6 +304,10 @@ class VecImageEnv:
             self._policy_cat = bool(cfg.get("discrete_action"))
             self.world.enable_policy("categorical" if self._policy_cat else "gaussian", int(self.policy.get("seed", 0)),
                                      store=self.rollout_horizon > 0)
+            # loss=True: PPO's loss of a minibatch and its gradients on the network's outputs (imgenv_policy_loss_enable), three
+            # launches instead of torch's chain of small ones and its autograd -- policy_loss().  Opt-in as well.
+            if self.policy.get("loss"):
+                self.world.enable_policy_loss(self.minibatch_batch)
 
     def _need_policy(self):
         if self.policy is None:
@@ -311,6 +347,74 @@ class VecImageEnv:
         if self.rollout_horizon <= 0:
             raise RuntimeError("VecImageEnv was made without rollout=T")
         self.world.policy_value(values)
+
+    def policy_loss(self, mb, logits=None, mean=None, log_std=None, values=None, clip=0.2, vf_coef=0.5, ent_coef=0.0, clip_vf=None,
+                    keys=None):
+        """PPO's loss of one minibatch on the device (``imgenv_policy_loss``): ``mb`` is a dict from ``rollout_minibatches``,
+        ``logits`` ``[B, A]`` (or ``mean`` ``[B, C]`` and ``log_std`` ``[C]`` / ``[B, C]``) and ``values`` ``[B]`` are the
+        network's outputs for ``mb``'s observations under its present parameters.  Returns ``(loss, info)``: ``loss`` is a 0-dim
+        tensor whose ``backward()`` hands the library's closed-form gradients, times the incoming one, to ``logits`` / ``mean``,
+        ``log_std`` and ``values`` -- ``loss.backward(); optimizer.step()`` as with a loss written in torch ops; call it before
+        the next ``policy_loss`` (the gradients live in library-owned tensors that the next call rewrites; RuntimeError
+        otherwise).  ``info``: ``loss``, ``pg_loss``, ``value_loss``, ``entropy``, ``approx_kl``, ``clip_fraction`` and
+        ``weight_sum`` (0-dim views of ``stats``), ``n_bad``, and the row tensors ``logp``, ``row_entropy``, ``ratio``, ``pg``,
+        ``vl``.  Nothing synchronises.  ``clip_vf``: the clipped value loss (needs the old values among the scalars).
+
+        ``keys`` names ``mb``'s scalars: ``dict(action="action", old_logp="old_logp", old_value="old_value", adv="adv",
+        ret="ret")``; for a Gaussian head ``action`` is the sequence of its C column names.  A PPO loop passes, with ``ro =
+        rollout()`` and ``adv, ret = rollout_advantages(ro["pol_value"])``::
+
+            scalars = dict(action=ro["pol_raw"][0], old_logp=ro["pol_logp"], old_value=ro["pol_value"], adv=adv, ret=ret)
+            for mb in vec.rollout_minibatches(scalars, seed, normalise="adv"):
+                logits, values = net(mb["mb_vector_states"])
+                loss, info = vec.policy_loss(mb, logits=logits, values=values, clip_vf=0.2)
+                optimizer.zero_grad(); loss.backward(); optimizer.step()
+
+        (Gaussian: ``action0=ro["pol_raw"][0], action1=ro["pol_raw"][1], ...`` and ``keys=dict(action=("action0", "action1"))``.)
+        A minibatch carries at most 6 scalars: a Gaussian head with C = 3 has 3 + old_logp + adv + ret already, so ``clip_vf``
+        with C = 3 raises ValueError."""
+        import torch
+        self._need_policy()
+        w = self.world
+        if w.policy_loss_out is None:
+            raise RuntimeError("VecImageEnv was made without policy=dict(seed=s, loss=True)")
+        if (logits is None) != (not self._policy_cat) or values is None:
+            raise ValueError("policy_loss: %s and values" % ("logits" if self._policy_cat else "mean and log_std"))
+        names = dict(action="action", old_logp="old_logp", old_value="old_value", adv="adv", ret="ret")
+        names.update(keys or {})
+        C = w._pol_params
+        if not self._policy_cat and C == 3 and clip_vf is not None:
+            raise ValueError("policy_loss: clip_vf with a Gaussian head of 3 columns needs 7 scalars (3 action columns, old_logp, "
+                             "old_value, adv, ret) and a minibatch carries %d" % _cabi.MB_MAX_SCALARS)
+        if self._policy_cat:
+            action = mb[names["action"]]
+        else:
+            cols = names["action"]
+            action = [mb[k] for k in ((cols,) if isinstance(cols, str) else cols)]
+        params = logits if self._policy_cat else mean
+        old_value = mb[names["old_value"]] if clip_vf is not None else None
+
+        def run(params, values, ls):
+            return w.policy_loss(params, values.reshape(-1), action, mb[names["old_logp"]], mb[names["adv"]], mb[names["ret"]],
+                                 mb["mb_weight"], log_std=ls, old_value=old_value, clip=clip, clip_vf=clip_vf, vf_coef=vf_coef,
+                                 ent_coef=ent_coef)
+
+        def fresh(serial):
+            # (the World counts the calls it queued, whoever made them: forward notes its own, backward compares)
+            if serial is not None and w.policy_loss_serial != serial:
+                raise RuntimeError("policy_loss: backward() after a later policy_loss call has rewritten the gradients")
+            return w.policy_loss_serial
+
+        args = (params, values) if self._policy_cat else (params, values, log_std)
+        if any(not isinstance(t, torch.Tensor) for t in args):
+            raise ValueError("policy_loss: the network's outputs are torch tensors")
+        loss = _loss_function().apply(run, fresh, *args)
+        out = w.policy_loss_out
+        info = {k: out["stats"][q] for q, k in enumerate(_cabi.PLOSS_STATS)}
+        B = int(params.shape[0])
+        info.update(n_bad=out["n_bad"], logp=out["logp"][:B], row_entropy=out["entropy"][:B], ratio=out["ratio"][:B], pg=out["pg"][:B],
+                    vl=out["vl"][:B])
+        return loss, info
 
     def rollout(self):
         """``{"n": transitions stored, "resets": reset chains stored, **World.rollout}``: the device tensors as they are -- no

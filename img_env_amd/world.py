@@ -119,6 +119,7 @@ class World:
         self.episode_log_capacity = 0
         self.action_outputs = None  # enable_actions()
         self.policy = None  # enable_policy()
+        self.policy_loss_out = None  # enable_policy_loss()
         self.obs_post = None  # enable_obs_post()
         self.final_obs = None  # enable_final_obs()
         self.rollout = None  # enable_rollout()
@@ -423,7 +424,7 @@ class World:
             self._pol_keep = None
         return self.policy
 
-    def _pol_tensor(self, t, shapes, what):
+    def _pol_tensor(self, t, shapes, what, who="policy_sample"):
         import torch
         if t is None:
             return None
@@ -432,7 +433,7 @@ class World:
         if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
             t = t.to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(t.shape) not in shapes:
-            raise ValueError("policy_sample: %s float32 %s" % (what, " or ".join(str(list(s)) for s in shapes)))
+            raise ValueError("%s: %s float32 %s" % (who, what, " or ".join(str(list(s)) for s in shapes)))
         return t
 
     def policy_sample(self, params, log_std=None, values=None, draw=0, deterministic=False, store=True):
@@ -478,6 +479,97 @@ class World:
         a.values = values.data_ptr() if values is not None else None
         self._pol_value_keep = values
         self._call(self.lib.imgenv_policy_sample(self.h, C.byref(a), self._stream()), "imgenv_policy_sample")
+
+    def enable_policy_loss(self, max_rows):
+        """PPO's loss on the device (``imgenv_policy_loss_enable``; needs ``enable_policy`` first, not the rollout):
+        ``self.policy_loss_out`` maps ``logp``, ``entropy``, ``ratio``, ``pg``, ``vl`` and ``d_values`` float32 ``[max_rows]``,
+        ``d_params`` float32 ``[max_rows * n]`` (row i of a call at ``i * n``, n = A or C: ``policy_loss`` returns the call's
+        ``[rows, n]`` view), for a Gaussian head ``d_log_std`` likewise and ``d_log_std_shared`` ``[C]``, ``stats`` float32 ``[8]``
+        (``_cabi.PLOSS_STATS``), ``n_bad`` int32 ``[1]`` and ``inv_w`` float32 ``[1]`` to zero-copy tensors over the library's memory,
+        filled by ``policy_loss``.  Read-only; valid until ``close()``.  ValueError for a refused cfg or a second call with another
+        ``max_rows``, RuntimeError before ``enable_policy``."""
+        c = _cabi.make_policy_loss_cfg(max_rows)
+        lo = _cabi.PolicyLossOut()
+        self._call(self.lib.imgenv_policy_loss_enable(self.h, C.byref(c), C.byref(lo)), "imgenv_policy_loss_enable")
+        if self.policy_loss_out is None:
+            B, n = lo.max_rows, lo.n_params
+            arrays = {k: (np.float32, (B,)) for k in ("logp", "entropy", "ratio", "pg", "vl", "d_values")}
+            arrays.update(d_params=(np.float32, (B * n,)), d_log_std=(np.float32, (B * n,)), d_log_std_shared=(np.float32, (n,)),
+                          stats=(np.float32, (8,)), n_bad=(np.int32, (1,)), inv_w=(np.float32, (1,)))
+            self.policy_loss_out = self._views(lo, arrays, "imgenv_policy_loss_out")
+            self._ploss_rows = B
+            self._ploss_keep = None
+            self.policy_loss_serial = 0  # calls queued so far: a holder of the outputs' views can tell whether they are still its call's
+        return self.policy_loss_out
+
+    def policy_loss(self, params, values, action, old_logp, adv, ret, weight, log_std=None, old_value=None, clip=0.2, clip_vf=None,
+                    vf_coef=0.5, ent_coef=0.0):
+        """``imgenv_policy_loss``: the network's new outputs ``params`` -- logits float32 ``[B, A]`` or means ``[B, C]`` with
+        ``log_std`` ``[C]`` or ``[B, C]`` -- and ``values`` ``[B]`` against the stored ``action`` (the index as float32 ``[B]``, or
+        a sequence of the C raw columns ``[B]`` each), ``old_logp``, ``adv``, ``ret`` and ``weight`` ``[B]``; ``clip_vf`` (with
+        ``old_value`` ``[B]``) selects the clipped value loss.  Three launches, ordered on the current stream; nothing
+        synchronises.  Returns the call's views of ``policy_loss_out``: the row arrays cut to ``[B]``, ``d_params`` (and
+        ``d_log_std``) as ``[B, n]``, rewritten by the next call (``policy_loss_serial`` counts the calls queued)."""
+        import torch
+        if self.policy_loss_out is None:
+            raise RuntimeError("policy_loss failed (%d): enable_policy_loss was not called" % _cabi.ESTATE)
+        n, cat = self._pol_params, self._pol_cat
+        if not isinstance(params, torch.Tensor):
+            params = torch.as_tensor(np.ascontiguousarray(params, np.float32), device=self.device)
+        if params.dim() != 2 or params.shape[1] != n or not 1 <= params.shape[0] <= self._ploss_rows:
+            raise ValueError("policy_loss: %s float32 [B, %d] with B in 1 .. %d" % ("logits" if cat else "mean", n, self._ploss_rows))
+        B = int(params.shape[0])
+        cols = [action] if cat else list(action)
+        if len(cols) != (1 if cat else n):
+            raise ValueError("policy_loss: action is %s" % ("the index, float32 [B]" if cat else "%d raw columns, float32 [B] each" % n))
+        a = _cabi.PolicyLossArgs()
+        a.struct_size = C.sizeof(_cabi.PolicyLossArgs)
+        a.rows = B
+        params = self._pol_tensor(params, [(B, n)], "params", "policy_loss")
+        keep = [params]
+        for name, t in (("values", values), ("old_logp", old_logp), ("adv", adv), ("ret", ret), ("weight", weight)):
+            t = self._pol_tensor(t, [(B,)], name, "policy_loss")
+            if t is None:
+                raise ValueError("policy_loss: %s is missing" % name)
+            setattr(a, name, t.data_ptr())
+            keep.append(t)
+        for q, t in enumerate(cols):
+            t = self._pol_tensor(t, [(B,)], "action", "policy_loss")
+            if t is None:
+                raise ValueError("policy_loss: action is missing")
+            a.action[q] = t.data_ptr()
+            keep.append(t)
+        a.params = params.data_ptr()
+        if not cat:
+            log_std = self._pol_tensor(log_std, [(n,), (B, n)], "log_std", "policy_loss")
+            if log_std is None:
+                raise ValueError("policy_loss: log_std is missing")
+            if log_std.dim() == 2:
+                a.flags |= _cabi.POLICY_LOG_STD_PER_ROW
+            a.log_std = log_std.data_ptr()
+            keep.append(log_std)
+        if clip_vf is not None:
+            old_value = self._pol_tensor(old_value, [(B,)], "old_value", "policy_loss")
+            if old_value is None:
+                raise ValueError("policy_loss: clip_vf needs old_value")
+            a.flags |= _cabi.PLOSS_CLIP_VALUE
+            a.old_value = old_value.data_ptr()
+            a.clip_vf = float(clip_vf)
+            keep.append(old_value)
+        a.clip, a.vf_coef, a.ent_coef = float(clip), float(vf_coef), float(ent_coef)
+        # (kept until the next call: the launches read them in stream order, a tensor made here from host data must outlive them)
+        self._ploss_keep = keep
+        self._call(self.lib.imgenv_policy_loss(self.h, C.byref(a), self._stream()), "imgenv_policy_loss")
+        self.policy_loss_serial += 1  # (behind every refusal: a refused call rewrites nothing)
+        out = {}
+        for k, t in self.policy_loss_out.items():
+            if k in ("d_params", "d_log_std"):
+                out[k] = t[:B * n].view(B, n)
+            elif k in ("logp", "entropy", "ratio", "pg", "vl", "d_values"):
+                out[k] = t[:B]
+            else:
+                out[k] = t
+        return out
 
     def enable_obs_post(self, ped_norm=True, close=None, avg=_cabi.PED_NORM_AVG, std=_cabi.PED_NORM_STD, close_dist=_cabi.CLOSE_DIST):
         """Device-side StatePedVectorWrapper and ``bool_get_close_to_human`` (``imgenv_obs_post_enable``): from now on every reset /
@@ -962,7 +1054,7 @@ class World:
     def close(self):
         if getattr(self, "h", None):
             self.episodes = self.episode_log = self.action_outputs = self.obs_post = self.final_obs = self.rollout = self.minibatch = None  # (views of memory the handle owns)
-            self.normalise = self.policy = None
+            self.normalise = self.policy = self.policy_loss_out = None
             self.lib.imgenv_destroy(self.h)
             self.h = None
 

@@ -777,6 +777,92 @@ int imgenv_policy_outputs(imgenv_t* h, imgenv_policy_out* out);
  * misaligned values. */
 int imgenv_policy_sample(imgenv_t* h, const imgenv_policy_args* args, void* stream);
 
+/* ---- PPO's loss: log-probabilities of STORED actions under new parameters, the loss and its gradients, on the device ----
+ * For every minibatch of every epoch a trainer evaluates the stored actions under the network's new outputs and needs the
+ * clipped-surrogate loss and its gradient on those outputs.  imgenv_policy_loss queues THREE launches (k_ploss_*,
+ * csrc/policy_loss.h: the rows, one fold, the gradients) on the caller's stream, without atomics and in a fixed order of every
+ * sum: two calls give identical bits.  Opt-in: a handle that never enables it allocates and launches exactly what it did; the
+ * launches are no part of a step and are not counted in imgenv_step_launches.
+ *
+ * Over the B = args.rows rows, row i with weight w_i (imgenv_minibatch_out.mb_weight), in float32 per row, float64 in the sums:
+ *   W        = max(sum_i w_i, 1)
+ *   logp_i, H_i   log-probability of the stored action and entropy under the new parameters -- CATEGORICAL: imgenv_policy_sample's
+ *              arithmetic on the same lanes (unchanged logits give the stored logp bit for bit; a -inf logit has p = 0 and adds
+ *              nothing to H); GAUSSIAN: z = (raw - mean) / expf(log_std), logp = sum_c (-0.5 z^2 - log_std - 0.5 ln 2 pi),
+ *              H = sum_c (0.5 + 0.5 ln 2 pi + log_std)
+ *   r_i      = expf(logp_i - old_logp_i)
+ *   pg_i     = -min(r_i adv_i, clamp(r_i, 1 - clip, 1 + clip) adv_i)
+ *   vl_i     = 0.5 (v_i - ret_i)^2, or with IMGENV_PLOSS_CLIP_VALUE 0.5 max((v_i - ret_i)^2, (vc_i - ret_i)^2),
+ *              vc_i = old_v_i + clamp(v_i - old_v_i, -clip_vf, clip_vf)
+ *   loss     = sum_i w_i (pg_i + vf_coef vl_i - ent_coef H_i) / W
+ *   stats[8] = loss, sum w pg / W, sum w vl / W, sum w H / W, sum w ((r - 1) - ln r) / W (approximate KL),
+ *              sum w [|r - 1| > clip] / W (clip fraction), sum w (unclamped), 0
+ * and the gradients of loss, closed forms: with active_i = (r_i adv_i <= clamp(r_i) adv_i), g_i = (w_i / W)(active_i ? -adv_i r_i : 0),
+ * gH_i = -ent_coef w_i / W:
+ *   CATEGORICAL  d_params[i][k] = g_i ([k == a_i] - p_ik) - gH_i p_ik (ln p_ik + H_i); a masked k gets exactly 0
+ *   GAUSSIAN     d_params[i][c] = g_i z_ic / sigma_c;  d_log_std[i][c] = g_i (z_ic^2 - 1) + gH_i;  d_log_std_shared[c] = their sum
+ *                over the rows (what a shared log_std [C] receives)
+ *   d_values[i]  = vf_coef (w_i / W) (v_i - ret_i); with CLIP_VALUE where the clipped square is strictly the larger:
+ *                vf_coef (w_i / W) (vc_i - ret_i) [|v_i - old_v_i| <= clip_vf]
+ * A row is BAD with a NaN or +inf parameter, no finite logit, a stored action that is no integer in [0, A) or is masked (-inf)
+ * under the new logits, a Gaussian log_std whose sigma or z is not finite, or a non-finite old_logp, adv, ret, value, old value,
+ * ratio or weight.  A bad row and a row of weight 0 (the slots behind a minibatch's valid list) count as weight 0 and every
+ * output and gradient of theirs is +0; n_bad, written fresh by every call, counts the bad rows whose own weight was not 0. */
+#define IMGENV_PLOSS_CLIP_VALUE 1        /* args.flags (beside IMGENV_POLICY_LOG_STD_PER_ROW = 2) */
+typedef struct imgenv_policy_loss_cfg {
+    int32_t struct_size;          /* sizeof(imgenv_policy_loss_cfg) */
+    int32_t max_rows;             /* the largest B of a call, >= 1 */
+    int32_t reserved[2];          /* 0 */
+} imgenv_policy_loss_cfg;
+/* Device pointers; owned by the handle, valid until imgenv_destroy(), contents valid once the stream work of the last
+ * imgenv_policy_loss has completed (rows [0, args.rows) of the row arrays), READ-ONLY for the caller. */
+typedef struct imgenv_policy_loss_out {
+    int32_t struct_size;          /* on entry 0 or sizeof(imgenv_policy_loss_out) */
+    int32_t n_params;             /* A or C */
+    int32_t max_rows;
+    int32_t reserved;
+    float* logp;                  /* [max_rows] */
+    float* entropy;               /* [max_rows] */
+    float* ratio;                 /* [max_rows] */
+    float* pg;                    /* [max_rows] */
+    float* vl;                    /* [max_rows] */
+    float* d_params;              /* [max_rows][A | C], rows packed: row i at i * n_params */
+    float* d_log_std;             /* [max_rows][C]  GAUSSIAN; NULL for CATEGORICAL */
+    float* d_log_std_shared;      /* [C]            GAUSSIAN; NULL for CATEGORICAL */
+    float* d_values;              /* [max_rows] */
+    float* stats;                 /* [8] */
+    int32_t* n_bad;               /* [1] */
+    float* inv_w;                 /* [1] (float)(1 / W) */
+} imgenv_policy_loss_out;
+typedef struct imgenv_policy_loss_args {
+    int32_t struct_size;          /* sizeof(imgenv_policy_loss_args) */
+    int32_t flags;                /* IMGENV_PLOSS_CLIP_VALUE | IMGENV_POLICY_LOG_STD_PER_ROW */
+    int32_t rows;                 /* B: 1 .. max_rows */
+    int32_t reserved;             /* 0 */
+    const float* params;          /* the network's NEW outputs, DEVICE f32: logits [B][A] | mean [B][C] */
+    const float* log_std;         /* [C] or [B][C]; GAUSSIAN only */
+    const float* values;          /* [B] */
+    const float* action[3];       /* [B] each: the index as float32 (pol_raw) | the C raw columns; the rest NULL */
+    const float* old_logp;        /* [B] */
+    const float* old_value;       /* [B]; NULL without IMGENV_PLOSS_CLIP_VALUE */
+    const float* adv;             /* [B] */
+    const float* ret;             /* [B] */
+    const float* weight;          /* [B] */
+    float clip, clip_vf, vf_coef, ent_coef;
+} imgenv_policy_loss_args;
+/* Legal once imgenv_policy_enable() has been called (IMGENV_ESTATE before it); it does not need the rollout.  One all-or-nothing
+ * block, every array on a 256-byte boundary.  IMGENV_EINVAL for a wrong struct_size, max_rows < 1, reserved != 0 or a second
+ * call whose cfg differs (same cfg: nothing changes, same pointers).  IMGENV_ENOMEM leaves the handle as it was.  `out` may be NULL. */
+int imgenv_policy_loss_enable(imgenv_t* h, const imgenv_policy_loss_cfg* cfg, imgenv_policy_loss_out* out);
+/* IMGENV_ESTATE before imgenv_policy_loss_enable() */
+int imgenv_policy_loss_outputs(imgenv_t* h, imgenv_policy_loss_out* out);
+/* The [B] inputs are what imgenv_rollout_minibatch leaves in mb_scalars' rows and mb_weight.  Pointers are DEVICE pointers,
+ * contiguous, 4-byte aligned, valid until the launches have run.  IMGENV_ESTATE before imgenv_policy_loss_enable(); IMGENV_EINVAL
+ * for a wrong struct_size, an unknown flag, reserved != 0, rows out of 1 .. max_rows, a null or misaligned pointer (log_std for
+ * GAUSSIAN, old_value with CLIP_VALUE, action[c] for c < 1 | C), clip < 0 or NaN, clip_vf < 0 or NaN with CLIP_VALUE, and
+ * LOG_STD_PER_ROW on a categorical head.  Nothing is queued on failure. */
+int imgenv_policy_loss(imgenv_t* h, const imgenv_policy_loss_args* args, void* stream);
+
 /* ---- observation post-processing: StatePedVectorWrapper (envs/wrapper/base.py:19-34) and InfoLogWrapper's
  * bool_get_close_to_human (base.py:250-252) for every local robot, on the device ----
  * One extra launch at the end of every chain (k_obs_post, csrc/obs_post.h; behind the stacks and the episode statistics): a step

@@ -20,6 +20,9 @@ the library (VecImageEnv(normalise={...}), imgenv_normalise_enable: two more lau
 --policy-compare alternates, with the device-side reset, wrappers=True and rollout=--horizon, the hop from logits over 11 actions
 to the stepped env done by the policy head (VecImageEnv(policy={...}).policy_step: one launch instead of the decode's) / by
 torch.distributions.Categorical (sample, log_prob, entropy, three stores into [T, n] tensors, then step on the indices).
+--loss-compare alternates, in one process, PPO's loss of one real minibatch of --batch rows -- from logits over 11 actions and
+values on the device to the gradients on them -- done by VecImageEnv(policy=dict(seed=s, loss=True)).policy_loss and backward()
+(imgenv_policy_loss: three launches) / by the same loss in torch ops and autograd; the two gradients are compared first.
 
 --rollout-compare runs device_reset steps three ways, one process per measurement, alternating over several rounds: no rollout
 storage, the library's (VecImageEnv(rollout=--horizon), imgenv_rollout_enable: one more launch per chain, a new window every
@@ -992,6 +995,97 @@ def compare_minibatch(args, rounds=3):
                 batch=args.batch, rounds=rounds, runs=runs, summary=summary)
 
 
+def compare_loss(args, rounds=3, window=0.6):
+    """PPO's loss of one minibatch, from logits and values on the device to the gradients on them: ``VecImageEnv.policy_loss`` and
+    ``backward()`` ("library": three launches and the autograd hand-over; "library_raw": ``World.policy_loss`` alone, whose
+    outputs are the gradients) / the same loss in torch ops and autograd ("torch"), on the same commit, alternating, `rounds`
+    times in one process.  The minibatch is a real one: a window of ``--horizon`` policy steps over 11 actions, advantages from the
+    library, ``--batch`` rows, the clipped value loss and an entropy bonus.  us per loss; every measurement runs as many losses
+    back to back as fill `window` seconds (counted from a short calibration run of the variant), then synchronises once: the
+    figure is the cost of a loss in a stream of losses, the host's enqueue included, not a single call's latency."""
+    import numpy as np
+    import torch
+    from img_env_amd import worldgen
+    from img_env_amd.vec_env import VecImageEnv
+    grid = worldgen.make_grid(200, 2)
+    A, T, n, B = 11, args.horizon, args.envs * args.robots, args.batch
+    table = [[0.06 * k, 0.18 * (k - 5)] for k in range(A)]
+    cfg = worldgen.make_yaml_cfg(args.robots, args.peds, grid, time_max=args.time_max, n_obstacles=args.obstacles, seed=5, discrete_action=True,
+                                 discrete_actions=table)
+    env = VecImageEnv(cfg, env_num=args.envs, seed=5, device_reset=True, wrappers=True, rollout=T, rollout_final=n, minibatch=B,
+                      policy=dict(seed=7, loss=True))
+    g = torch.Generator(device="cuda").manual_seed(1)
+    env.reset()
+    for s in range(T):
+        env.policy_step(logits=torch.randn(n, A, generator=g, device="cuda"), values=torch.randn(n, generator=g, device="cuda"))
+    env.policy_value(torch.randn(n, generator=g, device="cuda"))
+    ro = env.rollout()
+    adv, ret = env.rollout_advantages(ro["pol_value"], None, 0.99, 0.95)
+    scalars = dict(action=ro["pol_raw"][0], old_logp=ro["pol_logp"], old_value=ro["pol_value"], adv=adv, ret=ret)
+    mb = next(iter(env.rollout_minibatches(scalars, 3, normalise="adv")))
+    logits = (torch.randn(B, A, generator=g, device="cuda") * 0.5).requires_grad_()
+    values = (mb["old_value"] + 0.3 * torch.randn(B, generator=g, device="cuda")).requires_grad_()
+    clip, clip_vf, vf, ent = 0.2, 0.2, 0.5, 0.01
+    act = mb["action"].to(torch.int64)
+
+    def library():
+        logits.grad = values.grad = None
+        loss, _ = env.policy_loss(mb, logits=logits, values=values, clip=clip, vf_coef=vf, ent_coef=ent, clip_vf=clip_vf)
+        loss.backward()
+
+    def library_raw():
+        env.world.policy_loss(logits.detach(), values.detach(), mb["action"], mb["old_logp"], mb["adv"], mb["ret"], mb["mb_weight"],
+                              old_value=mb["old_value"], clip=clip, clip_vf=clip_vf, vf_coef=vf, ent_coef=ent)
+
+    def torch_ops():
+        logits.grad = values.grad = None
+        w = mb["mb_weight"]
+        ls = torch.log_softmax(logits, 1)
+        logp = ls.gather(1, act[:, None])[:, 0]
+        H = -(ls.exp() * ls).sum(1)
+        r = (logp - mb["old_logp"]).exp()
+        pg = -torch.min(r * mb["adv"], r.clamp(1 - clip, 1 + clip) * mb["adv"])
+        vc = mb["old_value"] + (values - mb["old_value"]).clamp(-clip_vf, clip_vf)
+        vl = 0.5 * torch.max((values - mb["ret"]) ** 2, (vc - mb["ret"]) ** 2)
+        W = w.sum().clamp(min=1)
+        loss = (w * (pg + vf * vl - ent * H)).sum() / W
+        loss.backward()
+    fns = dict(library=library, library_raw=library_raw, torch=torch_ops)
+    # the two agree before they are timed
+    library()
+    got = (logits.grad.clone(), values.grad.clone())
+    torch_ops()
+    agree = dict(d_logits=float((got[0] - logits.grad).abs().max().item()), d_values=float((got[1] - values.grad).abs().max().item()),
+                 weight_sum=float(mb["mb_weight"].sum().item()))
+    def timed(fn, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    iters = {}
+    for variant, fn in fns.items():  # warm up, then size the window
+        timed(fn, 50)
+        iters[variant] = max(300, int(window * 200 / timed(fn, 200)))
+    runs = []
+    for rnd in range(rounds):
+        for variant, fn in fns.items():
+            timed(fn, 20)
+            dt = timed(fn, iters[variant])
+            runs.append(dict(round=rnd, variant=variant, us_per_loss=1e6 * dt / iters[variant], losses=iters[variant], seconds=dt))
+            print(json.dumps(runs[-1]), flush=True)
+    env.close()
+    summary = {}
+    for variant in fns:
+        v = [x["us_per_loss"] for x in runs if x["variant"] == variant]
+        summary[variant] = dict(us_per_loss_rounds=v, median=float(np.median(v)), spread=max(v) - min(v))
+    summary["torch_minus_library_us"] = summary["torch"]["median"] - summary["library"]["median"]
+    summary["sum_of_spreads_us"] = summary["torch"]["spread"] + summary["library"]["spread"]
+    summary["agreement"] = agree
+    return dict(envs=args.envs, robots_per_env=args.robots, actions=A, horizon=T, batch=B, window_s=window, losses=iters, rounds=rounds, runs=runs, summary=summary)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
@@ -1042,6 +1136,8 @@ def main():
                          "from torch ops, alternating over --rounds rounds; one process per measurement")
     ap.add_argument("--minibatch-variant", default=None, choices=("library", "torch"), help="one measurement of --minibatch-compare")
     ap.add_argument("--batch", type=int, default=4096, help="--minibatch-compare: transitions per minibatch")
+    ap.add_argument("--loss-compare", action="store_true",
+                    help="PPO's loss of a minibatch and its gradients: policy_loss / torch ops and autograd, alternating over --rounds rounds in one process")
     ap.add_argument("--tree", default=None, help="import img_env_amd from this checkout instead of the tool's own")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None, help="--stack-compare / --episodes-compare: also write the JSON here")
@@ -1053,6 +1149,13 @@ def main():
     if args.minibatch_variant:
         print(json.dumps(measure_minibatch(args.minibatch_variant, args.envs, args.robots, args.peds, args.obstacles, args.time_max, args.horizon,
                                            args.batch)))
+        return
+    if args.loss_compare:
+        res = compare_loss(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
         return
     if args.minibatch_compare:
         res = compare_minibatch(args, args.rounds)

@@ -41,6 +41,9 @@
 #include "spawn_slot.h"
 #include "bank_host.h"
 #include "normalise.h"
+#include "feature_plan.h"
+
+static_assert(OBS_POST_PLAN_DIM == OBS_POST_DIM, "feature_plan.h against obs_post.h");
 
 static thread_local char g_err[512] = "";
 #define FAIL(code, ...)                              \
@@ -54,11 +57,15 @@ static thread_local char g_err[512] = "";
         if (e_ != hipSuccess) FAIL(IMGENV_EDEVICE, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-// a minibatch buffer's pointers: the public struct and, behind it, those of the normalised fields (imgenv_normalise_out.mb_norm_*)
-struct MbBufferAll {
-    imgenv_minibatch_buffer pub;
-    float* mb_norm_vector_states;
-    float* mb_norm_state_stack;
+// What the handle keeps of one optional feature (struct imgenv below has one record per feature, some with cursors of their own).
+// Per member: who sets it / who clears it / what it means while set.
+struct NoCfg {};  // (a feature whose repeated call is judged without a stored cfg)
+template <typename Dev, typename Cfg, typename Out>
+struct Feature {
+    bool on = false;  // enable_done / never / imgenv_X_enable has succeeded: dev, cfg and out are valid
+    Dev dev = {};     // imgenv_X_enable, just before enable_done / never / the kernel arguments the launches copy and complete
+    Cfg cfg = {};     // likewise / never / the cfg of the first call: what a repeated call is compared against
+    Out out = {};     // enable_done / never (a later enable may add a normalised field's pointer to norm.out) / what imgenv_X_outputs and a repeated enable hand back
 };
 
 struct imgenv {
@@ -186,6 +193,8 @@ struct imgenv {
         uint32_t gate_seq = 0;     // imgenv_step_begin counts the early steps / never / the number k_integrate opens the gate with and k_gate waits for (world.h: sync)
         unsigned orca_seq = 0;     // launch_side counts k_orca over every world / never / ped_snap's turn; 0: no snapshot yet
         unsigned view_seq = 0;     // launch_compose_views counts k_view over every world / never / rec_snap's turn
+        bool obs_exists = false;   // launch_views' end / never / a chain has completed on this handle: its output rows hold an observation (the features only read it)
+        uint64_t chain_seq = 0;    // launch_views and imgenv_rollout_begin count / never / chains and rollout windows queued so far: a minibatch index is of one value
     } step;
     // The social-force crowd a step AHEAD (sfm.h: SfmDev *_out): crowds that ignore the robots (relation_ped_robo = 0) depend on
     // nothing of a step, so k_sfm for step t + 1 runs on a stream of its own underneath step t's rasters and views, reads the
@@ -257,68 +266,52 @@ struct imgenv {
     int n_spans = 0, span_blocks = 0;
     unsigned long long* d_sums = nullptr;  // ... and their checksums: [2][n_spans], sealed | found at the next call
     const char* span_name[40];
-    // observation stacks (include/imgenv.h: imgenv_stack_enable; csrc/stack.h)
-    bool stack_on = false;       // imgenv_stack_enable has been called
-    StackDev stack;              // n_fields == 0: every depth is 0 or 1, nothing to launch
-    imgenv_stack_out stack_out;
-    // episode statistics (include/imgenv.h: imgenv_episodes_enable; csrc/episodes.h)
-    bool ep_on = false;          // imgenv_episodes_enable has been called
-    EpisodesDev ep;
-    imgenv_episodes_cfg ep_cfg;
-    imgenv_episodes_out ep_out;
-    size_t ep_clear_bytes = 0;   // what imgenv_episodes_clear zeroes, from ep.f on
-    // episode log (include/imgenv.h: imgenv_episode_log_enable; csrc/episode_log.h)
-    bool eplog_on = false;
-    EpisodeLogDev eplog;
-    imgenv_episode_log_out eplog_out;
-    // action decoding (include/imgenv.h: imgenv_actions_enable; csrc/actions.h)
-    bool act_on = false;         // imgenv_actions_enable has been called
-    ActionsDev act;
-    imgenv_actions_cfg act_cfg;  // (its table pointer is not kept: act_table is the copy)
-    std::vector<float> act_table;
-    imgenv_actions_out act_out;
-    int decode_launches = 0;     // k_actions / k_policy launches since the last step: they count with the step that consumes them
-    // the policy head (include/imgenv.h: imgenv_policy_enable; csrc/policy.h)
-    bool pol_on = false;
-    PolicyDev pol;               // what every launch shares; params, draw, flags and the slot's pointers are the call's
-    imgenv_policy_cfg pol_cfg;
-    imgenv_policy_out pol_out;
-    // PPO's loss (include/imgenv.h: imgenv_policy_loss_enable; csrc/policy_loss.h)
-    bool ploss_on = false;
-    PlossDev ploss;              // what every call shares: the handle's arrays; inputs, coefficients and rows are the call's
-    imgenv_policy_loss_cfg ploss_cfg;
-    imgenv_policy_loss_out ploss_out;
-    // observation post-processing (imgenv_obs_post_enable; csrc/obs_post.h)
-    bool post_on = false;
-    ObsPostDev post;
-    imgenv_obs_post_cfg post_cfg;
-    imgenv_obs_post_out post_out;
-    // final observations (imgenv_final_obs_enable; csrc/final_obs.h)
-    bool final_on = false;
-    bool obs_exists = false;     // a chain of launches has completed on this handle: its output rows hold an observation
-    FinalObsDev final_dev;
-    imgenv_final_obs_cfg final_cfg;
-    imgenv_final_obs_out final_out;
-    // rollout storage (imgenv_rollout_enable; csrc/rollout.h)
-    bool roll_on = false;
-    bool roll_begun = false;     // imgenv_rollout_begin has been called: chains store
-    int roll_n = 0;              // the cursor: transitions stored since the last begin
-    uint32_t roll_turn = 0;      // reset chains stored since the last begin
-    RolloutDev roll;
-    size_t roll_row_bytes[ROLLOUT_TABLE_FIELDS];
-    int roll_field_id[ROLLOUT_TABLE_FIELDS];  // which field (obs_fields.h) entry k of roll.f is
-    imgenv_rollout_cfg roll_cfg;
-    imgenv_rollout_out roll_out;
-    // rollout minibatches (imgenv_rollout_minibatch_enable; csrc/minibatch.h)
-    bool mb_on = false;
-    uint64_t chain_seq = 0;      // chains (and imgenv_rollout_begin calls) queued on the handle so far
-    bool mb_indexed = false;     // imgenv_rollout_index has run; its generation:
-    int mb_gen_n = 0;
-    uint64_t mb_gen_seq = 0;
-    bool mb_shuffled = false;    // imgenv_rollout_shuffle has run on that index
-    MbGatherDev mb_gather;       // the field table and the ring's scalars; dst pointers are the buffer's (mb_out)
-    imgenv_minibatch_cfg mb_cfg;
-    imgenv_minibatch_out mb_out;
+    // The optional features (include/imgenv.h: imgenv_*_enable): one record each -- Feature's four members and the
+    // feature's own host cursors.  What an enable call decides before it touches the device is feature_plan.h's, from
+    // feature_facts(h).  Per member: who sets it / who clears it / what it means while set.
+    // observation stacks (csrc/stack.h); dev.n_fields == 0: every depth is 0 or 1, nothing to launch
+    Feature<StackDev, NoCfg, imgenv_stack_out> stack;
+    // episode statistics (csrc/episodes.h)
+    struct Episodes : Feature<EpisodesDev, imgenv_episodes_cfg, imgenv_episodes_out> {
+        size_t clear_bytes = 0;      // imgenv_episodes_enable / never / what imgenv_episodes_clear zeroes, from dev.f on
+    } ep;
+    // episode log (csrc/episode_log.h); its capacity is dev's
+    Feature<EpisodeLogDev, NoCfg, imgenv_episode_log_out> eplog;
+    // action decoding (csrc/actions.h)
+    struct Actions : Feature<ActionsDev, imgenv_actions_cfg, imgenv_actions_out> {
+        std::vector<float> table;    // imgenv_actions_enable / never / the rows of a TABLE cfg: cfg.table is null, a repeated call is compared against this copy
+        int decode_launches = 0;     // imgenv_actions_decode, imgenv_policy_sample count / step_entry / k_actions and k_policy launches since the last step: they count with the step that consumes them
+    } act;
+    // the policy head (csrc/policy.h); dev is what every launch shares: params, draw, flags and the slot's pointers are the call's
+    Feature<PolicyDev, imgenv_policy_cfg, imgenv_policy_out> pol;
+    // PPO's loss (csrc/policy_loss.h); dev is the handle's arrays: inputs, coefficients and rows are the call's
+    Feature<PlossDev, imgenv_policy_loss_cfg, imgenv_policy_loss_out> ploss;
+    // observation post-processing (csrc/obs_post.h)
+    Feature<ObsPostDev, imgenv_obs_post_cfg, imgenv_obs_post_out> post;
+    // final observations (csrc/final_obs.h)
+    Feature<FinalObsDev, imgenv_final_obs_cfg, imgenv_final_obs_out> final_obs;
+    // rollout storage (csrc/rollout.h)
+    struct Rollout : Feature<RolloutDev, imgenv_rollout_cfg, imgenv_rollout_out> {
+        bool begun = false;          // imgenv_rollout_begin / imgenv_rollout_enable / a window is open: chains store
+        int n = 0;                   // tail_rollout counts the step chains / imgenv_rollout_begin / the cursor: transitions stored in this window
+        uint32_t turn = 0;           // tail_rollout counts the reset chains / imgenv_rollout_begin / reset chains stored in this window
+        size_t row_bytes[ROLLOUT_TABLE_FIELDS];  // imgenv_rollout_enable / never / the row of entry k of dev.f ...
+        int field_id[ROLLOUT_TABLE_FIELDS];      // ... and which field (obs_fields.h) it is
+    } roll;
+    // rollout minibatches (csrc/minibatch.h); dev holds the field table and the ring's scalars, its dst pointers are the call's buffer's
+    struct Minibatch : Feature<MbGatherDev, imgenv_minibatch_cfg, imgenv_minibatch_out> {
+        bool indexed = false;        // imgenv_rollout_index / imgenv_rollout_minibatch_enable / the valid list exists, of the generation (gen_n, gen_seq)
+        int gen_n = 0;               // imgenv_rollout_index / never / roll.n when the index was made
+        uint64_t gen_seq = 0;        // imgenv_rollout_index / never / step.chain_seq then: any chain or window since makes the index stale
+        bool shuffled = false;       // imgenv_rollout_shuffle / imgenv_rollout_index / `order` is a permutation of that index
+        unsigned char* dst[IMGENV_MB_MAX_BUFFERS][ROLLOUT_TABLE_FIELDS];  // imgenv_rollout_minibatch_enable / never / where buffer b keeps entry k of dev.f, the normalised fields included
+    } mb;
+    // running normalisation (csrc/normalise.h); dev.n_obs as enabled: n_ret, cols, update, the turns and the rows are the launch's
+    struct Normalise : Feature<NormDev, imgenv_normalise_cfg, imgenv_normalise_out> {
+        bool training = true;        // imgenv_normalise_enable, imgenv_normalise_training / the latter / the chains update the statistics
+        uint32_t turn = 0;           // tail_normalise counts / never / chains that have moved the statistics: which word of dev.stats is read
+        uint32_t ret_turn = 0;       // tail_normalise counts / never / step chains that have moved the returns: which word of dev.returns is read
+    } norm;
     std::vector<RvoObstacles> rvos;  // one obstacle set per world
     int sfm_cap_obs = 0;
     std::vector<int> sfm_nobs_w;  // pedscene, several worlds: obstacle segments of each world's crowd
@@ -330,15 +323,6 @@ struct imgenv {
     size_t t_used = 0;
     double t_ms[IMGENV_K_COUNT] = {0};
     int64_t t_cnt[IMGENV_K_COUNT] = {0};
-    // running normalisation (imgenv_normalise_enable; csrc/normalise.h)
-    bool norm_on = false;
-    bool norm_training = true;   // the chains update the statistics (imgenv_normalise_training)
-    uint32_t norm_turn = 0;      // chains that have moved the statistics: which word of NormDev::stats is read
-    uint32_t norm_ret_turn = 0;  // step chains that have moved the returns: which word of NormDev::returns is read
-    NormDev norm;                // n_obs as enabled; n_ret, cols, update, the turns and the rows are the launch's
-    imgenv_normalise_cfg norm_cfg;
-    imgenv_normalise_out norm_out;
-    MbBufferAll mb_all[IMGENV_MB_MAX_BUFFERS];  // the minibatch buffers' pointers, the normalised fields' included (mb_out.buf holds the public part)
 };
 
 // RCCL is resolved at run time so that single-GPU users do not need it: prefer the copy the process already
@@ -522,8 +506,8 @@ static int dev_upload(imgenv* h, const T** out, const std::vector<T>& v) {
     *out = p;
     return 0;
 }
-// DevTxn (bank_host.h) over the device: what imgenv_maps_add, imgenv_tracks_add, imgenv_scenarios_add, imgenv_episode_log_enable and
-// imgenv_final_obs_enable allocate through, each committing to h->allocs once everything is there
+// DevTxn (bank_host.h) over the device: what imgenv_maps_add, imgenv_tracks_add, imgenv_scenarios_add and the features' enables
+// allocate through, each committing to h->allocs once everything is there
 struct HipApi {
     static const char* text(hipError_t e) { return e == hipSuccess ? nullptr : ((void)hipGetLastError(), hipGetErrorString(e)); }
     static const char* malloc(void** p, size_t bytes) { return text(hipMalloc(p, bytes)); }
@@ -1585,8 +1569,8 @@ static TailRows tail_rows(const imgenv* h, int is_reset) {
 
 // A step on a handle whose rollout storage holds its whole horizon: refused by every step entry point before it queues anything
 static int rollout_room(const imgenv* h) {
-    if (h->roll_on && h->roll_begun && h->roll_n >= h->roll_cfg.horizon)
-        FAIL(IMGENV_EINVAL, "rollout full: imgenv_rollout_begin (all %d transitions of the horizon are stored)", h->roll_cfg.horizon);
+    if (h->roll.on && h->roll.begun && h->roll.n >= h->roll.cfg.horizon)
+        FAIL(IMGENV_EINVAL, "rollout full: imgenv_rollout_begin (all %d transitions of the horizon are stored)", h->roll.cfg.horizon);
     return 0;
 }
 
@@ -1611,7 +1595,7 @@ static constexpr int CHAIN_FIXED_LAUNCHES = 3;
 // covers, as the last step left them.  What a reset chain has launched before this point (the staged copies and map restores,
 // k_respawn and the rest of the device-side reset) writes none of them.
 static int launch_final_obs(imgenv* h, hipStream_t st) {
-    FinalObsDev fo = h->final_dev;
+    FinalObsDev fo = h->final_obs.dev;
     fo.rows = tail_rows(h, 1);
     const PlanChain cf = chain_facts(h, 1);
     const int guess = cf.n_dev ? plan_dev_reset(h->plan, h->finished_host[0], 0).guess : 0;
@@ -1712,7 +1696,7 @@ static void launch_tails(imgenv* h, hipStream_t st, const ChainPlans& k) {
 // SUM shard's.
 static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
     set_tail_fields(h, is_reset, h->elapsed);
-    if (is_reset && h->final_on && h->obs_exists) RTRY(launch_final_obs(h, st));
+    if (is_reset && h->final_obs.on && h->step.obs_exists) RTRY(launch_final_obs(h, st));
     if (h->P == 0) RTRY(chain_begin(h, st));
     ChainPlans k;
     k.is_reset = is_reset;
@@ -1738,8 +1722,8 @@ static int launch_views(imgenv* h, hipStream_t st, int is_reset) {
     launch_tails(h, st, k);
     HIPCHK(hipGetLastError());  // 9. finish and seal
     h->step.chain_open = false;
-    h->obs_exists = true;
-    h->chain_seq += 1;
+    h->step.obs_exists = true;
+    h->step.chain_seq += 1;
     return outputs_seal(h, st);
 }
 
@@ -2868,8 +2852,8 @@ static int step_entry(imgenv* h, const float* actions, hipStream_t st) {
     // ended -- the caller's exchange failed -- must not read as "the caller wrote into imgenv_out" at the reset that recovers it)
     h->guard_sealed = false;
     h->step.actions = actions;
-    h->launches = h->decode_launches;  // (imgenv_actions_decode in front of this step)
-    h->decode_launches = 0;
+    h->launches = h->act.decode_launches;  // (imgenv_actions_decode in front of this step)
+    h->act.decode_launches = 0;
     return 0;
 }
 
@@ -3521,24 +3505,57 @@ extern "C" int imgenv_outputs(imgenv_t* h, imgenv_out* out) {
     return IMGENV_OK;
 }
 
-// ---- what the enable / outputs entry points of the optional features (stacks, episode statistics, action decoding, observation
-// post-processing) share ----
-// the cfg and the caller's out struct of an enable call, before the handle is looked at: these refusals need no device.  An out
-// struct says 0 or this library's size.
-template <typename Cfg, typename Out>
-static int enable_args(const Cfg* c, const char* cfg_name, const Out* out, const char* out_name) {
-    if (!c) FAIL(IMGENV_EINVAL, "null argument");
-    if (c->struct_size != (int32_t)sizeof(Cfg)) FAIL(IMGENV_EINVAL, "%s.struct_size %d (this library's is %d)", cfg_name, c->struct_size, (int)sizeof(Cfg));
-    if (out && out->struct_size != 0 && out->struct_size != (int32_t)sizeof(Out)) FAIL(IMGENV_EINVAL, "%s.struct_size", out_name);
+// ---- what the enable / outputs entry points of the optional features share ----
+// Every enable has one shape: feature_plan.h's X_enable_plan (the cfg's refusals, the null handle, the repeated call, the refusals
+// that read the facts) -> the block's layout (launch_plan.h) -> ONE DevTxn -> fill dev and out -> enable_done.  Nothing of the
+// handle changes before the transaction has committed.
+// the facts the plan reads of this handle; nullptr for a null handle
+static const FeatureFacts* feature_facts(const imgenv* h, FeatureFacts& f) {
+    if (!h) return nullptr;
+    f.RL = h->RL; f.P = h->P; f.state_dim = h->out.state_dim; f.ped_vec_dim = h->cfg.ped_vec_dim; f.n_beams = h->out.n_beams;
+    f.keep_view_maps = h->d.keep_view_maps != 0;
+    f.any_reset = any_world_reset(h);
+    f.stack_on = h->stack.on; f.stack_state_depth = h->stack.out.state_depth; f.stack_n_fields = h->stack.dev.n_fields;
+    f.ep_on = h->ep.on;
+    f.eplog_on = h->eplog.on; f.eplog_capacity = h->eplog.dev.capacity;
+    f.act_on = h->act.on; f.act_mode = h->act.cfg.mode; f.act_n_table = h->act.cfg.n_table; f.act_n_cols = h->act.cfg.n_cols;
+    f.pol_on = h->pol.on; f.pol_kind = h->pol.cfg.kind; f.pol_flags = h->pol.cfg.flags; f.pol_A = h->pol.dev.A; f.pol_C = h->pol.dev.C;
+    f.ploss_on = h->ploss.on;
+    f.post_on = h->post.on; f.post_norm = h->post.dev.norm != nullptr;
+    f.final_on = h->final_obs.on;
+    f.roll_on = h->roll.on; f.roll_horizon = h->roll.cfg.horizon; f.roll_fields = h->roll.cfg.fields;
+    f.mb_on = h->mb.on;
+    f.norm_on = h->norm.on; f.norm_obs = h->norm.dev.norm_vector_states != nullptr; f.norm_rew = h->norm.dev.norm_rewards != nullptr;
+    return &f;
+}
+// what the plan decided, handed on: a refusal with its text; IMGENV_OK or ENABLE_REPEAT otherwise
+static int planned(int rc, const FeatureMsg msg) {
+    if (rc < 0) FAIL(rc, "%s", msg);
+    return rc;
+}
+// an entry point that needs a feature: "imgenv_X_enable was not called"
+static int needs(bool on, const char* enable_name) {
+    FeatureMsg msg;
+    return planned(feature_needed(on, enable_name, msg), msg);
+}
+// the same cfg again: the stored out struct, nothing changes
+template <typename F, typename Out>
+static int enable_repeated(const F& f, Out* out) {
+    if (out) *out = f.out;
     return IMGENV_OK;
 }
-// the end of an enable call: `o`, zeroed but for the feature's own fields, becomes the handle's struct and the feature is on
+// (imgenv_episode_log_out and imgenv_policy_loss_out have no n_local)
+template <typename Out, typename = void>
+struct HasNLocal : std::false_type {};
 template <typename Out>
-static int enable_done(imgenv* h, Out o, Out imgenv::*stored, bool imgenv::*on, Out* out) {
+struct HasNLocal<Out, std::void_t<decltype(Out::n_local)>> : std::true_type {};
+// the end of an enable call: `o`, zeroed but for the feature's own fields, becomes the handle's struct and the feature is on
+template <typename F, typename Out>
+static int enable_done(imgenv* h, F& f, Out o, Out* out) {
     o.struct_size = (int32_t)sizeof(Out);
-    o.n_local = h->RL;
-    h->*stored = o;
-    h->*on = true;
+    if constexpr (HasNLocal<Out>::value) o.n_local = h->RL;
+    f.out = o;
+    f.on = true;
     if (out) *out = o;
     return IMGENV_OK;
 }
@@ -3550,22 +3567,17 @@ static int feature_block(imgenv* h, size_t total, const char* enable_name, unsig
     txn.commit(h->allocs);
     return IMGENV_OK;
 }
-template <typename Out>
-static int feature_outputs(imgenv* h, bool imgenv::*on, Out imgenv::*stored, Out* out, const char* enable_name) {
+template <typename F, typename Out>
+static int feature_outputs(imgenv* h, F imgenv::*feature, Out* out, const char* enable_name) {
     if (!h || !out) FAIL(IMGENV_EINVAL, "null argument");
-    if (!(h->*on)) FAIL(IMGENV_ESTATE, "%s was not called", enable_name);
-    *out = h->*stored;
+    RTRY(needs((h->*feature).on, enable_name));
+    *out = (h->*feature).out;
     return IMGENV_OK;
 }
 
 // ---- observation stacks (include/imgenv.h; the kernel is csrc/stack.h) ----
-// the cfg's refusals, then launch_plan.h's plan_stack
-static int stack_plan(const imgenv_cfg& c, const imgenv_stack_cfg& s, int RL, StackPlan& p) {
-    if (s.image_batch < 0 || s.state_batch < 0) FAIL(IMGENV_EINVAL, "image_batch / state_batch must be >= 0");
-    if (s.image_batch > IMGENV_STACK_MAX_DEPTH || s.state_batch > IMGENV_STACK_MAX_DEPTH || s.laser_batch > IMGENV_STACK_MAX_DEPTH)
-        FAIL(IMGENV_EINVAL, "a stack depth above IMGENV_STACK_MAX_DEPTH (%d)", IMGENV_STACK_MAX_DEPTH);
-    p = plan_stack((size_t)c.image_size[0] * (size_t)c.image_size[1], c.state_dim, make_view_geom(c).B, s.image_batch, s.state_batch, s.laser_batch, (size_t)RL);
-    return IMGENV_OK;
+static StackPlan stack_plan(const imgenv_cfg& c, const imgenv_stack_cfg& s, int RL) {
+    return plan_stack((size_t)c.image_size[0] * (size_t)c.image_size[1], c.state_dim, make_view_geom(c).B, s.image_batch, s.state_batch, s.laser_batch, (size_t)RL);
 }
 
 extern "C" int64_t imgenv_stack_bytes(const imgenv_cfg* cfg, const imgenv_stack_cfg* s) {
@@ -3573,29 +3585,25 @@ extern "C" int64_t imgenv_stack_bytes(const imgenv_cfg* cfg, const imgenv_stack_
     if (cfg->struct_size != (int32_t)sizeof(imgenv_cfg) || s->struct_size != (int32_t)sizeof(imgenv_stack_cfg)) FAIL(IMGENV_EINVAL, "struct_size mismatch");
     int r0, r1;
     if (shard_of(*cfg, r0, r1)) FAIL(IMGENV_EINVAL, "bad robot shard");
-    StackPlan p;
-    if (int rc = stack_plan(*cfg, *s, r1 - r0, p)) return rc;
-    return (int64_t)p.total;
+    FeatureMsg msg;
+    if (int rc = planned(stack_cfg_refusals(*s, msg), msg)) return rc;
+    return (int64_t)stack_plan(*cfg, *s, r1 - r0).total;
 }
 
 extern "C" int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgenv_stack_out* out) {
-    // (unlike the other three: the handle with the cfg, a second call is refused, and so is one after the first reset)
-    if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    RTRY(enable_args(s, "imgenv_stack_cfg", out, "imgenv_stack_out"));
-    if (h->stack_on) FAIL(IMGENV_ESTATE, "imgenv_stack_enable has already been called on this handle");
-    if (any_world_reset(h)) FAIL(IMGENV_ESTATE, "imgenv_stack_enable after the first reset");
-    StackPlan p;
-    if (int rc = stack_plan(h->cfg, *s, h->RL, p)) return rc;
+    FeatureMsg msg;
+    FeatureFacts facts;
+    RTRY(planned(stack_enable_plan(s, out, feature_facts(h, facts), msg), msg));
+    const StackPlan p = stack_plan(h->cfg, *s, h->RL);
+    if (p.total > 0 && s->arena) RTRY(planned(stack_arena_refusals(*s, p.total, msg), msg));
     HIPCHK(hipSetDevice(h->cfg.device));
     unsigned char* base = nullptr;
     if (p.total > 0) {
         if (s->arena) {
-            if (s->arena_bytes < (int64_t)p.total) FAIL(IMGENV_EINVAL, "stack arena too small: %lld < %zu", (long long)s->arena_bytes, p.total);
-            if ((uintptr_t)s->arena & 255) FAIL(IMGENV_EINVAL, "stack arena must be 256-byte aligned");
             base = (unsigned char*)s->arena;
             HIPCHK(hipMemset(base, 0, p.total));
         } else {
-            RTRY(dev_alloc(h, &base, p.total));  // (zeroed)
+            RTRY(feature_block(h, p.total, "imgenv_stack_enable", &base));
         }
     }
     const imgenv_out& pub = h->pub_arena ? h->pub_out : h->out;
@@ -3619,17 +3627,17 @@ extern "C" int imgenv_stack_enable(imgenv_t* h, const imgenv_stack_cfg* s, imgen
         f.depth = p.depth[k];
         sd.chunks_per_robot += f.chunks;
     }
-    h->stack = sd;
+    h->stack.dev = sd;
     imgenv_stack_out o = {};
     o.image_depth = p.depth[0]; o.state_depth = p.depth[1]; o.laser_depth = p.depth[2];
     o.sensor_maps = (uint16_t*)ptr[0]; o.vector_states = (float*)ptr[1]; o.lasers = (double*)ptr[2];
-    return enable_done(h, o, &imgenv::stack_out, &imgenv::stack_on, out);
+    return enable_done(h, h->stack, o, out);
 }
 
 // the chain's tail (launch_tails): a step pushes every local robot's new frames, a reset chain restarts the stacks of the robots it covers
 static void tail_stack(imgenv* h, hipStream_t st, const ChainPlans& k) {
-    if (!h->stack_on || h->stack.n_fields <= 0) return;
-    StackDev sd = h->stack;
+    if (!h->stack.on || h->stack.dev.n_fields <= 0) return;
+    StackDev sd = h->stack.dev;
     sd.rows = tail_rows(h, k.is_reset);
     const LaunchShape g = plan_tail_launch(h->plan, k.c, sd.chunks_per_robot, STACK_BLOCK, STACK_MAX_BLOCKS);
     (k.is_reset ? k_stack<true> : k_stack<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(sd);
@@ -3637,28 +3645,20 @@ static void tail_stack(imgenv* h, hipStream_t st, const ChainPlans& k) {
 }
 
 extern "C" int imgenv_stack_outputs(imgenv_t* h, imgenv_stack_out* out) {
-    return feature_outputs(h, &imgenv::stack_on, &imgenv::stack_out, out, "imgenv_stack_enable");
+    return feature_outputs(h, &imgenv::stack, out, "imgenv_stack_enable");
 }
 
 // ---- episode statistics (include/imgenv.h; the kernel is csrc/episodes.h) ----
 static_assert(EPF_OPEN_ROWS == IMGENV_EP_OPEN_F64 && EPI_EPISODES - EPI_ENDS0 == IMGENV_EP_END_BINS && EPF_RETURN_SUM - EPF_FIG0 == IMGENV_EP_FIGURES,
               "episodes.h rows against include/imgenv.h");
 extern "C" int imgenv_episodes_enable(imgenv_t* h, const imgenv_episodes_cfg* c, imgenv_episodes_out* out) {
-    // (the cfg first: its refusals need no handle, and so no device)
-    RTRY(enable_args(c, "imgenv_episodes_cfg", out, "imgenv_episodes_out"));
-    if (!(c->dt > 0.0) || !std::isfinite(c->dt)) FAIL(IMGENV_EINVAL, "imgenv_episodes_cfg.dt must be > 0 (the YAML's control_hz)");
-    if (c->min_steps < 0) FAIL(IMGENV_EINVAL, "imgenv_episodes_cfg.min_steps must be >= 0");
-    if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (h->ep_on) {
-        if (c->min_steps != h->ep_cfg.min_steps || c->dt != h->ep_cfg.dt)
-            FAIL(IMGENV_EINVAL, "imgenv_episodes_enable: the handle already keeps statistics with min_steps %d, dt %g", h->ep_cfg.min_steps, h->ep_cfg.dt);
-        if (out) *out = h->ep_out;
-        return IMGENV_OK;
-    }
-    HIPCHK(hipSetDevice(h->cfg.device));
+    FeatureMsg msg;
+    FeatureFacts facts;
+    const int plan = planned(episodes_enable_plan(c, out, feature_facts(h, facts), h ? &h->ep.cfg : nullptr, msg), msg);
+    if (plan) return plan < 0 ? plan : enable_repeated(h->ep, out);
     const size_t RL = (size_t)h->RL, f_bytes = sizeof(double) * EPF_ROWS * RL, i_bytes = sizeof(int32_t) * EPI_ROWS * RL;
     unsigned char* base = nullptr;
-    RTRY(dev_alloc(h, &base, f_bytes + i_bytes));  // (zeroed: no episode open)
+    RTRY(feature_block(h, f_bytes + i_bytes, "imgenv_episodes_enable", &base));  // (zeroed: no episode open)
     EpisodesDev e;
     memset(&e, 0, sizeof(e));
     e.f = (double*)base;
@@ -3668,9 +3668,9 @@ extern "C" int imgenv_episodes_enable(imgenv_t* h, const imgenv_episodes_cfg* c,
     e.step_dones_info = h->out.step_dones_info;
     e.dt = c->dt;
     e.min_steps = c->min_steps;
-    h->ep = e;
-    h->ep_cfg = *c;
-    h->ep_clear_bytes = f_bytes + sizeof(int32_t) * EPI_CLEARED_ROWS * RL;
+    h->ep.dev = e;
+    h->ep.cfg = *c;
+    h->ep.clear_bytes = f_bytes + sizeof(int32_t) * EPI_CLEARED_ROWS * RL;
     imgenv_episodes_out o = {};
     o.ends = e.i + EPI_ENDS0 * RL; o.episodes = e.i + EPI_EPISODES * RL; o.short_episodes = e.i + EPI_SHORT * RL;
     o.speed_steps = e.i + EPI_SPEED_STEPS * RL; o.arrive_steps = e.i + EPI_ARRIVE_STEPS * RL; o.len_sum = e.i + EPI_LEN_SUM * RL;
@@ -3678,7 +3678,7 @@ extern "C" int imgenv_episodes_enable(imgenv_t* h, const imgenv_episodes_cfg* c,
     o.last_code = e.i + EPI_LAST_CODE * RL; o.last_steps = e.i + EPI_LAST_STEPS * RL; o.last_len = e.i + EPI_LAST_LEN * RL;
     o.last_episode = e.i + EPI_LAST_EPISODE * RL; o.last_return = e.f + EPF_LAST_RETURN * RL;
     o.open_f64 = e.f; o.open_steps = e.i + EPI_TMP_STEPS * RL; o.open_len = e.i + EPI_LEN * RL; o.open = e.i + EPI_OPEN * RL;
-    return enable_done(h, o, &imgenv::ep_out, &imgenv::ep_on, out);
+    return enable_done(h, h->ep, o, out);
 }
 
 // the chain's tail (launch_tails): a step's command, reward and is_clean go into every local robot's open episode, a reset chain
@@ -3686,12 +3686,12 @@ extern "C" int imgenv_episodes_enable(imgenv_t* h, const imgenv_episodes_cfg* c,
 // (episode_log.h): one record per episode this chain closes, and the tags of the episodes it opens -- from the words the chain's
 // earlier launches have written (the banks' pointers are taken here: they may have come, or been rebuilt, after the log's enable)
 static void tail_episodes(imgenv* h, hipStream_t st, const ChainPlans& k) {
-    if (!h->ep_on) return;
-    EpisodesDev ed = h->ep;
+    if (!h->ep.on) return;
+    EpisodesDev ed = h->ep.dev;
     ed.actions = h->step.actions;
     ed.rows = tail_rows(h, k.is_reset);
-    if (k.is_reset && h->eplog_on) {
-        EpisodeLogDev lg = h->eplog;
+    if (k.is_reset && h->eplog.on) {
+        EpisodeLogDev lg = h->eplog.dev;
         lg.map_cur = h->d_map_cur; lg.trk_cur = h->d_trk_cur; lg.scn_world = h->d_scn_world; lg.scn_mark = h->d_scn_mark;
         lg.place_serial = h->dev.ready ? h->dev.pool.place_serial : nullptr;
         const LaunchShape gl = plan_episode_log_launch();
@@ -3704,14 +3704,14 @@ static void tail_episodes(imgenv* h, hipStream_t st, const ChainPlans& k) {
 }
 
 extern "C" int imgenv_episodes_outputs(imgenv_t* h, imgenv_episodes_out* out) {
-    return feature_outputs(h, &imgenv::ep_on, &imgenv::ep_out, out, "imgenv_episodes_enable");
+    return feature_outputs(h, &imgenv::ep, out, "imgenv_episodes_enable");
 }
 
 extern "C" int imgenv_episodes_clear(imgenv_t* h, void* stream) {
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->ep_on) FAIL(IMGENV_ESTATE, "imgenv_episodes_enable was not called");
+    RTRY(needs(h->ep.on, "imgenv_episodes_enable"));
     HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipMemsetAsync(h->ep.f, 0, h->ep_clear_bytes, (hipStream_t)stream));
+    HIPCHK(hipMemsetAsync(h->ep.dev.f, 0, h->ep.clear_bytes, (hipStream_t)stream));
     return IMGENV_OK;
 }
 
@@ -3720,17 +3720,10 @@ static_assert(EPL_I32_ROWS == IMGENV_EPLOG_I32 && EPL_F64_ROWS == IMGENV_EPLOG_F
                   sizeof(imgenv_episode_record) == 128,
               "episode_log.h rows against include/imgenv.h");
 extern "C" int imgenv_episode_log_enable(imgenv_t* h, const imgenv_episode_log_cfg* c, imgenv_episode_log_out* out) {
-    RTRY(enable_args(c, "imgenv_episode_log_cfg", out, "imgenv_episode_log_out"));
-    if (c->capacity < 1 || c->capacity > IMGENV_EPLOG_MAX_CAPACITY)
-        FAIL(IMGENV_EINVAL, "imgenv_episode_log_cfg.capacity %d: 1 .. %d", c->capacity, IMGENV_EPLOG_MAX_CAPACITY);
-    if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->ep_on) FAIL(IMGENV_ESTATE, "imgenv_episode_log_enable before imgenv_episodes_enable");
-    if (h->eplog_on) {
-        if (c->capacity != h->eplog.capacity)
-            FAIL(IMGENV_EINVAL, "imgenv_episode_log_enable: the handle already keeps a log of capacity %d", h->eplog.capacity);
-        if (out) *out = h->eplog_out;
-        return IMGENV_OK;
-    }
+    FeatureMsg msg;
+    FeatureFacts facts;
+    const int plan = planned(episode_log_enable_plan(c, out, feature_facts(h, facts), msg), msg);
+    if (plan) return plan < 0 ? plan : enable_repeated(h->eplog, out);
     HIPCHK(hipSetDevice(h->cfg.device));
     // two blocks: the counter and the ring's placement | f64 | i32 columns, zeroed; the per-robot tags (placement | i32), which start
     // as "open before the log was" (all bits set: -1 and ~0).  Nothing of the handle changes before both are there.
@@ -3752,29 +3745,25 @@ extern "C" int imgenv_episode_log_enable(imgenv_t* h, const imgenv_episode_log_c
     g.tags = (int32_t*)(t + 8 * RL);
     g.capacity = c->capacity;
     g.W = h->W;
-    h->eplog = g;
+    h->eplog.dev = g;
     imgenv_episode_log_out o = {};
-    o.struct_size = (int32_t)sizeof(o);
     o.capacity = c->capacity;
     o.n_written = (uint64_t*)g.n_written; o.i32 = g.i32; o.f64 = g.f64; o.placement = (uint64_t*)g.placement;
-    h->eplog_out = o;
-    h->eplog_on = true;
-    if (out) *out = o;
-    return IMGENV_OK;
+    return enable_done(h, h->eplog, o, out);
 }
 
 extern "C" int imgenv_episode_log_outputs(imgenv_t* h, imgenv_episode_log_out* out) {
-    return feature_outputs(h, &imgenv::eplog_on, &imgenv::eplog_out, out, "imgenv_episode_log_enable");
+    return feature_outputs(h, &imgenv::eplog, out, "imgenv_episode_log_enable");
 }
 
 extern "C" int64_t imgenv_episode_log_read(imgenv_t* h, uint64_t first, int32_t max, imgenv_episode_record* rec, uint64_t* oldest, uint64_t* n_written,
                                            void* stream) {
     if (!h || max < 0 || (max > 0 && !rec)) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->eplog_on) FAIL(IMGENV_ESTATE, "imgenv_episode_log_enable was not called");
+    RTRY(needs(h->eplog.on, "imgenv_episode_log_enable"));
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     if (int rc = check_device_flags(h)) return rc;
-    const EpisodeLogDev& g = h->eplog;
+    const EpisodeLogDev& g = h->eplog.dev;
     const uint64_t C = (uint64_t)g.capacity;
     unsigned long long n = 0;
     HIPCHK(hipMemcpy(&n, g.n_written, sizeof(n), hipMemcpyDeviceToHost));
@@ -3819,63 +3808,47 @@ extern "C" int64_t imgenv_episode_log_read(imgenv_t* h, uint64_t first, int32_t 
 }
 
 // ---- action decoding (include/imgenv.h; the kernel is csrc/actions.h) ----
-static bool actions_cfg_same(const imgenv* h, const imgenv_actions_cfg* c) {
-    const imgenv_actions_cfg& o = h->act_cfg;
-    if (c->mode != o.mode || c->n_cols != o.n_cols) return false;
-    if (c->mode == IMGENV_ACTIONS_TABLE)
-        return c->n_table == o.n_table && memcmp(c->table, h->act_table.data(), sizeof(float) * 3 * (size_t)c->n_table) == 0;
-    return memcmp(c->clip, o.clip, sizeof(float) * 2 * (size_t)c->n_cols) == 0;
-}
 extern "C" int imgenv_actions_enable(imgenv_t* h, const imgenv_actions_cfg* c, imgenv_actions_out* out) {
-    // (the cfg first: its refusals need no handle, and so no device)
-    RTRY(enable_args(c, "imgenv_actions_cfg", out, "imgenv_actions_out"));
-    if (c->mode != IMGENV_ACTIONS_TABLE && c->mode != IMGENV_ACTIONS_CLIP) FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.mode %d", c->mode);
-    if (c->n_cols != 2 && c->n_cols != 3) FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.n_cols %d: 2 (v, w) or 3 (v, w, beep)", c->n_cols);
-    if (c->mode == IMGENV_ACTIONS_TABLE) {
-        if (!c->table || c->n_table < 1 || c->n_table > IMGENV_ACTIONS_MAX_TABLE)
-            FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.table: 1 .. %d rows (n_table %d)", IMGENV_ACTIONS_MAX_TABLE, c->n_table);
-        for (int q = 0; q < 3 * c->n_table; q++)
-            if (!std::isfinite(c->table[q])) FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.table row %d holds a value that is not finite", q / 3);
-    } else {
-        for (int i = 0; i < c->n_cols; i++)
-            if (!std::isfinite(c->clip[i][0]) || !std::isfinite(c->clip[i][1]) || c->clip[i][0] > c->clip[i][1])
-                FAIL(IMGENV_EINVAL, "imgenv_actions_cfg.clip[%d] = (%g, %g): finite bounds with lo <= hi", i, c->clip[i][0], c->clip[i][1]);
-    }
-    if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (h->act_on) {
-        if (!actions_cfg_same(h, c)) FAIL(IMGENV_EINVAL, "imgenv_actions_enable: the handle already decodes actions with another cfg");
-        if (out) *out = h->act_out;
-        return IMGENV_OK;
-    }
+    FeatureMsg msg;
+    FeatureFacts facts;
+    const int plan = planned(actions_enable_plan(c, out, feature_facts(h, facts), h ? &h->act.cfg : nullptr, h ? h->act.table.data() : nullptr, msg), msg);
+    if (plan) return plan < 0 ? plan : enable_repeated(h->act, out);
     HIPCHK(hipSetDevice(h->cfg.device));
     const size_t RL = (size_t)h->RL;
     ActionsDev a;
     memset(&a, 0, sizeof(a));
-    RTRY(dev_alloc(h, &a.actions, RL * 3));  // (zeroed)
-    RTRY(dev_alloc(h, &a.speeds, RL * 2));
-    RTRY(dev_alloc(h, &a.n_bad, 1));
+    // three zeroed arrays and, in TABLE mode, the rows: one transaction, nothing of the handle changes before all are there
     std::vector<float> table;
+    float* d_table = nullptr;
+    DevTxn<HipApi> txn;
+    txn.room(&a.actions, RL * 3, 0);
+    txn.room(&a.speeds, RL * 2, 0);
+    txn.room(&a.n_bad, 1, 0);
     if (c->mode == IMGENV_ACTIONS_TABLE) {
         table.assign(c->table, c->table + 3 * (size_t)c->n_table);
-        RTRY(dev_upload(h, &a.table, table));
+        txn.room(&d_table, table.size(), 0);
+        txn.put(d_table, table.data(), sizeof(float) * table.size());
         a.n_table = c->n_table;
     } else {
         for (int i = 0; i < c->n_cols; i++) { a.lo[i] = c->clip[i][0]; a.hi[i] = c->clip[i][1]; }
     }
+    if (txn.code()) FAIL(txn.code(), "imgenv_actions_enable: %s", txn.error());
+    txn.commit(h->allocs);
+    a.table = d_table;
     a.clean_state = h->d.clean_state;
     a.n_cols = c->n_cols;
     a.RL = h->RL;
-    h->act = a;
-    h->act_cfg = *c;
-    h->act_cfg.table = nullptr;
-    h->act_table.swap(table);
+    h->act.dev = a;
+    h->act.cfg = *c;
+    h->act.cfg.table = nullptr;
+    h->act.table.swap(table);
     imgenv_actions_out o = {};
     o.actions = a.actions; o.speeds = a.speeds; o.n_bad = a.n_bad;
-    return enable_done(h, o, &imgenv::act_out, &imgenv::act_on, out);
+    return enable_done(h, h->act, o, out);
 }
 
 extern "C" int imgenv_actions_outputs(imgenv_t* h, imgenv_actions_out* out) {
-    return feature_outputs(h, &imgenv::act_on, &imgenv::act_out, out, "imgenv_actions_enable");
+    return feature_outputs(h, &imgenv::act, out, "imgenv_actions_enable");
 }
 
 // k_actions<DTYPE, MODE>: the six instantiations (indices are not clipped)
@@ -3891,68 +3864,50 @@ static ActionsKernel k_actions_for(int dtype, int mode) {
 }
 extern "C" int imgenv_actions_decode(imgenv_t* h, const void* raw, int32_t dtype, void* stream) {
     if (!h || !raw) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->act_on) FAIL(IMGENV_ESTATE, "imgenv_actions_enable was not called");
+    RTRY(needs(h->act.on, "imgenv_actions_enable"));
     if (!h->has_reset) FAIL(IMGENV_ESTATE, "imgenv_actions_decode before the first reset");
     if (dtype < IMGENV_RAW_I32 || dtype > IMGENV_RAW_F64) FAIL(IMGENV_EINVAL, "imgenv_actions_decode: dtype %d", dtype);
     const bool integer = dtype == IMGENV_RAW_I32 || dtype == IMGENV_RAW_I64;
-    if (integer && h->act_cfg.mode == IMGENV_ACTIONS_CLIP) FAIL(IMGENV_EINVAL, "imgenv_actions_decode: indices in CLIP mode (the handle has no table)");
+    if (integer && h->act.cfg.mode == IMGENV_ACTIONS_CLIP) FAIL(IMGENV_EINVAL, "imgenv_actions_decode: indices in CLIP mode (the handle has no table)");
     const size_t elem = dtype == IMGENV_RAW_I32 || dtype == IMGENV_RAW_F32 ? 4 : 8;
     if ((uintptr_t)raw % elem != 0) FAIL(IMGENV_EINVAL, "imgenv_actions_decode: raw is not aligned to its %d-byte elements", (int)elem);
     HIPCHK(hipSetDevice(h->cfg.device));
-    ActionsDev a = h->act;
+    ActionsDev a = h->act.dev;
     a.raw = raw;
     const LaunchShape g = plan_actions_launch(h->plan);
-    k_actions_for(dtype, h->act_cfg.mode)<<<dim3(g.grid), dim3(g.block), 0, (hipStream_t)stream>>>(a);
+    k_actions_for(dtype, h->act.cfg.mode)<<<dim3(g.grid), dim3(g.block), 0, (hipStream_t)stream>>>(a);
     HIPCHK(hipGetLastError());
-    h->decode_launches += 1;
+    h->act.decode_launches += 1;
     return IMGENV_OK;
 }
 
 // ---- the policy head (include/imgenv.h; the kernels are csrc/policy.h) ----
 extern "C" int imgenv_policy_enable(imgenv_t* h, const imgenv_policy_cfg* c, imgenv_policy_out* out) {
-    // (the cfg first, as above)
-    RTRY(enable_args(c, "imgenv_policy_cfg", out, "imgenv_policy_out"));
-    if (c->kind != IMGENV_POLICY_CATEGORICAL && c->kind != IMGENV_POLICY_GAUSSIAN) FAIL(IMGENV_EINVAL, "imgenv_policy_cfg.kind %d", c->kind);
-    if (c->flags & ~IMGENV_POLICY_STORE) FAIL(IMGENV_EINVAL, "imgenv_policy_cfg.flags %d", c->flags);
-    if (c->reserved != 0) FAIL(IMGENV_EINVAL, "imgenv_policy_cfg.reserved %d", c->reserved);
-    if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (h->pol_on) {
-        const imgenv_policy_cfg& o = h->pol_cfg;
-        if (c->kind != o.kind || c->flags != o.flags || c->seed != o.seed)
-            FAIL(IMGENV_EINVAL, "imgenv_policy_enable: the handle already has a policy head with another cfg");
-        if (out) *out = h->pol_out;
-        return IMGENV_OK;
-    }
-    if (!h->act_on) FAIL(IMGENV_ESTATE, "imgenv_policy_enable before imgenv_actions_enable");
-    const bool cat = c->kind == IMGENV_POLICY_CATEGORICAL;
-    if (h->act_cfg.mode != (cat ? IMGENV_ACTIONS_TABLE : IMGENV_ACTIONS_CLIP))
-        FAIL(IMGENV_EINVAL, "imgenv_policy_enable: a %s head needs imgenv_actions_enable in %s mode", cat ? "categorical" : "Gaussian", cat ? "TABLE" : "CLIP");
-    const bool store = (c->flags & IMGENV_POLICY_STORE) != 0;
-    if (store && !h->roll_on) FAIL(IMGENV_ESTATE, "imgenv_policy_enable: IMGENV_POLICY_STORE before imgenv_rollout_enable");
-    const size_t RL = (size_t)h->RL, T = store ? (size_t)h->roll_cfg.horizon : 0;
-    const int n_params = cat ? h->act_cfg.n_table : h->act_cfg.n_cols;
-    const size_t cols = cat ? 1 : (size_t)n_params;
-    // one block, every array on a 256-byte boundary, zeroed; nothing of the handle changes before it is there
-    Carve cv;
-    const size_t off_index = cv.take(cat ? RL * 4 : 0), off_raw = cv.take(cat ? 0 : RL * cols * 4), off_logp = cv.take(RL * 4), off_ent = cv.take(RL * 4);
-    const size_t off_praw = cv.take(cols * T * RL * 4), off_plogp = cv.take(T * RL * 4), off_pvalue = cv.take(store ? (T + 1) * RL * 4 : 0);
+    FeatureMsg msg;
+    FeatureFacts facts;
+    const int plan = planned(policy_enable_plan(c, out, feature_facts(h, facts), h ? &h->pol.cfg : nullptr, msg), msg);
+    if (plan) return plan < 0 ? plan : enable_repeated(h->pol, out);
+    const bool cat = c->kind == IMGENV_POLICY_CATEGORICAL, store = (c->flags & IMGENV_POLICY_STORE) != 0;
+    const size_t RL = (size_t)h->RL, T = store ? (size_t)facts.roll_horizon : 0;
+    const int n_params = cat ? facts.act_n_table : facts.act_n_cols;
+    const PolicyLayout l = plan_policy_layout(cat, cat ? 1 : (size_t)n_params, RL, T);
     unsigned char* block = nullptr;
-    RTRY(feature_block(h, cv.total, "imgenv_policy_enable", &block));
+    RTRY(feature_block(h, l.total, "imgenv_policy_enable", &block));
     imgenv_policy_out o = {};
     o.n_params = n_params;
     o.horizon = (int32_t)T;
-    if (cat) o.index = (int32_t*)(block + off_index);
-    else o.raw = (float*)(block + off_raw);
-    o.logp = (float*)(block + off_logp);
-    o.entropy = (float*)(block + off_ent);
+    if (cat) o.index = (int32_t*)(block + l.index);
+    else o.raw = (float*)(block + l.raw);
+    o.logp = (float*)(block + l.logp);
+    o.entropy = (float*)(block + l.entropy);
     if (store) {
-        o.pol_raw = (float*)(block + off_praw);
-        o.pol_logp = (float*)(block + off_plogp);
-        o.pol_value = (float*)(block + off_pvalue);
+        o.pol_raw = (float*)(block + l.pol_raw);
+        o.pol_logp = (float*)(block + l.pol_logp);
+        o.pol_value = (float*)(block + l.pol_value);
     }
     PolicyDev p;
     memset(&p, 0, sizeof(p));
-    const ActionsDev& a = h->act;
+    const ActionsDev& a = h->act.dev;
     p.table = a.table; p.actions = a.actions; p.speeds = a.speeds; p.n_bad = a.n_bad; p.clean_state = a.clean_state;
     for (int i = 0; i < 3; i++) { p.lo[i] = a.lo[i]; p.hi[i] = a.hi[i]; }
     p.index = o.index; p.raw = o.raw; p.logp = o.logp; p.entropy = o.entropy;
@@ -3960,13 +3915,13 @@ extern "C" int imgenv_policy_enable(imgenv_t* h, const imgenv_policy_cfg* c, img
     p.g0 = (unsigned long long)h->r0;
     p.seed_lo = (uint32_t)c->seed; p.seed_hi = (uint32_t)(c->seed >> 32);
     p.A = cat ? n_params : 0; p.C = cat ? 0 : n_params; p.RL = h->RL;
-    h->pol = p;
-    h->pol_cfg = *c;
-    return enable_done(h, o, &imgenv::pol_out, &imgenv::pol_on, out);
+    h->pol.dev = p;
+    h->pol.cfg = *c;
+    return enable_done(h, h->pol, o, out);
 }
 
 extern "C" int imgenv_policy_outputs(imgenv_t* h, imgenv_policy_out* out) {
-    return feature_outputs(h, &imgenv::pol_on, &imgenv::pol_out, out, "imgenv_policy_enable");
+    return feature_outputs(h, &imgenv::pol, out, "imgenv_policy_enable");
 }
 
 typedef void (*PolicyKernel)(const PolicyDev);
@@ -3980,14 +3935,14 @@ extern "C" int imgenv_policy_sample(imgenv_t* h, const imgenv_policy_args* g, vo
     if (g->struct_size != (int32_t)sizeof(imgenv_policy_args)) FAIL(IMGENV_EINVAL, "imgenv_policy_args.struct_size %d (this library's is %d)", g->struct_size, (int)sizeof(imgenv_policy_args));
     const int32_t known = IMGENV_POLICY_DETERMINISTIC | IMGENV_POLICY_LOG_STD_PER_ROW | IMGENV_POLICY_NO_STORE | IMGENV_POLICY_VALUE_ONLY;
     if (g->flags & ~known) FAIL(IMGENV_EINVAL, "imgenv_policy_args.flags %d", g->flags);
-    if (!h->pol_on) FAIL(IMGENV_ESTATE, "imgenv_policy_enable was not called");
+    RTRY(needs(h->pol.on, "imgenv_policy_enable"));
     if (!h->has_reset) FAIL(IMGENV_ESTATE, "imgenv_policy_sample before the first reset");
-    const bool cat = h->pol_cfg.kind == IMGENV_POLICY_CATEGORICAL, value_only = (g->flags & IMGENV_POLICY_VALUE_ONLY) != 0;
-    const bool stores = (h->pol_cfg.flags & IMGENV_POLICY_STORE) && !(g->flags & IMGENV_POLICY_NO_STORE);
+    const bool cat = h->pol.cfg.kind == IMGENV_POLICY_CATEGORICAL, value_only = (g->flags & IMGENV_POLICY_VALUE_ONLY) != 0;
+    const bool stores = (h->pol.cfg.flags & IMGENV_POLICY_STORE) && !(g->flags & IMGENV_POLICY_NO_STORE);
     auto misaligned = [](const void* p) { return (uintptr_t)p % 4 != 0; };
     if (value_only) {
         if (g->flags != IMGENV_POLICY_VALUE_ONLY) FAIL(IMGENV_EINVAL, "imgenv_policy_args.flags %d: IMGENV_POLICY_VALUE_ONLY stands alone", g->flags);
-        if (!(h->pol_cfg.flags & IMGENV_POLICY_STORE)) FAIL(IMGENV_ESTATE, "imgenv_policy_sample: IMGENV_POLICY_VALUE_ONLY on a head without IMGENV_POLICY_STORE");
+        if (!(h->pol.cfg.flags & IMGENV_POLICY_STORE)) FAIL(IMGENV_ESTATE, "imgenv_policy_sample: IMGENV_POLICY_VALUE_ONLY on a head without IMGENV_POLICY_STORE");
         if (!g->values || misaligned(g->values)) FAIL(IMGENV_EINVAL, "imgenv_policy_args.values is null or misaligned");
     } else {
         if (!g->params || misaligned(g->params)) FAIL(IMGENV_EINVAL, "imgenv_policy_args.params is null or misaligned");
@@ -3995,15 +3950,15 @@ extern "C" int imgenv_policy_sample(imgenv_t* h, const imgenv_policy_args* g, vo
         if (cat && (g->flags & IMGENV_POLICY_LOG_STD_PER_ROW)) FAIL(IMGENV_EINVAL, "imgenv_policy_args.flags: IMGENV_POLICY_LOG_STD_PER_ROW on a categorical head");
         if (g->values && misaligned(g->values)) FAIL(IMGENV_EINVAL, "imgenv_policy_args.values is misaligned");
     }
-    PolicyDev p = h->pol;
+    PolicyDev p = h->pol.dev;
     if (stores || value_only) {
         // the slot: the rollout cursor as the host holds it (the state the window's next transition starts from)
-        const int n = h->roll_begun ? h->roll_n : -1, T = h->roll_cfg.horizon;
+        const int n = h->roll.begun ? h->roll.n : -1, T = h->roll.cfg.horizon;
         if (n < 0 || n > T || (n == T && !value_only))
             FAIL(IMGENV_ESTATE, "imgenv_policy_sample: slot %d of a window of %d (imgenv_rollout_begin starts the next one)", n, T);
         const size_t at = (size_t)n * (size_t)h->RL;
-        if (!value_only) { p.st_raw = h->pol_out.pol_raw + at; p.st_logp = h->pol_out.pol_logp + at; }
-        p.st_value = h->pol_out.pol_value + at;
+        if (!value_only) { p.st_raw = h->pol.out.pol_raw + at; p.st_logp = h->pol.out.pol_logp + at; }
+        p.st_value = h->pol.out.pol_value + at;
     }
     p.params = g->params; p.log_std = g->log_std; p.values = g->values;
     p.draw_lo = (uint32_t)g->draw; p.draw_hi = (uint32_t)(g->draw >> 32);
@@ -4014,64 +3969,47 @@ extern "C" int imgenv_policy_sample(imgenv_t* h, const imgenv_policy_args* g, vo
     const PolicyKernel k = value_only ? k_policy_value : cat ? k_policy_cat_for(plan_policy_group(p.A)) : k_policy_gauss;
     k<<<dim3(s.grid), dim3(s.block), 0, (hipStream_t)stream>>>(p);
     HIPCHK(hipGetLastError());
-    if (!value_only) h->decode_launches += 1;  // (the values-only call belongs to no step)
+    if (!value_only) h->act.decode_launches += 1;  // (the values-only call belongs to no step)
     return IMGENV_OK;
 }
 
 // ---- PPO's loss (include/imgenv.h; the kernels are csrc/policy_loss.h) ----
 extern "C" int imgenv_policy_loss_enable(imgenv_t* h, const imgenv_policy_loss_cfg* c, imgenv_policy_loss_out* out) {
-    // (the cfg first, as above)
-    RTRY(enable_args(c, "imgenv_policy_loss_cfg", out, "imgenv_policy_loss_out"));
-    if (c->max_rows < 1) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_cfg.max_rows %d (at least 1)", c->max_rows);
-    if (c->reserved[0] != 0 || c->reserved[1] != 0) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_cfg.reserved");
-    if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (h->ploss_on) {
-        if (c->max_rows != h->ploss_cfg.max_rows) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_enable: the handle already has a policy loss with another cfg");
-        if (out) *out = h->ploss_out;
-        return IMGENV_OK;
-    }
-    if (!h->pol_on) FAIL(IMGENV_ESTATE, "imgenv_policy_loss_enable before imgenv_policy_enable");
-    const bool cat = h->pol_cfg.kind == IMGENV_POLICY_CATEGORICAL;
-    const size_t B = (size_t)c->max_rows, n = (size_t)(cat ? h->pol.A : h->pol.C);
-    const size_t n_rec = plan_policy_loss_launch(c->max_rows, cat ? h->pol.A : 0).grid;
-    // one block, every array on a 256-byte boundary, zeroed; nothing of the handle changes before it is there
-    Carve cv;
-    const size_t off_logp = cv.take(B * 4), off_ent = cv.take(B * 4), off_ratio = cv.take(B * 4), off_pg = cv.take(B * 4), off_vl = cv.take(B * 4);
-    const size_t off_dp = cv.take(B * n * 4), off_dls = cv.take(cat ? 0 : B * n * 4), off_dlss = cv.take(cat ? 0 : n * 4), off_dv = cv.take(B * 4);
-    const size_t off_stats = cv.take(8 * 4), off_bad = cv.take(4), off_invw = cv.take(4);
-    const size_t off_m = cv.take(cat ? B * 4 : 0), off_ls = cv.take(cat ? B * 4 : 0), off_gu = cv.take(B * 4), off_w = cv.take(B * 4);
-    const size_t off_rec = cv.take(n_rec * PLOSS_REC * 8);
+    FeatureMsg msg;
+    FeatureFacts facts;
+    const int plan = planned(policy_loss_enable_plan(c, out, feature_facts(h, facts), h ? &h->ploss.cfg : nullptr, msg), msg);
+    if (plan) return plan < 0 ? plan : enable_repeated(h->ploss, out);
+    const bool cat = facts.pol_kind == IMGENV_POLICY_CATEGORICAL;
+    const size_t n = (size_t)(cat ? facts.pol_A : facts.pol_C);
+    const size_t n_rec = plan_policy_loss_launch(c->max_rows, cat ? facts.pol_A : 0).grid;
+    const PolicyLossLayout l = plan_policy_loss_layout(cat, (size_t)c->max_rows, n, n_rec, PLOSS_REC);
     unsigned char* block = nullptr;
-    RTRY(feature_block(h, cv.total, "imgenv_policy_loss_enable", &block));
+    RTRY(feature_block(h, l.total, "imgenv_policy_loss_enable", &block));
     imgenv_policy_loss_out o = {};
-    o.struct_size = (int32_t)sizeof(o);
     o.n_params = (int32_t)n;
     o.max_rows = c->max_rows;
-    o.logp = (float*)(block + off_logp); o.entropy = (float*)(block + off_ent); o.ratio = (float*)(block + off_ratio);
-    o.pg = (float*)(block + off_pg); o.vl = (float*)(block + off_vl);
-    o.d_params = (float*)(block + off_dp);
-    if (!cat) { o.d_log_std = (float*)(block + off_dls); o.d_log_std_shared = (float*)(block + off_dlss); }
-    o.d_values = (float*)(block + off_dv);
-    o.stats = (float*)(block + off_stats); o.n_bad = (int32_t*)(block + off_bad); o.inv_w = (float*)(block + off_invw);
+    o.logp = (float*)(block + l.logp); o.entropy = (float*)(block + l.entropy); o.ratio = (float*)(block + l.ratio);
+    o.pg = (float*)(block + l.pg); o.vl = (float*)(block + l.vl);
+    o.d_params = (float*)(block + l.d_params);
+    if (!cat) { o.d_log_std = (float*)(block + l.d_log_std); o.d_log_std_shared = (float*)(block + l.d_log_std_shared); }
+    o.d_values = (float*)(block + l.d_values);
+    o.stats = (float*)(block + l.stats); o.n_bad = (int32_t*)(block + l.n_bad); o.inv_w = (float*)(block + l.inv_w);
     PlossDev p;
     memset(&p, 0, sizeof(p));
     p.logp = o.logp; p.entropy = o.entropy; p.ratio = o.ratio; p.pg = o.pg; p.vl = o.vl;
     p.d_params = o.d_params; p.d_log_std = o.d_log_std; p.d_log_std_shared = o.d_log_std_shared; p.d_values = o.d_values;
     p.stats = o.stats; p.n_bad = o.n_bad; p.inv_W = o.inv_w;
-    if (cat) { p.row_m = (float*)(block + off_m); p.row_log_s = (float*)(block + off_ls); }
-    p.row_gu = (float*)(block + off_gu); p.row_w = (float*)(block + off_w);
-    p.rec = (double*)(block + off_rec);
-    p.A = h->pol.A; p.C = h->pol.C;
-    h->ploss = p;
-    h->ploss_cfg = *c;
-    h->ploss_out = o;
-    h->ploss_on = true;
-    if (out) *out = o;
-    return IMGENV_OK;
+    if (cat) { p.row_m = (float*)(block + l.row_m); p.row_log_s = (float*)(block + l.row_log_s); }
+    p.row_gu = (float*)(block + l.row_gu); p.row_w = (float*)(block + l.row_w);
+    p.rec = (double*)(block + l.rec);
+    p.A = facts.pol_A; p.C = facts.pol_C;
+    h->ploss.dev = p;
+    h->ploss.cfg = *c;
+    return enable_done(h, h->ploss, o, out);
 }
 
 extern "C" int imgenv_policy_loss_outputs(imgenv_t* h, imgenv_policy_loss_out* out) {
-    return feature_outputs(h, &imgenv::ploss_on, &imgenv::ploss_out, out, "imgenv_policy_loss_enable");
+    return feature_outputs(h, &imgenv::ploss, out, "imgenv_policy_loss_enable");
 }
 
 typedef void (*PlossKernel)(const PlossDev);
@@ -4083,20 +4021,20 @@ extern "C" int imgenv_policy_loss(imgenv_t* h, const imgenv_policy_loss_args* g,
     if (g->struct_size != (int32_t)sizeof(imgenv_policy_loss_args)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.struct_size %d (this library's is %d)", g->struct_size, (int)sizeof(imgenv_policy_loss_args));
     if (g->flags & ~(IMGENV_PLOSS_CLIP_VALUE | IMGENV_POLICY_LOG_STD_PER_ROW)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.flags %d", g->flags);
     if (g->reserved != 0) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.reserved %d", g->reserved);
-    if (!h->ploss_on) FAIL(IMGENV_ESTATE, "imgenv_policy_loss_enable was not called");
-    if (g->rows < 1 || g->rows > h->ploss_cfg.max_rows) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.rows %d (1 .. %d)", g->rows, h->ploss_cfg.max_rows);
-    const bool cat = h->pol_cfg.kind == IMGENV_POLICY_CATEGORICAL, clip_value = (g->flags & IMGENV_PLOSS_CLIP_VALUE) != 0;
+    RTRY(needs(h->ploss.on, "imgenv_policy_loss_enable"));
+    if (g->rows < 1 || g->rows > h->ploss.cfg.max_rows) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.rows %d (1 .. %d)", g->rows, h->ploss.cfg.max_rows);
+    const bool cat = h->pol.cfg.kind == IMGENV_POLICY_CATEGORICAL, clip_value = (g->flags & IMGENV_PLOSS_CLIP_VALUE) != 0;
     if (cat && (g->flags & IMGENV_POLICY_LOG_STD_PER_ROW)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.flags: IMGENV_POLICY_LOG_STD_PER_ROW on a categorical head");
     auto missing = [](const void* p) { return !p || (uintptr_t)p % 4 != 0; };
     if (missing(g->params) || missing(g->values) || missing(g->old_logp) || missing(g->adv) || missing(g->ret) || missing(g->weight))
         FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args: params, values, old_logp, adv, ret or weight is null or misaligned");
     if (!cat && missing(g->log_std)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.log_std is null or misaligned");
     if (clip_value && missing(g->old_value)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.old_value is null or misaligned");
-    for (int c = 0; c < (cat ? 1 : h->ploss.C); c++)
+    for (int c = 0; c < (cat ? 1 : h->ploss.dev.C); c++)
         if (missing(g->action[c])) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.action[%d] is null or misaligned", c);
     if (!(g->clip >= 0.0f)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.clip %g", (double)g->clip);
     if (clip_value && !(g->clip_vf >= 0.0f)) FAIL(IMGENV_EINVAL, "imgenv_policy_loss_args.clip_vf %g", (double)g->clip_vf);
-    PlossDev p = h->ploss;
+    PlossDev p = h->ploss.dev;
     p.params = g->params; p.log_std = g->log_std; p.values = g->values;
     for (int c = 0; c < 3; c++) p.action[c] = g->action[c];
     p.old_logp = g->old_logp; p.old_value = g->old_value; p.adv = g->adv; p.ret = g->ret; p.weight = g->weight;
@@ -4119,28 +4057,10 @@ extern "C" int imgenv_policy_loss(imgenv_t* h, const imgenv_policy_loss_args* g,
 
 // ---- observation post-processing (include/imgenv.h; the kernel is csrc/obs_post.h) ----
 extern "C" int imgenv_obs_post_enable(imgenv_t* h, const imgenv_obs_post_cfg* c, imgenv_obs_post_out* out) {
-    // (the cfg first, as above)
-    RTRY(enable_args(c, "imgenv_obs_post_cfg", out, "imgenv_obs_post_out"));
-    if (c->flags == 0 || (c->flags & ~(IMGENV_OBS_PED_NORM | IMGENV_OBS_CLOSE))) FAIL(IMGENV_EINVAL, "imgenv_obs_post_cfg.flags %d", c->flags);
-    if (c->flags & IMGENV_OBS_PED_NORM)
-        for (int k = 0; k < OBS_POST_DIM; k++) {
-            if (!std::isfinite(c->avg[k]) || !std::isfinite(c->std[k])) FAIL(IMGENV_EINVAL, "imgenv_obs_post_cfg: avg[%d] / std[%d] is not finite", k, k);
-            if (c->std[k] == 0.0) FAIL(IMGENV_EINVAL, "imgenv_obs_post_cfg.std[%d] is 0", k);
-        }
-    if ((c->flags & IMGENV_OBS_CLOSE) && std::isnan(c->close_dist)) FAIL(IMGENV_EINVAL, "imgenv_obs_post_cfg.close_dist is not a number");
-    if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (h->post_on) {
-        const imgenv_obs_post_cfg& o = h->post_cfg;
-        bool same = c->flags == o.flags;
-        if (same && (c->flags & IMGENV_OBS_PED_NORM)) same = memcmp(c->avg, o.avg, sizeof(o.avg)) == 0 && memcmp(c->std, o.std, sizeof(o.std)) == 0;
-        if (same && (c->flags & IMGENV_OBS_CLOSE)) same = c->close_dist == o.close_dist;
-        if (!same) FAIL(IMGENV_EINVAL, "imgenv_obs_post_enable: the handle already post-processes its observations with another cfg");
-        if (out) *out = h->post_out;
-        return IMGENV_OK;
-    }
-    if ((c->flags & IMGENV_OBS_PED_NORM) && h->cfg.ped_vec_dim != OBS_POST_DIM)
-        FAIL(IMGENV_EINVAL, "IMGENV_OBS_PED_NORM: ped_vec_dim %d (the wrapper's constants are for %d)", h->cfg.ped_vec_dim, OBS_POST_DIM);
-    if ((c->flags & IMGENV_OBS_CLOSE) && h->P == 0) FAIL(IMGENV_EINVAL, "IMGENV_OBS_CLOSE on a handle without pedestrians");
+    FeatureMsg msg;
+    FeatureFacts facts;
+    const int plan = planned(obs_post_enable_plan(c, out, feature_facts(h, facts), h ? &h->post.cfg : nullptr, msg), msg);
+    if (plan) return plan < 0 ? plan : enable_repeated(h->post, out);
     HIPCHK(hipSetDevice(h->cfg.device));
     ObsPostDev p;
     memset(&p, 0, sizeof(p));
@@ -4150,27 +4070,31 @@ extern "C" int imgenv_obs_post_enable(imgenv_t* h, const imgenv_obs_post_cfg* c,
     p.per_row = (c->flags & IMGENV_OBS_PED_NORM) ? p.PV : 1;
     p.ped_vector_states = h->out.ped_vector_states;  // (the working arena, also under IMGENV_FLAG_FULL_REWRITE)
     p.ped_min_dists = h->out.ped_min_dists;
+    // one zeroed array per flag, in one transaction: nothing of the handle changes before both are there
+    DevTxn<HipApi> txn;
     if (c->flags & IMGENV_OBS_PED_NORM) {
-        RTRY(dev_alloc(h, &p.norm, (size_t)h->RL * p.PV));
+        txn.room(&p.norm, (size_t)h->RL * p.PV, 0);
         for (int k = 0; k < OBS_POST_DIM; k++) { p.avg[k] = c->avg[k]; p.std[k] = c->std[k]; }
     }
     if (c->flags & IMGENV_OBS_CLOSE) {
-        RTRY(dev_alloc(h, &p.close, (size_t)h->RL));
+        txn.room(&p.close, (size_t)h->RL, 0);
         p.close_dist = c->close_dist;
     }
-    h->post = p;
-    h->post_cfg = *c;
+    if (txn.code()) FAIL(txn.code(), "imgenv_obs_post_enable: %s", txn.error());
+    txn.commit(h->allocs);
+    h->post.dev = p;
+    h->post.cfg = *c;
     imgenv_obs_post_out o = {};
     o.ped_vector_norm = p.norm;
     o.close_to_human = p.close;
-    return enable_done(h, o, &imgenv::post_out, &imgenv::post_on, out);
+    return enable_done(h, h->post, o, out);
 }
 
 // the chain's tail (launch_tails): the normalised pedestrian vectors and close_to_human of every local robot after a step, of the
 // robots a reset chain covers
 static void tail_obs_post(imgenv* h, hipStream_t st, const ChainPlans& k) {
-    if (!h->post_on) return;
-    ObsPostDev pd = h->post;
+    if (!h->post.on) return;
+    ObsPostDev pd = h->post.dev;
     pd.rows = tail_rows(h, k.is_reset);
     const LaunchShape g = plan_tail_launch(h->plan, k.c, (size_t)pd.per_row, OBS_POST_BLOCK, OBS_POST_MAX_BLOCKS);
     (k.is_reset ? k_obs_post<true> : k_obs_post<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(pd);
@@ -4178,27 +4102,20 @@ static void tail_obs_post(imgenv* h, hipStream_t st, const ChainPlans& k) {
 }
 
 extern "C" int imgenv_obs_post_outputs(imgenv_t* h, imgenv_obs_post_out* out) {
-    return feature_outputs(h, &imgenv::post_on, &imgenv::post_out, out, "imgenv_obs_post_enable");
+    return feature_outputs(h, &imgenv::post, out, "imgenv_obs_post_enable");
 }
 
 // ---- running normalisation (include/imgenv.h; the kernels are csrc/normalise.h) ----
 extern "C" int imgenv_normalise_enable(imgenv_t* h, const imgenv_normalise_cfg* c, imgenv_normalise_out* out) {
-    // (the cfg first, as above)
-    RTRY(enable_args(c, "imgenv_normalise_cfg", out, "imgenv_normalise_out"));
-    if (c->flags == 0 || (c->flags & ~(IMGENV_NORM_OBS | IMGENV_NORM_REWARD))) FAIL(IMGENV_EINVAL, "imgenv_normalise_cfg.flags %d", c->flags);
-    if (!std::isfinite(c->clip_obs) || c->clip_obs <= 0.0) FAIL(IMGENV_EINVAL, "imgenv_normalise_cfg.clip_obs %g: finite and above 0", c->clip_obs);
-    if (!std::isfinite(c->clip_reward) || c->clip_reward <= 0.0) FAIL(IMGENV_EINVAL, "imgenv_normalise_cfg.clip_reward %g: finite and above 0", c->clip_reward);
-    if (!std::isfinite(c->eps) || c->eps <= 0.0) FAIL(IMGENV_EINVAL, "imgenv_normalise_cfg.eps %g: finite and above 0", c->eps);
-    if (!(c->gamma >= 0.0 && c->gamma <= 1.0)) FAIL(IMGENV_EINVAL, "imgenv_normalise_cfg.gamma %g: 0 .. 1", c->gamma);
-    if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (h->norm_on) FAIL(IMGENV_EINVAL, "imgenv_normalise_enable has already been called on this handle");
+    FeatureMsg msg;
+    FeatureFacts facts;
+    RTRY(planned(normalise_enable_plan(c, out, feature_facts(h, facts), msg), msg));
     const imgenv_out& w = h->out;
-    const int D = w.state_dim;
-    if (D < 1 || D + 1 > NORM_MAX_COLS) FAIL(IMGENV_EINVAL, "imgenv_normalise_enable: state_dim %d (1 .. %d)", D, NORM_MAX_COLS - 1);
+    const imgenv_stack_out& so = h->stack.out;
+    const int D = facts.state_dim;
     const bool obs = (c->flags & IMGENV_NORM_OBS) != 0, rew = (c->flags & IMGENV_NORM_REWARD) != 0;
-    const imgenv_stack_out& so = h->stack_out;
-    const int K = obs && h->stack_on && so.state_depth >= 2 ? so.state_depth : 0;
-    // one block, every array on a 256-byte boundary, zeroed; nothing of the handle changes before it is there
+    const int K = normalise_stack_depth(facts, obs);
+    // one block with the initial statistics in it; nothing of the handle changes before it is there
     const size_t words = NORM_STATS_WORDS(D);
     const NormaliseLayout l = plan_normalise_layout((size_t)h->RL, D, K, obs, rew);
     HIPCHK(hipSetDevice(h->cfg.device));
@@ -4232,10 +4149,10 @@ extern "C" int imgenv_normalise_enable(imgenv_t* h, const imgenv_normalise_cfg* 
     n.D = D;
     n.K = K;
     n.n_obs = obs ? D : 0;
-    h->norm = n;
-    h->norm_cfg = *c;
-    h->norm_training = true;
-    h->norm_turn = h->norm_ret_turn = 0;
+    h->norm.dev = n;
+    h->norm.cfg = *c;
+    h->norm.training = true;
+    h->norm.turn = h->norm.ret_turn = 0;
     imgenv_normalise_out o = {};
     o.state_dim = D;
     o.state_depth = K;
@@ -4245,17 +4162,17 @@ extern "C" int imgenv_normalise_enable(imgenv_t* h, const imgenv_normalise_cfg* 
     o.stats = n.stats;
     o.returns = n.returns;
     o.training = 1;
-    return enable_done(h, o, &imgenv::norm_out, &imgenv::norm_on, out);
+    return enable_done(h, h->norm, o, out);
 }
 
 // the chain's tail (launch_tails): what plan_norm_chain says of this chain -- the batch into the statistics, the statistics onto the rows
 static void tail_normalise(imgenv* h, hipStream_t st, const ChainPlans& k) {
-    if (!h->norm_on) return;
-    NormDev nd = h->norm;
-    const NormChain n = plan_norm_chain(h->norm_training, (h->norm_cfg.flags & IMGENV_NORM_REWARD) != 0, nd.n_obs, k.is_reset != 0);
+    if (!h->norm.on) return;
+    NormDev nd = h->norm.dev;
+    const NormChain n = plan_norm_chain(h->norm.training, (h->norm.cfg.flags & IMGENV_NORM_REWARD) != 0, nd.n_obs, k.is_reset != 0);
     nd.rows = tail_rows(h, k.is_reset);
     nd.n_ret = n.n_ret; nd.cols = n.cols; nd.update = n.update;
-    nd.turn = h->norm_turn; nd.ret_turn = h->norm_ret_turn;
+    nd.turn = h->norm.turn; nd.ret_turn = h->norm.ret_turn;
     if (n.part) {
         const LaunchShape g = plan_norm_part_launch(h->plan, k.c, nd.cols);
         (k.is_reset ? k_norm_part<true> : k_norm_part<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(nd);
@@ -4266,31 +4183,31 @@ static void tail_normalise(imgenv* h, hipStream_t st, const ChainPlans& k) {
         (k.is_reset ? k_norm_apply<true> : k_norm_apply<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(nd);
         h->launches += 1;
     }
-    if (n.turn) h->norm_turn += 1;
-    if (n.ret_turn) h->norm_ret_turn += 1;
+    if (n.turn) h->norm.turn += 1;
+    if (n.ret_turn) h->norm.ret_turn += 1;
 }
 
 extern "C" int imgenv_normalise_outputs(imgenv_t* h, imgenv_normalise_out* out) {
-    if (int rc = feature_outputs(h, &imgenv::norm_on, &imgenv::norm_out, out, "imgenv_normalise_enable")) return rc;
-    out->stats_word = (int32_t)(h->norm_turn & 1);
-    out->returns_word = (int32_t)(h->norm_ret_turn & 1);
-    out->training = h->norm_training ? 1 : 0;
+    if (int rc = feature_outputs(h, &imgenv::norm, out, "imgenv_normalise_enable")) return rc;
+    out->stats_word = (int32_t)(h->norm.turn & 1);
+    out->returns_word = (int32_t)(h->norm.ret_turn & 1);
+    out->training = h->norm.training ? 1 : 0;
     return IMGENV_OK;
 }
 
 extern "C" int imgenv_normalise_training(imgenv_t* h, int32_t on, void* stream) {
     (void)stream;  // (a host-side switch: the chains queued from now on take it by value)
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->norm_on) FAIL(IMGENV_ESTATE, "imgenv_normalise_enable was not called");
-    h->norm_training = on != 0;
+    RTRY(needs(h->norm.on, "imgenv_normalise_enable"));
+    h->norm.training = on != 0;
     return IMGENV_OK;
 }
 
 static int normalise_stats_args(const imgenv* h, const imgenv_normalise_stats* s) {
     if (!h || !s) FAIL(IMGENV_EINVAL, "null argument");
     if (s->struct_size != (int32_t)sizeof(imgenv_normalise_stats)) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats.struct_size %d (this library's is %d)", s->struct_size, (int)sizeof(imgenv_normalise_stats));
-    if (!h->norm_on) FAIL(IMGENV_ESTATE, "imgenv_normalise_enable was not called");
-    if (s->state_dim != h->norm.D || s->n_rows != h->RL) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats: state_dim %d, n_rows %d (the handle's are %d, %d)", s->state_dim, s->n_rows, h->norm.D, h->RL);
+    RTRY(needs(h->norm.on, "imgenv_normalise_enable"));
+    if (s->state_dim != h->norm.dev.D || s->n_rows != h->RL) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats: state_dim %d, n_rows %d (the handle's are %d, %d)", s->state_dim, s->n_rows, h->norm.dev.D, h->RL);
     if (!s->obs_mean || !s->obs_var) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats: null obs_mean / obs_var");
     return IMGENV_OK;
 }
@@ -4299,17 +4216,17 @@ extern "C" int imgenv_normalise_stats_get(imgenv_t* h, imgenv_normalise_stats* s
     RTRY(normalise_stats_args(h, s));
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(hipDeviceSynchronize());
-    const size_t D = (size_t)h->norm.D, words = NORM_STATS_WORDS(D), RL = (size_t)h->RL;
+    const size_t D = (size_t)h->norm.dev.D, words = NORM_STATS_WORDS(D), RL = (size_t)h->RL;
     std::vector<double> host(words);
-    HIPCHK(hipMemcpy(host.data(), h->norm.stats + (size_t)(h->norm_turn & 1) * words, words * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(host.data(), h->norm.dev.stats + (size_t)(h->norm.turn & 1) * words, words * 8, hipMemcpyDeviceToHost));
     s->obs_count = host[0]; s->ret_count = host[1]; s->ret_mean = host[2]; s->ret_var = host[3];
     for (size_t d = 0; d < D; d++) {
         s->obs_mean[d] = host[4 + d];
         s->obs_var[d] = host[4 + D + d];
     }
     if (s->returns) {
-        if (h->norm.returns)
-            HIPCHK(hipMemcpy(s->returns, h->norm.returns + (size_t)(h->norm_ret_turn & 1) * RL, RL * 8, hipMemcpyDeviceToHost));
+        if (h->norm.dev.returns)
+            HIPCHK(hipMemcpy(s->returns, h->norm.dev.returns + (size_t)(h->norm.ret_turn & 1) * RL, RL * 8, hipMemcpyDeviceToHost));
         else
             std::fill(s->returns, s->returns + RL, 0.0);
     }
@@ -4318,7 +4235,7 @@ extern "C" int imgenv_normalise_stats_get(imgenv_t* h, imgenv_normalise_stats* s
 
 extern "C" int imgenv_normalise_stats_set(imgenv_t* h, const imgenv_normalise_stats* s) {
     RTRY(normalise_stats_args(h, s));
-    const size_t D = (size_t)h->norm.D, words = NORM_STATS_WORDS(D), RL = (size_t)h->RL;
+    const size_t D = (size_t)h->norm.dev.D, words = NORM_STATS_WORDS(D), RL = (size_t)h->RL;
     std::vector<double> host(words);
     host[0] = s->obs_count; host[1] = s->ret_count; host[2] = s->ret_mean; host[3] = s->ret_var;
     for (size_t d = 0; d < D; d++) {
@@ -4336,9 +4253,9 @@ extern "C" int imgenv_normalise_stats_set(imgenv_t* h, const imgenv_normalise_st
             if (!std::isfinite(s->returns[r])) FAIL(IMGENV_EINVAL, "imgenv_normalise_stats.returns[%d] is not finite", (int)r);
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(h->norm.stats + (size_t)(h->norm_turn & 1) * words, host.data(), words * 8, hipMemcpyHostToDevice));
-    if (s->returns && h->norm.returns)
-        HIPCHK(hipMemcpy(h->norm.returns + (size_t)(h->norm_ret_turn & 1) * RL, s->returns, RL * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->norm.dev.stats + (size_t)(h->norm.turn & 1) * words, host.data(), words * 8, hipMemcpyHostToDevice));
+    if (s->returns && h->norm.dev.returns)
+        HIPCHK(hipMemcpy(h->norm.dev.returns + (size_t)(h->norm.ret_turn & 1) * RL, s->returns, RL * 8, hipMemcpyHostToDevice));
     HIPCHK(hipDeviceSynchronize());
     return IMGENV_OK;
 }
@@ -4350,188 +4267,93 @@ static void handle_obs_fields(const imgenv* h, ObsField (&f)[OBSF_COUNT]) {
     a.out = h->out;
     a.ped_image_size[0] = h->cfg.ped_image_size[0];
     a.ped_image_size[1] = h->cfg.ped_image_size[1];
-    a.stack = h->stack_out;
-    a.ped_vector_norm = h->post.norm;
-    if (h->norm_on) {  // (normalise.h's arrays; the stack only where the handle keeps one)
-        a.norm_vector_states = h->norm.norm_vector_states;
-        a.norm_state_stack = h->norm.norm_state_stack;
-        a.norm_K = h->norm.K;
+    a.stack = h->stack.out;
+    a.ped_vector_norm = h->post.dev.norm;
+    if (h->norm.on) {  // (normalise.h's arrays; the stack only where the handle keeps one)
+        a.norm_vector_states = h->norm.dev.norm_vector_states;
+        a.norm_state_stack = h->norm.dev.norm_state_stack;
+        a.norm_K = h->norm.dev.K;
     }
     obs_fields(a, f);
-}
-// the fields of a feature's `list` that `want` names, in the list's order: sel[], their row sizes and their count in n
-template <typename L, int N>
-static int select_obs_fields(const ObsField (&f)[OBSF_COUNT], const L (&list)[N], int want, const char* cfg_name, const L* (&sel)[N], size_t* row_bytes, int& n) {
-    int bad_bit = 0;
-    n = obs_fields_select(f, list, want, sel, &bad_bit);
-    if (n < 0) FAIL(IMGENV_EINVAL, "%s.fields: bit %d names a field of no bytes on this handle", cfg_name, bad_bit);
-    for (int k = 0; k < n; k++) row_bytes[k] = f[sel[k]->id].row_bytes;
-    return IMGENV_OK;
 }
 
 // ---- final observations (include/imgenv.h; the kernel is csrc/final_obs.h) ----
 extern "C" int imgenv_final_obs_enable(imgenv_t* h, const imgenv_final_obs_cfg* c, imgenv_final_obs_out* out) {
-    // (the cfg first, as above)
-    RTRY(enable_args(c, "imgenv_final_obs_cfg", out, "imgenv_final_obs_out"));
-    if (c->fields == 0 || (c->fields & ~(IMGENV_FINAL_ALL | IMGENV_FINAL_NORM_STATES))) FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields %d", c->fields);
-    if ((c->fields & IMGENV_FINAL_NORM_STATES) && !(h && h->norm_on && h->norm.norm_vector_states))
-        FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields %d: IMGENV_FINAL_NORM_STATES before imgenv_normalise_enable with IMGENV_NORM_OBS", c->fields);
-    if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (h->final_on) {
-        if (c->fields != h->final_cfg.fields)
-            FAIL(IMGENV_EINVAL, "imgenv_final_obs_enable: the handle already keeps final observations of the fields %d", h->final_cfg.fields);
-        if (out) *out = h->final_out;
-        return IMGENV_OK;
-    }
-    const int want = c->fields;
-    if ((want & (IMGENV_FINAL_LASERS | IMGENV_FINAL_LASERS_RAW)) && h->out.n_beams <= 0) FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields: lasers on a handle without use_laser");
-    if ((want & IMGENV_FINAL_VIEW_MAPS) && !h->d.keep_view_maps) FAIL(IMGENV_EINVAL, "imgenv_final_obs_cfg.fields: view_maps under IMGENV_FLAG_NO_VIEW_MAPS");
-    if ((want & IMGENV_FINAL_STACKS) && !h->stack_on) FAIL(IMGENV_ESTATE, "IMGENV_FINAL_STACKS before imgenv_stack_enable");
-    if ((want & IMGENV_FINAL_STACKS) && h->stack.n_fields == 0) FAIL(IMGENV_EINVAL, "IMGENV_FINAL_STACKS: no stack of this handle is deeper than 1");
-    if ((want & IMGENV_FINAL_PED_NORM) && !(h->post_on && h->post.norm)) FAIL(IMGENV_ESTATE, "IMGENV_FINAL_PED_NORM before imgenv_obs_post_enable with IMGENV_OBS_PED_NORM");
-    // the fields in the block's order, with where the out struct keeps the copy's pointer
-    imgenv_final_obs_out o = {};
-    imgenv_normalise_out no = h->norm_out;  // (the normalised fields' pointers are handed out there: this struct keeps its layout)
-    struct Slot {
-        int bit, id;
-        void** slot;
-    };
-    const Slot list[] = {
-        {IMGENV_FINAL_VECTOR_STATES, OBSF_VECTOR_STATES, (void**)&o.vector_states},
-        {IMGENV_FINAL_SENSOR_MAPS, OBSF_SENSOR_MAPS, (void**)&o.sensor_maps},
-        {IMGENV_FINAL_LASERS, OBSF_LASERS, (void**)&o.lasers},
-        {IMGENV_FINAL_PED_VECTOR_STATES, OBSF_PED_VECTOR_STATES, (void**)&o.ped_vector_states},
-        {IMGENV_FINAL_PED_MAPS, OBSF_PED_MAPS, (void**)&o.ped_maps},
-        {IMGENV_FINAL_IS_COLLISIONS, OBSF_IS_COLLISIONS, (void**)&o.is_collisions},
-        {IMGENV_FINAL_IS_ARRIVES, OBSF_IS_ARRIVES, (void**)&o.is_arrives},
-        {IMGENV_FINAL_STEP_DS, OBSF_STEP_DS, (void**)&o.step_ds},
-        {IMGENV_FINAL_PED_MIN_DISTS, OBSF_PED_MIN_DISTS, (void**)&o.ped_min_dists},
-        {IMGENV_FINAL_VIEW_MAPS, OBSF_VIEW_MAPS, (void**)&o.view_maps},
-        {IMGENV_FINAL_LASERS_RAW, OBSF_LASERS_RAW, (void**)&o.lasers_raw},
-        {IMGENV_FINAL_STACKS, OBSF_STACK_SENSOR_MAPS, (void**)&o.stack_sensor_maps},
-        {IMGENV_FINAL_STACKS, OBSF_STACK_VECTOR_STATES, (void**)&o.stack_vector_states},
-        {IMGENV_FINAL_STACKS, OBSF_STACK_LASERS, (void**)&o.stack_lasers},
-        {IMGENV_FINAL_PED_NORM, OBSF_PED_VECTOR_NORM, (void**)&o.ped_vector_norm},
-        {IMGENV_FINAL_NORM_STATES, OBSF_NORM_VECTOR_STATES, (void**)&no.final_norm_vector_states},
-        {IMGENV_FINAL_NORM_STATES, OBSF_NORM_STATE_STACK, (void**)&no.final_norm_state_stack},
-    };
-    static_assert(sizeof(list) / sizeof(list[0]) <= FINAL_MAX_FIELDS, "FINAL_MAX_FIELDS");
+    FeatureMsg msg;
+    FeatureFacts facts;
+    const int plan_rc = planned(final_obs_enable_plan(c, out, feature_facts(h, facts), h ? &h->final_obs.cfg : nullptr, msg), msg);
+    if (plan_rc) return plan_rc < 0 ? plan_rc : enable_repeated(h->final_obs, out);
     ObsField fields[OBSF_COUNT];
     handle_obs_fields(h, fields);
-    const Slot* sel[sizeof(list) / sizeof(list[0])];
-    size_t row_bytes[FINAL_MAX_FIELDS];
-    int n = 0;
-    RTRY(select_obs_fields(fields, list, want, "imgenv_final_obs_cfg", sel, row_bytes, n));
-    const FinalPlan plan = plan_final_fields(row_bytes, n);
+    FieldSelection s;
+    RTRY(planned(select_feature_fields(FIELDS_FINAL, fields, c->fields, c->fields, s, msg), msg));
+    const FinalPlan plan = plan_final_fields(s.row_bytes, s.n);
     // one zeroed block (launch_plan.h).  Nothing of the handle changes before it is there.
-    const FinalObsLayout l = plan_final_obs_layout(row_bytes, n, (size_t)h->RL);
+    const FinalObsLayout l = plan_final_obs_layout(s.row_bytes, s.n, (size_t)h->RL);
     unsigned char* block = nullptr;
     RTRY(feature_block(h, l.total, "imgenv_final_obs_enable", &block));
+    imgenv_final_obs_out o = {};
     FinalObsDev fo;
     memset(&fo, 0, sizeof(fo));
     fo.n_fields = plan.n_fields;
     fo.chunks_per_row = plan.chunks_per_row;
     fo.count = (uint32_t*)(block + l.count);
-    for (int k = 0; k < n; k++) {
+    for (int k = 0; k < s.n; k++) {
+        const ObsSlot& slot = OBS_SLOTS[s.id[k]];
         fo.f[k].dst = block + l.field[k];
-        fo.f[k].src = (const unsigned char*)fields[sel[k]->id].src;
+        fo.f[k].src = (const unsigned char*)fields[s.id[k]].src;
         fo.f[k].unit = plan.f[k].unit;
         fo.f[k].chunks = plan.f[k].chunks;
-        *sel[k]->slot = fo.f[k].dst;
+        obs_slot_put(slot, slot.final_out, &o, &h->norm.out, fo.f[k].dst);
     }
     o.final_count = fo.count;
-    h->final_dev = fo;
-    if (h->norm_on) h->norm_out = no;
-    h->final_cfg = *c;
-    return enable_done(h, o, &imgenv::final_out, &imgenv::final_on, out);
+    h->final_obs.dev = fo;
+    h->final_obs.cfg = *c;
+    return enable_done(h, h->final_obs, o, out);
 }
 
 extern "C" int imgenv_final_obs_outputs(imgenv_t* h, imgenv_final_obs_out* out) {
-    return feature_outputs(h, &imgenv::final_on, &imgenv::final_out, out, "imgenv_final_obs_enable");
+    return feature_outputs(h, &imgenv::final_obs, out, "imgenv_final_obs_enable");
 }
 
 // ---- rollout storage (include/imgenv.h; the kernels are csrc/rollout.h) ----
 extern "C" int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* c, imgenv_rollout_out* out) {
-    // (the cfg first, as above)
-    RTRY(enable_args(c, "imgenv_rollout_cfg", out, "imgenv_rollout_out"));
-    if (c->horizon < 1) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.horizon %d: at least 1", c->horizon);
-    if (c->final_capacity < 1) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.final_capacity %d: at least 1", c->final_capacity);
-    const int norm_bits = IMGENV_ROLLOUT_NORM_STATES | IMGENV_ROLLOUT_NORM_REWARDS;
-    if (c->fields == 0 || (c->fields & ~(IMGENV_ROLLOUT_ALL | norm_bits))) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d", c->fields);
-    if (c->fields & norm_bits) {
-        if (!(h && h->norm_on)) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d: IMGENV_ROLLOUT_NORM_* before imgenv_normalise_enable", c->fields);
-        if ((c->fields & IMGENV_ROLLOUT_NORM_STATES) && !h->norm.norm_vector_states)
-            FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d: IMGENV_ROLLOUT_NORM_STATES without IMGENV_NORM_OBS", c->fields);
-        if ((c->fields & IMGENV_ROLLOUT_NORM_REWARDS) && !h->norm.norm_rewards)
-            FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d: IMGENV_ROLLOUT_NORM_REWARDS without IMGENV_NORM_REWARD", c->fields);
-        if (!(c->fields & ~IMGENV_ROLLOUT_NORM_REWARDS)) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d: IMGENV_ROLLOUT_NORM_REWARDS selects no field", c->fields);
-    }
-    if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (h->roll_on) {
-        const imgenv_rollout_cfg& o = h->roll_cfg;
-        if (c->horizon != o.horizon || c->final_capacity != o.final_capacity || c->fields != o.fields)
-            FAIL(IMGENV_EINVAL, "imgenv_rollout_enable: the handle already keeps a rollout of horizon %d, final_capacity %d, fields %d", o.horizon,
-                 o.final_capacity, o.fields);
-        return out ? imgenv_rollout_outputs(h, out) : IMGENV_OK;
-    }
+    FeatureMsg msg;
+    FeatureFacts facts;
+    const int plan = planned(rollout_enable_plan(c, out, feature_facts(h, facts), h ? &h->roll.cfg : nullptr, msg), msg);
+    if (plan < 0) return plan;
+    if (plan == ENABLE_REPEAT) return out ? imgenv_rollout_outputs(h, out) : IMGENV_OK;  // (with the live n / resets)
     const int want = c->fields;
     const size_t RL = (size_t)h->RL, T = (size_t)c->horizon, F = (size_t)c->final_capacity;
-    if ((T + 1) * RL > 0x7fffffffu) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.horizon %d: (horizon + 1) x %d robots is beyond 2^31 - 1", c->horizon, h->RL);
-    if ((want & IMGENV_ROLLOUT_LASERS) && h->out.n_beams <= 0) FAIL(IMGENV_EINVAL, "imgenv_rollout_cfg.fields: lasers on a handle without use_laser");
-    if ((want & IMGENV_ROLLOUT_STACKS) && !h->stack_on) FAIL(IMGENV_ESTATE, "IMGENV_ROLLOUT_STACKS before imgenv_stack_enable");
-    if ((want & IMGENV_ROLLOUT_STACKS) && h->stack.n_fields == 0) FAIL(IMGENV_EINVAL, "IMGENV_ROLLOUT_STACKS: no stack of this handle is deeper than 1");
-    if ((want & IMGENV_ROLLOUT_PED_NORM) && !(h->post_on && h->post.norm)) FAIL(IMGENV_ESTATE, "IMGENV_ROLLOUT_PED_NORM before imgenv_obs_post_enable with IMGENV_OBS_PED_NORM");
-    // the fields in the block's order, with where the out struct keeps the ring's and the final list's pointers
-    const imgenv_out& w = h->out;
-    imgenv_rollout_out o = {};
-    imgenv_normalise_out no = h->norm_out;  // (the normalised fields' ring and final pointers are handed out there)
-    struct Slot {
-        int bit, id;
-        void** ring;
-        void** fin;
-    };
-    const Slot list[] = {
-        {IMGENV_ROLLOUT_SENSOR_MAPS, OBSF_SENSOR_MAPS, (void**)&o.obs_sensor_maps, (void**)&o.final_sensor_maps},
-        {IMGENV_ROLLOUT_VECTOR_STATES, OBSF_VECTOR_STATES, (void**)&o.obs_vector_states, (void**)&o.final_vector_states},
-        {IMGENV_ROLLOUT_LASERS, OBSF_LASERS, (void**)&o.obs_lasers, (void**)&o.final_lasers},
-        {IMGENV_ROLLOUT_PED_VECTOR_STATES, OBSF_PED_VECTOR_STATES, (void**)&o.obs_ped_vector_states, (void**)&o.final_ped_vector_states},
-        {IMGENV_ROLLOUT_PED_MAPS, OBSF_PED_MAPS, (void**)&o.obs_ped_maps, (void**)&o.final_ped_maps},
-        {IMGENV_ROLLOUT_PED_NORM, OBSF_PED_VECTOR_NORM, (void**)&o.obs_ped_vector_norm, (void**)&o.final_ped_vector_norm},
-        {IMGENV_ROLLOUT_STACKS, OBSF_STACK_SENSOR_MAPS, (void**)&o.obs_stack_sensor_maps, (void**)&o.final_stack_sensor_maps},
-        {IMGENV_ROLLOUT_STACKS, OBSF_STACK_VECTOR_STATES, (void**)&o.obs_stack_vector_states, (void**)&o.final_stack_vector_states},
-        {IMGENV_ROLLOUT_STACKS, OBSF_STACK_LASERS, (void**)&o.obs_stack_lasers, (void**)&o.final_stack_lasers},
-        {IMGENV_ROLLOUT_NORM_STATES, OBSF_NORM_VECTOR_STATES, (void**)&no.rollout_obs_norm_vector_states, (void**)&no.rollout_final_norm_vector_states},
-        {IMGENV_ROLLOUT_NORM_STATES, OBSF_NORM_STATE_STACK, (void**)&no.rollout_obs_norm_state_stack, (void**)&no.rollout_final_norm_state_stack},
-    };
-    static_assert(sizeof(list) / sizeof(list[0]) <= ROLLOUT_TABLE_FIELDS, "ROLLOUT_TABLE_FIELDS");
     ObsField fields[OBSF_COUNT];
     handle_obs_fields(h, fields);
-    const Slot* sel[sizeof(list) / sizeof(list[0])];
-    size_t row_bytes[ROLLOUT_TABLE_FIELDS];
-    int n = 0;
-    RTRY(select_obs_fields(fields, list, want, "imgenv_rollout_cfg", sel, row_bytes, n));
+    FieldSelection s;
+    RTRY(planned(select_feature_fields(FIELDS_ROLLOUT, fields, want, want, s, msg), msg));
     // one zeroed block (launch_plan.h); nothing of the handle changes before it is there
-    const RolloutLayout l = plan_rollout_layout(row_bytes, n, RL, T, F);
+    const RolloutLayout l = plan_rollout_layout(s.row_bytes, s.n, RL, T, F);
     unsigned char* block = nullptr;
     RTRY(feature_block(h, l.total, "imgenv_rollout_enable", &block));
+    const imgenv_out& w = h->out;
+    imgenv_rollout_out o = {};
     RolloutDev ro;
     memset(&ro, 0, sizeof(ro));
-    ro.n_fields = n;
-    for (int k = 0; k < n; k++) {
-        const FinalFieldPlan f = plan_final_field(row_bytes[k]);
+    ro.n_fields = s.n;
+    for (int k = 0; k < s.n; k++) {
+        const ObsSlot& slot = OBS_SLOTS[s.id[k]];
+        const FinalFieldPlan f = plan_final_field(s.row_bytes[k]);
         ro.f[k].ring = block + l.ring[k];
         ro.f[k].fin = block + l.fin[k];
-        ro.f[k].src = (const unsigned char*)fields[sel[k]->id].src;
+        ro.f[k].src = (const unsigned char*)fields[s.id[k]].src;
         ro.f[k].unit = f.unit;
         ro.f[k].chunks = f.chunks;
         ro.chunks_per_row += f.chunks;
-        h->roll_row_bytes[k] = row_bytes[k];
-        h->roll_field_id[k] = sel[k]->id;
-        *sel[k]->ring = ro.f[k].ring;
-        *sel[k]->fin = ro.f[k].fin;
+        h->roll.row_bytes[k] = s.row_bytes[k];
+        h->roll.field_id[k] = s.id[k];
+        obs_slot_put(slot, slot.ring_out, &o, &h->norm.out, ro.f[k].ring);
+        obs_slot_put(slot, slot.fin_out, &o, &h->norm.out, ro.f[k].fin);
     }
     // (the working arena, also under IMGENV_FLAG_FULL_REWRITE; IMGENV_ROLLOUT_NORM_REWARDS: what k_norm_apply has just written)
-    ro.rew_src = (want & IMGENV_ROLLOUT_NORM_REWARDS) ? h->norm.norm_rewards : w.step_rewards;
+    ro.rew_src = (want & IMGENV_ROLLOUT_NORM_REWARDS) ? h->norm.dev.norm_rewards : w.step_rewards;
     ro.done_src = w.step_dones;
     ro.clean_src = w.step_is_clean;
     ro.info_src = w.step_dones_info;
@@ -4548,54 +4370,53 @@ extern "C" int imgenv_rollout_enable(imgenv_t* h, const imgenv_rollout_cfg* c, i
     o.horizon = c->horizon;
     o.final_capacity = c->final_capacity;
     o.n = -1;
-    h->roll = ro;
-    if (h->norm_on) h->norm_out = no;
-    h->roll_cfg = *c;
-    h->roll_begun = false;
-    h->roll_n = 0;
-    h->roll_turn = 0;
-    return enable_done(h, o, &imgenv::roll_out, &imgenv::roll_on, out);
+    h->roll.dev = ro;
+    h->roll.cfg = *c;
+    h->roll.begun = false;
+    h->roll.n = 0;
+    h->roll.turn = 0;
+    return enable_done(h, h->roll, o, out);
 }
 
 // the chain's tail (launch_tails), once imgenv_rollout_begin has been called: a step stores transition n and the observation it
 // led to in slot n + 1 (rollout_room has refused a step on a full ring), a reset chain moves the rows of slot n it covers into the
 // final list and stores the new episode's first observation there
 static void tail_rollout(imgenv* h, hipStream_t st, const ChainPlans& k) {
-    if (!h->roll_on || !h->roll_begun) return;
-    RolloutDev ro = h->roll;
+    if (!h->roll.on || !h->roll.begun) return;
+    RolloutDev ro = h->roll.dev;
     ro.rows = tail_rows(h, k.is_reset);
     ro.act_src = h->step.actions;
-    ro.n = h->roll_n;
-    ro.turn = h->roll_turn;
+    ro.n = h->roll.n;
+    ro.turn = h->roll.turn;
     const LaunchShape g = plan_rollout_launch(h->plan, k.c, ro.chunks_per_row);
     (k.is_reset ? k_rollout<true> : k_rollout<false>)<<<dim3(g.grid), dim3(g.block), 0, st>>>(ro);
     h->launches += 1;
     if (k.is_reset)
-        h->roll_turn += 1;
+        h->roll.turn += 1;
     else
-        h->roll_n += 1;
+        h->roll.n += 1;
 }
 
 extern "C" int imgenv_rollout_outputs(imgenv_t* h, imgenv_rollout_out* out) {
-    if (int rc = feature_outputs(h, &imgenv::roll_on, &imgenv::roll_out, out, "imgenv_rollout_enable")) return rc;
-    out->n = h->roll_begun ? h->roll_n : -1;
-    out->resets = (int32_t)h->roll_turn;
+    if (int rc = feature_outputs(h, &imgenv::roll, out, "imgenv_rollout_enable")) return rc;
+    out->n = h->roll.begun ? h->roll.n : -1;
+    out->resets = (int32_t)h->roll.turn;
     return IMGENV_OK;
 }
 
 extern "C" int imgenv_rollout_begin(imgenv_t* h, void* stream) {
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->roll_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_enable was not called");
-    if (!h->obs_exists) FAIL(IMGENV_ESTATE, "imgenv_rollout_begin before the first reset: there is no observation yet");
+    RTRY(needs(h->roll.on, "imgenv_rollout_enable"));
+    if (!h->step.obs_exists) FAIL(IMGENV_ESTATE, "imgenv_rollout_begin before the first reset: there is no observation yet");
     if (h->step.obs_forked) FAIL(IMGENV_ESTATE, "imgenv_rollout_begin between imgenv_step_begin and imgenv_step_end");
     HIPCHK(hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;
     const size_t RL = (size_t)h->RL;
-    if (!h->roll_begun || h->roll_n > 0) {
+    if (!h->roll.begun || h->roll.n > 0) {
         // slot n -> slot 0 (the first time: the live arrays -> slot 0): k_rollout's step instantiation with the scalars off
-        RolloutDev ro = h->roll;
-        if (h->roll_begun)
-            for (int k = 0; k < ro.n_fields; k++) ro.f[k].src = ro.f[k].ring + (size_t)h->roll_n * RL * h->roll_row_bytes[k];
+        RolloutDev ro = h->roll.dev;
+        if (h->roll.begun)
+            for (int k = 0; k < ro.n_fields; k++) ro.f[k].src = ro.f[k].ring + (size_t)h->roll.n * RL * h->roll.row_bytes[k];
         ro.rewards = nullptr;
         ro.n = -1;
         ro.rows = tail_rows(h, 0);
@@ -4603,24 +4424,24 @@ extern "C" int imgenv_rollout_begin(imgenv_t* h, void* stream) {
         k_rollout<false><<<dim3(g.grid), dim3(g.block), 0, st>>>(ro);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipMemsetAsync(h->roll.final_idx, 0xFF, ((size_t)h->roll_cfg.horizon + 1) * RL * 4, st));
-    HIPCHK(hipMemsetAsync(h->roll.final_n, 0, 8, st));
-    h->roll_begun = true;
-    h->roll_n = 0;
-    h->roll_turn = 0;
-    h->chain_seq += 1;
+    HIPCHK(hipMemsetAsync(h->roll.dev.final_idx, 0xFF, ((size_t)h->roll.cfg.horizon + 1) * RL * 4, st));
+    HIPCHK(hipMemsetAsync(h->roll.dev.final_n, 0, 8, st));
+    h->roll.begun = true;
+    h->roll.n = 0;
+    h->roll.turn = 0;
+    h->step.chain_seq += 1;
     return IMGENV_OK;
 }
 
 extern "C" int imgenv_rollout_gae(imgenv_t* h, const float* values, const float* final_values, float gamma, float lam, float* adv, float* ret,
                                   void* stream) {
     if (!h || !values || !adv || !ret) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->roll_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_enable was not called");
-    if (!h->roll_begun) FAIL(IMGENV_ESTATE, "imgenv_rollout_gae before imgenv_rollout_begin");
-    if (h->roll_n == 0) return IMGENV_OK;  // (no transition yet: every row of adv / ret is left untouched)
+    RTRY(needs(h->roll.on, "imgenv_rollout_enable"));
+    if (!h->roll.begun) FAIL(IMGENV_ESTATE, "imgenv_rollout_gae before imgenv_rollout_begin");
+    if (h->roll.n == 0) return IMGENV_OK;  // (no transition yet: every row of adv / ret is left untouched)
     HIPCHK(hipSetDevice(h->cfg.device));
-    const RolloutDev& ro = h->roll;
-    const RolloutGaeDev g = {ro.rewards, ro.dones, ro.is_clean, ro.dones_info, ro.final_idx, values, final_values, adv, ret, gamma, lam, h->roll_n, ro.F, h->RL};
+    const RolloutDev& ro = h->roll.dev;
+    const RolloutGaeDev g = {ro.rewards, ro.dones, ro.is_clean, ro.dones_info, ro.final_idx, values, final_values, adv, ret, gamma, lam, h->roll.n, ro.F, h->RL};
     const LaunchShape s = plan_rollout_gae_launch(h->plan);
     k_rollout_gae<<<dim3(s.grid), dim3(s.block), 0, (hipStream_t)stream>>>(g);
     HIPCHK(hipGetLastError());
@@ -4629,68 +4450,34 @@ extern "C" int imgenv_rollout_gae(imgenv_t* h, const float* values, const float*
 
 // ---- rollout minibatches (include/imgenv.h; the kernels are csrc/minibatch.h) ----
 extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibatch_cfg* c, imgenv_minibatch_out* out) {
-    // (the cfg first, as above)
-    RTRY(enable_args(c, "imgenv_minibatch_cfg", out, "imgenv_minibatch_out"));
-    if (c->batch < 1) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.batch %d: at least 1", c->batch);
-    if (c->buffers < 1 || c->buffers > IMGENV_MB_MAX_BUFFERS) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.buffers %d: 1 .. %d", c->buffers, IMGENV_MB_MAX_BUFFERS);
-    if (c->fields & ~(IMGENV_ROLLOUT_ALL | IMGENV_ROLLOUT_NORM_STATES)) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d", c->fields);  // (NORM_REWARDS names no field)
-    if ((c->fields & IMGENV_ROLLOUT_NORM_STATES) && !(h && h->norm_on)) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: IMGENV_ROLLOUT_NORM_* before imgenv_normalise_enable", c->fields);
-    if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->roll_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch_enable before imgenv_rollout_enable");
-    if (h->mb_on) {
-        const imgenv_minibatch_cfg& o = h->mb_cfg;
-        if (c->batch != o.batch || c->buffers != o.buffers || c->fields != o.fields)
-            FAIL(IMGENV_EINVAL, "imgenv_rollout_minibatch_enable: the handle already gathers minibatches of batch %d, buffers %d, fields %d", o.batch,
-                 o.buffers, o.fields);
-        return out ? imgenv_rollout_minibatch_outputs(h, out) : IMGENV_OK;
-    }
-    const int want = c->fields ? c->fields : (h->roll_cfg.fields & ~IMGENV_ROLLOUT_NORM_REWARDS);
-    if (want & ~h->roll_cfg.fields) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: the rollout stores %d", c->fields, h->roll_cfg.fields);
-    // what the ring keeps, as a catalogue, and the buffers' fields in the ring's own order (imgenv_rollout_enable's list)
+    FeatureMsg msg;
+    FeatureFacts facts;
+    int want = 0;
+    const int plan = planned(minibatch_enable_plan(c, out, feature_facts(h, facts), h ? &h->mb.cfg : nullptr, &want, msg), msg);
+    if (plan < 0) return plan;
+    if (plan == ENABLE_REPEAT) return out ? imgenv_rollout_minibatch_outputs(h, out) : IMGENV_OK;
+    // what the ring keeps, as a catalogue: the buffers' fields come out in the ring's own order
     ObsField ring[OBSF_COUNT] = {};
-    for (int k = 0; k < h->roll.n_fields; k++) ring[h->roll_field_id[k]] = {h->roll.f[k].ring, h->roll_row_bytes[k]};
-    struct Slot {
-        int bit, id;
-        size_t slot;  // of MbBufferAll, in bytes
-    };
-    const Slot list[] = {
-        {IMGENV_ROLLOUT_SENSOR_MAPS, OBSF_SENSOR_MAPS, offsetof(imgenv_minibatch_buffer, mb_sensor_maps)},
-        {IMGENV_ROLLOUT_VECTOR_STATES, OBSF_VECTOR_STATES, offsetof(imgenv_minibatch_buffer, mb_vector_states)},
-        {IMGENV_ROLLOUT_LASERS, OBSF_LASERS, offsetof(imgenv_minibatch_buffer, mb_lasers)},
-        {IMGENV_ROLLOUT_PED_VECTOR_STATES, OBSF_PED_VECTOR_STATES, offsetof(imgenv_minibatch_buffer, mb_ped_vector_states)},
-        {IMGENV_ROLLOUT_PED_MAPS, OBSF_PED_MAPS, offsetof(imgenv_minibatch_buffer, mb_ped_maps)},
-        {IMGENV_ROLLOUT_PED_NORM, OBSF_PED_VECTOR_NORM, offsetof(imgenv_minibatch_buffer, mb_ped_vector_norm)},
-        {IMGENV_ROLLOUT_STACKS, OBSF_STACK_SENSOR_MAPS, offsetof(imgenv_minibatch_buffer, mb_stack_sensor_maps)},
-        {IMGENV_ROLLOUT_STACKS, OBSF_STACK_VECTOR_STATES, offsetof(imgenv_minibatch_buffer, mb_stack_vector_states)},
-        {IMGENV_ROLLOUT_STACKS, OBSF_STACK_LASERS, offsetof(imgenv_minibatch_buffer, mb_stack_lasers)},
-        // (the normalised fields: their buffers' pointers are imgenv_normalise_out's, kept behind the public struct in MbBufferAll)
-        {IMGENV_ROLLOUT_NORM_STATES, OBSF_NORM_VECTOR_STATES, offsetof(MbBufferAll, mb_norm_vector_states)},
-        {IMGENV_ROLLOUT_NORM_STATES, OBSF_NORM_STATE_STACK, offsetof(MbBufferAll, mb_norm_state_stack)},
-    };
-    static_assert(sizeof(list) / sizeof(list[0]) <= ROLLOUT_TABLE_FIELDS, "ROLLOUT_TABLE_FIELDS");
-    const Slot* sel[sizeof(list) / sizeof(list[0])];
-    size_t row_bytes[ROLLOUT_TABLE_FIELDS];
-    int n = 0;
-    RTRY(select_obs_fields(ring, list, want, "imgenv_minibatch_cfg", sel, row_bytes, n));
-    if (n == 0) FAIL(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: no field of the rollout", c->fields);
+    for (int k = 0; k < h->roll.dev.n_fields; k++) ring[h->roll.field_id[k]] = {h->roll.dev.f[k].ring, h->roll.row_bytes[k]};
+    FieldSelection s;
+    RTRY(planned(select_feature_fields(FIELDS_MINIBATCH, ring, want, c->fields, s, msg), msg));
     // one zeroed block (launch_plan.h); nothing of the handle changes before it is there
-    const size_t RL = (size_t)h->RL, T = (size_t)h->roll_cfg.horizon, NB = (size_t)c->buffers;
-    const MinibatchLayout l = plan_minibatch_layout(row_bytes, n, RL, T, (size_t)c->batch, NB);
+    const size_t RL = (size_t)h->RL, T = (size_t)h->roll.cfg.horizon, NB = (size_t)c->buffers;
+    const MinibatchLayout l = plan_minibatch_layout(s.row_bytes, s.n, RL, T, (size_t)c->batch, NB);
     unsigned char* block = nullptr;
     RTRY(feature_block(h, l.total, "imgenv_rollout_minibatch_enable", &block));
     MbGatherDev g;
     memset(&g, 0, sizeof(g));
-    g.n_fields = n;
-    for (int k = 0; k < n; k++) {
-        const FinalFieldPlan f = plan_final_field(row_bytes[k]);  // (the ring's own chunking)
-        g.f[k].ring = (const unsigned char*)ring[sel[k]->id].src;
-        g.f[k].dst = (unsigned char*)(uintptr_t)sel[k]->slot;  // (which pointer of the buffer: mb_gather_args)
-        g.f[k].unit = f.unit;
+    g.n_fields = s.n;
+    for (int k = 0; k < s.n; k++) {
+        const FinalFieldPlan f = plan_final_field(s.row_bytes[k]);  // (the ring's own chunking)
+        g.f[k].ring = (const unsigned char*)ring[s.id[k]].src;
+        g.f[k].unit = f.unit;  // (dst: the buffer's, h->mb.dst, at the call)
         g.f[k].chunks = f.chunks;
         g.chunks_per_row += f.chunks;
     }
     imgenv_minibatch_out o = {};
-    o.horizon = h->roll_cfg.horizon;
+    o.horizon = h->roll.cfg.horizon;
     o.batch = c->batch;
     o.buffers = c->buffers;
     o.fields = want;
@@ -4703,10 +4490,12 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
     o.stat_part = (double*)(block + l.stat_part);
     o.stat_mean = (double*)(block + l.stat_mean);
     for (size_t b = 0; b < NB; b++) {
-        MbBufferAll& all_b = h->mb_all[b];
-        all_b = MbBufferAll{};
-        imgenv_minibatch_buffer& m = all_b.pub;
-        for (int k = 0; k < n; k++) *(void**)((unsigned char*)&all_b + sel[k]->slot) = block + l.field[b][k];
+        imgenv_minibatch_buffer& m = o.buf[b];
+        for (int k = 0; k < s.n; k++) {
+            const ObsSlot& slot = OBS_SLOTS[s.id[k]];
+            h->mb.dst[b][k] = block + l.field[b][k];
+            obs_slot_put_mb(slot, &m, &h->norm.out, (int)b, h->mb.dst[b][k]);
+        }
         m.mb_actions = (float*)(block + l.scalar[b][MB_S_ACTIONS]);
         m.mb_rewards = (float*)(block + l.scalar[b][MB_S_REWARDS]);
         m.mb_dones = block + l.scalar[b][MB_S_DONES];
@@ -4714,56 +4503,51 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
         m.mb_index = (int32_t*)(block + l.scalar[b][MB_S_INDEX]);
         m.mb_weight = (float*)(block + l.scalar[b][MB_S_WEIGHT]);
         m.mb_scalars = (float*)(block + l.scalar[b][MB_S_SCALARS]);
-        o.buf[b] = m;
-        if (h->norm_on) {
-            h->norm_out.mb_norm_vector_states[b] = all_b.mb_norm_vector_states;
-            h->norm_out.mb_norm_state_stack[b] = all_b.mb_norm_state_stack;
-        }
     }
     g.order = o.order;
     g.B = (uint32_t)c->batch;
     g.TR = (uint32_t)(T * RL);
-    g.actions = h->roll.actions;
-    g.rewards = h->roll.rewards;
-    g.dones = h->roll.dones;
-    g.dones_info = h->roll.dones_info;
-    h->mb_gather = g;
-    h->mb_cfg = *c;
-    h->mb_indexed = h->mb_shuffled = false;
-    return enable_done(h, o, &imgenv::mb_out, &imgenv::mb_on, out);
+    g.actions = h->roll.dev.actions;
+    g.rewards = h->roll.dev.rewards;
+    g.dones = h->roll.dev.dones;
+    g.dones_info = h->roll.dev.dones_info;
+    h->mb.dev = g;
+    h->mb.cfg = *c;
+    h->mb.indexed = h->mb.shuffled = false;
+    return enable_done(h, h->mb, o, out);
 }
 
 extern "C" int imgenv_rollout_minibatch_outputs(imgenv_t* h, imgenv_minibatch_out* out) {
-    return feature_outputs(h, &imgenv::mb_on, &imgenv::mb_out, out, "imgenv_rollout_minibatch_enable");
+    return feature_outputs(h, &imgenv::mb, out, "imgenv_rollout_minibatch_enable");
 }
 
 // the index is of this moment: no chain and no imgenv_rollout_begin since
 static int minibatch_fresh(const imgenv* h, const char* who) {
-    if (!h->mb_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch_enable was not called");
-    if (!h->mb_indexed) FAIL(IMGENV_ESTATE, "%s before imgenv_rollout_index", who);
-    if (!h->roll_begun || h->mb_gen_n != h->roll_n || h->mb_gen_seq != h->chain_seq) FAIL(IMGENV_ESTATE, "%s: rollout changed since imgenv_rollout_index", who);
+    RTRY(needs(h->mb.on, "imgenv_rollout_minibatch_enable"));
+    if (!h->mb.indexed) FAIL(IMGENV_ESTATE, "%s before imgenv_rollout_index", who);
+    if (!h->roll.begun || h->mb.gen_n != h->roll.n || h->mb.gen_seq != h->step.chain_seq) FAIL(IMGENV_ESTATE, "%s: rollout changed since imgenv_rollout_index", who);
     return IMGENV_OK;
 }
 
 extern "C" int imgenv_rollout_index(imgenv_t* h, void* stream) {
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->mb_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch_enable was not called");
-    if (!h->roll_begun) FAIL(IMGENV_ESTATE, "imgenv_rollout_index before imgenv_rollout_begin");
-    if (h->roll_n == 0) FAIL(IMGENV_ESTATE, "imgenv_rollout_index: no transition is stored yet");
+    RTRY(needs(h->mb.on, "imgenv_rollout_minibatch_enable"));
+    if (!h->roll.begun) FAIL(IMGENV_ESTATE, "imgenv_rollout_index before imgenv_rollout_begin");
+    if (h->roll.n == 0) FAIL(IMGENV_ESTATE, "imgenv_rollout_index: no transition is stored yet");
     HIPCHK(hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;
-    const imgenv_minibatch_out& o = h->mb_out;
-    const size_t total = (size_t)h->roll_n * (size_t)h->RL;
-    const MbIndexDev d = {h->roll.is_clean, o.valid, o.tile_count, o.tile_base, o.valid_n, (uint32_t)total, (uint32_t)plan_mb_tiles(total)};
+    const imgenv_minibatch_out& o = h->mb.out;
+    const size_t total = (size_t)h->roll.n * (size_t)h->RL;
+    const MbIndexDev d = {h->roll.dev.is_clean, o.valid, o.tile_count, o.tile_base, o.valid_n, (uint32_t)total, (uint32_t)plan_mb_tiles(total)};
     const LaunchShape tiles = plan_mb_index_launch(total), one = plan_mb_scan_launch();
     k_mb_count<<<dim3(tiles.grid), dim3(tiles.block), 0, st>>>(d);
     k_mb_scan<<<dim3(one.grid), dim3(one.block), 0, st>>>(d);
     k_mb_scatter<<<dim3(tiles.grid), dim3(tiles.block), 0, st>>>(d);
     HIPCHK(hipGetLastError());
-    h->mb_indexed = true;
-    h->mb_shuffled = false;
-    h->mb_gen_n = h->roll_n;
-    h->mb_gen_seq = h->chain_seq;
+    h->mb.indexed = true;
+    h->mb.shuffled = false;
+    h->mb.gen_n = h->roll.n;
+    h->mb.gen_seq = h->step.chain_seq;
     return IMGENV_OK;
 }
 
@@ -4773,8 +4557,8 @@ extern "C" int imgenv_rollout_stats(imgenv_t* h, const float* x, double eps, flo
     RTRY(minibatch_fresh(h, "imgenv_rollout_stats"));
     HIPCHK(hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;
-    const imgenv_minibatch_out& o = h->mb_out;
-    const size_t total = (size_t)h->mb_gen_n * (size_t)h->RL;
+    const imgenv_minibatch_out& o = h->mb.out;
+    const size_t total = (size_t)h->mb.gen_n * (size_t)h->RL;
     const MbStatsDev s = {x, o.valid, o.valid_n, o.stat_part, o.stat_mean, norm_out ? norm_out : o.norm, eps, (uint32_t)plan_mb_stats_tiles(total)};
     const LaunchShape tiles = plan_mb_stats_launch(total), one = plan_mb_stats_final_launch();
     k_mb_stats<false><<<dim3(tiles.grid), dim3(tiles.block), 0, st>>>(s);
@@ -4789,12 +4573,12 @@ extern "C" int imgenv_rollout_shuffle(imgenv_t* h, uint32_t seed_lo, uint32_t se
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
     RTRY(minibatch_fresh(h, "imgenv_rollout_shuffle"));
     HIPCHK(hipSetDevice(h->cfg.device));
-    const imgenv_minibatch_out& o = h->mb_out;
-    const MbShuffleDev s = {o.valid, o.valid_n, o.order, h->mb_gather.TR, mb_keys(seed_lo, seed_hi)};
+    const imgenv_minibatch_out& o = h->mb.out;
+    const MbShuffleDev s = {o.valid, o.valid_n, o.order, h->mb.dev.TR, mb_keys(seed_lo, seed_hi)};
     const LaunchShape g = plan_mb_shuffle_launch(s.TR);
     k_mb_shuffle<<<dim3(g.grid), dim3(g.block), 0, (hipStream_t)stream>>>(s);
     HIPCHK(hipGetLastError());
-    h->mb_shuffled = true;
+    h->mb.shuffled = true;
     return IMGENV_OK;
 }
 
@@ -4808,15 +4592,14 @@ extern "C" int imgenv_rollout_minibatch(imgenv_t* h, const imgenv_minibatch_args
     for (int s = 0; s < a->n_scalars; s++)
         if (!a->scalars[s]) FAIL(IMGENV_EINVAL, "imgenv_minibatch_args.scalars[%d] is null", s);
     if (!h) FAIL(IMGENV_EINVAL, "null argument");
-    if (!h->mb_on) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch_enable was not called");
-    if (a->buffer < 0 || a->buffer >= h->mb_cfg.buffers) FAIL(IMGENV_EINVAL, "imgenv_minibatch_args.buffer %d: 0 .. %d", a->buffer, h->mb_cfg.buffers - 1);
+    RTRY(needs(h->mb.on, "imgenv_rollout_minibatch_enable"));
+    if (a->buffer < 0 || a->buffer >= h->mb.cfg.buffers) FAIL(IMGENV_EINVAL, "imgenv_minibatch_args.buffer %d: 0 .. %d", a->buffer, h->mb.cfg.buffers - 1);
     RTRY(minibatch_fresh(h, "imgenv_rollout_minibatch"));
-    if (!h->mb_shuffled) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch before imgenv_rollout_shuffle");
+    if (!h->mb.shuffled) FAIL(IMGENV_ESTATE, "imgenv_rollout_minibatch before imgenv_rollout_shuffle");
     HIPCHK(hipSetDevice(h->cfg.device));
-    const MbBufferAll& all_b = h->mb_all[a->buffer];
-    const imgenv_minibatch_buffer& m = all_b.pub;
-    MbGatherDev g = h->mb_gather;
-    for (int k = 0; k < g.n_fields; k++) g.f[k].dst = *(unsigned char* const*)((const unsigned char*)&all_b + (size_t)(uintptr_t)g.f[k].dst);
+    const imgenv_minibatch_buffer& m = h->mb.out.buf[a->buffer];
+    MbGatherDev g = h->mb.dev;
+    for (int k = 0; k < g.n_fields; k++) g.f[k].dst = h->mb.dst[a->buffer][k];
     g.first = (size_t)a->j * (size_t)g.B;
     g.mb_actions = m.mb_actions;
     g.mb_rewards = m.mb_rewards;
@@ -4828,7 +4611,7 @@ extern "C" int imgenv_rollout_minibatch(imgenv_t* h, const imgenv_minibatch_args
     for (int s = 0; s < a->n_scalars; s++) g.scalars[s] = a->scalars[s];
     g.n_scalars = a->n_scalars;
     g.normalise = a->normalise;
-    g.norm = a->norm ? a->norm : h->mb_out.norm;
+    g.norm = a->norm ? a->norm : h->mb.out.norm;
     const LaunchShape s = plan_mb_gather_launch(g.B, g.chunks_per_row);
     k_rollout_gather<<<dim3(s.grid), dim3(s.block), 0, (hipStream_t)stream>>>(g);
     HIPCHK(hipGetLastError());

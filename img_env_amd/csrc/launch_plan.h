@@ -694,7 +694,8 @@ inline LaunchShape plan_norm_apply_launch(const PlanHandle& h, const PlanChain& 
 // ---------------------------------------------------------------------------------------- the features' device blocks
 // A feature's arrays live in ONE zeroed allocation, every array on a 256-byte boundary (so a row of any field starts on a multiple
 // of its unit).  The layouts are fixed here, device-free: the enable functions of imgenv_hip.hip allocate `total` bytes and hand
-// out block + offset; tests/host/field_rows_check.cpp pins every offset.
+// out block + offset; tests/host/field_rows_check.cpp pins every offset of all seven (the stacks, the final observations, the
+// rollout, the minibatches, the normalisation, the policy head, the PPO loss).
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 struct Carve {
     size_t total = 0;
@@ -810,6 +811,55 @@ inline NormaliseLayout plan_normalise_layout(size_t RL, int D, int K, bool obs, 
     l.norm_vector_states = c.take(obs ? RL * D * 4 : 0);
     l.norm_state_stack = c.take((size_t)K * RL * D * 4);
     l.norm_rewards = c.take(rew ? RL * 8 : 0);
+    l.total = c.total;
+    return l;
+}
+
+// imgenv_policy_enable (policy.h): a categorical head (`cat`) keeps the index drawn, a Gaussian one the raw sample of its `cols`
+// columns (cat: 1); T > 0 (IMGENV_POLICY_STORE, the rollout's horizon) adds what the window stores per slot
+struct PolicyLayout {
+    size_t index, raw, logp, entropy, pol_raw, pol_logp, pol_value, total;
+};
+inline PolicyLayout plan_policy_layout(bool cat, size_t cols, size_t RL, size_t T) {
+    PolicyLayout l = {};
+    Carve c;
+    l.index = c.take(cat ? RL * 4 : 0);
+    l.raw = c.take(cat ? 0 : RL * cols * 4);
+    l.logp = c.take(RL * 4);
+    l.entropy = c.take(RL * 4);
+    l.pol_raw = c.take(cols * T * RL * 4);
+    l.pol_logp = c.take(T * RL * 4);
+    l.pol_value = c.take(T > 0 ? (T + 1) * RL * 4 : 0);
+    l.total = c.total;
+    return l;
+}
+
+// imgenv_policy_loss_enable (policy_loss.h): B = max_rows, n = A (cat) or C, n_rec = the workgroups of the largest row launch
+// (plan_policy_loss_launch(max_rows, ...).grid), each of which leaves one record of `rec_doubles` (PLOSS_REC) float64
+struct PolicyLossLayout {
+    size_t logp, entropy, ratio, pg, vl, d_params, d_log_std, d_log_std_shared, d_values, stats, n_bad, inv_w;
+    size_t row_m, row_log_s, row_gu, row_w, rec, total;
+};
+inline PolicyLossLayout plan_policy_loss_layout(bool cat, size_t B, size_t n, size_t n_rec, size_t rec_doubles) {
+    PolicyLossLayout l = {};
+    Carve c;
+    l.logp = c.take(B * 4);
+    l.entropy = c.take(B * 4);
+    l.ratio = c.take(B * 4);
+    l.pg = c.take(B * 4);
+    l.vl = c.take(B * 4);
+    l.d_params = c.take(B * n * 4);
+    l.d_log_std = c.take(cat ? 0 : B * n * 4);
+    l.d_log_std_shared = c.take(cat ? 0 : n * 4);
+    l.d_values = c.take(B * 4);
+    l.stats = c.take(8 * 4);
+    l.n_bad = c.take(4);
+    l.inv_w = c.take(4);
+    l.row_m = c.take(cat ? B * 4 : 0);
+    l.row_log_s = c.take(cat ? B * 4 : 0);
+    l.row_gu = c.take(B * 4);
+    l.row_w = c.take(B * 4);
+    l.rec = c.take(n_rec * rec_doubles * 8);
     l.total = c.total;
     return l;
 }

@@ -1,10 +1,10 @@
 // obs_fields.h -- the observation fields a feature can copy rows of (final observations, rollout storage, rollout minibatches):
 // which they are, where a handle keeps each one and how long its row is.  Host code, nothing of HIP: plain C++17, compiled by g++
-// for tests/host/field_rows_check.cpp.
+// for tests/host/field_rows_check.cpp and tests/host/feature_plan_check.cpp.
 //
-// A feature keeps only its own ordered list of (bit of its cfg, field, where its out struct keeps the copy's pointer); the order
-// decides the layout of its block.  obs_fields fills the catalogue from plain facts about the handle, obs_fields_select picks a
-// list's fields.
+// The slot catalogue (OBS_SLOTS) says, per field, which bit of a feature's cfg names it and where the feature's out struct keeps
+// the copy's pointer; a feature keeps only the order of its block.  obs_fields fills a handle's catalogue of arrays from plain
+// facts about it, obs_fields_select picks a list's fields (feature_plan.h: select_feature_fields).
 #pragma once
 #include <stddef.h>
 
@@ -64,13 +64,72 @@ inline void obs_fields(const ObsFacts& a, ObsField (&f)[OBSF_COUNT]) {
     f[OBSF_NORM_STATE_STACK] = {a.norm_state_stack, depth(a.norm_K) * D * 4};
 }
 
+// ---------------------------------------------------------------------------------------- the slot catalogue
+// One row per field: the bit that names it in imgenv_final_obs_cfg and in imgenv_rollout_cfg / imgenv_minibatch_cfg (0: the feature
+// has no such field), and where each feature hands the copy's pointer out, as a byte offset into imgenv_final_obs_out,
+// imgenv_rollout_out (ring and final list) and imgenv_minibatch_buffer.  `norm`: the field is normalise.h's, and every one of its
+// slots is a member of imgenv_normalise_out instead (those structs keep their layout); its minibatch slot is entry 0 of an array
+// with one entry per buffer.
+#define OBS_NO_SLOT ((size_t)-1)
+struct ObsSlot {
+    int final_bit, rollout_bit;
+    size_t final_out, ring_out, fin_out, mb_out;
+    bool norm;
+};
+#define OBS_SLOT_FINAL_ONLY(bit, member) {bit, 0, offsetof(imgenv_final_obs_out, member), OBS_NO_SLOT, OBS_NO_SLOT, OBS_NO_SLOT, false}
+#define OBS_SLOT_ALL(fbit, rbit, member)                                                                                       \
+    {fbit, rbit, offsetof(imgenv_final_obs_out, member), offsetof(imgenv_rollout_out, obs_##member),                           \
+     offsetof(imgenv_rollout_out, final_##member), offsetof(imgenv_minibatch_buffer, mb_##member), false}
+#define OBS_SLOT_NORM(member)                                                                                                  \
+    {IMGENV_FINAL_NORM_STATES, IMGENV_ROLLOUT_NORM_STATES, offsetof(imgenv_normalise_out, final_##member),                     \
+     offsetof(imgenv_normalise_out, rollout_obs_##member), offsetof(imgenv_normalise_out, rollout_final_##member),             \
+     offsetof(imgenv_normalise_out, mb_##member), true}
+static const ObsSlot OBS_SLOTS[OBSF_COUNT] = {
+    OBS_SLOT_ALL(IMGENV_FINAL_VECTOR_STATES, IMGENV_ROLLOUT_VECTOR_STATES, vector_states),
+    OBS_SLOT_ALL(IMGENV_FINAL_SENSOR_MAPS, IMGENV_ROLLOUT_SENSOR_MAPS, sensor_maps),
+    OBS_SLOT_ALL(IMGENV_FINAL_LASERS, IMGENV_ROLLOUT_LASERS, lasers),
+    OBS_SLOT_ALL(IMGENV_FINAL_PED_VECTOR_STATES, IMGENV_ROLLOUT_PED_VECTOR_STATES, ped_vector_states),
+    OBS_SLOT_ALL(IMGENV_FINAL_PED_MAPS, IMGENV_ROLLOUT_PED_MAPS, ped_maps),
+    OBS_SLOT_FINAL_ONLY(IMGENV_FINAL_IS_COLLISIONS, is_collisions),
+    OBS_SLOT_FINAL_ONLY(IMGENV_FINAL_IS_ARRIVES, is_arrives),
+    OBS_SLOT_FINAL_ONLY(IMGENV_FINAL_STEP_DS, step_ds),
+    OBS_SLOT_FINAL_ONLY(IMGENV_FINAL_PED_MIN_DISTS, ped_min_dists),
+    OBS_SLOT_FINAL_ONLY(IMGENV_FINAL_VIEW_MAPS, view_maps),
+    OBS_SLOT_FINAL_ONLY(IMGENV_FINAL_LASERS_RAW, lasers_raw),
+    OBS_SLOT_ALL(IMGENV_FINAL_STACKS, IMGENV_ROLLOUT_STACKS, stack_sensor_maps),
+    OBS_SLOT_ALL(IMGENV_FINAL_STACKS, IMGENV_ROLLOUT_STACKS, stack_vector_states),
+    OBS_SLOT_ALL(IMGENV_FINAL_STACKS, IMGENV_ROLLOUT_STACKS, stack_lasers),
+    OBS_SLOT_ALL(IMGENV_FINAL_PED_NORM, IMGENV_ROLLOUT_PED_NORM, ped_vector_norm),
+    OBS_SLOT_NORM(norm_vector_states),
+    OBS_SLOT_NORM(norm_state_stack),
+};
+// A feature keeps only the order of its block.  The final observations: the enum's.  The rollout and the minibatches: sensor_maps
+// in front of vector_states, ped_vector_norm in front of the stacks (the order of the blocks already handed out: it must not change).
+static const int FINAL_FIELD_ORDER[] = {
+    OBSF_VECTOR_STATES, OBSF_SENSOR_MAPS, OBSF_LASERS, OBSF_PED_VECTOR_STATES, OBSF_PED_MAPS, OBSF_IS_COLLISIONS, OBSF_IS_ARRIVES,
+    OBSF_STEP_DS, OBSF_PED_MIN_DISTS, OBSF_VIEW_MAPS, OBSF_LASERS_RAW, OBSF_STACK_SENSOR_MAPS, OBSF_STACK_VECTOR_STATES,
+    OBSF_STACK_LASERS, OBSF_PED_VECTOR_NORM, OBSF_NORM_VECTOR_STATES, OBSF_NORM_STATE_STACK};
+static const int ROLLOUT_FIELD_ORDER[] = {
+    OBSF_SENSOR_MAPS, OBSF_VECTOR_STATES, OBSF_LASERS, OBSF_PED_VECTOR_STATES, OBSF_PED_MAPS, OBSF_PED_VECTOR_NORM,
+    OBSF_STACK_SENSOR_MAPS, OBSF_STACK_VECTOR_STATES, OBSF_STACK_LASERS, OBSF_NORM_VECTOR_STATES, OBSF_NORM_STATE_STACK};
+// the pointer a slot receives: member `off` (the slot's final_out, ring_out or fin_out) of `own`, the feature's out struct -- of
+// `norm_out` for a normalised field
+inline void obs_slot_put(const ObsSlot& s, size_t off, void* own, imgenv_normalise_out* norm_out, void* p) {
+    *(void**)((unsigned char*)(s.norm ? (void*)norm_out : own) + off) = p;
+}
+// likewise for minibatch buffer `b`: the slot's mb_out member of `buf` (that buffer's struct), or entry b of norm_out's array
+inline void obs_slot_put_mb(const ObsSlot& s, imgenv_minibatch_buffer* buf, imgenv_normalise_out* norm_out, int b, void* p) {
+    obs_slot_put(s, s.mb_out + (s.norm ? (size_t)b * sizeof(void*) : 0), buf, norm_out, p);
+}
+
 // the entries of `list` (any struct with `bit` and `id`) whose bit is in `want`, in the list's order, into sel[]; their count.
 // An optional field the handle lacks is skipped silently; any other field without an array or of no bytes is refused: -1, and
 // *bad_bit is the bit that named it.
-template <typename L, int N>
-inline int obs_fields_select(const ObsField (&f)[OBSF_COUNT], const L (&list)[N], int want, const L* (&sel)[N], int* bad_bit) {
+template <typename L>
+inline int obs_fields_select_n(const ObsField (&f)[OBSF_COUNT], const L* list, int n_list, int want, const L** sel, int* bad_bit) {
     int n = 0;
-    for (const L& s : list) {
+    for (int q = 0; q < n_list; q++) {
+        const L& s = list[q];
         const ObsField& of = f[s.id];
         if (!(want & s.bit) || (s.id >= OBSF_FIRST_OPTIONAL && !of.src)) continue;
         if (!of.src || of.row_bytes == 0) {
@@ -80,4 +139,8 @@ inline int obs_fields_select(const ObsField (&f)[OBSF_COUNT], const L (&list)[N]
         sel[n++] = &s;
     }
     return n;
+}
+template <typename L, int N>
+inline int obs_fields_select(const ObsField (&f)[OBSF_COUNT], const L (&list)[N], int want, const L* (&sel)[N], int* bad_bit) {
+    return obs_fields_select_n(f, list, N, want, sel, bad_bit);
 }

@@ -1,6 +1,7 @@
 // field_rows_check.cpp -- what the row-copy features share, on the CPU: the chunk walk and the unit dispatch of
 // img_env_amd/csrc/field_rows.h, the catalogue of capturable fields of obs_fields.h, and the block layouts of launch_plan.h
-// (plan_stack, plan_final_obs_layout, plan_rollout_layout, plan_minibatch_layout, plan_normalise_layout).
+// (plan_stack, plan_final_obs_layout, plan_rollout_layout, plan_minibatch_layout, plan_normalise_layout, plan_policy_layout,
+// plan_policy_loss_layout).
 //   g++ -std=c++17 tests/host/field_rows_check.cpp -o check && ./check
 // (also built with -fsanitize=address,undefined by tests/test_field_rows.py)
 //
@@ -365,10 +366,69 @@ static void check_layouts() {
     }
 }
 
+// The policy head's and the PPO loss's blocks.  The literals are the offsets of the commit before plan_policy_layout and
+// plan_policy_loss_layout existed, derived by hand from the cv.take lines imgenv_policy_enable and imgenv_policy_loss_enable then
+// spelled out (each array rounded up to 256 bytes, in the order written there; an array of no bytes sits at the next one's offset).
+static void check_policy_layouts() {
+    const size_t RL = 4, T = 3;
+    struct PolicyCase {
+        bool cat;
+        size_t cols, T;
+        size_t want[8];  // index, raw, logp, entropy, pol_raw, pol_logp, pol_value, total
+        size_t bytes[7];
+    };
+    const PolicyCase policy[4] = {
+        // categorical, A = 11: index [RL] i32 and no raw sample; without STORE nothing behind entropy
+        {true, 1, 0, {0, 256, 256, 512, 768, 768, 768, 768}, {16, 0, 16, 16, 0, 0, 0}},
+        // with STORE: pol_raw [1][T][RL], pol_logp [T][RL], pol_value [T + 1][RL]
+        {true, 1, T, {0, 256, 256, 512, 768, 1024, 1280, 1536}, {16, 0, 16, 16, 48, 48, 64}},
+        // Gaussian, C = 2: raw [RL][2] and no index
+        {false, 2, 0, {0, 0, 256, 512, 768, 768, 768, 768}, {0, 32, 16, 16, 0, 0, 0}},
+        {false, 2, T, {0, 0, 256, 512, 768, 1024, 1280, 1536}, {0, 32, 16, 16, 96, 48, 64}},
+    };
+    for (const PolicyCase& c : policy) {
+        const PolicyLayout l = plan_policy_layout(c.cat, c.cols, RL, c.T);
+        const size_t got[8] = {l.index, l.raw, l.logp, l.entropy, l.pol_raw, l.pol_logp, l.pol_value, l.total};
+        std::vector<std::pair<size_t, size_t>> arrays;
+        for (int k = 0; k < 8; k++) CHECK_EQ(got[k], c.want[k]);
+        for (int k = 0; k < 7; k++) arrays.push_back({got[k], c.bytes[k]});
+        check_block(arrays, l.total);
+    }
+    // the loss: max_rows 5; one workgroup's record (PLOSS_REC = 10 float64) at these sizes
+    const size_t B = 5, REC = 10;
+    struct LossCase {
+        bool cat;
+        int n;
+        size_t want[18];  // logp, entropy, ratio, pg, vl, d_params, d_log_std, d_log_std_shared, d_values, stats, n_bad, inv_w,
+                          // row_m, row_log_s, row_gu, row_w, rec, total
+        size_t bytes[17];
+    };
+    const LossCase loss[2] = {
+        {true, 11,
+         {0, 256, 512, 768, 1024, 1280, 1536, 1536, 1536, 1792, 2048, 2304, 2560, 2816, 3072, 3328, 3584, 3840},
+         {20, 20, 20, 20, 20, 220, 0, 0, 20, 32, 4, 4, 20, 20, 20, 20, 80}},
+        {false, 2,
+         {0, 256, 512, 768, 1024, 1280, 1536, 1792, 2048, 2304, 2560, 2816, 3072, 3072, 3072, 3328, 3584, 3840},
+         {20, 20, 20, 20, 20, 40, 40, 8, 20, 32, 4, 4, 0, 0, 20, 20, 80}},
+    };
+    for (const LossCase& c : loss) {
+        const size_t n_rec = plan_policy_loss_launch((int)B, c.cat ? c.n : 0).grid;
+        CHECK_EQ(n_rec, 1);
+        const PolicyLossLayout l = plan_policy_loss_layout(c.cat, B, (size_t)c.n, n_rec, REC);
+        const size_t got[18] = {l.logp, l.entropy, l.ratio, l.pg, l.vl, l.d_params, l.d_log_std, l.d_log_std_shared, l.d_values, l.stats, l.n_bad, l.inv_w,
+                                l.row_m, l.row_log_s, l.row_gu, l.row_w, l.rec, l.total};
+        std::vector<std::pair<size_t, size_t>> arrays;
+        for (int k = 0; k < 18; k++) CHECK_EQ(got[k], c.want[k]);
+        for (int k = 0; k < 17; k++) arrays.push_back({got[k], c.bytes[k]});
+        check_block(arrays, l.total);
+    }
+}
+
 int main() {
     check_walk();
     check_catalogue();
     check_layouts();
+    check_policy_layouts();
     if (g_fail) {
         printf("%d of %d checks failed\n", g_fail, g_checks);
         return 1;

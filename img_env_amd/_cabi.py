@@ -381,7 +381,10 @@ ROLLOUT_BITS = {"sensor_maps": 1, "vector_states": 2, "lasers": 4, "ped_vector_s
 ROLLOUT_ALL = 127
 #: after imgenv_normalise_enable only, not part of ROLLOUT_ALL: the normalised state (and its stack) as fields; the normalised reward as ``rewards``
 ROLLOUT_NORM_STATES, ROLLOUT_NORM_REWARDS = 128, 256
-_ROLLOUT_NAMES = dict(ROLLOUT_BITS, norm_states=ROLLOUT_NORM_STATES, norm_rewards=ROLLOUT_NORM_REWARDS)
+#: not part of ROLLOUT_ALL either (and no name of ROLLOUT_BITS: it excludes ``ped_maps``): the ring keeps no ped_maps, the minibatches
+#: draw ``mb_ped_maps`` from the stored ``ped_vector_states`` (imgenv_ped_maps_draw; csrc/ped_draw.h)
+ROLLOUT_PED_MAPS_DRAWN = 512
+_ROLLOUT_NAMES = dict(ROLLOUT_BITS, norm_states=ROLLOUT_NORM_STATES, norm_rewards=ROLLOUT_NORM_REWARDS, ped_maps_drawn=ROLLOUT_PED_MAPS_DRAWN)
 #: the stored observation fields, in the order of imgenv_rollout_out's obs_* and final_* pointers
 ROLLOUT_FIELDS = ("sensor_maps", "vector_states", "lasers", "ped_vector_states", "ped_maps", "ped_vector_norm",
                   "stack_sensor_maps", "stack_vector_states", "stack_lasers")
@@ -391,6 +394,7 @@ ROLLOUT_NORM_FIELDS = ("norm_vector_states", "norm_state_stack")
 ROLLOUT_SCALARS = ("actions", "rewards", "dones", "is_clean", "dones_info", "final_idx", "final_slot", "final_row", "final_n")
 ROLLOUT_HEADER = ("struct_size", "n_local", "horizon", "final_capacity", "n", "resets")
 ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS, GAE_BLOCK, GAE_MAX_BLOCKS = 256, 1024, 64, 1024  # the launch shapes (csrc/launch_plan.h)
+PED_DRAW_BLOCK, PED_DRAW_MAX_BLOCKS, PED_DRAW_LDS_BYTES = 256, 2048, 65536            # k_ped_draw's (csrc/ped_draw.h)
 
 
 class RolloutCfg(C.Structure):
@@ -403,7 +407,8 @@ class RolloutOut(C.Structure):
 
 
 def make_rollout_cfg(horizon, final_capacity, fields):
-    """``imgenv_rollout_cfg``: ``fields`` is an int of IMGENV_ROLLOUT_* bits or an iterable of ``ROLLOUT_BITS`` names"""
+    """``imgenv_rollout_cfg``: ``fields`` is an int of IMGENV_ROLLOUT_* bits or an iterable of names: ``ROLLOUT_BITS``', ``"norm_states"``,
+    ``"norm_rewards"``, ``"ped_maps_drawn"``"""
     c = RolloutCfg()
     c.struct_size = C.sizeof(RolloutCfg)
     c.horizon, c.final_capacity = int(horizon), int(final_capacity)
@@ -413,7 +418,7 @@ def make_rollout_cfg(horizon, final_capacity, fields):
         names = list(fields)
         unknown = [n for n in names if n not in _ROLLOUT_NAMES]
         if unknown:
-            raise ValueError("rollout fields: unknown %s (known: %s)" % (unknown, ", ".join(ROLLOUT_BITS)))
+            raise ValueError("rollout fields: unknown %s (known: %s)" % (unknown, ", ".join(_ROLLOUT_NAMES)))
         c.fields = sum({_ROLLOUT_NAMES[n] for n in names})
     return c
 
@@ -448,7 +453,7 @@ class MinibatchArgs(C.Structure):
 
 def make_minibatch_cfg(batch, buffers=1, fields=0):
     """``imgenv_minibatch_cfg``: ``fields`` is an int of IMGENV_ROLLOUT_* bits (0: every field the rollout stores) or an iterable
-    of ``ROLLOUT_BITS`` names"""
+    of the names ``make_rollout_cfg`` takes"""
     c = MinibatchCfg()
     c.struct_size = C.sizeof(MinibatchCfg)
     c.batch, c.buffers = int(batch), int(buffers)
@@ -460,7 +465,7 @@ def make_minibatch_cfg(batch, buffers=1, fields=0):
         names = list(fields)
         unknown = [n for n in names if n not in _ROLLOUT_NAMES]
         if unknown:
-            raise ValueError("minibatch fields: unknown %s (known: %s)" % (unknown, ", ".join(ROLLOUT_BITS)))
+            raise ValueError("minibatch fields: unknown %s (known: %s)" % (unknown, ", ".join(_ROLLOUT_NAMES)))
         c.fields = sum({_ROLLOUT_NAMES[n] for n in names})
     return c
 
@@ -682,7 +687,7 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_policy_enable", "imgenv_policy_outputs", "imgenv_policy_sample",
            "imgenv_policy_loss_enable", "imgenv_policy_loss_outputs", "imgenv_policy_loss",
            "imgenv_final_obs_enable", "imgenv_final_obs_outputs",
-           "imgenv_rollout_enable", "imgenv_rollout_outputs", "imgenv_rollout_begin", "imgenv_rollout_gae",
+           "imgenv_rollout_enable", "imgenv_rollout_outputs", "imgenv_rollout_begin", "imgenv_rollout_gae", "imgenv_ped_maps_draw",
            "imgenv_rollout_minibatch_enable", "imgenv_rollout_minibatch_outputs", "imgenv_rollout_index", "imgenv_rollout_stats",
            "imgenv_rollout_shuffle", "imgenv_rollout_minibatch",
            "imgenv_normalise_enable", "imgenv_normalise_outputs", "imgenv_normalise_training", "imgenv_normalise_stats_get",
@@ -765,6 +770,7 @@ def bind(lib):
     lib.imgenv_rollout_outputs.argtypes = [C.c_void_p, C.POINTER(RolloutOut)]
     lib.imgenv_rollout_begin.argtypes = [C.c_void_p, C.c_void_p]
     lib.imgenv_rollout_gae.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.imgenv_ped_maps_draw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.imgenv_rollout_minibatch_enable.argtypes = [C.c_void_p, C.POINTER(MinibatchCfg), C.POINTER(MinibatchOut)]
     lib.imgenv_rollout_minibatch_outputs.argtypes = [C.c_void_p, C.POINTER(MinibatchOut)]
     lib.imgenv_rollout_index.argtypes = [C.c_void_p, C.c_void_p]

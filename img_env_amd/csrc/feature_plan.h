@@ -53,6 +53,7 @@ struct FeatureFacts {
     int roll_horizon = 0, roll_fields = 0;
     bool mb_on = false;
     bool norm_on = false, norm_obs = false, norm_rew = false;  // the arrays of IMGENV_NORM_OBS / IMGENV_NORM_REWARD exist
+    int ped_h = 0, ped_w = 0;    // imgenv_cfg.ped_image_size (IMGENV_ROLLOUT_PED_MAPS_DRAWN: the map must fit k_ped_draw's rank plane)
 };
 
 // the cfg and the caller's out struct of an enable call, before the handle is looked at.  An out struct says 0 or this library's size.
@@ -243,11 +244,14 @@ struct FieldFeatureNames {
 };
 inline FieldFeatureNames field_feature(FieldFeature which) {
     static const int n_final = (int)(sizeof(FINAL_FIELD_ORDER) / sizeof(int)), n_roll = (int)(sizeof(ROLLOUT_FIELD_ORDER) / sizeof(int));
+    static const int n_mb = (int)(sizeof(MINIBATCH_FIELD_ORDER) / sizeof(int));
     static_assert(sizeof(FINAL_FIELD_ORDER) / sizeof(int) <= FINAL_MAX_FIELDS && sizeof(ROLLOUT_FIELD_ORDER) / sizeof(int) <= ROLLOUT_TABLE_FIELDS, "field tables");
+    // (the minibatches' order lists the stored and the drawn ped_maps: one more than a selection can hold, select_feature_fields checks)
+    static_assert(sizeof(MINIBATCH_FIELD_ORDER) / sizeof(int) <= FINAL_MAX_FIELDS, "field tables");
     switch (which) {
         case FIELDS_FINAL: return {"imgenv_final_obs_cfg", "IMGENV_FINAL", FINAL_FIELD_ORDER, n_final};
         case FIELDS_ROLLOUT: return {"imgenv_rollout_cfg", "IMGENV_ROLLOUT", ROLLOUT_FIELD_ORDER, n_roll};
-        default: return {"imgenv_minibatch_cfg", "IMGENV_ROLLOUT", ROLLOUT_FIELD_ORDER, n_roll};
+        default: return {"imgenv_minibatch_cfg", "IMGENV_ROLLOUT", MINIBATCH_FIELD_ORDER, n_mb};
     }
 }
 inline int field_bit(FieldFeature which, int id) { return which == FIELDS_FINAL ? OBS_SLOTS[id].final_bit : OBS_SLOTS[id].rollout_bit; }
@@ -274,19 +278,24 @@ struct FieldSelection {
 };
 // The fields of `which`'s order whose bit is in `want`, out of the catalogue `cat` (the handle's arrays; for the minibatches what
 // the ring keeps).  An optional field the catalogue lacks is skipped silently, any other without an array or of no bytes refused.
-// `cfg_fields`: the cfg's own word, for the texts.
-inline int select_feature_fields(FieldFeature which, const ObsField (&cat)[OBSF_COUNT], int want, int cfg_fields, FieldSelection& s, FeatureMsg msg) {
+// `cfg_fields`: the cfg's own word, for the texts.  `drawn_row_bytes`: the row of a drawn field (the minibatches': ped_maps_row_bytes).
+inline size_t ped_maps_row_bytes(const FeatureFacts& f) { return 3 * (size_t)(f.ped_h > 0 ? f.ped_h : 0) * (size_t)(f.ped_w > 0 ? f.ped_w : 0) * 4; }
+inline int select_feature_fields(FieldFeature which, const ObsField (&cat)[OBSF_COUNT], int want, int cfg_fields, FieldSelection& s, FeatureMsg msg,
+                                 size_t drawn_row_bytes = 0) {
     struct Pick { int bit, id; } list[FINAL_MAX_FIELDS];
     const Pick* sel[FINAL_MAX_FIELDS];
     const FieldFeatureNames n = field_feature(which);
     for (int k = 0; k < n.n_order; k++) list[k] = {field_bit(which, n.order[k]), n.order[k]};
     int bad_bit = 0;
-    s.n = obs_fields_select_n(cat, list, n.n_order, want, sel, &bad_bit);
+    ObsField ext[OBSF_SLOT_COUNT];
+    obs_fields_with_drawn(cat, drawn_row_bytes, ext);
+    s.n = obs_fields_select_n(ext, list, n.n_order, want, sel, &bad_bit);
     if (s.n < 0) FEATURE_REFUSE(IMGENV_EINVAL, "%s.fields: bit %d names a field of no bytes on this handle", n.cfg, bad_bit);
     for (int k = 0; k < s.n; k++) {
         s.id[k] = sel[k]->id;
-        s.row_bytes[k] = cat[s.id[k]].row_bytes;
+        s.row_bytes[k] = ext[s.id[k]].row_bytes;
     }
+    if (which != FIELDS_FINAL && s.n > ROLLOUT_TABLE_FIELDS) FEATURE_REFUSE(IMGENV_EINVAL, "%s.fields %d: more fields than a table holds", n.cfg, cfg_fields);
     if (which == FIELDS_MINIBATCH && s.n == 0) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: no field of the rollout", cfg_fields);
     return IMGENV_OK;
 }
@@ -317,8 +326,14 @@ inline int rollout_enable_plan(const imgenv_rollout_cfg* c, const imgenv_rollout
     FEATURE_TRY(enable_args(c, "imgenv_rollout_cfg", out, "imgenv_rollout_out", msg));
     if (c->horizon < 1) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_rollout_cfg.horizon %d: at least 1", c->horizon);
     if (c->final_capacity < 1) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_rollout_cfg.final_capacity %d: at least 1", c->final_capacity);
-    const int norm_bits = IMGENV_ROLLOUT_NORM_STATES | IMGENV_ROLLOUT_NORM_REWARDS;
-    if (c->fields == 0 || (c->fields & ~(IMGENV_ROLLOUT_ALL | norm_bits))) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d", c->fields);
+    const int norm_bits = IMGENV_ROLLOUT_NORM_STATES | IMGENV_ROLLOUT_NORM_REWARDS, drawn = IMGENV_ROLLOUT_PED_MAPS_DRAWN;
+    if (c->fields == 0 || (c->fields & ~(IMGENV_ROLLOUT_ALL | norm_bits | drawn))) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d", c->fields);
+    // the drawn ped_maps: the ring keeps the vector they are drawn from, and not the maps themselves
+    if (c->fields == drawn) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d", c->fields);  // (the bit alone stores nothing: the text of a word without a field)
+    if ((c->fields & drawn) && !(c->fields & IMGENV_ROLLOUT_PED_VECTOR_STATES))
+        FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d: IMGENV_ROLLOUT_PED_MAPS_DRAWN needs IMGENV_ROLLOUT_PED_VECTOR_STATES", c->fields);
+    if ((c->fields & drawn) && (c->fields & IMGENV_ROLLOUT_PED_MAPS))
+        FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d: IMGENV_ROLLOUT_PED_MAPS_DRAWN excludes IMGENV_ROLLOUT_PED_MAPS", c->fields);
     if (c->fields & norm_bits) {
         if (!(f && f->norm_on)) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d: IMGENV_ROLLOUT_NORM_* before imgenv_normalise_enable", c->fields);
         if ((c->fields & IMGENV_ROLLOUT_NORM_STATES) && !f->norm_obs)
@@ -336,6 +351,9 @@ inline int rollout_enable_plan(const imgenv_rollout_cfg* c, const imgenv_rollout
     }
     if (((size_t)c->horizon + 1) * (size_t)f->RL > 0x7fffffffu)
         FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_rollout_cfg.horizon %d: (horizon + 1) x %d robots is beyond 2^31 - 1", c->horizon, f->RL);
+    if ((c->fields & drawn) && !plan_ped_draw_fits(f->ped_h, f->ped_w))
+        FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_rollout_cfg.fields %d: IMGENV_ROLLOUT_PED_MAPS_DRAWN with pedestrian maps of %d x %d cells (a plane of %d bytes at most)",
+                       c->fields, f->ped_h, f->ped_w, PED_DRAW_LDS_BYTES);
     return field_bits_refusals(FIELDS_ROLLOUT, *f, c->fields, msg);
 }
 
@@ -349,7 +367,7 @@ inline int minibatch_enable_plan(const imgenv_minibatch_cfg* c, const imgenv_min
     FEATURE_TRY(enable_args(c, "imgenv_minibatch_cfg", out, "imgenv_minibatch_out", msg));
     if (c->batch < 1) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_minibatch_cfg.batch %d: at least 1", c->batch);
     if (c->buffers < 1 || c->buffers > IMGENV_MB_MAX_BUFFERS) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_minibatch_cfg.buffers %d: 1 .. %d", c->buffers, IMGENV_MB_MAX_BUFFERS);
-    if (c->fields & ~(IMGENV_ROLLOUT_ALL | IMGENV_ROLLOUT_NORM_STATES)) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d", c->fields);  // (NORM_REWARDS names no field)
+    if (c->fields & ~(IMGENV_ROLLOUT_ALL | IMGENV_ROLLOUT_NORM_STATES | IMGENV_ROLLOUT_PED_MAPS_DRAWN)) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d", c->fields);  // (NORM_REWARDS names no field)
     if ((c->fields & IMGENV_ROLLOUT_NORM_STATES) && !(f && f->norm_on))
         FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: IMGENV_ROLLOUT_NORM_* before imgenv_normalise_enable", c->fields);
     FEATURE_TRY(enable_null_handle(f, msg));

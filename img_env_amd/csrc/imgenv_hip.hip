@@ -37,6 +37,7 @@
 #include "final_obs.h"
 #include "rollout.h"
 #include "minibatch.h"
+#include "ped_draw.h"
 #include "map_bank.h"
 #include "spawn_slot.h"
 #include "bank_host.h"
@@ -305,6 +306,8 @@ struct imgenv {
         uint64_t gen_seq = 0;        // imgenv_rollout_index / never / step.chain_seq then: any chain or window since makes the index stale
         bool shuffled = false;       // imgenv_rollout_shuffle / imgenv_rollout_index / `order` is a permutation of that index
         unsigned char* dst[IMGENV_MB_MAX_BUFFERS][ROLLOUT_TABLE_FIELDS];  // imgenv_rollout_minibatch_enable / never / where buffer b keeps entry k of dev.f, the normalised fields included
+        PedDrawDev draw = {};        // imgenv_rollout_minibatch_enable / never / IMGENV_ROLLOUT_PED_MAPS_DRAWN is selected (draw.vec != nullptr): k_ped_draw's arguments but for the call's buffer and minibatch
+        float* draw_dst[IMGENV_MB_MAX_BUFFERS] = {};  // imgenv_rollout_minibatch_enable / never / buffer b's mb_ped_maps where they are drawn
     } mb;
     // running normalisation (csrc/normalise.h); dev.n_obs as enabled: n_ret, cols, update, the turns and the rows are the launch's
     struct Normalise : Feature<NormDev, imgenv_normalise_cfg, imgenv_normalise_out> {
@@ -3526,6 +3529,7 @@ static const FeatureFacts* feature_facts(const imgenv* h, FeatureFacts& f) {
     f.roll_on = h->roll.on; f.roll_horizon = h->roll.cfg.horizon; f.roll_fields = h->roll.cfg.fields;
     f.mb_on = h->mb.on;
     f.norm_on = h->norm.on; f.norm_obs = h->norm.dev.norm_vector_states != nullptr; f.norm_rew = h->norm.dev.norm_rewards != nullptr;
+    f.ped_h = h->cfg.ped_image_size[0]; f.ped_w = h->cfg.ped_image_size[1];
     return &f;
 }
 // what the plan decided, handed on: a refusal with its text; IMGENV_OK or ENABLE_REPEAT otherwise
@@ -4448,6 +4452,23 @@ extern "C" int imgenv_rollout_gae(imgenv_t* h, const float* values, const float*
     return IMGENV_OK;
 }
 
+// k_ped_draw's arguments for `n` maps of this handle's geometry drawn from rows of `vec` (ped_draw.h); `out` may come later
+static PedDrawDev ped_draw_args(const imgenv* h, const float* vec, const int32_t* rows, uint32_t n, float* out) {
+    PedDrawDev d = {};
+    d.vec = vec;
+    d.rows = rows;
+    d.out = out;
+    d.n = n;
+    d.PV = h->d.PV; d.Hp = h->d.Hp; d.Wp = h->d.Wp;
+    d.res = h->d.ped_res; d.inv_res = h->d.ped_inv_res; d.r = h->d.ped_image_r; d.r2 = h->d.ped_image_r2;
+    return d;
+}
+static void launch_ped_draw(PedDrawDev d, hipStream_t st) {
+    d.wide = ((size_t)d.Hp * (size_t)d.Wp) % 4 == 0 && ((uintptr_t)d.out & 15) == 0;
+    const LaunchShape s = plan_ped_draw_launch(d.n, d.Hp, d.Wp);
+    k_ped_draw<<<dim3(s.grid), dim3(s.block), s.lds, st>>>(d);
+}
+
 // ---- rollout minibatches (include/imgenv.h; the kernels are csrc/minibatch.h) ----
 extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibatch_cfg* c, imgenv_minibatch_out* out) {
     FeatureMsg msg;
@@ -4460,7 +4481,7 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
     ObsField ring[OBSF_COUNT] = {};
     for (int k = 0; k < h->roll.dev.n_fields; k++) ring[h->roll.field_id[k]] = {h->roll.dev.f[k].ring, h->roll.row_bytes[k]};
     FieldSelection s;
-    RTRY(planned(select_feature_fields(FIELDS_MINIBATCH, ring, want, c->fields, s, msg), msg));
+    RTRY(planned(select_feature_fields(FIELDS_MINIBATCH, ring, want, c->fields, s, msg, ped_maps_row_bytes(facts)), msg));
     // one zeroed block (launch_plan.h); nothing of the handle changes before it is there
     const size_t RL = (size_t)h->RL, T = (size_t)h->roll.cfg.horizon, NB = (size_t)c->buffers;
     const MinibatchLayout l = plan_minibatch_layout(s.row_bytes, s.n, RL, T, (size_t)c->batch, NB);
@@ -4468,14 +4489,22 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
     RTRY(feature_block(h, l.total, "imgenv_rollout_minibatch_enable", &block));
     MbGatherDev g;
     memset(&g, 0, sizeof(g));
-    g.n_fields = s.n;
+    // the gather's table: the selection without the drawn field (entry `of[k]` of the selection), which is k_ped_draw's
+    int of[ROLLOUT_TABLE_FIELDS] = {}, drawn = -1;
     for (int k = 0; k < s.n; k++) {
+        if (s.id[k] == OBSF_PED_MAPS_DRAWN) {
+            drawn = k;
+            continue;
+        }
         const FinalFieldPlan f = plan_final_field(s.row_bytes[k]);  // (the ring's own chunking)
-        g.f[k].ring = (const unsigned char*)ring[s.id[k]].src;
-        g.f[k].unit = f.unit;  // (dst: the buffer's, h->mb.dst, at the call)
-        g.f[k].chunks = f.chunks;
+        MbGatherField& gf = g.f[g.n_fields];
+        gf.ring = (const unsigned char*)ring[s.id[k]].src;
+        gf.unit = f.unit;  // (dst: the buffer's, h->mb.dst, at the call)
+        gf.chunks = f.chunks;
         g.chunks_per_row += f.chunks;
+        of[g.n_fields++] = k;
     }
+    if (g.n_fields == 0) g.chunks_per_row = 1;  // (nothing to copy: the one chunk per slot is the scalars' lane)
     imgenv_minibatch_out o = {};
     o.horizon = h->roll.cfg.horizon;
     o.batch = c->batch;
@@ -4491,11 +4520,9 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
     o.stat_mean = (double*)(block + l.stat_mean);
     for (size_t b = 0; b < NB; b++) {
         imgenv_minibatch_buffer& m = o.buf[b];
-        for (int k = 0; k < s.n; k++) {
-            const ObsSlot& slot = OBS_SLOTS[s.id[k]];
-            h->mb.dst[b][k] = block + l.field[b][k];
-            obs_slot_put_mb(slot, &m, &h->norm.out, (int)b, h->mb.dst[b][k]);
-        }
+        for (int k = 0; k < s.n; k++) obs_slot_put_mb(OBS_SLOTS[s.id[k]], &m, &h->norm.out, (int)b, block + l.field[b][k]);
+        for (int k = 0; k < g.n_fields; k++) h->mb.dst[b][k] = block + l.field[b][of[k]];
+        if (drawn >= 0) h->mb.draw_dst[b] = (float*)(block + l.field[b][drawn]);
         m.mb_actions = (float*)(block + l.scalar[b][MB_S_ACTIONS]);
         m.mb_rewards = (float*)(block + l.scalar[b][MB_S_REWARDS]);
         m.mb_dones = block + l.scalar[b][MB_S_DONES];
@@ -4511,6 +4538,12 @@ extern "C" int imgenv_rollout_minibatch_enable(imgenv_t* h, const imgenv_minibat
     g.rewards = h->roll.dev.rewards;
     g.dones = h->roll.dev.dones;
     g.dones_info = h->roll.dev.dones_info;
+    h->mb.draw = {};
+    if (drawn >= 0) {
+        h->mb.draw = ped_draw_args(h, (const float*)ring[OBS_SLOTS[OBSF_PED_MAPS_DRAWN].from].src, nullptr, g.B, nullptr);
+        h->mb.draw.order = o.order;
+        h->mb.draw.TR = g.TR;
+    }
     h->mb.dev = g;
     h->mb.cfg = *c;
     h->mb.indexed = h->mb.shuffled = false;
@@ -4614,6 +4647,26 @@ extern "C" int imgenv_rollout_minibatch(imgenv_t* h, const imgenv_minibatch_args
     g.norm = a->norm ? a->norm : h->mb.out.norm;
     const LaunchShape s = plan_mb_gather_launch(g.B, g.chunks_per_row);
     k_rollout_gather<<<dim3(s.grid), dim3(s.block), 0, (hipStream_t)stream>>>(g);
+    if (h->mb.draw.vec) {  // IMGENV_ROLLOUT_PED_MAPS_DRAWN: mb_ped_maps of the same slots, one more launch
+        PedDrawDev d = h->mb.draw;
+        d.out = h->mb.draw_dst[a->buffer];
+        d.first = g.first;
+        launch_ped_draw(d, (hipStream_t)stream);
+    }
+    HIPCHK(hipGetLastError());
+    return IMGENV_OK;
+}
+
+// ---- pedestrian maps drawn from pedestrian vectors (include/imgenv.h; the kernel is csrc/ped_draw.h) ----
+extern "C" int imgenv_ped_maps_draw(imgenv_t* h, const float* ped_vectors, const int32_t* rows, int64_t n, float* out, void* stream) {
+    if (!h || !ped_vectors || !out) FAIL(IMGENV_EINVAL, "null argument");
+    if (n < 0 || n > 0x7fffffff) FAIL(IMGENV_EINVAL, "imgenv_ped_maps_draw: n %lld", (long long)n);
+    if (h->P <= 0 || h->out.ped_vec_len <= 0) FAIL(IMGENV_EINVAL, "imgenv_ped_maps_draw on a handle without pedestrians");
+    if (!plan_ped_draw_fits(h->d.Hp, h->d.Wp))
+        FAIL(IMGENV_EINVAL, "imgenv_ped_maps_draw: pedestrian maps of %d x %d cells (a plane of %d bytes at most)", h->d.Hp, h->d.Wp, PED_DRAW_LDS_BYTES);
+    if (n == 0) return IMGENV_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    launch_ped_draw(ped_draw_args(h, ped_vectors, rows, (uint32_t)n, out), (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return IMGENV_OK;
 }

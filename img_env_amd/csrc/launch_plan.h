@@ -54,6 +54,9 @@
 #define MB_STATS_TILE (MB_STATS_BLOCK * MB_STATS_PER_LANE)
 #define MB_SHUFFLE_BLOCK 256 // k_mb_shuffle: one lane per position of `order`
 #define MB_ROUNDS 6          // Feistel rounds of the shuffle's permutation
+#define PED_DRAW_BLOCK 256       // k_ped_draw (ped_draw.h): one workgroup per drawn map, four wavefronts
+#define PED_DRAW_MAX_BLOCKS 2048 // eight workgroups per CU of 256; the kernel strides over further rows
+#define PED_DRAW_LDS_BYTES 65536 // the rank plane, a word per cell: 128 x 128 cells at most (96 x 96 takes 36 864 bytes)
 #define NORM_BLOCK 256       // k_norm_part / k_norm_apply (normalise.h): four wavefronts, a lane per (row, column)
 #define NORM_PER_LANE 8      // k_norm_part: the rows of a tile whose samples a lane holds in registers
 #define NORM_MAX_COLS 64     // state_dim + 1 (the return) columns at most: the columns of a row lie in one wavefront
@@ -673,6 +676,16 @@ inline LaunchShape plan_mb_shuffle_launch(size_t positions) {
 }
 inline LaunchShape plan_mb_gather_launch(size_t batch, uint32_t chunks_per_row) {
     return plan_tail(batch * chunks_per_row, ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS);
+}
+
+// ---------------------------------------------------------------------------------------- anywhere: k_ped_draw
+// ped_draw.h: one workgroup per map, capped -- the kernel strides -- with the map's rank plane, a word per cell, as dynamic LDS.  A
+// pedestrian map whose plane is beyond PED_DRAW_LDS_BYTES cannot be drawn: imgenv_ped_maps_draw and IMGENV_ROLLOUT_PED_MAPS_DRAWN
+// refuse it.
+inline size_t plan_ped_draw_lds(int Hp, int Wp) { return (size_t)std::max(Hp, 0) * (size_t)std::max(Wp, 0) * 4; }
+inline bool plan_ped_draw_fits(int Hp, int Wp) { return Hp >= 1 && Wp >= 1 && plan_ped_draw_lds(Hp, Wp) <= PED_DRAW_LDS_BYTES; }
+inline LaunchShape plan_ped_draw_launch(size_t rows, int Hp, int Wp) {
+    return {(unsigned)std::min<size_t>(PED_DRAW_MAX_BLOCKS, std::max<size_t>(1, rows)), PED_DRAW_BLOCK, plan_ped_draw_lds(Hp, Wp)};
 }
 
 // ---------------------------------------------------------------------------------------- chain tail: k_norm_part, k_norm_apply

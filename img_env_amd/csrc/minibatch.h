@@ -266,6 +266,7 @@ TAIL_HD void mb_gather_item(const MbGatherDev& g, size_t t) {
         g.mb_weight[i] = k >= 0 ? 1.0f : 0.0f;
         mb_gather_scalars<0>(g, k, i);
     }
+    if (g.n_fields == 0) return;  // (every selected field is drawn, ped_draw.h: chunks_per_row is 1, the scalars' lane)
     const MbGatherField f = field_walk(g.f, g.n_fields, c);
     field_dispatch(f.unit, [&](auto chunk) { mb_gather_chunk<typename decltype(chunk)::type>(f.ring, f.dst, f.chunks, k, i, c); });
 }

@@ -19,7 +19,11 @@ enum ObsFieldId {
     OBSF_PED_VECTOR_NORM,                                                 // imgenv_obs_post_enable
     OBSF_NORM_VECTOR_STATES, OBSF_NORM_STATE_STACK,                       // imgenv_normalise_enable
     OBSF_COUNT,
-    OBSF_FIRST_OPTIONAL = OBSF_STACK_SENSOR_MAPS
+    OBSF_FIRST_OPTIONAL = OBSF_STACK_SENSOR_MAPS,
+    // behind the fields a handle has arrays of (an ObsField catalogue has OBSF_COUNT entries), the slots no array stands behind:
+    // ped_maps drawn from the ring's ped_vector_states (ped_draw.h) -- a minibatch field only
+    OBSF_PED_MAPS_DRAWN = OBSF_COUNT,
+    OBSF_SLOT_COUNT
 };
 
 struct ObsFacts {
@@ -69,22 +73,27 @@ inline void obs_fields(const ObsFacts& a, ObsField (&f)[OBSF_COUNT]) {
 // has no such field), and where each feature hands the copy's pointer out, as a byte offset into imgenv_final_obs_out,
 // imgenv_rollout_out (ring and final list) and imgenv_minibatch_buffer.  `norm`: the field is normalise.h's, and every one of its
 // slots is a member of imgenv_normalise_out instead (those structs keep their layout); its minibatch slot is entry 0 of an array
-// with one entry per buffer.
+// with one entry per buffer.  A drawn field (the ids from OBSF_COUNT on) has a minibatch slot alone: no feature stores it, the
+// minibatches draw it from the ring of field `from` into the buffer member of the field it stands for; how long its row is the
+// caller says (obs_fields_with_drawn).
 #define OBS_NO_SLOT ((size_t)-1)
 struct ObsSlot {
     int final_bit, rollout_bit;
     size_t final_out, ring_out, fin_out, mb_out;
     bool norm;
+    int from;  // a drawn field's source field; -1 for every other
 };
-#define OBS_SLOT_FINAL_ONLY(bit, member) {bit, 0, offsetof(imgenv_final_obs_out, member), OBS_NO_SLOT, OBS_NO_SLOT, OBS_NO_SLOT, false}
+#define OBS_SLOT_FINAL_ONLY(bit, member) {bit, 0, offsetof(imgenv_final_obs_out, member), OBS_NO_SLOT, OBS_NO_SLOT, OBS_NO_SLOT, false, -1}
+#define OBS_SLOT_DRAWN(rbit, member, from_id) \
+    {0, rbit, OBS_NO_SLOT, OBS_NO_SLOT, OBS_NO_SLOT, offsetof(imgenv_minibatch_buffer, mb_##member), false, from_id}
 #define OBS_SLOT_ALL(fbit, rbit, member)                                                                                       \
     {fbit, rbit, offsetof(imgenv_final_obs_out, member), offsetof(imgenv_rollout_out, obs_##member),                           \
-     offsetof(imgenv_rollout_out, final_##member), offsetof(imgenv_minibatch_buffer, mb_##member), false}
+     offsetof(imgenv_rollout_out, final_##member), offsetof(imgenv_minibatch_buffer, mb_##member), false, -1}
 #define OBS_SLOT_NORM(member)                                                                                                  \
     {IMGENV_FINAL_NORM_STATES, IMGENV_ROLLOUT_NORM_STATES, offsetof(imgenv_normalise_out, final_##member),                     \
      offsetof(imgenv_normalise_out, rollout_obs_##member), offsetof(imgenv_normalise_out, rollout_final_##member),             \
-     offsetof(imgenv_normalise_out, mb_##member), true}
-static const ObsSlot OBS_SLOTS[OBSF_COUNT] = {
+     offsetof(imgenv_normalise_out, mb_##member), true, -1}
+static const ObsSlot OBS_SLOTS[OBSF_SLOT_COUNT] = {
     OBS_SLOT_ALL(IMGENV_FINAL_VECTOR_STATES, IMGENV_ROLLOUT_VECTOR_STATES, vector_states),
     OBS_SLOT_ALL(IMGENV_FINAL_SENSOR_MAPS, IMGENV_ROLLOUT_SENSOR_MAPS, sensor_maps),
     OBS_SLOT_ALL(IMGENV_FINAL_LASERS, IMGENV_ROLLOUT_LASERS, lasers),
@@ -102,15 +111,21 @@ static const ObsSlot OBS_SLOTS[OBSF_COUNT] = {
     OBS_SLOT_ALL(IMGENV_FINAL_PED_NORM, IMGENV_ROLLOUT_PED_NORM, ped_vector_norm),
     OBS_SLOT_NORM(norm_vector_states),
     OBS_SLOT_NORM(norm_state_stack),
+    OBS_SLOT_DRAWN(IMGENV_ROLLOUT_PED_MAPS_DRAWN, ped_maps, OBSF_PED_VECTOR_STATES),
 };
 // A feature keeps only the order of its block.  The final observations: the enum's.  The rollout and the minibatches: sensor_maps
 // in front of vector_states, ped_vector_norm in front of the stacks (the order of the blocks already handed out: it must not change).
+// The minibatches: the rollout's, with the drawn ped_maps where the stored ones stand (the rollout excludes one of the two, so a
+// selection still has ROLLOUT_TABLE_FIELDS entries at most).
 static const int FINAL_FIELD_ORDER[] = {
     OBSF_VECTOR_STATES, OBSF_SENSOR_MAPS, OBSF_LASERS, OBSF_PED_VECTOR_STATES, OBSF_PED_MAPS, OBSF_IS_COLLISIONS, OBSF_IS_ARRIVES,
     OBSF_STEP_DS, OBSF_PED_MIN_DISTS, OBSF_VIEW_MAPS, OBSF_LASERS_RAW, OBSF_STACK_SENSOR_MAPS, OBSF_STACK_VECTOR_STATES,
     OBSF_STACK_LASERS, OBSF_PED_VECTOR_NORM, OBSF_NORM_VECTOR_STATES, OBSF_NORM_STATE_STACK};
 static const int ROLLOUT_FIELD_ORDER[] = {
     OBSF_SENSOR_MAPS, OBSF_VECTOR_STATES, OBSF_LASERS, OBSF_PED_VECTOR_STATES, OBSF_PED_MAPS, OBSF_PED_VECTOR_NORM,
+    OBSF_STACK_SENSOR_MAPS, OBSF_STACK_VECTOR_STATES, OBSF_STACK_LASERS, OBSF_NORM_VECTOR_STATES, OBSF_NORM_STATE_STACK};
+static const int MINIBATCH_FIELD_ORDER[] = {
+    OBSF_SENSOR_MAPS, OBSF_VECTOR_STATES, OBSF_LASERS, OBSF_PED_VECTOR_STATES, OBSF_PED_MAPS, OBSF_PED_MAPS_DRAWN, OBSF_PED_VECTOR_NORM,
     OBSF_STACK_SENSOR_MAPS, OBSF_STACK_VECTOR_STATES, OBSF_STACK_LASERS, OBSF_NORM_VECTOR_STATES, OBSF_NORM_STATE_STACK};
 // the pointer a slot receives: member `off` (the slot's final_out, ring_out or fin_out) of `own`, the feature's out struct -- of
 // `norm_out` for a normalised field
@@ -122,11 +137,21 @@ inline void obs_slot_put_mb(const ObsSlot& s, imgenv_minibatch_buffer* buf, imge
     obs_slot_put(s, s.mb_out + (s.norm ? (size_t)b * sizeof(void*) : 0), buf, norm_out, p);
 }
 
+// a catalogue with the drawn fields behind it: a drawn field is there where its source is, with a row of `drawn_row_bytes` (the one
+// drawn field there is: a pedestrian map, feature_plan.h's ped_maps_row_bytes)
+inline void obs_fields_with_drawn(const ObsField (&f)[OBSF_COUNT], size_t drawn_row_bytes, ObsField (&ext)[OBSF_SLOT_COUNT]) {
+    for (int k = 0; k < OBSF_COUNT; k++) ext[k] = f[k];
+    for (int k = OBSF_COUNT; k < OBSF_SLOT_COUNT; k++) {
+        const ObsSlot& s = OBS_SLOTS[k];
+        ext[k] = f[s.from].src ? ObsField{f[s.from].src, drawn_row_bytes} : ObsField{nullptr, 0};
+    }
+}
+
 // the entries of `list` (any struct with `bit` and `id`) whose bit is in `want`, in the list's order, into sel[]; their count.
 // An optional field the handle lacks is skipped silently; any other field without an array or of no bytes is refused: -1, and
 // *bad_bit is the bit that named it.
-template <typename L>
-inline int obs_fields_select_n(const ObsField (&f)[OBSF_COUNT], const L* list, int n_list, int want, const L** sel, int* bad_bit) {
+template <typename L, int NF>
+inline int obs_fields_select_n(const ObsField (&f)[NF], const L* list, int n_list, int want, const L** sel, int* bad_bit) {
     int n = 0;
     for (int q = 0; q < n_list; q++) {
         const L& s = list[q];

@@ -67,7 +67,9 @@ class VecImageEnv:
     ``final_obs=True``: ``info`` gains ``final_observation`` (Gym's: the state the restarted envs' last action led to, in the rows
     where ``all_down`` is set; other rows hold older captures) and ``final_count``.
     ``rollout=T``: the trainer's ``[T, n, ...]`` storage and the advantage pass inside the library: ``rollout()``,
-    ``rollout_begin()``, ``rollout_advantages(values, final_values, gamma, lam)``.
+    ``rollout_begin()``, ``rollout_advantages(values, final_values, gamma, lam)``.  ``rollout_draw_ped_maps=True``: the storage
+    keeps no ``ped_maps`` (78 % of a default slot) but the pedestrian vectors they are a function of; the minibatches draw
+    ``mb_ped_maps`` from those, ``rollout_ped_maps(t)`` and ``rollout_final_ped_maps()`` draw a slot and the final list.
     ``minibatch=B`` (with ``rollout=T``): the PPO epoch's minibatches gathered by the library, without a host read:
     ``rollout_minibatches(scalars, seed, normalise)``.
     ``normalise=dict(...)``: running normalisation of ``vector_states`` and of the reward inside the library (VecNormalize): the
@@ -81,11 +83,13 @@ class VecImageEnv:
                  map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3, wrappers=False,
                  ped_tracks=None, tracks_policy="keep", tracks_repeat=1, info_track_sets=False, scenarios=None, scenario_policy="queue",
                  episode_log=0, final_obs=False, rollout=0, rollout_final=None, rollout_fields=None, minibatch=0, minibatch_buffers=1,
-                 normalise=None, policy=None):
+                 normalise=None, policy=None, rollout_draw_ped_maps=False):
         import torch
         from .world import World
         if int(minibatch or 0) > 0 and int(rollout or 0) <= 0:
             raise ValueError("minibatch=B needs rollout=T")
+        if rollout_draw_ped_maps and int(rollout or 0) <= 0:
+            raise ValueError("rollout_draw_ped_maps=True needs rollout=T")
         if policy is not None and not wrappers:
             raise ValueError("policy=dict(seed=s) needs wrappers=True")
         if policy is not None and set(policy) - {"seed", "loss"}:
@@ -276,6 +280,8 @@ class VecImageEnv:
                     fields.append("ped_vector_norm")
                 if self._norm_obs:  # (the normalised state instead of the raw one)
                     fields = [n for n in fields if n != "vector_states"]
+                if rollout_draw_ped_maps:  # the raw vector the maps are drawn from instead of the maps (beside the normalised one, if any)
+                    fields = [n for n in fields if n not in ("ped_maps", "ped_vector_states")] + ["ped_vector_states", "ped_maps_drawn"]
             else:
                 fields = rollout_fields
             if self.normalise is not None:  # the two bits follow the handle's normalisation: the ring holds what ``step`` hands out
@@ -426,6 +432,25 @@ class VecImageEnv:
         if self.policy is not None:  # the policy head's columns of the same window
             out.update({k: t for k, t in self.world.policy.items() if k.startswith("pol_")})
         return out
+
+    def rollout_ped_maps(self, t):
+        """``[n, 3, Hp, Wp]``: the pedestrian maps of slot ``t`` of a storage made with ``rollout_draw_ped_maps=True``, drawn from
+        its ``obs_ped_vector_states[t]`` -- what ``obs_ped_maps[t]`` would hold.  One launch; nothing synchronises."""
+        w = self.world
+        if self.rollout_horizon <= 0 or not w.rollout_draws_ped_maps:
+            raise RuntimeError("VecImageEnv was made without rollout=T, rollout_draw_ped_maps=True")
+        if not 0 <= int(t) <= self.rollout_horizon:
+            raise ValueError("rollout_ped_maps: slot %d of 0 .. %d" % (t, self.rollout_horizon))
+        return w.draw_ped_maps(w.rollout["obs_ped_vector_states"][int(t)])
+
+    def rollout_final_ped_maps(self):
+        """``[rollout_final, 3, Hp, Wp]``: the pedestrian maps of the final list, drawn from ``final_ped_vector_states`` -- what
+        ``final_ped_maps`` would hold; entries from ``final_n`` on are zeros (the list is zeroed memory).  One launch; nothing
+        synchronises."""
+        w = self.world
+        if self.rollout_horizon <= 0 or not w.rollout_draws_ped_maps:
+            raise RuntimeError("VecImageEnv was made without rollout=T, rollout_draw_ped_maps=True")
+        return w.draw_ped_maps(w.rollout["final_ped_vector_states"])
 
     def rollout_begin(self):
         """start the next window: the last slot becomes slot 0 (``imgenv_rollout_begin``)"""

@@ -123,6 +123,7 @@ class World:
         self.obs_post = None  # enable_obs_post()
         self.final_obs = None  # enable_final_obs()
         self.rollout = None  # enable_rollout()
+        self.rollout_draws_ped_maps = False  # ... with "ped_maps_drawn"
         self.minibatch = None  # enable_minibatch()
         self.normalise = None  # enable_normalise()
         if self.n_maps > 1:
@@ -682,11 +683,13 @@ class World:
         the row shapes and dtypes of ``out`` / ``stack`` / ``obs_post``, ``actions`` float32 ``[T, R, 3]``, ``rewards`` float32,
         ``dones`` / ``is_clean`` uint8 and ``dones_info`` int32 ``[T, R]``, ``final_idx`` int32 ``[T + 1, R]``, ``final_slot`` /
         ``final_row`` int32 ``[F]`` and ``final_n`` int32 ``[2]`` (include/imgenv.h has the semantics).  ``fields``: names of
-        ``_cabi.ROLLOUT_BITS``; None = the five single-frame fields (without ``lasers`` on a handle without a laser).  One extra
+        ``_cabi.ROLLOUT_BITS`` (and ``"norm_states"``, ``"norm_rewards"``, ``"ped_maps_drawn"``, below); None = the five single-frame fields (without ``lasers`` on a handle without a laser).  One extra
         launch per chain; nothing synchronises.  Read-only; valid until ``close()``.  ValueError for a refused cfg or a second
         call with another one, RuntimeError for ``"stacks"`` / ``"ped_vector_norm"`` before their own enable call.  After
         ``enable_normalise``: ``"norm_states"`` stores ``norm_vector_states`` (and ``norm_state_stack``) like any field,
-        ``"norm_rewards"`` makes ``rewards`` the normalised ones (ValueError before it)."""
+        ``"norm_rewards"`` makes ``rewards`` the normalised ones (ValueError before it).  ``"ped_maps_drawn"`` (with
+        ``"ped_vector_states"``, without ``"ped_maps"``; ValueError otherwise): the ring keeps no ``obs_ped_maps`` / ``final_ped_maps``,
+        the minibatches draw ``mb_ped_maps`` from the stored vectors, ``draw_ped_maps`` draws any slot."""
         if fields is None:
             fields = [n for n in list(_cabi.ROLLOUT_BITS)[:5] if n != "lasers" or self.cfg.use_laser]
         c = _cabi.make_rollout_cfg(horizon, final_capacity, fields)
@@ -719,6 +722,7 @@ class World:
                     self.rollout[name[len("rollout_"):]] = t
             self.rollout_horizon, self.rollout_final_capacity = T, F
             self._rollout_rows = rows
+            self.rollout_draws_ped_maps = bool(c.fields & _cabi.ROLLOUT_PED_MAPS_DRAWN)
         return self.rollout
 
     def rollout_cursor(self):
@@ -759,14 +763,42 @@ class World:
                                                 C.c_void_p(adv.data_ptr()), C.c_void_p(ret.data_ptr()), self._stream()), "imgenv_rollout_gae")
         return adv, ret
 
+    def draw_ped_maps(self, ped_vectors, rows=None, out=None):
+        """``imgenv_ped_maps_draw``: the pedestrian maps of pedestrian vectors, bit for bit what ``out["ped_maps"]`` showed beside
+        them; one launch on the current stream, nothing synchronises.  ``ped_vectors`` float32 ``[m, ped_vec_len]``; ``rows`` int32
+        ``[n]`` or None: map ``i`` is drawn from row ``rows[i]`` (below 0: all zeros), or from row ``i``; ``out`` float32
+        ``[n, 3, Hp, Wp]`` (made unless given).  All contiguous tensors on the handle's device.  Returns ``out``."""
+        import torch
+        PV, (Hp, Wp) = self._out_header.ped_vec_len, self.cfg.ped_image_size
+
+        def ok(t, dtype, shape):
+            return (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.device and t.is_contiguous() and t.dim() == len(shape)
+                    and all(want is None or got == want for got, want in zip(t.shape, shape)))
+        if not ok(ped_vectors, torch.float32, (None, PV)):
+            raise ValueError("draw_ped_maps: ped_vectors float32 [m, %d], contiguous on %s" % (PV, self.device))
+        if rows is not None and not ok(rows, torch.int32, (None,)):
+            raise ValueError("draw_ped_maps: rows int32 [n] or None, contiguous on %s" % (self.device,))
+        n = int(rows.shape[0] if rows is not None else ped_vectors.shape[0])
+        if out is None:
+            out = torch.empty((n, 3, Hp, Wp), dtype=torch.float32, device=self.device)
+        if not ok(out, torch.float32, (n, 3, Hp, Wp)):
+            raise ValueError("draw_ped_maps: out float32 [%d, 3, %d, %d], contiguous on %s" % (n, Hp, Wp, self.device))
+        if n == 0:  # (an empty tensor has no address to hand over)
+            return out
+        rp = C.c_void_p(rows.data_ptr()) if rows is not None else None
+        self._call(self.lib.imgenv_ped_maps_draw(self.h, C.c_void_p(ped_vectors.data_ptr()), rp, n, C.c_void_p(out.data_ptr()), self._stream()),
+                   "imgenv_ped_maps_draw")
+        return out
+
     def enable_minibatch(self, batch, buffers=1, fields=None):
         """Minibatches out of the rollout storage (``imgenv_rollout_minibatch_enable``; needs ``enable_rollout`` first):
         ``self.minibatch`` -- zero-copy tensors over the library's memory: ``mb_<field>`` ``[buffers, B, ...]`` with the row shapes
         and dtypes of ``rollout["obs_<field>"]``, ``mb_actions`` float32 ``[buffers, B, 3]``, ``mb_rewards`` / ``mb_weight`` float32,
         ``mb_dones`` uint8, ``mb_dones_info`` / ``mb_index`` int32 ``[buffers, B]``, ``mb_scalars`` float32 ``[buffers, 6, B]``
         (``t[b]`` is contiguous; the buffers of an array lie 256-byte aligned side by side), and ``valid`` / ``order`` int32
-        ``[T * R]``, ``valid_n`` int32 ``[1]``, ``norm`` float32 ``[2]``.  ``fields``: names of ``_cabi.ROLLOUT_BITS``, a subset
-        of the rollout's; None = all of them.  Nothing is launched; read-only; valid until ``close()``.  ValueError for a refused
+        ``[T * R]``, ``valid_n`` int32 ``[1]``, ``norm`` float32 ``[2]``.  ``fields``: the names ``enable_rollout``
+        takes (``_cabi.ROLLOUT_BITS``' and ``"norm_states"``, ``"ped_maps_drawn"``), a subset of the rollout's; None = all of them
+        (``"ped_maps_drawn"``: ``mb_ped_maps``, drawn by one more launch per minibatch).  Nothing is launched; read-only; valid until ``close()``.  ValueError for a refused
         cfg or a second call with another one, RuntimeError before ``enable_rollout``."""
         import torch
         c = _cabi.make_minibatch_cfg(batch, buffers, fields)
@@ -777,7 +809,8 @@ class World:
             views = self._views(mo, {"valid": (np.int32, (TR,)), "order": (np.int32, (TR,)), "valid_n": (np.int32, (1,)),  # (valid_n: uint32 in the library)
                                      "norm": (np.float32, (2,))}, "imgenv_minibatch_out")
             rows = {"mb_" + name: (self._rollout_rows[name][0], tuple(self._rollout_rows[name][1][1:]))
-                    for name in _cabi.ROLLOUT_FIELDS if "obs_" + name in (self.rollout or {}) and getattr(mo.buf[0], "mb_" + name)}
+                    for name in _cabi.ROLLOUT_FIELDS if getattr(mo.buf[0], "mb_" + name)
+                    and ("obs_" + name in (self.rollout or {}) or (name == "ped_maps" and self.rollout_draws_ped_maps))}
             norm_ptrs = {}  # the normalised fields' buffers: imgenv_normalise_out.mb_norm_*
             if self.normalise is not None:
                 no = self._normalise_out()

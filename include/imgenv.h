@@ -998,7 +998,7 @@ int imgenv_final_obs_outputs(imgenv_t* h, imgenv_final_obs_out* out);
  * ("rollout full: imgenv_rollout_begin") before it queues anything.
  * Memory: (T + 1) R x the selected rows + F x the same + 22 T R + 4 (T + 1) R + 8 F + 8 bytes (each array on a 256-byte
  * boundary).  The five single-frame fields at 48 x 48 views, 360 beams, ped_vec_len 71 and 48 x 48 pedestrian maps is about 35 KB per robot and slot -- about 18 GB for T = 128 at 4096 robots, 78 % of
- * it ped_maps: select what the policy reads.  Single frames unless STACKS is selected.  Read-only for the caller; stream order as
+ * it ped_maps: select what the policy reads, or IMGENV_ROLLOUT_PED_MAPS_DRAWN (7.8 KB per robot and slot, about 4.1 GB).  Single frames unless STACKS is selected.  Read-only for the caller; stream order as
  * for imgenv_out; no part of the output arena. */
 #define IMGENV_ROLLOUT_SENSOR_MAPS 1
 #define IMGENV_ROLLOUT_VECTOR_STATES 2
@@ -1013,6 +1013,13 @@ int imgenv_final_obs_outputs(imgenv_t* h, imgenv_final_obs_out* out);
                                              * the ring's pointers are imgenv_normalise_out.rollout_* / mb_norm_* */
 #define IMGENV_ROLLOUT_NORM_REWARDS 256     /* `rewards` holds imgenv_normalise_out.norm_rewards instead of step_rewards (IMGENV_NORM_REWARD);
                                              * selects no field of its own: at least one other bit is needed */
+/* not part of IMGENV_ROLLOUT_ALL: the ring keeps NO ped_maps (obs_ped_maps and final_ped_maps stay NULL, nothing is allocated for
+ * them, k_rollout moves 78 % fewer bytes at the five single-frame fields) and the minibatches draw mb_ped_maps from the stored
+ * ped_vector_states instead (imgenv_ped_maps_draw below has the definition): bit for bit the maps IMGENV_ROLLOUT_PED_MAPS would have
+ * stored.  Needs IMGENV_ROLLOUT_PED_VECTOR_STATES in the same cfg and excludes IMGENV_ROLLOUT_PED_MAPS (IMGENV_EINVAL otherwise, and
+ * for pedestrian maps beyond 16384 cells).  In imgenv_minibatch_cfg.fields the bit selects mb_ped_maps like any field; the
+ * minibatch needs mb_ped_vector_states only if the caller selects that too. */
+#define IMGENV_ROLLOUT_PED_MAPS_DRAWN 512
 typedef struct imgenv_rollout_cfg {
     int32_t struct_size;          /* sizeof(imgenv_rollout_cfg) */
     int32_t horizon;              /* T >= 1 */
@@ -1085,6 +1092,28 @@ int imgenv_rollout_begin(imgenv_t* h, void* stream);
  * IMGENV_EINVAL for a null values / adv / ret, IMGENV_ESTATE before imgenv_rollout_begin(). */
 int imgenv_rollout_gae(imgenv_t* h, const float* values, const float* final_values, float gamma, float lam, float* adv, float* ret, void* stream);
 
+/* ---- pedestrian maps drawn from pedestrian vectors ----
+ * imgenv_out.ped_maps is a pure function of imgenv_out.ped_vector_states: k_obs stamps the discs from the float32 (px, py, vx, vy) it
+ * stores as the first four of every pedestrian's seven floats, in rank order.  This draws the map again (k_ped_draw,
+ * csrc/ped_draw.h), bit for bit, so that a trainer keeps the vector row (4 ped_vec_len bytes) instead of the map (12 Hp Wp bytes).
+ * DEVICE pointers: ped_vectors f32 [.][PV], PV = ped_vec_len; rows i32 [n] or NULL; out f32 [n][3][Hp][Wp], (Hp, Wp) =
+ * imgenv_cfg.ped_image_size.  Row i of out is drawn from row (rows ? rows[i] : i) of ped_vectors; every cell of it is written:
+ *   n_ped = v[0] truncated to an integer and clamped to [0, (PV - 1) / 7]; 0 where v[0] is negative or not finite
+ *   for q = 0 .. n_ped - 1, ascending: (px, py, vx, vy) = v[1 + 7 q .. 4 + 7 q]
+ *     the pedestrian is skipped where (double)px > 3 or < -3, likewise py, or where px or py is not a number
+ *     tmx = -(double)px + 3; tmy = -(double)py + 3
+ *     jj runs over [floor((tmx - r) / res), floor((tmx + r) / res)), kk over the same with tmy, r = ped_image_r, res = 6 / Hp;
+ *       floor(x / res) is floor(x * (1 / res)) where res is a power of two, Python's x // res otherwise
+ *     cell (jj, kk) inside [0, Hp) x [0, Wp) takes the disc where ((jj + 0.5) res - tmx)^2 + ((kk + 0.5) res - tmy)^2 < r^2, in
+ *       float64 and in this order
+ *   a cell ends with the disc of the highest q that covers it: planes (1.0f, vx, vy), vx and vy copied bit for bit (-0.0f stays);
+ *     a cell under no disc is 0.0f in all three planes
+ *   a source row index below 0 gives an all-zero map (an index at or beyond the rows of ped_vectors is the caller's error)
+ * One launch on `stream`: nothing synchronises and no state of the handle changes; no feature needs to be enabled.  n == 0 succeeds
+ * and launches nothing.  IMGENV_EINVAL for a null handle, ped_vectors or out, n < 0, a handle without pedestrians (n_peds == 0 at
+ * imgenv_create) and for pedestrian maps of more than 16384 cells (the kernel keeps a word of LDS per cell). */
+int imgenv_ped_maps_draw(imgenv_t* h, const float* ped_vectors, const int32_t* rows, int64_t n, float* out, void* stream);
+
 /* ---- rollout minibatches: which stored transitions count, a random order over them, their statistics, the gather ----
  * Between "T steps collected" and "optimiser step" a trainer finds the transitions that count (is_clean != 0: a frozen robot of
  * MultiRobotCleanWrapper has advantage 0), normalises its advantages over exactly those, draws a fresh order over them every epoch
@@ -1113,7 +1142,8 @@ typedef struct imgenv_minibatch_cfg {
     int32_t struct_size;          /* sizeof(imgenv_minibatch_cfg) */
     int32_t batch;                /* B >= 1 */
     int32_t buffers;              /* 1 .. IMGENV_MB_MAX_BUFFERS */
-    int32_t fields;               /* IMGENV_ROLLOUT_* bits, a subset of the rollout's; 0: all of them */
+    int32_t fields;               /* IMGENV_ROLLOUT_* bits, a subset of the rollout's; 0: all of them (mb_ped_maps too where the rollout
+                                   * has IMGENV_ROLLOUT_PED_MAPS_DRAWN: one more launch per minibatch, k_ped_draw behind the gather) */
 } imgenv_minibatch_cfg;
 typedef struct imgenv_minibatch_buffer {
     /* [B][row]; NULL where not selected */

@@ -34,6 +34,11 @@ two ways, one process per measurement, alternating over several rounds: the libr
 imgenv_rollout_index + _stats + _shuffle and one gather launch per minibatch, no host read) and the same tensors from torch ops on
 the library's ring (nonzero on is_clean, masked mean / std, randperm, one index_select per field and scalar).
 
+--ped-draw-compare runs device_reset steps with rollout=--horizon and the default fields two ways, one process per measurement,
+alternating over several rounds: ped_maps stored in the ring / drawn at gather time from the stored pedestrian vectors
+(rollout_draw_ped_maps=True; --parent-tree adds the stored path of another checkout); per variant the time per step, the device time
+per minibatch of --batch transitions, the ring's bytes and, drawn, k_ped_draw alone against a copy of the bytes it writes.
+
 --wrappers table|clip feeds the policy's raw output (indices into a 28-row table, or float rows to be clipped) to
 VecImageEnv(wrappers=True): decode, speeds, normalised pedestrian vectors and close_to_human kept by the library;
 --torch-wrappers keeps the same with torch ops on top of a plain VecImageEnv; --wrappers-compare alternates pre-decoded actions
@@ -995,6 +1000,126 @@ def compare_minibatch(args, rounds=3):
                 batch=args.batch, rounds=rounds, runs=runs, summary=summary)
 
 
+def measure_ped_draw(variant, envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, horizon=32, batch=4096):
+    """One process of --ped-draw-compare: device_reset steps with ``rollout=horizon`` and the default fields, ``ped_maps`` stored
+    ("stored"; also what "parent" runs, from another checkout) or drawn at gather time ("drawn": ``rollout_draw_ped_maps=True``).
+    (a) us per step, windows restarted every ``horizon`` steps; (b) us per minibatch of ``batch`` transitions, device time between
+    two events around 20 gathers (the drawn variant: gather + k_ped_draw), of every field on this handle and of the maps alone on
+    a second one made afterwards (a handle's minibatch fields are chosen once); (c) "drawn": k_ped_draw alone over ``batch`` rows
+    of the ring, against the bytes it writes and a copy of as many; the ring's bytes"""
+    import torch
+    from img_env_amd import worldgen
+    from img_env_amd.vec_env import VecImageEnv
+    grid = worldgen.make_grid(200, 2)
+    cfg = worldgen.make_yaml_cfg(robots, peds, grid, time_max=time_max, n_obstacles=obstacles, seed=5)
+    T, n, B = horizon, envs * robots, batch
+    extra = dict(rollout_draw_ped_maps=True) if variant == "drawn" else {}
+    env = VecImageEnv(cfg, env_num=envs, seed=5, device_reset=True, rollout=T, rollout_final=n, **extra)
+    w = env.world
+    g = torch.Generator(device="cuda").manual_seed(1)
+    acts = torch.zeros(16, n, 3, device="cuda")
+    acts[:, :, 0] = torch.rand(16, n, generator=g, device="cuda") * 0.6
+    acts[:, :, 1] = torch.rand(16, n, generator=g, device="cuda") * 1.8 - 0.9
+    cursor = [0]
+
+    def step(a):
+        if cursor[0] == T:
+            env.rollout_begin()
+            cursor[0] = 0
+        env.step(a)
+        cursor[0] += 1
+    env.reset()
+    for s in range(time_max + 20):  # the drift phase: past the first wave of time limits
+        step(acts[s % 16])
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for s in range(steps):
+        step(acts[s % 16])
+    torch.cuda.synchronize()
+    res = dict(us_per_step=1e6 * (time.perf_counter() - t0) / steps, horizon=T, rows=n, batch=B,
+               ring_bytes=sum(t.numel() * t.element_size() for t in w.rollout.values()))
+    while cursor[0] < T:  # a full window for the minibatches
+        step(acts[cursor[0] % 16])
+
+    def device_us(fn, reps=20):
+        fn()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for k in range(reps):
+            fn(k)
+        b.record()
+        torch.cuda.synchronize()
+        return 1e3 * a.elapsed_time(b) / reps
+    maps = "ped_maps_drawn" if variant == "drawn" else "ped_maps"
+    w.enable_minibatch(B, 2, None)
+    w.rollout_index()
+    w.rollout_shuffle(7)
+    count = -(-T * n // B)
+    res["us_per_minibatch_all_fields"] = device_us(lambda k=0: w.rollout_minibatch(k % count, k % 2))
+    res["valid"] = w.rollout_valid_count()
+    res["maps_field"] = maps
+    if variant == "drawn":
+        ring = w.rollout["obs_ped_vector_states"].view(-1, w.rollout["obs_ped_vector_states"].shape[-1])
+        out = torch.empty((B,) + tuple(w.minibatch["mb_ped_maps"].shape[2:]), device="cuda")
+        rows = w.minibatch["order"][:B].clamp(min=0).contiguous()
+        res["us_ped_draw_alone_shuffled_rows"] = device_us(lambda k=0: w.draw_ped_maps(ring, rows, out))
+        res["us_ped_draw_alone_first_rows"] = device_us(lambda k=0: w.draw_ped_maps(ring[:B], None, out))
+        res["ped_draw_bytes_written"] = out.numel() * 4
+        src, dst = torch.empty_like(out), torch.empty_like(out)
+        res["us_copy_same_bytes"] = device_us(lambda k=0: dst.copy_(src))  # (a device-to-device copy: reads and writes that many bytes)
+        res["maps_not_zero"] = int((out.view(B, -1) != 0).any(dim=1).sum().item())
+    env.close()
+    # the maps alone: a second handle, one full window, the minibatch of that one field
+    env = VecImageEnv(cfg, env_num=envs, seed=5, device_reset=True, rollout=T, rollout_final=n, **extra)
+    w = env.world
+    env.reset()
+    for s in range(T):
+        env.step(acts[s % 16])
+    w.enable_minibatch(B, 2, [maps])
+    w.rollout_index()
+    w.rollout_shuffle(7)
+    res["us_per_minibatch_maps_alone"] = device_us(lambda k=0: w.rollout_minibatch(k % count, k % 2))
+    env.close()
+    return res
+
+
+def compare_ped_draw(args, rounds=3):
+    """stored / drawn (/ parent: the stored path from --parent-tree, a built checkout of the parent commit), alternating, `rounds`
+    times; one process per measurement"""
+    import subprocess
+    base = [sys.executable, os.path.abspath(__file__), "--envs", str(args.envs), "--robots", str(args.robots), "--peds", str(args.peds),
+            "--obstacles", str(args.obstacles), "--steps", str(args.steps), "--time-max", str(args.time_max), "--horizon", str(args.horizon),
+            "--batch", str(args.batch)]
+    variants, runs = ["stored", "drawn"] + (["parent"] if args.parent_tree else []), []
+    for rnd in range(rounds):
+        for variant in variants:
+            cmd = base + ["--ped-draw-variant", "stored" if variant == "parent" else variant]
+            if variant == "parent":
+                cmd += ["--tree", args.parent_tree]
+            out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+            if out.returncode != 0:
+                raise RuntimeError("%s: exit %d\n%s" % (variant, out.returncode, out.stderr[-2000:]))
+            runs.append(dict(round=rnd, variant=variant, **json.loads(out.stdout.strip().splitlines()[-1])))
+            print(json.dumps(runs[-1]), flush=True)
+    summary = {}
+    for variant in variants:
+        mine = [x for x in runs if x["variant"] == variant]
+        summary[variant] = {}
+        for key in ("us_per_step", "us_per_minibatch_all_fields", "us_per_minibatch_maps_alone", "us_ped_draw_alone_shuffled_rows", "us_ped_draw_alone_first_rows", "us_copy_same_bytes"):
+            v = [x[key] for x in mine if key in x]
+            if v:
+                summary[variant][key] = dict(rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
+        summary[variant]["ring_bytes"] = mine[0]["ring_bytes"]
+    summary["step_saving_us"] = summary["stored"]["us_per_step"]["median"] - summary["drawn"]["us_per_step"]["median"]
+    summary["minibatch_drawn_minus_stored_us"] = (summary["drawn"]["us_per_minibatch_all_fields"]["median"] -
+                                                  summary["stored"]["us_per_minibatch_all_fields"]["median"])
+    summary["minibatch_maps_alone_drawn_minus_stored_us"] = (summary["drawn"]["us_per_minibatch_maps_alone"]["median"] -
+                                                             summary["stored"]["us_per_minibatch_maps_alone"]["median"])
+    return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, steps=args.steps, time_max=args.time_max,
+                horizon=args.horizon, batch=args.batch, rounds=rounds, runs=runs, summary=summary)
+
+
 def compare_loss(args, rounds=3, window=0.6):
     """PPO's loss of one minibatch, from logits and values on the device to the gradients on them: ``VecImageEnv.policy_loss`` and
     ``backward()`` ("library": three launches and the autograd hand-over; "library_raw": ``World.policy_loss`` alone, whose
@@ -1136,6 +1261,9 @@ def main():
                          "from torch ops, alternating over --rounds rounds; one process per measurement")
     ap.add_argument("--minibatch-variant", default=None, choices=("library", "torch"), help="one measurement of --minibatch-compare")
     ap.add_argument("--batch", type=int, default=4096, help="--minibatch-compare: transitions per minibatch")
+    ap.add_argument("--ped-draw-compare", action="store_true",
+                    help="rollout=--horizon with ped_maps stored / drawn at gather time (/ the parent's, --parent-tree): us per step, per minibatch, k_ped_draw alone")
+    ap.add_argument("--ped-draw-variant", default=None, choices=("stored", "drawn"), help="one measurement of --ped-draw-compare")
     ap.add_argument("--loss-compare", action="store_true",
                     help="PPO's loss of a minibatch and its gradients: policy_loss / torch ops and autograd, alternating over --rounds rounds in one process")
     ap.add_argument("--tree", default=None, help="import img_env_amd from this checkout instead of the tool's own")
@@ -1149,6 +1277,17 @@ def main():
     if args.minibatch_variant:
         print(json.dumps(measure_minibatch(args.minibatch_variant, args.envs, args.robots, args.peds, args.obstacles, args.time_max, args.horizon,
                                            args.batch)))
+        return
+    if args.ped_draw_variant:
+        print(json.dumps(measure_ped_draw(args.ped_draw_variant, args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max,
+                                          args.horizon, args.batch)))
+        return
+    if args.ped_draw_compare:
+        res = compare_ped_draw(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
         return
     if args.loss_compare:
         res = compare_loss(args, args.rounds)

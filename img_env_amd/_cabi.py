@@ -470,6 +470,63 @@ def make_minibatch_cfg(batch, buffers=1, fields=0):
     return c
 
 
+#: sequence minibatches (imgenv_rollout_seq_enable; csrc/sequences.h)
+SEQ_MAX_STATES, SEQ_MAX_STATE_BYTES, SEQ_FLAG_BLOCK = 2, 65536, 256
+#: the arrays of imgenv_seq_buffer behind its mb_<field> pointers (the normalised fields' included), in the struct's order
+SEQ_SCALARS = ("mb_actions", "mb_rewards", "mb_dones", "mb_dones_info", "mb_index", "mb_weight", "mb_first", "mb_scalars", "mb_seq", "mb_seq_len",
+               "mb_seq_state")
+SEQ_HEADER = ("struct_size", "n_local", "horizon", "length", "batch", "buffers", "fields", "max_sequences", "state_bytes")
+#: the handle-wide pointers of imgenv_seq_out, in the struct's order
+SEQ_ARRAYS = ("seq_flag", "seq_valid", "seq_order", "seq_valid_n", "tile_count", "tile_base")
+
+
+class SeqCfg(C.Structure):
+    _fields_ = [("struct_size", _i32), ("length", _i32), ("batch", _i32), ("buffers", _i32), ("fields", _i32), ("state_bytes", _i32 * SEQ_MAX_STATES),
+                ("reserved", _i32)]
+
+
+class SeqBuffer(C.Structure):
+    _fields_ = ([("mb_" + name, C.c_void_p) for name in ROLLOUT_FIELDS + ROLLOUT_NORM_FIELDS] + [(name, C.c_void_p) for name in SEQ_SCALARS[:-1]] +
+                [("mb_seq_state", C.c_void_p * SEQ_MAX_STATES)])
+
+
+class SeqOut(C.Structure):
+    _fields_ = ([(name, _i32) for name in SEQ_HEADER[:-1]] + [("state_bytes", _i32 * SEQ_MAX_STATES)] + [(name, C.c_void_p) for name in SEQ_ARRAYS] +
+                [("buf", SeqBuffer * MB_MAX_BUFFERS)])
+
+
+class SeqArgs(C.Structure):
+    _fields_ = [("struct_size", _i32), ("j", _i32), ("buffer", _i32), ("n_scalars", _i32), ("normalise", _i32), ("reserved", _i32),
+                ("scalars", C.c_void_p * MB_MAX_SCALARS), ("norm", C.c_void_p), ("states", C.c_void_p * SEQ_MAX_STATES)]
+
+
+def make_seq_cfg(length, batch, buffers=1, fields=0, state_bytes=()):
+    """``imgenv_seq_cfg``: ``fields`` as ``make_minibatch_cfg`` takes them; ``state_bytes``: up to 2 row sizes of the caller's state arrays"""
+    c = SeqCfg()
+    c.struct_size = C.sizeof(SeqCfg)
+    c.length, c.batch, c.buffers = int(length), int(batch), int(buffers)
+    c.fields = make_minibatch_cfg(1, 1, fields).fields
+    state_bytes = list(state_bytes)
+    if len(state_bytes) > SEQ_MAX_STATES:
+        raise ValueError("sequences: at most %d state arrays" % SEQ_MAX_STATES)
+    for a, nb in enumerate(state_bytes):
+        c.state_bytes[a] = int(nb)
+    return c
+
+
+def make_seq_args(j, buffer=0, scalars=(), normalise=-1, norm=None, states=()):
+    """``imgenv_seq_args``: ``scalars`` and ``states`` device addresses (ints), ``norm`` one or None"""
+    a = SeqArgs()
+    a.struct_size = C.sizeof(SeqArgs)
+    a.j, a.buffer, a.n_scalars, a.normalise = int(j), int(buffer), len(scalars), int(normalise)
+    for s, ptr in enumerate(scalars[:MB_MAX_SCALARS]):
+        a.scalars[s] = ptr
+    a.norm = norm
+    for q, ptr in enumerate(states[:SEQ_MAX_STATES]):
+        a.states[q] = ptr
+    return a
+
+
 #: running normalisation (imgenv_normalise_enable; csrc/normalise.h)
 NORM_OBS, NORM_REWARD = 1, 2
 NORM_BLOCK, NORM_PER_LANE, NORM_MAX_COLS, NORM_MAX_BLOCKS = 256, 8, 64, 1024  # the launch shapes (csrc/launch_plan.h)
@@ -690,6 +747,8 @@ SYMBOLS = ("imgenv_backend", "imgenv_abi_version", "imgenv_last_error", "imgenv_
            "imgenv_rollout_enable", "imgenv_rollout_outputs", "imgenv_rollout_begin", "imgenv_rollout_gae", "imgenv_ped_maps_draw",
            "imgenv_rollout_minibatch_enable", "imgenv_rollout_minibatch_outputs", "imgenv_rollout_index", "imgenv_rollout_stats",
            "imgenv_rollout_shuffle", "imgenv_rollout_minibatch",
+           "imgenv_rollout_seq_enable", "imgenv_rollout_seq_outputs", "imgenv_rollout_seq_index", "imgenv_rollout_seq_shuffle",
+           "imgenv_rollout_seq_minibatch",
            "imgenv_normalise_enable", "imgenv_normalise_outputs", "imgenv_normalise_training", "imgenv_normalise_stats_get",
            "imgenv_normalise_stats_set",
            "imgenv_maps_add", "imgenv_world_maps_set", "imgenv_maps_policy", "imgenv_map_for_placement", "imgenv_world_maps",
@@ -777,6 +836,11 @@ def bind(lib):
     lib.imgenv_rollout_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
     lib.imgenv_rollout_shuffle.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.imgenv_rollout_minibatch.argtypes = [C.c_void_p, C.POINTER(MinibatchArgs), C.c_void_p]
+    lib.imgenv_rollout_seq_enable.argtypes = [C.c_void_p, C.POINTER(SeqCfg), C.POINTER(SeqOut)]
+    lib.imgenv_rollout_seq_outputs.argtypes = [C.c_void_p, C.POINTER(SeqOut)]
+    lib.imgenv_rollout_seq_index.argtypes = [C.c_void_p, C.c_void_p]
+    lib.imgenv_rollout_seq_shuffle.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.imgenv_rollout_seq_minibatch.argtypes = [C.c_void_p, C.POINTER(SeqArgs), C.c_void_p]
     lib.imgenv_normalise_enable.argtypes = [C.c_void_p, C.POINTER(NormaliseCfg), C.POINTER(NormaliseOut)]
     lib.imgenv_normalise_outputs.argtypes = [C.c_void_p, C.POINTER(NormaliseOut)]
     lib.imgenv_normalise_training.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

@@ -54,6 +54,7 @@ struct FeatureFacts {
     bool mb_on = false;
     bool norm_on = false, norm_obs = false, norm_rew = false;  // the arrays of IMGENV_NORM_OBS / IMGENV_NORM_REWARD exist
     int ped_h = 0, ped_w = 0;    // imgenv_cfg.ped_image_size (IMGENV_ROLLOUT_PED_MAPS_DRAWN: the map must fit k_ped_draw's rank plane)
+    bool seq_on = false;         // sequences.h
 };
 
 // the cfg and the caller's out struct of an enable call, before the handle is looked at.  An out struct says 0 or this library's size.
@@ -236,7 +237,7 @@ inline int normalise_enable_plan(const imgenv_normalise_cfg* c, const imgenv_nor
 inline int normalise_stack_depth(const FeatureFacts& f, bool obs) { return obs && f.stack_on && f.stack_state_depth >= 2 ? f.stack_state_depth : 0; }
 
 // ---------------------------------------------------------------------------------------- the row-copy features' fields
-enum FieldFeature { FIELDS_FINAL, FIELDS_ROLLOUT, FIELDS_MINIBATCH };
+enum FieldFeature { FIELDS_FINAL, FIELDS_ROLLOUT, FIELDS_MINIBATCH, FIELDS_SEQ };  // (the sequences gather the minibatches' fields)
 struct FieldFeatureNames {
     const char *cfg, *bits;  // "imgenv_X_cfg" and the prefix of its bits' names
     const int* order;        // the block's order (obs_fields.h)
@@ -251,6 +252,7 @@ inline FieldFeatureNames field_feature(FieldFeature which) {
     switch (which) {
         case FIELDS_FINAL: return {"imgenv_final_obs_cfg", "IMGENV_FINAL", FINAL_FIELD_ORDER, n_final};
         case FIELDS_ROLLOUT: return {"imgenv_rollout_cfg", "IMGENV_ROLLOUT", ROLLOUT_FIELD_ORDER, n_roll};
+        case FIELDS_SEQ: return {"imgenv_seq_cfg", "IMGENV_ROLLOUT", MINIBATCH_FIELD_ORDER, n_mb};
         default: return {"imgenv_minibatch_cfg", "IMGENV_ROLLOUT", MINIBATCH_FIELD_ORDER, n_mb};
     }
 }
@@ -297,6 +299,7 @@ inline int select_feature_fields(FieldFeature which, const ObsField (&cat)[OBSF_
     }
     if (which != FIELDS_FINAL && s.n > ROLLOUT_TABLE_FIELDS) FEATURE_REFUSE(IMGENV_EINVAL, "%s.fields %d: more fields than a table holds", n.cfg, cfg_fields);
     if (which == FIELDS_MINIBATCH && s.n == 0) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: no field of the rollout", cfg_fields);
+    if (which == FIELDS_SEQ && s.n == 0) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_seq_cfg.fields %d: no field of the rollout", cfg_fields);
     return IMGENV_OK;
 }
 
@@ -380,5 +383,41 @@ inline int minibatch_enable_plan(const imgenv_minibatch_cfg* c, const imgenv_min
     }
     *want = c->fields ? c->fields : (f->roll_fields & ~IMGENV_ROLLOUT_NORM_REWARDS);
     if (*want & ~f->roll_fields) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_minibatch_cfg.fields %d: the rollout stores %d", c->fields, f->roll_fields);
+    return IMGENV_OK;
+}
+
+// ---------------------------------------------------------------------------------------- sequence minibatches (need the rollout,
+// not the minibatches)
+inline bool seq_cfg_same(const imgenv_seq_cfg& c, const imgenv_seq_cfg& o) {
+    return c.length == o.length && c.batch == o.batch && c.buffers == o.buffers && c.fields == o.fields && c.state_bytes[0] == o.state_bytes[0] &&
+           c.state_bytes[1] == o.state_bytes[1];
+}
+// (*want: the bits in effect, as minibatch_enable_plan's)
+inline int seq_enable_plan(const imgenv_seq_cfg* c, const imgenv_seq_out* out, const FeatureFacts* f, const imgenv_seq_cfg* stored, int* want, FeatureMsg msg) {
+    FEATURE_TRY(enable_args(c, "imgenv_seq_cfg", out, "imgenv_seq_out", msg));
+    if (c->length < 1) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_seq_cfg.length %d: at least 1", c->length);
+    if (c->batch < 1) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_seq_cfg.batch %d: at least 1", c->batch);
+    if (c->buffers < 1 || c->buffers > IMGENV_MB_MAX_BUFFERS) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_seq_cfg.buffers %d: 1 .. %d", c->buffers, IMGENV_MB_MAX_BUFFERS);
+    if (c->fields & ~(IMGENV_ROLLOUT_ALL | IMGENV_ROLLOUT_NORM_STATES | IMGENV_ROLLOUT_PED_MAPS_DRAWN)) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_seq_cfg.fields %d", c->fields);
+    for (int a = 0; a < IMGENV_SEQ_MAX_STATES; a++)
+        if (c->state_bytes[a] < 0 || c->state_bytes[a] % 4 != 0 || c->state_bytes[a] > SEQ_MAX_STATE_BYTES)
+            FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_seq_cfg.state_bytes[%d] %d: a multiple of 4, 0 .. %d", a, c->state_bytes[a], SEQ_MAX_STATE_BYTES);
+    if (c->reserved != 0) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_seq_cfg.reserved %d", c->reserved);
+    if ((c->fields & IMGENV_ROLLOUT_NORM_STATES) && !(f && f->norm_on))
+        FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_seq_cfg.fields %d: IMGENV_ROLLOUT_NORM_* before imgenv_normalise_enable", c->fields);
+    FEATURE_TRY(enable_null_handle(f, msg));
+    if (!f->roll_on) FEATURE_REFUSE(IMGENV_ESTATE, "imgenv_rollout_seq_enable before imgenv_rollout_enable");
+    if (f->seq_on) {
+        if (!seq_cfg_same(*c, *stored))
+            FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_rollout_seq_enable: the handle already gathers sequences of length %d, batch %d, buffers %d, fields %d, state_bytes %d, %d",
+                           stored->length, stored->batch, stored->buffers, stored->fields, stored->state_bytes[0], stored->state_bytes[1]);
+        return ENABLE_REPEAT;
+    }
+    if (c->length > f->roll_horizon) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_seq_cfg.length %d: 1 .. the rollout's horizon %d", c->length, f->roll_horizon);
+    if (plan_seq_chunks((size_t)f->roll_horizon, (size_t)c->length) * (size_t)f->RL > 0x7fffffffu)
+        FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_seq_cfg.length %d: %zu chunks x %d robots is beyond 2^31 - 1", c->length,
+                       plan_seq_chunks((size_t)f->roll_horizon, (size_t)c->length), f->RL);
+    *want = c->fields ? c->fields : (f->roll_fields & ~IMGENV_ROLLOUT_NORM_REWARDS);
+    if (*want & ~f->roll_fields) FEATURE_REFUSE(IMGENV_EINVAL, "imgenv_seq_cfg.fields %d: the rollout stores %d", c->fields, f->roll_fields);
     return IMGENV_OK;
 }

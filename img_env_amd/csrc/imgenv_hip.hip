@@ -37,6 +37,7 @@
 #include "final_obs.h"
 #include "rollout.h"
 #include "minibatch.h"
+#include "sequences.h"
 #include "ped_draw.h"
 #include "map_bank.h"
 #include "spawn_slot.h"
@@ -309,6 +310,16 @@ struct imgenv {
         PedDrawDev draw = {};        // imgenv_rollout_minibatch_enable / never / IMGENV_ROLLOUT_PED_MAPS_DRAWN is selected (draw.vec != nullptr): k_ped_draw's arguments but for the call's buffer and minibatch
         float* draw_dst[IMGENV_MB_MAX_BUFFERS] = {};  // imgenv_rollout_minibatch_enable / never / buffer b's mb_ped_maps where they are drawn
     } mb;
+    // sequence minibatches (csrc/sequences.h); dev holds the field table, the ring's scalars and the sizes, its dst pointers are the call's buffer's
+    struct Sequences : Feature<SeqGatherDev, imgenv_seq_cfg, imgenv_seq_out> {
+        bool indexed = false;        // imgenv_rollout_seq_index / imgenv_rollout_seq_enable / seq_valid exists, of the generation (gen_n, gen_seq)
+        int gen_n = 0;               // imgenv_rollout_seq_index / never / roll.n when the index was made
+        uint64_t gen_seq = 0;        // imgenv_rollout_seq_index / never / step.chain_seq then
+        bool shuffled = false;       // imgenv_rollout_seq_shuffle / imgenv_rollout_seq_index / seq_order is a permutation of that index
+        unsigned char* dst[IMGENV_MB_MAX_BUFFERS][ROLLOUT_TABLE_FIELDS];  // imgenv_rollout_seq_enable / never / where buffer b keeps entry k of dev.f
+        PedDrawDev draw = {};        // imgenv_rollout_seq_enable / never / IMGENV_ROLLOUT_PED_MAPS_DRAWN is selected (draw.vec != nullptr): k_ped_draw's arguments but for the call's buffer
+        float* draw_dst[IMGENV_MB_MAX_BUFFERS] = {};  // imgenv_rollout_seq_enable / never / buffer b's mb_ped_maps where they are drawn
+    } seq;
     // running normalisation (csrc/normalise.h); dev.n_obs as enabled: n_ret, cols, update, the turns and the rows are the launch's
     struct Normalise : Feature<NormDev, imgenv_normalise_cfg, imgenv_normalise_out> {
         bool training = true;        // imgenv_normalise_enable, imgenv_normalise_training / the latter / the chains update the statistics
@@ -3528,6 +3539,7 @@ static const FeatureFacts* feature_facts(const imgenv* h, FeatureFacts& f) {
     f.final_on = h->final_obs.on;
     f.roll_on = h->roll.on; f.roll_horizon = h->roll.cfg.horizon; f.roll_fields = h->roll.cfg.fields;
     f.mb_on = h->mb.on;
+    f.seq_on = h->seq.on;
     f.norm_on = h->norm.on; f.norm_obs = h->norm.dev.norm_vector_states != nullptr; f.norm_rew = h->norm.dev.norm_rewards != nullptr;
     f.ped_h = h->cfg.ped_image_size[0]; f.ped_w = h->cfg.ped_image_size[1];
     return &f;
@@ -4651,6 +4663,205 @@ extern "C" int imgenv_rollout_minibatch(imgenv_t* h, const imgenv_minibatch_args
         PedDrawDev d = h->mb.draw;
         d.out = h->mb.draw_dst[a->buffer];
         d.first = g.first;
+        launch_ped_draw(d, (hipStream_t)stream);
+    }
+    HIPCHK(hipGetLastError());
+    return IMGENV_OK;
+}
+
+
+// ---- sequence minibatches (include/imgenv.h; the kernels are csrc/sequences.h) ----
+extern "C" int imgenv_rollout_seq_enable(imgenv_t* h, const imgenv_seq_cfg* c, imgenv_seq_out* out) {
+    FeatureMsg msg;
+    FeatureFacts facts;
+    int want = 0;
+    const int plan = planned(seq_enable_plan(c, out, feature_facts(h, facts), h ? &h->seq.cfg : nullptr, &want, msg), msg);
+    if (plan < 0) return plan;
+    if (plan == ENABLE_REPEAT) return out ? imgenv_rollout_seq_outputs(h, out) : IMGENV_OK;
+    // what the ring keeps, as a catalogue: the buffers' fields come out in the ring's own order
+    ObsField ring[OBSF_COUNT] = {};
+    for (int k = 0; k < h->roll.dev.n_fields; k++) ring[h->roll.field_id[k]] = {h->roll.dev.f[k].ring, h->roll.row_bytes[k]};
+    FieldSelection s;
+    RTRY(planned(select_feature_fields(FIELDS_SEQ, ring, want, c->fields, s, msg, ped_maps_row_bytes(facts)), msg));
+    // one zeroed block (launch_plan.h); nothing of the handle changes before it is there
+    const size_t RL = (size_t)h->RL, T = (size_t)h->roll.cfg.horizon, NB = (size_t)c->buffers, L = (size_t)c->length, Bs = (size_t)c->batch;
+    const size_t state_bytes[SEQ_MAX_STATES] = {(size_t)c->state_bytes[0], (size_t)c->state_bytes[1]};
+    const SeqLayout l = plan_seq_layout(s.row_bytes, s.n, RL, T, L, Bs, NB, state_bytes);
+    unsigned char* block = nullptr;
+    RTRY(feature_block(h, l.total, "imgenv_rollout_seq_enable", &block));
+    SeqGatherDev g;
+    memset(&g, 0, sizeof(g));
+    // the gather's table: the selection without the drawn field (entry `of[k]` of the selection), which is k_ped_draw's
+    int of[ROLLOUT_TABLE_FIELDS] = {}, drawn = -1;
+    for (int k = 0; k < s.n; k++) {
+        if (s.id[k] == OBSF_PED_MAPS_DRAWN) {
+            drawn = k;
+            continue;
+        }
+        const FinalFieldPlan f = plan_final_field(s.row_bytes[k]);  // (the ring's own chunking)
+        MbGatherField& gf = g.f[g.n_fields];
+        gf.ring = (const unsigned char*)ring[s.id[k]].src;
+        gf.unit = f.unit;  // (dst: the buffer's, h->seq.dst, at the call)
+        gf.chunks = f.chunks;
+        g.chunks_per_row += f.chunks;
+        of[g.n_fields++] = k;
+    }
+    if (g.n_fields == 0) g.chunks_per_row = 1;  // (nothing to copy: the one chunk per step is the scalars' lane)
+    for (int a = 0; a < SEQ_MAX_STATES; a++) {
+        const FinalFieldPlan f = plan_final_field(state_bytes[a]);
+        g.st[a].unit = f.unit;
+        g.st[a].chunks = state_bytes[a] ? f.chunks : 0;
+        g.state_chunks += g.st[a].chunks;
+    }
+    imgenv_seq_out o = {};
+    o.horizon = h->roll.cfg.horizon;
+    o.length = c->length;
+    o.batch = c->batch;
+    o.buffers = c->buffers;
+    o.fields = want;
+    o.max_sequences = (int32_t)(plan_seq_chunks(T, L) * RL);
+    o.state_bytes[0] = c->state_bytes[0];
+    o.state_bytes[1] = c->state_bytes[1];
+    o.seq_flag = block + l.flag;
+    o.seq_valid = (int32_t*)(block + l.valid);
+    o.seq_order = (int32_t*)(block + l.order);
+    o.seq_valid_n = (uint32_t*)(block + l.valid_n);
+    o.tile_count = (int32_t*)(block + l.tile_count);
+    o.tile_base = (int32_t*)(block + l.tile_base);
+    for (size_t b = 0; b < NB; b++) {
+        imgenv_seq_buffer& m = o.buf[b];
+        for (int k = 0; k < s.n; k++) obs_slot_put_seq(OBS_SLOTS[s.id[k]], &m, block + l.field[b][k]);
+        for (int k = 0; k < g.n_fields; k++) h->seq.dst[b][k] = block + l.field[b][of[k]];
+        if (drawn >= 0) h->seq.draw_dst[b] = (float*)(block + l.field[b][drawn]);
+        m.mb_actions = (float*)(block + l.scalar[b][SEQ_S_ACTIONS]);
+        m.mb_rewards = (float*)(block + l.scalar[b][SEQ_S_REWARDS]);
+        m.mb_dones = block + l.scalar[b][SEQ_S_DONES];
+        m.mb_dones_info = (int32_t*)(block + l.scalar[b][SEQ_S_DONES_INFO]);
+        m.mb_index = (int32_t*)(block + l.scalar[b][SEQ_S_INDEX]);
+        m.mb_weight = (float*)(block + l.scalar[b][SEQ_S_WEIGHT]);
+        m.mb_first = block + l.scalar[b][SEQ_S_FIRST];
+        m.mb_scalars = (float*)(block + l.scalar[b][SEQ_S_SCALARS]);
+        m.mb_seq = (int32_t*)(block + l.scalar[b][SEQ_S_SEQ]);
+        m.mb_seq_len = (int32_t*)(block + l.scalar[b][SEQ_S_SEQ_LEN]);
+        for (int a = 0; a < SEQ_MAX_STATES; a++) m.mb_seq_state[a] = state_bytes[a] ? block + l.scalar[b][SEQ_S_STATE0 + a] : nullptr;
+    }
+    g.order = o.seq_order;
+    g.Bs = (uint32_t)c->batch;
+    g.L = (uint32_t)c->length;
+    g.R = (uint32_t)RL;
+    g.S = (uint32_t)o.max_sequences;
+    g.actions = h->roll.dev.actions;
+    g.rewards = h->roll.dev.rewards;
+    g.dones = h->roll.dev.dones;
+    g.is_clean = h->roll.dev.is_clean;
+    g.dones_info = h->roll.dev.dones_info;
+    g.final_idx = h->roll.dev.final_idx;
+    h->seq.draw = {};
+    if (drawn >= 0) h->seq.draw = ped_draw_args(h, (const float*)ring[OBS_SLOTS[OBSF_PED_MAPS_DRAWN].from].src, nullptr, (uint32_t)(L * Bs), nullptr);
+    h->seq.dev = g;
+    h->seq.cfg = *c;
+    h->seq.indexed = h->seq.shuffled = false;
+    return enable_done(h, h->seq, o, out);
+}
+
+extern "C" int imgenv_rollout_seq_outputs(imgenv_t* h, imgenv_seq_out* out) {
+    return feature_outputs(h, &imgenv::seq, out, "imgenv_rollout_seq_enable");
+}
+
+// the index is of this moment: no chain and no imgenv_rollout_begin since
+static int seq_fresh(const imgenv* h, const char* who) {
+    RTRY(needs(h->seq.on, "imgenv_rollout_seq_enable"));
+    if (!h->seq.indexed) FAIL(IMGENV_ESTATE, "%s before imgenv_rollout_seq_index", who);
+    if (!h->roll.begun || h->seq.gen_n != h->roll.n || h->seq.gen_seq != h->step.chain_seq) FAIL(IMGENV_ESTATE, "%s: rollout changed since imgenv_rollout_seq_index", who);
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_rollout_seq_index(imgenv_t* h, void* stream) {
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    RTRY(needs(h->seq.on, "imgenv_rollout_seq_enable"));
+    if (!h->roll.begun) FAIL(IMGENV_ESTATE, "imgenv_rollout_seq_index before imgenv_rollout_begin");
+    if (h->roll.n == 0) FAIL(IMGENV_ESTATE, "imgenv_rollout_seq_index: no transition is stored yet");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    const imgenv_seq_out& o = h->seq.out;
+    const SeqGatherDev& g = h->seq.dev;
+    const size_t total = plan_seq_chunks((size_t)h->roll.n, (size_t)g.L) * (size_t)g.R;  // C R <= C_max R
+    const SeqFlagDev f = {h->roll.dev.is_clean, o.seq_flag, g.R, g.L, (uint32_t)h->roll.n, (uint32_t)total};
+    const MbIndexDev d = {o.seq_flag, o.seq_valid, o.tile_count, o.tile_base, o.seq_valid_n, (uint32_t)total, (uint32_t)plan_mb_tiles(total)};
+    const LaunchShape lanes = plan_seq_flag_launch(total), tiles = plan_mb_index_launch(total), one = plan_mb_scan_launch();
+    k_seq_flag<<<dim3(lanes.grid), dim3(lanes.block), 0, st>>>(f);
+    k_mb_count<<<dim3(tiles.grid), dim3(tiles.block), 0, st>>>(d);
+    k_mb_scan<<<dim3(one.grid), dim3(one.block), 0, st>>>(d);
+    k_mb_scatter<<<dim3(tiles.grid), dim3(tiles.block), 0, st>>>(d);
+    HIPCHK(hipGetLastError());
+    h->seq.indexed = true;
+    h->seq.shuffled = false;
+    h->seq.gen_n = h->roll.n;
+    h->seq.gen_seq = h->step.chain_seq;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_rollout_seq_shuffle(imgenv_t* h, uint32_t seed_lo, uint32_t seed_hi, void* stream) {
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    RTRY(seq_fresh(h, "imgenv_rollout_seq_shuffle"));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const imgenv_seq_out& o = h->seq.out;
+    const MbShuffleDev s = {o.seq_valid, o.seq_valid_n, o.seq_order, h->seq.dev.S, mb_keys(seed_lo, seed_hi)};
+    const LaunchShape g = plan_mb_shuffle_launch(s.TR);
+    k_mb_shuffle<<<dim3(g.grid), dim3(g.block), 0, (hipStream_t)stream>>>(s);
+    HIPCHK(hipGetLastError());
+    h->seq.shuffled = true;
+    return IMGENV_OK;
+}
+
+extern "C" int imgenv_rollout_seq_minibatch(imgenv_t* h, const imgenv_seq_args* a, void* stream) {
+    if (!a) FAIL(IMGENV_EINVAL, "null argument");
+    if (a->struct_size != (int32_t)sizeof(imgenv_seq_args))
+        FAIL(IMGENV_EINVAL, "imgenv_seq_args.struct_size %d (this library's is %d)", a->struct_size, (int)sizeof(imgenv_seq_args));
+    if (a->j < 0) FAIL(IMGENV_EINVAL, "imgenv_seq_args.j %d", a->j);
+    if (a->n_scalars < 0 || a->n_scalars > IMGENV_MB_MAX_SCALARS) FAIL(IMGENV_EINVAL, "imgenv_seq_args.n_scalars %d: 0 .. %d", a->n_scalars, IMGENV_MB_MAX_SCALARS);
+    if (a->normalise < -1 || a->normalise >= a->n_scalars) FAIL(IMGENV_EINVAL, "imgenv_seq_args.normalise %d: -1 or an index below n_scalars %d", a->normalise, a->n_scalars);
+    for (int s = 0; s < a->n_scalars; s++)
+        if (!a->scalars[s]) FAIL(IMGENV_EINVAL, "imgenv_seq_args.scalars[%d] is null", s);
+    if (a->normalise >= 0 && !a->norm) FAIL(IMGENV_EINVAL, "imgenv_seq_args.norm is null with normalise %d", a->normalise);
+    if (!h) FAIL(IMGENV_EINVAL, "null argument");
+    RTRY(needs(h->seq.on, "imgenv_rollout_seq_enable"));
+    if (a->buffer < 0 || a->buffer >= h->seq.cfg.buffers) FAIL(IMGENV_EINVAL, "imgenv_seq_args.buffer %d: 0 .. %d", a->buffer, h->seq.cfg.buffers - 1);
+    for (int q = 0; q < SEQ_MAX_STATES; q++)
+        if (h->seq.cfg.state_bytes[q] > 0 && (!a->states[q] || ((uintptr_t)a->states[q] & 15)))
+            FAIL(IMGENV_EINVAL, "imgenv_seq_args.states[%d] is %s", q, a->states[q] ? "not 16-byte aligned" : "null");
+    RTRY(seq_fresh(h, "imgenv_rollout_seq_minibatch"));
+    if (!h->seq.shuffled) FAIL(IMGENV_ESTATE, "imgenv_rollout_seq_minibatch before imgenv_rollout_seq_shuffle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const imgenv_seq_buffer& m = h->seq.out.buf[a->buffer];
+    SeqGatherDev g = h->seq.dev;
+    for (int k = 0; k < g.n_fields; k++) g.f[k].dst = h->seq.dst[a->buffer][k];
+    for (int q = 0; q < SEQ_MAX_STATES; q++) {
+        g.st[q].src = (const unsigned char*)a->states[q];
+        g.st[q].dst = m.mb_seq_state[q];
+    }
+    g.first = (size_t)a->j * (size_t)g.Bs;
+    g.n = h->seq.gen_n;
+    g.mb_actions = m.mb_actions;
+    g.mb_rewards = m.mb_rewards;
+    g.mb_dones = m.mb_dones;
+    g.mb_dones_info = m.mb_dones_info;
+    g.mb_index = m.mb_index;
+    g.mb_weight = m.mb_weight;
+    g.mb_first = m.mb_first;
+    g.mb_scalars = m.mb_scalars;
+    g.mb_seq = m.mb_seq;
+    g.mb_seq_len = m.mb_seq_len;
+    for (int s = 0; s < a->n_scalars; s++) g.scalars[s] = a->scalars[s];
+    g.n_scalars = a->n_scalars;
+    g.normalise = a->normalise;
+    g.norm = a->norm;
+    const LaunchShape s = plan_seq_gather_launch(g.L, g.Bs, g.chunks_per_row, g.state_chunks);
+    k_rollout_seq_gather<<<dim3(s.grid), dim3(s.block), 0, (hipStream_t)stream>>>(g);
+    if (h->seq.draw.vec) {  // IMGENV_ROLLOUT_PED_MAPS_DRAWN: mb_ped_maps of the same steps, one more launch, the buffer's mb_index its rows
+        PedDrawDev d = h->seq.draw;
+        d.out = h->seq.draw_dst[a->buffer];
+        d.rows = m.mb_index;
         launch_ped_draw(d, (hipStream_t)stream);
     }
     HIPCHK(hipGetLastError());

@@ -54,6 +54,9 @@
 #define MB_STATS_TILE (MB_STATS_BLOCK * MB_STATS_PER_LANE)
 #define MB_SHUFFLE_BLOCK 256 // k_mb_shuffle: one lane per position of `order`
 #define MB_ROUNDS 6          // Feistel rounds of the shuffle's permutation
+#define SEQ_FLAG_BLOCK 256   // k_seq_flag (sequences.h): one lane per sequence
+#define SEQ_MAX_STATES 2     // caller state arrays a sequence gather carries (IMGENV_SEQ_MAX_STATES)
+#define SEQ_MAX_STATE_BYTES 65536
 #define PED_DRAW_BLOCK 256       // k_ped_draw (ped_draw.h): one workgroup per drawn map, four wavefronts
 #define PED_DRAW_MAX_BLOCKS 2048 // eight workgroups per CU of 256; the kernel strides over further rows
 #define PED_DRAW_LDS_BYTES 65536 // the rank plane, a word per cell: 128 x 128 cells at most (96 x 96 takes 36 864 bytes)
@@ -677,6 +680,16 @@ inline LaunchShape plan_mb_shuffle_launch(size_t positions) {
 inline LaunchShape plan_mb_gather_launch(size_t batch, uint32_t chunks_per_row) {
     return plan_tail(batch * chunks_per_row, ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS);
 }
+// sequences.h.  The flags: a lane per sequence, no cap (2^31 sequences are 2^23 workgroups).  The compaction and the shuffle are
+// the minibatches' launches over the sequences.  The gather: length x batch x chunks per row field items, then batch x state chunks
+// state items, capped; the kernel strides.
+inline size_t plan_seq_chunks(size_t steps, size_t length) { return (steps + length - 1) / length; }
+inline LaunchShape plan_seq_flag_launch(size_t sequences) {
+    return {(unsigned)std::max<size_t>(1, (sequences + SEQ_FLAG_BLOCK - 1) / SEQ_FLAG_BLOCK), SEQ_FLAG_BLOCK, 0};
+}
+inline LaunchShape plan_seq_gather_launch(size_t length, size_t batch, uint32_t chunks_per_row, uint32_t state_chunks) {
+    return plan_tail(length * batch * chunks_per_row + batch * state_chunks, ROLLOUT_BLOCK, ROLLOUT_MAX_BLOCKS);
+}
 
 // ---------------------------------------------------------------------------------------- anywhere: k_ped_draw
 // ped_draw.h: one workgroup per map, capped -- the kernel strides -- with the map's rank plane, a word per cell, as dynamic LDS.  A
@@ -800,6 +813,34 @@ inline MinibatchLayout plan_minibatch_layout(const size_t* row_bytes, int n, siz
         for (size_t b = 0; b < buffers; b++) l.field[b][k] = c.take(B * row_bytes[k]);
     const size_t scalar_bytes[MB_S_COUNT] = {B * 12, B * 4, B, B * 4, B * 4, B * 4, B * 4 * IMGENV_MB_MAX_SCALARS};
     for (int q = 0; q < MB_S_COUNT; q++)
+        for (size_t b = 0; b < buffers; b++) l.scalar[b][q] = c.take(scalar_bytes[q]);
+    l.total = c.total;
+    return l;
+}
+
+// imgenv_rollout_seq_enable (sequences.h): the flags, the index and its tile scratch, then per gathered field and per scalar array
+// its `buffers` copies side by side, as the minibatches'.  S = C_max RL sequences, a buffer holds length x batch steps.
+enum { SEQ_S_ACTIONS, SEQ_S_REWARDS, SEQ_S_DONES, SEQ_S_DONES_INFO, SEQ_S_INDEX, SEQ_S_WEIGHT, SEQ_S_FIRST, SEQ_S_SCALARS, SEQ_S_SEQ, SEQ_S_SEQ_LEN,
+       SEQ_S_STATE0, SEQ_S_STATE1, SEQ_S_COUNT };
+struct SeqLayout {
+    size_t flag, valid, order, valid_n, tile_count, tile_base;
+    size_t field[IMGENV_MB_MAX_BUFFERS][ROLLOUT_TABLE_FIELDS], scalar[IMGENV_MB_MAX_BUFFERS][SEQ_S_COUNT], total;
+};
+inline SeqLayout plan_seq_layout(const size_t* row_bytes, int n, size_t RL, size_t T, size_t length, size_t batch, size_t buffers, const size_t* state_bytes) {
+    SeqLayout l = {};
+    const size_t S = plan_seq_chunks(T, length) * RL, tiles = plan_mb_tiles(S), N = length * batch;
+    Carve c;
+    l.flag = c.take(S);
+    l.valid = c.take(S * 4);
+    l.order = c.take(S * 4);
+    l.valid_n = c.take(4);
+    l.tile_count = c.take(tiles * 4);
+    l.tile_base = c.take(tiles * 4);
+    for (int k = 0; k < n; k++)
+        for (size_t b = 0; b < buffers; b++) l.field[b][k] = c.take(N * row_bytes[k]);
+    const size_t scalar_bytes[SEQ_S_COUNT] = {N * 12, N * 4, N, N * 4, N * 4, N * 4, N, N * 4 * IMGENV_MB_MAX_SCALARS, batch * 4, batch * 4,
+                                              batch * state_bytes[0], batch * state_bytes[1]};
+    for (int q = 0; q < SEQ_S_COUNT; q++)
         for (size_t b = 0; b < buffers; b++) l.scalar[b][q] = c.take(scalar_bytes[q]);
     l.total = c.total;
     return l;

@@ -82,17 +82,20 @@ struct ObsSlot {
     size_t final_out, ring_out, fin_out, mb_out;
     bool norm;
     int from;  // a drawn field's source field; -1 for every other
+    size_t seq_out;  // imgenv_seq_buffer's member (sequences.h), the normalised fields' too: that struct holds them itself
 };
-#define OBS_SLOT_FINAL_ONLY(bit, member) {bit, 0, offsetof(imgenv_final_obs_out, member), OBS_NO_SLOT, OBS_NO_SLOT, OBS_NO_SLOT, false, -1}
+#define OBS_SLOT_FINAL_ONLY(bit, member) {bit, 0, offsetof(imgenv_final_obs_out, member), OBS_NO_SLOT, OBS_NO_SLOT, OBS_NO_SLOT, false, -1, OBS_NO_SLOT}
 #define OBS_SLOT_DRAWN(rbit, member, from_id) \
-    {0, rbit, OBS_NO_SLOT, OBS_NO_SLOT, OBS_NO_SLOT, offsetof(imgenv_minibatch_buffer, mb_##member), false, from_id}
+    {0, rbit, OBS_NO_SLOT, OBS_NO_SLOT, OBS_NO_SLOT, offsetof(imgenv_minibatch_buffer, mb_##member), false, from_id, \
+     offsetof(imgenv_seq_buffer, mb_##member)}
 #define OBS_SLOT_ALL(fbit, rbit, member)                                                                                       \
     {fbit, rbit, offsetof(imgenv_final_obs_out, member), offsetof(imgenv_rollout_out, obs_##member),                           \
-     offsetof(imgenv_rollout_out, final_##member), offsetof(imgenv_minibatch_buffer, mb_##member), false, -1}
+     offsetof(imgenv_rollout_out, final_##member), offsetof(imgenv_minibatch_buffer, mb_##member), false, -1,                  \
+     offsetof(imgenv_seq_buffer, mb_##member)}
 #define OBS_SLOT_NORM(member)                                                                                                  \
     {IMGENV_FINAL_NORM_STATES, IMGENV_ROLLOUT_NORM_STATES, offsetof(imgenv_normalise_out, final_##member),                     \
      offsetof(imgenv_normalise_out, rollout_obs_##member), offsetof(imgenv_normalise_out, rollout_final_##member),             \
-     offsetof(imgenv_normalise_out, mb_##member), true, -1}
+     offsetof(imgenv_normalise_out, mb_##member), true, -1, offsetof(imgenv_seq_buffer, mb_##member)}
 static const ObsSlot OBS_SLOTS[OBSF_SLOT_COUNT] = {
     OBS_SLOT_ALL(IMGENV_FINAL_VECTOR_STATES, IMGENV_ROLLOUT_VECTOR_STATES, vector_states),
     OBS_SLOT_ALL(IMGENV_FINAL_SENSOR_MAPS, IMGENV_ROLLOUT_SENSOR_MAPS, sensor_maps),
@@ -136,6 +139,9 @@ inline void obs_slot_put(const ObsSlot& s, size_t off, void* own, imgenv_normali
 inline void obs_slot_put_mb(const ObsSlot& s, imgenv_minibatch_buffer* buf, imgenv_normalise_out* norm_out, int b, void* p) {
     obs_slot_put(s, s.mb_out + (s.norm ? (size_t)b * sizeof(void*) : 0), buf, norm_out, p);
 }
+
+// likewise for a sequence buffer (sequences.h): always a member of `buf` itself
+inline void obs_slot_put_seq(const ObsSlot& s, imgenv_seq_buffer* buf, void* p) { *(void**)((unsigned char*)buf + s.seq_out) = p; }
 
 // a catalogue with the drawn fields behind it: a drawn field is there where its source is, with a row of `drawn_row_bytes` (the one
 // drawn field there is: a pedestrian map, feature_plan.h's ped_maps_row_bytes)

@@ -72,6 +72,8 @@ class VecImageEnv:
     ``mb_ped_maps`` from those, ``rollout_ped_maps(t)`` and ``rollout_final_ped_maps()`` draw a slot and the final list.
     ``minibatch=B`` (with ``rollout=T``): the PPO epoch's minibatches gathered by the library, without a host read:
     ``rollout_minibatches(scalars, seed, normalise)``.
+    ``sequences=dict(length=L, batch=Bs, buffers=1, state_bytes=())`` (with ``rollout=T``): minibatches of whole sequences for a
+    recurrent policy, time-major ``[L, Bs, ...]``: ``rollout_sequences(scalars, seed, states)``, ``sequence_rows(mb)``.
     ``normalise=dict(...)``: running normalisation of ``vector_states`` and of the reward inside the library (VecNormalize): the
     state and the reward handed out are the normalised ones, ``info`` gains ``raw_vector_states`` and ``raw_rewards``.
     ``policy=dict(seed=s)`` (with ``wrappers=True``): the action sampled from the network's logits (or mean and log-std) inside
@@ -83,11 +85,15 @@ class VecImageEnv:
                  map_policy="keep", world_maps=None, episode_stats=False, episode_min_steps=3, wrappers=False,
                  ped_tracks=None, tracks_policy="keep", tracks_repeat=1, info_track_sets=False, scenarios=None, scenario_policy="queue",
                  episode_log=0, final_obs=False, rollout=0, rollout_final=None, rollout_fields=None, minibatch=0, minibatch_buffers=1,
-                 normalise=None, policy=None, rollout_draw_ped_maps=False):
+                 normalise=None, policy=None, rollout_draw_ped_maps=False, sequences=None):
         import torch
         from .world import World
         if int(minibatch or 0) > 0 and int(rollout or 0) <= 0:
             raise ValueError("minibatch=B needs rollout=T")
+        if sequences is not None and int(rollout or 0) <= 0:
+            raise ValueError("sequences=dict(length=L, batch=Bs) needs rollout=T")
+        if sequences is not None and (set(sequences) - {"length", "batch", "buffers", "state_bytes"} or not {"length", "batch"} <= set(sequences)):
+            raise ValueError("sequences: dict(length=L, batch=Bs, buffers=1, state_bytes=())")
         if rollout_draw_ped_maps and int(rollout or 0) <= 0:
             raise ValueError("rollout_draw_ped_maps=True needs rollout=T")
         if policy is not None and not wrappers:
@@ -295,6 +301,13 @@ class VecImageEnv:
         self.minibatch_batch = int(minibatch or 0)
         if self.minibatch_batch > 0:
             self.world.enable_minibatch(self.minibatch_batch, int(minibatch_buffers))
+        # sequences=dict(...): the same window cut into chunks of L steps per robot for a recurrent policy (imgenv_rollout_seq_enable):
+        # which chunks count, a fresh order over them and the gather of Bs of them into time-major tensors -- rollout_sequences().
+        # Nothing is launched by steps or resets; nothing synchronises.  Opt-in: None allocates and launches nothing.
+        self.sequences = dict(sequences) if sequences is not None else None
+        if self.sequences is not None:
+            self.world.enable_sequences(int(self.sequences["length"]), int(self.sequences["batch"]), int(self.sequences.get("buffers", 1)),
+                                        None, tuple(self.sequences.get("state_bytes", ())))
         # policy=dict(seed=s) (with wrappers=True): the hop from the network's output to the action inside the library
         # (imgenv_policy_enable) -- categorical over cfg["discrete_actions"] where discrete_action is True, a diagonal Gaussian over
         # cfg["continuous_actions"] where not.  policy_sample() draws the action from logits / mean and log_std with a counter-based
@@ -313,7 +326,10 @@ class VecImageEnv:
             # loss=True: PPO's loss of a minibatch and its gradients on the network's outputs (imgenv_policy_loss_enable), three
             # launches instead of torch's chain of small ones and its autograd -- policy_loss().  Opt-in as well.
             if self.policy.get("loss"):
-                self.world.enable_policy_loss(self.minibatch_batch)
+                rows = self.minibatch_batch  # (a sequence minibatch flattened by sequence_rows() has L Bs rows)
+                if self.sequences is not None:
+                    rows = max(rows, self.world.seq_length * self.world.seq_batch)
+                self.world.enable_policy_loss(rows)
 
     def _need_policy(self):
         if self.policy is None:
@@ -497,6 +513,53 @@ class VecImageEnv:
             for s, name in enumerate(names):
                 mb[name] = rows[s]
             yield mb
+
+    def rollout_sequences(self, scalars, seed, states=(), normalise=None, eps=1e-8):
+        """One epoch over the stored window as sequences for a recurrent policy: robot ``row``'s steps ``c * L .. c * L + L - 1`` are
+        sequence ``q = c * n_robots + row`` (chunks aligned to the window; an episode boundary inside one is marked by ``mb_first``,
+        where the network resets its state).  Indexes the sequences with at least one transition that counts, shuffles them with
+        ``seed`` and yields ``ceil(C * n_robots / Bs)`` dicts of time-major views ``[L, Bs, ...]`` -- the ``mb_*`` tensors of
+        ``World.sequences`` and every scalar under the caller's own name (float32 ``[L, Bs]``).  ``mb_weight`` is 0 for a step that
+        does not count or does not exist; ``mb_seq_state0`` / ``1`` ``[Bs, state_bytes]`` hold ``states[a]``'s row at each sequence's
+        first step (``states``: tensors ``[T or T + 1, n, ...]``, the recurrent state the rollout saw there).  ``normalise`` names a
+        scalar that comes out as ``(x - mean) / sqrt(var + eps)`` with the statistics over the valid TRANSITIONS (``minibatch=B``'s
+        ``rollout_index`` + ``rollout_stats``: ValueError without ``minibatch``).  The buffers alternate; nothing synchronises.  No step
+        or reset while the generator runs."""
+        if self.sequences is None:
+            raise RuntimeError("VecImageEnv was made without sequences=dict(length=L, batch=Bs)")
+        names = list(scalars)
+        if normalise is not None and normalise not in scalars:
+            raise ValueError("normalise: one of the scalars' names")
+        if normalise is not None and self.minibatch_batch <= 0:
+            raise ValueError("rollout_sequences: normalise needs minibatch >= 1 (the statistics over the valid transitions are the minibatches')")
+        w = self.world
+        n, _ = w.rollout_cursor()
+        norm = None
+        if normalise is not None:
+            w.rollout_index()
+            norm = w.rollout_stats(scalars[normalise], eps)
+        w.rollout_seq_index()
+        w.rollout_seq_shuffle(seed)
+        count = -(-(-(-n // w.seq_length)) * len(self) // w.seq_batch)
+        return self._sequences(names, [scalars[k] for k in names], None if normalise is None else names.index(normalise), norm, list(states), count)
+
+    def _sequences(self, names, tensors, normalise, norm, states, count):
+        w = self.world
+        for j in range(count):
+            mb = w.rollout_seq_minibatch(j, j % w.seq_buffers, tensors, normalise, norm, states)
+            rows = mb.pop("mb_scalars")
+            for s, name in enumerate(names):
+                mb[name] = rows[s]
+            yield mb
+
+    def sequence_rows(self, mb):
+        """a dict from ``rollout_sequences`` with every ``[L, Bs, ...]`` tensor as its flat ``[L * Bs, ...]`` view (row ``l * Bs + i``;
+        the per-sequence ``mb_seq``, ``mb_seq_len`` and ``mb_seq_state*`` as they are): ``policy_loss(sequence_rows(mb), ...)``"""
+        if self.sequences is None:
+            raise RuntimeError("VecImageEnv was made without sequences=dict(length=L, batch=Bs)")
+        L, Bs = self.world.seq_length, self.world.seq_batch
+        return {k: (t.reshape((L * Bs,) + tuple(t.shape[2:])) if k not in ("mb_seq", "mb_seq_len") and not k.startswith("mb_seq_state") else t)
+                for k, t in mb.items()}
 
     def episode_tensors(self):
         """the per-robot device tensors of the statistics (``World.episodes``: ``ends`` [6, n], ``episodes``, ``last_episode``,

@@ -125,6 +125,7 @@ class World:
         self.rollout = None  # enable_rollout()
         self.rollout_draws_ped_maps = False  # ... with "ped_maps_drawn"
         self.minibatch = None  # enable_minibatch()
+        self.sequences = None  # enable_sequences()
         self.normalise = None  # enable_normalise()
         if self.n_maps > 1:
             rest = self.grids[1:]
@@ -898,6 +899,115 @@ class World:
         self._call(self.lib.imgenv_rollout_minibatch(self.h, C.byref(a), self._stream()), "imgenv_rollout_minibatch")
         return {name: t[buffer] for name, t in self.minibatch.items() if name.startswith("mb_")}
 
+    def _side_by_side(self, name, ptrs, dt, shape, what):
+        """one ``[len(ptrs)] + shape`` view over an array's buffers: buffer b starts (size rounded up to 256 bytes) behind buffer b - 1"""
+        import torch
+        NB, item = len(ptrs), np.dtype(dt).itemsize
+        nbytes = int(np.prod(shape)) * item
+        pitch = (nbytes + 255) // 256 * 256
+        if any(ptrs[b] != ptrs[0] + b * pitch for b in range(NB)):
+            raise RuntimeError("%s.%s: the buffers do not lie side by side" % (what, name))
+        first = types.SimpleNamespace(**{name: ptrs[0]})
+        span = self._views(first, {name: (dt, ((NB - 1) * pitch // item + nbytes // item,))}, what)[name]
+        strides, acc = [], 1
+        for d in reversed(shape):
+            strides.insert(0, acc)
+            acc *= d
+        return torch.as_strided(span, (NB,) + tuple(shape), (pitch // item,) + tuple(strides))
+
+    def enable_sequences(self, length, batch, buffers=1, fields=None, state_bytes=()):
+        """Sequence minibatches for recurrent policies out of the rollout storage (``imgenv_rollout_seq_enable``; needs
+        ``enable_rollout`` first, not ``enable_minibatch``): the window cut into chunks of ``length`` steps per row, sequence ``q = c *
+        R + row``.  ``self.sequences`` -- zero-copy tensors over the library's memory, TIME-MAJOR: ``mb_<field>`` ``[buffers, L, Bs,
+        ...]`` with the row shapes and dtypes of ``rollout["obs_<field>"]``, ``mb_actions`` float32 ``[buffers, L, Bs, 3]``,
+        ``mb_rewards`` / ``mb_weight`` float32, ``mb_dones`` / ``mb_first`` uint8, ``mb_dones_info`` / ``mb_index`` int32 ``[buffers, L,
+        Bs]``, ``mb_scalars`` float32 ``[buffers, 6, L, Bs]``, ``mb_seq`` / ``mb_seq_len`` int32 ``[buffers, Bs]``, ``mb_seq_state0`` /
+        ``mb_seq_state1`` uint8 ``[buffers, Bs, state_bytes[a]]`` (``.view(dtype)`` them), and ``seq_flag`` uint8, ``seq_valid`` /
+        ``seq_order`` int32 ``[C_max * R]``, ``seq_valid_n`` int32 ``[1]``.  ``mb_first``: a reset rewrote that step's observation, the
+        row's episode starts there (it does not say whether slot 0 continues the previous window).  ``fields`` as ``enable_minibatch``
+        takes them; ``state_bytes``: the row sizes of up to 2 state arrays (LSTM h and c), multiples of 4.  Nothing is launched;
+        read-only; valid until ``close()``.  ValueError for a refused cfg or a second call with another one, RuntimeError before
+        ``enable_rollout``."""
+        c = _cabi.make_seq_cfg(length, batch, buffers, fields, state_bytes)
+        so = _cabi.SeqOut()
+        self._call(self.lib.imgenv_rollout_seq_enable(self.h, C.byref(c), C.byref(so)), "imgenv_rollout_seq_enable")
+        if self.sequences is None:
+            L, Bs, NB, S = so.length, so.batch, so.buffers, so.max_sequences
+            views = self._views(so, {"seq_flag": (np.uint8, (S,)), "seq_valid": (np.int32, (S,)), "seq_order": (np.int32, (S,)),
+                                     "seq_valid_n": (np.int32, (1,))}, "imgenv_seq_out")  # (seq_valid_n: uint32 in the library)
+            rows = {"mb_" + name: (self._rollout_rows[name][0], (L, Bs) + tuple(self._rollout_rows[name][1][1:]))
+                    for name in _cabi.ROLLOUT_FIELDS + _cabi.ROLLOUT_NORM_FIELDS if getattr(so.buf[0], "mb_" + name)}
+            rows.update(mb_actions=(np.float32, (L, Bs, 3)), mb_rewards=(np.float32, (L, Bs)), mb_dones=(np.uint8, (L, Bs)),
+                        mb_dones_info=(np.int32, (L, Bs)), mb_index=(np.int32, (L, Bs)), mb_weight=(np.float32, (L, Bs)),
+                        mb_first=(np.uint8, (L, Bs)), mb_scalars=(np.float32, (_cabi.MB_MAX_SCALARS, L, Bs)), mb_seq=(np.int32, (Bs,)),
+                        mb_seq_len=(np.int32, (Bs,)))
+            for name, (dt, shape) in rows.items():
+                views[name] = self._side_by_side(name, [getattr(so.buf[b], name) for b in range(NB)], dt, shape, "imgenv_seq_buffer")
+            for a in range(_cabi.SEQ_MAX_STATES):
+                if so.state_bytes[a] > 0:
+                    views["mb_seq_state%d" % a] = self._side_by_side("mb_seq_state%d" % a, [so.buf[b].mb_seq_state[a] for b in range(NB)], np.uint8,
+                                                                     (Bs, so.state_bytes[a]), "imgenv_seq_buffer")
+            self.sequences = views
+            self.seq_length, self.seq_batch, self.seq_buffers, self.seq_state_bytes = L, Bs, NB, tuple(so.state_bytes)
+        return self.sequences
+
+    def _need_sequences(self):
+        if self.sequences is None:
+            raise RuntimeError("enable_sequences() was not called")
+
+    def rollout_seq_index(self):
+        """``imgenv_rollout_seq_index``: ``sequences["seq_flag"][q]`` = 1 where any transition sequence ``q`` covers has ``is_clean !=
+        0``, ``seq_valid`` the ascending list of those, ``seq_valid_n`` their count; four launches on the current stream, nothing
+        synchronises.  A later step, reset or ``rollout_begin()`` makes the index stale: ``rollout_seq_shuffle`` / ``_seq_minibatch``
+        then raise RuntimeError."""
+        self._need_sequences()
+        self._check(self.lib.imgenv_rollout_seq_index(self.h, self._stream()), "imgenv_rollout_seq_index")
+
+    def rollout_seq_count(self):
+        """``seq_valid_n`` as a Python int.  SYNCHRONISES: it waits for the stream and reads one word from the device."""
+        self._need_sequences()
+        return int(self.sequences["seq_valid_n"].item())
+
+    def rollout_seq_shuffle(self, seed):
+        """``imgenv_rollout_seq_shuffle``: ``sequences["seq_order"]`` = the valid sequences in a fresh order drawn from the 64-bit
+        ``seed`` (``rollout_shuffle``'s bijection over ``seq_valid_n``), -1 behind; one launch"""
+        self._need_sequences()
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._check(self.lib.imgenv_rollout_seq_shuffle(self.h, seed & 0xFFFFFFFF, seed >> 32, self._stream()), "imgenv_rollout_seq_shuffle")
+
+    def rollout_seq_minibatch(self, j, buffer=0, scalars=(), normalise=None, norm=None, states=()):
+        """``imgenv_rollout_seq_minibatch``: sequence minibatch ``j`` of the current order into buffer ``buffer``, one launch (two
+        where the rollout draws its ``ped_maps``).  ``scalars``: up to 6 float32 tensors ``[T, R]`` or ``[T + 1, R]``, gathered into
+        ``sequences["mb_scalars"][buffer, s]`` ``[L, Bs]``; ``normalise``: an index into them whose values become ``(x - norm[0]) *
+        norm[1]`` with ``norm`` float32 ``[2]`` (required then).  ``states``: one contiguous tensor ``[T or T + 1, R, ...]`` per
+        ``state_bytes`` entry of ``enable_sequences``, rows of exactly that many bytes, 16-byte aligned: ``mb_seq_state<a>[buffer,
+        i]`` is its row at the first step of slot ``i``'s sequence.  Steps that do not exist and slots behind the valid list are
+        zeros with ``mb_index`` -1 and ``mb_weight`` 0.  Returns the dict of buffer ``buffer``'s views."""
+        import torch
+        self._need_sequences()
+        T, R = self.rollout_horizon, self.n_local
+        scalars, states = list(scalars), list(states)
+        if len(scalars) > _cabi.MB_MAX_SCALARS:
+            raise ValueError("rollout_seq_minibatch: at most %d scalars" % _cabi.MB_MAX_SCALARS)
+        ptrs = [self._mb_tensor(t, "rollout_seq_minibatch: scalars[%d]" % s, [(T, R), (T + 1, R)]).value for s, t in enumerate(scalars)]
+        np_ = self._mb_tensor(norm, "rollout_seq_minibatch: norm", [(2,)]).value if norm is not None else None
+        if normalise is not None and norm is None:
+            raise ValueError("rollout_seq_minibatch: normalise needs norm, float32 [2]")
+        want = [nb for nb in self.seq_state_bytes if nb > 0]
+        if len(states) != len(want):
+            raise ValueError("rollout_seq_minibatch: %d state arrays (enable_sequences was given %d)" % (len(states), len(want)))
+        sp = [None] * _cabi.SEQ_MAX_STATES
+        slots = [a for a, nb in enumerate(self.seq_state_bytes) if nb > 0]
+        for a, t in zip(slots, states):
+            nb = self.seq_state_bytes[a]
+            if not (isinstance(t, torch.Tensor) and t.device == self.device and t.is_contiguous() and t.dim() >= 2 and t.shape[0] in (T, T + 1)
+                    and t.shape[1] == R and t[0, 0].numel() * t.element_size() == nb):
+                raise ValueError("rollout_seq_minibatch: states[%d]: [%d or %d, %d, ...] with rows of %d bytes, contiguous on %s" % (a, T, T + 1, R, nb, self.device))
+            sp[a] = t.data_ptr()
+        a = _cabi.make_seq_args(j, buffer, ptrs, -1 if normalise is None else normalise, np_, sp)
+        self._call(self.lib.imgenv_rollout_seq_minibatch(self.h, C.byref(a), self._stream()), "imgenv_rollout_seq_minibatch")
+        return {name: t[buffer] for name, t in self.sequences.items() if name.startswith("mb_")}
+
     def reset(self, layout):
         """Reset everything. A handle of several worlds (``n_worlds`` > 1) takes either one batch of all robots and
         pedestrians (world-major) with an obstacle list shared by every world, or a list of one layout per world."""
@@ -1087,7 +1197,7 @@ class World:
     def close(self):
         if getattr(self, "h", None):
             self.episodes = self.episode_log = self.action_outputs = self.obs_post = self.final_obs = self.rollout = self.minibatch = None  # (views of memory the handle owns)
-            self.normalise = self.policy = self.policy_loss_out = None
+            self.normalise = self.policy = self.policy_loss_out = self.sequences = None
             self.lib.imgenv_destroy(self.h)
             self.h = None
 

@@ -1309,6 +1309,127 @@ int imgenv_normalise_training(imgenv_t* h, int32_t on, void* stream);
 int imgenv_normalise_stats_get(imgenv_t* h, imgenv_normalise_stats* stats);
 int imgenv_normalise_stats_set(imgenv_t* h, const imgenv_normalise_stats* stats);
 
+/* ---- sequence minibatches: the window cut into chunks of L steps per row, for recurrent policies ----
+ * imgenv_rollout_shuffle permutes single transitions; an LSTM or GRU policy needs each row's steps in order.  Here the window is
+ * cut into sequences (csrc/sequences.h): with R local rows, horizon T, cursor n and a chunk length 1 <= L <= T there are
+ * C = ceil(n / L) chunks per row (C_max = ceil(T / L)), and sequence q = c R + row, 0 <= q < C R, covers row `row`'s transitions
+ * t = c L .. min(c L + L, n) - 1.  Chunks are aligned to the WINDOW, not to episodes: an episode boundary inside a chunk is marked
+ * (mb_first), not split -- the env-major convention, the network resets its state where mb_first is set.  Needs
+ * imgenv_rollout_enable(); does NOT need imgenv_rollout_minibatch_enable().
+ *
+ * All arrays are the library's, one all-or-nothing allocation, each on a 256-byte boundary:
+ *   seq_flag     u8  [C_max R]  imgenv_rollout_seq_index: 1 iff any covered transition has is_clean != 0
+ *   seq_valid    i32 [C_max R]  the q with seq_flag set, ascending;  seq_valid_n u32  their count Vs
+ *   seq_order    i32 [C_max R]  imgenv_rollout_seq_shuffle: seq_order[p] = seq_valid[pi(p)] for p < Vs, -1 from Vs on
+ *   tile_count, tile_base i32 [ceil(C_max R / 4096)]   the index's scratch
+ *   per buffer (imgenv_seq_buffer), Bs = batch, TIME-MAJOR: x[l] is the contiguous batch a recurrent network consumes at step l
+ *   mb_<field>   [L][Bs][row]   the selected fields' rows, shapes and types as obs_<field>
+ *   mb_actions f32 [L][Bs][3], mb_rewards f32, mb_dones u8, mb_dones_info i32 [L][Bs]   the ring's scalars of transition k
+ *   mb_index     i32 [L][Bs]    k = t R + row, -1 for a step that does not exist
+ *   mb_weight    f32 [L][Bs]    is_clean[k] != 0 ? 1 : 0; 0 for a step that does not exist
+ *   mb_first     u8  [L][Bs]    final_idx[t][row] >= 0: a reset chain rewrote slot t's observation, the row's episode STARTS at
+ *                               this step (the device-side reset, the host-side ones, a caller's reset in mid-episode or at n = 0).
+ *                               It does NOT say whether slot 0 continues the previous window: imgenv_rollout_begin clears final_idx,
+ *                               and the caller's stored initial state (mb_seq_state) carries that.
+ *   mb_scalars   f32 [IMGENV_MB_MAX_SCALARS][L][Bs]   the caller's arrays at k
+ *   mb_seq       i32 [Bs]       q, or -1 for a slot behind the valid list
+ *   mb_seq_len   i32 [Bs]       the steps of the slot with k >= 0
+ *   mb_seq_state[a] u8 [Bs][state_bytes[a]]   the caller's row at the sequence's FIRST step, k0 = c L R + row; zeros where q = -1
+ * The index has a generation exactly as imgenv_rollout_index's: a later chain or imgenv_rollout_begin makes it stale, and
+ * imgenv_rollout_seq_shuffle / _seq_minibatch then fail with IMGENV_ESTATE ("rollout changed since imgenv_rollout_seq_index")
+ * before they queue anything. */
+#define IMGENV_SEQ_MAX_STATES 2
+typedef struct imgenv_seq_cfg {
+    int32_t struct_size;          /* sizeof(imgenv_seq_cfg) */
+    int32_t length;               /* L: 1 .. the rollout's horizon */
+    int32_t batch;                /* Bs >= 1 sequences per minibatch */
+    int32_t buffers;              /* 1 .. IMGENV_MB_MAX_BUFFERS */
+    int32_t fields;               /* IMGENV_ROLLOUT_* bits, a subset of the rollout's; 0: all of them */
+    int32_t state_bytes[IMGENV_SEQ_MAX_STATES];  /* the row of caller array a: a multiple of 4, at most 65536; 0: none */
+    int32_t reserved;             /* 0 */
+} imgenv_seq_cfg;
+typedef struct imgenv_seq_buffer {
+    /* [L][Bs][row]; NULL where not selected */
+    uint16_t* mb_sensor_maps;
+    float* mb_vector_states;
+    double* mb_lasers;
+    float* mb_ped_vector_states;
+    float* mb_ped_maps;
+    float* mb_ped_vector_norm;
+    uint16_t* mb_stack_sensor_maps;
+    float* mb_stack_vector_states;
+    double* mb_stack_lasers;
+    float* mb_norm_vector_states;  /* IMGENV_ROLLOUT_NORM_STATES: here, not in imgenv_normalise_out */
+    float* mb_norm_state_stack;
+    float* mb_actions;
+    float* mb_rewards;
+    uint8_t* mb_dones;
+    int32_t* mb_dones_info;
+    int32_t* mb_index;
+    float* mb_weight;
+    uint8_t* mb_first;
+    float* mb_scalars;
+    int32_t* mb_seq;
+    int32_t* mb_seq_len;
+    uint8_t* mb_seq_state[IMGENV_SEQ_MAX_STATES];
+} imgenv_seq_buffer;
+typedef struct imgenv_seq_out {
+    int32_t struct_size;          /* on entry 0 or sizeof(imgenv_seq_out) */
+    int32_t n_local;              /* R */
+    int32_t horizon;              /* T */
+    int32_t length;               /* L */
+    int32_t batch;                /* Bs */
+    int32_t buffers;
+    int32_t fields;               /* the bits in effect */
+    int32_t max_sequences;        /* C_max R */
+    int32_t state_bytes[IMGENV_SEQ_MAX_STATES];
+    uint8_t* seq_flag;
+    int32_t* seq_valid;
+    int32_t* seq_order;
+    uint32_t* seq_valid_n;
+    int32_t* tile_count;
+    int32_t* tile_base;
+    imgenv_seq_buffer buf[IMGENV_MB_MAX_BUFFERS];  /* buf[b] all NULL for b >= buffers */
+} imgenv_seq_out;
+/* Legal once imgenv_rollout_enable() has been called (IMGENV_ESTATE before).  IMGENV_EINVAL for a wrong struct_size, length outside
+ * 1 .. T, batch < 1, buffers outside 1 .. 4, unknown bits, a bit the rollout does not store, a state_bytes that is negative, no
+ * multiple of 4 or above 65536, C_max R >= 2^31, or a second call whose cfg differs from the first's (same cfg: `out` is filled
+ * again, nothing changes).  IMGENV_ENOMEM when the arrays cannot be allocated; the handle is then unchanged.  `out` may be NULL.
+ * Nothing is launched, and no chain of the handle changes. */
+int imgenv_rollout_seq_enable(imgenv_t* h, const imgenv_seq_cfg* cfg, imgenv_seq_out* out);
+/* IMGENV_ESTATE before imgenv_rollout_seq_enable() */
+int imgenv_rollout_seq_outputs(imgenv_t* h, imgenv_seq_out* out);
+/* seq_flag, then seq_valid / seq_valid_n by imgenv_rollout_index's stable compaction over the flags: four launches, no workgroup
+ * waits for another.  Records the generation.  IMGENV_ESTATE before imgenv_rollout_seq_enable(), before imgenv_rollout_begin() or
+ * with n == 0. */
+int imgenv_rollout_seq_index(imgenv_t* h, void* stream);
+/* seq_order[p] = seq_valid[pi(p)] for p < seq_valid_n (read on the device), -1 for seq_valid_n <= p < C_max R; one launch; pi and
+ * its keys are imgenv_rollout_shuffle's, over Vs.  IMGENV_ESTATE for a stale or missing index. */
+int imgenv_rollout_seq_shuffle(imgenv_t* h, uint32_t seed_lo, uint32_t seed_hi, void* stream);
+typedef struct imgenv_seq_args {
+    int32_t struct_size;          /* sizeof(imgenv_seq_args) */
+    int32_t j;                    /* minibatch number >= 0: the slots take seq_order[j Bs .. j Bs + Bs - 1] */
+    int32_t buffer;               /* 0 .. buffers - 1 */
+    int32_t n_scalars;            /* 0 .. IMGENV_MB_MAX_SCALARS */
+    int32_t normalise;            /* an index into scalars, or -1 */
+    int32_t reserved;             /* 0 */
+    const float* scalars[IMGENV_MB_MAX_SCALARS];  /* DEVICE f32 arrays indexed by k, row stride R: [T][R] or [T+1][R] */
+    const float* norm;            /* DEVICE f32 [2] for `normalise`, the caller's; may be NULL only where normalise is -1 */
+    const void* states[IMGENV_SEQ_MAX_STATES];  /* DEVICE [T or T+1][R][state_bytes[a]], 16-byte aligned; unused where state_bytes[a] is 0 */
+} imgenv_seq_args;
+/* Minibatch j into buffer `buffer`, one launch (k_rollout_seq_gather); under IMGENV_ROLLOUT_PED_MAPS_DRAWN a second one, k_ped_draw
+ * with the buffer's own mb_index as its rows.  Slot i < Bs takes q = seq_order[j Bs + i], -1 from C_max R on; step l < L of it is
+ * t = c L + l, k = t R + row where q >= 0 and t < n, else k = -1.
+ *   k >= 0: mb_<field>[l][i] = obs_<field>[k], the ring's actions / rewards / dones / dones_info of k, mb_index = k, mb_weight =
+ *           is_clean[k] != 0, mb_first = final_idx[t][row] >= 0, mb_scalars[s][l][i] = scalars[s][k], for s == normalise
+ *           (x - norm[0]) * norm[1] in float32 (two roundings);
+ *   k <  0: every byte of the step's rows 0, mb_index = -1, mb_weight, mb_first and every scalar 0.
+ * The buffer is fully defined after every gather but for the rows of mb_scalars from n_scalars on.  IMGENV_EINVAL for a wrong
+ * struct_size, j < 0, a buffer, n_scalars or normalise out of range, a null scalars[s], a null norm with normalise >= 0, a null or
+ * misaligned states[a] where state_bytes[a] > 0; IMGENV_ESTATE for a stale or missing index or before
+ * imgenv_rollout_seq_shuffle() on this index. */
+int imgenv_rollout_seq_minibatch(imgenv_t* h, const imgenv_seq_args* args, void* stream);
+
 /* ---- map bank: several static maps in one handle, one of them per world and episode ----
  * The reference trains one policy over a set of maps: its trainer is started from several YAML files side by side
  * (create_launch.py:57-65, one node per (env_name, env_num) pair), each env process loads its own global_map.map_file

@@ -34,6 +34,11 @@ two ways, one process per measurement, alternating over several rounds: the libr
 imgenv_rollout_index + _stats + _shuffle and one gather launch per minibatch, no host read) and the same tensors from torch ops on
 the library's ring (nonzero on is_clean, masked mean / std, randperm, one index_select per field and scalar).
 
+--sequences-compare times one epoch of SEQUENCE minibatches (--seq-length steps x --seq-batch sequences, time-major, two 512-byte
+state arrays) over the same window the same two ways: the library's (VecImageEnv(sequences=dict(...)): imgenv_rollout_seq_index +
+_seq_shuffle and one gather launch per minibatch) and torch ops on the library's ring (chunk flags by reshape / any, nonzero,
+randperm, one index_select per field and scalar).
+
 --ped-draw-compare runs device_reset steps with rollout=--horizon and the default fields two ways, one process per measurement,
 alternating over several rounds: ped_maps stored in the ring / drawn at gather time from the stored pedestrian vectors
 (rollout_draw_ped_maps=True; --parent-tree adds the stored path of another checkout); per variant the time per step, the device time
@@ -1000,6 +1005,111 @@ def compare_minibatch(args, rounds=3):
                 batch=args.batch, rounds=rounds, runs=runs, summary=summary)
 
 
+def measure_sequences(variant, envs=1024, robots=4, peds=3, obstacles=2, time_max=100, horizon=32, length=16, batch=256, epochs=5):
+    """us per epoch's worth of SEQUENCE minibatches (``length`` steps x ``batch`` sequences, time-major) over a full window of
+    ``horizon`` device_reset steps, all five single-frame fields, four caller scalars and two 512-byte state arrays:
+    "library": ``VecImageEnv.rollout_sequences`` (index + shuffle + one gather per minibatch, no host read);
+    "torch": the same time-major tensors from torch ops on the library's ring -- chunk flags by ``reshape`` / ``any``, ``nonzero`` (a
+    host synchronisation), ``randperm``, one ``index_select`` per field and scalar and minibatch"""
+    import torch
+    from img_env_amd import worldgen
+    from img_env_amd.vec_env import VecImageEnv
+    grid = worldgen.make_grid(200, 2)
+    cfg = worldgen.make_yaml_cfg(robots, peds, grid, time_max=time_max, n_obstacles=obstacles, seed=5)
+    T, n, L, Bs = horizon, envs * robots, length, batch
+    if T % L:
+        raise ValueError("--horizon must be a multiple of --seq-length here (the torch route reshapes the window)")
+    env = VecImageEnv(cfg, env_num=envs, seed=5, device_reset=True, rollout=T, rollout_final=n,
+                      sequences=dict(length=L, batch=Bs, buffers=2, state_bytes=(512, 512)) if variant == "library" else None)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    acts = torch.zeros(16, n, 3, device="cuda")
+    acts[:, :, 0] = torch.rand(16, n, generator=g, device="cuda") * 0.6
+    acts[:, :, 1] = torch.rand(16, n, generator=g, device="cuda") * 1.8 - 0.9
+    env.reset()
+    windows = max(1, -(-(time_max + 20) // T))  # past the first wave of time limits, ending on a full window
+    for s in range(windows * T):
+        if s and s % T == 0:
+            env.rollout_begin()
+        env.step(acts[s % 16])
+    values = torch.randn(T + 1, n, generator=g, device="cuda")
+    adv, ret = env.rollout_advantages(values, None, 0.99, 0.95)
+    logp = torch.randn(T, n, generator=g, device="cuda")
+    states = [torch.randn(T + 1, n, 128, generator=g, device="cuda") for _ in range(2)]
+    r = env.rollout()
+    fields = [k[4:] for k in r if k.startswith("obs_")]
+    C = T // L
+    steps = torch.arange(L, device="cuda")
+
+    def library(seed):
+        count = 0
+        for mb in env.rollout_sequences({"adv": adv, "ret": ret, "values": values, "logp": logp}, seed, states=states):
+            count += 1
+        return count
+
+    def torch_epoch(seed):
+        flags = (r["is_clean"][:T].reshape(C, L, n) != 0).any(dim=1).reshape(-1)
+        valid = torch.nonzero(flags).flatten()  # (the host waits here: the size of the result)
+        order = valid[torch.randperm(valid.numel(), device="cuda", generator=g)]
+        flat = {k: r["obs_" + k].flatten(0, 1) for k in fields}
+        ring = {k: r[k].flatten(0, 1) for k in ("actions", "rewards", "dones", "dones_info", "is_clean")}
+        mine = {"adv": adv.reshape(-1), "ret": ret.reshape(-1), "values": values.reshape(-1), "logp": logp.reshape(-1)}
+        first = r["final_idx"].reshape(-1)
+        count = 0
+        for j in range(-(-C * n // Bs)):
+            q = order[j * Bs:(j + 1) * Bs]
+            k0 = (q // n) * (L * n) + q % n
+            idx = (k0[None, :] + steps[:, None] * n).reshape(-1)  # time-major [L, Bs]
+            mb = {k: v.index_select(0, idx) for k, v in flat.items()}
+            mb.update({k: v.index_select(0, idx) for k, v in ring.items()})
+            mb.update({k: v.index_select(0, idx) for k, v in mine.items()})
+            mb["mb_first"] = first.index_select(0, idx) >= 0
+            mb["state0"], mb["state1"] = (s.flatten(0, 1).index_select(0, k0) for s in states)
+            count += 1
+        return count
+    fn = library if variant == "library" else torch_epoch
+    fn(0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for e in range(epochs):
+        count = fn(e + 1)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    flags = (r["is_clean"][:T].reshape(C, L, n) != 0).any(dim=1)
+    row_bytes = sum(r["obs_" + k][0, 0].numel() * r["obs_" + k].element_size() for k in fields)
+    env.close()
+    return dict(us_per_epoch=1e6 * dt / epochs, minibatches=count, length=L, batch=Bs, horizon=T, rows=n, sequences=C * n, valid=int(flags.sum().item()),
+                row_bytes=row_bytes, fields=fields)
+
+
+def compare_sequences(args, rounds=3):
+    """library / torch, alternating, `rounds` times; one process per measurement, each under its own time limit"""
+    import subprocess
+    base = [sys.executable, os.path.abspath(__file__), "--envs", str(args.envs), "--robots", str(args.robots), "--peds", str(args.peds),
+            "--obstacles", str(args.obstacles), "--time-max", str(args.time_max), "--horizon", str(args.horizon), "--seq-length", str(args.seq_length),
+            "--seq-batch", str(args.seq_batch)]
+    variants, runs = ("library", "torch"), []
+    for rnd in range(rounds):
+        for variant in variants:
+            out = subprocess.run(base + ["--sequences-variant", variant], capture_output=True, text=True, timeout=300)
+            if out.returncode != 0:
+                raise RuntimeError("%s: exit %d\n%s" % (variant, out.returncode, out.stderr[-2000:]))
+            runs.append(dict(round=rnd, variant=variant, **json.loads(out.stdout.strip().splitlines()[-1])))
+            print(json.dumps(runs[-1]), flush=True)
+    summary = {}
+    for variant in variants:
+        v = [x["us_per_epoch"] for x in runs if x["variant"] == variant]
+        summary[variant] = dict(us_per_epoch_rounds=v, median=sorted(v)[len(v) // 2], spread=max(v) - min(v))
+    summary["torch_minus_library_us"] = summary["torch"]["median"] - summary["library"]["median"]
+    lib = [x for x in runs if x["variant"] == "library"][0]
+    # the gathers' algorithmic bytes (read + written) per second of the library's whole epoch -- index and shuffle included
+    per_step = lib["row_bytes"] + 12 + 4 + 1 + 4 + 1 + 4 + 4 * 4
+    moved = 2 * lib["minibatches"] * (lib["length"] * lib["batch"] * per_step + lib["batch"] * 1024)
+    summary["library_gather_bytes_per_epoch"] = moved
+    summary["library_tb_per_s"] = moved / (summary["library"]["median"] * 1e-6) / 1e12
+    return dict(envs=args.envs, robots_per_env=args.robots, peds_per_env=args.peds, time_max=args.time_max, horizon=args.horizon,
+                length=args.seq_length, batch=args.seq_batch, rounds=rounds, runs=runs, summary=summary)
+
+
 def measure_ped_draw(variant, envs=1024, robots=4, peds=3, obstacles=2, steps=300, time_max=100, horizon=32, batch=4096):
     """One process of --ped-draw-compare: device_reset steps with ``rollout=horizon`` and the default fields, ``ped_maps`` stored
     ("stored"; also what "parent" runs, from another checkout) or drawn at gather time ("drawn": ``rollout_draw_ped_maps=True``).
@@ -1261,6 +1371,11 @@ def main():
                          "from torch ops, alternating over --rounds rounds; one process per measurement")
     ap.add_argument("--minibatch-variant", default=None, choices=("library", "torch"), help="one measurement of --minibatch-compare")
     ap.add_argument("--batch", type=int, default=4096, help="--minibatch-compare: transitions per minibatch")
+    ap.add_argument("--sequences-compare", action="store_true",
+                    help="one epoch of sequence minibatches over a full window: the library against torch ops on its ring, alternating rounds")
+    ap.add_argument("--sequences-variant", default=None, choices=("library", "torch"), help="one measurement of --sequences-compare")
+    ap.add_argument("--seq-length", type=int, default=16, help="--sequences-compare: steps per sequence")
+    ap.add_argument("--seq-batch", type=int, default=256, help="--sequences-compare: sequences per minibatch")
     ap.add_argument("--ped-draw-compare", action="store_true",
                     help="rollout=--horizon with ped_maps stored / drawn at gather time (/ the parent's, --parent-tree): us per step, per minibatch, k_ped_draw alone")
     ap.add_argument("--ped-draw-variant", default=None, choices=("stored", "drawn"), help="one measurement of --ped-draw-compare")
@@ -1277,6 +1392,17 @@ def main():
     if args.minibatch_variant:
         print(json.dumps(measure_minibatch(args.minibatch_variant, args.envs, args.robots, args.peds, args.obstacles, args.time_max, args.horizon,
                                            args.batch)))
+        return
+    if args.sequences_variant:
+        print(json.dumps(measure_sequences(args.sequences_variant, args.envs, args.robots, args.peds, args.obstacles, args.time_max, args.horizon,
+                                           args.seq_length, args.seq_batch)))
+        return
+    if args.sequences_compare:
+        res = compare_sequences(args, args.rounds)
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["summary"]))
         return
     if args.ped_draw_variant:
         print(json.dumps(measure_ped_draw(args.ped_draw_variant, args.envs, args.robots, args.peds, args.obstacles, args.steps, args.time_max,

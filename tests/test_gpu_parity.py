@@ -330,7 +330,7 @@ def test_two_sharded_handles_match_single_world(worlds, by_x, layer):
     other rank's robots arrive as bitmaps in their records, k_remote) and with the composed owner layers (each rank rasterises
     the other's robots itself, clipped to what its own robots can see: spatially separated shards)."""
     from img_env_amd import _cabi
-    World, _ = worlds
+    World, OracleWorld = worlds
     n, n_peds, steps = 24, 10, 30
     grid, params, layout = small_world(n, n_peds, seed=31, grid_size=320, clearance=0.8)
     if layer == "composed":
@@ -339,19 +339,21 @@ def test_two_sharded_handles_match_single_world(worlds, by_x, layer):
         order = np.argsort(layout.robot_pose[:, 0], kind="stable")
         layout.robot_pose = layout.robot_pose[order].copy()
         layout.robot_goal = layout.robot_goal[order].copy()
-    full = World(params, grid)
+    full, cpu = World(params, grid), OracleWorld(params, grid)
     ranks = [World(dict(params, robot_begin=r * n // 2, robot_end=(r + 1) * n // 2), grid) for r in range(2)]
     try:
         for w in ranks:
             mode = w.layer_mode()
             assert mode["layer"] == layer and mode["shard_bitmaps"] == (layer == "counting") and mode["early_observation"], mode
         full.reset(layout)
+        cpu.reset(layout)
         for w in ranks:
             w.reset(layout)
         rng = np.random.default_rng(5)
         for s in range(steps):
             a = random_actions(rng, n)
             full.step(a)
+            cpu.step(a)
             for r, w in enumerate(ranks):
                 w.step_begin(a[r * n // 2:(r + 1) * n // 2])
             _exchange_by_hand(ranks, [0, n // 2, n])
@@ -363,8 +365,12 @@ def test_two_sharded_handles_match_single_world(worlds, by_x, layer):
                 sl = slice(r * n // 2, (r + 1) * n // 2)
                 for k in SHARD_FIELDS:
                     assert np.array_equal(got[k], want[k][sl]), (s, r, k)
+        # ... and the whole-world handle the shards were held to is itself the oracle's world at the episode's end
+        bad = compare(full.snapshot(), cpu.snapshot())
+        assert not bad, ("whole world against the oracle", bad)
     finally:
         full.close()
+        cpu.close()
         for w in ranks:
             w.close()
 
@@ -377,7 +383,7 @@ def test_four_shards_through_a_reset_match_single_world(worlds, case):
     `no_pedestrians`: no side streams at all; `fine_grid_falls_back`: 0.05 m cells, where a footprint's box no longer fits the
     record's 64-bit bitmap and the shards keep the composed owner layers."""
     from img_env_amd import worldgen
-    World, _ = worlds
+    World, OracleWorld = worlds
     n, n_peds, nr = 256, (0 if case == "no_pedestrians" else 12), 4
     res = 0.05 if case == "fine_grid_falls_back" else 0.125
     size = 400 if case == "fine_grid_falls_back" else 168
@@ -388,7 +394,7 @@ def test_four_shards_through_a_reset_match_single_world(worlds, case):
     if case == "mixed_classes":
         _mixed(params, n)
     layouts = [worldgen.make_layout(grid, res, n, n_peds, seed=41 + q, n_obstacles=2, clearance=0.6 if case == "mixed_classes" else 0.45) for q in range(2)]
-    full = World(params, grid)
+    full, cpu = World(params, grid), OracleWorld(params, grid)
     bounds = [q * n // nr for q in range(nr + 1)]
     ranks = [World(dict(params, robot_begin=bounds[r], robot_end=bounds[r + 1]), grid) for r in range(nr)]
     try:
@@ -399,12 +405,14 @@ def test_four_shards_through_a_reset_match_single_world(worlds, case):
         collided = 0
         for episode, steps in enumerate((25, 15)):
             full.reset(layouts[episode])
+            cpu.reset(layouts[episode])
             for w in ranks:
                 w.reset(layouts[episode])
             for s in range(-1, steps):
                 if s >= 0:
                     a = random_actions(rng, n)
                     full.step(a)
+                    cpu.step(a)
                     for r, w in enumerate(ranks):
                         w.step_begin(a[bounds[r]:bounds[r + 1]])
                     _exchange_by_hand(ranks, bounds)
@@ -418,9 +426,13 @@ def test_four_shards_through_a_reset_match_single_world(worlds, case):
                             continue
                         assert np.array_equal(got[k], want[k][bounds[r]:bounds[r + 1]]), (case, episode, s, r, k)
             collided += int((want["is_collisions"] == 3).sum())
+            # the whole-world handle the shards were held to is itself the oracle's world at the episode's end
+            bad = compare(want, cpu.snapshot())
+            assert not bad, (case, episode, "whole world against the oracle", bad)
         assert collided > 0, "no robot ever ran into another one: the case does not exercise the inter-robot layer"
     finally:
         full.close()
+        cpu.close()
         for w in ranks:
             w.close()
 
